@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- OmChat hot path on MI355X: ViT tiles -> projector -> splice -> prefill -> greedy decode.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--gen G] [--workload both|configs1|configs2|configs3|configs4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--gen G] [--workload both|configs1|configs2|configs3|configs4] [--full]
+                    [--dump-outputs DIR]
     python bench.py --shard-of 8 [...]            # ONE rank of a TP = 8 group on one GPU, exchanges removed (kernel time per rank)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -14,21 +15,24 @@ Workloads (BASELINE.json `configs`):
   configs1  one sample = one 448x448 picture => 3 anyres tiles (mm_utils.py:28-37,151) + 512 text ids => S = 3584 prefill
             tokens, then G greedy tokens, batch 1.  `value` = generated tokens / s over whole steps (prefill included).
   configs2  32 such samples per step: 96 tiles through the ViT, right-padded batch prefill of 32 x 3584 rows, G batched
-            decode steps.  Reported under "configs2" (tokens / s, samples / s, HBM fraction of the decode steps); it is `value`
-            only with --workload configs2.
+            decode steps.  Reported under "configs2" by the default workload with --full (tokens / s, samples / s, HBM fraction of
+            the decode steps); it is `value` only with --workload configs2.
   configs3  OmChat-2.1-8B (InternViT-300M + Qwen2-7B): one sample = 8 pictures of 448x448, each through the dynamic tiling of
             mm_utils.py:276-323 (device front end, bit-exact) -> 8 tiles in ONE batched tower pass, prefill of 8 x 1024 + 512 = 8704
-            positions, G greedy tokens.  Side block "configs3" of the default run (own context); `value` with --workload configs3.
+            positions, G greedy tokens.  Side block "configs3" of the default workload with --full (own context); `value` with --workload configs3.
   configs4  one 32-frame clip: 32 tiles through the ViT, prefill of 32 x 1024 + 512 = 33 280 positions (>= 16 k visual + text
             tokens), greedy tokens with the fp8 modes on: e4m3 decode weights, e4m3 KV cache, fp8 x fp8 MFMA for the qkv / gate|up
             prefill GEMMs.  A quantised computation: not comparable with `value` of configs1.  Side block "configs4" of the default
-            run (own context, 64 tokens); `value` with --workload configs4.
+            workload with --full (own context, 64 tokens); `value` with --workload configs4.
 Inputs are resident in HBM before the timed region.  Weights: deterministic synthetic (omchat_amd/synth.py) at the full
 geometry, generated on the device; under TP every rank keeps its SHARD of the same values, and the first 32 greedy ids are
 checked against a TP = 1 context that rank 0 runs first in the same process ("tokens_match_tp1").
 
 Prints ONE JSON line (rank 0): `roofline` = dominant kernel of the step (decode gate|up weight stream, HBM-bound) from HIP
-events on the launch stream inside the timed region; `cpu_baseline` = the oracle on a bounded sample (N = 1 only).
+events on the launch stream inside the timed region; with --full also `cpu_baseline` = the oracle on a bounded sample (N = 1 only) and
+the other side measurements (see --help).  A run without --full sets up, warms up, times the --steps steps and prints the line.
+--dump-outputs DIR: after the timed steps, the outputs of the last one (image features, prefill logits, generated ids) as .npy files;
+the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -55,8 +59,14 @@ def parse():
     ap.add_argument("--images", type=int, default=8, help="configs3: pictures per sample")
     ap.add_argument("--graph", action="store_true", help="replay each decode step as one captured hipGraph instead of ~230 eager launches "
                     "(measured SLOWER on ROCm 7.2 / MI355X: 3.21 vs 2.96 ms per token, so it is off by default)")
-    ap.add_argument("--no-fp8", action="store_true", help="skip the (untimed) weight-only fp8 decode measurement")
-    ap.add_argument("--no-side", action="store_true", help="default workload: skip the configs3 / configs4 side blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: the configs2 side measurement of the default workload, the configs3 / "
+                         "configs4 side blocks, weight-only fp8 decode, generate(), the image front end, the CPU baseline and (N > 1) the "
+                         "data-parallel tower.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-fp8", action="store_true", help="--full: skip the (untimed) weight-only fp8 decode measurement")
+    ap.add_argument("--no-side", action="store_true", help="--full, default workload: skip the configs3 / configs4 side blocks")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--gen", type=int, default=256, help="greedy decode tokens per step")
@@ -77,7 +87,7 @@ def parse():
     ap.add_argument("--tp1-check-dtype", default="", choices=["", "bf16", "f16"],
                     help="N > 1: dtype of the TP = N vs TP = 1 logit / id cross-check contexts (default f16: every position clears the margin "
                          "guard there; the timed run keeps --dtype)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--tiny", action="store_true", help="debug: tiny geometry (NOT the benchmark config)")
     ap.add_argument("--tuning", default="", help="debug: comma-separated key=value pairs for omchat_op_set_tuning (include/omchat_hip.h)")
     return ap.parse_args()
@@ -301,6 +311,32 @@ def algorithmic(cfg):
             "kv_bytes_per_pos": Lt * 2.0 * kvd * 2.0}
 
 
+DUMP_SAMPLE = 4 << 20          # --dump-outputs: an array of more elements is written as a fixed seeded sample of this many
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files together
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: every output as d/<name>.npy, integer ids as float64 (exact), everything else as float32.  An array of more than
+    DUMP_SAMPLE elements goes to <name>_sample.npy: its elements at DUMP_SAMPLE sorted flat indices drawn with seed 0, the same indices for
+    the same shape in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        t = torch.as_tensor(t)
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        arr = t.to(torch.float32 if t.is_floating_point() else torch.float64).cpu().numpy()
+        total += arr.nbytes
+        if total > DUMP_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(d, name + ".npy"), arr)
+
+
 def main():
     a = parse()
     if a.workload == "configs4":
@@ -343,8 +379,9 @@ def main():
     ntok = cfg.num_image_tokens
     S = n_tiles * ntok + a.text_tokens
     do1 = a.workload in ("both", "configs1", "configs3", "configs4")      # configs3 / 4 run through the batch-1 leg with their own tiles / modes
-    do2 = a.workload in ("both", "configs2")
-    B2 = a.batch2 if do2 else 1
+    do2 = a.workload == "configs2" or (a.workload == "both" and a.full)      # configs2 beside configs1: a --full measurement
+    # the default workload's context is sized for the configs2 batch with or without --full: the headline runs in the same context either way
+    B2 = a.batch2 if a.workload in ("both", "configs2") else 1
     shard = a.shard_of if a.shard_of > 1 else 0
     tp_size = shard or world
     full = not a.tiny
@@ -554,7 +591,9 @@ def main():
                 out.append(tok)
             t[4].record()
             torch.cuda.synchronize()
-            return (t[0].elapsed_time(t[1]), t[1].elapsed_time(t[2]), t[3].elapsed_time(t[4]), torch.stack(out))
+            # what a caller of the path receives (every engine call returns a fresh tensor: holding them copies nothing)
+            outputs = {"image_features": feats, "prefill_logits": logits, "tokens": torch.stack(out, dim=1)}
+            return (t[0].elapsed_time(t[1]), t[1].elapsed_time(t[2]), t[3].elapsed_time(t[4]), outputs)
 
         for _ in range(warmup):
             step()
@@ -563,7 +602,10 @@ def main():
             e.prof_read(c, reset=True)
         barrier()
         t0 = time.perf_counter()
-        parts = [step() for _ in range(steps)]
+        parts = []
+        for _ in range(steps):
+            *times, outputs = step()          # the outputs of the last step are kept
+            parts.append(times)
         barrier()
         wall = time.perf_counter() - t0
         e.prof_enable(False)
@@ -576,7 +618,7 @@ def main():
         tiles = int(px.shape[0])
         return dict(wall=wall, steps=steps, b=b, gen=gen, tiles=tiles, S=int(ids.shape[1]) + (tiles // b) * (e.ntok - 1),
                     prof=prof, vit_ms=med([p[0] for p in parts]), pre_ms=med([p[1] for p in parts]), dec_ms=med([p[2] for p in parts]),
-                    max_tiles=e.c.max_tiles, local=e.local)
+                    max_tiles=e.c.max_tiles, local=e.local, outputs=outputs)
 
     def summarise(r, cfg_, decode_bytes=None):
         """decode_bytes(b, L) -> algorithmic bytes of one decode step (default: 16-bit weights + 16-bit KV)"""
@@ -666,9 +708,18 @@ def main():
     if peer_timeouts:
         raise SystemExit("bench.py: a peer-exchange barrier timed out on some rank inside the measured steps: the kernels went on with stale slots, "
                          "the numbers are void (ranks oversubscribing one GPU can starve each other; one rank per GPU: a lost peer)")
+    outputs = (r1 if do1 else r2)["outputs"]
+    for r in (r1, r2):
+        if r is not None:
+            del r["outputs"]
+    if a.dump_outputs and world > 1:
+        outputs["prefill_logits"] = eng.full_logits(outputs["prefill_logits"])      # vocabulary shards -> [b, V] (every rank takes part)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outputs)
+    del outputs
     # data-parallel tower beside the tensor-parallel headline: same tiles, replicated tower, one gather (all ranks take part)
     vit_dp_side = None
-    if world > 1 and a.vit == "both":
+    if world > 1 and a.vit == "both" and a.full:
         tower = make_tower()
         vit_dp_side = {}
         for nm, bb in (("configs1", 1),) + ((("configs2", B2),) if do2 else ()):
@@ -751,7 +802,7 @@ def main():
                    "note": "side measurement in the same process and context; NOT part of `value`"})
         res["configs2"] = s2
     # weight-only fp8 decode (row f-2 / configs[4]), outside the timed region: same prompt, 64 greedy tokens on the e4m3 replica
-    if world == 1 and not shard and not a.no_fp8 and not do4 and not do3:
+    if a.full and world == 1 and not shard and not a.no_fp8 and not do4 and not do3:
         px, ids = make_inputs(1)
         eng.enable_fp8_decode(True)
         n8 = min(64, a.gen)
@@ -774,7 +825,7 @@ def main():
                                      "prefill, KV cache and activations stay 16-bit; NOT part of `value`"}
     # the drop-in entry (single_inference.py:53-62): model.generate(input_ids, images=...) on the same sample -- tower, splice, prefill and
     # the greedy loop with the host looking at every token (EOS / streamer), next to the engine-level loop of `value`
-    if world == 1 and not shard and do1 and not do3 and not do4:
+    if a.full and world == 1 and not shard and do1 and not do3 and not do4:
         from omchat_amd.model.omchat_qwen2 import OmChatQwen2ForCausalLM
         model = OmChatQwen2ForCausalLM(cfg.clone(), eng)
         px, ids = make_inputs(1)
@@ -828,7 +879,7 @@ def main():
         if bits:
             raise SystemExit(f"bench.py: a hand-off of the fused decode launch timed out (bits {bits:#x}): results invalid")
     rgb = pins = None
-    if world == 1 and not shard and not do3:
+    if a.full and world == 1 and not shard and not do3:
         # image front-end (row f-1), outside the timed region: raw RGB bytes on the host -> normalised tiles in HBM
         pins = [(448, 896), (896, 448), (896, 896), (1344, 448), (448, 1344), (1344, 1344)]
         rgb = np.random.default_rng(0).integers(0, 256, (380, 570, 3), dtype=np.uint8)       # size of the reference's sample picture -> 3 tiles
@@ -842,7 +893,7 @@ def main():
         res["frontend_ms_p50"] = sorted(fe[2:])[len(fe[2:]) // 2]
 
     # ---- side blocks of the default run (N = 1): BASELINE configs[3] and configs[4], each in its own context
-    side = a.workload == "both" and world == 1 and not shard and not a.no_side and full
+    side = a.full and a.workload == "both" and world == 1 and not shard and not a.no_side and full
     if side:
         eng.close()
         del eng
@@ -884,7 +935,7 @@ def main():
         torch.cuda.empty_cache()
     # GEMM tile choices come from the committed omchat_amd/gemm_tune_gfx950.txt: 0 = no first-use tuning ran in this process
     res["gemm_tune_measurements"] = int(_lib.lib().omchat_gemm_tune_runs())
-    if world == 1 and not shard and not a.no_cpu_baseline:          # CPU baseline: rank 0 at N = 1 only
+    if a.full and world == 1 and not shard and not a.no_cpu_baseline:          # CPU baseline: rank 0 at N = 1 only
         res["cpu_baseline"] = cpu_baseline(cfg, S, a.gen, n_tiles)
         if rgb is not None:
             from PIL import Image

@@ -284,7 +284,32 @@ def test_entry_scripts_parse_and_bench_cli():
     for f in [os.path.join(root, "bench.py"), os.path.join(root, "__graft_entry__.py")] + glob.glob(os.path.join(root, "tools", "*.py")):
         ast.parse(open(f).read(), filename=f)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and all(flag in out.stdout for flag in ("--gpus", "--steps", "--warmup"))
+    assert out.returncode == 0 and all(flag in out.stdout for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"))
+
+
+def test_bench_dump_outputs_dtypes_fixed_sample_and_budget(tmp_path):
+    """bench.py --dump-outputs: ids as float64 (exact), 16-bit / fp32 arrays as float32, an array above DUMP_SAMPLE elements as a sample at
+    seeded indices -- the same ones in every run, so two builds compare element for element -- and the files stay within DUMP_BYTES"""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    feats = torch.randn(96, 256, 3584 // 16, generator=g).to(torch.bfloat16)          # more than DUMP_SAMPLE elements
+    logits = torch.randn(2, 152064, generator=g)
+    ids = torch.tensor([[151642, 0, 17], [3, 4, 5]], dtype=torch.int32)
+    assert feats.numel() > bench.DUMP_SAMPLE >= logits.numel()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"image_features": feats, "prefill_logits": logits, "tokens": ids})
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["image_features_sample.npy", "prefill_logits.npy", "tokens.npy"]
+    assert a["tokens.npy"].dtype == np.float64 and np.array_equal(a["tokens.npy"], ids.numpy())
+    assert a["prefill_logits.npy"].dtype == np.float32 and np.array_equal(a["prefill_logits.npy"], logits.numpy())
+    s = a["image_features_sample.npy"]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_SAMPLE,)
+    assert np.isin(s, feats.float().numpy()).all()                                        # values of the array, not a reduction of it
+    for f, x in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f), x)                             # same sample in every run
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in a) <= bench.DUMP_BYTES
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": torch.zeros(bench.DUMP_SAMPLE) for i in range(5)})
 
 
 def test_public_header_is_plain_c(tmp_path):
