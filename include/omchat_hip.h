@@ -149,6 +149,18 @@ int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float* logits, vo
 /* greedy pick (HF generate with do_sample=False: argmax of the last position, first index wins): logits fp32
  * [b, t_vocab] (rank-local slice under tensor parallelism; the (max, index) pairs are exchanged) -> int32 [b] */
 int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream);
+/* ---- sampling (HF generate with do_sample=True) ----------------------------------------------- */
+/* omchat_set_sampling: from now on every token pick of this context -- omchat_sample, omchat_decode_step, both masked steps, the captured
+ * decode graph -- samples instead of taking the argmax.  Processing order as HF's sampling path: repetition penalty (rep_penalty; 1 = off),
+ * temperature (> 0), top-k (0 = off; ties at the k-th value are kept; top_k == 1 is exactly the greedy pick), top-p (1 = off; the smallest set
+ * of highest tokens whose mass reaches top_p, ties at the threshold kept), then a Gumbel-max draw keyed by (seed, row, step, global vocabulary
+ * index): the same ids at every TP degree.  seen_ids host int32, the rows' seen ids one after another (n_seen_per_row host int32 [b]); ids
+ * outside [0, vocab) -- the -200 image sentinel -- are ignored; each pick adds its id.  Resets the rows' step counters to 0.  b = 0 switches
+ * sampling off (greedy again).  A parameter change drops the captured decode graphs.  Synchronises. */
+int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                        const int32_t* seen_ids, const int32_t* n_seen_per_row, void* stream);
+/* the sampled counterpart of omchat_greedy (the first token after the prefill); omchat_greedy itself when sampling is off */
+int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream);
 int omchat_kv_lengths(omchat_ctx* ctx, int32_t* out, int b);      /* host copy of the current KV lengths */
 /* take back the last n decode steps of sequences 0..b-1 (generate() enqueues step k + 1 before it has read token k on the host, as the
  * reference's HF loop cannot; when token k ends the generation -- EOS, a stopping criterion -- that step is forgotten).  Synchronises. */
@@ -389,6 +401,10 @@ int omchat_op_rope_kv(int dtype, void* qkv, int b, int S, int Hq, int Hkv, int p
 int omchat_op_rope_kv_q8(int dtype, void* qkv, int b, int S, int Hq, int Hkv, int pos0, float theta, void* kcache, void* vcache, int cap,
                          void* k8, void* v8, float* ks, float* vs, void* stream);
 int omchat_op_argmax(const float* logits, int b, int V, int32_t* out, void* stream);
+/* context-free sampler over logits fp32 [b, V] with the parameters of omchat_set_sampling; every row at step `step`.  thr_out (device uint32 [b]
+ * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */
+int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                     const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream);
 int omchat_op_fill_uniform(int dtype, void* dst, int64_t n, uint64_t key, float scale, float offset, void* stream);
 
 /* ---- image front-end: process_anyres_image (omchat/mm_utils.py:119-158) + CLIPImageProcessor ---- */

@@ -49,6 +49,8 @@ _SIGS = {
     "omchat_decode_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_lm_head": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_greedy": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "omchat_set_sampling": (_i, [_vp, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _vp]),
+    "omchat_sample": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
     "omchat_decode_step_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -102,6 +104,7 @@ _SIGS = {
     "omchat_op_rope_kv": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "omchat_op_rope_kv_q8": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_argmax": (_i, [_vp, _i, _i, _vp, _vp]),
+    "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_op_fill_uniform": (_i, [_i, _vp, _i64, _u64, _f, _f, _vp]),
     "omchat_preproc_plan": (_i, [_i, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "omchat_preproc_anyres": (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -320,6 +320,42 @@ extern "C" int omchat_op_argmax(const float* logits, int b, int V, int32_t* out,
   return rc;
 }
 
+extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                                const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream) {
+  OM_CHECK(logits && out && b >= 1 && V >= 1, "bad argument");
+  OM_CHECK(temperature > 0.f && top_k >= 0 && top_p > 0.0 && top_p <= 1.0 && rep_penalty > 0.f, "sampling parameters out of range");
+  const int bmw = (V + 31) / 32;
+  std::vector<uint32_t> bm((size_t)b * bmw, 0u);
+  if (rep_penalty != 1.f && seen_ids && n_seen_per_row) {
+    size_t off = 0;
+    for (int i = 0; i < b; ++i) {
+      for (int j = 0; j < n_seen_per_row[i]; ++j) {
+        const int id = seen_ids[off + j];
+        if (id >= 0 && id < V) bm[(size_t)i * bmw + (id >> 5)] |= 1u << (id & 31);
+      }
+      off += (size_t)n_seen_per_row[i];
+    }
+  }
+  std::vector<int> steps(b, step);
+  const size_t ws_bytes = sample_ws_bytes(b);
+  char* mem = nullptr;
+  OM_HIP(hipMalloc(&mem, ws_bytes + bm.size() * 4 + (size_t)b * 8));
+  uint32_t* d_bm = (uint32_t*)(mem + ws_bytes);
+  int* d_last = (int*)(mem + ws_bytes + bm.size() * 4);
+  int* d_step = d_last + b;
+  hipMemcpyAsync(d_bm, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, S(stream));
+  hipMemcpyAsync(d_step, steps.data(), (size_t)b * 4, hipMemcpyHostToDevice, S(stream));
+  SampleArgs a;
+  a.logits = logits; a.ld = V; a.b = b; a.V = V; a.V_total = V;
+  a.seed = seed; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.penalty = rep_penalty;
+  if (rep_penalty != 1.f) { a.bitmap = d_bm; a.bm_words = bmw; }
+  a.last_set = d_last; a.step = d_step; a.out = out; a.thr_out = thr_out; a.ws = mem;
+  int rc = launch_sample(a, S(stream));
+  hipStreamSynchronize(S(stream));
+  hipFree(mem);
+  return rc;
+}
+
 extern "C" int omchat_op_fill_uniform(int dtype, void* dst, int64_t n, uint64_t key, float scale, float offset, void* stream) {
   return launch_fill_uniform(dtype, dst, n, key, scale, offset, S(stream));
 }

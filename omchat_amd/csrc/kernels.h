@@ -331,6 +331,27 @@ int launch_copy_rows(int dtype, const void* src, int64_t src_ld, void* dst, int6
 size_t argmax_scratch_bytes(int b);
 // adv_pos / adv_len (optional, device [b]): incremented by one in the second stage -- the decode step's position bookkeeping without a launch of its own
 int launch_argmax(const float* logits, int ld, int b, int V, int* out, void* scratch, hipStream_t s, int* adv_pos = nullptr, int* adv_len = nullptr);   // scratch: argmax_scratch_bytes(b)
+// on-device sampling (sample.hip): repetition penalty, temperature, top-k, top-p, Gumbel-max draw keyed by (seed, row, step[row], global
+// index); tests/sampling_ref.py restates it.  Rank-local logits [b, ld]; under tensor parallelism (tp > 1) the integer histograms and the final
+// (value, index) pairs go through xchg (the context's fp32 all-reduce) and `table` ([tp][b][2] fp32, the greedy exchange's).
+struct SampleArgs {
+  const float* logits = nullptr; int ld = 0, b = 0, V = 0, V_total = 0;   // V: this rank's vocabulary slice
+  int rank = 0, tp = 1;
+  uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f;
+  uint32_t* bitmap = nullptr; int bm_words = 0;     // [b][bm_words] seen tokens of this rank's slice (read when penalty != 1, picked id set)
+  int* last_set = nullptr;                          // [b] local index whose bit the last pick set, -1 = none (omchat_kv_rewind)
+  int* step = nullptr;                              // [b] device step counters, advanced by one
+  int* adv_pos = nullptr; int* adv_len = nullptr;   // optional: decode positions advanced with the pick
+  int* out = nullptr; uint32_t* thr_out = nullptr;  // picked ids [b]; optional threshold keys [b] (test hook)
+  void* ws = nullptr;                               // sample_ws_bytes(b)
+  float* table = nullptr;
+  int (*xchg)(void* user, float* buf, size_t count, hipStream_t s) = nullptr;
+  void* xchg_user = nullptr;
+};
+size_t sample_ws_bytes(int b);
+int launch_sample(const SampleArgs& a, hipStream_t s);
+// take back n picks: clears the bit the last pick set (n == 1), step -= n
+int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s);
 // deterministic synthetic fill (bit-identical to omchat_amd/synth.py::uniform)
 int launch_fill_uniform(int dtype, void* dst, int64_t n, uint64_t key, float scale, float offset, hipStream_t s);
 int launch_cast_f32(int dtype, const void* src, float* dst, int64_t n, hipStream_t s);

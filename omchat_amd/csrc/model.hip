@@ -179,6 +179,13 @@ struct omchat_ctx {
   unsigned long long* dbg_stamps = nullptr;      // experiments build: [layers][8] clock stamps of the last decode step (tuning key 42 bit 4)
   unsigned* dyn_ctr = nullptr;      // [layers][65 * 64] work counters of the dynamic gate|up GEMV (gemv_rows_norm_dyn_kernel), zero between launches
   int *d_pos = nullptr, *d_len = nullptr, *d_idx = nullptr, *d_start = nullptr;
+  // on-device sampling (omchat_set_sampling; sample.hip): uniform parameters for the batch, per-row device step counters, the repetition
+  // penalty's seen-token bitmap of this rank's vocabulary slice [max_batch][smp_bmw] and the local index of the bit each row's last pick set
+  struct Sampling { bool on = false; uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f; };
+  Sampling smp;
+  void* smp_ws = nullptr;
+  uint32_t* smp_bm = nullptr; int smp_bmw = 0;
+  int *smp_last = nullptr, *smp_step = nullptr;
   bool left_padded = false;
   // decode of a padded batch as the reference computes it (omchat_decode_step_masked): every row's cache holds pre_S + masked_steps slots;
   // dec_mode: 0 = no decode step since the prefill, 1 = omchat_decode_step (per-sequence lengths), 2 = omchat_decode_step_masked
@@ -1224,6 +1231,24 @@ static int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_to
   return 0;
 }
 
+static int smp_xchg(void* user, float* buf, size_t count, hipStream_t s) { return ((omchat_ctx*)user)->allreduce_f32(buf, count, s); }
+
+// the token pick of a step: greedy unless omchat_set_sampling switched the sampler on; `advance` moves the decode positions in the same launch
+static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false) {
+  if (!ctx->smp.on) return greedy_pick(ctx, lg, b, next_tokens, s, advance);
+  const omchat_config& c = ctx->c;
+  SampleArgs a;
+  a.logits = lg; a.ld = c.t_vocab; a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total;
+  a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
+  a.seed = ctx->smp.seed; a.temperature = ctx->smp.temperature; a.top_k = ctx->smp.top_k; a.top_p = ctx->smp.top_p; a.penalty = ctx->smp.penalty;
+  if (ctx->smp.penalty != 1.f) { a.bitmap = ctx->smp_bm; a.bm_words = ctx->smp_bmw; }
+  a.last_set = ctx->smp_last; a.step = ctx->smp_step;
+  if (advance) { a.adv_pos = ctx->d_pos; a.adv_len = ctx->d_len; }
+  a.out = next_tokens; a.ws = ctx->smp_ws; a.table = ctx->tp_table;
+  a.xchg = smp_xchg; a.xchg_user = ctx;
+  return launch_sample(a, s);
+}
+
 extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
   return greedy_pick(ctx, logits, b, next_tokens, (hipStream_t)stream);
@@ -1652,7 +1677,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, f8, fused && pk));
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
-  if (next_tokens) TRY(greedy_pick(ctx, lg, b, next_tokens, s, true));
+  if (next_tokens) TRY(pick_next(ctx, lg, b, next_tokens, s, true));
   else hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
   OM_LAUNCH_CHECK();
   return 0;
@@ -1662,6 +1687,66 @@ static void destroy_graph(omchat_ctx::DecodeGraph& g) {
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (g.graph) (void)hipGraphDestroy(g.graph);
   g = omchat_ctx::DecodeGraph{};
+}
+
+// Sampling parameters live in the kernel arguments of the captured decode graphs: a change drops them (re-captured on the next step).
+extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                                   const int32_t* seen_ids, const int32_t* n_seen_per_row, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  const omchat_config& c = ctx->c;
+  omchat_ctx::Sampling p;
+  p.on = b > 0;
+  if (p.on) {
+    OM_CHECK(b <= c.max_batch, "sampling: batch exceeds max_batch");
+    OM_CHECK(temperature > 0.f && isfinite(temperature), "sampling: temperature must be a strictly positive float (greedy: do_sample=False)");
+    OM_CHECK(top_k >= 0, "sampling: top_k >= 0 (0 = off)");
+    OM_CHECK(top_p > 0.0 && top_p <= 1.0, "sampling: top_p in (0, 1] (1 = off)");
+    OM_CHECK(rep_penalty > 0.f && isfinite(rep_penalty), "sampling: repetition_penalty must be a strictly positive float");
+    p.seed = seed; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.penalty = rep_penalty;
+  }
+  const omchat_ctx::Sampling& o = ctx->smp;
+  const bool same = o.on == p.on && o.seed == p.seed && o.temperature == p.temperature && o.top_k == p.top_k && o.top_p == p.top_p &&
+                    o.penalty == p.penalty;
+  if (!same) {
+    for (auto& kv : ctx->graphs) destroy_graph(kv.second);
+    ctx->graphs.clear();
+  }
+  ctx->smp = p;
+  if (!p.on) return 0;
+  if (!ctx->smp_ws) {
+    ctx->smp_bmw = (c.t_vocab + 31) / 32;
+    TRY(ctx->alloc(&ctx->smp_ws, sample_ws_bytes(c.max_batch)));
+    TRY(ctx->alloc((void**)&ctx->smp_bm, (size_t)c.max_batch * ctx->smp_bmw * 4));
+    TRY(ctx->alloc((void**)&ctx->smp_last, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&ctx->smp_step, (size_t)c.max_batch * 4));
+  }
+  // this rank's slice of the seen sets; ids outside the vocabulary (the -200 image sentinel) are never seen
+  std::vector<uint32_t> bm((size_t)c.max_batch * ctx->smp_bmw, 0u);
+  if (rep_penalty != 1.f && seen_ids && n_seen_per_row) {
+    const int64_t lo = (int64_t)ctx->tp_rank * c.t_vocab;
+    size_t off = 0;
+    for (int i = 0; i < b; ++i) {
+      OM_CHECK(n_seen_per_row[i] >= 0, "sampling: n_seen_per_row >= 0");
+      for (int j = 0; j < n_seen_per_row[i]; ++j) {
+        const int64_t li = (int64_t)seen_ids[off + j] - lo;
+        if (seen_ids[off + j] >= 0 && seen_ids[off + j] < c.t_vocab_total && li >= 0 && li < c.t_vocab)
+          bm[(size_t)i * ctx->smp_bmw + (li >> 5)] |= 1u << (li & 31);
+      }
+      off += (size_t)n_seen_per_row[i];
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemcpyAsync(ctx->smp_bm, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(ctx->smp_step, 0, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipMemsetAsync(ctx->smp_last, 0xFF, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipStreamSynchronize(s));     // host vector
+  return 0;
+}
+
+// the first token after the prefill (omchat_greedy's sampled counterpart): advances the step counters, not the decode positions
+extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
+  OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  return pick_next(ctx, logits, b, next_tokens, (hipStream_t)stream);
 }
 
 extern "C" int omchat_enable_decode_graph(omchat_ctx* ctx, int on) {
@@ -1969,6 +2054,12 @@ extern "C" int omchat_fused_status(omchat_ctx* ctx, long* launches, unsigned* ti
 extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   OM_CHECK(ctx && b >= 1 && b <= (int)ctx->h_len.size() && n >= 0, "bad argument");
   if (n == 0) return 0;
+  if (ctx->smp.on) {
+    // the sampler's step counters go back with the slots, and the seen bit the last pick set is cleared (only that pick is recorded)
+    OM_CHECK(n == 1 || ctx->smp.penalty == 1.f, "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded");
+    TRY(launch_sample_rewind(ctx->smp.penalty != 1.f ? ctx->smp_bm : nullptr, ctx->smp_bmw, ctx->smp_last, ctx->smp_step, b, n,
+                             (hipStream_t)stream));
+  }
   if (ctx->dec_mode == 2) {
     OM_CHECK(n <= ctx->masked_steps, "rewind beyond the prefill");
     ctx->masked_steps -= n;

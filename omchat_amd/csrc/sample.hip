@@ -1,0 +1,381 @@
+// On-device sampling for generate(do_sample=True): repetition penalty, temperature, top-k, top-p and the categorical draw, in the order of
+// HF's sampling path.  No sort: the top-k / top-p thresholds are found by a radix select over the order-preserving
+// uint32 key of each processed fp32 logit (11 / 11 / 10 bits), the draw is an exponential race (Gumbel-max) whose noise is a counter-based
+// hash of (seed, row, step, GLOBAL vocabulary index).  Every quantity that crosses workgroups or ranks is an integer (token counts, fixed-point
+// probability mass, max keys), so the kept set -- and with the global-index noise the picked id -- is the same at every TP degree and in
+// every launch order.  tests/sampling_ref.py is the CPU restatement, bit for bit.
+#include "kernels.h"
+#include <limits.h>
+#include <math.h>
+
+namespace {
+
+constexpr int SMP_BINS = 2048;         // 11-bit digits (the last round uses 1024 of them)
+constexpr int SMP_XS = 3 * SMP_BINS;   // exchange row under TP: every bin as three 21-bit limbs in fp32
+constexpr int SMP_HIST_CH = 16;        // workgroups per row of the histogram / max passes
+constexpr int SMP_RACE_CH = 64;        // workgroups per row of the race (= the 64 lanes of the final wave)
+constexpr int SMP_ST = 8;              // int64 state words per row
+// state words
+enum { ST_PREFIX = 0, ST_CUM = 1, ST_TK = 2, ST_MKEY = 3, ST_TARGET = 4, ST_THR = 5 };
+constexpr double SMP_FIX = 4294967296.0;    // probability mass in units of 2^-32 of the max token's weight
+
+__device__ __forceinline__ uint64_t smp_mix(uint64_t x) {      // splitmix64, as elementwise.hip's fill_uniform_kernel
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t smp_row_key(uint64_t seed, int row, int step) {
+  return smp_mix(seed ^ smp_mix(((uint64_t)(uint32_t)row << 32) | (uint32_t)step));
+}
+// Gumbel noise -log(E), E = -log(U) ~ Exp(1), U in (0, 1) from 52 hash bits; evaluated in fp64 and rounded once to fp32
+__device__ __forceinline__ float smp_noise(uint64_t rk, uint32_t gi) {
+  const uint64_t h = smp_mix(rk + (uint64_t)gi * 0x9E3779B97F4A7C15ull);
+  const double u = ((double)(h >> 12) + 0.5) * 0x1p-52;
+  return (float)(-log(-log(u)));
+}
+__device__ __forceinline__ uint32_t smp_key(float f) {
+  uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);     // -0 and +0 are one key (HF compares values)
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float smp_unkey(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+// RepetitionPenaltyLogitsProcessor (seen: < 0 -> * p, else / p), then TemperatureLogitsWarper (/ T), in fp32 as HF computes them
+__device__ __forceinline__ float smp_penalised(const float* row, const uint32_t* seen, int i, float pen) {
+  float l = row[i];
+  if (seen && ((seen[i >> 5] >> (i & 31)) & 1u)) l = l < 0.f ? __fmul_rn(l, pen) : __fdiv_rn(l, pen);
+  return l;
+}
+__device__ __forceinline__ void smp_better(float& best, int& besti, float v, int i) {
+  if (v > best || (v == best && i < besti)) { best = v; besti = i; }
+}
+__device__ __forceinline__ int smp_shift(int round) { return round == 0 ? 21 : round == 1 ? 10 : 0; }
+
+// local max key of the processed logits (top-p needs the max for its softmax): one u64 atomicMax per workgroup into bin 0 of the row
+__global__ __launch_bounds__(256) void smp_max_kernel(const float* logits, int ld, int V, const uint32_t* seen, int bmw, float pen, float T,
+                                                      uint64_t* hist) {
+  const int row = blockIdx.y;
+  const float* lg = logits + (size_t)row * ld;
+  const uint32_t* sn = seen ? seen + (size_t)row * bmw : nullptr;
+  const int per = (V + SMP_HIST_CH - 1) / SMP_HIST_CH;
+  const int lo = blockIdx.x * per, hi = min(lo + per, V);
+  uint32_t m = 0;
+  for (int i = lo + threadIdx.x; i < hi; i += 256) m = max(m, smp_key(__fdiv_rn(smp_penalised(lg, sn, i, pen), T)));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+  __shared__ uint32_t wm[4];
+  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(wm[0], wm[1]), max(wm[2], wm[3]));
+    atomicMax((unsigned long long*)&hist[(size_t)row * SMP_BINS], (unsigned long long)m);
+  }
+}
+
+// one radix round: MASS = 0 counts the tokens per digit, MASS = 1 sums their fixed-point weight exp(x - m) * 2^32 over keys >= the top-k
+// threshold.  Only keys whose higher digits equal the prefix found so far take part.  Integer LDS atomics, then one global atomic per digit.
+template <int MASS>
+__global__ __launch_bounds__(256) void smp_hist_kernel(const float* logits, int ld, int V, const uint32_t* seen, int bmw, float pen, float T,
+                                                       const int64_t* st, uint64_t* hist, int round) {
+  __shared__ unsigned long long bins[SMP_BINS];
+  const int row = blockIdx.y;
+  for (int j = threadIdx.x; j < SMP_BINS; j += 256) bins[j] = 0;
+  __syncthreads();
+  const float* lg = logits + (size_t)row * ld;
+  const uint32_t* sn = seen ? seen + (size_t)row * bmw : nullptr;
+  const int64_t* s = st + (size_t)row * SMP_ST;
+  const uint32_t prefix = (uint32_t)s[ST_PREFIX];
+  const int shift = smp_shift(round), hs = round == 1 ? 21 : 10;
+  const uint32_t lo_key = MASS ? (uint32_t)s[ST_TK] : 0u;
+  const double m = MASS ? (double)smp_unkey((uint32_t)s[ST_MKEY]) : 0.0;
+  const int per = (V + SMP_HIST_CH - 1) / SMP_HIST_CH;
+  const int lo = blockIdx.x * per, hi = min(lo + per, V);
+  for (int i = lo + threadIdx.x; i < hi; i += 256) {
+    const float x = __fdiv_rn(smp_penalised(lg, sn, i, pen), T);
+    const uint32_t k = smp_key(x);
+    if (k < lo_key || (round > 0 && (k >> hs) != (prefix >> hs))) continue;
+    const int bin = (k >> shift) & (round == 2 ? 1023u : 2047u);
+    const unsigned long long w = MASS ? (unsigned long long)llrint(exp((double)x - m) * SMP_FIX) : 1ull;
+    if (w) atomicAdd(&bins[bin], w);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < SMP_BINS; j += 256)
+    if (bins[j]) atomicAdd((unsigned long long*)&hist[(size_t)row * SMP_BINS + j], bins[j]);
+}
+
+// tensor parallelism: the row's integer bins -> three exact fp32 limbs each (the all-reduce sums at most 8 ranks: < 2^24 per limb); the max
+// stage puts this rank's key as two 16-bit limbs into its own slot and zeros in the others'
+__global__ __launch_bounds__(256) void smp_to_limbs_kernel(const uint64_t* hist, float* xb, int max_stage, int rank) {
+  const int row = blockIdx.x;
+  const uint64_t* h = hist + (size_t)row * SMP_BINS;
+  float* x = xb + (size_t)row * SMP_XS;
+  if (max_stage) {
+    for (int j = threadIdx.x; j < 16; j += 256) {
+      const uint32_t k = (uint32_t)h[0];
+      x[j] = j == 2 * rank ? (float)(k & 0xFFFFu) : j == 2 * rank + 1 ? (float)(k >> 16) : 0.f;
+    }
+    return;
+  }
+  for (int j = threadIdx.x; j < SMP_BINS; j += 256) {
+    const uint64_t v = h[j];
+    x[3 * j] = (float)(v & 0x1FFFFFull);
+    x[3 * j + 1] = (float)((v >> 21) & 0x1FFFFFull);
+    x[3 * j + 2] = (float)(v >> 42);
+  }
+}
+
+// Close a round (one workgroup per row): read the row's bins (summed over the ranks), find the digit at which the running total from the top
+// reaches the target -- k tokens, or top_p of the kept mass -- and fix it in the prefix; the mass strictly above it carries to the next round.
+// stage: 0 = max, 1 = count round, 2 = mass round.  Zeroes the row's bins for the next pass.
+__global__ __launch_bounds__(256) void smp_select_kernel(uint64_t* hist, const float* xb, int tp, int64_t* st, int stage, int round, int top_k,
+                                                         double top_p, int p_follows) {
+  const int row = blockIdx.x, t = threadIdx.x;
+  uint64_t* h = hist + (size_t)row * SMP_BINS;
+  const float* x = xb ? xb + (size_t)row * SMP_XS : nullptr;
+  int64_t* s = st + (size_t)row * SMP_ST;
+  if (stage == 0) {
+    __syncthreads();
+    if (t == 0) {
+      uint32_t m = 0;
+      if (x) {
+        for (int r = 0; r < tp; ++r) m = max(m, (uint32_t)x[2 * r] | ((uint32_t)x[2 * r + 1] << 16));
+      } else {
+        m = (uint32_t)h[0];
+      }
+      s[ST_MKEY] = m;
+      h[0] = 0;
+    }
+    return;
+  }
+  __shared__ unsigned long long tot[256];
+  __shared__ int pick;
+  __shared__ unsigned long long above;
+  constexpr int PER = SMP_BINS / 256;
+  unsigned long long v[PER];
+  unsigned long long mine = 0;
+#pragma unroll
+  for (int e = 0; e < PER; ++e) {
+    const int j = t * PER + e;
+    v[e] = x ? (unsigned long long)x[3 * j] + ((unsigned long long)x[3 * j + 1] << 21) + ((unsigned long long)x[3 * j + 2] << 42) : h[j];
+    h[j] = 0;
+    mine += v[e];
+  }
+  tot[t] = mine;
+  if (t == 0) { pick = -1; above = 0; }
+  __syncthreads();
+  // inclusive suffix sums over the thread totals (digit order = thread order): tot[t] = sum of threads >= t
+  for (int o = 1; o < 256; o <<= 1) {
+    const unsigned long long add = t + o < 256 ? tot[t + o] : 0ull;
+    __syncthreads();
+    tot[t] += add;
+    __syncthreads();
+  }
+  const unsigned long long cum = (unsigned long long)s[ST_CUM];
+  double target;
+  if (stage == 1) {
+    target = (double)top_k;
+  } else if (round == 0) {
+    target = top_p * (double)tot[0];          // Z = the whole kept mass (keys >= the top-k threshold); P = top_p * Z
+  } else {
+    target = __longlong_as_double(s[ST_TARGET]);
+  }
+  // the largest digit j with cum + (mass of digits >= j) >= target; digits run upwards inside a thread's PER
+  unsigned long long run = (t + 1 < 256 ? tot[t + 1] : 0ull);     // everything above this thread's digits
+  int found = -1;
+  unsigned long long found_above = 0;
+#pragma unroll
+  for (int e = PER - 1; e >= 0; --e) {
+    const unsigned long long incl = run + v[e];
+    if (found < 0 && (double)(cum + incl) >= target) { found = t * PER + e; found_above = run; }
+    run = incl;
+  }
+  __syncthreads();
+  if (found >= 0) atomicMax(&pick, found);
+  __syncthreads();
+  if (found >= 0 && found == pick) above = found_above;
+  __syncthreads();
+  if (t == 0) {
+    const int j = pick < 0 ? 0 : pick;                 // (a target beyond the total cannot occur for valid parameters: keep everything)
+    const uint32_t prefix = (uint32_t)s[ST_PREFIX] | ((uint32_t)j << smp_shift(round));
+    if (stage == 2 && round == 0) s[ST_TARGET] = __double_as_longlong(target);
+    if (round < 2) {
+      s[ST_PREFIX] = prefix;
+      s[ST_CUM] = (int64_t)(cum + (pick < 0 ? 0ull : above));
+    } else {
+      s[ST_PREFIX] = 0; s[ST_CUM] = 0;
+      if (stage == 1) s[ST_TK] = prefix;
+      if (stage == 2 || !p_follows) s[ST_THR] = prefix;
+    }
+  }
+}
+
+// the race over the kept tokens (key >= threshold): argmax of x + Gumbel noise, first (global) index on ties.  greedy = 1 (top_k == 1): the
+// argmax of the penalised logits without noise or temperature, i.e. greedy_pick's id.
+__global__ __launch_bounds__(256) void smp_race_kernel(const float* logits, int ld, int V, const uint32_t* seen, int bmw, float pen, float T,
+                                                       const int64_t* st, int use_thr, int greedy, uint64_t seed, const int* step, int gbase,
+                                                       float* pv, int* pi) {
+  const int row = blockIdx.y;
+  const float* lg = logits + (size_t)row * ld;
+  const uint32_t* sn = seen ? seen + (size_t)row * bmw : nullptr;
+  const uint32_t thr = use_thr ? (uint32_t)st[(size_t)row * SMP_ST + ST_THR] : 0u;
+  const uint64_t rk = smp_row_key(seed, row, step[row]);
+  const int per = (V + SMP_RACE_CH - 1) / SMP_RACE_CH;
+  const int lo = blockIdx.x * per, hi = min(lo + per, V);
+  float best = -INFINITY;
+  int besti = INT_MAX;
+  for (int i = lo + threadIdx.x; i < hi; i += 256) {
+    const float l = smp_penalised(lg, sn, i, pen);
+    if (greedy) { smp_better(best, besti, l, gbase + i); continue; }
+    const float x = __fdiv_rn(l, T);
+    if (smp_key(x) < thr) continue;
+    smp_better(best, besti, __fadd_rn(x, smp_noise(rk, (uint32_t)(gbase + i))), gbase + i);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) smp_better(best, besti, __shfl_xor(best, o, 64), __shfl_xor(besti, o, 64));
+  __shared__ float bv[4];
+  __shared__ int bi[4];
+  if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) smp_better(best, besti, bv[w], bi[w]);
+    pv[row * SMP_RACE_CH + blockIdx.x] = best;
+    pi[row * SMP_RACE_CH + blockIdx.x] = besti;
+  }
+}
+
+// the picked id of a row: record it in the repetition bitmap (its own shard's bit; `last` remembers a newly set bit for omchat_kv_rewind),
+// advance the step counter and the decode positions
+__device__ __forceinline__ void smp_commit(int row, int id, int gbase, int V, uint32_t* bm, int bmw, int* last, int* step, int* adv_pos,
+                                           int* adv_len, int* out) {
+  out[row] = id;
+  if (bm) {
+    const int li = id - gbase;
+    int set = -1;
+    if (li >= 0 && li < V) {
+      uint32_t* w = bm + (size_t)row * bmw + (li >> 5);
+      const uint32_t bit = 1u << (li & 31);
+      if (!(*w & bit)) { *w |= bit; set = li; }
+    }
+    last[row] = set;
+  }
+  step[row] += 1;
+  if (adv_pos) adv_pos[row] += 1;
+  if (adv_len) adv_len[row] += 1;
+}
+
+// the 64 race partials of a row -> its winner.  TP = 1: commit.  TP > 1: (value, global index) into this rank's slot of the zeroed table that
+// the greedy exchange uses (model.hip: tp_argmax_scatter_kernel's layout)
+__global__ __launch_bounds__(64) void smp_final_kernel(const float* pv, const int* pi, int b, int tp, int rank, float* table, int gbase, int V,
+                                                       uint32_t* bm, int bmw, int* last, int* step, int* adv_pos, int* adv_len, int* out,
+                                                       const int64_t* st, uint32_t* thr_out) {
+  const int row = blockIdx.x;
+  float best = pv[row * SMP_RACE_CH + threadIdx.x];
+  int besti = pi[row * SMP_RACE_CH + threadIdx.x];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) smp_better(best, besti, __shfl_xor(best, o, 64), __shfl_xor(besti, o, 64));
+  if (threadIdx.x != 0) return;
+  if (thr_out) thr_out[row] = (uint32_t)st[(size_t)row * SMP_ST + ST_THR];
+  if (tp > 1) {
+    table[((size_t)rank * b + row) * 2] = best;
+    table[((size_t)rank * b + row) * 2 + 1] = besti == INT_MAX ? -1.f : (float)besti;
+    return;
+  }
+  smp_commit(row, besti == INT_MAX ? 0 : besti, gbase, V, bm, bmw, last, step, adv_pos, adv_len, out);
+}
+
+// after the exchange: ranks hold ascending index ranges, so strict > keeps the first index on ties (tp_argmax_pick_kernel's rule)
+__global__ void smp_tp_pick_kernel(const float* table, int b, int tp, int gbase, int V, uint32_t* bm, int bmw, int* last, int* step,
+                                   int* adv_pos, int* adv_len, int* out) {
+  const int i = threadIdx.x;
+  if (i >= b) return;
+  float best = table[(size_t)i * 2];
+  int bi = (int)table[(size_t)i * 2 + 1];
+  for (int r = 1; r < tp; ++r) {
+    const float v = table[((size_t)r * b + i) * 2];
+    if (v > best) { best = v; bi = (int)table[((size_t)r * b + i) * 2 + 1]; }
+  }
+  smp_commit(i, bi < 0 ? 0 : bi, gbase, V, bm, bmw, last, step, adv_pos, adv_len, out);
+}
+
+__global__ void smp_rewind_kernel(uint32_t* bm, int bmw, int* last, int* step, int b, int n) {
+  const int i = threadIdx.x;
+  if (i >= b) return;
+  if (bm && last[i] >= 0) bm[(size_t)i * bmw + (last[i] >> 5)] &= ~(1u << (last[i] & 31));
+  if (bm) last[i] = -1;
+  step[i] -= n;
+}
+
+}  // namespace
+
+size_t sample_ws_bytes(int b) {
+  return (size_t)b * (SMP_BINS * 8 + SMP_ST * 8 + SMP_XS * 4 + SMP_RACE_CH * 8);
+}
+
+int launch_sample(const SampleArgs& a, hipStream_t s) {
+  OM_CHECK(a.b >= 1 && a.V >= 1 && a.ws && a.out && a.step, "launch_sample: bad argument");
+  OM_CHECK(a.temperature > 0.f, "sampling: temperature must be > 0");
+  OM_CHECK(a.top_p > 0.0 && a.top_p <= 1.0, "sampling: top_p in (0, 1]");
+  OM_CHECK(a.tp == 1 || (a.xchg && a.table), "sampling under tensor parallelism needs the exchange");
+  const int b = a.b, V = a.V;
+  char* w = (char*)a.ws;
+  uint64_t* hist = (uint64_t*)w;                 w += (size_t)b * SMP_BINS * 8;
+  int64_t* st = (int64_t*)w;                     w += (size_t)b * SMP_ST * 8;
+  float* xb = (float*)w;                         w += (size_t)b * SMP_XS * 4;
+  float* pv = (float*)w;                         w += (size_t)b * SMP_RACE_CH * 4;
+  int* pi = (int*)w;
+  const int gbase = a.rank * V;
+  const bool pen = a.bitmap && a.penalty != 1.f;
+  const uint32_t* seen = pen ? a.bitmap : nullptr;
+  const bool greedy = a.top_k == 1;
+  const bool use_k = !greedy && a.top_k > 1 && a.top_k < a.V_total;
+  const bool use_p = !greedy && a.top_p < 1.0;
+  float* xbp = a.tp > 1 ? xb : nullptr;
+  auto exchange = [&](int max_stage, int rows) -> int {
+    if (a.tp == 1) return 0;
+    hipLaunchKernelGGL(smp_to_limbs_kernel, dim3(rows), dim3(256), 0, s, hist, xb, max_stage, a.rank);
+    return a.xchg(a.xchg_user, xb, (size_t)rows * SMP_XS, s);
+  };
+  if (use_k || use_p) {
+    OM_HIP(hipMemsetAsync(hist, 0, (size_t)b * (SMP_BINS + SMP_ST) * 8, s));
+    const dim3 hg(SMP_HIST_CH, b);
+    if (use_k) {
+      for (int r = 0; r < 3; ++r) {
+        hipLaunchKernelGGL(smp_hist_kernel<0>, hg, dim3(256), 0, s, a.logits, a.ld, V, seen, a.bm_words, a.penalty, a.temperature, st, hist, r);
+        if (int rc = exchange(0, b)) return rc;
+        hipLaunchKernelGGL(smp_select_kernel, dim3(b), dim3(256), 0, s, hist, xbp, a.tp, st, 1, r, a.top_k, a.top_p, (int)use_p);
+      }
+    }
+    if (use_p) {
+      hipLaunchKernelGGL(smp_max_kernel, hg, dim3(256), 0, s, a.logits, a.ld, V, seen, a.bm_words, a.penalty, a.temperature, hist);
+      if (int rc = exchange(1, b)) return rc;
+      hipLaunchKernelGGL(smp_select_kernel, dim3(b), dim3(256), 0, s, hist, xbp, a.tp, st, 0, 0, a.top_k, a.top_p, 1);
+      for (int r = 0; r < 3; ++r) {
+        hipLaunchKernelGGL(smp_hist_kernel<1>, hg, dim3(256), 0, s, a.logits, a.ld, V, seen, a.bm_words, a.penalty, a.temperature, st, hist, r);
+        if (int rc = exchange(0, b)) return rc;
+        hipLaunchKernelGGL(smp_select_kernel, dim3(b), dim3(256), 0, s, hist, xbp, a.tp, st, 2, r, a.top_k, a.top_p, 1);
+      }
+    }
+  }
+  if (a.tp > 1) OM_HIP(hipMemsetAsync(a.table, 0, (size_t)a.tp * b * 2 * 4, s));
+  hipLaunchKernelGGL(smp_race_kernel, dim3(SMP_RACE_CH, b), dim3(256), 0, s, a.logits, a.ld, V, seen, a.bm_words, a.penalty, a.temperature,
+                     st, (int)(use_k || use_p), (int)greedy, a.seed, a.step, gbase, pv, pi);
+  uint32_t* bm = pen ? a.bitmap : nullptr;
+  hipLaunchKernelGGL(smp_final_kernel, dim3(b), dim3(64), 0, s, pv, pi, b, a.tp, a.rank, a.table, gbase, V, bm, a.bm_words, a.last_set, a.step,
+                     a.adv_pos, a.adv_len, a.out, st, (use_k || use_p) ? a.thr_out : nullptr);
+  if (a.tp > 1) {
+    // the greedy exchange: zeroed table, one slot per rank, summed
+    OM_LAUNCH_CHECK();
+    if (int rc = a.xchg(a.xchg_user, a.table, (size_t)a.tp * b * 2, s)) return rc;
+    hipLaunchKernelGGL(smp_tp_pick_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, a.table, b, a.tp, gbase, V, bm, a.bm_words, a.last_set, a.step,
+                       a.adv_pos, a.adv_len, a.out);
+  }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s) {
+  hipLaunchKernelGGL(smp_rewind_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, bitmap, bm_words, last_set, step, b, n);
+  OM_LAUNCH_CHECK();
+  return 0;
+}

@@ -351,3 +351,25 @@ class Engine:
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=self.device)
         check(self.lib.omchat_greedy(self.h, ptr(logits), logits.shape[0], ptr(out), cur_stream()))
         return out
+
+    # ------------------------------------------------------------------ sampling (include/omchat_hip.h: omchat_set_sampling)
+    def set_sampling(self, b, seed=0, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seen=None):
+        """every following token pick of rows 0..b-1 samples (HF order: repetition penalty, temperature, top-k, top-p; Gumbel-max keyed by
+        (seed, row, step, global id)); seen: per-row lists of already-seen ids for the penalty (ids outside the vocabulary are ignored).
+        Resets the rows' step counters.  b = 0: greedy again."""
+        torch = _torch()
+        seen = seen if seen is not None else [[] for _ in range(max(b, 0))]
+        n = torch.tensor([len(r) for r in seen] or [0], dtype=torch.int32)
+        flat = torch.tensor([int(i) for r in seen for i in r] or [0], dtype=torch.int32)
+        check(self.lib.omchat_set_sampling(self.h, int(b), int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), int(top_k or 0),
+                                           float(1.0 if top_p is None else top_p), float(repetition_penalty), ptr(flat), ptr(n), cur_stream()))
+
+    def sampling_off(self):
+        check(self.lib.omchat_set_sampling(self.h, 0, 0, 1.0, 0, 1.0, 1.0, None, None, cur_stream()))
+
+    def sample(self, logits):
+        """the sampled counterpart of argmax (first token after the prefill): rank-local logits [b, V / tp] -> int32 [b]"""
+        torch = _torch()
+        out = torch.empty(logits.shape[0], dtype=torch.int32, device=self.device)
+        check(self.lib.omchat_sample(self.h, ptr(logits), logits.shape[0], ptr(out), cur_stream()))
+        return out

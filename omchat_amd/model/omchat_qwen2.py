@@ -106,7 +106,10 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         args = types.SimpleNamespace(**config.mm)
         self.vision_tower = build_vision_tower(args, engine=engine) if engine.c.v_layers > 0 else None
         self.mm_projector = build_vision_projector(args, engine=engine) if engine.c.v_layers > 0 else None
-        self.generation_config = _GenerationConfig(pad_token_id=None, eos_token_id=None, max_new_tokens=None)
+        # sampling defaults as HF's GenerationConfig (temperature 1, top_k 50, top_p 1, no penalty); `seed` is this project's: the on-device
+        # sampler draws from an explicit seed, never from torch's global RNG state
+        self.generation_config = _GenerationConfig(pad_token_id=None, eos_token_id=None, max_new_tokens=None, do_sample=False, temperature=1.0,
+                                                   top_k=50, top_p=1.0, repetition_penalty=1.0, seed=None)
         self._last_lengths = None
         self.device = engine.device
         self.dtype = engine.torch_dtype
@@ -203,13 +206,43 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                              "attention_mask": attention_mask, "images": kwargs.get("images", None)})
         return model_inputs
 
+    def _sampling_params(self, temperature, top_k, top_p, repetition_penalty, seed, generator):
+        """HF's resolution of the sampling arguments (None -> generation_config), validated as HF's warpers validate them"""
+        gc = self.generation_config
+        pick = lambda v, name, d: v if v is not None else (getattr(gc, name, None) if getattr(gc, name, None) is not None else d)
+        T = pick(temperature, "temperature", 1.0)
+        k = pick(top_k, "top_k", 0)
+        p = pick(top_p, "top_p", 1.0)
+        rp = pick(repetition_penalty, "repetition_penalty", 1.0)
+        if not float(T) > 0:
+            raise ValueError(f"`temperature` (={T}) has to be a strictly positive float, otherwise your next token scores will be invalid. "
+                             "If you're looking for greedy decoding strategies, set `do_sample=False`.")
+        if not (isinstance(k, int) and k >= 0):
+            raise ValueError(f"`top_k` has to be a non-negative integer, but is {k}")
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {p}")
+        if not float(rp) > 0:
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {rp}")
+        if seed is None and generator is not None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator, dtype=torch.int64))
+        if seed is None:
+            seed = getattr(gc, "seed", None)
+        if seed is None:
+            raise NotImplementedError("do_sample=True draws on the device from an explicit seed: pass seed=<int> or generator=<torch.Generator> "
+                                      "(or set generation_config.seed); sampling from torch's global RNG state is not implemented")
+        return dict(seed=int(seed), temperature=float(T), top_k=int(k), top_p=float(p), repetition_penalty=float(rp))
+
     @torch.no_grad()
-    def generate(self, input_ids=None, images=None, do_sample=False, temperature=0, max_new_tokens=None, streamer=None, use_cache=True,
-                 eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, **kwargs):
-        """Greedy loop as HF GenerationMixin drives it for single_inference.py:53-62: argmax of the last position (first
-        index wins), stop on EOS (kept in the output) or max_new_tokens; returns prompt + new ids [b, T + new]."""
-        if do_sample:
-            raise NotImplementedError("sampling is outside the hot path; the reference CLIs call generate(do_sample=False)")
+    def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
+                 eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
+                 repetition_penalty=None, seed=None, generator=None, **kwargs):
+        """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
+        prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
+        (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
+        and the generated ones, temperature, top-k, top-p -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed."""
+        if do_sample is None:
+            do_sample = bool(getattr(self.generation_config, "do_sample", False))
+        smp = self._sampling_params(temperature, top_k, top_p, repetition_penalty, seed, generator) if do_sample else None
         if max_new_tokens is None:
             max_new_tokens = self.generation_config.max_new_tokens or 20
         eos = eos_token_id if eos_token_id is not None else self.generation_config.eos_token_id
@@ -220,8 +253,16 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             streamer.put(input_ids.cpu())
         out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
         # ONE rule for the first token at every TP degree: omchat_greedy on this rank's vocabulary shard -- local first-index-wins argmax,
-        # then the (max, index) exchange the decode step uses (model.hip: greedy_pick); no torch re-statement on the gathered logits
-        tok = self.engine.argmax(out.local_logits)
+        # then the (max, index) exchange the decode step uses (model.hip: greedy_pick); no torch re-statement on the gathered logits.
+        # Sampling: the same seam with the sampler (omchat_sample); the decode steps below then sample too, the penalty's seen set growing
+        # on the device.  HF drives the processors with input_ids (the prompt, pads included) + the generated ids.
+        if smp is not None:
+            seen = [[int(i) for i in row if int(i) >= 0] for row in input_ids.tolist()]
+            self.engine.set_sampling(b, seen=seen, **smp)
+            tok = self.engine.sample(out.local_logits)
+        else:
+            self.engine.sampling_off()
+            tok = self.engine.argmax(out.local_logits)
         padded = getattr(self, "_padded_batch", False)
         # The KV cache is context-owned with a fixed capacity (the reference's DynamicCache grows without bound): generate as
         # many tokens as fit and stop cleanly, returning what was produced, instead of failing mid-stream with 'KV cache full'.
