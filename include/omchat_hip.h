@@ -166,6 +166,28 @@ int omchat_kv_lengths(omchat_ctx* ctx, int32_t* out, int b);      /* host copy o
  * reference's HF loop cannot; when token k ends the generation -- EOS, a stopping criterion -- that step is forgotten).  Synchronises. */
 int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream);
 
+/* ---- beam search (HF generate with num_beams = N > 1, _beam_search) --------------------------------------------- */
+/* omchat_beam_begin: after the prefill of b prompts into rows 0..b-1, every row prompt_tok_len cache slots long (equal lengths, no left
+ * padding; the caller guarantees the lengths, the first step forks exactly prompt_tok_len slots).  early_stopping: 0 = False, 1 = True, 2 = "never"; eos_ids host int32 [n_eos] (n_eos <= 8); max(2, 1 + n_eos) * num_beams
+ * <= 32; b * num_beams <= max_batch; prompt_tok_len + max_new - 1 <= max_seq.  Allocates the device state, the exchange table and the stash
+ * of the KV gather (counted in omchat_device_bytes).  The stash has room for every beam row's generated slots -- any row can be both a
+ * destination and a parent when parents form cycles --: layers * b*N * kv_heads * max_new * 512 bytes (776 with the e4m3 cache), e.g.
+ * 1.9 GB at 28 layers, 4 kv heads, b*N = 32, max_new = 1024; it is kept (grown, never shrunk) until the context is destroyed.
+ * Logits passed to omchat_beam_step must hold at least max(2, 1 + n_eos) * num_beams finite values per row.  Synchronises. */
+int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float length_penalty, int early_stopping, const int32_t* eos_ids, int n_eos,
+                      int max_new, int prompt_tok_len, void* stream);
+/* One beam step on rank-local logits fp32 [rows, t_vocab].  The first call takes the prefill's logits (rows == b): it selects, then forks
+ * prompt i's cache row into rows i*N .. i*N+N-1 (host and device lengths included).  Every later call takes the decode step's logits of
+ * the b*N beam rows: it selects, then copies the generated slots of each row whose parent is another row.  next_tokens (device int32
+ * [b*N]): the tokens to feed the next decode step.  done_word (device int32, may be NULL): 1 once every prompt's search is over -- a
+ * prompt that is over is frozen, so a step enqueued ahead of reading the word changes nothing.  Under tensor parallelism the candidates
+ * cross ranks through one fp32 all-reduce; every rank takes the same decisions.  No host sync. */
+int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* next_tokens, int32_t* done_word, void* stream);
+/* The best num_return (<= N) finished hypotheses of every prompt, best first: tokens host int32 [b*num_return][max_len] (generated ids
+ * only), lengths host int32 [b*num_return], scores host fp32 [b*num_return] (HF's sequences_scores).  Synchronises the device.  After a
+ * beam search the cache rows hold running beams, not the returned hypotheses; omchat_kv_rewind leaves the beam state alone. */
+int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t* lengths, float* scores, int max_len);
+
 /* ---- decode step as a hipGraph ------------------------------------------------------------------------------------ */
 /* With on != 0, omchat_decode_step on a TP = 1 context (b <= 32) replays one captured graph per step instead of issuing its
  * ~230 kernel launches (same kernels, same results: tests compare bit for bit).  Captured on a context-owned stream that is
@@ -405,6 +427,18 @@ int omchat_op_argmax(const float* logits, int b, int V, int32_t* out, void* stre
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */
 int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
                      const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream);
+/* context-free beam step (test hook of omchat_beam_step's selection, TP = 1): logits fp32 [rows, V] (rows = b at t = 0, else b*N), step t
+ * of max_new; state: device int32 [omchat_beam_state_words(b, N, max_new)] carried from call to call (initialised by the t = 0 call).
+ * Outputs device int32: tokens [b*N], parents [b*N] (rows; a row's own index at t = 0 and for frozen prompts), done_word [1]. */
+size_t omchat_beam_state_words(int b, int N, int max_new);
+int omchat_op_beam_select(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty, int early_stopping,
+                          const int32_t* eos_ids, int n_eos, int32_t* state, int32_t* tokens, int32_t* parents, int32_t* done_word, void* stream);
+/* KV-cache rows between sequences (test hook of the beam step's gather): k / v 16-bit [layers][rows_cap][kvh][max_seq][128]; k8 / v8 (e4m3
+ * bytes, same layout) and ks / vs (fp32 [layers][rows_cap][kvh][max_seq]) or NULL.  Row r in [row0, row0 + nrows) becomes a copy of
+ * parents[r] (device int32, values in [row0, row0 + nrows)) over slots [lo, hi), for any parent map (cycles, repeats); parents == NULL:
+ * of row fork_src.  Synchronises. */
+int omchat_op_kv_gather(int dtype, void* k, void* v, void* k8, void* v8, float* ks, float* vs, int layers, int rows_cap, int kvh, int max_seq,
+                        const int32_t* parents, int row0, int nrows, int fork_src, int lo, int hi, void* stream);
 int omchat_op_fill_uniform(int dtype, void* dst, int64_t n, uint64_t key, float scale, float offset, void* stream);
 
 /* ---- image front-end: process_anyres_image (omchat/mm_utils.py:119-158) + CLIPImageProcessor ---- */

@@ -53,6 +53,9 @@ _SIGS = {
     "omchat_sample": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
+    "omchat_beam_begin": (_i, [_vp, _i, _i, _f, _i, _vp, _i, _i, _i, _vp]),
+    "omchat_beam_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "omchat_beam_result": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
     "omchat_decode_step_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_masked_decode_begin": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "omchat_decode_step_masked_next": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -105,6 +108,9 @@ _SIGS = {
     "omchat_op_rope_kv_q8": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_argmax": (_i, [_vp, _i, _i, _vp, _vp]),
     "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
+    "omchat_beam_state_words": (_sz, [_i, _i, _i]),
+    "omchat_op_beam_select": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "omchat_op_kv_gather": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "omchat_op_fill_uniform": (_i, [_i, _vp, _i64, _u64, _f, _f, _vp]),
     "omchat_preproc_plan": (_i, [_i, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "omchat_preproc_anyres": (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

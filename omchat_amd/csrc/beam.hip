@@ -1,0 +1,394 @@
+// Beam search on the device for generate(num_beams=N): HF's _beam_search step -- log_softmax, accumulated scores,
+// top (max(2, 1 + n_eos) * N) continuations over N x V, finished set with the length penalty and the early-stop heuristic -- without a sort
+// of the vocabulary and without a host sync per step.  tests/beam_ref.py is the CPU restatement.
+//
+// One pass over the logits (beam_select_kernel, one workgroup per (row, vocabulary slice)): the slice's max, the fixed-point sum of
+// exp(x - max) (integers, so the sum does not depend on order) and the slice's top K raw (value, global index) pairs.  The vocabulary is cut
+// into the same slices at every TP degree (beam_slices), so a rank owns whole slices and the exchange table -- zero-filled, every rank
+// writes its own slices, one fp32 all-reduce -- holds the same numbers as a TP = 1 run.  x -> fl(fl(x - max) - lse) + r is monotone in
+// x within a row, so the prompt's top K accumulated candidates are inside the union of the rows' top K raw logits.
+//
+// beam_finish_kernel (one workgroup per prompt) merges the slices, scores the candidates in HF's order of fp32 operations and updates the
+// running beams, the finished set and the per-prompt done flag.  A done prompt is frozen: later steps leave its state alone.
+// launch_kv_gather moves KV-cache rows (16-bit cache, and the e4m3 replica with its scales) between sequences.
+#include "kernels.h"
+#include <math.h>
+
+// no fused multiply-adds: the fp64 lse sum and every fp32 score are rounded after each operation, as tests/beam_ref.py rounds them
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int SEL_THREADS = 512;
+constexpr int SEL_PER = BEAM_SLICE_CAP / SEL_THREADS;     // logits per thread, held in registers between the three reductions
+constexpr double BEAM_FIX = 4294967296.0;                 // exp(x - max) in units of 2^-32
+constexpr float NEG = -1.0e9f;                            // HF's mask constant
+constexpr int FIN_THREADS = 256;
+
+__device__ __forceinline__ bool beats(float v, int g, float v2, int g2) { return v > v2 || (v == v2 && g < g2); }
+
+// ---------------------------------------------------------------------------------------------------------------- select
+// grid (slices of this rank, rows); table row: [ns][4 + 2K] fp32 = max, three 21-bit limbs of the fixed-point sum, K x (value, global index)
+__global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(const float* logits, int ld, int sl, int s0, int gbase, int ns, int K,
+                                                                  float* table) {
+  const int row = blockIdx.y, sloc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const float* x = logits + (size_t)row * ld + (size_t)sloc * sl;
+  __shared__ float red_v[SEL_THREADS / 64];
+  __shared__ int red_i[SEL_THREADS / 64];
+  __shared__ unsigned long long red_s[SEL_THREADS / 64];
+  __shared__ int winner;
+  float v[SEL_PER];
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < SEL_PER; ++k) {
+    const int i = k * SEL_THREADS + tid;
+    v[k] = i < sl ? x[i] : -INFINITY;
+    m = fmaxf(m, v[k]);
+  }
+  m = wave_max(m);
+  if (lane == 0) red_v[wid] = m;
+  __syncthreads();
+  m = red_v[0];
+#pragma unroll
+  for (int w = 1; w < SEL_THREADS / 64; ++w) m = fmaxf(m, red_v[w]);
+  // fixed-point sum: terms below 2^-33 of the max round to 0 and are skipped
+  unsigned long long acc = 0;
+#pragma unroll
+  for (int k = 0; k < SEL_PER; ++k) {
+    const double d = (double)v[k] - (double)m;
+    if (d >= -23.0) acc += (unsigned long long)llrint(exp(d) * BEAM_FIX);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) red_s[wid] = acc;
+  float* out = table + (size_t)row * ns * (4 + 2 * K) + (size_t)(s0 + sloc) * (4 + 2 * K);
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long s = 0;
+    for (int w = 0; w < SEL_THREADS / 64; ++w) s += red_s[w];
+    out[0] = m;
+    out[1] = (float)(s & 0x1FFFFFull);
+    out[2] = (float)((s >> 21) & 0x1FFFFFull);
+    out[3] = (float)(s >> 42);
+  }
+  // top K by (value desc, index asc): K rounds of a block argmax over every thread's best remaining element
+  float bv = -INFINITY; int bk = -1;
+#pragma unroll
+  for (int k = 0; k < SEL_PER; ++k)
+    if (v[k] > bv) { bv = v[k]; bk = k; }      // strict: the lowest k (lowest index) wins a tie
+  for (int r = 0; r < K; ++r) {
+    float wv = bv; int wi = bk >= 0 ? bk * SEL_THREADS + tid : 0x7FFFFFFF;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(wv, o, 64); const int oi = __shfl_xor(wi, o, 64);
+      if (beats(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+    }
+    if (lane == 0) { red_v[wid] = wv; red_i[wid] = wi; }
+    __syncthreads();
+    if (tid == 0) {
+      float gv = red_v[0]; int gi = red_i[0];
+      for (int w = 1; w < SEL_THREADS / 64; ++w)
+        if (beats(red_v[w], red_i[w], gv, gi)) { gv = red_v[w]; gi = red_i[w]; }
+      const bool ok = gi != 0x7FFFFFFF && gv != -INFINITY;
+      out[4 + 2 * r] = ok ? gv : -INFINITY;
+      out[5 + 2 * r] = ok ? (float)(gbase + sloc * sl + gi) : -1.f;
+      winner = ok ? gi : -1;
+    }
+    __syncthreads();
+    const int w = winner;
+    if (w >= 0 && (w % SEL_THREADS) == tid) {
+      const int kk = w / SEL_THREADS;
+      bv = -INFINITY; bk = -1;
+#pragma unroll
+      for (int k = 0; k < SEL_PER; ++k) {
+        if (k == kk) v[k] = -INFINITY;
+        if (v[k] > bv) { bv = v[k]; bk = k; }
+      }
+    }
+    __syncthreads();      // red_v / red_i / winner are reused by the next round
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- finish
+__device__ __forceinline__ float ld_f(const int* p) { return __int_as_float(*p); }
+__device__ __forceinline__ void st_f(int* p, float v) { *p = __float_as_int(v); }
+
+__global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(BeamFinishArgs a) {
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int N = a.N, K = a.K, KB = a.KB, ns = a.ns, b = a.b, t = a.t;
+  const int bN = b * N;
+  const int rows_pp = t == 0 ? 1 : N;
+  const int rbase = t == 0 ? i : i * N;
+  const int TS = ns * (4 + 2 * K);
+  const bool last = t + 1 >= a.max_new;
+  int* st = a.state;
+  int* run = st + BST_RUN * bN;
+  int* fsc = st + BST_FSC * bN;
+  int* ffl = st + BST_FFL * bN;
+  int* fstp = st + BST_FSTEP * bN;
+  int* fpa = st + BST_FPAR * bN;
+  int* ftk = st + BST_FTOK * bN;
+  int* unsat_w = st + 6 * bN;
+  int* done_w = unsat_w + b;
+  int* bp = done_w + b + (size_t)t * bN * 2;
+  int* ctr = st + beam_state_words(b, N, a.max_new) - 2;     // [0] prompts done, [1] ticket of the last workgroup
+
+  __shared__ float sM[BEAM_NMAX], sL[BEAM_NMAX];
+  __shared__ float sv_acc[BEAM_NMAX * BEAM_KMAX], sv_raw[BEAM_NMAX * BEAM_KMAX];
+  __shared__ int sv_g[BEAM_NMAX * BEAM_KMAX];
+  __shared__ float c_acc[BEAM_KMAX], c_raw[BEAM_KMAX], c_trl[BEAM_KMAX], c_s[BEAM_KMAX];
+  __shared__ int c_row[BEAM_KMAX], c_tok[BEAM_KMAX], c_hit[BEAM_KMAX];
+  __shared__ float o_sc[BEAM_NMAX]; __shared__ int o_fl[BEAM_NMAX], o_st[BEAM_NMAX], o_pa[BEAM_NMAX], o_tk[BEAM_NMAX];
+  __shared__ int new_run[BEAM_NMAX], new_fin[BEAM_NMAX];
+  __shared__ int s_unsat, s_done_old;
+
+  if (tid == 0) {
+    s_unsat = t == 0 ? 1 : unsat_w[i];
+    s_done_old = t == 0 ? 0 : done_w[i];
+  }
+  if (tid < N) {      // the finished set before this step (HF's initial one at step 0)
+    const int r = i * N + tid;
+    o_sc[tid] = t == 0 ? NEG : ld_f(fsc + r);
+    o_fl[tid] = t == 0 ? 0 : ffl[r];
+    o_st[tid] = t == 0 ? -1 : fstp[r];
+    o_pa[tid] = t == 0 ? 0 : fpa[r];
+    o_tk[tid] = t == 0 ? 0 : ftk[r];
+    new_run[tid] = 0; new_fin[tid] = 0;      // (ranks form a permutation; this only keeps NaN logits inside the arrays)
+  }
+  __syncthreads();
+  const bool frozen = s_done_old != 0;
+  if (!frozen) {
+    // lse of every row: the slices' sums rebased to the row max in fp64, in slice order
+    if (tid < rows_pp) {
+      const float* tr = a.table + (size_t)(rbase + tid) * TS;
+      float M = -INFINITY;
+      for (int s = 0; s < ns; ++s) M = fmaxf(M, tr[s * (4 + 2 * K)]);
+      double S = 0.0;
+      for (int s = 0; s < ns; ++s) {
+        const float* e = tr + s * (4 + 2 * K);
+        const unsigned long long q = (unsigned long long)e[1] + ((unsigned long long)e[2] << 21) + ((unsigned long long)e[3] << 42);
+        S += ldexp((double)q, -32) * exp((double)e[0] - (double)M);
+      }
+      sM[tid] = M;
+      sL[tid] = (float)log(S);
+    }
+    __syncthreads();
+    // a row with fewer than K finite logits leaves survivor slots unwritten: they start as -inf with distinct out-of-vocabulary ids, so
+    // the ranking below stays a permutation (such a row is outside the contract: model logits are finite)
+    for (int e = tid; e < rows_pp * K; e += FIN_THREADS) { sv_acc[e] = -INFINITY; sv_raw[e] = -INFINITY; sv_g[e] = a.V_total + e; }
+    __syncthreads();
+    // each row's top K over its slices' sorted lists: rank = position in its own list + entries of the other lists that beat it
+    const int ncand = rows_pp * ns * K;
+    for (int c = tid; c < ncand; c += FIN_THREADS) {
+      const int j = c / (ns * K), s = (c / K) % ns, p = c % K;
+      const float* tr = a.table + (size_t)(rbase + j) * TS;
+      const float v = tr[s * (4 + 2 * K) + 4 + 2 * p];
+      const int g = (int)tr[s * (4 + 2 * K) + 5 + 2 * p];
+      if (g < 0) continue;
+      int rank = p;
+      for (int s2 = 0; s2 < ns && rank < K; ++s2) {
+        if (s2 == s) continue;
+        const float* l2 = tr + s2 * (4 + 2 * K) + 4;
+        for (int q = 0; q < K; ++q) {
+          const int g2 = (int)l2[2 * q + 1];
+          if (g2 < 0 || !beats(l2[2 * q], g2, v, g)) break;
+          ++rank;
+        }
+      }
+      if (rank < K) {
+        const float r0 = t == 0 ? 0.f : ld_f(run + i * N + j);
+        // HF: log_softmax = (x - max) - log(sum), then + running score, all fp32
+        const float lp = __fsub_rn(__fsub_rn(v, sM[j]), sL[j]);
+        sv_acc[j * K + rank] = __fadd_rn(lp, r0);
+        sv_raw[j * K + rank] = v;
+        sv_g[j * K + rank] = g;
+      }
+    }
+    __syncthreads();
+    // the prompt's top KB by (accumulated desc, raw desc, flat index asc)
+    for (int e = tid; e < rows_pp * K; e += FIN_THREADS) {
+      const float ea = sv_acc[e], er = sv_raw[e];
+      const int ej = e / K, eg = sv_g[e];
+      int rank = 0;
+      for (int f = 0; f < rows_pp * K; ++f) {
+        const float fa = sv_acc[f], fr = sv_raw[f];
+        const int fj = f / K, fg = sv_g[f];
+        rank += fa > ea || (fa == ea && (fr > er || (fr == er && (fj < ej || (fj == ej && fg < eg)))));
+      }
+      if (rank < KB) { c_acc[rank] = ea; c_raw[rank] = er; c_row[rank] = ej; c_tok[rank] = eg; }
+    }
+    __syncthreads();
+    const bool full = a.es == 1 && [&] { for (int j = 0; j < N; ++j) if (!o_fl[j]) return false; return true; }();
+    if (tid < KB) {
+      bool hit = last;
+      for (int q = 0; q < a.n_eos; ++q) hit = hit || c_tok[tid] == a.eos[q];
+      c_hit[tid] = hit;
+      c_trl[tid] = hit ? __fadd_rn(c_acc[tid], NEG) : c_acc[tid];
+      // _update_finished_beams: / generated_len ** length_penalty, then the three -1e9 masks in HF's order
+      float s = __fdiv_rn(c_acc[tid], a.dn[t + 1]);
+      if (full) s = __fadd_rn(s, NEG);
+      if (!s_unsat) s = __fadd_rn(s, NEG);
+      if (!(hit && tid < N)) s = __fadd_rn(s, NEG);
+      c_s[tid] = s;
+    }
+    __syncthreads();
+    if (tid < KB) {       // the best N non-finished continuations (ties: lower position first)
+      int rank = 0;
+      for (int k = 0; k < KB; ++k) rank += c_trl[k] > c_trl[tid] || (c_trl[k] == c_trl[tid] && k < tid);
+      if (rank < N) new_run[rank] = tid;
+    }
+    if (tid < N + KB) {   // merge [old finished | this step's candidates], keep the best N
+      const float val = tid < N ? o_sc[tid] : c_s[tid - N];
+      int rank = 0;
+      for (int e = 0; e < N + KB; ++e) {
+        const float ov = e < N ? o_sc[e] : c_s[e - N];
+        rank += ov > val || (ov == val && e < tid);
+      }
+      if (rank < N) new_fin[rank] = tid;
+    }
+    __syncthreads();
+    if (tid < N) {
+      const int r = i * N + tid, k = new_run[tid];
+      st_f(run + r, c_trl[k]);
+      a.tokens[r] = c_tok[k];
+      a.parents[r] = t == 0 ? r : i * N + c_row[k];
+      bp[2 * r] = c_row[k]; bp[2 * r + 1] = c_tok[k];
+      const int e = new_fin[tid];
+      if (e < N) {
+        st_f(fsc + r, o_sc[e]); ffl[r] = o_fl[e]; fstp[r] = o_st[e]; fpa[r] = o_pa[e]; ftk[r] = o_tk[e];
+      } else {
+        const int q = e - N;
+        st_f(fsc + r, c_s[q]); ffl[r] = c_hit[q] && q < N; fstp[r] = t; fpa[r] = c_row[q]; ftk[r] = c_tok[q];
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      // _check_early_stop_heuristic on the new running scores and finished set
+      const float hd = (a.es == 2 && a.lp_pos) ? a.dn[a.max_new] : a.dn[t + 1];
+      const float best = __fdiv_rn(c_trl[new_run[0]], hd);
+      float mn = INFINITY; bool all_fin = true;
+      for (int j = 0; j < N; ++j) { mn = fminf(mn, ld_f(fsc + i * N + j)); all_fin = all_fin && ffl[i * N + j]; }
+      bool any = false;
+      for (int j = 0; j < N; ++j) any = any || best > (ffl[i * N + j] ? mn : NEG);
+      const int unsat = s_unsat && any;
+      const int done = !unsat || (a.es == 1 && all_fin) || last;
+      unsat_w[i] = unsat;
+      done_w[i] = done;
+      if (done) atomicAdd(ctr, 1);
+    }
+  } else if (tid < N) {   // frozen: every row keeps its cache (parent = itself); the fed token is never read back
+    const int r = i * N + tid;
+    a.tokens[r] = 0;
+    a.parents[r] = r;
+    bp[2 * r] = tid; bp[2 * r + 1] = 0;
+  }
+  if (tid == 0) {
+    // the last workgroup of the step publishes "every prompt done"
+    __threadfence();
+    const int ticket = atomicAdd(ctr + 1, 1);
+    if ((ticket + 1) % b == 0) {
+      __threadfence();
+      const int n = atomicAdd(ctr, 0);
+      if (a.done_word) *a.done_word = n >= b ? 1 : 0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- KV gather
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void copy_nt(char* dst, const char* src, int n16) {
+  const u32x4* s = (const u32x4*)src;
+  u32x4* d = (u32x4*)dst;
+  for (int i = threadIdx.x; i < n16; i += blockDim.x) __builtin_nontemporal_store(__builtin_nontemporal_load(s + i), d + i);
+}
+__device__ __forceinline__ void copy_f32(float* dst, const float* src, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
+// phase 0: rows [row0, row0 + nrows) <- fork_src (parents == nullptr) or <- parents[r], straight from the cache (no row is both read and
+// written); phase 1: rows that are both a destination and some other row's parent -> stash; phase 2: every destination <- its parent,
+// from the stash when the parent is itself a destination
+__global__ __launch_bounds__(256) void kv_gather_kernel(KvGatherArgs a, const int* parents, int row0, int nrows, int fork_src, int lo, int hi,
+                                                        int phase) {
+  const int r = row0 + blockIdx.x, h = blockIdx.y, l = blockIdx.z;
+  int src_row, dst_row;
+  bool from_stash = false, to_stash = false;
+  if (phase == 1) {
+    if (parents[r] == r) return;
+    bool needed = false;
+    for (int q = row0; q < row0 + nrows; ++q) needed = needed || (q != r && parents[q] == r);
+    if (!needed) return;
+    src_row = r; dst_row = r; to_stash = true;
+  } else {
+    const int p = parents ? parents[r] : fork_src;
+    if (p == r) return;
+    src_row = p; dst_row = r;
+    from_stash = phase == 2 && parents[p] != p;
+  }
+  const int n = hi - lo;
+  const int64_t c_src = (((int64_t)l * a.rows_cap + src_row) * a.kvh + h) * a.max_seq + lo;      // slot index in the cache
+  const int64_t c_dst = (((int64_t)l * a.rows_cap + dst_row) * a.kvh + h) * a.max_seq + lo;
+  const int64_t s_idx = (((int64_t)l * a.st_rows + (to_stash ? dst_row : src_row)) * a.kvh + h) * a.st_slots;      // slot index in the stash
+  const int64_t src = from_stash ? s_idx : c_src, dst = to_stash ? s_idx : c_dst;
+  const char* k_src = from_stash ? a.sk : a.k;  char* k_dst = to_stash ? a.sk : a.k;
+  const char* v_src = from_stash ? a.sv : a.v;  char* v_dst = to_stash ? a.sv : a.v;
+  copy_nt(k_dst + dst * 256, k_src + src * 256, n * 16);
+  copy_nt(v_dst + dst * 256, v_src + src * 256, n * 16);
+  if (a.k8) {
+    const char* k8s = from_stash ? a.sk8 : a.k8;  char* k8d = to_stash ? a.sk8 : a.k8;
+    const char* v8s = from_stash ? a.sv8 : a.v8;  char* v8d = to_stash ? a.sv8 : a.v8;
+    copy_nt(k8d + dst * 128, k8s + src * 128, n * 8);
+    copy_nt(v8d + dst * 128, v8s + src * 128, n * 8);
+    copy_f32((to_stash ? a.sks : a.ks) + dst, (from_stash ? a.sks : a.ks) + src, n);
+    copy_f32((to_stash ? a.svs : a.vs) + dst, (from_stash ? a.svs : a.vs) + src, n);
+  }
+}
+
+}  // namespace
+
+int beam_slices(int V_total, int tp) {
+  if (V_total < 1 || tp < 1) return -1;
+  for (int n = 1; n <= V_total && n <= BEAM_NS_MAX; ++n) {
+    if (V_total % n || V_total / n > BEAM_SLICE_CAP) continue;
+    if (V_total % 8 == 0 ? n % 8 != 0 : n % tp != 0) continue;
+    if (n % tp) continue;
+    return n;
+  }
+  return -1;
+}
+
+int launch_beam_select(const float* logits, int ld, int rows, int V_local, int rank, int tp, int ns, int K, float* table, hipStream_t s) {
+  OM_CHECK(ns >= 1 && ns % tp == 0 && K >= 1 && K <= BEAM_KMAX && rows >= 1, "beam select: bad geometry");
+  const int nl = ns / tp, sl = V_local / nl;
+  OM_CHECK(sl * nl == V_local && sl <= BEAM_SLICE_CAP, "beam select: the rank's vocabulary is not whole slices");
+  hipLaunchKernelGGL(beam_select_kernel, dim3(nl, rows), dim3(SEL_THREADS), 0, s, logits, ld, sl, rank * nl, rank * V_local, ns, K, table);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_beam_finish(const BeamFinishArgs& a, hipStream_t s) {
+  OM_CHECK(a.b >= 1 && a.N >= 1 && a.N <= BEAM_NMAX && a.KB <= BEAM_KMAX && a.K == a.KB && a.n_eos <= BEAM_EOS_MAX &&
+           a.ns <= BEAM_NS_MAX && a.t >= 0 && a.t < a.max_new, "beam finish: bad geometry");
+  if (a.t == 0) OM_HIP(hipMemsetAsync(a.state + beam_state_words(a.b, a.N, a.max_new) - 2, 0, 8, s));
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(a.b), dim3(FIN_THREADS), 0, s, a);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_kv_gather(const KvGatherArgs& a, const int* parents, int row0, int nrows, int fork_src, int lo, int hi, hipStream_t s) {
+  OM_CHECK(row0 >= 0 && nrows >= 1 && row0 + nrows <= a.rows_cap && lo >= 0 && hi <= a.max_seq, "kv gather: rows / slots out of range");
+  if (hi <= lo) return 0;
+  if (!parents) {
+    OM_CHECK(fork_src >= 0 && fork_src < a.rows_cap, "kv gather: fork source out of range");
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(nrows, a.kvh, a.layers), dim3(256), 0, s, a, parents, row0, nrows, fork_src, lo, hi, 0);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
+  OM_CHECK(a.sk && a.sv && row0 + nrows <= a.st_rows && hi - lo <= a.st_slots && (!a.k8 || (a.sk8 && a.sv8 && a.sks && a.svs)),
+           "kv gather: stash too small");
+  hipLaunchKernelGGL(kv_gather_kernel, dim3(nrows, a.kvh, a.layers), dim3(256), 0, s, a, parents, row0, nrows, -1, lo, hi, 1);
+  hipLaunchKernelGGL(kv_gather_kernel, dim3(nrows, a.kvh, a.layers), dim3(256), 0, s, a, parents, row0, nrows, -1, lo, hi, 2);
+  OM_LAUNCH_CHECK();
+  return 0;
+}

@@ -356,6 +356,71 @@ extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed
   return rc;
 }
 
+extern "C" size_t omchat_beam_state_words(int b, int N, int max_new) { return beam_state_words(b, N, max_new); }
+
+extern "C" int omchat_op_beam_select(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty,
+                                     int early_stopping, const int32_t* eos_ids, int n_eos, int32_t* state, int32_t* tokens, int32_t* parents,
+                                     int32_t* done_word, void* stream) {
+  OM_CHECK(logits && state && tokens && parents && b >= 1 && N >= 2 && N <= BEAM_NMAX, "bad argument");
+  OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "at most 8 eos ids");
+  const int KB = std::max(2, 1 + n_eos) * N;
+  OM_CHECK(KB <= BEAM_KMAX && V >= KB, "max(2, 1 + n_eos) * N must not exceed 32 (nor V)");
+  OM_CHECK(t >= 0 && t < max_new && rows == (t == 0 ? b : b * N), "rows = b at t = 0, b * N afterwards");
+  OM_CHECK(early_stopping >= 0 && early_stopping <= 2, "early_stopping 0, 1 or 2");
+  const int ns = beam_slices(V, 1);
+  OM_CHECK(ns >= 1, "vocabulary cannot be sliced");
+  const size_t TS = (size_t)ns * (4 + 2 * KB);
+  std::vector<float> dn(max_new + 1, 1.f);
+  for (int g = 1; g <= max_new; ++g) dn[g] = (float)pow((double)g, (double)length_penalty);
+  char* mem = nullptr;
+  OM_HIP(hipMalloc(&mem, rows * TS * 4 + dn.size() * 4));
+  float* table = (float*)mem;
+  float* d_dn = table + rows * TS;
+  hipStream_t s = S(stream);
+  hipMemcpyAsync(d_dn, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s);
+  int rc = launch_beam_select(logits, V, rows, V, 0, 1, ns, KB, table, s);
+  if (!rc) {
+    BeamFinishArgs a;
+    a.table = table; a.ns = ns; a.K = a.KB = KB; a.V_total = V;
+    a.b = b; a.N = N; a.t = t; a.max_new = max_new; a.es = early_stopping; a.lp_pos = length_penalty > 0.f;
+    a.dn = d_dn; a.n_eos = n_eos;
+    for (int q = 0; q < n_eos; ++q) a.eos[q] = eos_ids[q];
+    a.state = state; a.tokens = tokens; a.parents = parents; a.done_word = done_word;
+    rc = launch_beam_finish(a, s);
+  }
+  hipStreamSynchronize(s);
+  hipFree(mem);
+  return rc;
+}
+
+extern "C" int omchat_op_kv_gather(int dtype, void* k, void* v, void* k8, void* v8, float* ks, float* vs, int layers, int rows_cap, int kvh,
+                                   int max_seq, const int32_t* parents, int row0, int nrows, int fork_src, int lo, int hi, void* stream) {
+  OM_CHECK(k && v && (dtype == OMCHAT_F16 || dtype == OMCHAT_BF16) && layers >= 1 && kvh >= 1 && max_seq >= 1, "bad argument");
+  OM_CHECK(row0 >= 0 && nrows >= 1 && row0 + nrows <= rows_cap && lo >= 0 && hi <= max_seq, "rows / slots out of range");
+  const bool f8 = k8 || v8 || ks || vs;
+  OM_CHECK(!f8 || (k8 && v8 && ks && vs), "e4m3 cache: k8, v8, ks and vs together");
+  hipStream_t s = S(stream);
+  KvGatherArgs g;
+  g.k = (char*)k; g.v = (char*)v; g.layers = layers; g.kvh = kvh; g.max_seq = max_seq; g.rows_cap = rows_cap;
+  if (f8) { g.k8 = (char*)k8; g.v8 = (char*)v8; g.ks = ks; g.vs = vs; }
+  char* mem = nullptr;
+  if (parents) {
+    std::vector<int32_t> hp(rows_cap);
+    OM_HIP(hipMemcpy(hp.data() + row0, parents + row0, (size_t)nrows * 4, hipMemcpyDeviceToHost));
+    for (int r = row0; r < row0 + nrows; ++r) OM_CHECK(hp[r] >= row0 && hp[r] < row0 + nrows, "parents out of [row0, row0 + nrows)");
+    const int n = std::max(hi - lo, 1);
+    const size_t slots = (size_t)layers * (row0 + nrows) * kvh * n;
+    OM_HIP(hipMalloc(&mem, slots * (f8 ? 776 : 512)));
+    g.sk = mem; g.sv = mem + slots * 256;
+    if (f8) { g.sk8 = mem + slots * 512; g.sv8 = mem + slots * 640; g.sks = (float*)(mem + slots * 768); g.svs = (float*)(mem + slots * 772); }
+    g.st_rows = row0 + nrows; g.st_slots = n;
+  }
+  int rc = launch_kv_gather(g, parents, row0, nrows, fork_src, lo, hi, s);
+  hipStreamSynchronize(s);
+  if (mem) hipFree(mem);
+  return rc;
+}
+
 extern "C" int omchat_op_fill_uniform(int dtype, void* dst, int64_t n, uint64_t key, float scale, float offset, void* stream) {
   return launch_fill_uniform(dtype, dst, n, key, scale, offset, S(stream));
 }

@@ -352,6 +352,42 @@ size_t sample_ws_bytes(int b);
 int launch_sample(const SampleArgs& a, hipStream_t s);
 // take back n picks: clears the bit the last pick set (n == 1), step -= n
 int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s);
+// beam search (beam.hip; tests/beam_ref.py restates it).  The vocabulary is cut into beam_slices(V, tp) equal slices
+// of at most BEAM_SLICE_CAP ids, the same at every TP degree; a rank owns ns / tp whole slices.  Exchange table: [rows][ns][4 + 2K] fp32.
+constexpr int BEAM_KMAX = 32;            // candidates kept per step and prompt: max(2, 1 + n_eos) * N
+constexpr int BEAM_NMAX = 16;
+constexpr int BEAM_EOS_MAX = 8;
+constexpr int BEAM_NS_MAX = 16;
+constexpr int BEAM_SLICE_CAP = 20480;
+int beam_slices(int V_total, int tp);    // -1: no slicing for this vocabulary and TP degree
+// state words (int32 / fp32 bits) of b prompts x N beams: running score, finished score / flag / step / parent beam / token ([6][b * N]),
+// early-stop flag [b], done flag [b], backpointers [max_new][b * N][2] (parent beam, token), two counters
+enum { BST_RUN = 0, BST_FSC = 1, BST_FFL = 2, BST_FSTEP = 3, BST_FPAR = 4, BST_FTOK = 5 };
+__host__ __device__ inline size_t beam_state_words(int b, int N, int max_new) {
+  return (size_t)6 * b * N + 2 * (size_t)b + (size_t)2 * max_new * b * N + 2;
+}
+struct BeamFinishArgs {
+  const float* table = nullptr; int ns = 1, K = 0, KB = 0, V_total = 0;
+  int b = 0, N = 0, t = 0, max_new = 0;
+  int es = 0; bool lp_pos = false;         // early_stopping: 0 False, 1 True, 2 "never"; length_penalty > 0
+  const float* dn = nullptr;               // [max_new + 1]: dn[g] = fp32(pow(g, length_penalty))
+  int eos[BEAM_EOS_MAX] = {0}; int n_eos = 0;
+  int* state = nullptr;                    // beam_state_words(b, N, max_new)
+  int* tokens = nullptr; int* parents = nullptr; int* done_word = nullptr;      // [b * N], [b * N] (cache rows), 1 word
+};
+int launch_beam_select(const float* logits, int ld, int rows, int V_local, int rank, int tp, int ns, int K, float* table, hipStream_t s);
+int launch_beam_finish(const BeamFinishArgs& a, hipStream_t s);
+// KV rows between sequences: cache layout [layers][rows_cap][kvh][max_seq][128] (16-bit; e4m3 bytes in the same layout, scales
+// [layers][rows_cap][kvh][max_seq]); the stash holds [layers][st_rows][kvh][st_slots] slots of the same kinds
+struct KvGatherArgs {
+  char *k = nullptr, *v = nullptr, *k8 = nullptr, *v8 = nullptr; float *ks = nullptr, *vs = nullptr;
+  int layers = 0, kvh = 0, max_seq = 0, rows_cap = 0;
+  char *sk = nullptr, *sv = nullptr, *sk8 = nullptr, *sv8 = nullptr; float *sks = nullptr, *svs = nullptr;
+  int st_rows = 0, st_slots = 0;
+};
+// row r in [row0, row0 + nrows) becomes a copy of its parent over slots [lo, hi): parents (device, values in [row0, row0 + nrows)) through
+// the stash, free of hazards for any parent map; parents == nullptr: every row <- fork_src, straight (the caller orders forks)
+int launch_kv_gather(const KvGatherArgs& a, const int* parents, int row0, int nrows, int fork_src, int lo, int hi, hipStream_t s);
 // deterministic synthetic fill (bit-identical to omchat_amd/synth.py::uniform)
 int launch_fill_uniform(int dtype, void* dst, int64_t n, uint64_t key, float scale, float offset, hipStream_t s);
 int launch_cast_f32(int dtype, const void* src, float* dst, int64_t n, hipStream_t s);

@@ -186,6 +186,22 @@ struct omchat_ctx {
   void* smp_ws = nullptr;
   uint32_t* smp_bm = nullptr; int smp_bmw = 0;
   int *smp_last = nullptr, *smp_step = nullptr;
+  // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand
+  // (state words, exchange table, length-penalty denominators, parent rows, stash of the KV gather)
+  struct Beam { bool on = false; int b = 0, N = 0, KB = 0, max_new = 0, P = 0, es = 0, ns = 1, t = 0; float lp = 1.f; std::vector<int> eos; };
+  Beam beam;
+  struct Grown { void* p = nullptr; size_t cap = 0; };
+  Grown bm_state, bm_table, bm_dn, bm_parents, bm_stash;
+  bool bm_stash8 = false;
+  std::vector<int> bm_hpos, bm_hlen;      // host sources of the fork's device lengths (alive until the next begin)
+  int grow(Grown& g, size_t n) {
+    if (n <= g.cap) return 0;
+    if (g.p) { hipFree(g.p); bytes -= g.cap; g.p = nullptr; g.cap = 0; }
+    hipError_t e = hipMalloc(&g.p, n);
+    if (e != hipSuccess) { omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e)); return 2; }
+    g.cap = n; bytes += n;
+    return 0;
+  }
   bool left_padded = false;
   // decode of a padded batch as the reference computes it (omchat_decode_step_masked): every row's cache holds pre_S + masked_steps slots;
   // dec_mode: 0 = no decode step since the prefill, 1 = omchat_decode_step (per-sequence lengths), 2 = omchat_decode_step_masked
@@ -570,6 +586,8 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
+  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash})
+    if (g->p) hipFree(g->p);
   delete ctx;
 }
 
@@ -1364,6 +1382,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     TRY(lm_head_rows(ctx, ctx->tw_last, b, logits_last, s));
   }
   ctx->kv8_valid = false;
+  ctx->beam.on = false;         // a prefill ends any beam search
   if (ctx->fp8_kv) {      // fp8 KV cache for the decode steps: quantise what this prefill wrote -- ALL S slots of every row: the masked decode
                           // of a padded batch exposes padded slots too (omchat_arch.py:61-70), and the per-sequence step overwrites them as it appends
     for (int i = 0; i < c.t_layers; ++i) {
@@ -2078,6 +2097,142 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   OM_HIP(hipMemcpyAsync(ctx->d_pos, pos.data(), (size_t)b * 4, hipMemcpyHostToDevice, s));
   OM_HIP(hipMemcpyAsync(ctx->d_len, len1.data(), (size_t)b * 4, hipMemcpyHostToDevice, s));
   OM_HIP(hipStreamSynchronize(s));     // stack vectors
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// beam search: selection and KV gather in beam.hip, the search state on the device
+// ---------------------------------------------------------------------------------------------------------
+static KvGatherArgs beam_kv_args(omchat_ctx* ctx, bool with_stash) {
+  const omchat_config& c = ctx->c;
+  KvGatherArgs g;
+  g.k = (char*)ctx->kcache; g.v = (char*)ctx->vcache;
+  g.layers = c.t_layers; g.kvh = c.t_kv_heads; g.max_seq = c.max_seq; g.rows_cap = c.max_batch;
+  const bool f8 = ctx->fp8_kv && ctx->kv8_valid;
+  if (f8) { g.k8 = (char*)ctx->k8cache; g.v8 = (char*)ctx->v8cache; g.ks = ctx->ks8; g.vs = ctx->vs8; }
+  if (with_stash) {
+    const int rows = ctx->beam.b * ctx->beam.N;
+    const size_t slots = (size_t)c.t_layers * rows * c.t_kv_heads * ctx->beam.max_new;
+    char* p = (char*)ctx->bm_stash.p;
+    g.sk = p; g.sv = p + slots * 256;
+    if (f8 && ctx->bm_stash8) {
+      g.sk8 = p + slots * 512; g.sv8 = p + slots * 640;
+      g.sks = (float*)(p + slots * 768); g.svs = (float*)(p + slots * 772);
+    }
+    g.st_rows = rows; g.st_slots = ctx->beam.max_new;
+  }
+  return g;
+}
+
+extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float length_penalty, int early_stopping, const int32_t* eos_ids,
+                                 int n_eos, int max_new, int prompt_tok_len, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  const int N = num_beams;
+  OM_CHECK(b >= 1 && N >= 2 && N <= BEAM_NMAX, "beam search: b >= 1 and 2 <= num_beams <= 16");
+  OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
+  OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
+  const int KB = std::max(2, 1 + n_eos) * N;
+  OM_CHECK(KB <= BEAM_KMAX, "beam search: max(2, 1 + n_eos) * num_beams must not exceed 32");
+  OM_CHECK(early_stopping >= 0 && early_stopping <= 2, "beam search: early_stopping 0 (False), 1 (True) or 2 (never)");
+  OM_CHECK(isfinite(length_penalty), "beam search: length_penalty must be finite");
+  OM_CHECK(max_new >= 1 && prompt_tok_len >= 1 && prompt_tok_len + max_new - 1 <= c.max_seq, "beam search: prompt + max_new exceed max_seq");
+  OM_CHECK(c.t_vocab_total >= KB, "beam search: vocabulary smaller than the candidates kept per step");
+  const int ns = beam_slices(c.t_vocab_total, ctx->tp_size);
+  OM_CHECK(ns >= 1, "beam search: the vocabulary cannot be cut into equal slices of <= 20480 ids for this TP degree");
+  OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "beam search: a left-padded or masked-decode batch (pad equal or use b = 1)");
+  omchat_ctx::Beam& B = ctx->beam;
+  B = omchat_ctx::Beam{};
+  B.b = b; B.N = N; B.KB = KB; B.max_new = max_new; B.P = prompt_tok_len; B.es = early_stopping; B.ns = ns; B.lp = length_penalty;
+  B.eos.assign(eos_ids, eos_ids + n_eos);
+  const int rows = b * N;
+  const size_t TS = (size_t)ns * (4 + 2 * KB);
+  const bool f8 = ctx->fp8_kv && ctx->kv8_valid;
+  const size_t slots = (size_t)c.t_layers * rows * c.t_kv_heads * max_new;
+  TRY(ctx->grow(ctx->bm_state, beam_state_words(b, N, max_new) * 4));
+  TRY(ctx->grow(ctx->bm_table, (rows * TS + 16) * 4));
+  TRY(ctx->grow(ctx->bm_dn, (size_t)(max_new + 1) * 4));
+  TRY(ctx->grow(ctx->bm_parents, (size_t)rows * 4));
+  TRY(ctx->grow(ctx->bm_stash, slots * (f8 ? 776 : 512)));
+  ctx->bm_stash8 = f8;
+  std::vector<float> dn(max_new + 1, 1.f);      // fp32(pow(g, length_penalty)): the Python float HF divides by, rounded as torch rounds it
+  for (int g = 1; g <= max_new; ++g) dn[g] = (float)pow((double)g, (double)length_penalty);
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemcpyAsync(ctx->bm_dn.p, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipStreamSynchronize(s));      // host vector
+  B.on = true;
+  return 0;
+}
+
+extern "C" int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* next_tokens, int32_t* done_word, void* stream) {
+  OM_CHECK(ctx && logits && next_tokens, "null argument");
+  omchat_ctx::Beam& B = ctx->beam;
+  OM_CHECK(B.on, "omchat_beam_step without omchat_beam_begin (or after a new prefill)");
+  OM_CHECK(B.t < B.max_new, "beam search: max_new steps taken");
+  OM_CHECK(rows == (B.t == 0 ? B.b : B.b * B.N), "beam step: rows = b on the prefill logits, b * num_beams afterwards");
+  const omchat_config& c = ctx->c;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t TS = (size_t)B.ns * (4 + 2 * B.KB);
+  float* table = (float*)ctx->bm_table.p;
+  if (ctx->tp_size > 1) OM_HIP(hipMemsetAsync(table, 0, rows * TS * 4, s));
+  TRY(launch_beam_select(logits, c.t_vocab, rows, c.t_vocab, ctx->tp_rank, ctx->tp_size, B.ns, B.KB, table, s));
+  if (ctx->tp_size > 1) TRY(ctx->allreduce_f32(table, rows * TS, s));
+  BeamFinishArgs a;
+  a.table = table; a.ns = B.ns; a.K = a.KB = B.KB; a.V_total = c.t_vocab_total;
+  a.b = B.b; a.N = B.N; a.t = B.t; a.max_new = B.max_new; a.es = B.es; a.lp_pos = B.lp > 0.f;
+  a.dn = (const float*)ctx->bm_dn.p;
+  a.n_eos = (int)B.eos.size();
+  for (int q = 0; q < a.n_eos; ++q) a.eos[q] = B.eos[q];
+  a.state = (int*)ctx->bm_state.p; a.tokens = next_tokens; a.parents = (int*)ctx->bm_parents.p; a.done_word = done_word;
+  TRY(launch_beam_finish(a, s));
+  const int bN = B.b * B.N;
+  if (B.t == 0) {
+    // fork: prompt i's row -> rows i*N .. i*N+N-1, last prompt first (its target rows lie above every source row not yet read)
+    const KvGatherArgs g = beam_kv_args(ctx, false);
+    for (int i = B.b - 1; i >= 0; --i) TRY(launch_kv_gather(g, nullptr, i * B.N, B.N, i, 0, B.P, s));
+    ctx->bm_hpos.assign(bN, B.P);
+    ctx->bm_hlen.assign(bN, B.P + 1);
+    for (int r = 0; r < bN; ++r) ctx->h_len[r] = B.P;
+    OM_HIP(hipMemcpyAsync(ctx->d_pos, ctx->bm_hpos.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
+    OM_HIP(hipMemcpyAsync(ctx->d_len, ctx->bm_hlen.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
+  } else {
+    const int L = ctx->h_len[0];
+    for (int r = 1; r < bN; ++r) OM_CHECK(ctx->h_len[r] == L, "beam step: the beam rows differ in length");
+    if (L > B.P) TRY(launch_kv_gather(beam_kv_args(ctx, true), (const int*)ctx->bm_parents.p, 0, bN, -1, B.P, L, s));
+  }
+  B.t++;
+  return 0;
+}
+
+extern "C" int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t* lengths, float* scores, int max_len) {
+  OM_CHECK(ctx && tokens && lengths && scores, "null argument");
+  const omchat_ctx::Beam& B = ctx->beam;
+  OM_CHECK(B.b > 0 && B.t > 0, "omchat_beam_result before a beam step");
+  OM_CHECK(num_return >= 1 && num_return <= B.N, "num_return_sequences must be in [1, num_beams]");
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<int> st(beam_state_words(B.b, B.N, B.max_new));
+  OM_HIP(hipMemcpy(st.data(), ctx->bm_state.p, st.size() * 4, hipMemcpyDeviceToHost));
+  const int bN = B.b * B.N;
+  const int* bp = st.data() + 6 * bN + 2 * B.b;
+  for (int i = 0; i < B.b; ++i)
+    for (int q = 0; q < num_return; ++q) {
+      const int e = i * B.N + q, o = i * num_return + q;
+      float sc; memcpy(&sc, &st[BST_FSC * bN + e], 4);
+      scores[o] = sc;
+      const int step = st[BST_FSTEP * bN + e];
+      const int n = step + 1;
+      OM_CHECK(n <= max_len, "beam result: max_len too small");
+      lengths[o] = n;
+      if (n == 0) continue;
+      tokens[(size_t)o * max_len + step] = st[BST_FTOK * bN + e];
+      int beam = st[BST_FPAR * bN + e];
+      for (int u = step - 1; u >= 0; --u) {
+        const int* rec = bp + ((size_t)u * bN + i * B.N + beam) * 2;
+        tokens[(size_t)o * max_len + u] = rec[1];
+        beam = rec[0];
+      }
+    }
   return 0;
 }
 

@@ -373,3 +373,34 @@ class Engine:
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=self.device)
         check(self.lib.omchat_sample(self.h, ptr(logits), logits.shape[0], ptr(out), cur_stream()))
         return out
+
+    # ------------------------------------------------------------------ beam search (include/omchat_hip.h: omchat_beam_begin)
+    def beam_begin(self, b, num_beams, length_penalty=1.0, early_stopping=False, eos=(), max_new=20, prompt_len=None):
+        """after the prefill of b equal-length prompts: HF's _beam_search state on the device.  early_stopping: False, True or "never"."""
+        torch = _torch()
+        es = 2 if early_stopping == "never" else int(bool(early_stopping))
+        ev = torch.tensor(list(eos) or [0], dtype=torch.int32)
+        P = prompt_len if prompt_len is not None else self.kv_lengths(b)[0]
+        check(self.lib.omchat_beam_begin(self.h, int(b), int(num_beams), float(length_penalty), es, ptr(ev), len(eos), int(max_new), int(P),
+                                         cur_stream()))
+        self._beam = (int(b), int(num_beams), int(max_new))
+        self.beam_done = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def beam_step(self, logits):
+        """one beam step on rank-local logits [rows, V / tp] (the prefill's b rows first, then the b * num_beams beam rows) -> the next
+        tokens of the b * num_beams rows (int32, device); self.beam_done turns 1 once every prompt is done"""
+        torch = _torch()
+        b, N, _ = self._beam
+        out = torch.empty(b * N, dtype=torch.int32, device=self.device)
+        check(self.lib.omchat_beam_step(self.h, ptr(logits), logits.shape[0], ptr(out), ptr(self.beam_done), cur_stream()))
+        return out
+
+    def beam_result(self, num_return=1):
+        """-> (list of b * num_return generated id lists, best first per prompt, scores fp32 numpy [b * num_return])"""
+        torch = _torch()
+        b, N, max_new = self._beam
+        toks = torch.zeros(b * num_return, max_new, dtype=torch.int32)
+        lens = torch.zeros(b * num_return, dtype=torch.int32)
+        scores = torch.zeros(b * num_return, dtype=torch.float32)
+        check(self.lib.omchat_beam_result(self.h, int(num_return), ptr(toks), ptr(lens), ptr(scores), max_new))
+        return [toks[o, :int(lens[o])].tolist() for o in range(b * num_return)], scores.numpy()

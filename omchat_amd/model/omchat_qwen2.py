@@ -109,7 +109,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         # sampling defaults as HF's GenerationConfig (temperature 1, top_k 50, top_p 1, no penalty); `seed` is this project's: the on-device
         # sampler draws from an explicit seed, never from torch's global RNG state
         self.generation_config = _GenerationConfig(pad_token_id=None, eos_token_id=None, max_new_tokens=None, do_sample=False, temperature=1.0,
-                                                   top_k=50, top_p=1.0, repetition_penalty=1.0, seed=None)
+                                                   top_k=50, top_p=1.0, repetition_penalty=1.0, seed=None, num_beams=1,
+                                                   length_penalty=1.0, early_stopping=False, num_return_sequences=1)
         self._last_lengths = None
         self.device = engine.device
         self.dtype = engine.torch_dtype
@@ -235,13 +236,20 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
-                 repetition_penalty=None, seed=None, generator=None, **kwargs):
+                 repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
+                 num_return_sequences=None, return_dict_in_generate=False, **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
         and the generated ones, temperature, top-k, top-p -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
+        gc = self.generation_config
+        nb = int(num_beams if num_beams is not None else (getattr(gc, "num_beams", None) or 1))
+        if nb > 1:
+            return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
+                                       stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
+                                       return_dict_in_generate)
         smp = self._sampling_params(temperature, top_k, top_p, repetition_penalty, seed, generator) if do_sample else None
         if max_new_tokens is None:
             max_new_tokens = self.generation_config.max_new_tokens or 20
@@ -324,3 +332,108 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if streamer is not None:
             streamer.end()
         return torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+
+    def _spliced_lengths(self, ids, images):
+        """the rows' lengths after the image-token splice, from the host-side plan alone (omchat_splice_plan: integers, nothing enqueued)"""
+        from .. import _lib
+        ids = ids.to(torch.int64).contiguous()
+        b, T = ids.shape
+        lens = torch.zeros(b, dtype=torch.int32)
+        S = _lib.C.c_int(0)
+        _lib.check(self.engine.lib.omchat_splice_plan(_lib.ptr(ids), None, b, T, self.engine.ntok, max(_n_tiles(images), int((ids == -200).sum())),
+                                                      0, -1, None, _lib.ptr(lens), _lib.C.byref(S), 0))
+        return [int(x) for x in lens]
+
+    def _beam_generate(self, input_ids, images, attention_mask, N, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
+                       stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences, return_dict_in_generate):
+        """HF's _beam_search on the device (include/omchat_hip.h: omchat_beam_begin) with the one-step-ahead loop of
+        the greedy path: each prompt is prefilled once and its cache row forked into its N beam rows.  Every refusal is raised before any
+        work is enqueued."""
+        gc = self.generation_config
+        pick = lambda v, name, d: v if v is not None else (getattr(gc, name, None) if getattr(gc, name, None) is not None else d)
+        lp = float(pick(length_penalty, "length_penalty", 1.0))
+        es = pick(early_stopping, "early_stopping", False)
+        nret = int(pick(num_return_sequences, "num_return_sequences", 1))
+        rp = pick(repetition_penalty, "repetition_penalty", 1.0)
+        if do_sample:
+            raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not implemented: use do_sample=False")
+        if streamer is not None:
+            raise ValueError("`streamer` cannot be used with beam search (yet!). Make sure that `num_beams` is set to 1.")
+        if stopping_criteria:
+            raise NotImplementedError("custom stopping_criteria are not implemented under beam search")
+        if float(rp) != 1.0:
+            raise NotImplementedError("repetition_penalty is not implemented under beam search")
+        if es not in (True, False, "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es}.")
+        if nret > N:
+            raise ValueError(f"`num_return_sequences` ({nret}) has to be smaller or equal to `num_beams` ({N}).")
+        b = input_ids.shape[0]
+        if b * N > self.engine.c.max_batch:
+            raise ValueError(f"beam search needs b * num_beams = {b * N} cache rows: create the model with max_batch >= {b * N} "
+                             f"(it has {self.engine.c.max_batch})")
+        ids_cpu = input_ids.detach().cpu()
+        if attention_mask is not None and bool((attention_mask == 0).any()):
+            raise NotImplementedError("beam search over a padded batch (attention_mask with zeros) is not implemented: pad the prompts to "
+                                      "equal length or use b = 1")
+        if b > 1 and len(set(self._spliced_lengths(ids_cpu, images))) > 1:
+            raise NotImplementedError("beam search over rows of different spliced length is not implemented: pad the prompts to equal "
+                                      "length or use b = 1")
+        if max_new_tokens is None:
+            max_new_tokens = gc.max_new_tokens or 20
+        eos = eos_token_id if eos_token_id is not None else gc.eos_token_id
+        eos = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else ([eos] if eos is not None else []))]
+        pad = pad_token_id if pad_token_id is not None else gc.pad_token_id
+        fill = (pad or eos[0]) if eos else -1                   # HF: `pad_token_id or eos_token_id[0] if eos_token_id is not None else -1`
+        out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
+        lens = self.engine.kv_lengths(b)
+        if getattr(self, "_padded_batch", False) or len(set(lens)) > 1:
+            raise NotImplementedError("beam search over rows of different spliced length is not implemented: pad the prompts to equal "
+                                      "length or use b = 1")
+        P = lens[0]
+        room = self.engine.c.max_seq - P + 1                    # as the greedy path clamps it
+        if max_new_tokens > room:
+            import warnings
+            warnings.warn(f"max_new_tokens={max_new_tokens} clamped to {room}: KV cache capacity max_seq={self.engine.c.max_seq}")
+            max_new_tokens = max(room, 1)
+        e = self.engine
+        e.sampling_off()
+        e.beam_begin(b, N, lp, es, eos, max_new_tokens, P)
+        tok = e.beam_step(out.local_logits)
+        stage = self._stage_buffer(1, 1)
+        evt = self._stage_event
+        # one step ahead: the done word of step t - 1 goes to pinned memory behind an event, step t is enqueued, and only then the host
+        # waits; a prompt that is done is frozen, so the step enqueued after the last one changes nothing
+        for t in range(1, max_new_tokens):
+            stage[0].copy_(e.beam_done, non_blocking=True)
+            evt.record()
+            _, lg = e.decode_step(tok, want_logits=True)
+            tok = e.beam_step(lg)
+            evt.synchronize()
+            if int(stage[0, 0]):
+                break
+        hyps, scores = e.beam_result(nret)
+        gen = max(len(h) for h in hyps)
+        rows = []
+        for o, h in enumerate(hyps):
+            rows.append(torch.cat([ids_cpu[o // nret], torch.tensor(h + [fill] * (gen - len(h)), dtype=ids_cpu.dtype)]))
+        seqs = torch.stack(rows)
+        if not return_dict_in_generate:
+            return seqs
+        return BeamSearchOutput(seqs, torch.from_numpy(scores.copy()))
+
+
+def _n_tiles(images):
+    if images is None:
+        return 0
+    if isinstance(images, (list, tuple)):
+        return sum(_n_tiles(x) for x in images)
+    return int(images.shape[0]) if images.dim() == 4 else 1
+
+
+class BeamSearchOutput(dict):
+    """generate(num_beams > 1, return_dict_in_generate=True): `.sequences` [b * num_return_sequences, T + new] and `.sequences_scores`
+    (HF's GenerateBeamDecoderOnlyOutput fields of the same names; per-step `scores` are not kept)"""
+
+    def __init__(self, sequences, sequences_scores):
+        super().__init__(sequences=sequences, sequences_scores=sequences_scores)
+        self.sequences, self.sequences_scores = sequences, sequences_scores
