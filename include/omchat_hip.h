@@ -188,6 +188,23 @@ int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* ne
  * beam search the cache rows hold running beams, not the returned hypotheses; omchat_kv_rewind leaves the beam state alone. */
 int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t* lengths, float* scores, int max_len);
 
+/* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=k)) -------------------------- */
+#define OMCHAT_VERIFY_KEEP_ALL 1
+/* T >= 2 tokens of sequence 0 on top of its cache (b = 1 context state, after omchat_prefill):
+ * tokens device int32 [T] = the last emitted token (not yet cached) followed by T - 1 draft tokens.
+ * Appends T slots at L..L+T-1.
+ * logits: device fp32 [T, t_vocab] or NULL (rank-local under TP).
+ * picks: device int32 [T], the greedy pick at each position.
+ * *n_accept (host): n = the largest n <= T-1 with tokens[j+1] == picks[j] for all j < n.
+ * The cache is then trimmed to L + 1 + n slots, device and host lengths both.
+ * flags & OMCHAT_VERIFY_KEEP_ALL keeps all T slots (teacher forcing; n is still reported).
+ * Refused while sampling or a beam search is active, with the e4m3 cache, and when L + T > max_seq.
+ * T <= 16 and T * (t_heads / t_kv_heads) <= 128 (the query rows of one kv head in the attention kernel), checked before anything is enqueued.  The rows go through the batched decode path (packed-operand GEMVs: the first verify step builds the packed weight replica, as
+ * the first batched omchat_decode_step does) and the multi-query attention of omchat_op_attn_verify; never captured in the decode graph.
+ * Synchronises (the host needs n). */
+int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int T, float* logits, int32_t* picks,
+                         int* n_accept, int flags, void* stream);
+
 /* ---- decode step as a hipGraph ------------------------------------------------------------------------------------ */
 /* With on != 0, omchat_decode_step on a TP = 1 context (b <= 32) replays one captured graph per step instead of issuing its
  * ~230 kernel launches (same kernels, same results: tests compare bit for bit).  Captured on a context-owned stream that is
@@ -403,6 +420,18 @@ int omchat_op_layernorm(int dtype, const void* x, const void* w, const void* b, 
 size_t omchat_op_attn_decode_ws(int b, int Hq, int L);
 int omchat_op_attn_decode(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Hq, int Hkv,
                           int cap, int L, const int32_t* kv_len, float scale, void* ws, size_t ws_bytes, void* stream);
+/* Multi-query decode attention of the verify step: T (1..16) consecutive new tokens of ONE sequence over its cache k / v [Hkv,cap,128];
+ * query row t sits at position L + t and sees keys 0 .. L + t.  q [T,Hq,128] already rotated, the cache already holding L + T keys;
+ * out [T,Hq,128]; ws of omchat_op_attn_decode_ws(T, Hq, L + T) bytes.  T * Hq / Hkv <= 128. */
+int omchat_op_attn_verify(int dtype, const void* q, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap, int L, float scale,
+                          void* ws, size_t ws_bytes, void* stream);
+/* 64-key tiles per split that omchat_op_attn_verify takes over `keys` (= L + T) keys with Hkv kv heads on the current device */
+int omchat_op_attn_verify_tpw(int keys, int Hkv);
+/* the same with the RoPE + append fused in, as the verify step runs it: qkv [T][(Hq + 2 Hkv) * 128] raw projections (not modified);
+ * q / k rotated at positions L .. L + T - 1 (table of omchat_op_rope_kv), k / v appended to rows L .. L + T - 1 of the cache
+ * (the bytes omchat_op_rope_kv writes).  Synchronises. */
+int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,
+                                 int L, float scale, void* ws, size_t ws_bytes, void* stream);
 /* the same over an e4m3 KV cache (omchat_enable_fp8_kv; BASELINE configs[4]): k8 / v8 [b,Hkv,cap,128] OCP e4m3 bytes, ks / vs [b,Hkv,cap] fp32, one
  * scale per cached row (as omchat_op_rope_kv_q8 writes them): score = (q . k8) * ks in fp32, the value scale folded into the probabilities */
 int omchat_op_attn_decode_kv8(int dtype, const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out, int b,

@@ -56,6 +56,7 @@ _SIGS = {
     "omchat_beam_begin": (_i, [_vp, _i, _i, _f, _i, _vp, _i, _i, _i, _vp]),
     "omchat_beam_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_beam_result": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "omchat_decode_verify": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "omchat_decode_step_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_masked_decode_begin": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "omchat_decode_step_masked_next": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -102,6 +103,9 @@ _SIGS = {
     "omchat_op_layernorm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "omchat_op_attn_decode_ws": (_sz, [_i, _i, _i]),
     "omchat_op_attn_decode": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
+    "omchat_op_attn_verify_tpw": (_i, [_i, _i]),
+    "omchat_op_attn_verify": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "omchat_op_attn_verify_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_rope_kv": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),

@@ -2015,3 +2015,234 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
   OM_LAUNCH_CHECK();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Multi-query decode attention (prompt-lookup verify): T consecutive new tokens of ONE sequence over its cache.
+// The query columns of the transposed formulation are the T x n_rep rows (token t = r / n_rep, head hq0 + r % n_rep) instead of the n_rep
+// heads of one token, so a K / V tile is read from HBM once for all T tokens.  Workgroup = NW waves per (split, kv head); wave w owns query
+// rows 16 w .. 16 w + 15 (waves beyond T n_rep / 16 only load).  A split walks p.tpw tiles of 64 keys:
+//   all waves load the tile's K and V rows (whole 256-byte rows, lane (fg, fc) = chunk fc of row 4 i + fg) into two LDS images
+//   (K: chunk ^ (row & 15), V: chunk ^ ((row & 7) << 1) -- the images of attn_decode_multi_kernel<KLDS>), one barrier, then every
+//   active wave forms S^T = K Q^T with 16x16x32, the online softmax per column, and O^T += V^T P^T through ds_read_b64_tr_b16.
+// Causal bound: query row t (position L + t) sees keys <= L + t; the bound is applied only in tiles that hold keys beyond L.  A column
+// whose keys are all masked in a split leaves the neutral partial (m = NEG_BIG, l = 0, O = 0).
+// Fused RoPE + append (p.rope != null): q rows are rotated at L + t in registers; key rows >= L are taken from the raw k_new / v_new rows
+// (k rotated here: rope_chunk, rope_kv_kernel's arithmetic), and the lane group that loads such a row also appends it to the cache.  No
+// workgroup ever reads a cache slot >= L, so the appends race with nothing.
+// ---------------------------------------------------------------------------------------------------------
+template <typename T, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
+  typedef typename V8<T>::type frag_t;
+  constexpr int PER = 16 / NW;                // row groups of 4 loaded per wave and tile
+  __shared__ __attribute__((aligned(256))) char Ks[KV_TILE * 256];
+  __shared__ __attribute__((aligned(256))) char Vs[KV_TILE * 256];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fc = lane & 15, fg = lane >> 4;
+  const int split = blockIdx.x, kvh = blockIdx.y;
+  const int n_rep = p.q_heads / p.kv_heads, hq0 = kvh * n_rep;
+  const int NT = p.Sq, L = p.q_pos0, Lt = p.Skv;
+  const int R = NT * n_rep;
+  const bool active = 16 * w < R;             // wave-uniform
+  const int r = min(16 * w + fc, R - 1), t = r / n_rep, hh = r - t * n_rep;
+  const int qpos = L + t;
+  const int key_base = split * KV_TILE * p.tpw;
+  float* wsb = p.ws + ((size_t)(t * p.q_heads + hq0 + hh) * p.nsplit + split) * WS_STRIDE;
+  const bool own = active && 16 * w + fc < R;
+  const bool fuse = p.rope != nullptr;
+  const T* Kg = (const T*)p.K + kvh * p.k_sh;
+  const T* Vg = (const T*)p.V + kvh * p.v_sh;
+  const T* kn = fuse ? (const T*)p.k_new + kvh * 128 : nullptr;
+  const T* vn = fuse ? (const T*)p.v_new + kvh * 128 : nullptr;
+
+  frag_t qf[4];
+  {
+    const T* qp = (const T*)p.Q + t * p.q_sb + (hq0 + hh) * p.q_sh;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) qf[ds] = ld8<T>(qp + ds * 32 + fg * 8);
+    if (fuse) {
+      const int pt = qpos < p.rope_max ? qpos : p.rope_max - 1;
+#pragma unroll
+      for (int ds = 0; ds < 2; ++ds) {
+        const float* cs = p.rope + ((size_t)pt * 64 + ds * 32 + fg * 8) * 2;
+        const frag_t lo = qf[ds], hi = qf[ds + 2];
+        qf[ds] = rope_chunk<T>(lo, hi, cs, false);
+        qf[ds + 2] = rope_chunk<T>(hi, lo, cs, true);
+      }
+    }
+  }
+  f32x4 o[8];
+#pragma unroll
+  for (int dn = 0; dn < 8; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m_run = NEG_BIG, l_run = 0.f;
+  const int tq = fc >> 2, tp = fc & 3;
+  const int vrow_lo = 4 * fg + tq;
+  const int vswz = ((vrow_lo & 7) << 1);
+
+  for (int tt = 0; tt < p.tpw; ++tt) {
+    const int key0 = key_base + tt * KV_TILE;
+    if (key0 >= Lt) break;                    // uniform
+    // ---- K and V rows of the tile: every load in flight at once
+    frag_t kr[PER], vr[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int row = 4 * (w + NW * i) + fg, key = min(key0 + row, Lt - 1);
+      const bool fresh = fuse && key >= L;
+      kr[i] = ld8s<T>((fresh ? kn + (int64_t)(key - L) * p.new_sb : Kg + (int64_t)key * p.k_sr) + fc * 8);
+      vr[i] = ld8s<T>((fresh ? vn + (int64_t)(key - L) * p.new_sb : Vg + (int64_t)key * p.v_sr) + fc * 8);
+    }
+    if (fuse && key0 + KV_TILE > L) {         // only tiles that hold new rows (uniform)
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const int row0 = 4 * (w + NW * i);
+        if (key0 + row0 + 3 >= L && key0 + row0 < Lt) {      // uniform: some lane group of this register holds a new row
+          const int key = key0 + row0 + fg;
+          const int pk = min(key, Lt - 1), pt = pk < p.rope_max ? pk : p.rope_max - 1;
+          const float* cs = p.rope + ((size_t)pt * 64 + (fc & 7) * 8) * 2;
+          // rotate-half partner of chunk fc is chunk fc ^ 8 of the same row: lane ^ 8
+          typedef int i32x4 __attribute__((ext_vector_type(4)));
+          const i32x4 mine = __builtin_bit_cast(i32x4, kr[i]);
+          i32x4 oth;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) oth[q] = __shfl_xor(mine[q], 8, 64);
+          const frag_t rot = rope_chunk<T>(kr[i], __builtin_bit_cast(frag_t, oth), cs, fc >= 8);
+          if (key >= L && key < Lt) {
+            kr[i] = rot;
+            st8<T>((T*)p.k_cache_w + kvh * p.k_sh + (int64_t)key * p.k_sr + fc * 8, rot);
+            st8<T>((T*)p.v_cache_w + kvh * p.v_sh + (int64_t)key * p.v_sr + fc * 8, vr[i]);
+          }
+        }
+      }
+    }
+    if (tt > 0) __syncthreads();              // every wave is done with the previous tile's images
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int row = 4 * (w + NW * i) + fg;
+      *reinterpret_cast<frag_t*>(Ks + row * 256 + ((fc ^ (row & 15)) << 4)) = kr[i];
+      *reinterpret_cast<frag_t*>(Vs + row * 256 + ((fc ^ ((row & 7) << 1)) << 4)) = vr[i];
+    }
+    __syncthreads();
+    if (!active) continue;                    // uniform: loader-only wave
+    f32x4 s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      frag_t kf[4];
+#pragma unroll
+      for (int ds = 0; ds < 4; ++ds) kf[ds] = *reinterpret_cast<const frag_t*>(Ks + (kt * 16 + fc) * 256 + (((ds * 4 + fg) ^ fc) << 4));
+      s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ds = 0; ds < 4; ++ds) s[kt] = mfma16(kf[ds], qf[ds], s[kt]);
+    }
+    if (key0 + KV_TILE > L + 1) {             // the tile holds keys beyond L: causal bound per column (uniform)
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (key0 + kt * 16 + 4 * fg + q > qpos) s[kt][q] = NEG_BIG;
+    }
+    float mx = NEG_BIG;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) mx = fmaxf(mx, s[kt][q]);
+    mx = max_xor32(max_xor16(mx));
+    if (tt > 0) {
+      const float m_new = fmaxf(m_run, mx);
+      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.c);
+      l_run *= alpha;
+#pragma unroll
+      for (int dn = 0; dn < 8; ++dn) o[dn] *= alpha;
+      mx = m_new;
+    }
+    m_run = mx;
+    const float mc = mx * p.c;
+    float psum = 0.f;
+    frag_t pf[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      typedef float f32x8 __attribute__((ext_vector_type(8)));
+      f32x8 e;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float sv = s[2 * ks + (j >> 2)][j & 3];
+        e[j] = sv > NEG_BIG ? __builtin_amdgcn_exp2f(fmaf(sv, p.c, -mc)) : 0.f;      // a masked key weighs 0 (also in an all-masked column)
+        psum += e[j];
+      }
+      pf[ks] = __builtin_convertvector(e, frag_t);
+    }
+    l_run += psum;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int dn = 0; dn < 8; ++dn) {
+        const int ch = (2 * dn + (tp >> 1)) ^ vswz;
+        const char* a0 = Vs + (ks * 32 + vrow_lo) * 256 + (ch << 4) + 8 * (tp & 1);
+        const s16x4 lo = tr_read(a0);
+        const s16x4 hi = tr_read(a0 + 16 * 256);
+        typedef short s16x8 __attribute__((ext_vector_type(8)));
+        const s16x8 cat = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[dn] = mfma16(__builtin_bit_cast(frag_t, cat), pf[ks], o[dn]);
+      }
+  }
+  const float l = sum_xor32(sum_xor16(l_run));
+  if (own) {
+#pragma unroll
+    for (int dn = 0; dn < 8; ++dn) *reinterpret_cast<f32x4*>(wsb + dn * 16 + fg * 4) = o[dn];
+    if (fg == 0) { wsb[128] = m_run; wsb[129] = l; }
+  }
+}
+
+// the split-KV merge of launch_attn_decode's 16-bit path, for `rows` rows of `nsplit` partials each (every row holds L keys)
+template <typename T>
+static void launch_merge_rows(const float* ws, int nsplit, int q_heads, int rows, int L, float c, T* O, int64_t o_sb, int64_t o_sh, int pack_nb,
+                              int split_keys, hipStream_t s) {
+  const dim3 mgrid(q_heads, rows);
+  if (nsplit > g_merge_mid_min && nsplit <= 256) {
+    if (g_merge_dg == 2) hipLaunchKernelGGL((attn_merge_mid_kernel<T, 4, 2>), dim3(q_heads, rows, 2), dim3(512), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
+    else hipLaunchKernelGGL((attn_merge_mid_kernel<T, 4, 1>), mgrid, dim3(512), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
+  } else if (nsplit > 256 && nsplit <= 1024) {
+    if (g_merge_dg >= 1) hipLaunchKernelGGL((attn_merge_mid_kernel<T, 8, 4>), dim3(q_heads, rows, 4), dim3(1024), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
+    else hipLaunchKernelGGL((attn_merge_mid_kernel<T, 8, 1>), mgrid, dim3(1024), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
+  } else {
+    hipLaunchKernelGGL(attn_merge_kernel<T>, mgrid, dim3(128), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys,
+                       nullptr, 0u, 0, nullptr);
+  }
+}
+
+// tiles per split: one while the grid is short of two workgroups per CU (latency: one sequence at a few thousand keys), more for long
+// contexts so that the partials written here and read by the merge stay few
+int attn_verify_tpw(int keys, int kv_heads) {
+  return std::max(1, std::min(8, cdiv(cdiv(keys, KV_TILE) * kv_heads, 2 * device_cus())));
+}
+
+int launch_attn_verify(int dtype, const AttnVerifyArgs& a, hipStream_t s) {
+  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
+  const int n_rep = a.q_heads / a.kv_heads;
+  OM_CHECK(a.T >= 1 && a.T <= VERIFY_MAX_T && a.T * n_rep <= 128, "verify attention: 1 <= T <= 16 and T * n_rep <= 128 query rows");
+  OM_CHECK(a.L >= 0, "negative cache length");
+  OM_CHECK(!a.rope || (a.k_new && a.v_new && a.L + a.T <= a.rope_max), "fused RoPE needs k_new / v_new and a table covering L + T positions");
+  OM_CHECK(a.o_pack_nb == 0 || (a.T <= 16 * a.o_pack_nb && a.o_sh == 128), "packed output: T <= 16 * NB, head stride 128");
+  const int Lt = a.L + a.T;
+  const int tpw = attn_verify_tpw(Lt, a.kv_heads);
+  const int split_keys = KV_TILE * tpw, nsplit = cdiv(Lt, split_keys);
+  OM_CHECK(a.ws && a.ws_bytes >= attn_decode_ws_bytes(a.T, a.q_heads, Lt), "workspace too small");
+  AttnP p{};
+  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
+  p.K = a.K; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
+  p.V = a.V; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
+  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.T; p.Skv = Lt; p.q_pos0 = a.L; p.nsplit = nsplit;
+  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
+  p.rope = a.rope; p.rope_max = a.rope_max; p.k_new = a.k_new; p.v_new = a.v_new; p.new_sb = a.new_sb;
+  p.k_cache_w = a.K; p.v_cache_w = a.V;
+  const bool wide = a.T * n_rep > 64;
+  const dim3 grid(nsplit, a.kv_heads);
+  if (dtype == OMCHAT_F16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, a.T, Lt, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, s);
+  } else if (dtype == OMCHAT_BF16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, a.T, Lt, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, s);
+  } else { omchat_set_error("launch_attn_verify: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
+}

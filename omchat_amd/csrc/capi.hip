@@ -247,6 +247,42 @@ static float* rope_table_device(int max_pos, float theta) {
   return d;
 }
 
+extern "C" int omchat_op_attn_verify_tpw(int keys, int Hkv) { return attn_verify_tpw(keys, Hkv); }
+
+extern "C" int omchat_op_attn_verify(int dtype, const void* q, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap, int L, float scale,
+                                     void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(q && k && v && out && ws, "null argument");
+  OM_CHECK(Hkv > 0 && L >= 0 && L + T <= cap, "L + T exceeds the cache capacity");
+  AttnVerifyArgs a{};
+  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
+  a.K = k; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.T = T; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  return launch_attn_verify(dtype, a, S(stream));
+}
+
+extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,
+                                            int L, float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(qkv && k && v && out && ws, "null argument");
+  OM_CHECK(Hkv > 0 && L >= 0 && T >= 1 && L + T <= cap, "L + T exceeds the cache capacity");
+  float* tab = rope_table_device(L + T, theta);
+  OM_CHECK(tab, "rope table allocation failed");
+  const int64_t qkvd = (int64_t)(Hq + 2 * Hkv) * 128;
+  AttnVerifyArgs a{};
+  a.Q = qkv; a.q_sb = qkvd; a.q_sh = 128;
+  a.K = k; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.T = T; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  a.rope = tab; a.rope_max = L + T;
+  a.k_new = (const char*)qkv + (size_t)Hq * 128 * 2; a.v_new = (const char*)qkv + (size_t)(Hq + Hkv) * 128 * 2; a.new_sb = qkvd;
+  const int rc = launch_attn_verify(dtype, a, S(stream));
+  hipStreamSynchronize(S(stream));
+  hipFree(tab);
+  return rc;
+}
+
 // One decode step's attention over the e4m3 cache INCLUDING the new token's RoPE + append, as the decoder layer issues it (model.hip): qkv
 // [b][(Hq + 2 Hkv) * 128] raw projections of the new token; sequence i holds kv_len[i] keys counting the new one (NULL: L for every sequence), the
 // new row goes to position kv_len[i] - 1 of k8 / v8 / ks / vs and of the 16-bit caches k16 / v16.  Long launches take the walking form, which does

@@ -253,6 +253,27 @@ int launch_kv_quant(int dtype, const void* kc, const void* vc, void* k8, void* v
 size_t attn_decode_ws_bytes(int batch, int q_heads, int max_len);
 int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s);
 
+// Multi-query decode attention (prompt-lookup verify): T consecutive new tokens of ONE sequence on top of its L cached
+// keys.  Query row t sits at position L + t and sees keys 0 .. L + t.  Every K / V tile is read once for all T x n_rep query rows.
+// rope != null: q and the new k rows are rotated at positions L .. L + T - 1 and k / v are appended to the cache (rope_kv_kernel's bytes);
+// the raw new rows are read from k_new / v_new, never from the cache slots being written.  rope == null: Q is rotated and the cache already
+// holds L + T keys.  Partials go to ws as a batch of T rows (attn_decode_ws_bytes(T, q_heads, L + T)), merged by the decode merge.
+struct AttnVerifyArgs {
+  const void* Q; int64_t q_sb, q_sh;            // [T, q_heads, 128] (row stride q_sb)
+  void* K; int64_t k_sh, k_sr;                  // cache of the sequence [kv_heads, cap, 128]
+  void* V; int64_t v_sh, v_sr;
+  void* O; int64_t o_sb, o_sh;                  // [T, q_heads, 128]
+  int T, q_heads, kv_heads, L;
+  float scale;
+  float* ws; size_t ws_bytes;
+  const float* rope; int rope_max;              // cos/sin table [max_pos][64][2] or null
+  const void* k_new; const void* v_new; int64_t new_sb;   // raw k / v rows [T][kv_heads * 128], row stride new_sb
+  int o_pack_nb;                                // != 0: O in the packed x layout (common.h) for the batched o_proj GEMV
+};
+constexpr int VERIFY_MAX_T = 16;
+int launch_attn_verify(int dtype, const AttnVerifyArgs& a, hipStream_t s);
+int attn_verify_tpw(int keys, int kv_heads);      // 64-key tiles per split of launch_attn_verify over `keys` keys
+
 // batch-1 decode on one GPU (fused_decode.hip, round 4): launch_attn_decode + the o_proj GEMV with EPI_RESID as ONE launch, same bits.
 // x [H] is the residual stream (read, x + o_proj(attn) written in place), Wo [H][qd] row-major; ws = fused_decode_ws_bytes(q_heads) bytes
 // of zero-initialised device memory owned by the caller and used by no other launch at the same time; epoch: a value that no earlier launch

@@ -34,6 +34,15 @@ __global__ void advance_lens_kernel(int* pos, int* len, int b) {
   const int i = threadIdx.x;
   if (i < b) { pos[i] += 1; len[i] += 1; }
 }
+// prompt-lookup verify (omchat_decode_verify): n = leading drafts equal to the picks; sequence 0 keeps L + 1 + n slots (all T with keep_all)
+__global__ void verify_accept_kernel(const int32_t* tokens, const int32_t* picks, int T, int L, int keep_all, int* pos, int* len, int* n_out) {
+  if (threadIdx.x != 0) return;
+  int n = 0;
+  while (n < T - 1 && tokens[n + 1] == picks[n]) ++n;
+  const int kept = keep_all ? T : n + 1;
+  pos[0] = L + kept; len[0] = L + kept + 1;
+  n_out[0] = n;
+}
 __global__ void last_row_index_kernel(const int* len, int S, int b, int* idx) {
   const int i = threadIdx.x;
   if (i < b) idx[i] = i * S + len[i] - 1;
@@ -179,6 +188,7 @@ struct omchat_ctx {
   unsigned long long* dbg_stamps = nullptr;      // experiments build: [layers][8] clock stamps of the last decode step (tuning key 42 bit 4)
   unsigned* dyn_ctr = nullptr;      // [layers][65 * 64] work counters of the dynamic gate|up GEMV (gemv_rows_norm_dyn_kernel), zero between launches
   int *d_pos = nullptr, *d_len = nullptr, *d_idx = nullptr, *d_start = nullptr;
+  int* d_verify_n = nullptr;      // omchat_decode_verify: accepted drafts of the last verify step
   // on-device sampling (omchat_set_sampling; sample.hip): uniform parameters for the batch, per-row device step counters, the repetition
   // penalty's seen-token bitmap of this rank's vocabulary slice [max_batch][smp_bmw] and the local index of the bit each row's last pick set
   struct Sampling { bool on = false; uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f; };
@@ -469,10 +479,12 @@ int build(omchat_ctx* ctx) {
     TRY(ctx->alloc(&ctx->tw_ao, R * ctx->t_qdim * 2));
     TRY(ctx->alloc(&ctx->tw_act, R * It * 2));
     TRY(ctx->alloc(&ctx->tw_last, (size_t)c.max_batch * H * 2));
-    TRY(ctx->alloc((void**)&ctx->tw_logits, (size_t)c.max_batch * c.t_vocab * 4));
-    ctx->tw_attn_ws_bytes = attn_decode_ws_bytes(c.max_batch, c.t_heads, c.max_seq);
+    // decode-step rows: max_batch sequences, or the up to VERIFY_MAX_T tokens of a prompt-lookup verify step (omchat_decode_verify)
+    const size_t DR = std::max(c.max_batch, VERIFY_MAX_T);
+    TRY(ctx->alloc((void**)&ctx->tw_logits, DR * c.t_vocab * 4));
+    ctx->tw_attn_ws_bytes = attn_decode_ws_bytes((int)DR, c.t_heads, c.max_seq);
     TRY(ctx->alloc((void**)&ctx->tw_attn_ws, ctx->tw_attn_ws_bytes));
-    TRY(ctx->alloc((void**)&ctx->tw_part, (size_t)DEC_KS_MAX * c.max_batch * H * 4));
+    TRY(ctx->alloc((void**)&ctx->tw_part, (size_t)DEC_KS_MAX * DR * H * 4));
     if (OMCHAT_EXPERIMENTS) {
       const size_t fb = fused_decode_ws_bytes(c.t_heads);
       TRY(ctx->alloc(&ctx->fd_ws, fb));
@@ -487,8 +499,9 @@ int build(omchat_ctx* ctx) {
       TRY(ctx->alloc((void**)&ctx->dbg_stamps, (size_t)c.t_layers * 256));
       OM_HIP(hipMemset(ctx->dbg_stamps, 0, (size_t)c.t_layers * 256));
     }
-    TRY(ctx->alloc(&ctx->arg_scratch, argmax_scratch_bytes(c.max_batch)));
-    TRY(ctx->alloc((void**)&ctx->tp_table, (size_t)ctx->tp_size * c.max_batch * 2 * 4));
+    TRY(ctx->alloc(&ctx->arg_scratch, argmax_scratch_bytes((int)DR)));
+    TRY(ctx->alloc((void**)&ctx->tp_table, (size_t)ctx->tp_size * DR * 2 * 4));
+    TRY(ctx->alloc((void**)&ctx->d_verify_n, 16));
     TRY(ctx->alloc((void**)&ctx->d_pos, (size_t)c.max_batch * 4));
     TRY(ctx->alloc((void**)&ctx->d_len, (size_t)c.max_batch * 4));
     TRY(ctx->alloc((void**)&ctx->d_idx, (size_t)c.max_batch * 4));
@@ -1461,8 +1474,10 @@ static int ensure_packed(omchat_ctx* ctx) {
 // lengths from d_len).  Every argument is a context pointer or a step-invariant scalar when called for graph capture.
 // exact_len: every sequence holds exactly Lmax keys after this step (eager launches only): the attention launches then take the length
 // as a kernel argument instead of loading d_len first -- one dependent memory round trip less in two latency-bound launches per layer.
+// vL >= 0: prompt-lookup verify step (omchat_decode_verify) -- the b rows are consecutive tokens of sequence 0 at positions vL .. vL + b - 1
+// (multi-query attention, launch_attn_verify), and next_tokens receives the greedy pick of every row without moving any position.
 static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, float* logits, int32_t* next_tokens, hipStream_t s, bool allow_prof,
-                       bool exact_len = false, bool masked = false) {
+                       bool exact_len = false, bool masked = false, int vL = -1) {
   const omchat_config& c = ctx->c;
   const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
   const bool lead = ctx->tp_rank == 0;
@@ -1606,7 +1621,18 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     // bits as the three launches).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     bool ao_oproj = false;
     const bool fuse_ao = g_fuse_attn_oproj && n2 && exact_len && !f8 && a.rope && ctx->fd_ws && attn_oproj_fused_ok(a, H, qd);
-    if (fuse_ao) {
+    if (vL >= 0) {
+      AttnVerifyArgs va{};
+      va.Q = ctx->tw_qkv; va.q_sb = qkvd; va.q_sh = 128;
+      va.K = kc; va.k_sh = ctx->cache_sh(); va.k_sr = 128;
+      va.V = vc; va.v_sh = ctx->cache_sh(); va.v_sr = 128;
+      va.O = ctx->tw_ao; va.o_sb = qd; va.o_sh = 128;
+      va.T = b; va.q_heads = c.t_heads; va.kv_heads = c.t_kv_heads; va.L = vL; va.scale = a.scale;
+      va.ws = ctx->tw_attn_ws; va.ws_bytes = ctx->tw_attn_ws_bytes;
+      va.rope = ctx->rope; va.rope_max = c.max_seq; va.k_new = a.k_new; va.v_new = a.v_new; va.new_sb = qkvd;
+      va.o_pack_nb = a.o_pack_nb;
+      TRY(launch_attn_verify(ctx->dt, va, s));
+    } else if (fuse_ao) {
       FusedDecodeArgs fa{L.wo, qd, x, H, qd, ctx->fd_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       TRY(launch_attn_oproj_fused(ctx->dt, a, fa, s));
       ++ctx->n_fused_launches;
@@ -1696,7 +1722,8 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, f8, fused && pk));
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
-  if (next_tokens) TRY(pick_next(ctx, lg, b, next_tokens, s, true));
+  if (vL >= 0) TRY(greedy_pick(ctx, lg, b, next_tokens, s));
+  else if (next_tokens) TRY(pick_next(ctx, lg, b, next_tokens, s, true));
   else hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
   OM_LAUNCH_CHECK();
   return 0;
@@ -1846,6 +1873,37 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
     OM_HIP(hipStreamWaitEvent(s, ctx->graph_ev_out, 0));
   }
   for (int i = 0; i < b; ++i) ctx->h_len[i] += 1;
+  ctx->dec_mode = 1;
+  return 0;
+}
+
+// Prompt-lookup verify (include/omchat_hip.h): T tokens of sequence 0 through every layer as the batched decode step
+// runs T sequences, with the multi-query attention in place of the per-sequence one, then the acceptance of the drafts on the device.
+extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int T, float* logits, int32_t* picks, int* n_accept, int flags,
+                                    void* stream) {
+  OM_CHECK(ctx && tokens && picks && n_accept, "null argument");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(T >= 2 && T <= VERIFY_MAX_T, "2 <= T <= 16 tokens (T = 1 is omchat_decode_step)");
+  OM_CHECK(c.t_kv_heads > 0 && T * (c.t_heads / c.t_kv_heads) <= 128, "T * (q heads per kv head) must be <= 128 (the verify attention's query rows)");
+  OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "after a padded-batch prefill or masked decode steps");
+  OM_CHECK(!ctx->smp.on, "sampling is on: prompt-lookup decoding is greedy only");
+  OM_CHECK(!ctx->beam.on, "a beam search is active");
+  OM_CHECK(!(ctx->fp8_kv && ctx->kv8_valid), "the e4m3 KV cache is not implemented");
+  const int L = ctx->h_len[0];
+  OM_CHECK(L >= 1, "decode before prefill");
+  OM_CHECK(L + T <= c.max_seq, "KV cache full (max_seq)");
+  hipStream_t s = (hipStream_t)stream;
+  TRY(ensure_packed(ctx));      // the first verify step (like the first batched step) builds the packed weight replica
+  TRY(decode_body(ctx, tokens, T, L + T, logits, picks, s, false, false, false, L));
+  hipLaunchKernelGGL(verify_accept_kernel, dim3(1), dim3(64), 0, s, tokens, picks, T, L, (flags & OMCHAT_VERIFY_KEEP_ALL) ? 1 : 0,
+                     ctx->d_pos, ctx->d_len, ctx->d_verify_n);
+  OM_LAUNCH_CHECK();
+  int n = 0;
+  OM_HIP(hipMemcpyAsync(&n, ctx->d_verify_n, 4, hipMemcpyDeviceToHost, s));
+  OM_HIP(hipStreamSynchronize(s));
+  *n_accept = n;
+  ctx->h_len[0] = L + ((flags & OMCHAT_VERIFY_KEEP_ALL) ? T : n + 1);
   ctx->dec_mode = 1;
   return 0;
 }

@@ -51,6 +51,7 @@ class Engine:
             check(self.lib.omchat_ctx_create(C.byref(c), tp_rank, tp_size, comm, C.byref(h)))
         self.h = h
         self._keep = []
+        self._lookup_st = dict(verify_steps=0, drafted=0, accepted=0)
 
     def close(self):
         if getattr(self, "h", None):
@@ -269,6 +270,33 @@ class Engine:
         nxt = torch.empty(b, dtype=torch.int32, device=self.device)
         check(self.lib.omchat_decode_step(self.h, ptr(tk), b, ptr(logits), ptr(nxt), cur_stream()))
         return nxt, logits
+
+    def decode_verify(self, tokens, keep_all=False, want_logits=False):
+        """Prompt-lookup verify step (include/omchat_hip.h: omchat_decode_verify): tokens = [last emitted token, draft...] (2..16 ids) of
+        sequence 0 through the decoder at once.  -> (picks int32 [T] on the device, n accepted drafts); the cache keeps L + 1 + n slots
+        (all T with keep_all).  want_logits: -> (picks, n, rank-local logits fp32 [T, V / tp])."""
+        torch = _torch()
+        tk = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+        T = tk.shape[0]
+        logits = torch.empty(T, self.c.t_vocab, dtype=torch.float32, device=self.device) if want_logits else None
+        picks = torch.empty(T, dtype=torch.int32, device=self.device)
+        n = C.c_int(0)
+        check(self.lib.omchat_decode_verify(self.h, ptr(tk), T, ptr(logits), ptr(picks), C.byref(n), 1 if keep_all else 0, cur_stream()))
+        st = self._lookup_st
+        st["verify_steps"] += 1; st["drafted"] += T - 1; st["accepted"] += n.value
+        return (picks, n.value, logits) if want_logits else (picks, n.value)
+
+    def lookup_stats(self, reset=False):
+        """counters of decode_verify since the engine was made (or the last reset): verify steps, drafted and accepted draft tokens"""
+        out = dict(self._lookup_st)
+        if reset:
+            for key in self._lookup_st:
+                self._lookup_st[key] = 0
+        return out
+
+    def verify_max_tokens(self):
+        """the most tokens one decode_verify takes on this context: 16, fewer when T * (q heads per kv head) would exceed 128"""
+        return min(16, 128 // max(1, self.c.t_heads // max(1, self.c.t_kv_heads)))
 
     def decode_step_masked(self, tokens, position_ids, attention_mask, want_logits=False):
         """Decode step of a padded batch as the reference computes it (omchat_arch.py:61-70): `position_ids` [b] or [b, 1] and

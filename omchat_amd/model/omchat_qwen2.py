@@ -233,6 +233,31 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                                       "(or set generation_config.seed); sampling from torch's global RNG state is not implemented")
         return dict(seed=int(seed), temperature=float(T), top_k=int(k), top_p=float(p), repetition_penalty=float(rp))
 
+    def _lookup_params(self, input_ids, kwargs, do_sample, num_beams):
+        """(k, m) of prompt-lookup decoding, or None when prompt_lookup_num_tokens is not set (argument or generation_config); every
+        refusal is raised here, before any work is enqueued"""
+        from ..lookup import MAX_LOOKUP_TOKENS
+        gc = self.generation_config
+        k = kwargs.pop("prompt_lookup_num_tokens", None)
+        m = kwargs.pop("max_matching_ngram_size", None)
+        k = k if k is not None else getattr(gc, "prompt_lookup_num_tokens", None)
+        if k is None:
+            return None
+        m = m if m is not None else (getattr(gc, "max_matching_ngram_size", None) or 2)
+        if input_ids.shape[0] > 1:
+            raise ValueError("assisted generate is only supported for batch_size = 1")
+        if do_sample:
+            raise NotImplementedError("prompt-lookup decoding with do_sample=True is not implemented: it verifies greedy picks only")
+        if num_beams > 1:
+            raise NotImplementedError("prompt-lookup decoding with num_beams > 1 is not implemented")
+        if getattr(self.engine, "_fp8_kv", False):
+            raise NotImplementedError("prompt-lookup decoding over the e4m3 KV cache is not implemented: enable_fp8_kv(False)")
+        if int(k) <= 0 or int(m) <= 0:
+            raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")
+        if int(k) > MAX_LOOKUP_TOKENS:
+            raise ValueError(f"prompt_lookup_num_tokens={k} exceeds the limit of {MAX_LOOKUP_TOKENS} draft tokens per verify step")
+        return int(k), int(m)
+
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
@@ -241,11 +266,17 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
-        and the generated ones, temperature, top-k, top-p -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed."""
+        and the generated ones, temperature, top-k, top-p -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed.
+        prompt_lookup_num_tokens=k (max_matching_ngram_size=m, default 2; both also read from generation_config): HF's prompt-lookup
+        decoding for b = 1, greedy (omchat_amd/lookup.py): drafts of up to k ids copied from the prompt + generated ids are verified in
+        one verify step each.  Exactness: the verify rows go through the batched (MFMA-form) GEMVs and plain steps through the batch-1
+        whole-row forms, so a position's logits can differ in the last bits and the ids can differ from greedy only at near-ties, as in
+        HF's assisted decoding in fp16."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
         nb = int(num_beams if num_beams is not None else (getattr(gc, "num_beams", None) or 1))
+        lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -282,6 +313,14 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             import warnings
             warnings.warn(f"max_new_tokens={max_new_tokens} clamped to {room}: KV cache capacity max_seq={self.engine.c.max_seq}")
             max_new_tokens = max(room, 1)
+        if lookup is not None:
+            from ..lookup import lookup_loop
+            gen = lookup_loop(self.engine, input_ids, int(tok.view(-1)[0]), max_new_tokens, eos, lookup[0], lookup[1],
+                              self.engine.c.t_vocab_total, streamer, stopping_criteria, getattr(self, "_lookup_draft_hook", None),
+                              self.engine.verify_max_tokens())
+            if streamer is not None:
+                streamer.end()
+            return torch.cat([input_ids.cpu(), torch.tensor([gen], dtype=torch.int64)], dim=1)
         new = []
         done = torch.zeros(b, dtype=torch.bool)
         # padded batch (rows of different spliced length, or left padding): decoded as the reference does it (omchat_arch.py:61-70).  HF generate
