@@ -205,6 +205,25 @@ int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t
 int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int T, float* logits, int32_t* picks,
                          int* n_accept, int flags, void* stream);
 
+/* ---- multi-turn: continue sequence 0's cache (generate(reuse_cache=True)) ---------------------- */
+/* Sequence 0 of a context whose cache state is ONE right-aligned sequence (after omchat_prefill with b = 1, any number of omchat_decode_step /
+ * omchat_decode_verify calls, or an earlier extend).  Sets the sequence's length to keep (0 <= keep <= current length: slots >= keep are
+ * forgotten, slots < keep are not written), runs the decoder over the S_new rows embeds [S_new, t_hidden] at positions keep .. keep + S_new - 1,
+ * appends their K / V and leaves device and host lengths / positions as an omchat_prefill of keep + S_new rows would, so decode steps, verify
+ * steps, sampling and the decode graph continue unchanged.  logits_last: device fp32 [t_vocab] of the last row (or NULL); hidden_out: optional
+ * [S_new, t_hidden] post-final-norm rows (test hook).  keep = 0 issues exactly omchat_prefill's launches (same bits).  The attention takes
+ * the prefill kernel with q_pos0 = keep when the block alone fills the GPU and the split-KV block attention (omchat_op_attn_extend) otherwise
+ * (omchat_extend_attn_form).  Refused before anything is enqueued: no live sequence-0 state, a b > 1 state, a left-padded or masked-decode
+ * state, an active beam search, keep outside [0, length], S_new < 1, S_new > max_prefill_rows, keep + S_new > max_seq, the e4m3 KV cache,
+ * fp8 x fp8 prefill GEMMs and tensor-parallel contexts.  Synchronises. */
+int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_new, int keep, float* logits_last, void* hidden_out, void* stream);
+/* the attention form omchat_prefill_extend takes for S_new rows on top of keep cached ones with Hkv kv heads on the current device:
+ * 0 = the prefill kernel with q_pos0, 1 = the split-KV block attention */
+int omchat_extend_attn_form(int S_new, int keep, int Hkv);
+/* test hook: rows [pos0, pos0 + n) of sequence 0's 16-bit K (which = 0) or V (which = 1) cache of decoder layer `layer`, copied to
+ * out [t_kv_heads, n, 128] (device, context dtype) */
+int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, int n, void* out, void* stream);
+
 /* ---- decode step as a hipGraph ------------------------------------------------------------------------------------ */
 /* With on != 0, omchat_decode_step on a TP = 1 context (b <= 32) replays one captured graph per step instead of issuing its
  * ~230 kernel launches (same kernels, same results: tests compare bit for bit).  Captured on a context-owned stream that is
@@ -427,6 +446,12 @@ int omchat_op_attn_verify(int dtype, const void* q, void* k, void* v, void* out,
                           void* ws, size_t ws_bytes, void* stream);
 /* 64-key tiles per split that omchat_op_attn_verify takes over `keys` (= L + T) keys with Hkv kv heads on the current device */
 int omchat_op_attn_verify_tpw(int keys, int Hkv);
+/* Split-KV block attention of omchat_prefill_extend: Sq >= 1 new query rows of ONE sequence at positions L .. L + Sq - 1
+ * (q [Sq,Hq,128] already rotated) over k / v [Hkv,cap,128] that already hold L + Sq keys; row t sees keys 0 .. L + t.  out [Sq,Hq,128];
+ * ws of omchat_op_attn_extend_ws(Sq, Hq, Hkv, L) bytes (never more than omchat_op_attn_decode_ws(Sq, Hq, L + Sq)).  Hq / Hkv <= 8. */
+size_t omchat_op_attn_extend_ws(int Sq, int Hq, int Hkv, int L);
+int omchat_op_attn_extend(int dtype, const void* q, const void* k, const void* v, void* out, int Sq, int Hq, int Hkv, int cap, int L,
+                          float scale, void* ws, size_t ws_bytes, void* stream);
 /* the same with the RoPE + append fused in, as the verify step runs it: qkv [T][(Hq + 2 Hkv) * 128] raw projections (not modified);
  * q / k rotated at positions L .. L + T - 1 (table of omchat_op_rope_kv), k / v appended to rows L .. L + T - 1 of the cache
  * (the bytes omchat_op_rope_kv writes).  Synchronises. */

@@ -105,6 +105,11 @@ _SIGS = {
     "omchat_op_attn_decode": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_verify_tpw": (_i, [_i, _i]),
     "omchat_op_attn_verify": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "omchat_op_attn_extend_ws": (_sz, [_i, _i, _i, _i]),
+    "omchat_op_attn_extend": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "omchat_prefill_extend": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "omchat_extend_attn_form": (_i, [_i, _i, _i]),
+    "omchat_kv_read": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "omchat_op_attn_verify_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _sz, _vp]),

@@ -2030,7 +2030,10 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
 // (k rotated here: rope_chunk, rope_kv_kernel's arithmetic), and the lane group that loads such a row also appends it to the cache.  No
 // workgroup ever reads a cache slot >= L, so the appends race with nothing.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int NW>
+// EXT (split-KV block attention of omchat_prefill_extend, launch_attn_extend): blockIdx.z = chunk of 16 query tokens of
+// a block of p.Sq rows at positions p.q_pos0 ..; chunk c owns tokens 16 c .. min(16 c + 15, Sq - 1) and walks keys up to its last row's
+// bound only (a split that starts beyond it leaves the neutral partial without loading a tile).  q is rotated and the cache holds every key.
+template <typename T, int NW, bool EXT = false>
 __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   typedef typename V8<T>::type frag_t;
   constexpr int PER = 16 / NW;                // row groups of 4 loaded per wave and tile
@@ -2039,15 +2042,16 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fc = lane & 15, fg = lane >> 4;
   const int split = blockIdx.x, kvh = blockIdx.y;
   const int n_rep = p.q_heads / p.kv_heads, hq0 = kvh * n_rep;
-  const int NT = p.Sq, L = p.q_pos0, Lt = p.Skv;
+  const int t0 = EXT ? (int)blockIdx.z * 16 : 0;                  // first token of this chunk
+  const int NT = EXT ? min(16, p.Sq - t0) : p.Sq, L = p.q_pos0 + t0, Lt = EXT ? L + NT : p.Skv;
   const int R = NT * n_rep;
   const bool active = 16 * w < R;             // wave-uniform
   const int r = min(16 * w + fc, R - 1), t = r / n_rep, hh = r - t * n_rep;
   const int qpos = L + t;
   const int key_base = split * KV_TILE * p.tpw;
-  float* wsb = p.ws + ((size_t)(t * p.q_heads + hq0 + hh) * p.nsplit + split) * WS_STRIDE;
+  float* wsb = p.ws + ((size_t)((t0 + t) * p.q_heads + hq0 + hh) * p.nsplit + split) * WS_STRIDE;
   const bool own = active && 16 * w + fc < R;
-  const bool fuse = p.rope != nullptr;
+  const bool fuse = !EXT && p.rope != nullptr;
   const T* Kg = (const T*)p.K + kvh * p.k_sh;
   const T* Vg = (const T*)p.V + kvh * p.v_sh;
   const T* kn = fuse ? (const T*)p.k_new + kvh * 128 : nullptr;
@@ -2055,7 +2059,7 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
 
   frag_t qf[4];
   {
-    const T* qp = (const T*)p.Q + t * p.q_sb + (hq0 + hh) * p.q_sh;
+    const T* qp = (const T*)p.Q + (t0 + t) * p.q_sb + (hq0 + hh) * p.q_sh;
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) qf[ds] = ld8<T>(qp + ds * 32 + fg * 8);
     if (fuse) {
@@ -2243,6 +2247,54 @@ int launch_attn_verify(int dtype, const AttnVerifyArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4>), grid, dim3(256), 0, s, p);
     launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, a.T, Lt, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, s);
   } else { omchat_set_error("launch_attn_verify: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Split-KV block attention (omchat_prefill_extend): Sq new query rows of ONE sequence at positions L .. L + Sq - 1 over
+// the L + Sq keys of its cache.  attn_verify_kernel<EXT> with a third grid dimension over 16-token query chunks, the keys cut into splits
+// so that the launch is about two workgroups per CU whatever Sq is; partials [Sq][q_heads][nsplit], folded by the decode merge.
+// ---------------------------------------------------------------------------------------------------------
+static void attn_extend_plan(int Sq, int keys, int kv_heads, int* tpw, int* nsplit) {
+  const int chunks = cdiv(Sq, 16), tiles = cdiv(keys, KV_TILE);
+  const int want = std::max(1, 2 * device_cus() / std::max(1, chunks * kv_heads));      // splits for ~2 workgroups per CU
+  *tpw = std::max(1, cdiv(tiles, want));
+  *nsplit = cdiv(tiles, *tpw);
+}
+size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L) {
+  int tpw, nsplit;
+  attn_extend_plan(Sq, L + Sq, kv_heads, &tpw, &nsplit);
+  return (size_t)Sq * q_heads * nsplit * WS_STRIDE * sizeof(float);
+}
+
+int launch_attn_extend(int dtype, const AttnExtendArgs& a, hipStream_t s) {
+  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
+  const int n_rep = a.q_heads / a.kv_heads;
+  OM_CHECK(n_rep <= 8, "extend attention: at most 8 query heads per kv head (16 tokens x n_rep <= 128 query rows per workgroup)");
+  OM_CHECK(a.Sq >= 1 && a.L >= 0, "extend attention: Sq >= 1, L >= 0");
+  const int Lt = a.L + a.Sq;
+  int tpw, nsplit;
+  attn_extend_plan(a.Sq, Lt, a.kv_heads, &tpw, &nsplit);
+  OM_CHECK(a.ws && a.ws_bytes >= attn_extend_ws_bytes(a.Sq, a.q_heads, a.kv_heads, a.L), "workspace too small");
+  AttnP p{};
+  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
+  p.K = a.K; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
+  p.V = a.V; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
+  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.Sq; p.Skv = Lt; p.q_pos0 = a.L; p.nsplit = nsplit;
+  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
+  const bool wide = 16 * n_rep > 64;
+  const dim3 grid(nsplit, a.kv_heads, cdiv(a.Sq, 16));
+  const int split_keys = KV_TILE * tpw;
+  if (dtype == OMCHAT_F16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4, true>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, a.Sq, Lt, p.c, (f16*)a.O, a.o_sb, a.o_sh, 0, split_keys, s);
+  } else if (dtype == OMCHAT_BF16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, true>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, a.Sq, Lt, p.c, (bf16*)a.O, a.o_sb, a.o_sh, 0, split_keys, s);
+  } else { omchat_set_error("launch_attn_extend: bad dtype"); return 1; }
   OM_LAUNCH_CHECK();
   return 0;
 }

@@ -103,6 +103,7 @@ extern "C" int omchat_op_set_tuning(int key, int value) {
   if (key == 46) { attn_set_peel(value); return 0; }
   if (key == 47) { attn_set_kv8_tpw(value); return 0; }
   if (key == 48) { attn_set_kv8_fuse(value); return 0; }
+  if (key == 49) { model_set_extend_attn(value); return 0; }
   if (key == 38) { gemv_set_gu_rr(value); return 0; }
   if (key == 39) { gemv_set_longk_direct(value); return 0; }
   if (key == 40) { norm_set_wave(value); return 0; }
@@ -260,6 +261,21 @@ extern "C" int omchat_op_attn_verify(int dtype, const void* q, void* k, void* v,
   a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
   a.T = T; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
   return launch_attn_verify(dtype, a, S(stream));
+}
+
+extern "C" size_t omchat_op_attn_extend_ws(int Sq, int Hq, int Hkv, int L) { return attn_extend_ws_bytes(Sq, Hq, Hkv, L); }
+
+extern "C" int omchat_op_attn_extend(int dtype, const void* q, const void* k, const void* v, void* out, int Sq, int Hq, int Hkv, int cap, int L,
+                                     float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(q && k && v && out && ws, "null argument");
+  OM_CHECK(Hkv > 0 && L >= 0 && Sq >= 1 && L + Sq <= cap, "L + Sq exceeds the cache capacity");
+  AttnExtendArgs a{};
+  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
+  a.K = k; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.Sq = Sq; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  return launch_attn_extend(dtype, a, S(stream));
 }
 
 extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,

@@ -199,6 +199,7 @@ void attn_set_kg(int v);      // tuning key 36
 void attn_set_peel(int v);    // tuning key 46
 void attn_set_kv8_tpw(int v); // tuning key 47
 void attn_set_kv8_fuse(int v); // tuning key 48
+void model_set_extend_attn(int v); // tuning key 49
 bool attn_decode_kv8_fuses_rope(int batch, int kv_heads, int L, bool masked);
 void attn_set_merge_mid_min(int v);
 void attn_set_merge_dg(int v);
@@ -273,6 +274,21 @@ struct AttnVerifyArgs {
 constexpr int VERIFY_MAX_T = 16;
 int launch_attn_verify(int dtype, const AttnVerifyArgs& a, hipStream_t s);
 int attn_verify_tpw(int keys, int kv_heads);      // 64-key tiles per split of launch_attn_verify over `keys` keys
+
+// Split-KV block attention of omchat_prefill_extend: Sq new query rows of ONE sequence at positions L .. L + Sq - 1 (Q already
+// rotated) over the L + Sq keys its cache already holds; row t sees keys 0 .. L + t.  The keys are split over workgroups for any Sq (16-token
+// query chunks x key splits), partials in ws (attn_extend_ws_bytes), folded by the decode merge.  q_heads / kv_heads <= 8.
+struct AttnExtendArgs {
+  const void* Q; int64_t q_sb, q_sh;            // [Sq, q_heads, 128] (row stride q_sb)
+  const void* K; int64_t k_sh, k_sr;            // cache of the sequence [kv_heads, cap, 128]
+  const void* V; int64_t v_sh, v_sr;
+  void* O; int64_t o_sb, o_sh;                  // [Sq, q_heads, 128]
+  int Sq, q_heads, kv_heads, L;
+  float scale;
+  float* ws; size_t ws_bytes;
+};
+size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L);
+int launch_attn_extend(int dtype, const AttnExtendArgs& a, hipStream_t s);
 
 // batch-1 decode on one GPU (fused_decode.hip, round 4): launch_attn_decode + the o_proj GEMV with EPI_RESID as ONE launch, same bits.
 // x [H] is the residual stream (read, x + o_proj(attn) written in place), Wo [H][qd] row-major; ws = fused_decode_ws_bytes(q_heads) bytes

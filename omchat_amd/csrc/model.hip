@@ -43,9 +43,9 @@ __global__ void verify_accept_kernel(const int32_t* tokens, const int32_t* picks
   pos[0] = L + kept; len[0] = L + kept + 1;
   n_out[0] = n;
 }
-__global__ void last_row_index_kernel(const int* len, int S, int b, int* idx) {
+__global__ void last_row_index_kernel(const int* len, int S, int b, int* idx, int keep) {      // (keep: cached rows in front of the S prefilled ones)
   const int i = threadIdx.x;
-  if (i < b) idx[i] = i * S + len[i] - 1;
+  if (i < b) idx[i] = i * S + len[i] - keep - 1;
 }
 
 // vocab-parallel greedy: every rank contributes (max logit, global index) per sequence; summed into a zeroed table
@@ -202,6 +202,7 @@ struct omchat_ctx {
   Beam beam;
   struct Grown { void* p = nullptr; size_t cap = 0; };
   Grown bm_state, bm_table, bm_dn, bm_parents, bm_stash;
+  Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
   bool bm_stash8 = false;
   std::vector<int> bm_hpos, bm_hlen;      // host sources of the fork's device lengths (alive until the next begin)
   int grow(Grown& g, size_t n) {
@@ -599,7 +600,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash})
+  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash, &ctx->ext_ws})
     if (g->p) hipFree(g->p);
   delete ctx;
 }
@@ -1290,13 +1291,32 @@ extern "C" int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float*
   return lm_head_rows(ctx, hidden, n, logits, (hipStream_t)stream);
 }
 
+// Attention form of omchat_prefill_extend (measured with tools/bench_extend.py, LOG.md).  The prefill kernel issues
+// wgs = cdiv(S, 32) * kv_heads workgroups, each walking all keys serially: its time does not fall with S while wgs <= CUs (28 / 4 heads, bf16,
+// S = 16 .. 1024: 99 us at 3.6 k keys, 212 at 8 k, 838 at 33 k).  The split-KV block attention reads the keys once per 16-row chunk and grows
+// with S (3.6 k keys: 18 / 28 / 50 / 122 us at S = 16 / 64 / 256 / 1024; 33 k keys: 39 / 76 / 237 / 738): it wins by 2 - 20 x up to a quarter
+// of the CUs' worth of query blocks, at half of them only where the key range is long enough to amortise its partials (S = 1024: 122 vs 97 us
+// at 3.6 k keys, 217 vs 212 at 8 k, 738 vs 838 at 33 k), and loses beyond (S = 4096: 671 vs 365 us at 8 k keys).  keep = 0 is omchat_prefill's
+// launch, always.
+int g_extend_attn = -1;      // omchat_op_set_tuning key 49: attention form of omchat_prefill_extend for keep > 0: -1 = by the rule below, 0 = prefill kernel, 1 = split-KV (A/B)
+void model_set_extend_attn(int v) { g_extend_attn = v; }
+static bool extend_attn_split(int S, int keep, int kv_heads) {
+  if (keep <= 0 || kv_heads <= 0) return false;
+  if (g_extend_attn >= 0) return g_extend_attn != 0;
+  const long wgs = (long)cdiv(S, 32) * kv_heads;
+  if (4 * wgs <= device_cus()) return true;
+  return 2 * wgs <= device_cus() && keep + S >= 16384;
+}
+extern "C" int omchat_extend_attn_form(int S_new, int keep, int Hkv) { return extend_attn_split(S_new, keep, Hkv) ? 1 : 0; }
+
+// keep > 0 (omchat_prefill_extend, b = 1, right-aligned): the S rows sit at positions keep .. keep + S - 1 on top of keep cached slots
 static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const int32_t* lengths, float* logits_last, void* hidden_out,
-                        void* stream, bool left) {
+                        void* stream, bool left, int keep = 0) {
   OM_CHECK(ctx && embeds && lengths, "null argument");
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(b >= 1 && b <= c.max_batch, "batch exceeds max_batch");
-  OM_CHECK(S >= 1 && S <= c.max_seq, "sequence exceeds max_seq");
+  OM_CHECK(S >= 1 && keep + S <= c.max_seq, "sequence exceeds max_seq");
   OM_CHECK((int64_t)b * S <= c.max_prefill_rows, "b * S exceeds max_prefill_rows");
   OM_CHECK(omchat_weights_missing(ctx) == 0, std::string(omchat_last_error()));
   for (int i = 0; i < b; ++i) OM_CHECK(lengths[i] >= 1 && lengths[i] <= S, "lengths must be in [1, S]");
@@ -1305,16 +1325,18 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   const int H = c.t_hidden, It = c.t_mlp, rows = b * S, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
   const bool lead = ctx->tp_rank == 0;
 
+  const bool split_attn = extend_attn_split(S, keep, c.t_kv_heads) && c.t_heads / c.t_kv_heads <= 8;
+  if (split_attn) TRY(ctx->grow(ctx->ext_ws, attn_extend_ws_bytes(S, c.t_heads, c.t_kv_heads, keep)));      // before anything is enqueued
   std::vector<int> pos(b), len1(b), klen(b), kstart(b);
   // left-padded batch (omchat_arch.py:176-184): row i holds its n_i tokens at [S - n_i, S); the reference drops position_ids
   // (:206-207), so RoPE runs on arange(S) for every row, the padded keys are masked, and every row's last token sits at S - 1
   for (int i = 0; i < b; ++i) {
-    ctx->h_len[i] = left ? 0 : lengths[i];            // 0 = no decode after a left-padded prefill (see omchat_decode_step)
-    pos[i] = lengths[i]; len1[i] = lengths[i] + 1;
-    klen[i] = left ? S : lengths[i]; kstart[i] = left ? S - lengths[i] : 0;
+    ctx->h_len[i] = left ? 0 : keep + lengths[i];            // 0 = no decode after a left-padded prefill (see omchat_decode_step)
+    pos[i] = keep + lengths[i]; len1[i] = keep + lengths[i] + 1;
+    klen[i] = left ? S : keep + lengths[i]; kstart[i] = left ? S - lengths[i] : 0;
   }
   ctx->left_padded = left;
-  ctx->pre_S = S; ctx->pre_b = b; ctx->masked_steps = 0; ctx->dec_mode = 0; ctx->mask_on_device = false;
+  ctx->pre_S = keep + S; ctx->pre_b = b; ctx->masked_steps = 0; ctx->dec_mode = 0; ctx->mask_on_device = false;
   // d_len holds the valid key range end during prefill; switched to (len + 1, pos = len) for the decode steps at the end
   OM_HIP(hipMemcpyAsync(ctx->d_len, klen.data(), (size_t)b * 4, hipMemcpyHostToDevice, s));
   if (left) OM_HIP(hipMemcpyAsync(ctx->d_start, kstart.data(), (size_t)b * 4, hipMemcpyHostToDevice, s));
@@ -1344,17 +1366,27 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
       if (sp) TRY(gemm_after_sp(ctx, ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, rows, qkvd, H, L.bqkv, EPI_NONE, s));
       else TRY(gemm(ctx, ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, rows, qkvd, H, L.bqkv, nullptr, nullptr, 0, EPI_NONE, s));
     }
-    RopeArgs r{ctx->tw_qkv, qkvd, rows, S, c.t_heads, c.t_kv_heads, nullptr, 0, ctx->rope, c.max_seq, kc, vc, ctx->cache_sb(), ctx->cache_sh()};
+    RopeArgs r{ctx->tw_qkv, qkvd, rows, S, c.t_heads, c.t_kv_heads, nullptr, keep, ctx->rope, c.max_seq, kc, vc, ctx->cache_sb(), ctx->cache_sh()};
     TRY(launch_rope_kv(ctx->dt, r, s));
+    if (split_attn) {      // few new rows over many cached keys: the keys split across workgroups (launch_attn_extend)
+      AttnExtendArgs e{};
+      e.Q = ctx->tw_qkv; e.q_sb = qkvd; e.q_sh = 128;
+      e.K = kc; e.k_sh = ctx->cache_sh(); e.k_sr = 128;
+      e.V = vc; e.v_sh = e.k_sh; e.v_sr = 128;
+      e.O = ctx->tw_ao; e.o_sb = qd; e.o_sh = 128;
+      e.Sq = S; e.q_heads = c.t_heads; e.kv_heads = c.t_kv_heads; e.L = keep; e.scale = 0.08838834764831845f;
+      e.ws = (float*)ctx->ext_ws.p; e.ws_bytes = ctx->ext_ws.cap;
+      TRY(launch_attn_extend(ctx->dt, e, s));
+    }
     AttnArgs a{};
     a.Q = ctx->tw_qkv; a.q_sb = (int64_t)S * qkvd; a.q_sh = 128; a.q_sr = qkvd;
     a.K = kc; a.k_sb = ctx->cache_sb(); a.k_sh = ctx->cache_sh(); a.k_sr = 128;
     a.V = vc; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
     a.O = ctx->tw_ao; a.o_sb = (int64_t)S * qd; a.o_sh = 128; a.o_sr = qd;
-    a.batch = b; a.q_heads = c.t_heads; a.kv_heads = c.t_kv_heads; a.Sq = S; a.Skv = S; a.kv_len = ctx->d_len; a.causal = 1; a.q_pos0 = 0;
+    a.batch = b; a.q_heads = c.t_heads; a.kv_heads = c.t_kv_heads; a.Sq = S; a.Skv = keep + S; a.kv_len = ctx->d_len; a.causal = 1; a.q_pos0 = keep;
     a.kv_start = left ? ctx->d_start : nullptr;
     a.scale = 0.08838834764831845f;
-    TRY(launch_attn_prefill(ctx->dt, a, s));
+    if (!split_attn) TRY(launch_attn_prefill(ctx->dt, a, s));
     // left-padded batch: a padded query row sees no key at all; the reference's eager attention (the CPU path) then attends EVERY key of
     // the sequence with weight 1 / S (all scores are finfo.min -> softmax uniform, future keys included), and these rows' K / V in the
     // next layers are what a masked decode step exposes (omchat_arch.py:61-70).  The flash kernel leaves exactly 0 there; fill them.
@@ -1389,7 +1421,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   if (hidden_out) TRY(launch_rmsnorm(ctx->dt, x, H, ctx->t_norm, hidden_out, H, rows, H, c.t_eps, s));
   if (logits_last) {
     // only the last valid position feeds generation (Qwen2ForCausalLM.forward :462-465 projects all; same values)
-    hipLaunchKernelGGL(last_row_index_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_len, S, b, ctx->d_idx);
+    hipLaunchKernelGGL(last_row_index_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_len, S, b, ctx->d_idx, keep);
     TRY(launch_gather_rows(ctx->dt, ctx->d_idx, x, nullptr, ctx->tw_last, b, H, s));
     TRY(launch_rmsnorm(ctx->dt, ctx->tw_last, H, ctx->t_norm, ctx->tw_last, H, b, H, c.t_eps, s));
     TRY(lm_head_rows(ctx, ctx->tw_last, b, logits_last, s));
@@ -1420,6 +1452,37 @@ extern "C" int omchat_prefill(omchat_ctx* ctx, const void* embeds, int b, int S,
 extern "C" int omchat_prefill_left(omchat_ctx* ctx, const void* embeds, int b, int S, const int32_t* lengths, float* logits_last,
                                    void* hidden_out, void* stream) {
   return prefill_impl(ctx, embeds, b, S, lengths, logits_last, hidden_out, stream, true);
+}
+
+extern "C" int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_new, int keep, float* logits_last, void* hidden_out, void* stream) {
+  OM_CHECK(ctx, "null argument");
+  OM_CHECK(S_new >= 1, "prefill_extend: S_new < 1");
+  OM_CHECK(embeds, "null argument");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(ctx->tp_size == 1, "prefill_extend: tensor-parallel contexts are not implemented (DESIGN.md section 7)");
+  OM_CHECK(!ctx->fp8_kv, "prefill_extend: the e4m3 KV cache is not implemented (DESIGN.md section 7): omchat_enable_fp8_kv(ctx, 0)");
+  OM_CHECK(!ctx->fp8_prefill, "prefill_extend: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
+  OM_CHECK(!ctx->left_padded, "prefill_extend: the cache holds a left-padded batch");
+  OM_CHECK(ctx->dec_mode != 2, "prefill_extend: the cache holds a masked-decode (padded batch) state");
+  OM_CHECK(!ctx->beam.on, "prefill_extend: a beam search is active");
+  OM_CHECK(ctx->pre_b >= 1 && ctx->h_len[0] >= 1, "prefill_extend: no live sequence-0 state (omchat_prefill with b = 1 first)");
+  OM_CHECK(ctx->pre_b == 1, "prefill_extend: the cache holds a b > 1 state");
+  OM_CHECK(keep >= 0 && keep <= ctx->h_len[0], "prefill_extend: keep outside [0, current length]");
+  OM_CHECK(S_new <= c.max_prefill_rows, "prefill_extend: S_new > max_prefill_rows");
+  OM_CHECK((int64_t)keep + S_new <= c.max_seq, "prefill_extend: keep + S_new > max_seq");
+  const int32_t len = S_new;
+  return prefill_impl(ctx, embeds, 1, S_new, &len, logits_last, hidden_out, stream, false, keep);
+}
+
+extern "C" int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, int n, void* out, void* stream) {
+  OM_CHECK(ctx && out, "null argument");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(layer >= 0 && layer < c.t_layers && (which == 0 || which == 1) && pos0 >= 0 && n >= 1 && pos0 + n <= c.max_seq, "bad argument");
+  const char* src = (const char*)(which ? ctx->vcache : ctx->kcache) + ((size_t)layer * ctx->cache_layer_stride() + (size_t)pos0 * 128) * 2;
+  OM_HIP(hipMemcpy2DAsync(out, (size_t)n * 256, src, (size_t)ctx->cache_sh() * 2, (size_t)n * 256, (size_t)c.t_kv_heads, hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+  return 0;
 }
 
 // (re)build the packed weight replica of the decode-streamed decoder weights; synchronous, never inside a graph capture.

@@ -52,6 +52,10 @@ class Engine:
         self.h = h
         self._keep = []
         self._lookup_st = dict(verify_steps=0, drafted=0, accepted=0)
+        # generate(reuse_cache=True): what sequence 0's cache holds (omchat_amd/prefix.py) with last call's tiles and feature rows
+        self._prefix = None
+        self._tile_key_next = 0
+        self._ext_st = dict(kept_slots=0, prefilled_rows=0, tiles_encoded=0, tiles_reused=0)
 
     def close(self):
         if getattr(self, "h", None):
@@ -75,6 +79,7 @@ class Engine:
         t = t.contiguous()
         shape = (C.c_int64 * max(t.dim(), 1))(*(list(t.shape) or [1]))
         check(self.lib.omchat_load_tensor(self.h, name.encode(), ptr(t), shape, max(t.dim(), 1), _lib.dtype_code(t.dtype)))
+        self._prefix = None      # the cache rows came from other weights
 
     def load_state_dict(self, sd, strict=True):
         """sd: omchat-native keys -> full (unsharded) tensors; sharded here for tp_size > 1."""
@@ -159,6 +164,7 @@ class Engine:
         """fp8 (e4m3 + per-position scale) KV cache for the decode steps that follow the NEXT prefill (BASELINE configs[4])"""
         check(self.lib.omchat_enable_fp8_kv(self.h, int(on)))
         self._fp8_kv = bool(on)
+        self._prefix = None
 
     def masked_decode_supported(self):
         """omchat_decode_step_masked (padded-batch decode as omchat_arch.py:61-70 computes it) runs on one GPU; see include/omchat_hip.h"""
@@ -167,6 +173,8 @@ class Engine:
     def enable_fp8_prefill(self, on=True):
         """fp8 x fp8 MFMA for the qkv and gate|up GEMMs of the prefill (activations quantised per token, weights per output row)"""
         check(self.lib.omchat_enable_fp8_prefill(self.h, int(on)))
+        self._fp8_prefill = bool(on)
+        self._prefix = None
 
     def enable_decode_graph(self, on=True):
         """Replay each decode step as one hipGraph launch (TP = 1, b <= 32); same kernels and results as the eager step."""
@@ -259,8 +267,92 @@ class Engine:
         logits = torch.empty(b, self.c.t_vocab, dtype=torch.float32, device=self.device) if want_logits else None
         hidden = torch.empty(b, S, self.cfg.text["hidden_size"], dtype=self.torch_dtype, device=self.device) if want_hidden else None
         fn = self.lib.omchat_prefill_left if padding_side == "left" else self.lib.omchat_prefill
+        self._prefix = None      # every prefill overwrites sequence 0: generate(reuse_cache=True) records again after its own
         check(fn(self.h, ptr(e), b, S, ptr(lens), ptr(logits), ptr(hidden), cur_stream()))
         return logits, hidden
+
+    def prefill_extend(self, embeds, keep, want_hidden=False, want_logits=True):
+        """Continue sequence 0's cache (include/omchat_hip.h: omchat_prefill_extend): embeds [S_new, H] (or [1, S_new, H]) are the rows at
+        positions keep .. keep + S_new - 1; slots >= keep are forgotten, slots < keep stay.  -> (logits fp32 [1, V] of the last row,
+        hidden [1, S_new, H] or None)"""
+        torch = _torch()
+        e = embeds.to(device=self.device, dtype=self.torch_dtype).contiguous()
+        if e.dim() == 3:
+            if e.shape[0] != 1:
+                raise ValueError("prefill_extend continues ONE sequence: embeds [S_new, H] or [1, S_new, H]")
+            e = e[0]
+        S = e.shape[0]
+        logits = torch.empty(1, self.c.t_vocab, dtype=torch.float32, device=self.device) if want_logits else None
+        hidden = torch.empty(1, S, self.cfg.text["hidden_size"], dtype=self.torch_dtype, device=self.device) if want_hidden else None
+        check(self.lib.omchat_prefill_extend(self.h, ptr(e), S, int(keep), ptr(logits), ptr(hidden), cur_stream()))
+        return logits, hidden
+
+    def extend_attn_form(self, S_new, keep):
+        """0 = prefill_extend(S_new rows, keep) takes the prefill attention kernel with q_pos0, 1 = the split-KV block attention"""
+        return int(self.lib.omchat_extend_attn_form(int(S_new), int(keep), self.c.t_kv_heads))
+
+    def kv_read(self, layer, which, pos0, n):
+        """test hook: rows [pos0, pos0 + n) of sequence 0's K (which = 0) / V (1) cache of one layer -> [kv_heads, n, 128]"""
+        torch = _torch()
+        out = torch.empty(self.c.t_kv_heads, n, 128, dtype=self.torch_dtype, device=self.device)
+        check(self.lib.omchat_kv_read(self.h, int(layer), int(which), int(pos0), int(n), ptr(out), cur_stream()))
+        return out
+
+    def extend_stats(self, reset=False):
+        """the last generate(reuse_cache=True) call: cache slots kept, rows prefilled, tiles run through the tower / taken from last call"""
+        out = dict(self._ext_st)
+        if reset:
+            for key in self._ext_st:
+                self._ext_st[key] = 0
+        return out
+
+    def drop_prefix(self):
+        """forget what sequence 0's cache holds, with the kept tiles and feature rows (model.reset_cache())"""
+        self._prefix = None
+
+    def tile_keys(self, px):
+        """content keys of the tiles px [n, 3, s, s] (engine dtype, on the device): a tile bit-equal to one kept from the last
+        reuse_cache call gets that tile's key, any other a fresh one.  One device-to-host copy.  -> (keys, index of the equal kept tile or -1)"""
+        torch = _torch()
+        n = 0 if px is None else px.shape[0]
+        kept = self._prefix
+        src = [-1] * n
+        if n and kept is not None and kept.get("px") is not None and kept["px"].shape[1:] == px.shape[1:]:
+            eq = torch.stack([(kept["px"] == px[j]).flatten(1).all(dim=1) for j in range(n)]).cpu()
+            for j in range(n):
+                hit = torch.nonzero(eq[j])
+                if hit.numel():
+                    src[j] = int(hit[0])
+        keys = []
+        for j in range(n):
+            if src[j] >= 0:
+                keys.append(kept["keys"][src[j]])
+            else:
+                keys.append(self._tile_key_next)
+                self._tile_key_next += 1
+        return keys, src
+
+    def splice_plan(self, input_ids, n_tiles, max_length=None):
+        """omchat_splice_plan of ONE unpadded row: -> src_index int32 [S] (CPU)"""
+        torch = _torch()
+        ids = input_ids.detach().to("cpu", torch.int64).contiguous().view(1, -1)
+        T = ids.shape[1]
+        ml = -1 if max_length is None else int(max_length)
+        S = C.c_int(0)
+        lens = torch.zeros(1, dtype=torch.int32)
+        check(self.lib.omchat_splice_plan(ptr(ids), None, 1, T, self.ntok, n_tiles, 0, ml, None, ptr(lens), C.byref(S), self.c.t_vocab_total))
+        idx = torch.empty(1, S.value, dtype=torch.int32)
+        check(self.lib.omchat_splice_plan(ptr(ids), None, 1, T, self.ntok, n_tiles, 0, ml, ptr(idx), ptr(lens), C.byref(S), 0))
+        return idx[0]
+
+    def gather_rows(self, src_index, feats):
+        """embedding rows of a (slice of a) splice plan: src_index int32 [rows], feats [n_tiles, ntok, H] or None -> [rows, H]"""
+        torch = _torch()
+        idx_d = src_index.to(torch.int32).contiguous().to(self.device)
+        f = None if feats is None else feats.to(device=self.device, dtype=self.torch_dtype).contiguous()
+        out = torch.empty(idx_d.shape[0], self.cfg.text["hidden_size"], dtype=self.torch_dtype, device=self.device)
+        check(self.lib.omchat_splice_gather(self.h, ptr(idx_d), ptr(f), ptr(out), idx_d.shape[0], cur_stream()))
+        return out
 
     def decode_step(self, tokens, want_logits=False):
         torch = _torch()
@@ -412,6 +504,7 @@ class Engine:
         check(self.lib.omchat_beam_begin(self.h, int(b), int(num_beams), float(length_penalty), es, ptr(ev), len(eos), int(max_new), int(P),
                                          cur_stream()))
         self._beam = (int(b), int(num_beams), int(max_new))
+        self._prefix = None      # the fork overwrites sequence 0's row
         self.beam_done = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def beam_step(self, logits):

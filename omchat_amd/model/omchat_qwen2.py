@@ -110,13 +110,18 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         # sampler draws from an explicit seed, never from torch's global RNG state
         self.generation_config = _GenerationConfig(pad_token_id=None, eos_token_id=None, max_new_tokens=None, do_sample=False, temperature=1.0,
                                                    top_k=50, top_p=1.0, repetition_penalty=1.0, seed=None, num_beams=1,
-                                                   length_penalty=1.0, early_stopping=False, num_return_sequences=1)
+                                                   length_penalty=1.0, early_stopping=False, num_return_sequences=1, reuse_cache=False)
         self._last_lengths = None
         self.device = engine.device
         self.dtype = engine.torch_dtype
 
     def get_model(self):
         return self
+
+    def reset_cache(self):
+        """forget the conversation generate(reuse_cache=True) keeps in sequence 0's cache (record, tiles, feature rows): the next call
+        prefills its whole prompt"""
+        self.engine.drop_prefix()
 
     def eval(self):
         return self
@@ -262,7 +267,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
                  repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
-                 num_return_sequences=None, return_dict_in_generate=False, **kwargs):
+                 num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
@@ -271,11 +276,24 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         decoding for b = 1, greedy (omchat_amd/lookup.py): drafts of up to k ids copied from the prompt + generated ids are verified in
         one verify step each.  Exactness: the verify rows go through the batched (MFMA-form) GEMVs and plain steps through the batch-1
         whole-row forms, so a position's logits can differ in the last bits and the ids can differ from greedy only at near-ties, as in
-        HF's assisted decoding in fp16."""
+        HF's assisted decoding in fp16.
+        reuse_cache=True (also read from generation_config; b = 1, num_beams = 1, no padding): multi-turn chat.  The
+        call records what sequence 0's cache holds when it returns; the next reuse_cache=True call keeps the longest common prefix of that
+        record and its own prompt -- tiles are compared bit for bit, equal ones reuse their feature rows -- and prefills only the rest
+        (Engine.prefill_extend).  Kept slots written by decode steps came from the GEMV forms, so a position's logits can differ in the
+        last bits from a fresh prefill's, and ids at near-ties only.  Default False: nothing is kept."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
         nb = int(num_beams if num_beams is not None else (getattr(gc, "num_beams", None) or 1))
+        reuse = bool(reuse_cache if reuse_cache is not None else getattr(gc, "reuse_cache", False))
+        if reuse:      # every refusal before any work
+            from ..prefix import check_reuse_args
+            check_reuse_args(input_ids.shape[0], nb, None if attention_mask is None else attention_mask.tolist(),
+                             getattr(self.config, "tokenizer_padding_side", "right"))
+            if getattr(self.engine, "_fp8_kv", False) or getattr(self.engine, "_fp8_prefill", False) or self.engine.tp_size > 1:
+                raise NotImplementedError("reuse_cache=True with the e4m3 KV cache, fp8 x fp8 prefill GEMMs or tensor parallelism is not "
+                                          "implemented (DESIGN.md section 7)")
         lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
@@ -290,7 +308,11 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         b = input_ids.shape[0]
         if streamer is not None:
             streamer.put(input_ids.cpu())
-        out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
+        prompt_slots = None
+        if reuse:
+            out, prompt_slots = self._forward_reuse(input_ids, images)
+        else:
+            out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
         # ONE rule for the first token at every TP degree: omchat_greedy on this rank's vocabulary shard -- local first-index-wins argmax,
         # then the (max, index) exchange the decode step uses (model.hip: greedy_pick); no torch re-statement on the gathered logits.
         # Sampling: the same seam with the sampler (omchat_sample); the decode steps below then sample too, the penalty's seen set growing
@@ -320,6 +342,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                               self.engine.verify_max_tokens())
             if streamer is not None:
                 streamer.end()
+            self._record_prefix(prompt_slots, gen)
             return torch.cat([input_ids.cpu(), torch.tensor([gen], dtype=torch.int64)], dim=1)
         new = []
         done = torch.zeros(b, dtype=torch.bool)
@@ -370,7 +393,61 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             tok = ahead
         if streamer is not None:
             streamer.end()
+        self._record_prefix(prompt_slots, [int(t[0]) for t in new])
         return torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+
+    def _forward_reuse(self, input_ids, images):
+        """The prefill of generate(reuse_cache=True), b = 1: keeps the slots of sequence 0's cache that the new prompt shares with the
+        recorded one and prefills the rest; the tower runs on tiles that differ from every kept tile only.  -> (forward()'s output for
+        the last position, the prompt's slot list).  The engine's record is pending (dropped) until _record_prefix."""
+        from ..prefix import slots_from_plan, keep_count
+        e = self.engine
+        px = None
+        if images is not None and self.get_vision_tower() is not None:
+            if type(images) is list:
+                if any(im.ndim != 3 for im in images):
+                    raise NotImplementedError("video inputs: the reference calls an undefined encode_videos (omchat_arch.py:87)")
+                images = torch.stack(images)
+            elif images.ndim == 5:
+                raise NotImplementedError("video inputs: the reference calls an undefined encode_videos (omchat_arch.py:87)")
+            px = e._px(images)
+        n = 0 if px is None else px.shape[0]
+        keys, src = e.tile_keys(px)
+        idx = e.splice_plan(input_ids, n, getattr(self.config, "tokenizer_model_max_length", None))
+        slots = slots_from_plan(idx.tolist(), e.ntok, keys)
+        S = len(slots)
+        kept = e._prefix
+        P = keep_count(kept["record"], slots, e.kv_lengths(1)[0]) if kept is not None and kept.get("record") else 0
+        feats = None
+        fresh = [j for j in range(n) if src[j] < 0]
+        if n:
+            feats = torch.empty(n, e.ntok, e.cfg.text["hidden_size"], dtype=e.torch_dtype, device=e.device)
+            for j in range(n):
+                if src[j] >= 0:
+                    feats[j].copy_(kept["feats"][src[j]])
+            if fresh:
+                feats[fresh] = self.encode_images(px[fresh]).to(e.torch_dtype)
+        if P > 0:
+            logits, _ = e.prefill_extend(e.gather_rows(idx[P:], feats), P)
+        else:
+            logits, _ = e.prefill(e.gather_rows(idx, feats).unsqueeze(0), [S])
+        e._prefix = dict(record=None, px=px, feats=feats, keys=keys)
+        e._ext_st = dict(kept_slots=P, prefilled_rows=S - P, tiles_encoded=len(fresh), tiles_reused=n - len(fresh))
+        self._padded_batch = False
+        self._prefill_slots = S
+        self._last_lengths = None
+        out = CausalLMOutputWithPast(e.full_logits(logits).unsqueeze(1), KVHandle(e, 1))
+        out.local_logits = logits
+        return out, slots
+
+    def _record_prefix(self, prompt_slots, generated):
+        """end of a reuse_cache=True call: the record = the prompt's slots + the generated ids that are cached (not the last emitted one)"""
+        if prompt_slots is None:
+            return
+        from ..prefix import extend_record
+        e = self.engine
+        if e._prefix is not None:
+            e._prefix["record"] = extend_record(prompt_slots, generated, e.kv_lengths(1)[0])
 
     def _spliced_lengths(self, ids, images):
         """the rows' lengths after the image-token splice, from the host-side plan alone (omchat_splice_plan: integers, nothing enqueued)"""
