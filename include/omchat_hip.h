@@ -161,6 +161,29 @@ int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float temperature
                         const int32_t* seen_ids, const int32_t* n_seen_per_row, void* stream);
 /* the sampled counterpart of omchat_greedy (the first token after the prefill); omchat_greedy itself when sampling is off */
 int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream);
+/* ---- HF logits constraints (generate's no_repeat_ngram_size, bad_words_ids, min_new_tokens / min_length, suppress_tokens,
+ * begin_suppress_tokens) ------------------------------------------------------------------------------------------ */
+#define OMCHAT_CON_MAX_NGRAM 64          /* no_repeat_ngram_size */
+#define OMCHAT_CON_MAX_EOS 16            /* eos ids */
+#define OMCHAT_CON_MAX_SUPPRESS 1024     /* suppress ids, and begin-suppress ids */
+#define OMCHAT_CON_MAX_BAD_WORDS 1024    /* bad words */
+#define OMCHAT_CON_MAX_BAD_WORD_IDS 8192 /* ids of all bad words together */
+/* omchat_set_constraints: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both
+ * masked steps, the captured decode graph -- excludes the ids HF 5.x's NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength, SuppressTokens
+ * and SuppressTokensAtBegin processors would set to -inf, given the row's token history: the prompt row as passed (prompt_ids host int32, the
+ * rows one after another, prompt_len host int32 [b]; the -200 image sentinel and pad ids are ordinary values for matching) plus the token every
+ * decode step is fed, appended on the device before that step's pick.  The pick (argmax or sampler) runs on a context-owned copy of the logits
+ * with the banned ids at -inf: logits handed in or returned stay raw.  no_repeat_ngram_size 0 = off; min_new_tokens / min_length 0 = off (they
+ * ban eos_ids); bad words are flattened (bad_word_offsets host int32 [n_bad_words + 1] into bad_word_ids); a bad word equal to one eos id is
+ * dropped; ids outside [0, t_vocab_total) are never banned.  max_new: the most decode steps that will follow (sizes the history; a step beyond
+ * it is refused).  The history is grown on demand, never shrunk, and counted in omchat_device_bytes.  omchat_kv_rewind takes the history back
+ * with the slots.  b = 0 switches constraints off.  Refused (before anything is enqueued): values above the caps, a beam search in progress;
+ * omchat_decode_verify and omchat_beam_begin refuse while constraints are on.  A parameter change drops the captured decode graphs.
+ * Synchronises. */
+int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids, int n_eos,
+                           const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
+                           const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
+                           const int32_t* prompt_len, int max_new, void* stream);
 int omchat_kv_lengths(omchat_ctx* ctx, int32_t* out, int b);      /* host copy of the current KV lengths */
 /* take back the last n decode steps of sequences 0..b-1 (generate() enqueues step k + 1 before it has read token k on the host, as the
  * reference's HF loop cannot; when token k ends the generation -- EOS, a stopping criterion -- that step is forgotten).  Synchronises. */
@@ -477,6 +500,15 @@ int omchat_op_rope_kv(int dtype, void* qkv, int b, int S, int Hq, int Hkv, int p
 int omchat_op_rope_kv_q8(int dtype, void* qkv, int b, int S, int Hq, int Hkv, int pos0, float theta, void* kcache, void* vcache, int cap,
                          void* k8, void* v8, float* ks, float* vs, void* stream);
 int omchat_op_argmax(const float* logits, int b, int V, int32_t* out, void* stream);
+/* context-free ban pass of omchat_set_constraints (test hook): histories host int32, the rows one after another (hist_len host int32 [b]; prompt_len
+ * host int32 [b] = how many of them are the prompt); V ids of the vocabulary slice of `rank` out of V_total; fed_last != 0 passes each row's last
+ * id as the token a decode step is fed instead of as stored history (the same set either way).  ban_out device uint32 [b][(V + 31) / 32]: bit i
+ * of a row = local id i is banned.  Synchronises. */
+int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_len, const int32_t* prompt_len, int b, int V, int V_total, int rank, int fed_last,
+                        int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids, int n_eos, const int32_t* suppress_ids,
+                        int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress, const int32_t* bad_word_ids,
+                        const int32_t* bad_word_offsets, int n_bad_words, uint32_t* ban_out, void* stream);
+
 /* context-free sampler over logits fp32 [b, V] with the parameters of omchat_set_sampling; every row at step `step`.  thr_out (device uint32 [b]
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */
 int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,

@@ -408,6 +408,60 @@ extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed
   return rc;
 }
 
+static_assert(CON_NGRAM_MAX == OMCHAT_CON_MAX_NGRAM && CON_EOS_MAX == OMCHAT_CON_MAX_EOS && CON_SUPPRESS_MAX == OMCHAT_CON_MAX_SUPPRESS &&
+              CON_BAD_WORDS_MAX == OMCHAT_CON_MAX_BAD_WORDS && CON_BAD_WORD_IDS_MAX == OMCHAT_CON_MAX_BAD_WORD_IDS, "constraint caps: kernels.h and omchat_hip.h");
+
+extern "C" int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_len, const int32_t* prompt_len, int b, int V, int V_total, int rank,
+                                   int fed_last, int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids, int n_eos,
+                                   const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
+                                   const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, uint32_t* ban_out, void* stream) {
+  OM_CHECK(hist_ids && hist_len && prompt_len && ban_out && b >= 1 && V >= 1 && V_total >= V && rank >= 0, "bad argument");
+  OM_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= CON_NGRAM_MAX && min_new_tokens >= 0 && min_length >= 0, "constraint parameters out of range");
+  int maxL = 0;
+  for (int i = 0; i < b; ++i) {
+    OM_CHECK(hist_len[i] >= (fed_last ? 1 : 0) && prompt_len[i] >= 0, "history lengths out of range");
+    maxL = std::max(maxL, hist_len[i]);
+  }
+  ConstrainArgs a;
+  std::vector<int32_t> lists(CON_LIST_WORDS);
+  if (int rc = constrain_pack_lists(eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_word_ids, bad_word_offsets,
+                                    n_bad_words, lists.data(), a)) return rc;
+  const int ld = (maxL + 4) / 4 * 4, bmw = (V + 31) / 32;
+  // the rows as the context keeps them: fed_last holds each row's last id back as the token the step is fed
+  std::vector<int32_t> h((size_t)b * ld, 0), len(b), tok(b, 0);
+  size_t off = 0;
+  for (int i = 0; i < b; ++i) {
+    len[i] = hist_len[i] - (fed_last ? 1 : 0);
+    std::copy(hist_ids + off, hist_ids + off + len[i], h.begin() + (size_t)i * ld);
+    if (fed_last) tok[i] = hist_ids[off + len[i]];
+    off += (size_t)hist_len[i];
+  }
+  hipStream_t s = S(stream);
+  char* mem = nullptr;
+  const size_t hb = h.size() * 4, lb = lists.size() * 4, rb = ((size_t)b * 4 + 15) / 16 * 16;
+  OM_HIP(hipMalloc(&mem, hb + lb + 3 * rb));
+  int32_t* d_h = (int32_t*)mem;
+  int32_t* d_lists = (int32_t*)(mem + hb);
+  int* d_len = (int*)(mem + hb + lb);
+  int* d_plen = (int*)(mem + hb + lb + rb);
+  int32_t* d_tok = (int32_t*)(mem + hb + lb + 2 * rb);
+  hipMemcpyAsync(d_h, h.data(), hb, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_lists, lists.data(), lb, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_len, len.data(), (size_t)b * 4, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_plen, prompt_len, (size_t)b * 4, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_tok, tok.data(), (size_t)b * 4, hipMemcpyHostToDevice, s);
+  hipMemsetAsync(ban_out, 0, (size_t)b * bmw * 4, s);
+  a.hist = d_h; a.hist_ld = ld; a.len = d_len; a.plen = d_plen; a.tok = fed_last ? d_tok : nullptr;
+  a.b = b; a.V = V; a.V_total = V_total; a.gbase = rank * V;
+  a.ngram = no_repeat_ngram_size; a.min_new = min_new_tokens; a.min_len = min_length;
+  constrain_bind_lists(d_lists, a);
+  a.ban = ban_out; a.bmw = bmw;
+  int rc = launch_constrain_ban(a, s);
+  hipStreamSynchronize(s);
+  hipFree(mem);
+  return rc;
+}
+
 extern "C" size_t omchat_beam_state_words(int b, int N, int max_new) { return beam_state_words(b, N, max_new); }
 
 extern "C" int omchat_op_beam_select(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty,

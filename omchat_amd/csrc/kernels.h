@@ -389,6 +389,28 @@ size_t sample_ws_bytes(int b);
 int launch_sample(const SampleArgs& a, hipStream_t s);
 // take back n picks: clears the bit the last pick set (n == 1), step -= n
 int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s);
+// HF logits constraints (constrain.hip; tests/constraints_ref.py restates the ban set).  The caps are the public
+// header's OMCHAT_CON_* (capi.hip asserts they agree).
+constexpr int CON_NGRAM_MAX = 64, CON_EOS_MAX = 16, CON_SUPPRESS_MAX = 1024, CON_BAD_WORDS_MAX = 1024, CON_BAD_WORD_IDS_MAX = 8192;
+constexpr int CON_LIST_WORDS = CON_EOS_MAX + 2 * CON_SUPPRESS_MAX + CON_BAD_WORDS_MAX + 1 + CON_BAD_WORD_IDS_MAX;      // int32 words of the device lists
+struct ConstrainArgs {
+  int32_t* hist = nullptr; int hist_ld = 0;         // [b][hist_ld] token history as HF's processors see it (prompt row + fed ids)
+  int* len = nullptr; const int* plen = nullptr;    // [b] ids held / ids of the prompt row
+  const int32_t* tok = nullptr;                     // [b] the token this decode step is fed (appended at hist[len]), NULL at the first pick
+  int b = 0, V = 0, V_total = 0, gbase = 0;         // V: this rank's vocabulary slice, gbase = rank * V
+  int ngram = 0, min_new = 0, min_len = 0;
+  const int32_t *eos = nullptr, *sup = nullptr, *bsup = nullptr, *bw_ids = nullptr, *bw_off = nullptr;
+  int n_eos = 0, n_sup = 0, n_bsup = 0, n_bw = 0;
+  uint32_t* ban = nullptr; int bmw = 0;             // [b][bmw] ban bitmap, all-zero on entry; bits of this pick's ban set are set
+};
+int launch_constrain_ban(const ConstrainArgs& a, hipStream_t s);
+// out [b][V] = logits with the banned ids at -inf; clears the bitmap; len (optional) += 1: the fed token the ban pass stored is now counted
+int launch_constrain_apply(const float* logits, int ld, int b, int V, uint32_t* ban, int bmw, float* out, int* len, int hist_ld, hipStream_t s);
+int launch_constrain_append(int32_t* hist, int hist_ld, int* len, const int32_t* tok, int b, hipStream_t s);
+int launch_constrain_rewind(int* len, const int* plen, int b, int n, hipStream_t s);
+int constrain_pack_lists(const int32_t* eos, int n_eos, const int32_t* sup, int n_sup, const int32_t* bsup, int n_bsup, const int32_t* bw_ids,
+                         const int32_t* bw_off, int n_bw, int32_t* out, ConstrainArgs& a);      // out: [CON_LIST_WORDS], host
+void constrain_bind_lists(const int32_t* d_lists, ConstrainArgs& a);
 // beam search (beam.hip; tests/beam_ref.py restates it).  The vocabulary is cut into beam_slices(V, tp) equal slices
 // of at most BEAM_SLICE_CAP ids, the same at every TP degree; a rank owns ns / tp whole slices.  Exchange table: [rows][ns][4 + 2K] fp32.
 constexpr int BEAM_KMAX = 32;            // candidates kept per step and prompt: max(2, 1 + n_eos) * N

@@ -196,6 +196,22 @@ struct omchat_ctx {
   void* smp_ws = nullptr;
   uint32_t* smp_bm = nullptr; int smp_bmw = 0;
   int *smp_last = nullptr, *smp_step = nullptr;
+  // HF logits constraints (omchat_set_constraints; constrain.hip): uniform parameters, the rows' token history as HF's processors see it
+  // [max_batch][con_ld] with device lengths, the id lists, the ban bitmap of this rank's vocabulary slice (all-zero between picks) and the
+  // banned copy of the logits the pick runs on.  con_fed: decode steps fed since the begin (host bound for the history's capacity).
+  struct Constraints {
+    bool on = false; int b = 0, ngram = 0, min_new = 0, min_len = 0, n_eos = 0, n_sup = 0, n_bsup = 0, n_bw = 0;
+    bool operator==(const Constraints& o) const {
+      return on == o.on && b == o.b && ngram == o.ngram && min_new == o.min_new && min_len == o.min_len && n_eos == o.n_eos && n_sup == o.n_sup &&
+             n_bsup == o.n_bsup && n_bw == o.n_bw;
+    }
+  };
+  Constraints con;
+  int con_ld = 0, con_fed = 0, con_room = 0;
+  int *con_len = nullptr, *con_plen = nullptr;
+  int32_t* con_lists = nullptr;
+  uint32_t* con_ban = nullptr; int con_bmw = 0;
+  float* con_logits = nullptr;
   // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand
   // (state words, exchange table, length-penalty denominators, parent rows, stash of the KV gather)
   struct Beam { bool on = false; int b = 0, N = 0, KB = 0, max_new = 0, P = 0, es = 0, ns = 1, t = 0; float lp = 1.f; std::vector<int> eos; };
@@ -203,6 +219,7 @@ struct omchat_ctx {
   struct Grown { void* p = nullptr; size_t cap = 0; };
   Grown bm_state, bm_table, bm_dn, bm_parents, bm_stash;
   Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
+  Grown con_hist;    // token history of the logits constraints (omchat_set_constraints)
   bool bm_stash8 = false;
   std::vector<int> bm_hpos, bm_hlen;      // host sources of the fork's device lengths (alive until the next begin)
   int grow(Grown& g, size_t n) {
@@ -600,7 +617,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash, &ctx->ext_ws})
+  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash, &ctx->ext_ws, &ctx->con_hist})
     if (g->p) hipFree(g->p);
   delete ctx;
 }
@@ -1265,8 +1282,35 @@ static int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_to
 
 static int smp_xchg(void* user, float* buf, size_t count, hipStream_t s) { return ((omchat_ctx*)user)->allreduce_f32(buf, count, s); }
 
+static ConstrainArgs con_args(omchat_ctx* ctx, int b, const int32_t* fed) {
+  const omchat_config& c = ctx->c;
+  ConstrainArgs a;
+  a.hist = (int32_t*)ctx->con_hist.p; a.hist_ld = ctx->con_ld; a.len = ctx->con_len; a.plen = ctx->con_plen; a.tok = fed;
+  a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total; a.gbase = ctx->tp_rank * c.t_vocab;
+  a.ngram = ctx->con.ngram; a.min_new = ctx->con.min_new; a.min_len = ctx->con.min_len;
+  constrain_bind_lists(ctx->con_lists, a);
+  a.n_eos = ctx->con.n_eos; a.n_sup = ctx->con.n_sup; a.n_bsup = ctx->con.n_bsup; a.n_bw = ctx->con.n_bw;
+  a.ban = ctx->con_ban; a.bmw = ctx->con_bmw;
+  return a;
+}
+
+// The ban stage in front of a pick (omchat_set_constraints; nothing when constraints are off): `fed` = the tokens the decode step was fed
+// (appended to the history first), NULL at the first pick after the prefill.  *lg then points at the context's banned copy of the logits;
+// the caller's logits are not written.
+static int ban_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fed, hipStream_t s) {
+  if (!ctx->con.on) return 0;
+  OM_CHECK(b <= ctx->con.b, "constraints are on for fewer rows than this pick has (omchat_set_constraints)");
+  const omchat_config& c = ctx->c;
+  TRY(launch_constrain_ban(con_args(ctx, b, fed), s));
+  TRY(launch_constrain_apply(*lg, c.t_vocab, b, c.t_vocab, ctx->con_ban, ctx->con_bmw, ctx->con_logits, fed ? ctx->con_len : nullptr, ctx->con_ld, s));
+  *lg = ctx->con_logits;
+  return 0;
+}
+
 // the token pick of a step: greedy unless omchat_set_sampling switched the sampler on; `advance` moves the decode positions in the same launch
-static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false) {
+static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false,
+                     const int32_t* fed = nullptr) {
+  TRY(ban_stage(ctx, &lg, b, fed, s));
   if (!ctx->smp.on) return greedy_pick(ctx, lg, b, next_tokens, s, advance);
   const omchat_config& c = ctx->c;
   SampleArgs a;
@@ -1283,6 +1327,7 @@ static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_toke
 
 extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  TRY(ban_stage(ctx, &logits, b, nullptr, (hipStream_t)stream));
   return greedy_pick(ctx, logits, b, next_tokens, (hipStream_t)stream);
 }
 
@@ -1786,8 +1831,11 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
   if (vL >= 0) TRY(greedy_pick(ctx, lg, b, next_tokens, s));
-  else if (next_tokens) TRY(pick_next(ctx, lg, b, next_tokens, s, true));
-  else hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
+  else if (next_tokens) TRY(pick_next(ctx, lg, b, next_tokens, s, true, tokens));
+  else {
+    hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
+    if (ctx->con.on && b <= ctx->con.b) TRY(launch_constrain_append((int32_t*)ctx->con_hist.p, ctx->con_ld, ctx->con_len, tokens, b, s));
+  }
   OM_LAUNCH_CHECK();
   return 0;
 }
@@ -1852,6 +1900,86 @@ extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float 
   return 0;
 }
 
+// Constraint parameters live in the kernel arguments of the captured decode graphs, as the sampling ones do: a change (or a history buffer
+// that had to grow) drops them.  The id lists are read from device memory at every pick, so new contents of the same size keep the graphs.
+extern "C" int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids,
+                                      int n_eos, const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
+                                      const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
+                                      const int32_t* prompt_len, int max_new, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  const omchat_config& c = ctx->c;
+  auto drop_graphs = [&]() {
+    for (auto& kv : ctx->graphs) destroy_graph(kv.second);
+    ctx->graphs.clear();
+  };
+  if (b <= 0) {
+    if (ctx->con.on) drop_graphs();
+    ctx->con = omchat_ctx::Constraints{};
+    return 0;
+  }
+  // every refusal before anything is enqueued or changed
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(b <= c.max_batch, "constraints: batch exceeds max_batch");
+  OM_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= CON_NGRAM_MAX, "constraints: 0 <= no_repeat_ngram_size <= 64 (0 = off)");
+  OM_CHECK(min_new_tokens >= 0 && min_length >= 0, "constraints: min_new_tokens and min_length >= 0");
+  OM_CHECK(prompt_ids && prompt_len && max_new >= 1, "constraints: prompt ids, per-row lengths and max_new >= 1");
+  OM_CHECK(!ctx->beam.on, "constraints: a beam search is active (the processors act on log-softmax scores there)");
+  int maxP = 0;
+  for (int i = 0; i < b; ++i) {
+    OM_CHECK(prompt_len[i] >= 0, "constraints: prompt_len >= 0");
+    maxP = std::max(maxP, prompt_len[i]);
+  }
+  omchat_ctx::Constraints p;
+  p.on = true; p.b = b; p.ngram = no_repeat_ngram_size; p.min_new = min_new_tokens; p.min_len = min_length;
+  std::vector<int32_t> lists(CON_LIST_WORDS);
+  ConstrainArgs la;
+  TRY(constrain_pack_lists(eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_word_ids, bad_word_offsets,
+                           n_bad_words, lists.data(), la));
+  p.n_eos = la.n_eos; p.n_sup = la.n_sup; p.n_bsup = la.n_bsup; p.n_bw = la.n_bw;
+  if (!ctx->con_lists) {
+    ctx->con_bmw = (c.t_vocab + 31) / 32;
+    TRY(ctx->alloc((void**)&ctx->con_lists, (size_t)CON_LIST_WORDS * 4));
+    TRY(ctx->alloc((void**)&ctx->con_len, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&ctx->con_plen, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&ctx->con_ban, (size_t)c.max_batch * ctx->con_bmw * 4));
+    TRY(ctx->alloc((void**)&ctx->con_logits, (size_t)c.max_batch * c.t_vocab * 4));
+  }
+  // history rows: the prompt, one id per decode step, grown on demand and never shrunk; rows 16-byte aligned
+  const int need = (maxP + max_new + 1 + 3) / 4 * 4;
+  void* old = ctx->con_hist.p;
+  if (need > ctx->con_ld) {
+    TRY(ctx->grow(ctx->con_hist, (size_t)c.max_batch * need * 4));
+    ctx->con_ld = need;
+  }
+  if (!(p == ctx->con) || old != ctx->con_hist.p) drop_graphs();
+  ctx->con = p;
+  ctx->con_fed = 0;
+  ctx->con_room = ctx->con_ld - maxP;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> len(c.max_batch, 0);
+  std::copy(prompt_len, prompt_len + b, len.begin());
+  OM_HIP(hipMemcpyAsync(ctx->con_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(ctx->con_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(ctx->con_plen, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(ctx->con_ban, 0, (size_t)c.max_batch * ctx->con_bmw * 4, s));
+  size_t off = 0;
+  for (int i = 0; i < b; ++i) {
+    if (prompt_len[i])
+      OM_HIP(hipMemcpyAsync((int32_t*)ctx->con_hist.p + (size_t)i * ctx->con_ld, prompt_ids + off, (size_t)prompt_len[i] * 4, hipMemcpyHostToDevice, s));
+    off += (size_t)prompt_len[i];
+  }
+  OM_HIP(hipStreamSynchronize(s));     // host vectors and the caller's ids
+  return 0;
+}
+
+// one more decode step feeds the history: refuse before the step is enqueued when it has no room left (max_new of omchat_set_constraints)
+static int con_count_step(omchat_ctx* ctx) {
+  if (!ctx->con.on) return 0;
+  OM_CHECK(ctx->con_fed + 1 < ctx->con_room, "constraints: more decode steps than the max_new given to omchat_set_constraints");
+  ctx->con_fed += 1;
+  return 0;
+}
+
 // the first token after the prefill (omchat_greedy's sampled counterpart): advances the step counters, not the decode positions
 extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
@@ -1901,6 +2029,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   // a weight reload (omchat_load_tensor) leaves the e4m3 replica stale: re-quantise IN PLACE before streaming it (same device
   // pointers, so a captured decode graph stays valid and replays the fresh bytes)
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
+  TRY(con_count_step(ctx));
   ctx->graph_steps++;
   // graph replay needs replay-invariant arguments: single-GPU fused path only; with profiling on, every 8th step runs eagerly
   // so that the HIP-event brackets of the dominant kernel are still recorded inside the timed region
@@ -1951,6 +2080,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(c.t_kv_heads > 0 && T * (c.t_heads / c.t_kv_heads) <= 128, "T * (q heads per kv head) must be <= 128 (the verify attention's query rows)");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "after a padded-batch prefill or masked decode steps");
   OM_CHECK(!ctx->smp.on, "sampling is on: prompt-lookup decoding is greedy only");
+  OM_CHECK(!ctx->con.on, "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
   OM_CHECK(!ctx->beam.on, "a beam search is active");
   OM_CHECK(!(ctx->fp8_kv && ctx->kv8_valid), "the e4m3 KV cache is not implemented");
   const int L = ctx->h_len[0];
@@ -2006,6 +2136,7 @@ extern "C" int omchat_decode_step_masked(omchat_ctx* ctx, const int32_t* tokens,
     OM_CHECK(positions[i] >= 0 && positions[i] < c.max_seq, "position outside the RoPE table");
     OM_CHECK(key_mask[(size_t)i * mask_ld + Lc] != 0, "the new token must see itself");
   }
+  TRY(con_count_step(ctx));
   ctx->mask_on_device = false;      // the device copy holds THIS step's mask, zero-padded: omchat_decode_step_masked_next needs a new begin
   OM_HIP(hipMemsetAsync(ctx->d_mask, 0, (size_t)b * ctx->mask_sb, s));
   OM_HIP(hipMemcpy2DAsync(ctx->d_mask, (size_t)ctx->mask_sb, key_mask, (size_t)mask_ld, (size_t)Lc + 1, (size_t)b, hipMemcpyHostToDevice, s));
@@ -2054,6 +2185,7 @@ extern "C" int omchat_decode_step_masked_next(omchat_ctx* ctx, const int32_t* to
   TRY(masked_common_checks(ctx, b));
   OM_CHECK(ctx->mask_on_device, "omchat_decode_step_masked_next: call omchat_masked_decode_begin after the prefill (and after any omchat_decode_step_masked)");
   const int Lc = ctx->pre_S + ctx->masked_steps;
+  TRY(con_count_step(ctx));
   const int rc = decode_body(ctx, tokens, b, Lc + 1, logits, next_tokens, (hipStream_t)stream, false, true, true);
   if (rc) return rc;
   ctx->masked_steps += 1;
@@ -2194,14 +2326,25 @@ extern "C" int omchat_fused_status(omchat_ctx* ctx, long* launches, unsigned* ti
 extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   OM_CHECK(ctx && b >= 1 && b <= (int)ctx->h_len.size() && n >= 0, "bad argument");
   if (n == 0) return 0;
+  // every refusal before anything is enqueued or changed: the sampler's counters, the constraint history and the KV lengths stay in step
+  OM_CHECK(!ctx->smp.on || n == 1 || ctx->smp.penalty == 1.f,
+           "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded");
+  if (ctx->dec_mode == 2) {
+    OM_CHECK(n <= ctx->masked_steps, "rewind beyond the prefill");
+  } else {
+    for (int i = 0; i < b; ++i) OM_CHECK(ctx->h_len[i] - n >= 1, "rewind beyond the prefill");
+  }
   if (ctx->smp.on) {
     // the sampler's step counters go back with the slots, and the seen bit the last pick set is cleared (only that pick is recorded)
-    OM_CHECK(n == 1 || ctx->smp.penalty == 1.f, "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded");
     TRY(launch_sample_rewind(ctx->smp.penalty != 1.f ? ctx->smp_bm : nullptr, ctx->smp_bmw, ctx->smp_last, ctx->smp_step, b, n,
                              (hipStream_t)stream));
   }
+  if (ctx->con.on) {
+    // the history forgets the fed ids with the slots
+    TRY(launch_constrain_rewind(ctx->con_len, ctx->con_plen, std::min(b, ctx->con.b), n, (hipStream_t)stream));
+    ctx->con_fed = std::max(0, ctx->con_fed - n);
+  }
   if (ctx->dec_mode == 2) {
-    OM_CHECK(n <= ctx->masked_steps, "rewind beyond the prefill");
     ctx->masked_steps -= n;
     // the device-resident positions (omchat_decode_step_masked_next) go back with the slots; the host-mask form passes its positions every step
     hipLaunchKernelGGL(add_positions_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, (hipStream_t)stream, ctx->d_pos, b, -n);
@@ -2210,7 +2353,6 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   }
   std::vector<int> pos(b), len1(b);
   for (int i = 0; i < b; ++i) {
-    OM_CHECK(ctx->h_len[i] - n >= 1, "rewind beyond the prefill");
     ctx->h_len[i] -= n;
     pos[i] = ctx->h_len[i]; len1[i] = ctx->h_len[i] + 1;
   }
@@ -2252,6 +2394,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   const int N = num_beams;
   OM_CHECK(b >= 1 && N >= 2 && N <= BEAM_NMAX, "beam search: b >= 1 and 2 <= num_beams <= 16");
+  OM_CHECK(!ctx->con.on, "beam search: constraints are on (omchat_set_constraints with b = 0 first); HF applies them to log-softmax scores there");
   OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
   OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
   const int KB = std::max(2, 1 + n_eos) * N;

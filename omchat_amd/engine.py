@@ -494,6 +494,30 @@ class Engine:
         check(self.lib.omchat_sample(self.h, ptr(logits), logits.shape[0], ptr(out), cur_stream()))
         return out
 
+    # ------------------------------------------------------------------ HF logits constraints (include/omchat_hip.h: omchat_set_constraints)
+    def set_constraints(self, b, prompt, max_new, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, min_length=0, eos=(),
+                        suppress_tokens=(), begin_suppress_tokens=()):
+        """every following token pick of rows 0..b-1 (argmax or sampler) excludes what HF's NoRepeatNGram, NoBadWords, MinLength,
+        MinNewTokensLength, SuppressTokens and SuppressTokensAtBegin processors would set to -inf.  prompt: the b prompt rows as HF's
+        processors see them (lists of ids, -200 sentinels and pads included); every decode step appends the token it is fed on the device.
+        max_new: the most decode steps that follow.  Sticky until constraints_off() (or b = 0)."""
+        torch = _torch()
+        i32 = lambda xs: torch.tensor([int(x) for x in xs] or [0], dtype=torch.int32)
+        words = [list(w) for w in (bad_words_ids or [])]
+        off = [0]
+        for w in words:
+            off.append(off[-1] + len(w))
+        eos, sup, bsup = list(eos or ()), list(suppress_tokens or ()), list(begin_suppress_tokens or ())
+        rows = [list(r) for r in prompt]
+        t_eos, t_sup, t_bsup, t_bw, t_off = i32(eos), i32(sup), i32(bsup), i32([i for w in words for i in w]), i32(off)
+        t_ids, t_len = i32([i for r in rows for i in r]), i32([len(r) for r in rows])
+        check(self.lib.omchat_set_constraints(self.h, int(b), int(no_repeat_ngram_size or 0), int(min_new_tokens or 0), int(min_length or 0),
+                                              ptr(t_eos), len(eos), ptr(t_sup), len(sup), ptr(t_bsup), len(bsup), ptr(t_bw), ptr(t_off),
+                                              len(words), ptr(t_ids), ptr(t_len), int(max_new), cur_stream()))
+
+    def constraints_off(self):
+        check(self.lib.omchat_set_constraints(self.h, 0, 0, 0, 0, None, 0, None, 0, None, 0, None, None, 0, None, None, 0, cur_stream()))
+
     # ------------------------------------------------------------------ beam search (include/omchat_hip.h: omchat_beam_begin)
     def beam_begin(self, b, num_beams, length_penalty=1.0, early_stopping=False, eos=(), max_new=20, prompt_len=None):
         """after the prefill of b equal-length prompts: HF's _beam_search state on the device.  early_stopping: False, True or "never"."""

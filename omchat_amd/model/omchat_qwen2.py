@@ -281,7 +281,10 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         call records what sequence 0's cache holds when it returns; the next reuse_cache=True call keeps the longest common prefix of that
         record and its own prompt -- tiles are compared bit for bit, equal ones reuse their feature rows -- and prefills only the rest
         (Engine.prefill_extend).  Kept slots written by decode steps came from the GEMV forms, so a position's logits can differ in the
-        last bits from a fresh prefill's, and ids at near-ties only.  Default False: nothing is kept."""
+        last bits from a fresh prefill's, and ids at near-ties only.  Default False: nothing is kept.
+        no_repeat_ngram_size, bad_words_ids, min_new_tokens, min_length, suppress_tokens, begin_suppress_tokens (also read from
+        generation_config): HF's processors of the same names as a ban stage on the device in front of the pick,
+        greedy or sampled; refused with num_beams > 1 and with prompt_lookup_num_tokens."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -295,6 +298,13 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 raise NotImplementedError("reuse_cache=True with the e4m3 KV cache, fp8 x fp8 prefill GEMMs or tensor parallelism is not "
                                           "implemented (DESIGN.md section 7)")
         lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
+        # HF's token-banning arguments (omchat_amd/constraints.py): resolved and refused here, before any work
+        from ..constraints import resolve_constraints
+        eos_ids = eos_token_id if eos_token_id is not None else gc.eos_token_id
+        eos_ids = list(eos_ids) if isinstance(eos_ids, (list, tuple)) else ([eos_ids] if eos_ids is not None else [])
+        con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None)
+        if con is None:                                               # sticky context state, like the sampler: off unless this call sets it
+            self.engine.constraints_off()                             # (set below, after the prefill; equal parameters keep the decode graphs)
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -317,6 +327,9 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         # then the (max, index) exchange the decode step uses (model.hip: greedy_pick); no torch re-statement on the gathered logits.
         # Sampling: the same seam with the sampler (omchat_sample); the decode steps below then sample too, the penalty's seen set growing
         # on the device.  HF drives the processors with input_ids (the prompt, pads included) + the generated ids.
+        if con is not None:
+            # the history HF's processors see: the prompt rows as passed (-200 sentinels and pads included) + the ids every step is fed
+            self.engine.set_constraints(b, input_ids.tolist(), max_new_tokens, **con)
         if smp is not None:
             seen = [[int(i) for i in row if int(i) >= 0] for row in input_ids.tolist()]
             self.engine.set_sampling(b, seen=seen, **smp)
