@@ -184,6 +184,23 @@ int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngram_size, int
                            const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
                            const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
                            const int32_t* prompt_len, int max_new, void* stream);
+/* ---- per-token log-probabilities of the picked ids (generate(output_logprobs=True)) ---------------------------------- */
+/* omchat_set_logprobs: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both
+ * masked steps, the captured decode graph -- also records two fp32 numbers on the device, without a host sync: raw = log_softmax(logits)[id]
+ * over the whole vocabulary (HF: compute_transition_scores(sequences, out.logits, normalize_logits=True)) and processed =
+ * log_softmax(scores)[id], scores = what HF's processors leave of the row (banned ids at -inf, repetition penalty with the seen set from
+ * before the pick, / temperature, ids outside the top-k / top-p kept set at -inf; HF: the same call on out.scores).  An id whose processed
+ * value is -inf records -inf.  Greedy without constraints: processed is raw, bit for bit.  The record holds max_new picks per row (a pick
+ * beyond it is refused before anything is enqueued), is grown on demand, never shrunk, and counted in omchat_device_bytes; every call resets
+ * the rows' counters to 0.  omchat_kv_rewind takes the counters back with the slots.  b = 0 switches it off: no launch, allocation or graph
+ * node remains.  Refused: a beam search in progress; omchat_decode_verify and omchat_beam_begin refuse while it is on, omchat_greedy while
+ * it and sampling are both on.  Switching on or off, another b, or a max_new beyond the record's capacity drops the captured decode graphs; a max_new
+ * within it keeps them.  While it is on, omchat_kv_rewind must cover all its rows (b >= the b given here).  Under tensor parallelism
+ * the ranks' partial sums cross in one fp32 all-reduce and every rank records the same numbers. */
+int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream);
+/* host copy of the record of rows 0..b-1: raw / processed host fp32 [b][max_len] (entries behind a row's count are left as they are),
+ * counts host int32 [b] = picks recorded per row.  Synchronises the device. */
+int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* processed, int32_t* counts, int max_len);
 int omchat_kv_lengths(omchat_ctx* ctx, int32_t* out, int b);      /* host copy of the current KV lengths */
 /* take back the last n decode steps of sequences 0..b-1 (generate() enqueues step k + 1 before it has read token k on the host, as the
  * reference's HF loop cannot; when token k ends the generation -- EOS, a stopping criterion -- that step is forgotten).  Synchronises. */
@@ -513,6 +530,13 @@ int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_len, const 
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */
 int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
                      const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream);
+/* context-free log-probability stage of omchat_set_logprobs (test hook): logits device fp32 [b][ld] (ld >= V), ids host int32 [b] (the picked
+ * ids), ban device uint32 [b][(V + 31) / 32] or NULL (set bit = processed value -inf), seen ids as omchat_op_sample takes them (read when
+ * rep_penalty != 1), newly_seen host int32 [b] or NULL (!= 0: the pick set its id's seen bit, so the id counts as unseen), thr device uint32 [b]
+ * or NULL (omchat_op_sample's thr_out; 0 = everything kept).  raw_out / processed_out device fp32 [b].  Synchronises. */
+int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
+                            float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
+                            const uint32_t* thr, float* raw_out, float* processed_out, void* stream);
 /* context-free beam step (test hook of omchat_beam_step's selection, TP = 1): logits fp32 [rows, V] (rows = b at t = 0, else b*N), step t
  * of max_new; state: device int32 [omchat_beam_state_words(b, N, max_new)] carried from call to call (initialised by the t = 0 call).
  * Outputs device int32: tokens [b*N], parents [b*N] (rows; a row's own index at t = 0 and for frozen prompts), done_word [1]. */

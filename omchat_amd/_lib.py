@@ -54,6 +54,8 @@ _SIGS = {
     "omchat_set_constraints": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
+    "omchat_set_logprobs": (_i, [_vp, _i, _i, _vp]),
+    "omchat_read_logprobs": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
     "omchat_beam_begin": (_i, [_vp, _i, _i, _f, _i, _vp, _i, _i, _i, _vp]),
     "omchat_beam_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_beam_result": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
@@ -118,6 +120,7 @@ _SIGS = {
     "omchat_op_rope_kv_q8": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_argmax": (_i, [_vp, _i, _i, _vp, _vp]),
     "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
+    "omchat_op_token_logprob": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_constrain": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "omchat_beam_state_words": (_sz, [_i, _i, _i]),
     "omchat_op_beam_select": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

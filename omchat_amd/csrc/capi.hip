@@ -408,6 +408,57 @@ extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed
   return rc;
 }
 
+extern "C" int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
+                                       float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
+                                       const uint32_t* thr, float* raw_out, float* processed_out, void* stream) {
+  OM_CHECK(logits && ids && raw_out && processed_out && b >= 1 && V >= 1 && ld >= V, "bad argument");
+  OM_CHECK(temperature > 0.f && rep_penalty > 0.f, "sampling parameters out of range");
+  const int bmw = (V + 31) / 32;
+  std::vector<uint32_t> bm((size_t)b * bmw, 0u);
+  std::vector<int> last(b, -1);
+  const bool pen = rep_penalty != 1.f && seen_ids && n_seen_per_row;
+  size_t off = 0;
+  for (int i = 0; i < b; ++i) {
+    OM_CHECK(ids[i] >= 0 && ids[i] < V, "picked id outside the vocabulary");
+    if (!pen) continue;
+    for (int j = 0; j < n_seen_per_row[i]; ++j) {
+      const int id = seen_ids[off + j];
+      if (id >= 0 && id < V) bm[(size_t)i * bmw + (id >> 5)] |= 1u << (id & 31);
+    }
+    off += (size_t)n_seen_per_row[i];
+    if (newly_seen && newly_seen[i]) {      // as smp_commit leaves it: the bit set, its index remembered
+      bm[(size_t)i * bmw + (ids[i] >> 5)] |= 1u << (ids[i] & 31);
+      last[i] = ids[i];
+    }
+  }
+  hipStream_t s = S(stream);
+  const size_t wsb = logprob_ws_bytes(b), bmb = bm.size() * 4, rb = ((size_t)b * 4 + 15) / 16 * 16;
+  char* mem = nullptr;
+  OM_HIP(hipMalloc(&mem, wsb + bmb + 5 * rb));
+  uint32_t* d_bm = (uint32_t*)(mem + wsb);
+  int* d_ids = (int*)(mem + wsb + bmb);
+  int* d_last = (int*)(mem + wsb + bmb + rb);
+  int* d_cnt = (int*)(mem + wsb + bmb + 2 * rb);
+  float* d_rec = (float*)(mem + wsb + bmb + 3 * rb);      // [2][1][b]
+  hipMemcpyAsync(d_bm, bm.data(), bmb, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_ids, ids, (size_t)b * 4, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_last, last.data(), (size_t)b * 4, hipMemcpyHostToDevice, s);
+  hipMemsetAsync(d_cnt, 0, (size_t)b * 4, s);
+  LogprobArgs a;
+  a.raw = logits; a.raw_ld = ld; a.b = b; a.V = V; a.ids = d_ids; a.ban = ban; a.bm_words = bmw;
+  if (pen) { a.seen = d_bm; a.last_set = d_last; }
+  a.temperature = temperature; a.penalty = rep_penalty; a.thr = thr; a.thr_stride = 1;
+  a.ws = mem; a.rec = d_rec; a.cnt = d_cnt; a.max_new = 1; a.rec_ld = b;
+  int rc = launch_logprob(a, s);
+  if (!rc) {
+    hipMemcpyAsync(raw_out, d_rec, (size_t)b * 4, hipMemcpyDeviceToDevice, s);
+    hipMemcpyAsync(processed_out, d_rec + b, (size_t)b * 4, hipMemcpyDeviceToDevice, s);
+  }
+  hipStreamSynchronize(s);
+  hipFree(mem);
+  return rc;
+}
+
 static_assert(CON_NGRAM_MAX == OMCHAT_CON_MAX_NGRAM && CON_EOS_MAX == OMCHAT_CON_MAX_EOS && CON_SUPPRESS_MAX == OMCHAT_CON_MAX_SUPPRESS &&
               CON_BAD_WORDS_MAX == OMCHAT_CON_MAX_BAD_WORDS && CON_BAD_WORD_IDS_MAX == OMCHAT_CON_MAX_BAD_WORD_IDS, "constraint caps: kernels.h and omchat_hip.h");
 

@@ -389,6 +389,33 @@ size_t sample_ws_bytes(int b);
 int launch_sample(const SampleArgs& a, hipStream_t s);
 // take back n picks: clears the bit the last pick set (n == 1), step -= n
 int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s);
+// where the last launch_sample on (ws, b) left row r's kept-set threshold key: words[r * *stride]; nullptr when the parameters keep every token
+const uint32_t* sample_thr_words(const void* ws, int b, int V_total, int top_k, double top_p, int* stride);
+// per-token log-probabilities of picked ids (logprob.hip; tests/logprob_ref.py restates it).  Rank-local fp32 logits
+// [b, V]; raw = log_softmax(raw)[id], processed = log_softmax(scores)[id] with scores evaluated on the fly from `proc` (the banned copy of
+// the constraints, or raw): ban bitmap, repetition penalty over `seen` (the bit the pick itself set, last_set, not counted), / temperature,
+// kept iff smp_key(value) >= thr[row * thr_stride] (thr == nullptr: everything kept; top1: only the maxima are kept, the sampler's top_k == 1).
+// An id that is not among the maxima records -inf under top1, as any cut id does.
+// Both land in rec = float [2][max_new][rec_ld] at column `row`, line cnt[row], and cnt[row] advances.  tp > 1: one xchg of `table`.
+struct LogprobArgs {
+  const float* raw = nullptr; int raw_ld = 0;
+  const float* proc = nullptr; int proc_ld = 0;     // nullptr: raw
+  int b = 0, V = 0, rank = 0, tp = 1;
+  const int* ids = nullptr;                          // [b] picked ids, global index, device
+  const uint32_t* ban = nullptr;                     // optional [b][bm_words]
+  const uint32_t* seen = nullptr; int bm_words = 0; const int* last_set = nullptr;
+  float temperature = 1.f, penalty = 1.f;
+  const uint32_t* thr = nullptr; int thr_stride = 1; int top1 = 0;
+  void* ws = nullptr;                                // logprob_ws_bytes(b)
+  float* table = nullptr;                            // logprob_table_bytes(b, tp), tp > 1
+  int (*xchg)(void* user, float* buf, size_t count, hipStream_t s) = nullptr;
+  void* xchg_user = nullptr;
+  float* rec = nullptr; int* cnt = nullptr; int max_new = 0, rec_ld = 0;
+};
+size_t logprob_ws_bytes(int b);
+size_t logprob_table_bytes(int b, int tp);
+int launch_logprob(const LogprobArgs& a, hipStream_t s);
+int launch_logprob_rewind(int* cnt, int b, int n, hipStream_t s);      // cnt[i] -= n for rows < b
 // HF logits constraints (constrain.hip; tests/constraints_ref.py restates the ban set).  The caps are the public
 // header's OMCHAT_CON_* (capi.hip asserts they agree).
 constexpr int CON_NGRAM_MAX = 64, CON_EOS_MAX = 16, CON_SUPPRESS_MAX = 1024, CON_BAD_WORDS_MAX = 1024, CON_BAD_WORD_IDS_MAX = 8192;

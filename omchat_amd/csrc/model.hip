@@ -212,6 +212,16 @@ struct omchat_ctx {
   int32_t* con_lists = nullptr;
   uint32_t* con_ban = nullptr; int con_bmw = 0;
   float* con_logits = nullptr;
+  // per-token log-probabilities of the picked ids (omchat_set_logprobs; logprob.hip): the record float [2][max_new][max_batch] (raw, processed)
+  // with a device counter per row, the slice partials, the exchange table under tensor parallelism; lp_picks: picks enqueued since the
+  // begin (host bound for the record's capacity)
+  struct Logprobs { bool on = false; int b = 0, max_new = 0; };
+  Logprobs lp;
+  int lp_picks = 0;
+  int lp_cap = 0;      // lines per plane of the record as allocated (>= lp.max_new; grown, never shrunk): the stride the kernels are given
+  int* lp_cnt = nullptr;
+  void* lp_ws = nullptr;
+  float* lp_table = nullptr;
   // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand
   // (state words, exchange table, length-penalty denominators, parent rows, stash of the KV gather)
   struct Beam { bool on = false; int b = 0, N = 0, KB = 0, max_new = 0, P = 0, es = 0, ns = 1, t = 0; float lp = 1.f; std::vector<int> eos; };
@@ -220,6 +230,7 @@ struct omchat_ctx {
   Grown bm_state, bm_table, bm_dn, bm_parents, bm_stash;
   Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
   Grown con_hist;    // token history of the logits constraints (omchat_set_constraints)
+  Grown lp_rec;      // record of the per-token log-probabilities (omchat_set_logprobs)
   bool bm_stash8 = false;
   std::vector<int> bm_hpos, bm_hlen;      // host sources of the fork's device lengths (alive until the next begin)
   int grow(Grown& g, size_t n) {
@@ -617,7 +628,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash, &ctx->ext_ws, &ctx->con_hist})
+  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash, &ctx->ext_ws, &ctx->con_hist, &ctx->lp_rec})
     if (g->p) hipFree(g->p);
   delete ctx;
 }
@@ -1307,11 +1318,41 @@ static int ban_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fe
   return 0;
 }
 
+// The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits, proc = what the pick ran on (the
+// banned copy when constraints are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
+static int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, const int32_t* ids, hipStream_t s) {
+  if (!ctx->lp.on) return 0;
+  const omchat_config& c = ctx->c;
+  LogprobArgs a;
+  a.raw = raw; a.raw_ld = c.t_vocab; a.proc = proc; a.proc_ld = c.t_vocab;
+  a.b = std::min(b, ctx->lp.b); a.V = c.t_vocab; a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
+  a.ids = ids;
+  if (ctx->smp.on) {
+    a.temperature = ctx->smp.temperature; a.penalty = ctx->smp.penalty;
+    if (ctx->smp.penalty != 1.f) { a.seen = ctx->smp_bm; a.bm_words = ctx->smp_bmw; a.last_set = ctx->smp_last; }
+    a.top1 = ctx->smp.top_k == 1;
+    a.thr = sample_thr_words(ctx->smp_ws, b, c.t_vocab_total, ctx->smp.top_k, ctx->smp.top_p, &a.thr_stride);
+  }
+  a.ws = ctx->lp_ws; a.table = ctx->lp_table; a.xchg = smp_xchg; a.xchg_user = ctx;
+  a.rec = (float*)ctx->lp_rec.p; a.cnt = ctx->lp_cnt; a.max_new = ctx->lp_cap; a.rec_ld = c.max_batch;
+  return launch_logprob(a, s);
+}
+
+// one more pick feeds the record: refuse before anything is enqueued when it is full (max_new of omchat_set_logprobs)
+static int lp_room(omchat_ctx* ctx) {
+  OM_CHECK(!ctx->lp.on || ctx->lp_picks < ctx->lp.max_new, "logprobs: more picks than the max_new given to omchat_set_logprobs");
+  return 0;
+}
+
 // the token pick of a step: greedy unless omchat_set_sampling switched the sampler on; `advance` moves the decode positions in the same launch
 static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false,
                      const int32_t* fed = nullptr) {
+  const float* raw = lg;
   TRY(ban_stage(ctx, &lg, b, fed, s));
-  if (!ctx->smp.on) return greedy_pick(ctx, lg, b, next_tokens, s, advance);
+  if (!ctx->smp.on) {
+    TRY(greedy_pick(ctx, lg, b, next_tokens, s, advance));
+    return logprob_stage(ctx, raw, lg, b, next_tokens, s);
+  }
   const omchat_config& c = ctx->c;
   SampleArgs a;
   a.logits = lg; a.ld = c.t_vocab; a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total;
@@ -1322,13 +1363,20 @@ static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_toke
   if (advance) { a.adv_pos = ctx->d_pos; a.adv_len = ctx->d_len; }
   a.out = next_tokens; a.ws = ctx->smp_ws; a.table = ctx->tp_table;
   a.xchg = smp_xchg; a.xchg_user = ctx;
-  return launch_sample(a, s);
+  TRY(launch_sample(a, s));
+  return logprob_stage(ctx, raw, lg, b, next_tokens, s);
 }
 
 extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  TRY(lp_room(ctx));
+  // (the sampler's state is not this pick's: with sampling on, the first token comes from omchat_sample)
+  OM_CHECK(!ctx->lp.on || !ctx->smp.on, "logprobs: omchat_greedy while sampling is on (omchat_sample picks the first token then)");
+  if (ctx->lp.on) ctx->lp_picks += 1;
+  const float* raw = logits;
   TRY(ban_stage(ctx, &logits, b, nullptr, (hipStream_t)stream));
-  return greedy_pick(ctx, logits, b, next_tokens, (hipStream_t)stream);
+  TRY(greedy_pick(ctx, logits, b, next_tokens, (hipStream_t)stream));
+  return logprob_stage(ctx, raw, logits, b, next_tokens, (hipStream_t)stream);
 }
 
 extern "C" int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float* logits, void* stream) {
@@ -1972,6 +2020,65 @@ extern "C" int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngra
   return 0;
 }
 
+// Per-token log-probabilities (include/omchat_hip.h).  The record and its geometry live in the kernel arguments of the captured decode graphs:
+// switching on or off, another b / max_new or a record that had to grow drops them.
+extern "C" int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  const omchat_config& c = ctx->c;
+  auto drop_graphs = [&]() {
+    for (auto& kv : ctx->graphs) destroy_graph(kv.second);
+    ctx->graphs.clear();
+  };
+  if (b <= 0) {
+    if (ctx->lp.on) drop_graphs();
+    ctx->lp = omchat_ctx::Logprobs{};
+    ctx->lp_picks = 0;
+    return 0;
+  }
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(b <= c.max_batch, "logprobs: batch exceeds max_batch");
+  OM_CHECK(max_new >= 1, "logprobs: max_new >= 1");
+  OM_CHECK(!ctx->beam.on, "logprobs: a beam search is active (it reports sequences_scores)");
+  if (!ctx->lp_cnt) {
+    TRY(ctx->alloc((void**)&ctx->lp_cnt, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc(&ctx->lp_ws, logprob_ws_bytes(c.max_batch)));
+    if (ctx->tp_size > 1) TRY(ctx->alloc((void**)&ctx->lp_table, logprob_table_bytes(c.max_batch, ctx->tp_size)));
+  }
+  // the captured graphs hold the record's address, its capacity (the stride of the processed plane) and b: another max_new within the
+  // capacity keeps them (the host refuses the picks beyond it)
+  void* old = ctx->lp_rec.p;
+  if (max_new > ctx->lp_cap) {
+    TRY(ctx->grow(ctx->lp_rec, (size_t)2 * max_new * c.max_batch * 4));
+    ctx->lp_cap = max_new;
+  }
+  if (!ctx->lp.on || ctx->lp.b != b || old != ctx->lp_rec.p) drop_graphs();
+  ctx->lp.on = true; ctx->lp.b = b; ctx->lp.max_new = max_new;
+  ctx->lp_picks = 0;
+  OM_HIP(hipMemsetAsync(ctx->lp_cnt, 0, (size_t)c.max_batch * 4, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* processed, int32_t* counts, int max_len) {
+  OM_CHECK(ctx && raw && processed && counts, "null argument");
+  OM_CHECK(ctx->lp.on && b >= 1 && b <= ctx->lp.b, "omchat_read_logprobs: rows that omchat_set_logprobs switched on");
+  const int mb = ctx->c.max_batch, mn = ctx->lp_cap;
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<float> rec((size_t)2 * mn * mb);
+  std::vector<int> cnt(mb);
+  OM_HIP(hipMemcpy(rec.data(), ctx->lp_rec.p, rec.size() * 4, hipMemcpyDeviceToHost));
+  OM_HIP(hipMemcpy(cnt.data(), ctx->lp_cnt, cnt.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < b; ++i) {
+    const int n = std::min(std::max(cnt[i], 0), ctx->lp.max_new);
+    OM_CHECK(n <= max_len, "omchat_read_logprobs: max_len too small");
+    counts[i] = n;
+    for (int t = 0; t < n; ++t) {
+      raw[(size_t)i * max_len + t] = rec[(size_t)t * mb + i];
+      processed[(size_t)i * max_len + t] = rec[((size_t)mn + t) * mb + i];
+    }
+  }
+  return 0;
+}
+
 // one more decode step feeds the history: refuse before the step is enqueued when it has no room left (max_new of omchat_set_constraints)
 static int con_count_step(omchat_ctx* ctx) {
   if (!ctx->con.on) return 0;
@@ -1983,6 +2090,8 @@ static int con_count_step(omchat_ctx* ctx) {
 // the first token after the prefill (omchat_greedy's sampled counterpart): advances the step counters, not the decode positions
 extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  TRY(lp_room(ctx));
+  if (ctx->lp.on) ctx->lp_picks += 1;
   return pick_next(ctx, logits, b, next_tokens, (hipStream_t)stream);
 }
 
@@ -2029,7 +2138,9 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   // a weight reload (omchat_load_tensor) leaves the e4m3 replica stale: re-quantise IN PLACE before streaming it (same device
   // pointers, so a captured decode graph stays valid and replays the fresh bytes)
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
+  if (next_tokens) TRY(lp_room(ctx));
   TRY(con_count_step(ctx));
+  if (ctx->lp.on && next_tokens) ctx->lp_picks += 1;
   ctx->graph_steps++;
   // graph replay needs replay-invariant arguments: single-GPU fused path only; with profiling on, every 8th step runs eagerly
   // so that the HIP-event brackets of the dominant kernel are still recorded inside the timed region
@@ -2082,6 +2193,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(!ctx->smp.on, "sampling is on: prompt-lookup decoding is greedy only");
   OM_CHECK(!ctx->con.on, "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
   OM_CHECK(!ctx->beam.on, "a beam search is active");
+  OM_CHECK(!ctx->lp.on, "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
   OM_CHECK(!(ctx->fp8_kv && ctx->kv8_valid), "the e4m3 KV cache is not implemented");
   const int L = ctx->h_len[0];
   OM_CHECK(L >= 1, "decode before prefill");
@@ -2136,7 +2248,9 @@ extern "C" int omchat_decode_step_masked(omchat_ctx* ctx, const int32_t* tokens,
     OM_CHECK(positions[i] >= 0 && positions[i] < c.max_seq, "position outside the RoPE table");
     OM_CHECK(key_mask[(size_t)i * mask_ld + Lc] != 0, "the new token must see itself");
   }
+  if (next_tokens) TRY(lp_room(ctx));
   TRY(con_count_step(ctx));
+  if (ctx->lp.on && next_tokens) ctx->lp_picks += 1;
   ctx->mask_on_device = false;      // the device copy holds THIS step's mask, zero-padded: omchat_decode_step_masked_next needs a new begin
   OM_HIP(hipMemsetAsync(ctx->d_mask, 0, (size_t)b * ctx->mask_sb, s));
   OM_HIP(hipMemcpy2DAsync(ctx->d_mask, (size_t)ctx->mask_sb, key_mask, (size_t)mask_ld, (size_t)Lc + 1, (size_t)b, hipMemcpyHostToDevice, s));
@@ -2185,7 +2299,9 @@ extern "C" int omchat_decode_step_masked_next(omchat_ctx* ctx, const int32_t* to
   TRY(masked_common_checks(ctx, b));
   OM_CHECK(ctx->mask_on_device, "omchat_decode_step_masked_next: call omchat_masked_decode_begin after the prefill (and after any omchat_decode_step_masked)");
   const int Lc = ctx->pre_S + ctx->masked_steps;
+  if (next_tokens) TRY(lp_room(ctx));
   TRY(con_count_step(ctx));
+  if (ctx->lp.on && next_tokens) ctx->lp_picks += 1;
   const int rc = decode_body(ctx, tokens, b, Lc + 1, logits, next_tokens, (hipStream_t)stream, false, true, true);
   if (rc) return rc;
   ctx->masked_steps += 1;
@@ -2327,6 +2443,7 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   OM_CHECK(ctx && b >= 1 && b <= (int)ctx->h_len.size() && n >= 0, "bad argument");
   if (n == 0) return 0;
   // every refusal before anything is enqueued or changed: the sampler's counters, the constraint history and the KV lengths stay in step
+  OM_CHECK(!ctx->lp.on || b >= ctx->lp.b, "rewind of fewer rows than omchat_set_logprobs switched on: the rows' records would fall out of step");
   OM_CHECK(!ctx->smp.on || n == 1 || ctx->smp.penalty == 1.f,
            "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded");
   if (ctx->dec_mode == 2) {
@@ -2338,6 +2455,11 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
     // the sampler's step counters go back with the slots, and the seen bit the last pick set is cleared (only that pick is recorded)
     TRY(launch_sample_rewind(ctx->smp.penalty != 1.f ? ctx->smp_bm : nullptr, ctx->smp_bmw, ctx->smp_last, ctx->smp_step, b, n,
                              (hipStream_t)stream));
+  }
+  if (ctx->lp.on) {
+    // the record forgets the picks of those steps
+    TRY(launch_logprob_rewind(ctx->lp_cnt, std::min(b, ctx->lp.b), n, (hipStream_t)stream));
+    ctx->lp_picks = std::max(0, ctx->lp_picks - n);
   }
   if (ctx->con.on) {
     // the history forgets the fed ids with the slots
@@ -2395,6 +2517,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   const int N = num_beams;
   OM_CHECK(b >= 1 && N >= 2 && N <= BEAM_NMAX, "beam search: b >= 1 and 2 <= num_beams <= 16");
   OM_CHECK(!ctx->con.on, "beam search: constraints are on (omchat_set_constraints with b = 0 first); HF applies them to log-softmax scores there");
+  OM_CHECK(!ctx->lp.on, "beam search: logprobs are on (omchat_set_logprobs with b = 0 first); a beam search reports sequences_scores");
   OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
   OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
   const int KB = std::max(2, 1 + n_eos) * N;

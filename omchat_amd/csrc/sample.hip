@@ -5,6 +5,7 @@
 // probability mass, max keys), so the kept set -- and with the global-index noise the picked id -- is the same at every TP degree and in
 // every launch order.  tests/sampling_ref.py is the CPU restatement, bit for bit.
 #include "kernels.h"
+#include "sample_common.h"
 #include <limits.h>
 #include <math.h>
 
@@ -33,19 +34,6 @@ __device__ __forceinline__ float smp_noise(uint64_t rk, uint32_t gi) {
   const uint64_t h = smp_mix(rk + (uint64_t)gi * 0x9E3779B97F4A7C15ull);
   const double u = ((double)(h >> 12) + 0.5) * 0x1p-52;
   return (float)(-log(-log(u)));
-}
-__device__ __forceinline__ uint32_t smp_key(float f) {
-  uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);     // -0 and +0 are one key (HF compares values)
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float smp_unkey(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-// RepetitionPenaltyLogitsProcessor (seen: < 0 -> * p, else / p), then TemperatureLogitsWarper (/ T), in fp32 as HF computes them
-__device__ __forceinline__ float smp_penalised(const float* row, const uint32_t* seen, int i, float pen) {
-  float l = row[i];
-  if (seen && ((seen[i >> 5] >> (i & 31)) & 1u)) l = l < 0.f ? __fmul_rn(l, pen) : __fdiv_rn(l, pen);
-  return l;
 }
 __device__ __forceinline__ void smp_better(float& best, int& besti, float v, int i) {
   if (v > best || (v == best && i < besti)) { best = v; besti = i; }
@@ -310,6 +298,15 @@ __global__ void smp_rewind_kernel(uint32_t* bm, int bmw, int* last, int* step, i
 
 size_t sample_ws_bytes(int b) {
   return (size_t)b * (SMP_BINS * 8 + SMP_ST * 8 + SMP_XS * 4 + SMP_RACE_CH * 8);
+}
+
+// where the log-probability stage (logprob.hip) finds the kept-set threshold key that the last launch_sample with these parameters left for
+// row r: words[r * stride] (the low word of ST_THR); nullptr when the parameters keep every token
+const uint32_t* sample_thr_words(const void* ws, int b, int V_total, int top_k, double top_p, int* stride) {
+  const bool use = top_k != 1 && ((top_k > 1 && top_k < V_total) || top_p < 1.0);
+  if (!use) return nullptr;
+  *stride = SMP_ST * 2;
+  return (const uint32_t*)((const char*)ws + (size_t)b * SMP_BINS * 8) + ST_THR * 2;
 }
 
 int launch_sample(const SampleArgs& a, hipStream_t s) {

@@ -56,6 +56,7 @@ class Engine:
         self._prefix = None
         self._tile_key_next = 0
         self._ext_st = dict(kept_slots=0, prefilled_rows=0, tiles_encoded=0, tiles_reused=0)
+        self._lp_max_new, self._logprobs_on = 0, False      # set_logprobs
 
     def close(self):
         if getattr(self, "h", None):
@@ -463,7 +464,8 @@ class Engine:
         return [int(x) for x in out]
 
     def kv_rewind(self, b, n=1):
-        """forget the last n decode steps of sequences 0..b-1 (see include/omchat_hip.h: omchat_kv_rewind)"""
+        """forget the last n decode steps of sequences 0..b-1 (see include/omchat_hip.h: omchat_kv_rewind).  While set_logprobs is on, b
+        must cover all the rows it was switched on for: the rows' records go back together"""
         check(self.lib.omchat_kv_rewind(self.h, b, n, cur_stream()))
 
     def argmax(self, logits):
@@ -493,6 +495,32 @@ class Engine:
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=self.device)
         check(self.lib.omchat_sample(self.h, ptr(logits), logits.shape[0], ptr(out), cur_stream()))
         return out
+
+    # ------------------------------------------------------------------ per-token log-probabilities (include/omchat_hip.h: omchat_set_logprobs)
+    def set_logprobs(self, b, max_new):
+        """every following token pick of rows 0..b-1 (argmax or sampler, eager or in the decode graph) records the raw and the processed
+        log-probability of its id on the device; at most max_new picks.  Resets the rows' counters.  Sticky until
+        logprobs_off() (or b = 0)."""
+        check(self.lib.omchat_set_logprobs(self.h, int(b), int(max_new), cur_stream()))
+        self._lp_max_new = int(max_new)
+        self._logprobs_on = int(b) > 0
+
+    def logprobs_off(self):
+        check(self.lib.omchat_set_logprobs(self.h, 0, 0, cur_stream()))
+        self._logprobs_on = False
+
+    def read_logprobs(self, b):
+        """one synchronising copy of the record (the whole device record, every row and line, whatever b: a few KB) -> (raw fp32 [b, n],
+        processed fp32 [b, n], counts list); n = the longest row's count, entries behind a row's own count are 0.  Refused by the library
+        when logprobs are off."""
+        torch = _torch()
+        n = max(self._lp_max_new, 1)
+        raw = torch.zeros(b, n, dtype=torch.float32)
+        proc = torch.zeros(b, n, dtype=torch.float32)
+        cnt = torch.zeros(b, dtype=torch.int32)
+        check(self.lib.omchat_read_logprobs(self.h, int(b), ptr(raw), ptr(proc), ptr(cnt), n))
+        m = int(cnt.max()) if b else 0
+        return raw[:, :m].contiguous(), proc[:, :m].contiguous(), [int(x) for x in cnt]
 
     # ------------------------------------------------------------------ HF logits constraints (include/omchat_hip.h: omchat_set_constraints)
     def set_constraints(self, b, prompt, max_new, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, min_length=0, eos=(),

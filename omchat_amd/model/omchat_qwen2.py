@@ -267,7 +267,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
                  repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
-                 num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, **kwargs):
+                 num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, output_logprobs=None, **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
@@ -284,7 +284,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         last bits from a fresh prefill's, and ids at near-ties only.  Default False: nothing is kept.
         no_repeat_ngram_size, bad_words_ids, min_new_tokens, min_length, suppress_tokens, begin_suppress_tokens (also read from
         generation_config): HF's processors of the same names as a ban stage on the device in front of the pick,
-        greedy or sampled; refused with num_beams > 1 and with prompt_lookup_num_tokens."""
+        greedy or sampled; refused with num_beams > 1 and with prompt_lookup_num_tokens.
+        output_logprobs=True with return_dict_in_generate=True (also read from generation_config): returns a
+        GenerateOutput whose .sequences is what the call returns otherwise, .logprobs [b, new] the log-probability of every generated id
+        under the model's raw distribution and .processed_logprobs [b, new] under the distribution the pick was made from (bans, repetition
+        penalty, temperature, top-k / top-p); recorded by the pick on the device, read back once at the end.  Positions behind a row's EOS,
+        where the sequence holds pad, are 0.  Refused with num_beams > 1 (sequences_scores) and with prompt_lookup_num_tokens."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -298,6 +303,16 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 raise NotImplementedError("reuse_cache=True with the e4m3 KV cache, fp8 x fp8 prefill GEMMs or tensor parallelism is not "
                                           "implemented (DESIGN.md section 7)")
         lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
+        olp = bool(output_logprobs if output_logprobs is not None else getattr(gc, "output_logprobs", False))
+        if olp:      # every refusal before any work
+            if not return_dict_in_generate:
+                raise ValueError("output_logprobs=True needs return_dict_in_generate=True: the log-probabilities come back as fields of a "
+                                 "GenerateOutput next to .sequences")
+            if nb > 1:
+                raise NotImplementedError("output_logprobs=True with num_beams > 1 is not implemented: beam search reports sequences_scores")
+            if lookup is not None:
+                raise NotImplementedError("output_logprobs=True with prompt_lookup_num_tokens is not implemented: a verify step's picks are "
+                                          "not recorded")
         # HF's token-banning arguments (omchat_amd/constraints.py): resolved and refused here, before any work
         from ..constraints import resolve_constraints
         eos_ids = eos_token_id if eos_token_id is not None else gc.eos_token_id
@@ -305,6 +320,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None)
         if con is None:                                               # sticky context state, like the sampler: off unless this call sets it
             self.engine.constraints_off()                             # (set below, after the prefill; equal parameters keep the decode graphs)
+        if not olp and getattr(self.engine, "_logprobs_on", False):   # sticky too: a call without the keyword records nothing
+            self.engine.logprobs_off()
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -330,6 +347,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if con is not None:
             # the history HF's processors see: the prompt rows as passed (-200 sentinels and pads included) + the ids every step is fed
             self.engine.set_constraints(b, input_ids.tolist(), max_new_tokens, **con)
+        if olp:
+            self.engine.set_logprobs(b, max_new_tokens)               # the prefill's pick below is record 0
         if smp is not None:
             seen = [[int(i) for i in row if int(i) >= 0] for row in input_ids.tolist()]
             self.engine.set_sampling(b, seen=seen, **smp)
@@ -357,7 +376,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 streamer.end()
             self._record_prefix(prompt_slots, gen)
             return torch.cat([input_ids.cpu(), torch.tensor([gen], dtype=torch.int64)], dim=1)
-        new = []
+        new, padded_out = [], []
         done = torch.zeros(b, dtype=torch.bool)
         # padded batch (rows of different spliced length, or left padding): decoded as the reference does it (omchat_arch.py:61-70).  HF generate
         # passes the token-level mask grown by one 1 per generated token and `images` on every step; the decode branch pads it with ones to the
@@ -392,6 +411,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             if pad is not None:
                 t_cpu = torch.where(done, torch.full_like(t_cpu, pad), t_cpu)
             new.append(t_cpu)
+            padded_out.append(done if pad is not None else torch.zeros_like(done))
             if streamer is not None:
                 streamer.put(t_cpu)
             done = done | torch.tensor([int(x) in eos for x in t_cpu])
@@ -407,7 +427,16 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if streamer is not None:
             streamer.end()
         self._record_prefix(prompt_slots, [int(t[0]) for t in new])
-        return torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+        seqs = torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+        if not olp:
+            return seqs
+        # the step enqueued ahead was taken back with its record: exactly one record per generated token
+        raw, proc, counts = self.engine.read_logprobs(b)
+        if counts != [len(new)] * b:
+            raise RuntimeError(f"log-probability record out of step with the generated tokens: {counts} records for {len(new)} tokens")
+        keep = ~torch.stack(padded_out, dim=1)
+        zero = torch.zeros((), dtype=torch.float32)
+        return GenerateOutput(seqs, torch.where(keep, raw, zero), torch.where(keep, proc, zero))
 
     def _forward_reuse(self, input_ids, images):
         """The prefill of generate(reuse_cache=True), b = 1: keeps the slots of sequence 0's cache that the new prompt shares with the
@@ -566,3 +595,14 @@ class BeamSearchOutput(dict):
     def __init__(self, sequences, sequences_scores):
         super().__init__(sequences=sequences, sequences_scores=sequences_scores)
         self.sequences, self.sequences_scores = sequences, sequences_scores
+
+
+class GenerateOutput(dict):
+    """generate(output_logprobs=True, return_dict_in_generate=True): `.sequences` [b, T + new] as the plain call returns them, `.logprobs`
+    [b, new] = log_softmax(logits)[token] of every generated token (HF: compute_transition_scores on out.logits with normalize_logits=True)
+    and `.processed_logprobs` [b, new] = the same under the processed scores the pick was made from (on out.scores); full-vocabulary
+    `scores` / `logits` tuples are not kept"""
+
+    def __init__(self, sequences, logprobs, processed_logprobs):
+        super().__init__(sequences=sequences, logprobs=logprobs, processed_logprobs=processed_logprobs)
+        self.sequences, self.logprobs, self.processed_logprobs = sequences, logprobs, processed_logprobs
