@@ -11,8 +11,10 @@
 // beam_finish_kernel (one workgroup per prompt) merges the slices, scores the candidates in HF's order of fp32 operations and updates the
 // running beams, the finished set and the per-prompt done flag.  A done prompt is frozen: later steps leave its state alone.
 // launch_kv_gather moves KV-cache rows (16-bit cache, and the e4m3 replica with its scales) between sequences.
-#include "kernels.h"
+#include "ctx.h"
 #include <math.h>
+#include <string.h>
+#include <algorithm>
 
 // no fused multiply-adds: the fp64 lse sum and every fp32 score are rounded after each operation, as tests/beam_ref.py rounds them
 #pragma clang fp contract(off)
@@ -390,5 +392,143 @@ int launch_kv_gather(const KvGatherArgs& a, const int* parents, int row0, int nr
   hipLaunchKernelGGL(kv_gather_kernel, dim3(nrows, a.kvh, a.layers), dim3(256), 0, s, a, parents, row0, nrows, -1, lo, hi, 1);
   hipLaunchKernelGGL(kv_gather_kernel, dim3(nrows, a.kvh, a.layers), dim3(256), 0, s, a, parents, row0, nrows, -1, lo, hi, 2);
   OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// context entry points (include/omchat_hip.h): the search state (BeamState, ctx.h) lives on the device
+// ---------------------------------------------------------------------------------------------------------
+static KvGatherArgs beam_kv_args(omchat_ctx* ctx, bool with_stash) {
+  const omchat_config& c = ctx->c;
+  KvGatherArgs g;
+  g.k = (char*)ctx->kcache; g.v = (char*)ctx->vcache;
+  g.layers = c.t_layers; g.kvh = c.t_kv_heads; g.max_seq = c.max_seq; g.rows_cap = c.max_batch;
+  const bool f8 = ctx->fp8_kv && ctx->kv8_valid;
+  if (f8) { g.k8 = (char*)ctx->k8cache; g.v8 = (char*)ctx->v8cache; g.ks = ctx->ks8; g.vs = ctx->vs8; }
+  if (with_stash) {
+    const int rows = ctx->beam.cur.b * ctx->beam.cur.N;
+    const size_t slots = (size_t)c.t_layers * rows * c.t_kv_heads * ctx->beam.cur.max_new;
+    char* p = (char*)ctx->beam.stash.p;
+    g.sk = p; g.sv = p + slots * 256;
+    if (f8 && ctx->beam.stash8) {
+      g.sk8 = p + slots * 512; g.sv8 = p + slots * 640;
+      g.sks = (float*)(p + slots * 768); g.svs = (float*)(p + slots * 772);
+    }
+    g.st_rows = rows; g.st_slots = ctx->beam.cur.max_new;
+  }
+  return g;
+}
+
+extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float length_penalty, int early_stopping, const int32_t* eos_ids,
+                                 int n_eos, int max_new, int prompt_tok_len, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  const int N = num_beams;
+  OM_CHECK(b >= 1 && N >= 2 && N <= BEAM_NMAX, "beam search: b >= 1 and 2 <= num_beams <= 16");
+  OM_CHECK(!ctx->pick.constraints_on(), "beam search: constraints are on (omchat_set_constraints with b = 0 first); HF applies them to log-softmax scores there");
+  OM_CHECK(!ctx->pick.logprobs_on(), "beam search: logprobs are on (omchat_set_logprobs with b = 0 first); a beam search reports sequences_scores");
+  OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
+  OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
+  const int KB = std::max(2, 1 + n_eos) * N;
+  OM_CHECK(KB <= BEAM_KMAX, "beam search: max(2, 1 + n_eos) * num_beams must not exceed 32");
+  OM_CHECK(early_stopping >= 0 && early_stopping <= 2, "beam search: early_stopping 0 (False), 1 (True) or 2 (never)");
+  OM_CHECK(isfinite(length_penalty), "beam search: length_penalty must be finite");
+  OM_CHECK(max_new >= 1 && prompt_tok_len >= 1 && prompt_tok_len + max_new - 1 <= c.max_seq, "beam search: prompt + max_new exceed max_seq");
+  OM_CHECK(c.t_vocab_total >= KB, "beam search: vocabulary smaller than the candidates kept per step");
+  const int ns = beam_slices(c.t_vocab_total, ctx->tp_size);
+  OM_CHECK(ns >= 1, "beam search: the vocabulary cannot be cut into equal slices of <= 20480 ids for this TP degree");
+  OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "beam search: a left-padded or masked-decode batch (pad equal or use b = 1)");
+  BeamState::Search& B = ctx->beam.cur;
+  B = BeamState::Search{};
+  B.b = b; B.N = N; B.KB = KB; B.max_new = max_new; B.P = prompt_tok_len; B.es = early_stopping; B.ns = ns; B.lp = length_penalty;
+  B.eos.assign(eos_ids, eos_ids + n_eos);
+  const int rows = b * N;
+  const size_t TS = (size_t)ns * (4 + 2 * KB);
+  const bool f8 = ctx->fp8_kv && ctx->kv8_valid;
+  const size_t slots = (size_t)c.t_layers * rows * c.t_kv_heads * max_new;
+  TRY(ctx->grow(ctx->beam.state, beam_state_words(b, N, max_new) * 4));
+  TRY(ctx->grow(ctx->beam.table, (rows * TS + 16) * 4));
+  TRY(ctx->grow(ctx->beam.dn, (size_t)(max_new + 1) * 4));
+  TRY(ctx->grow(ctx->beam.parents, (size_t)rows * 4));
+  TRY(ctx->grow(ctx->beam.stash, slots * (f8 ? 776 : 512)));
+  ctx->beam.stash8 = f8;
+  std::vector<float> dn(max_new + 1, 1.f);      // fp32(pow(g, length_penalty)): the Python float HF divides by, rounded as torch rounds it
+  for (int g = 1; g <= max_new; ++g) dn[g] = (float)pow((double)g, (double)length_penalty);
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemcpyAsync(ctx->beam.dn.p, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipStreamSynchronize(s));      // host vector
+  B.on = true;
+  return 0;
+}
+
+extern "C" int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* next_tokens, int32_t* done_word, void* stream) {
+  OM_CHECK(ctx && logits && next_tokens, "null argument");
+  BeamState::Search& B = ctx->beam.cur;
+  OM_CHECK(B.on, "omchat_beam_step without omchat_beam_begin (or after a new prefill)");
+  OM_CHECK(B.t < B.max_new, "beam search: max_new steps taken");
+  OM_CHECK(rows == (B.t == 0 ? B.b : B.b * B.N), "beam step: rows = b on the prefill logits, b * num_beams afterwards");
+  const omchat_config& c = ctx->c;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t TS = (size_t)B.ns * (4 + 2 * B.KB);
+  float* table = (float*)ctx->beam.table.p;
+  if (ctx->tp_size > 1) OM_HIP(hipMemsetAsync(table, 0, rows * TS * 4, s));
+  TRY(launch_beam_select(logits, c.t_vocab, rows, c.t_vocab, ctx->tp_rank, ctx->tp_size, B.ns, B.KB, table, s));
+  if (ctx->tp_size > 1) TRY(ctx->allreduce_f32(table, rows * TS, s));
+  BeamFinishArgs a;
+  a.table = table; a.ns = B.ns; a.K = a.KB = B.KB; a.V_total = c.t_vocab_total;
+  a.b = B.b; a.N = B.N; a.t = B.t; a.max_new = B.max_new; a.es = B.es; a.lp_pos = B.lp > 0.f;
+  a.dn = (const float*)ctx->beam.dn.p;
+  a.n_eos = (int)B.eos.size();
+  for (int q = 0; q < a.n_eos; ++q) a.eos[q] = B.eos[q];
+  a.state = (int*)ctx->beam.state.p; a.tokens = next_tokens; a.parents = (int*)ctx->beam.parents.p; a.done_word = done_word;
+  TRY(launch_beam_finish(a, s));
+  const int bN = B.b * B.N;
+  if (B.t == 0) {
+    // fork: prompt i's row -> rows i*N .. i*N+N-1, last prompt first (its target rows lie above every source row not yet read)
+    const KvGatherArgs g = beam_kv_args(ctx, false);
+    for (int i = B.b - 1; i >= 0; --i) TRY(launch_kv_gather(g, nullptr, i * B.N, B.N, i, 0, B.P, s));
+    ctx->beam.hpos.assign(bN, B.P);
+    ctx->beam.hlen.assign(bN, B.P + 1);
+    for (int r = 0; r < bN; ++r) ctx->h_len[r] = B.P;
+    OM_HIP(hipMemcpyAsync(ctx->d_pos, ctx->beam.hpos.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
+    OM_HIP(hipMemcpyAsync(ctx->d_len, ctx->beam.hlen.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
+  } else {
+    const int L = ctx->h_len[0];
+    for (int r = 1; r < bN; ++r) OM_CHECK(ctx->h_len[r] == L, "beam step: the beam rows differ in length");
+    if (L > B.P) TRY(launch_kv_gather(beam_kv_args(ctx, true), (const int*)ctx->beam.parents.p, 0, bN, -1, B.P, L, s));
+  }
+  B.t++;
+  return 0;
+}
+
+extern "C" int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t* lengths, float* scores, int max_len) {
+  OM_CHECK(ctx && tokens && lengths && scores, "null argument");
+  const BeamState::Search& B = ctx->beam.cur;
+  OM_CHECK(B.b > 0 && B.t > 0, "omchat_beam_result before a beam step");
+  OM_CHECK(num_return >= 1 && num_return <= B.N, "num_return_sequences must be in [1, num_beams]");
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<int> st(beam_state_words(B.b, B.N, B.max_new));
+  OM_HIP(hipMemcpy(st.data(), ctx->beam.state.p, st.size() * 4, hipMemcpyDeviceToHost));
+  const int bN = B.b * B.N;
+  const int* bp = st.data() + 6 * bN + 2 * B.b;
+  for (int i = 0; i < B.b; ++i)
+    for (int q = 0; q < num_return; ++q) {
+      const int e = i * B.N + q, o = i * num_return + q;
+      float sc; memcpy(&sc, &st[BST_FSC * bN + e], 4);
+      scores[o] = sc;
+      const int step = st[BST_FSTEP * bN + e];
+      const int n = step + 1;
+      OM_CHECK(n <= max_len, "beam result: max_len too small");
+      lengths[o] = n;
+      if (n == 0) continue;
+      tokens[(size_t)o * max_len + step] = st[BST_FTOK * bN + e];
+      int beam = st[BST_FPAR * bN + e];
+      for (int u = step - 1; u >= 0; --u) {
+        const int* rec = bp + ((size_t)u * bN + i * B.N + beam) * 2;
+        tokens[(size_t)o * max_len + u] = rec[1];
+        beam = rec[0];
+      }
+    }
   return 0;
 }

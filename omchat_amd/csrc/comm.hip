@@ -27,6 +27,7 @@
 // host reads with omchat_peer_error().
 #include "kernels.h"
 #include "../../include/omchat_hip.h"
+#include <rccl/rccl.h>
 #include <string.h>
 #include <vector>
 
@@ -518,4 +519,43 @@ extern "C" void omchat_peer_destroy(omchat_peer* p) {
   if (p->local) (void)hipFree(p->local);
   if (p->ctr) (void)hipFree(p->ctr);
   delete p;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// tensor-parallel bootstrap
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int omchat_comm_unique_id(char id[128]) {
+  static_assert(sizeof(ncclUniqueId) <= 128, "ncclUniqueId larger than 128 bytes");
+  ncclUniqueId u;
+  ncclResult_t r = ncclGetUniqueId(&u);
+  if (r != ncclSuccess) { omchat_set_error(std::string("ncclGetUniqueId: ") + ncclGetErrorString(r)); return 3; }
+  memset(id, 0, 128);
+  memcpy(id, &u, sizeof(u));
+  return 0;
+}
+extern "C" int omchat_comm_init(const char id[128], int rank, int size, void** comm_out) {
+  ncclUniqueId u;
+  memcpy(&u, id, sizeof(u));
+  ncclComm_t comm;
+  ncclResult_t r = ncclCommInitRank(&comm, size, u, rank);
+  if (r != ncclSuccess) { omchat_set_error(std::string("ncclCommInitRank: ") + ncclGetErrorString(r)); return 3; }
+  *comm_out = comm;
+  return 0;
+}
+extern "C" int omchat_comm_allreduce(void* comm, void* buf, size_t count, int dtype, void* stream) {
+  OM_CHECK(comm && buf, "null argument");
+  const ncclDataType_t t = dtype == OMCHAT_F16 ? ncclFloat16 : dtype == OMCHAT_BF16 ? ncclBfloat16 : ncclFloat32;
+  OM_CHECK(dtype == OMCHAT_F16 || dtype == OMCHAT_BF16 || dtype == OMCHAT_F32, "bad dtype");
+  ncclResult_t r = ncclAllReduce(buf, buf, count, t, ncclSum, (ncclComm_t)comm, (hipStream_t)stream);
+  if (r != ncclSuccess) { omchat_set_error(std::string("ncclAllReduce: ") + ncclGetErrorString(r)); return 3; }
+  return 0;
+}
+extern "C" int omchat_comm_count(void* comm, int* nranks) {
+  OM_CHECK(comm && nranks, "null argument");
+  ncclResult_t r = ncclCommCount((ncclComm_t)comm, nranks);
+  if (r != ncclSuccess) { omchat_set_error(std::string("ncclCommCount: ") + ncclGetErrorString(r)); return 3; }
+  return 0;
+}
+extern "C" void omchat_comm_destroy(void* comm) {
+  if (comm) ncclCommDestroy((ncclComm_t)comm);
 }

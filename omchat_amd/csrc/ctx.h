@@ -1,0 +1,324 @@
+// The context of one tensor-parallel rank and the state of the stages that own a part of it.  Private: for the .hip files that implement
+// context-level entry points (model.hip, pick.hip, beam.hip); the public interface is include/omchat_hip.h.
+#pragma once
+#include "kernels.h"
+#include "../../include/omchat_hip.h"
+#include <rccl/rccl.h>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+extern int g_fuse_peer_norm;      // model.hip: omchat_op_set_tuning key 9
+
+enum RouteKind { R_PLAIN = 0, R_GATE = 1, R_UP = 2, R_PATCH = 3 };
+struct Route {
+  void* dst = nullptr;
+  int64_t rows = 0, cols = 0;     // logical source shape (2-D view)
+  int64_t dst_ld = 0;             // destination row stride (elements)
+  int kind = R_PLAIN;
+  bool loaded = false;
+  float synth_std = 0.02f, synth_off = 0.f;
+};
+
+// a device buffer grown on demand and never shrunk (omchat_ctx::grow)
+struct Grown {
+  void* p = nullptr; size_t cap = 0;
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// The token pick of a step (pick.hip): ban stage, argmax or sampler, record stage -- with everything the three stages keep between picks.
+struct PickState {
+  void* arg_scratch = nullptr;      // partials of the two-stage argmax
+  float* tp_table = nullptr;        // (max, index) / sampler exchange table under tensor parallelism
+  // on-device sampling (omchat_set_sampling; sample.hip): uniform parameters for the batch, per-row device step counters, the repetition
+  // penalty's seen-token bitmap of this rank's vocabulary slice [max_batch][smp_bmw] and the local index of the bit each row's last pick set
+  struct Sampling { bool on = false; uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f; };
+  Sampling smp;
+  void* smp_ws = nullptr;
+  uint32_t* smp_bm = nullptr; int smp_bmw = 0;
+  int *smp_last = nullptr, *smp_step = nullptr;
+  // HF logits constraints (omchat_set_constraints; constrain.hip): uniform parameters, the rows' token history as HF's processors see it
+  // [max_batch][con_ld] with device lengths, the id lists, the ban bitmap of this rank's vocabulary slice (all-zero between picks) and the
+  // banned copy of the logits the pick runs on.  con_fed: decode steps fed since the begin (host bound for the history's capacity).
+  struct Constraints {
+    bool on = false; int b = 0, ngram = 0, min_new = 0, min_len = 0, n_eos = 0, n_sup = 0, n_bsup = 0, n_bw = 0;
+    bool operator==(const Constraints& o) const {
+      return on == o.on && b == o.b && ngram == o.ngram && min_new == o.min_new && min_len == o.min_len && n_eos == o.n_eos && n_sup == o.n_sup &&
+             n_bsup == o.n_bsup && n_bw == o.n_bw;
+    }
+  };
+  Constraints con;
+  int con_ld = 0, con_fed = 0, con_room = 0;
+  int *con_len = nullptr, *con_plen = nullptr;
+  int32_t* con_lists = nullptr;
+  uint32_t* con_ban = nullptr; int con_bmw = 0;
+  float* con_logits = nullptr;
+  // per-token log-probabilities of the picked ids (omchat_set_logprobs; logprob.hip): the record float [2][max_new][max_batch] (raw, processed)
+  // with a device counter per row, the slice partials, the exchange table under tensor parallelism; lp_picks: picks enqueued since the
+  // begin (host bound for the record's capacity)
+  struct Logprobs { bool on = false; int b = 0, max_new = 0; };
+  Logprobs lp;
+  int lp_picks = 0;
+  int lp_cap = 0;      // lines per plane of the record as allocated (>= lp.max_new; grown, never shrunk): the stride the kernels are given
+  int* lp_cnt = nullptr;
+  void* lp_ws = nullptr;
+  float* lp_table = nullptr;
+  Grown con_hist;    // token history of the logits constraints (omchat_set_constraints)
+  Grown lp_rec;      // record of the per-token log-probabilities (omchat_set_logprobs)
+  bool sampling_on() const { return smp.on; }
+  bool constraints_on() const { return con.on; }
+  bool logprobs_on() const { return lp.on; }
+  void release() { con_hist.release(); lp_rec.release(); }
+};
+
+// beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand
+// (state words, exchange table, length-penalty denominators, parent rows, stash of the KV gather)
+struct BeamState {
+  struct Search { bool on = false; int b = 0, N = 0, KB = 0, max_new = 0, P = 0, es = 0, ns = 1, t = 0; float lp = 1.f; std::vector<int> eos; };
+  Search cur;
+  Grown state, table, dn, parents, stash;
+  bool stash8 = false;
+  std::vector<int> hpos, hlen;      // host sources of the fork's device lengths (alive until the next begin)
+  bool on() const { return cur.on; }
+  void end() { cur.on = false; }
+  void release() { for (Grown* g : {&state, &table, &dn, &parents, &stash}) g->release(); }
+};
+
+struct omchat_ctx {
+  omchat_config c;
+  int dt = OMCHAT_BF16;
+  int tp_rank = 0, tp_size = 1;
+  ncclComm_t comm = nullptr;
+  std::vector<void*> allocs;
+  size_t bytes = 0;
+  std::unordered_map<std::string, Route> routes;
+
+  // derived geometry
+  int v_np = 0, v_ntok = 0, v_Cq = 0, v_kpad = 0, v_hd = 128;
+  int t_qdim = 0, t_kvdim = 0, t_qkvdim = 0;
+
+  // weights (device, compute dtype)
+  struct VitLayer { void *ls1, *ls2, *n1, *n2, *n1b, *n2b, *wqkv, *qn, *kn, *wproj, *bproj, *w1, *b1, *w2, *b2; };
+  struct DecLayer { void *ln1, *ln2, *wqkv, *bqkv, *wo, *wgu, *wd; };
+  // weight-only fp8 replica of the decode-streamed decoder weights (omchat_enable_fp8_decode): OCP e4m3 bytes + one fp32
+  // scale per output row; batch-1 decode steps stream these instead of the 16-bit weights, prefill keeps the 16-bit ones
+  struct DecLayer8 { void *wqkv, *wo, *wgu, *wd; float *sqkv, *so, *sgu, *sd; };
+  std::vector<DecLayer8> dl8;
+  // packed replica of the same weights for BATCHED decode steps (2 <= b <= 32): MFMA fragment order, every wave load 1 KiB contiguous
+  // (gemv.hip: gemv_pk_kernel; +14 GB at OmChat-13B, built on the first batched step; omchat_op_set_tuning key 6 = 0 disables it)
+  struct DecLayerP { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; };
+  std::vector<DecLayerP> dlp;
+  void* t_lmP = nullptr;
+  bool pk_ready = false, pk_unavailable = false;
+  void* t_lm8 = nullptr; float* t_lm8_s = nullptr;
+  bool fp8_decode = false, fp8_stale = false;
+  // BASELINE configs[4]: fp8 KV cache for decode (e4m3 bytes in the layout of the 16-bit cache + one fp32 scale per (layer, sequence,
+  // kv head, position)) and fp8 x fp8 MFMA prefill GEMMs (qkv and gate|up: the activations come quantised per token from the RMSNorm)
+  void *k8cache = nullptr, *v8cache = nullptr;
+  float *ks8 = nullptr, *vs8 = nullptr;
+  bool fp8_kv = false, kv8_valid = false, fp8_prefill = false;
+  void* tw_q8 = nullptr; float* tw_q8s = nullptr;
+  int64_t scale_layer_stride() const { return (int64_t)c.max_batch * c.t_kv_heads * c.max_seq; }
+  // decode step as a hipGraph (omchat_enable_decode_graph): ~230 launches per token replayed as one graph launch.  Captured on a
+  // context-owned stream (the caller's may be the legacy null stream, which cannot capture) with context-owned token / logits
+  // buffers so that every kernel argument is replay-invariant; the split-KV attention grid is captured for `cap_len` keys
+  // (empty splits exit at once) and the graph is re-captured when a sequence outgrows it.
+  struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0; };
+  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 4 + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0)
+  bool graph_on = false;
+  hipStream_t graph_stream = nullptr;
+  hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;
+  int32_t *d_tok_in = nullptr, *d_tok_out = nullptr;
+  long graph_steps = 0, graph_replays = 0, graph_captures = 0;
+  void *v_cls = nullptr, *v_pos = nullptr, *v_wpatch = nullptr, *v_bpatch = nullptr;
+  std::vector<VitLayer> vl;
+  void *p_w0 = nullptr, *p_b0 = nullptr, *p_w2 = nullptr, *p_b2 = nullptr;
+  void *t_embed = nullptr, *t_norm = nullptr, *t_lm = nullptr;
+  std::vector<DecLayer> dl;
+  float* rope = nullptr;          // [max_seq][64][2]
+
+  // workspaces
+  void *vw_cols = nullptr, *vw_pe = nullptr, *vw_x = nullptr, *vw_x2 = nullptr, *vw_xn = nullptr, *vw_qkv = nullptr, *vw_ao = nullptr,
+       *vw_h = nullptr, *vw_feat = nullptr, *vw_proj = nullptr;
+  float* vw_sumsq = nullptr;
+  // round 6, fused ViT layer (vit_run): statistics slots left by the GEMM epilogues, the row scale finished from them, and the copies of
+  // the qkv / fc1 weights with norm1 / norm2's weight folded into their columns (W'[n][k] = T(W[n][k] * w_norm[k])); rebuilt after a reload
+  float *vw_stats_x = nullptr, *vw_stats_qk = nullptr, *vw_rstd = nullptr;
+  int vw_stats_x_ld = 0, vw_stats_qk_ld = 0, vw_stats_x_ld_used = 1;      // (_used: slots of x's statistics written by the last producer)
+  struct VitFold { void *wqkv = nullptr, *w1 = nullptr; };
+  std::vector<VitFold> vfold;
+  bool vfold_stale = true;
+  void *tw_x = nullptr, *tw_x2 = nullptr, *tw_xn = nullptr, *tw_qkv = nullptr, *tw_ao = nullptr, *tw_act = nullptr, *tw_last = nullptr;
+  float* tw_logits = nullptr;
+  void* sk_ws = nullptr; size_t sk_ws_bytes = 0;      // stream-K slabs + flags of the MFMA GEMM
+  float* tp_f32_ws = nullptr; size_t tp_f32_bytes = 0;      // fp32 partial sums of a row-parallel projection (tuning key 29), grown on demand
+  float* tw_part = nullptr;       // split-K fp32 slices of the decode o_proj / down_proj [KS_MAX][max_batch][H]
+  float* tw_attn_ws = nullptr;
+  size_t tw_attn_ws_bytes = 0;
+  // fused attention + merge + o_proj launch of the batch-1 decode step (fused_decode.hip): granule buffers, sticky time-out word, and the
+  // launch counter that tags the granules of one launch
+  void* fd_ws = nullptr;
+  unsigned* fd_err = nullptr;
+  unsigned fd_epoch = 0;
+  long n_fused_launches = 0;
+  // one-launch decoder layer (decode_layer.hip): granule buffers; shares the error word and the launch counter above
+  void* dl_ws = nullptr;
+  long n_layer_launches = 0;
+  unsigned long long* dbg_stamps = nullptr;      // experiments build: [layers][8] clock stamps of the last decode step (tuning key 42 bit 4)
+  unsigned* dyn_ctr = nullptr;      // [layers][65 * 64] work counters of the dynamic gate|up GEMV (gemv_rows_norm_dyn_kernel), zero between launches
+  int *d_pos = nullptr, *d_len = nullptr, *d_idx = nullptr, *d_start = nullptr;
+  int* d_verify_n = nullptr;      // omchat_decode_verify: accepted drafts of the last verify step
+  PickState pick;
+  BeamState beam;
+  Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
+  int grow(Grown& g, size_t n) {
+    if (n <= g.cap) return 0;
+    if (g.p) { hipFree(g.p); bytes -= g.cap; g.p = nullptr; g.cap = 0; }
+    hipError_t e = hipMalloc(&g.p, n);
+    if (e != hipSuccess) { omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e)); return 2; }
+    g.cap = n; bytes += n;
+    return 0;
+  }
+  bool left_padded = false;
+  // decode of a padded batch as the reference computes it (omchat_decode_step_masked): every row's cache holds pre_S + masked_steps slots;
+  // dec_mode: 0 = no decode step since the prefill, 1 = omchat_decode_step (per-sequence lengths), 2 = omchat_decode_step_masked
+  int pre_S = 0, pre_b = 0, masked_steps = 0, dec_mode = 0;
+  unsigned char* d_mask = nullptr; int64_t mask_sb = 0;
+  bool mask_on_device = false;      // d_mask holds [prompt mask | ones] for the whole cache (omchat_masked_decode_begin)
+  void *kcache = nullptr, *vcache = nullptr;   // [layers][max_batch][kv_heads][max_seq][128]
+  std::vector<int> h_len;
+  // optional per-kernel-class HIP-event timing (bench.py roofline): category -> event pairs recorded on the launch stream
+  struct Prof { std::vector<hipEvent_t> ev; size_t used = 0; double ms = 0; long count = 0; };
+  bool prof_on = false;
+  Prof prof[OMCHAT_PROF_CATS];
+  void prof_mark(int cat, hipStream_t s) {
+    if (!prof_on) return;
+    Prof& p = prof[cat];
+    if (p.used == p.ev.size()) { hipEvent_t e; hipEventCreate(&e); p.ev.push_back(e); }
+    hipEventRecord(p.ev[p.used++], s);
+  }
+  void* stage_f32 = nullptr; size_t stage_f32_bytes = 0;
+  void* stage_t = nullptr; size_t stage_t_bytes = 0;
+
+  int alloc(void** p, size_t n) {
+    if (n == 0) n = 16;
+    hipError_t e = hipMalloc(p, n);
+    if (e != hipSuccess) { omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e)); return 2; }
+    allocs.push_back(*p);
+    bytes += n;
+    return 0;
+  }
+  size_t esz() const { return 2; }
+  int64_t cache_layer_stride() const { return (int64_t)c.max_batch * c.t_kv_heads * c.max_seq * 128; }
+  int64_t cache_sb() const { return (int64_t)c.t_kv_heads * c.max_seq * 128; }
+  int64_t cache_sh() const { return (int64_t)c.max_seq * 128; }
+
+  omchat_allreduce_fn hook = nullptr;
+  void* hook_user = nullptr;
+  // tensor-parallel prefill / ViT: the all-reduce of a row-parallel projection runs on its own stream, one row chunk behind the GEMM
+  static constexpr int AR_CHUNKS = 4;
+  hipStream_t comm_stream = nullptr;
+  hipEvent_t ev_chunk[AR_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_comm_done = nullptr;
+  // sequence-parallel form: the all-gather of row chunk i is done (communication stream); the NEXT column-parallel GEMM is issued per row chunk
+  // behind these events, so the exchange of chunk i + 1 also runs under the consumer's chunk i (gemm_sp / gemm_after_sp)
+  hipEvent_t ev_ag[AR_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
+  int sp_pend_nch = 0, sp_pend_rows_per = 0;
+  // transports of the tensor-parallel sum, in order of precedence: the test hook; the peer (IPC / xGMI) all-reduce of comm.hip for
+  // messages up to peer_max bytes (one-shot: decode-sized) or for every size when there is no RCCL communicator / peer_all is set;
+  // RCCL otherwise.  Every buffer passed here is context-owned with >= 16 bytes of slack, so the peer path may round the count up
+  // to whole 16-byte pieces (the extra elements are summed and never read).
+  omchat_peer* peer = nullptr;
+  size_t peer_max = 256 * 1024;
+  bool peer_all = false;
+  long n_ar_peer = 0, n_ar_rccl = 0;
+  int allreduce_any(void* buf, size_t count, int dtype, hipStream_t s) {
+    if (tp_size == 1) return 0;
+    if (hook) return hook(hook_user, buf, count, dtype, s);
+    const size_t esz = dtype == OMCHAT_F32 ? 4 : 2;
+    if (peer && (count * esz <= peer_max || !comm || peer_all)) {
+      const size_t per16 = 16 / esz;
+      ++n_ar_peer;
+      return omchat_peer_allreduce(peer, buf, (count + per16 - 1) / per16 * per16, dtype, s);
+    }
+    if (!comm) { omchat_set_error("tensor-parallel context without a transport: pass an RCCL communicator or call omchat_ctx_set_peer"); return 1; }
+    ++n_ar_rccl;
+    const ncclDataType_t t = dtype == OMCHAT_F32 ? ncclFloat32 : (dtype == OMCHAT_F16 ? ncclFloat16 : ncclBfloat16);
+    ncclResult_t r = ncclAllReduce(buf, buf, count, t, ncclSum, comm, s);
+    if (r != ncclSuccess) { omchat_set_error(std::string("ncclAllReduce: ") + ncclGetErrorString(r)); return 3; }
+    return 0;
+  }
+  // decode: sum of the split-K slices over the ranks + residual + RMSNorm.  With the peer transport that is ONE launch
+  // (omchat_peer_resid_rmsnorm, same bits); with the hook or RCCL: all-reduce of the slices, then the local kernel.
+  long n_fused_norm = 0;
+  int reduce_resid_rmsnorm(void* x, int ldx, float* part, int ks, const void* w, void* xn, int ldn, int rows, int H, float eps, int pack_nb,
+                           hipStream_t s) {
+    const size_t bytes = (size_t)ks * rows * H * 4;
+    if (tp_size > 1 && !hook && peer && g_fuse_peer_norm && rows <= 128 && bytes <= omchat_peer_capacity(peer) &&
+        (bytes <= peer_max || !comm || peer_all)) {
+      ++n_fused_norm;
+      return omchat_peer_resid_rmsnorm(peer, dt, x, ldx, part, ks, w, xn, ldn, rows, H, eps, pack_nb, s);
+    }
+    if (tp_size > 1) { const int rc = allreduce_any(part, (size_t)ks * rows * H, OMCHAT_F32, s); if (rc) return rc; }
+    return launch_resid_rmsnorm(dt, x, ldx, part, ks, w, xn, ldn, rows, H, eps, s, pack_nb);
+  }
+  // Sequence-parallel form (round 6): buf = [tp_size][blk_rows][N] 16-bit rows.  reduce_scatter_rows: afterwards block tp_rank holds the sum over
+  // the ranks (the other blocks are undefined); all_gather_rows: every rank contributes block tp_rank, afterwards all blocks are whole everywhere.
+  // RCCL: ncclReduceScatter / ncclAllGather in place -- together the bytes of ONE all-reduce; peer transport: the two halves of its two-shot
+  // all-reduce as kernels of their own (comm.hip omchat_peer_reduce_scatter / omchat_peer_all_gather).  The test hook has all-reduce only:
+  // reduce-scatter = all-reduce (every block comes back summed), all-gather = zero the foreign blocks, then all-reduce (x + 0 is exact).
+  long n_rs = 0, n_ag = 0;
+  bool sp_native(size_t bytes) const { return !hook && comm && !(peer && (bytes <= peer_max || peer_all)); }
+  bool sp_peer(size_t bytes) const { return !hook && peer && (bytes <= peer_max || !comm || peer_all); }
+  int reduce_scatter_rows(void* buf, int blk_rows, int N, hipStream_t s) {
+    if (tp_size == 1) return 0;
+    ++n_rs;
+    const size_t blk = (size_t)blk_rows * N;
+    if (sp_peer(blk * tp_size * 2)) { ++n_ar_peer; return omchat_peer_reduce_scatter(peer, buf, blk, dt, s); }
+    if (!sp_native(blk * tp_size * 2)) return allreduce_any(buf, blk * tp_size, dt, s);
+    ++n_ar_rccl;
+    ncclResult_t r = ncclReduceScatter(buf, (char*)buf + (size_t)tp_rank * blk * 2, blk, dt == OMCHAT_F16 ? ncclFloat16 : ncclBfloat16, ncclSum, comm, s);
+    if (r != ncclSuccess) { omchat_set_error(std::string("ncclReduceScatter: ") + ncclGetErrorString(r)); return 3; }
+    return 0;
+  }
+  int all_gather_rows(void* buf, int blk_rows, int N, hipStream_t s) {
+    if (tp_size == 1) return 0;
+    ++n_ag;
+    const size_t blk = (size_t)blk_rows * N;
+    if (sp_peer(blk * tp_size * 2)) { ++n_ar_peer; return omchat_peer_all_gather(peer, buf, blk, dt, s); }
+    if (!sp_native(blk * tp_size * 2)) {
+      if (hook == omchat_allreduce_noop) return 0;      // bench.py --shard-of: one rank's compute with the exchanges removed
+      if (tp_rank > 0 && hipMemsetAsync(buf, 0, (size_t)tp_rank * blk * 2, s) != hipSuccess) { omchat_set_error("all_gather_rows: memset"); return 2; }
+      if (tp_rank + 1 < tp_size && hipMemsetAsync((char*)buf + (size_t)(tp_rank + 1) * blk * 2, 0, (size_t)(tp_size - 1 - tp_rank) * blk * 2, s) != hipSuccess) {
+        omchat_set_error("all_gather_rows: memset"); return 2;
+      }
+      return allreduce_any(buf, blk * tp_size, dt, s);
+    }
+    ++n_ar_rccl;
+    ncclResult_t r = ncclAllGather((char*)buf + (size_t)tp_rank * blk * 2, buf, blk, dt == OMCHAT_F16 ? ncclFloat16 : ncclBfloat16, comm, s);
+    if (r != ncclSuccess) { omchat_set_error(std::string("ncclAllGather: ") + ncclGetErrorString(r)); return 3; }
+    return 0;
+  }
+  int allreduce(void* buf, size_t count, hipStream_t s) { return allreduce_any(buf, count, dt, s); }
+  int allreduce_f32(float* buf, size_t count, hipStream_t s) { return allreduce_any(buf, count, OMCHAT_F32, s); }
+};
+
+// ---- model.hip
+void drop_decode_graphs(omchat_ctx* ctx);      // pick parameters live in the kernel arguments of the captured decode graphs: a change drops them
+
+// ---- pick.hip: what model.hip knows of the pick pipeline
+int pick_alloc(omchat_ctx* ctx, int rows);      // context build: scratch of the argmax and the exchange table for picks of up to `rows` rows
+// every pick-side refusal of a step before anything is enqueued (the record's room when the step picks, then the history's when it feeds a
+// token), then the host counters
+int pick_admit(omchat_ctx* ctx, bool picks, bool feeds);
+// bare argmax of (rank-local) logits, no stage; `advance` moves the decode positions in the same launch
+int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false);
+// the pick of a step with its stages: greedy unless the sampler is on (or force_greedy); fed = the tokens the step was fed (NULL at the first
+// pick after the prefill)
+int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false, const int32_t* fed = nullptr,
+             bool force_greedy = false);
+int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s);      // a step that picks nothing still feeds the history
+const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n);      // why the pick state cannot go back n steps, or NULL
+int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s);

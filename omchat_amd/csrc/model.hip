@@ -1,9 +1,7 @@
 // Model-level loops of the OmChat hot path on one GPU (one tensor-parallel rank): context, weight routing, workspaces,
 // KV cache, and the kernel sequences for the vision tower, projector, prefill and decode.  Host C++; every FLOP runs
 // in the HIP kernels of this directory.
-#include "kernels.h"
-#include "../../include/omchat_hip.h"
-#include <rccl/rccl.h>
+#include "ctx.h"
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -48,37 +46,7 @@ __global__ void last_row_index_kernel(const int* len, int S, int b, int* idx, in
   if (i < b) idx[i] = i * S + len[i] - keep - 1;
 }
 
-// vocab-parallel greedy: every rank contributes (max logit, global index) per sequence; summed into a zeroed table
-__global__ void tp_argmax_scatter_kernel(const float* logits, int ld, const int* local_idx, int b, int rank, int v_local, float* table) {
-  const int i = threadIdx.x;
-  if (i < b) {
-    table[((size_t)rank * b + i) * 2] = logits[(size_t)i * ld + local_idx[i]];
-    table[((size_t)rank * b + i) * 2 + 1] = (float)(rank * v_local + local_idx[i]);
-  }
-}
-__global__ void tp_argmax_pick_kernel(const float* table, int b, int size, int* out) {
-  const int i = threadIdx.x;
-  if (i < b) {
-    float best = table[(size_t)i * 2]; int bi = (int)table[(size_t)i * 2 + 1];
-    for (int r = 1; r < size; ++r) {            // ranks hold ascending index ranges: strict > keeps the first index on ties
-      const float v = table[((size_t)r * b + i) * 2];
-      if (v > best) { best = v; bi = (int)table[((size_t)r * b + i) * 2 + 1]; }
-    }
-    out[i] = bi;
-  }
-}
-
 constexpr int DEC_KS_MAX = 8;
-
-enum RouteKind { R_PLAIN = 0, R_GATE = 1, R_UP = 2, R_PATCH = 3 };
-struct Route {
-  void* dst = nullptr;
-  int64_t rows = 0, cols = 0;     // logical source shape (2-D view)
-  int64_t dst_ld = 0;             // destination row stride (elements)
-  int kind = R_PLAIN;
-  bool loaded = false;
-  float synth_std = 0.02f, synth_off = 0.f;
-};
 
 }  // namespace
 
@@ -103,271 +71,7 @@ void model_set_ao_oproj(int v) { g_ao_oproj = v; }
 int g_fuse_peer_norm = 1;      // omchat_op_set_tuning key 9: 0 = tensor-parallel decode keeps the all-reduce and the residual + RMSNorm as two launches (A/B)
 void model_set_fuse_peer_norm(int v) { g_fuse_peer_norm = v; }
 
-struct omchat_ctx {
-  omchat_config c;
-  int dt = OMCHAT_BF16;
-  int tp_rank = 0, tp_size = 1;
-  ncclComm_t comm = nullptr;
-  std::vector<void*> allocs;
-  size_t bytes = 0;
-  std::unordered_map<std::string, Route> routes;
-
-  // derived geometry
-  int v_np = 0, v_ntok = 0, v_Cq = 0, v_kpad = 0, v_hd = 128;
-  int t_qdim = 0, t_kvdim = 0, t_qkvdim = 0;
-
-  // weights (device, compute dtype)
-  struct VitLayer { void *ls1, *ls2, *n1, *n2, *n1b, *n2b, *wqkv, *qn, *kn, *wproj, *bproj, *w1, *b1, *w2, *b2; };
-  struct DecLayer { void *ln1, *ln2, *wqkv, *bqkv, *wo, *wgu, *wd; };
-  // weight-only fp8 replica of the decode-streamed decoder weights (omchat_enable_fp8_decode): OCP e4m3 bytes + one fp32
-  // scale per output row; batch-1 decode steps stream these instead of the 16-bit weights, prefill keeps the 16-bit ones
-  struct DecLayer8 { void *wqkv, *wo, *wgu, *wd; float *sqkv, *so, *sgu, *sd; };
-  std::vector<DecLayer8> dl8;
-  // packed replica of the same weights for BATCHED decode steps (2 <= b <= 32): MFMA fragment order, every wave load 1 KiB contiguous
-  // (gemv.hip: gemv_pk_kernel; +14 GB at OmChat-13B, built on the first batched step; omchat_op_set_tuning key 6 = 0 disables it)
-  struct DecLayerP { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; };
-  std::vector<DecLayerP> dlp;
-  void* t_lmP = nullptr;
-  bool pk_ready = false, pk_unavailable = false;
-  void* t_lm8 = nullptr; float* t_lm8_s = nullptr;
-  bool fp8_decode = false, fp8_stale = false;
-  // BASELINE configs[4]: fp8 KV cache for decode (e4m3 bytes in the layout of the 16-bit cache + one fp32 scale per (layer, sequence,
-  // kv head, position)) and fp8 x fp8 MFMA prefill GEMMs (qkv and gate|up: the activations come quantised per token from the RMSNorm)
-  void *k8cache = nullptr, *v8cache = nullptr;
-  float *ks8 = nullptr, *vs8 = nullptr;
-  bool fp8_kv = false, kv8_valid = false, fp8_prefill = false;
-  void* tw_q8 = nullptr; float* tw_q8s = nullptr;
-  int64_t scale_layer_stride() const { return (int64_t)c.max_batch * c.t_kv_heads * c.max_seq; }
-  // decode step as a hipGraph (omchat_enable_decode_graph): ~230 launches per token replayed as one graph launch.  Captured on a
-  // context-owned stream (the caller's may be the legacy null stream, which cannot capture) with context-owned token / logits
-  // buffers so that every kernel argument is replay-invariant; the split-KV attention grid is captured for `cap_len` keys
-  // (empty splits exit at once) and the graph is re-captured when a sequence outgrows it.
-  struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0; };
-  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 2 + fp8
-  bool graph_on = false;
-  hipStream_t graph_stream = nullptr;
-  hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;
-  int32_t *d_tok_in = nullptr, *d_tok_out = nullptr;
-  long graph_steps = 0, graph_replays = 0, graph_captures = 0;
-  void *v_cls = nullptr, *v_pos = nullptr, *v_wpatch = nullptr, *v_bpatch = nullptr;
-  std::vector<VitLayer> vl;
-  void *p_w0 = nullptr, *p_b0 = nullptr, *p_w2 = nullptr, *p_b2 = nullptr;
-  void *t_embed = nullptr, *t_norm = nullptr, *t_lm = nullptr;
-  std::vector<DecLayer> dl;
-  float* rope = nullptr;          // [max_seq][64][2]
-
-  // workspaces
-  void *vw_cols = nullptr, *vw_pe = nullptr, *vw_x = nullptr, *vw_x2 = nullptr, *vw_xn = nullptr, *vw_qkv = nullptr, *vw_ao = nullptr,
-       *vw_h = nullptr, *vw_feat = nullptr, *vw_proj = nullptr;
-  float* vw_sumsq = nullptr;
-  // round 6, fused ViT layer (vit_run): statistics slots left by the GEMM epilogues, the row scale finished from them, and the copies of
-  // the qkv / fc1 weights with norm1 / norm2's weight folded into their columns (W'[n][k] = T(W[n][k] * w_norm[k])); rebuilt after a reload
-  float *vw_stats_x = nullptr, *vw_stats_qk = nullptr, *vw_rstd = nullptr;
-  int vw_stats_x_ld = 0, vw_stats_qk_ld = 0, vw_stats_x_ld_used = 1;      // (_used: slots of x's statistics written by the last producer)
-  struct VitFold { void *wqkv = nullptr, *w1 = nullptr; };
-  std::vector<VitFold> vfold;
-  bool vfold_stale = true;
-  void *tw_x = nullptr, *tw_x2 = nullptr, *tw_xn = nullptr, *tw_qkv = nullptr, *tw_ao = nullptr, *tw_act = nullptr, *tw_last = nullptr;
-  float* tw_logits = nullptr;
-  void* sk_ws = nullptr; size_t sk_ws_bytes = 0;      // stream-K slabs + flags of the MFMA GEMM
-  float* tp_table = nullptr;
-  float* tp_f32_ws = nullptr; size_t tp_f32_bytes = 0;      // fp32 partial sums of a row-parallel projection (tuning key 29), grown on demand
-  void* arg_scratch = nullptr;
-  float* tw_part = nullptr;       // split-K fp32 slices of the decode o_proj / down_proj [KS_MAX][max_batch][H]
-  float* tw_attn_ws = nullptr;
-  size_t tw_attn_ws_bytes = 0;
-  // fused attention + merge + o_proj launch of the batch-1 decode step (fused_decode.hip): granule buffers, sticky time-out word, and the
-  // launch counter that tags the granules of one launch
-  void* fd_ws = nullptr;
-  unsigned* fd_err = nullptr;
-  unsigned fd_epoch = 0;
-  long n_fused_launches = 0;
-  // one-launch decoder layer (decode_layer.hip): granule buffers; shares the error word and the launch counter above
-  void* dl_ws = nullptr;
-  long n_layer_launches = 0;
-  unsigned long long* dbg_stamps = nullptr;      // experiments build: [layers][8] clock stamps of the last decode step (tuning key 42 bit 4)
-  unsigned* dyn_ctr = nullptr;      // [layers][65 * 64] work counters of the dynamic gate|up GEMV (gemv_rows_norm_dyn_kernel), zero between launches
-  int *d_pos = nullptr, *d_len = nullptr, *d_idx = nullptr, *d_start = nullptr;
-  int* d_verify_n = nullptr;      // omchat_decode_verify: accepted drafts of the last verify step
-  // on-device sampling (omchat_set_sampling; sample.hip): uniform parameters for the batch, per-row device step counters, the repetition
-  // penalty's seen-token bitmap of this rank's vocabulary slice [max_batch][smp_bmw] and the local index of the bit each row's last pick set
-  struct Sampling { bool on = false; uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f; };
-  Sampling smp;
-  void* smp_ws = nullptr;
-  uint32_t* smp_bm = nullptr; int smp_bmw = 0;
-  int *smp_last = nullptr, *smp_step = nullptr;
-  // HF logits constraints (omchat_set_constraints; constrain.hip): uniform parameters, the rows' token history as HF's processors see it
-  // [max_batch][con_ld] with device lengths, the id lists, the ban bitmap of this rank's vocabulary slice (all-zero between picks) and the
-  // banned copy of the logits the pick runs on.  con_fed: decode steps fed since the begin (host bound for the history's capacity).
-  struct Constraints {
-    bool on = false; int b = 0, ngram = 0, min_new = 0, min_len = 0, n_eos = 0, n_sup = 0, n_bsup = 0, n_bw = 0;
-    bool operator==(const Constraints& o) const {
-      return on == o.on && b == o.b && ngram == o.ngram && min_new == o.min_new && min_len == o.min_len && n_eos == o.n_eos && n_sup == o.n_sup &&
-             n_bsup == o.n_bsup && n_bw == o.n_bw;
-    }
-  };
-  Constraints con;
-  int con_ld = 0, con_fed = 0, con_room = 0;
-  int *con_len = nullptr, *con_plen = nullptr;
-  int32_t* con_lists = nullptr;
-  uint32_t* con_ban = nullptr; int con_bmw = 0;
-  float* con_logits = nullptr;
-  // per-token log-probabilities of the picked ids (omchat_set_logprobs; logprob.hip): the record float [2][max_new][max_batch] (raw, processed)
-  // with a device counter per row, the slice partials, the exchange table under tensor parallelism; lp_picks: picks enqueued since the
-  // begin (host bound for the record's capacity)
-  struct Logprobs { bool on = false; int b = 0, max_new = 0; };
-  Logprobs lp;
-  int lp_picks = 0;
-  int lp_cap = 0;      // lines per plane of the record as allocated (>= lp.max_new; grown, never shrunk): the stride the kernels are given
-  int* lp_cnt = nullptr;
-  void* lp_ws = nullptr;
-  float* lp_table = nullptr;
-  // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand
-  // (state words, exchange table, length-penalty denominators, parent rows, stash of the KV gather)
-  struct Beam { bool on = false; int b = 0, N = 0, KB = 0, max_new = 0, P = 0, es = 0, ns = 1, t = 0; float lp = 1.f; std::vector<int> eos; };
-  Beam beam;
-  struct Grown { void* p = nullptr; size_t cap = 0; };
-  Grown bm_state, bm_table, bm_dn, bm_parents, bm_stash;
-  Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
-  Grown con_hist;    // token history of the logits constraints (omchat_set_constraints)
-  Grown lp_rec;      // record of the per-token log-probabilities (omchat_set_logprobs)
-  bool bm_stash8 = false;
-  std::vector<int> bm_hpos, bm_hlen;      // host sources of the fork's device lengths (alive until the next begin)
-  int grow(Grown& g, size_t n) {
-    if (n <= g.cap) return 0;
-    if (g.p) { hipFree(g.p); bytes -= g.cap; g.p = nullptr; g.cap = 0; }
-    hipError_t e = hipMalloc(&g.p, n);
-    if (e != hipSuccess) { omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e)); return 2; }
-    g.cap = n; bytes += n;
-    return 0;
-  }
-  bool left_padded = false;
-  // decode of a padded batch as the reference computes it (omchat_decode_step_masked): every row's cache holds pre_S + masked_steps slots;
-  // dec_mode: 0 = no decode step since the prefill, 1 = omchat_decode_step (per-sequence lengths), 2 = omchat_decode_step_masked
-  int pre_S = 0, pre_b = 0, masked_steps = 0, dec_mode = 0;
-  unsigned char* d_mask = nullptr; int64_t mask_sb = 0;
-  bool mask_on_device = false;      // d_mask holds [prompt mask | ones] for the whole cache (omchat_masked_decode_begin)
-  void *kcache = nullptr, *vcache = nullptr;   // [layers][max_batch][kv_heads][max_seq][128]
-  std::vector<int> h_len;
-  // optional per-kernel-class HIP-event timing (bench.py roofline): category -> event pairs recorded on the launch stream
-  struct Prof { std::vector<hipEvent_t> ev; size_t used = 0; double ms = 0; long count = 0; };
-  bool prof_on = false;
-  Prof prof[OMCHAT_PROF_CATS];
-  void prof_mark(int cat, hipStream_t s) {
-    if (!prof_on) return;
-    Prof& p = prof[cat];
-    if (p.used == p.ev.size()) { hipEvent_t e; hipEventCreate(&e); p.ev.push_back(e); }
-    hipEventRecord(p.ev[p.used++], s);
-  }
-  void* stage_f32 = nullptr; size_t stage_f32_bytes = 0;
-  void* stage_t = nullptr; size_t stage_t_bytes = 0;
-
-  int alloc(void** p, size_t n) {
-    if (n == 0) n = 16;
-    hipError_t e = hipMalloc(p, n);
-    if (e != hipSuccess) { omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e)); return 2; }
-    allocs.push_back(*p);
-    bytes += n;
-    return 0;
-  }
-  size_t esz() const { return 2; }
-  int64_t cache_layer_stride() const { return (int64_t)c.max_batch * c.t_kv_heads * c.max_seq * 128; }
-  int64_t cache_sb() const { return (int64_t)c.t_kv_heads * c.max_seq * 128; }
-  int64_t cache_sh() const { return (int64_t)c.max_seq * 128; }
-
-  omchat_allreduce_fn hook = nullptr;
-  void* hook_user = nullptr;
-  // tensor-parallel prefill / ViT: the all-reduce of a row-parallel projection runs on its own stream, one row chunk behind the GEMM
-  static constexpr int AR_CHUNKS = 4;
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_chunk[AR_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_comm_done = nullptr;
-  // sequence-parallel form: the all-gather of row chunk i is done (communication stream); the NEXT column-parallel GEMM is issued per row chunk
-  // behind these events, so the exchange of chunk i + 1 also runs under the consumer's chunk i (gemm_sp / gemm_after_sp)
-  hipEvent_t ev_ag[AR_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
-  int sp_pend_nch = 0, sp_pend_rows_per = 0;
-  // transports of the tensor-parallel sum, in order of precedence: the test hook; the peer (IPC / xGMI) all-reduce of comm.hip for
-  // messages up to peer_max bytes (one-shot: decode-sized) or for every size when there is no RCCL communicator / peer_all is set;
-  // RCCL otherwise.  Every buffer passed here is context-owned with >= 16 bytes of slack, so the peer path may round the count up
-  // to whole 16-byte pieces (the extra elements are summed and never read).
-  omchat_peer* peer = nullptr;
-  size_t peer_max = 256 * 1024;
-  bool peer_all = false;
-  long n_ar_peer = 0, n_ar_rccl = 0;
-  int allreduce_any(void* buf, size_t count, int dtype, hipStream_t s) {
-    if (tp_size == 1) return 0;
-    if (hook) return hook(hook_user, buf, count, dtype, s);
-    const size_t esz = dtype == OMCHAT_F32 ? 4 : 2;
-    if (peer && (count * esz <= peer_max || !comm || peer_all)) {
-      const size_t per16 = 16 / esz;
-      ++n_ar_peer;
-      return omchat_peer_allreduce(peer, buf, (count + per16 - 1) / per16 * per16, dtype, s);
-    }
-    if (!comm) { omchat_set_error("tensor-parallel context without a transport: pass an RCCL communicator or call omchat_ctx_set_peer"); return 1; }
-    ++n_ar_rccl;
-    const ncclDataType_t t = dtype == OMCHAT_F32 ? ncclFloat32 : (dtype == OMCHAT_F16 ? ncclFloat16 : ncclBfloat16);
-    ncclResult_t r = ncclAllReduce(buf, buf, count, t, ncclSum, comm, s);
-    if (r != ncclSuccess) { omchat_set_error(std::string("ncclAllReduce: ") + ncclGetErrorString(r)); return 3; }
-    return 0;
-  }
-  // decode: sum of the split-K slices over the ranks + residual + RMSNorm.  With the peer transport that is ONE launch
-  // (omchat_peer_resid_rmsnorm, same bits); with the hook or RCCL: all-reduce of the slices, then the local kernel.
-  long n_fused_norm = 0;
-  int reduce_resid_rmsnorm(void* x, int ldx, float* part, int ks, const void* w, void* xn, int ldn, int rows, int H, float eps, int pack_nb,
-                           hipStream_t s) {
-    const size_t bytes = (size_t)ks * rows * H * 4;
-    if (tp_size > 1 && !hook && peer && g_fuse_peer_norm && rows <= 128 && bytes <= omchat_peer_capacity(peer) &&
-        (bytes <= peer_max || !comm || peer_all)) {
-      ++n_fused_norm;
-      return omchat_peer_resid_rmsnorm(peer, dt, x, ldx, part, ks, w, xn, ldn, rows, H, eps, pack_nb, s);
-    }
-    if (tp_size > 1) { const int rc = allreduce_any(part, (size_t)ks * rows * H, OMCHAT_F32, s); if (rc) return rc; }
-    return launch_resid_rmsnorm(dt, x, ldx, part, ks, w, xn, ldn, rows, H, eps, s, pack_nb);
-  }
-  // Sequence-parallel form (round 6): buf = [tp_size][blk_rows][N] 16-bit rows.  reduce_scatter_rows: afterwards block tp_rank holds the sum over
-  // the ranks (the other blocks are undefined); all_gather_rows: every rank contributes block tp_rank, afterwards all blocks are whole everywhere.
-  // RCCL: ncclReduceScatter / ncclAllGather in place -- together the bytes of ONE all-reduce; peer transport: the two halves of its two-shot
-  // all-reduce as kernels of their own (comm.hip omchat_peer_reduce_scatter / omchat_peer_all_gather).  The test hook has all-reduce only:
-  // reduce-scatter = all-reduce (every block comes back summed), all-gather = zero the foreign blocks, then all-reduce (x + 0 is exact).
-  long n_rs = 0, n_ag = 0;
-  bool sp_native(size_t bytes) const { return !hook && comm && !(peer && (bytes <= peer_max || peer_all)); }
-  bool sp_peer(size_t bytes) const { return !hook && peer && (bytes <= peer_max || !comm || peer_all); }
-  int reduce_scatter_rows(void* buf, int blk_rows, int N, hipStream_t s) {
-    if (tp_size == 1) return 0;
-    ++n_rs;
-    const size_t blk = (size_t)blk_rows * N;
-    if (sp_peer(blk * tp_size * 2)) { ++n_ar_peer; return omchat_peer_reduce_scatter(peer, buf, blk, dt, s); }
-    if (!sp_native(blk * tp_size * 2)) return allreduce_any(buf, blk * tp_size, dt, s);
-    ++n_ar_rccl;
-    ncclResult_t r = ncclReduceScatter(buf, (char*)buf + (size_t)tp_rank * blk * 2, blk, dt == OMCHAT_F16 ? ncclFloat16 : ncclBfloat16, ncclSum, comm, s);
-    if (r != ncclSuccess) { omchat_set_error(std::string("ncclReduceScatter: ") + ncclGetErrorString(r)); return 3; }
-    return 0;
-  }
-  int all_gather_rows(void* buf, int blk_rows, int N, hipStream_t s) {
-    if (tp_size == 1) return 0;
-    ++n_ag;
-    const size_t blk = (size_t)blk_rows * N;
-    if (sp_peer(blk * tp_size * 2)) { ++n_ar_peer; return omchat_peer_all_gather(peer, buf, blk, dt, s); }
-    if (!sp_native(blk * tp_size * 2)) {
-      if (hook == omchat_allreduce_noop) return 0;      // bench.py --shard-of: one rank's compute with the exchanges removed
-      if (tp_rank > 0 && hipMemsetAsync(buf, 0, (size_t)tp_rank * blk * 2, s) != hipSuccess) { omchat_set_error("all_gather_rows: memset"); return 2; }
-      if (tp_rank + 1 < tp_size && hipMemsetAsync((char*)buf + (size_t)(tp_rank + 1) * blk * 2, 0, (size_t)(tp_size - 1 - tp_rank) * blk * 2, s) != hipSuccess) {
-        omchat_set_error("all_gather_rows: memset"); return 2;
-      }
-      return allreduce_any(buf, blk * tp_size, dt, s);
-    }
-    ++n_ar_rccl;
-    ncclResult_t r = ncclAllGather((char*)buf + (size_t)tp_rank * blk * 2, buf, blk, dt == OMCHAT_F16 ? ncclFloat16 : ncclBfloat16, comm, s);
-    if (r != ncclSuccess) { omchat_set_error(std::string("ncclAllGather: ") + ncclGetErrorString(r)); return 3; }
-    return 0;
-  }
-  int allreduce(void* buf, size_t count, hipStream_t s) { return allreduce_any(buf, count, dt, s); }
-  int allreduce_f32(float* buf, size_t count, hipStream_t s) { return allreduce_any(buf, count, OMCHAT_F32, s); }
-};
-
 namespace {
-
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 int add_route(omchat_ctx* ctx, const std::string& name, void** slot, int64_t rows, int64_t cols, float std_, float off,
               int kind = R_PLAIN, void* dst_override = nullptr, int64_t dst_ld = -1) {
@@ -528,8 +232,7 @@ int build(omchat_ctx* ctx) {
       TRY(ctx->alloc((void**)&ctx->dbg_stamps, (size_t)c.t_layers * 256));
       OM_HIP(hipMemset(ctx->dbg_stamps, 0, (size_t)c.t_layers * 256));
     }
-    TRY(ctx->alloc(&ctx->arg_scratch, argmax_scratch_bytes((int)DR)));
-    TRY(ctx->alloc((void**)&ctx->tp_table, (size_t)ctx->tp_size * DR * 2 * 4));
+    TRY(pick_alloc(ctx, (int)DR));
     TRY(ctx->alloc((void**)&ctx->d_verify_n, 16));
     TRY(ctx->alloc((void**)&ctx->d_pos, (size_t)c.max_batch * 4));
     TRY(ctx->alloc((void**)&ctx->d_len, (size_t)c.max_batch * 4));
@@ -614,10 +317,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (!ctx) return;
   for (void* p : ctx->allocs) hipFree(p);
   for (auto& pr : ctx->prof) for (hipEvent_t e : pr.ev) hipEventDestroy(e);
-  for (auto& kv : ctx->graphs) {
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-  }
+  drop_decode_graphs(ctx);
   if (ctx->graph_ev_in) (void)hipEventDestroy(ctx->graph_ev_in);
   if (ctx->graph_ev_out) (void)hipEventDestroy(ctx->graph_ev_out);
   if (ctx->graph_stream) (void)hipStreamDestroy(ctx->graph_stream);
@@ -628,8 +328,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  for (omchat_ctx::Grown* g : {&ctx->bm_state, &ctx->bm_table, &ctx->bm_dn, &ctx->bm_parents, &ctx->bm_stash, &ctx->ext_ws, &ctx->con_hist, &ctx->lp_rec})
-    if (g->p) hipFree(g->p);
+  ctx->beam.release(); ctx->ext_ws.release(); ctx->pick.release();
   delete ctx;
 }
 
@@ -1277,107 +976,6 @@ extern "C" int omchat_enable_fp8_prefill(omchat_ctx* ctx, int on) {
   return 0;
 }
 
-// greedy argmax over (rank-local) logits; under tensor parallelism the (max, index) pairs are exchanged
-static int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false) {
-  const omchat_config& c = ctx->c;
-  TRY(launch_argmax(lg, c.t_vocab, b, c.t_vocab, next_tokens, ctx->arg_scratch, s, advance ? ctx->d_pos : nullptr, advance ? ctx->d_len : nullptr));
-  if (ctx->tp_size > 1) {
-    const size_t n = (size_t)ctx->tp_size * b * 2;
-    OM_HIP(hipMemsetAsync(ctx->tp_table, 0, n * 4, s));
-    hipLaunchKernelGGL(tp_argmax_scatter_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, lg, c.t_vocab, next_tokens, b, ctx->tp_rank, c.t_vocab, ctx->tp_table);
-    TRY(ctx->allreduce_f32(ctx->tp_table, n, s));
-    hipLaunchKernelGGL(tp_argmax_pick_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->tp_table, b, ctx->tp_size, next_tokens);
-  }
-  return 0;
-}
-
-static int smp_xchg(void* user, float* buf, size_t count, hipStream_t s) { return ((omchat_ctx*)user)->allreduce_f32(buf, count, s); }
-
-static ConstrainArgs con_args(omchat_ctx* ctx, int b, const int32_t* fed) {
-  const omchat_config& c = ctx->c;
-  ConstrainArgs a;
-  a.hist = (int32_t*)ctx->con_hist.p; a.hist_ld = ctx->con_ld; a.len = ctx->con_len; a.plen = ctx->con_plen; a.tok = fed;
-  a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total; a.gbase = ctx->tp_rank * c.t_vocab;
-  a.ngram = ctx->con.ngram; a.min_new = ctx->con.min_new; a.min_len = ctx->con.min_len;
-  constrain_bind_lists(ctx->con_lists, a);
-  a.n_eos = ctx->con.n_eos; a.n_sup = ctx->con.n_sup; a.n_bsup = ctx->con.n_bsup; a.n_bw = ctx->con.n_bw;
-  a.ban = ctx->con_ban; a.bmw = ctx->con_bmw;
-  return a;
-}
-
-// The ban stage in front of a pick (omchat_set_constraints; nothing when constraints are off): `fed` = the tokens the decode step was fed
-// (appended to the history first), NULL at the first pick after the prefill.  *lg then points at the context's banned copy of the logits;
-// the caller's logits are not written.
-static int ban_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fed, hipStream_t s) {
-  if (!ctx->con.on) return 0;
-  OM_CHECK(b <= ctx->con.b, "constraints are on for fewer rows than this pick has (omchat_set_constraints)");
-  const omchat_config& c = ctx->c;
-  TRY(launch_constrain_ban(con_args(ctx, b, fed), s));
-  TRY(launch_constrain_apply(*lg, c.t_vocab, b, c.t_vocab, ctx->con_ban, ctx->con_bmw, ctx->con_logits, fed ? ctx->con_len : nullptr, ctx->con_ld, s));
-  *lg = ctx->con_logits;
-  return 0;
-}
-
-// The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits, proc = what the pick ran on (the
-// banned copy when constraints are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
-static int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, const int32_t* ids, hipStream_t s) {
-  if (!ctx->lp.on) return 0;
-  const omchat_config& c = ctx->c;
-  LogprobArgs a;
-  a.raw = raw; a.raw_ld = c.t_vocab; a.proc = proc; a.proc_ld = c.t_vocab;
-  a.b = std::min(b, ctx->lp.b); a.V = c.t_vocab; a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
-  a.ids = ids;
-  if (ctx->smp.on) {
-    a.temperature = ctx->smp.temperature; a.penalty = ctx->smp.penalty;
-    if (ctx->smp.penalty != 1.f) { a.seen = ctx->smp_bm; a.bm_words = ctx->smp_bmw; a.last_set = ctx->smp_last; }
-    a.top1 = ctx->smp.top_k == 1;
-    a.thr = sample_thr_words(ctx->smp_ws, b, c.t_vocab_total, ctx->smp.top_k, ctx->smp.top_p, &a.thr_stride);
-  }
-  a.ws = ctx->lp_ws; a.table = ctx->lp_table; a.xchg = smp_xchg; a.xchg_user = ctx;
-  a.rec = (float*)ctx->lp_rec.p; a.cnt = ctx->lp_cnt; a.max_new = ctx->lp_cap; a.rec_ld = c.max_batch;
-  return launch_logprob(a, s);
-}
-
-// one more pick feeds the record: refuse before anything is enqueued when it is full (max_new of omchat_set_logprobs)
-static int lp_room(omchat_ctx* ctx) {
-  OM_CHECK(!ctx->lp.on || ctx->lp_picks < ctx->lp.max_new, "logprobs: more picks than the max_new given to omchat_set_logprobs");
-  return 0;
-}
-
-// the token pick of a step: greedy unless omchat_set_sampling switched the sampler on; `advance` moves the decode positions in the same launch
-static int pick_next(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false,
-                     const int32_t* fed = nullptr) {
-  const float* raw = lg;
-  TRY(ban_stage(ctx, &lg, b, fed, s));
-  if (!ctx->smp.on) {
-    TRY(greedy_pick(ctx, lg, b, next_tokens, s, advance));
-    return logprob_stage(ctx, raw, lg, b, next_tokens, s);
-  }
-  const omchat_config& c = ctx->c;
-  SampleArgs a;
-  a.logits = lg; a.ld = c.t_vocab; a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total;
-  a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
-  a.seed = ctx->smp.seed; a.temperature = ctx->smp.temperature; a.top_k = ctx->smp.top_k; a.top_p = ctx->smp.top_p; a.penalty = ctx->smp.penalty;
-  if (ctx->smp.penalty != 1.f) { a.bitmap = ctx->smp_bm; a.bm_words = ctx->smp_bmw; }
-  a.last_set = ctx->smp_last; a.step = ctx->smp_step;
-  if (advance) { a.adv_pos = ctx->d_pos; a.adv_len = ctx->d_len; }
-  a.out = next_tokens; a.ws = ctx->smp_ws; a.table = ctx->tp_table;
-  a.xchg = smp_xchg; a.xchg_user = ctx;
-  TRY(launch_sample(a, s));
-  return logprob_stage(ctx, raw, lg, b, next_tokens, s);
-}
-
-extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
-  OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
-  TRY(lp_room(ctx));
-  // (the sampler's state is not this pick's: with sampling on, the first token comes from omchat_sample)
-  OM_CHECK(!ctx->lp.on || !ctx->smp.on, "logprobs: omchat_greedy while sampling is on (omchat_sample picks the first token then)");
-  if (ctx->lp.on) ctx->lp_picks += 1;
-  const float* raw = logits;
-  TRY(ban_stage(ctx, &logits, b, nullptr, (hipStream_t)stream));
-  TRY(greedy_pick(ctx, logits, b, next_tokens, (hipStream_t)stream));
-  return logprob_stage(ctx, raw, logits, b, next_tokens, (hipStream_t)stream);
-}
 
 extern "C" int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float* logits, void* stream) {
   OM_CHECK(ctx && hidden && logits, "null argument");
@@ -1520,7 +1118,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     TRY(lm_head_rows(ctx, ctx->tw_last, b, logits_last, s));
   }
   ctx->kv8_valid = false;
-  ctx->beam.on = false;         // a prefill ends any beam search
+  ctx->beam.end();         // a prefill ends any beam search
   if (ctx->fp8_kv) {      // fp8 KV cache for the decode steps: quantise what this prefill wrote -- ALL S slots of every row: the masked decode
                           // of a padded batch exposes padded slots too (omchat_arch.py:61-70), and the per-sequence step overwrites them as it appends
     for (int i = 0; i < c.t_layers; ++i) {
@@ -1558,7 +1156,7 @@ extern "C" int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_
   OM_CHECK(!ctx->fp8_prefill, "prefill_extend: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
   OM_CHECK(!ctx->left_padded, "prefill_extend: the cache holds a left-padded batch");
   OM_CHECK(ctx->dec_mode != 2, "prefill_extend: the cache holds a masked-decode (padded batch) state");
-  OM_CHECK(!ctx->beam.on, "prefill_extend: a beam search is active");
+  OM_CHECK(!ctx->beam.on(), "prefill_extend: a beam search is active");
   OM_CHECK(ctx->pre_b >= 1 && ctx->h_len[0] >= 1, "prefill_extend: no live sequence-0 state (omchat_prefill with b = 1 first)");
   OM_CHECK(ctx->pre_b == 1, "prefill_extend: the cache holds a b > 1 state");
   OM_CHECK(keep >= 0 && keep <= ctx->h_len[0], "prefill_extend: keep outside [0, current length]");
@@ -1879,10 +1477,10 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
   if (vL >= 0) TRY(greedy_pick(ctx, lg, b, next_tokens, s));
-  else if (next_tokens) TRY(pick_next(ctx, lg, b, next_tokens, s, true, tokens));
+  else if (next_tokens) TRY(pick_run(ctx, lg, b, next_tokens, s, true, tokens));
   else {
     hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
-    if (ctx->con.on && b <= ctx->con.b) TRY(launch_constrain_append((int32_t*)ctx->con_hist.p, ctx->con_ld, ctx->con_len, tokens, b, s));
+    TRY(pick_feed(ctx, tokens, b, s));
   }
   OM_LAUNCH_CHECK();
   return 0;
@@ -1894,206 +1492,11 @@ static void destroy_graph(omchat_ctx::DecodeGraph& g) {
   g = omchat_ctx::DecodeGraph{};
 }
 
-// Sampling parameters live in the kernel arguments of the captured decode graphs: a change drops them (re-captured on the next step).
-extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
-                                   const int32_t* seen_ids, const int32_t* n_seen_per_row, void* stream) {
-  OM_CHECK(ctx, "null ctx");
-  const omchat_config& c = ctx->c;
-  omchat_ctx::Sampling p;
-  p.on = b > 0;
-  if (p.on) {
-    OM_CHECK(b <= c.max_batch, "sampling: batch exceeds max_batch");
-    OM_CHECK(temperature > 0.f && isfinite(temperature), "sampling: temperature must be a strictly positive float (greedy: do_sample=False)");
-    OM_CHECK(top_k >= 0, "sampling: top_k >= 0 (0 = off)");
-    OM_CHECK(top_p > 0.0 && top_p <= 1.0, "sampling: top_p in (0, 1] (1 = off)");
-    OM_CHECK(rep_penalty > 0.f && isfinite(rep_penalty), "sampling: repetition_penalty must be a strictly positive float");
-    p.seed = seed; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.penalty = rep_penalty;
-  }
-  const omchat_ctx::Sampling& o = ctx->smp;
-  const bool same = o.on == p.on && o.seed == p.seed && o.temperature == p.temperature && o.top_k == p.top_k && o.top_p == p.top_p &&
-                    o.penalty == p.penalty;
-  if (!same) {
-    for (auto& kv : ctx->graphs) destroy_graph(kv.second);
-    ctx->graphs.clear();
-  }
-  ctx->smp = p;
-  if (!p.on) return 0;
-  if (!ctx->smp_ws) {
-    ctx->smp_bmw = (c.t_vocab + 31) / 32;
-    TRY(ctx->alloc(&ctx->smp_ws, sample_ws_bytes(c.max_batch)));
-    TRY(ctx->alloc((void**)&ctx->smp_bm, (size_t)c.max_batch * ctx->smp_bmw * 4));
-    TRY(ctx->alloc((void**)&ctx->smp_last, (size_t)c.max_batch * 4));
-    TRY(ctx->alloc((void**)&ctx->smp_step, (size_t)c.max_batch * 4));
-  }
-  // this rank's slice of the seen sets; ids outside the vocabulary (the -200 image sentinel) are never seen
-  std::vector<uint32_t> bm((size_t)c.max_batch * ctx->smp_bmw, 0u);
-  if (rep_penalty != 1.f && seen_ids && n_seen_per_row) {
-    const int64_t lo = (int64_t)ctx->tp_rank * c.t_vocab;
-    size_t off = 0;
-    for (int i = 0; i < b; ++i) {
-      OM_CHECK(n_seen_per_row[i] >= 0, "sampling: n_seen_per_row >= 0");
-      for (int j = 0; j < n_seen_per_row[i]; ++j) {
-        const int64_t li = (int64_t)seen_ids[off + j] - lo;
-        if (seen_ids[off + j] >= 0 && seen_ids[off + j] < c.t_vocab_total && li >= 0 && li < c.t_vocab)
-          bm[(size_t)i * ctx->smp_bmw + (li >> 5)] |= 1u << (li & 31);
-      }
-      off += (size_t)n_seen_per_row[i];
-    }
-  }
-  hipStream_t s = (hipStream_t)stream;
-  OM_HIP(hipMemcpyAsync(ctx->smp_bm, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, s));
-  OM_HIP(hipMemsetAsync(ctx->smp_step, 0, (size_t)c.max_batch * 4, s));
-  OM_HIP(hipMemsetAsync(ctx->smp_last, 0xFF, (size_t)c.max_batch * 4, s));
-  OM_HIP(hipStreamSynchronize(s));     // host vector
-  return 0;
+void drop_decode_graphs(omchat_ctx* ctx) {
+  for (auto& kv : ctx->graphs) destroy_graph(kv.second);
+  ctx->graphs.clear();
 }
 
-// Constraint parameters live in the kernel arguments of the captured decode graphs, as the sampling ones do: a change (or a history buffer
-// that had to grow) drops them.  The id lists are read from device memory at every pick, so new contents of the same size keep the graphs.
-extern "C" int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids,
-                                      int n_eos, const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
-                                      const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
-                                      const int32_t* prompt_len, int max_new, void* stream) {
-  OM_CHECK(ctx, "null ctx");
-  const omchat_config& c = ctx->c;
-  auto drop_graphs = [&]() {
-    for (auto& kv : ctx->graphs) destroy_graph(kv.second);
-    ctx->graphs.clear();
-  };
-  if (b <= 0) {
-    if (ctx->con.on) drop_graphs();
-    ctx->con = omchat_ctx::Constraints{};
-    return 0;
-  }
-  // every refusal before anything is enqueued or changed
-  OM_CHECK(c.t_layers > 0, "context has no decoder");
-  OM_CHECK(b <= c.max_batch, "constraints: batch exceeds max_batch");
-  OM_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= CON_NGRAM_MAX, "constraints: 0 <= no_repeat_ngram_size <= 64 (0 = off)");
-  OM_CHECK(min_new_tokens >= 0 && min_length >= 0, "constraints: min_new_tokens and min_length >= 0");
-  OM_CHECK(prompt_ids && prompt_len && max_new >= 1, "constraints: prompt ids, per-row lengths and max_new >= 1");
-  OM_CHECK(!ctx->beam.on, "constraints: a beam search is active (the processors act on log-softmax scores there)");
-  int maxP = 0;
-  for (int i = 0; i < b; ++i) {
-    OM_CHECK(prompt_len[i] >= 0, "constraints: prompt_len >= 0");
-    maxP = std::max(maxP, prompt_len[i]);
-  }
-  omchat_ctx::Constraints p;
-  p.on = true; p.b = b; p.ngram = no_repeat_ngram_size; p.min_new = min_new_tokens; p.min_len = min_length;
-  std::vector<int32_t> lists(CON_LIST_WORDS);
-  ConstrainArgs la;
-  TRY(constrain_pack_lists(eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_word_ids, bad_word_offsets,
-                           n_bad_words, lists.data(), la));
-  p.n_eos = la.n_eos; p.n_sup = la.n_sup; p.n_bsup = la.n_bsup; p.n_bw = la.n_bw;
-  if (!ctx->con_lists) {
-    ctx->con_bmw = (c.t_vocab + 31) / 32;
-    TRY(ctx->alloc((void**)&ctx->con_lists, (size_t)CON_LIST_WORDS * 4));
-    TRY(ctx->alloc((void**)&ctx->con_len, (size_t)c.max_batch * 4));
-    TRY(ctx->alloc((void**)&ctx->con_plen, (size_t)c.max_batch * 4));
-    TRY(ctx->alloc((void**)&ctx->con_ban, (size_t)c.max_batch * ctx->con_bmw * 4));
-    TRY(ctx->alloc((void**)&ctx->con_logits, (size_t)c.max_batch * c.t_vocab * 4));
-  }
-  // history rows: the prompt, one id per decode step, grown on demand and never shrunk; rows 16-byte aligned
-  const int need = (maxP + max_new + 1 + 3) / 4 * 4;
-  void* old = ctx->con_hist.p;
-  if (need > ctx->con_ld) {
-    TRY(ctx->grow(ctx->con_hist, (size_t)c.max_batch * need * 4));
-    ctx->con_ld = need;
-  }
-  if (!(p == ctx->con) || old != ctx->con_hist.p) drop_graphs();
-  ctx->con = p;
-  ctx->con_fed = 0;
-  ctx->con_room = ctx->con_ld - maxP;
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<int32_t> len(c.max_batch, 0);
-  std::copy(prompt_len, prompt_len + b, len.begin());
-  OM_HIP(hipMemcpyAsync(ctx->con_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
-  OM_HIP(hipMemcpyAsync(ctx->con_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
-  OM_HIP(hipMemcpyAsync(ctx->con_plen, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
-  OM_HIP(hipMemsetAsync(ctx->con_ban, 0, (size_t)c.max_batch * ctx->con_bmw * 4, s));
-  size_t off = 0;
-  for (int i = 0; i < b; ++i) {
-    if (prompt_len[i])
-      OM_HIP(hipMemcpyAsync((int32_t*)ctx->con_hist.p + (size_t)i * ctx->con_ld, prompt_ids + off, (size_t)prompt_len[i] * 4, hipMemcpyHostToDevice, s));
-    off += (size_t)prompt_len[i];
-  }
-  OM_HIP(hipStreamSynchronize(s));     // host vectors and the caller's ids
-  return 0;
-}
-
-// Per-token log-probabilities (include/omchat_hip.h).  The record and its geometry live in the kernel arguments of the captured decode graphs:
-// switching on or off, another b / max_new or a record that had to grow drops them.
-extern "C" int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream) {
-  OM_CHECK(ctx, "null ctx");
-  const omchat_config& c = ctx->c;
-  auto drop_graphs = [&]() {
-    for (auto& kv : ctx->graphs) destroy_graph(kv.second);
-    ctx->graphs.clear();
-  };
-  if (b <= 0) {
-    if (ctx->lp.on) drop_graphs();
-    ctx->lp = omchat_ctx::Logprobs{};
-    ctx->lp_picks = 0;
-    return 0;
-  }
-  OM_CHECK(c.t_layers > 0, "context has no decoder");
-  OM_CHECK(b <= c.max_batch, "logprobs: batch exceeds max_batch");
-  OM_CHECK(max_new >= 1, "logprobs: max_new >= 1");
-  OM_CHECK(!ctx->beam.on, "logprobs: a beam search is active (it reports sequences_scores)");
-  if (!ctx->lp_cnt) {
-    TRY(ctx->alloc((void**)&ctx->lp_cnt, (size_t)c.max_batch * 4));
-    TRY(ctx->alloc(&ctx->lp_ws, logprob_ws_bytes(c.max_batch)));
-    if (ctx->tp_size > 1) TRY(ctx->alloc((void**)&ctx->lp_table, logprob_table_bytes(c.max_batch, ctx->tp_size)));
-  }
-  // the captured graphs hold the record's address, its capacity (the stride of the processed plane) and b: another max_new within the
-  // capacity keeps them (the host refuses the picks beyond it)
-  void* old = ctx->lp_rec.p;
-  if (max_new > ctx->lp_cap) {
-    TRY(ctx->grow(ctx->lp_rec, (size_t)2 * max_new * c.max_batch * 4));
-    ctx->lp_cap = max_new;
-  }
-  if (!ctx->lp.on || ctx->lp.b != b || old != ctx->lp_rec.p) drop_graphs();
-  ctx->lp.on = true; ctx->lp.b = b; ctx->lp.max_new = max_new;
-  ctx->lp_picks = 0;
-  OM_HIP(hipMemsetAsync(ctx->lp_cnt, 0, (size_t)c.max_batch * 4, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* processed, int32_t* counts, int max_len) {
-  OM_CHECK(ctx && raw && processed && counts, "null argument");
-  OM_CHECK(ctx->lp.on && b >= 1 && b <= ctx->lp.b, "omchat_read_logprobs: rows that omchat_set_logprobs switched on");
-  const int mb = ctx->c.max_batch, mn = ctx->lp_cap;
-  OM_HIP(hipDeviceSynchronize());
-  std::vector<float> rec((size_t)2 * mn * mb);
-  std::vector<int> cnt(mb);
-  OM_HIP(hipMemcpy(rec.data(), ctx->lp_rec.p, rec.size() * 4, hipMemcpyDeviceToHost));
-  OM_HIP(hipMemcpy(cnt.data(), ctx->lp_cnt, cnt.size() * 4, hipMemcpyDeviceToHost));
-  for (int i = 0; i < b; ++i) {
-    const int n = std::min(std::max(cnt[i], 0), ctx->lp.max_new);
-    OM_CHECK(n <= max_len, "omchat_read_logprobs: max_len too small");
-    counts[i] = n;
-    for (int t = 0; t < n; ++t) {
-      raw[(size_t)i * max_len + t] = rec[(size_t)t * mb + i];
-      processed[(size_t)i * max_len + t] = rec[((size_t)mn + t) * mb + i];
-    }
-  }
-  return 0;
-}
-
-// one more decode step feeds the history: refuse before the step is enqueued when it has no room left (max_new of omchat_set_constraints)
-static int con_count_step(omchat_ctx* ctx) {
-  if (!ctx->con.on) return 0;
-  OM_CHECK(ctx->con_fed + 1 < ctx->con_room, "constraints: more decode steps than the max_new given to omchat_set_constraints");
-  ctx->con_fed += 1;
-  return 0;
-}
-
-// the first token after the prefill (omchat_greedy's sampled counterpart): advances the step counters, not the decode positions
-extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
-  OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
-  TRY(lp_room(ctx));
-  if (ctx->lp.on) ctx->lp_picks += 1;
-  return pick_next(ctx, logits, b, next_tokens, (hipStream_t)stream);
-}
 
 extern "C" int omchat_enable_decode_graph(omchat_ctx* ctx, int on) {
   OM_CHECK(ctx, "null ctx");
@@ -2138,9 +1541,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   // a weight reload (omchat_load_tensor) leaves the e4m3 replica stale: re-quantise IN PLACE before streaming it (same device
   // pointers, so a captured decode graph stays valid and replays the fresh bytes)
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
-  if (next_tokens) TRY(lp_room(ctx));
-  TRY(con_count_step(ctx));
-  if (ctx->lp.on && next_tokens) ctx->lp_picks += 1;
+  TRY(pick_admit(ctx, next_tokens != nullptr, true));
   ctx->graph_steps++;
   // graph replay needs replay-invariant arguments: single-GPU fused path only; with profiling on, every 8th step runs eagerly
   // so that the HIP-event brackets of the dominant kernel are still recorded inside the timed region
@@ -2190,10 +1591,10 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(T >= 2 && T <= VERIFY_MAX_T, "2 <= T <= 16 tokens (T = 1 is omchat_decode_step)");
   OM_CHECK(c.t_kv_heads > 0 && T * (c.t_heads / c.t_kv_heads) <= 128, "T * (q heads per kv head) must be <= 128 (the verify attention's query rows)");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "after a padded-batch prefill or masked decode steps");
-  OM_CHECK(!ctx->smp.on, "sampling is on: prompt-lookup decoding is greedy only");
-  OM_CHECK(!ctx->con.on, "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
-  OM_CHECK(!ctx->beam.on, "a beam search is active");
-  OM_CHECK(!ctx->lp.on, "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
+  OM_CHECK(!ctx->pick.sampling_on(), "sampling is on: prompt-lookup decoding is greedy only");
+  OM_CHECK(!ctx->pick.constraints_on(), "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
+  OM_CHECK(!ctx->beam.on(), "a beam search is active");
+  OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
   OM_CHECK(!(ctx->fp8_kv && ctx->kv8_valid), "the e4m3 KV cache is not implemented");
   const int L = ctx->h_len[0];
   OM_CHECK(L >= 1, "decode before prefill");
@@ -2248,9 +1649,7 @@ extern "C" int omchat_decode_step_masked(omchat_ctx* ctx, const int32_t* tokens,
     OM_CHECK(positions[i] >= 0 && positions[i] < c.max_seq, "position outside the RoPE table");
     OM_CHECK(key_mask[(size_t)i * mask_ld + Lc] != 0, "the new token must see itself");
   }
-  if (next_tokens) TRY(lp_room(ctx));
-  TRY(con_count_step(ctx));
-  if (ctx->lp.on && next_tokens) ctx->lp_picks += 1;
+  TRY(pick_admit(ctx, next_tokens != nullptr, true));
   ctx->mask_on_device = false;      // the device copy holds THIS step's mask, zero-padded: omchat_decode_step_masked_next needs a new begin
   OM_HIP(hipMemsetAsync(ctx->d_mask, 0, (size_t)b * ctx->mask_sb, s));
   OM_HIP(hipMemcpy2DAsync(ctx->d_mask, (size_t)ctx->mask_sb, key_mask, (size_t)mask_ld, (size_t)Lc + 1, (size_t)b, hipMemcpyHostToDevice, s));
@@ -2299,9 +1698,7 @@ extern "C" int omchat_decode_step_masked_next(omchat_ctx* ctx, const int32_t* to
   TRY(masked_common_checks(ctx, b));
   OM_CHECK(ctx->mask_on_device, "omchat_decode_step_masked_next: call omchat_masked_decode_begin after the prefill (and after any omchat_decode_step_masked)");
   const int Lc = ctx->pre_S + ctx->masked_steps;
-  if (next_tokens) TRY(lp_room(ctx));
-  TRY(con_count_step(ctx));
-  if (ctx->lp.on && next_tokens) ctx->lp_picks += 1;
+  TRY(pick_admit(ctx, next_tokens != nullptr, true));
   const int rc = decode_body(ctx, tokens, b, Lc + 1, logits, next_tokens, (hipStream_t)stream, false, true, true);
   if (rc) return rc;
   ctx->masked_steps += 1;
@@ -2443,29 +1840,14 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   OM_CHECK(ctx && b >= 1 && b <= (int)ctx->h_len.size() && n >= 0, "bad argument");
   if (n == 0) return 0;
   // every refusal before anything is enqueued or changed: the sampler's counters, the constraint history and the KV lengths stay in step
-  OM_CHECK(!ctx->lp.on || b >= ctx->lp.b, "rewind of fewer rows than omchat_set_logprobs switched on: the rows' records would fall out of step");
-  OM_CHECK(!ctx->smp.on || n == 1 || ctx->smp.penalty == 1.f,
-           "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded");
+  const char* why = pick_rewind_refusal(ctx, b, n);
+  OM_CHECK(!why, why);
   if (ctx->dec_mode == 2) {
     OM_CHECK(n <= ctx->masked_steps, "rewind beyond the prefill");
   } else {
     for (int i = 0; i < b; ++i) OM_CHECK(ctx->h_len[i] - n >= 1, "rewind beyond the prefill");
   }
-  if (ctx->smp.on) {
-    // the sampler's step counters go back with the slots, and the seen bit the last pick set is cleared (only that pick is recorded)
-    TRY(launch_sample_rewind(ctx->smp.penalty != 1.f ? ctx->smp_bm : nullptr, ctx->smp_bmw, ctx->smp_last, ctx->smp_step, b, n,
-                             (hipStream_t)stream));
-  }
-  if (ctx->lp.on) {
-    // the record forgets the picks of those steps
-    TRY(launch_logprob_rewind(ctx->lp_cnt, std::min(b, ctx->lp.b), n, (hipStream_t)stream));
-    ctx->lp_picks = std::max(0, ctx->lp_picks - n);
-  }
-  if (ctx->con.on) {
-    // the history forgets the fed ids with the slots
-    TRY(launch_constrain_rewind(ctx->con_len, ctx->con_plen, std::min(b, ctx->con.b), n, (hipStream_t)stream));
-    ctx->con_fed = std::max(0, ctx->con_fed - n);
-  }
+  TRY(pick_rewind(ctx, b, n, (hipStream_t)stream));
   if (ctx->dec_mode == 2) {
     ctx->masked_steps -= n;
     // the device-resident positions (omchat_decode_step_masked_next) go back with the slots; the host-mask form passes its positions every step
@@ -2485,186 +1867,9 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// beam search: selection and KV gather in beam.hip, the search state on the device
-// ---------------------------------------------------------------------------------------------------------
-static KvGatherArgs beam_kv_args(omchat_ctx* ctx, bool with_stash) {
-  const omchat_config& c = ctx->c;
-  KvGatherArgs g;
-  g.k = (char*)ctx->kcache; g.v = (char*)ctx->vcache;
-  g.layers = c.t_layers; g.kvh = c.t_kv_heads; g.max_seq = c.max_seq; g.rows_cap = c.max_batch;
-  const bool f8 = ctx->fp8_kv && ctx->kv8_valid;
-  if (f8) { g.k8 = (char*)ctx->k8cache; g.v8 = (char*)ctx->v8cache; g.ks = ctx->ks8; g.vs = ctx->vs8; }
-  if (with_stash) {
-    const int rows = ctx->beam.b * ctx->beam.N;
-    const size_t slots = (size_t)c.t_layers * rows * c.t_kv_heads * ctx->beam.max_new;
-    char* p = (char*)ctx->bm_stash.p;
-    g.sk = p; g.sv = p + slots * 256;
-    if (f8 && ctx->bm_stash8) {
-      g.sk8 = p + slots * 512; g.sv8 = p + slots * 640;
-      g.sks = (float*)(p + slots * 768); g.svs = (float*)(p + slots * 772);
-    }
-    g.st_rows = rows; g.st_slots = ctx->beam.max_new;
-  }
-  return g;
-}
-
-extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float length_penalty, int early_stopping, const int32_t* eos_ids,
-                                 int n_eos, int max_new, int prompt_tok_len, void* stream) {
-  OM_CHECK(ctx, "null ctx");
-  const omchat_config& c = ctx->c;
-  OM_CHECK(c.t_layers > 0, "context has no decoder");
-  const int N = num_beams;
-  OM_CHECK(b >= 1 && N >= 2 && N <= BEAM_NMAX, "beam search: b >= 1 and 2 <= num_beams <= 16");
-  OM_CHECK(!ctx->con.on, "beam search: constraints are on (omchat_set_constraints with b = 0 first); HF applies them to log-softmax scores there");
-  OM_CHECK(!ctx->lp.on, "beam search: logprobs are on (omchat_set_logprobs with b = 0 first); a beam search reports sequences_scores");
-  OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
-  OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
-  const int KB = std::max(2, 1 + n_eos) * N;
-  OM_CHECK(KB <= BEAM_KMAX, "beam search: max(2, 1 + n_eos) * num_beams must not exceed 32");
-  OM_CHECK(early_stopping >= 0 && early_stopping <= 2, "beam search: early_stopping 0 (False), 1 (True) or 2 (never)");
-  OM_CHECK(isfinite(length_penalty), "beam search: length_penalty must be finite");
-  OM_CHECK(max_new >= 1 && prompt_tok_len >= 1 && prompt_tok_len + max_new - 1 <= c.max_seq, "beam search: prompt + max_new exceed max_seq");
-  OM_CHECK(c.t_vocab_total >= KB, "beam search: vocabulary smaller than the candidates kept per step");
-  const int ns = beam_slices(c.t_vocab_total, ctx->tp_size);
-  OM_CHECK(ns >= 1, "beam search: the vocabulary cannot be cut into equal slices of <= 20480 ids for this TP degree");
-  OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "beam search: a left-padded or masked-decode batch (pad equal or use b = 1)");
-  omchat_ctx::Beam& B = ctx->beam;
-  B = omchat_ctx::Beam{};
-  B.b = b; B.N = N; B.KB = KB; B.max_new = max_new; B.P = prompt_tok_len; B.es = early_stopping; B.ns = ns; B.lp = length_penalty;
-  B.eos.assign(eos_ids, eos_ids + n_eos);
-  const int rows = b * N;
-  const size_t TS = (size_t)ns * (4 + 2 * KB);
-  const bool f8 = ctx->fp8_kv && ctx->kv8_valid;
-  const size_t slots = (size_t)c.t_layers * rows * c.t_kv_heads * max_new;
-  TRY(ctx->grow(ctx->bm_state, beam_state_words(b, N, max_new) * 4));
-  TRY(ctx->grow(ctx->bm_table, (rows * TS + 16) * 4));
-  TRY(ctx->grow(ctx->bm_dn, (size_t)(max_new + 1) * 4));
-  TRY(ctx->grow(ctx->bm_parents, (size_t)rows * 4));
-  TRY(ctx->grow(ctx->bm_stash, slots * (f8 ? 776 : 512)));
-  ctx->bm_stash8 = f8;
-  std::vector<float> dn(max_new + 1, 1.f);      // fp32(pow(g, length_penalty)): the Python float HF divides by, rounded as torch rounds it
-  for (int g = 1; g <= max_new; ++g) dn[g] = (float)pow((double)g, (double)length_penalty);
-  hipStream_t s = (hipStream_t)stream;
-  OM_HIP(hipMemcpyAsync(ctx->bm_dn.p, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s));
-  OM_HIP(hipStreamSynchronize(s));      // host vector
-  B.on = true;
-  return 0;
-}
-
-extern "C" int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* next_tokens, int32_t* done_word, void* stream) {
-  OM_CHECK(ctx && logits && next_tokens, "null argument");
-  omchat_ctx::Beam& B = ctx->beam;
-  OM_CHECK(B.on, "omchat_beam_step without omchat_beam_begin (or after a new prefill)");
-  OM_CHECK(B.t < B.max_new, "beam search: max_new steps taken");
-  OM_CHECK(rows == (B.t == 0 ? B.b : B.b * B.N), "beam step: rows = b on the prefill logits, b * num_beams afterwards");
-  const omchat_config& c = ctx->c;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t TS = (size_t)B.ns * (4 + 2 * B.KB);
-  float* table = (float*)ctx->bm_table.p;
-  if (ctx->tp_size > 1) OM_HIP(hipMemsetAsync(table, 0, rows * TS * 4, s));
-  TRY(launch_beam_select(logits, c.t_vocab, rows, c.t_vocab, ctx->tp_rank, ctx->tp_size, B.ns, B.KB, table, s));
-  if (ctx->tp_size > 1) TRY(ctx->allreduce_f32(table, rows * TS, s));
-  BeamFinishArgs a;
-  a.table = table; a.ns = B.ns; a.K = a.KB = B.KB; a.V_total = c.t_vocab_total;
-  a.b = B.b; a.N = B.N; a.t = B.t; a.max_new = B.max_new; a.es = B.es; a.lp_pos = B.lp > 0.f;
-  a.dn = (const float*)ctx->bm_dn.p;
-  a.n_eos = (int)B.eos.size();
-  for (int q = 0; q < a.n_eos; ++q) a.eos[q] = B.eos[q];
-  a.state = (int*)ctx->bm_state.p; a.tokens = next_tokens; a.parents = (int*)ctx->bm_parents.p; a.done_word = done_word;
-  TRY(launch_beam_finish(a, s));
-  const int bN = B.b * B.N;
-  if (B.t == 0) {
-    // fork: prompt i's row -> rows i*N .. i*N+N-1, last prompt first (its target rows lie above every source row not yet read)
-    const KvGatherArgs g = beam_kv_args(ctx, false);
-    for (int i = B.b - 1; i >= 0; --i) TRY(launch_kv_gather(g, nullptr, i * B.N, B.N, i, 0, B.P, s));
-    ctx->bm_hpos.assign(bN, B.P);
-    ctx->bm_hlen.assign(bN, B.P + 1);
-    for (int r = 0; r < bN; ++r) ctx->h_len[r] = B.P;
-    OM_HIP(hipMemcpyAsync(ctx->d_pos, ctx->bm_hpos.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
-    OM_HIP(hipMemcpyAsync(ctx->d_len, ctx->bm_hlen.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
-  } else {
-    const int L = ctx->h_len[0];
-    for (int r = 1; r < bN; ++r) OM_CHECK(ctx->h_len[r] == L, "beam step: the beam rows differ in length");
-    if (L > B.P) TRY(launch_kv_gather(beam_kv_args(ctx, true), (const int*)ctx->bm_parents.p, 0, bN, -1, B.P, L, s));
-  }
-  B.t++;
-  return 0;
-}
-
-extern "C" int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t* lengths, float* scores, int max_len) {
-  OM_CHECK(ctx && tokens && lengths && scores, "null argument");
-  const omchat_ctx::Beam& B = ctx->beam;
-  OM_CHECK(B.b > 0 && B.t > 0, "omchat_beam_result before a beam step");
-  OM_CHECK(num_return >= 1 && num_return <= B.N, "num_return_sequences must be in [1, num_beams]");
-  OM_HIP(hipDeviceSynchronize());
-  std::vector<int> st(beam_state_words(B.b, B.N, B.max_new));
-  OM_HIP(hipMemcpy(st.data(), ctx->bm_state.p, st.size() * 4, hipMemcpyDeviceToHost));
-  const int bN = B.b * B.N;
-  const int* bp = st.data() + 6 * bN + 2 * B.b;
-  for (int i = 0; i < B.b; ++i)
-    for (int q = 0; q < num_return; ++q) {
-      const int e = i * B.N + q, o = i * num_return + q;
-      float sc; memcpy(&sc, &st[BST_FSC * bN + e], 4);
-      scores[o] = sc;
-      const int step = st[BST_FSTEP * bN + e];
-      const int n = step + 1;
-      OM_CHECK(n <= max_len, "beam result: max_len too small");
-      lengths[o] = n;
-      if (n == 0) continue;
-      tokens[(size_t)o * max_len + step] = st[BST_FTOK * bN + e];
-      int beam = st[BST_FPAR * bN + e];
-      for (int u = step - 1; u >= 0; --u) {
-        const int* rec = bp + ((size_t)u * bN + i * B.N + beam) * 2;
-        tokens[(size_t)o * max_len + u] = rec[1];
-        beam = rec[0];
-      }
-    }
-  return 0;
-}
-
 extern "C" int omchat_kv_lengths(omchat_ctx* ctx, int32_t* out, int b) {
   OM_CHECK(ctx && out && b <= (int)ctx->h_len.size(), "bad argument");
   // after a left-padded prefill, and once a masked decode step ran, every row holds the same number of cache slots
   for (int i = 0; i < b; ++i) out[i] = (ctx->left_padded || ctx->dec_mode == 2) ? ctx->pre_S + ctx->masked_steps : ctx->h_len[i];
   return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// tensor-parallel bootstrap
-// ---------------------------------------------------------------------------------------------------------
-extern "C" int omchat_comm_unique_id(char id[128]) {
-  static_assert(sizeof(ncclUniqueId) <= 128, "ncclUniqueId larger than 128 bytes");
-  ncclUniqueId u;
-  ncclResult_t r = ncclGetUniqueId(&u);
-  if (r != ncclSuccess) { omchat_set_error(std::string("ncclGetUniqueId: ") + ncclGetErrorString(r)); return 3; }
-  memset(id, 0, 128);
-  memcpy(id, &u, sizeof(u));
-  return 0;
-}
-extern "C" int omchat_comm_init(const char id[128], int rank, int size, void** comm_out) {
-  ncclUniqueId u;
-  memcpy(&u, id, sizeof(u));
-  ncclComm_t comm;
-  ncclResult_t r = ncclCommInitRank(&comm, size, u, rank);
-  if (r != ncclSuccess) { omchat_set_error(std::string("ncclCommInitRank: ") + ncclGetErrorString(r)); return 3; }
-  *comm_out = comm;
-  return 0;
-}
-extern "C" int omchat_comm_allreduce(void* comm, void* buf, size_t count, int dtype, void* stream) {
-  OM_CHECK(comm && buf, "null argument");
-  const ncclDataType_t t = dtype == OMCHAT_F16 ? ncclFloat16 : dtype == OMCHAT_BF16 ? ncclBfloat16 : ncclFloat32;
-  OM_CHECK(dtype == OMCHAT_F16 || dtype == OMCHAT_BF16 || dtype == OMCHAT_F32, "bad dtype");
-  ncclResult_t r = ncclAllReduce(buf, buf, count, t, ncclSum, (ncclComm_t)comm, (hipStream_t)stream);
-  if (r != ncclSuccess) { omchat_set_error(std::string("ncclAllReduce: ") + ncclGetErrorString(r)); return 3; }
-  return 0;
-}
-extern "C" int omchat_comm_count(void* comm, int* nranks) {
-  OM_CHECK(comm && nranks, "null argument");
-  ncclResult_t r = ncclCommCount((ncclComm_t)comm, nranks);
-  if (r != ncclSuccess) { omchat_set_error(std::string("ncclCommCount: ") + ncclGetErrorString(r)); return 3; }
-  return 0;
-}
-extern "C" void omchat_comm_destroy(void* comm) {
-  if (comm) ncclCommDestroy((ncclComm_t)comm);
 }

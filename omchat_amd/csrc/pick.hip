@@ -1,0 +1,370 @@
+// The token pick of a step, with its state (PickState, ctx.h): the ban stage of the logits constraints (constrain.hip), the argmax
+// (elementwise.hip) or the sampler (sample.hip), the record stage of the per-token log-probabilities (logprob.hip) -- their order, the
+// refusals and host counters in front of a step, their setters and their rewind.  model.hip sees the functions ctx.h declares.  Host C++.
+#include "ctx.h"
+#include <math.h>
+#include <algorithm>
+
+namespace {
+
+// vocab-parallel greedy: every rank contributes (max logit, global index) per sequence; summed into a zeroed table
+__global__ void tp_argmax_scatter_kernel(const float* logits, int ld, const int* local_idx, int b, int rank, int v_local, float* table) {
+  const int i = threadIdx.x;
+  if (i < b) {
+    table[((size_t)rank * b + i) * 2] = logits[(size_t)i * ld + local_idx[i]];
+    table[((size_t)rank * b + i) * 2 + 1] = (float)(rank * v_local + local_idx[i]);
+  }
+}
+__global__ void tp_argmax_pick_kernel(const float* table, int b, int size, int* out) {
+  const int i = threadIdx.x;
+  if (i < b) {
+    float best = table[(size_t)i * 2]; int bi = (int)table[(size_t)i * 2 + 1];
+    for (int r = 1; r < size; ++r) {            // ranks hold ascending index ranges: strict > keeps the first index on ties
+      const float v = table[((size_t)r * b + i) * 2];
+      if (v > best) { best = v; bi = (int)table[((size_t)r * b + i) * 2 + 1]; }
+    }
+    out[i] = bi;
+  }
+}
+
+int smp_xchg(void* user, float* buf, size_t count, hipStream_t s) { return ((omchat_ctx*)user)->allreduce_f32(buf, count, s); }
+
+ConstrainArgs con_args(omchat_ctx* ctx, int b, const int32_t* fed) {
+  const omchat_config& c = ctx->c;
+  const PickState& P = ctx->pick;
+  ConstrainArgs a;
+  a.hist = (int32_t*)P.con_hist.p; a.hist_ld = P.con_ld; a.len = P.con_len; a.plen = P.con_plen; a.tok = fed;
+  a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total; a.gbase = ctx->tp_rank * c.t_vocab;
+  a.ngram = P.con.ngram; a.min_new = P.con.min_new; a.min_len = P.con.min_len;
+  constrain_bind_lists(P.con_lists, a);
+  a.n_eos = P.con.n_eos; a.n_sup = P.con.n_sup; a.n_bsup = P.con.n_bsup; a.n_bw = P.con.n_bw;
+  a.ban = P.con_ban; a.bmw = P.con_bmw;
+  return a;
+}
+
+// The ban stage in front of a pick (omchat_set_constraints; nothing when constraints are off): `fed` = the tokens the decode step was fed
+// (appended to the history first), NULL at the first pick after the prefill.  *lg then points at the context's banned copy of the logits;
+// the caller's logits are not written.
+int ban_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fed, hipStream_t s) {
+  const PickState& P = ctx->pick;
+  if (!P.con.on) return 0;
+  OM_CHECK(b <= P.con.b, "constraints are on for fewer rows than this pick has (omchat_set_constraints)");
+  const omchat_config& c = ctx->c;
+  TRY(launch_constrain_ban(con_args(ctx, b, fed), s));
+  TRY(launch_constrain_apply(*lg, c.t_vocab, b, c.t_vocab, P.con_ban, P.con_bmw, P.con_logits, fed ? P.con_len : nullptr, P.con_ld, s));
+  *lg = P.con_logits;
+  return 0;
+}
+
+// The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits, proc = what the pick ran on (the
+// banned copy when constraints are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
+int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, const int32_t* ids, hipStream_t s) {
+  const PickState& P = ctx->pick;
+  if (!P.lp.on) return 0;
+  const omchat_config& c = ctx->c;
+  LogprobArgs a;
+  a.raw = raw; a.raw_ld = c.t_vocab; a.proc = proc; a.proc_ld = c.t_vocab;
+  a.b = std::min(b, P.lp.b); a.V = c.t_vocab; a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
+  a.ids = ids;
+  if (P.smp.on) {
+    a.temperature = P.smp.temperature; a.penalty = P.smp.penalty;
+    if (P.smp.penalty != 1.f) { a.seen = P.smp_bm; a.bm_words = P.smp_bmw; a.last_set = P.smp_last; }
+    a.top1 = P.smp.top_k == 1;
+    a.thr = sample_thr_words(P.smp_ws, b, c.t_vocab_total, P.smp.top_k, P.smp.top_p, &a.thr_stride);
+  }
+  a.ws = P.lp_ws; a.table = P.lp_table; a.xchg = smp_xchg; a.xchg_user = ctx;
+  a.rec = (float*)P.lp_rec.p; a.cnt = P.lp_cnt; a.max_new = P.lp_cap; a.rec_ld = c.max_batch;
+  return launch_logprob(a, s);
+}
+
+// one more pick feeds the record: refuse before anything is enqueued when it is full (max_new of omchat_set_logprobs)
+int lp_room(omchat_ctx* ctx) {
+  OM_CHECK(!ctx->pick.lp.on || ctx->pick.lp_picks < ctx->pick.lp.max_new, "logprobs: more picks than the max_new given to omchat_set_logprobs");
+  return 0;
+}
+
+// one more decode step feeds the history: refuse before the step is enqueued when it has no room left (max_new of omchat_set_constraints)
+int con_count_step(omchat_ctx* ctx) {
+  if (!ctx->pick.con.on) return 0;
+  OM_CHECK(ctx->pick.con_fed + 1 < ctx->pick.con_room, "constraints: more decode steps than the max_new given to omchat_set_constraints");
+  ctx->pick.con_fed += 1;
+  return 0;
+}
+
+}  // namespace
+
+int pick_alloc(omchat_ctx* ctx, int rows) {
+  TRY(ctx->alloc(&ctx->pick.arg_scratch, argmax_scratch_bytes(rows)));
+  return ctx->alloc((void**)&ctx->pick.tp_table, (size_t)ctx->tp_size * rows * 2 * 4);
+}
+
+int pick_admit(omchat_ctx* ctx, bool picks, bool feeds) {
+  if (picks) TRY(lp_room(ctx));
+  if (feeds) TRY(con_count_step(ctx));
+  if (ctx->pick.lp.on && picks) ctx->pick.lp_picks += 1;
+  return 0;
+}
+
+// greedy argmax over (rank-local) logits; under tensor parallelism the (max, index) pairs are exchanged
+int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance) {
+  const omchat_config& c = ctx->c;
+  float* table = ctx->pick.tp_table;
+  TRY(launch_argmax(lg, c.t_vocab, b, c.t_vocab, next_tokens, ctx->pick.arg_scratch, s, advance ? ctx->d_pos : nullptr, advance ? ctx->d_len : nullptr));
+  if (ctx->tp_size > 1) {
+    const size_t n = (size_t)ctx->tp_size * b * 2;
+    OM_HIP(hipMemsetAsync(table, 0, n * 4, s));
+    hipLaunchKernelGGL(tp_argmax_scatter_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, lg, c.t_vocab, next_tokens, b, ctx->tp_rank, c.t_vocab, table);
+    TRY(ctx->allreduce_f32(table, n, s));
+    hipLaunchKernelGGL(tp_argmax_pick_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, table, b, ctx->tp_size, next_tokens);
+  }
+  return 0;
+}
+
+int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance, const int32_t* fed, bool force_greedy) {
+  const PickState& P = ctx->pick;
+  const float* raw = lg;
+  TRY(ban_stage(ctx, &lg, b, fed, s));
+  if (force_greedy || !P.smp.on) {
+    TRY(greedy_pick(ctx, lg, b, next_tokens, s, advance));
+    return logprob_stage(ctx, raw, lg, b, next_tokens, s);
+  }
+  const omchat_config& c = ctx->c;
+  SampleArgs a;
+  a.logits = lg; a.ld = c.t_vocab; a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total;
+  a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
+  a.seed = P.smp.seed; a.temperature = P.smp.temperature; a.top_k = P.smp.top_k; a.top_p = P.smp.top_p; a.penalty = P.smp.penalty;
+  if (P.smp.penalty != 1.f) { a.bitmap = P.smp_bm; a.bm_words = P.smp_bmw; }
+  a.last_set = P.smp_last; a.step = P.smp_step;
+  if (advance) { a.adv_pos = ctx->d_pos; a.adv_len = ctx->d_len; }
+  a.out = next_tokens; a.ws = P.smp_ws; a.table = P.tp_table;
+  a.xchg = smp_xchg; a.xchg_user = ctx;
+  TRY(launch_sample(a, s));
+  return logprob_stage(ctx, raw, lg, b, next_tokens, s);
+}
+
+// (rows beyond those the constraints are on for are not the history's: no refusal here, unlike the ban stage of a step that picks)
+int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s) {
+  const PickState& P = ctx->pick;
+  if (P.con.on && b <= P.con.b) TRY(launch_constrain_append((int32_t*)P.con_hist.p, P.con_ld, P.con_len, fed, b, s));
+  return 0;
+}
+
+const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n) {
+  const PickState& P = ctx->pick;
+  if (P.lp.on && b < P.lp.b) return "rewind of fewer rows than omchat_set_logprobs switched on: the rows' records would fall out of step";
+  if (P.smp.on && n != 1 && P.smp.penalty != 1.f) return "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded";
+  return nullptr;
+}
+
+int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s) {
+  PickState& P = ctx->pick;
+  if (P.smp.on) {
+    // the sampler's step counters go back with the slots, and the seen bit the last pick set is cleared (only that pick is recorded)
+    TRY(launch_sample_rewind(P.smp.penalty != 1.f ? P.smp_bm : nullptr, P.smp_bmw, P.smp_last, P.smp_step, b, n, s));
+  }
+  if (P.lp.on) {
+    // the record forgets the picks of those steps
+    TRY(launch_logprob_rewind(P.lp_cnt, std::min(b, P.lp.b), n, s));
+    P.lp_picks = std::max(0, P.lp_picks - n);
+  }
+  if (P.con.on) {
+    // the history forgets the fed ids with the slots
+    TRY(launch_constrain_rewind(P.con_len, P.con_plen, std::min(b, P.con.b), n, s));
+    P.con_fed = std::max(0, P.con_fed - n);
+  }
+  return 0;
+}
+
+extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
+  OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  TRY(lp_room(ctx));      // (in front of the refusal below as well: a full record is the first thing this call reports)
+  // (the sampler's state is not this pick's: with sampling on, the first token comes from omchat_sample)
+  OM_CHECK(!ctx->pick.lp.on || !ctx->pick.smp.on, "logprobs: omchat_greedy while sampling is on (omchat_sample picks the first token then)");
+  TRY(pick_admit(ctx, true, false));
+  return pick_run(ctx, logits, b, next_tokens, (hipStream_t)stream, false, nullptr, true);
+}
+
+// the first token after the prefill (omchat_greedy's sampled counterpart): advances the step counters, not the decode positions
+extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
+  OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  TRY(pick_admit(ctx, true, false));
+  return pick_run(ctx, logits, b, next_tokens, (hipStream_t)stream);
+}
+
+// Sampling parameters live in the kernel arguments of the captured decode graphs: a change drops them (re-captured on the next step).
+extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                                   const int32_t* seen_ids, const int32_t* n_seen_per_row, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  PickState::Sampling p;
+  p.on = b > 0;
+  if (p.on) {
+    OM_CHECK(b <= c.max_batch, "sampling: batch exceeds max_batch");
+    OM_CHECK(temperature > 0.f && isfinite(temperature), "sampling: temperature must be a strictly positive float (greedy: do_sample=False)");
+    OM_CHECK(top_k >= 0, "sampling: top_k >= 0 (0 = off)");
+    OM_CHECK(top_p > 0.0 && top_p <= 1.0, "sampling: top_p in (0, 1] (1 = off)");
+    OM_CHECK(rep_penalty > 0.f && isfinite(rep_penalty), "sampling: repetition_penalty must be a strictly positive float");
+    p.seed = seed; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.penalty = rep_penalty;
+  }
+  const PickState::Sampling& o = P.smp;
+  const bool same = o.on == p.on && o.seed == p.seed && o.temperature == p.temperature && o.top_k == p.top_k && o.top_p == p.top_p &&
+                    o.penalty == p.penalty;
+  if (!same) drop_decode_graphs(ctx);
+  P.smp = p;
+  if (!p.on) return 0;
+  if (!P.smp_ws) {
+    P.smp_bmw = (c.t_vocab + 31) / 32;
+    TRY(ctx->alloc(&P.smp_ws, sample_ws_bytes(c.max_batch)));
+    TRY(ctx->alloc((void**)&P.smp_bm, (size_t)c.max_batch * P.smp_bmw * 4));
+    TRY(ctx->alloc((void**)&P.smp_last, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&P.smp_step, (size_t)c.max_batch * 4));
+  }
+  // this rank's slice of the seen sets; ids outside the vocabulary (the -200 image sentinel) are never seen
+  std::vector<uint32_t> bm((size_t)c.max_batch * P.smp_bmw, 0u);
+  if (rep_penalty != 1.f && seen_ids && n_seen_per_row) {
+    const int64_t lo = (int64_t)ctx->tp_rank * c.t_vocab;
+    size_t off = 0;
+    for (int i = 0; i < b; ++i) {
+      OM_CHECK(n_seen_per_row[i] >= 0, "sampling: n_seen_per_row >= 0");
+      for (int j = 0; j < n_seen_per_row[i]; ++j) {
+        const int64_t li = (int64_t)seen_ids[off + j] - lo;
+        if (seen_ids[off + j] >= 0 && seen_ids[off + j] < c.t_vocab_total && li >= 0 && li < c.t_vocab)
+          bm[(size_t)i * P.smp_bmw + (li >> 5)] |= 1u << (li & 31);
+      }
+      off += (size_t)n_seen_per_row[i];
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemcpyAsync(P.smp_bm, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(P.smp_step, 0, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipMemsetAsync(P.smp_last, 0xFF, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipStreamSynchronize(s));     // host vector
+  return 0;
+}
+
+// Constraint parameters live in the kernel arguments of the captured decode graphs, as the sampling ones do: a change (or a history buffer
+// that had to grow) drops them.  The id lists are read from device memory at every pick, so new contents of the same size keep the graphs.
+extern "C" int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids,
+                                      int n_eos, const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
+                                      const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
+                                      const int32_t* prompt_len, int max_new, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  if (b <= 0) {
+    if (P.con.on) drop_decode_graphs(ctx);
+    P.con = PickState::Constraints{};
+    return 0;
+  }
+  // every refusal before anything is enqueued or changed
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(b <= c.max_batch, "constraints: batch exceeds max_batch");
+  OM_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= CON_NGRAM_MAX, "constraints: 0 <= no_repeat_ngram_size <= 64 (0 = off)");
+  OM_CHECK(min_new_tokens >= 0 && min_length >= 0, "constraints: min_new_tokens and min_length >= 0");
+  OM_CHECK(prompt_ids && prompt_len && max_new >= 1, "constraints: prompt ids, per-row lengths and max_new >= 1");
+  OM_CHECK(!ctx->beam.on(), "constraints: a beam search is active (the processors act on log-softmax scores there)");
+  int maxP = 0;
+  for (int i = 0; i < b; ++i) {
+    OM_CHECK(prompt_len[i] >= 0, "constraints: prompt_len >= 0");
+    maxP = std::max(maxP, prompt_len[i]);
+  }
+  PickState::Constraints p;
+  p.on = true; p.b = b; p.ngram = no_repeat_ngram_size; p.min_new = min_new_tokens; p.min_len = min_length;
+  std::vector<int32_t> lists(CON_LIST_WORDS);
+  ConstrainArgs la;
+  TRY(constrain_pack_lists(eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_word_ids, bad_word_offsets,
+                           n_bad_words, lists.data(), la));
+  p.n_eos = la.n_eos; p.n_sup = la.n_sup; p.n_bsup = la.n_bsup; p.n_bw = la.n_bw;
+  if (!P.con_lists) {
+    P.con_bmw = (c.t_vocab + 31) / 32;
+    TRY(ctx->alloc((void**)&P.con_lists, (size_t)CON_LIST_WORDS * 4));
+    TRY(ctx->alloc((void**)&P.con_len, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&P.con_plen, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&P.con_ban, (size_t)c.max_batch * P.con_bmw * 4));
+    TRY(ctx->alloc((void**)&P.con_logits, (size_t)c.max_batch * c.t_vocab * 4));
+  }
+  // history rows: the prompt, one id per decode step, grown on demand and never shrunk; rows 16-byte aligned
+  const int need = (maxP + max_new + 1 + 3) / 4 * 4;
+  void* old = P.con_hist.p;
+  if (need > P.con_ld) {
+    TRY(ctx->grow(P.con_hist, (size_t)c.max_batch * need * 4));
+    P.con_ld = need;
+  }
+  if (!(p == P.con) || old != P.con_hist.p) drop_decode_graphs(ctx);
+  P.con = p;
+  P.con_fed = 0;
+  P.con_room = P.con_ld - maxP;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> len(c.max_batch, 0);
+  std::copy(prompt_len, prompt_len + b, len.begin());
+  OM_HIP(hipMemcpyAsync(P.con_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(P.con_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(P.con_plen, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(P.con_ban, 0, (size_t)c.max_batch * P.con_bmw * 4, s));
+  size_t off = 0;
+  for (int i = 0; i < b; ++i) {
+    if (prompt_len[i])
+      OM_HIP(hipMemcpyAsync((int32_t*)P.con_hist.p + (size_t)i * P.con_ld, prompt_ids + off, (size_t)prompt_len[i] * 4, hipMemcpyHostToDevice, s));
+    off += (size_t)prompt_len[i];
+  }
+  OM_HIP(hipStreamSynchronize(s));     // host vectors and the caller's ids
+  return 0;
+}
+
+// Per-token log-probabilities (include/omchat_hip.h).  The record and its geometry live in the kernel arguments of the captured decode graphs:
+// switching on or off, another b / max_new or a record that had to grow drops them.
+extern "C" int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  if (b <= 0) {
+    if (P.lp.on) drop_decode_graphs(ctx);
+    P.lp = PickState::Logprobs{};
+    P.lp_picks = 0;
+    return 0;
+  }
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(b <= c.max_batch, "logprobs: batch exceeds max_batch");
+  OM_CHECK(max_new >= 1, "logprobs: max_new >= 1");
+  OM_CHECK(!ctx->beam.on(), "logprobs: a beam search is active (it reports sequences_scores)");
+  if (!P.lp_cnt) {
+    TRY(ctx->alloc((void**)&P.lp_cnt, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc(&P.lp_ws, logprob_ws_bytes(c.max_batch)));
+    if (ctx->tp_size > 1) TRY(ctx->alloc((void**)&P.lp_table, logprob_table_bytes(c.max_batch, ctx->tp_size)));
+  }
+  // the captured graphs hold the record's address, its capacity (the stride of the processed plane) and b: another max_new within the
+  // capacity keeps them (the host refuses the picks beyond it)
+  void* old = P.lp_rec.p;
+  if (max_new > P.lp_cap) {
+    TRY(ctx->grow(P.lp_rec, (size_t)2 * max_new * c.max_batch * 4));
+    P.lp_cap = max_new;
+  }
+  if (!P.lp.on || P.lp.b != b || old != P.lp_rec.p) drop_decode_graphs(ctx);
+  P.lp.on = true; P.lp.b = b; P.lp.max_new = max_new;
+  P.lp_picks = 0;
+  OM_HIP(hipMemsetAsync(P.lp_cnt, 0, (size_t)c.max_batch * 4, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* processed, int32_t* counts, int max_len) {
+  OM_CHECK(ctx && raw && processed && counts, "null argument");
+  const PickState& P = ctx->pick;
+  OM_CHECK(P.lp.on && b >= 1 && b <= P.lp.b, "omchat_read_logprobs: rows that omchat_set_logprobs switched on");
+  const int mb = ctx->c.max_batch, mn = P.lp_cap;
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<float> rec((size_t)2 * mn * mb);
+  std::vector<int> cnt(mb);
+  OM_HIP(hipMemcpy(rec.data(), P.lp_rec.p, rec.size() * 4, hipMemcpyDeviceToHost));
+  OM_HIP(hipMemcpy(cnt.data(), P.lp_cnt, cnt.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < b; ++i) {
+    const int n = std::min(std::max(cnt[i], 0), P.lp.max_new);
+    OM_CHECK(n <= max_len, "omchat_read_logprobs: max_len too small");
+    counts[i] = n;
+    for (int t = 0; t < n; ++t) {
+      raw[(size_t)i * max_len + t] = rec[(size_t)t * mb + i];
+      processed[(size_t)i * max_len + t] = rec[((size_t)mn + t) * mb + i];
+    }
+  }
+  return 0;
+}

@@ -253,7 +253,7 @@ __device__ __forceinline__ void smp_commit(int row, int id, int gbase, int V, ui
 }
 
 // the 64 race partials of a row -> its winner.  TP = 1: commit.  TP > 1: (value, global index) into this rank's slot of the zeroed table that
-// the greedy exchange uses (model.hip: tp_argmax_scatter_kernel's layout)
+// the greedy exchange uses (pick.hip: tp_argmax_scatter_kernel's layout)
 __global__ __launch_bounds__(64) void smp_final_kernel(const float* pv, const int* pi, int b, int tp, int rank, float* table, int gbase, int V,
                                                        uint32_t* bm, int bmw, int* last, int* step, int* adv_pos, int* adv_len, int* out,
                                                        const int64_t* st, uint32_t* thr_out) {
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(64) void smp_final_kernel(const float* pv, const in
   smp_commit(row, besti == INT_MAX ? 0 : besti, gbase, V, bm, bmw, last, step, adv_pos, adv_len, out);
 }
 
-// after the exchange: ranks hold ascending index ranges, so strict > keeps the first index on ties (tp_argmax_pick_kernel's rule)
+// after the exchange: ranks hold ascending index ranges, so strict > keeps the first index on ties (pick.hip: tp_argmax_pick_kernel's rule)
 __global__ void smp_tp_pick_kernel(const float* table, int b, int tp, int gbase, int V, uint32_t* bm, int bmw, int* last, int* step,
                                    int* adv_pos, int* adv_len, int* out) {
   const int i = threadIdx.x;

@@ -341,7 +341,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         else:
             out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
         # ONE rule for the first token at every TP degree: omchat_greedy on this rank's vocabulary shard -- local first-index-wins argmax,
-        # then the (max, index) exchange the decode step uses (model.hip: greedy_pick); no torch re-statement on the gathered logits.
+        # then the (max, index) exchange the decode step uses (pick.hip: greedy_pick); no torch re-statement on the gathered logits.
         # Sampling: the same seam with the sampler (omchat_sample); the decode steps below then sample too, the penalty's seen set growing
         # on the device.  HF drives the processors with input_ids (the prompt, pads included) + the generated ids.
         if con is not None:

@@ -259,6 +259,66 @@ def test_record_capacity_rewind_device_bytes_and_refusals(gpu_lib):
     e.close()
 
 
+LP_FULL = "more picks than the max_new given to omchat_set_logprobs"
+CON_FULL = "more decode steps than the max_new given to omchat_set_constraints"
+
+
+def _steps_until_refused(step, tok, message, limit=32):
+    """decode steps that succeed before one is refused with `message` -> (their number, the last token)"""
+    for n in range(limit):
+        try:
+            tok, _ = step(tok)
+        except ValueError as ex:
+            assert message in str(ex), str(ex)
+            return n, tok
+    raise AssertionError("no refusal within %d steps" % limit)
+
+
+@pytest.mark.parametrize("path", ["decode_step", "decode_step_masked_next"])
+def test_refused_pick_leaves_the_history_room_and_the_kv_lengths(gpu_lib, path):
+    """The admission of a step: the record's room (omchat_set_logprobs) is checked before the history's (omchat_set_constraints), and a
+    refused step moves no counter -- the history's budget, measured first without a record, is all still there after the refusal."""
+    _, e, m = _tiny_model()
+    if path == "decode_step":
+        ids, kw, step = torch.tensor([[3, 17, 18, 19], [5, 6, 11, 12]]), {}, e.decode_step
+    else:
+        ids, step = torch.tensor([[3, 17, 18, 19], [5, 6, 0, 0]]), e.decode_step_masked_next
+        kw = dict(attention_mask=torch.tensor([[1, 1, 1, 1], [1, 1, 0, 0]]))
+
+    def begin(logprobs):
+        fw = m.forward(input_ids=ids, use_cache=True, **kw)
+        e.sampling_off()
+        e.set_constraints(2, ids.tolist(), 6, no_repeat_ngram_size=2)
+        if logprobs:
+            e.set_logprobs(2, 2)
+        else:
+            e.logprobs_off()
+        if kw:      # positions and key mask of the first step as generate() takes them from the reference's decode branch
+            m1 = torch.cat([kw["attention_mask"], torch.ones(2, 1, dtype=torch.long)], 1)
+            _, pos1, mask1, _, _, _ = m.prepare_inputs_labels_for_multimodal(torch.zeros(2, 1, dtype=torch.long), None, m1, fw.past_key_values,
+                                                                             None, None)
+            if pos1 is None:
+                pos1 = torch.full((2, 1), fw.past_key_values.get_seq_length(), dtype=torch.long)
+            e.masked_decode_begin(pos1, mask1)
+        return e.argmax(fw.local_logits)
+
+    budget, _ = _steps_until_refused(step, begin(False), CON_FULL)      # the history's room in decode steps
+    assert budget >= 6
+    tok = begin(True)                                                   # the record's first line: the prefill's pick
+    taken, tok = _steps_until_refused(step, tok, LP_FULL)
+    assert taken == 1
+    kv = e.kv_lengths(2)
+    with pytest.raises(ValueError, match=LP_FULL):
+        step(tok)
+    assert e.kv_lengths(2) == kv and e.read_logprobs(2)[2] == [2, 2]
+    e.logprobs_off()
+    more, _ = _steps_until_refused(step, tok, CON_FULL)
+    assert more == budget - taken, (more, budget, taken)
+    assert e.kv_lengths(2) == [n + more for n in kv]
+    e.constraints_off()
+    e.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- generate()
 def test_generate_output_logprobs(gpu_lib):
     _, e, m = _tiny_model()
