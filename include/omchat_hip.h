@@ -517,6 +517,37 @@ int omchat_op_rope_kv(int dtype, void* qkv, int b, int S, int Hq, int Hkv, int p
 int omchat_op_rope_kv_q8(int dtype, void* qkv, int b, int S, int Hq, int Hkv, int pos0, float theta, void* kcache, void* vcache, int cap,
                          void* k8, void* v8, float* ks, float* vs, void* stream);
 int omchat_op_argmax(const float* logits, int b, int V, int32_t* out, void* stream);
+/* test hooks of the row / glue kernels (tests/test_gpu_glue_ops.py): the launchers the model loops call, with the arguments the entry points above
+ * do not expose.
+ * omchat_op_attn_prefill_left: omchat_op_attn_prefill of a LEFT-padded batch -- kv_start device int32 [b], keys j < kv_start[i] of sequence i are
+ * masked; fill_uniform != 0 then writes the uniform average of all Skv value rows to the query rows i < kv_start (what omchat_prefill_left does). */
+int omchat_op_attn_prefill_left(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Sq, int Skv, int Hq, int Hkv,
+                                const int32_t* kv_len, const int32_t* kv_start, int causal, int q_pos0, float scale, int fill_uniform, void* stream);
+/* test hook: omchat_op_rope_kv with per-row positions (pos device int32 [b * S] or NULL -> pos0 + s) and the cache slot slot0 + s instead of the
+ * position (slot0 = -1: the position itself); the cos / sin table holds max_pos positions.  A position >= max_pos or a slot >= cap is refused
+ * before anything is launched.  Synchronises. */
+int omchat_op_rope_kv_pos(int dtype, void* qkv, int b, int S, int Hq, int Hkv, const int32_t* pos, int pos0, int slot0, int max_pos, float theta,
+                          void* kcache, void* vcache, int cap, void* stream);
+/* test hook: omchat_op_argmax over rows of stride ld >= V; adv_pos / adv_len device int32 [b] or NULL: each advanced by one per row */
+int omchat_op_argmax_ld(const float* logits, int ld, int b, int V, int32_t* out, int32_t* adv_pos, int32_t* adv_len, void* stream);
+/* test hook: pixels [B,3,HW,HW] -> cols [B * (HW / patch)^2, Kpad], columns (channel, ky, kx), zero beyond 3 * patch^2 */
+int omchat_op_im2col(int dtype, const void* pixels, void* cols, int B, int HW, int patch, int Kpad, void* stream);
+/* test hook: x [B, np + 1, C]: x[b, 0] = cls + pos[0], x[b, 1 + p] = pe[b * np + p] + pos[1 + p] (fp32 sum, one rounding) */
+int omchat_op_vit_assemble(int dtype, const void* pe, const void* cls, const void* pos, void* x, int B, int np, int C, void* stream);
+/* test hook: out[r] = table[idx[r]] (idx >= 0) | feats[-1 - idx[r]] (idx < 0) | zeros (idx == INT_MIN); idx device int32 [rows] */
+int omchat_op_gather_rows(int dtype, const int32_t* idx, const void* table, const void* feats, void* out, int rows, int H, void* stream);
+/* test hook: dst[r] = src[(r / group) * (group + skip) + skip + r % group], rows of width H with strides src_ld / dst_ld (elements) */
+int omchat_op_copy_rows(int dtype, const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int rows, int H, int group, int skip, void* stream);
+/* test hook: out [M, N] = epi(sum [M, N] fp32, bias, ls, resid) with the rounding points of omchat_op_gemm's epilogues EPI_NONE / EPI_RESID / EPI_LS_RESID */
+int omchat_op_tp_finish(int dtype, const float* sum, const void* bias, const void* ls, const void* resid, void* out, int M, int N, int epi, void* stream);
+/* test hook: x = T(x + y) in place, then xn = RMSNorm(x) * w (b == NULL), LayerNorm(x) * w + b, or nothing (w == NULL) */
+int omchat_op_resid16_norm(int dtype, void* x, int ldx, const void* y, int ldy, const void* w, const void* b, void* xn, int ldn, int rows, int H,
+                           float eps, void* stream);
+/* test hook: dst fp32 [n] = src (dtype) [n] */
+int omchat_op_cast_f32(int dtype, const void* src, float* dst, int64_t n, void* stream);
+/* test hooks: omchat_op_rmsnorm / omchat_op_layernorm with row strides ldx / ldy >= H; pack_nb != 0 writes y in the packed x layout */
+int omchat_op_rmsnorm_ld(int dtype, const void* x, int ldx, const void* w, void* y, int ldy, int rows, int H, float eps, int pack_nb, void* stream);
+int omchat_op_layernorm_ld(int dtype, const void* x, int ldx, const void* w, const void* b, void* y, int ldy, int rows, int H, float eps, void* stream);
 /* context-free ban pass of omchat_set_constraints (test hook): histories host int32, the rows one after another (hist_len host int32 [b]; prompt_len
  * host int32 [b] = how many of them are the prompt); V ids of the vocabulary slice of `rank` out of V_total; fed_last != 0 passes each row's last
  * id as the token a decode step is fed instead of as stored history (the same set either way).  ban_out device uint32 [b][(V + 31) / 32]: bit i

@@ -9,6 +9,7 @@ _lib = None
 
 F16, BF16, F32 = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_LS_RESID, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3, 4
+EPI_F32OUT = 6      # raw fp32 accumulators (tensor parallelism; finished by omchat_op_tp_finish)
 EPI_LS_RESID_STATS, EPI_NONE_STATS = 7, 8      # round 6: the same epilogues + per-row sum-of-squares slots (kernels.h)
 PAD_ROW = -(2 ** 31)
 PROF_DECODE_GATEUP, PROF_PREFILL_GATEUP, PROF_VIT_FC1 = 0, 1, 2
@@ -119,6 +120,18 @@ _SIGS = {
     "omchat_op_rope_kv": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "omchat_op_rope_kv_q8": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_argmax": (_i, [_vp, _i, _i, _vp, _vp]),
+    "omchat_op_attn_prefill_left": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "omchat_op_rope_kv_pos": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "omchat_op_argmax_ld": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "omchat_op_im2col": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "omchat_op_vit_assemble": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "omchat_op_gather_rows": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "omchat_op_copy_rows": (_i, [_i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "omchat_op_tp_finish": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "omchat_op_resid16_norm": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "omchat_op_cast_f32": (_i, [_i, _vp, _vp, _i64, _vp]),
+    "omchat_op_rmsnorm_ld": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    "omchat_op_layernorm_ld": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_op_token_logprob": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_constrain": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),

@@ -640,3 +640,104 @@ extern "C" int omchat_op_attn_prefill_d(int dtype, const void* q, const void* k,
 extern "C" int omchat_op_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, int rows, int H, float eps, void* stream) {
   return launch_layernorm(dtype, x, H, w, b, y, H, rows, H, eps, S(stream));
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Test hooks of the row / glue kernels (tests/test_gpu_glue_ops.py): thin wrappers over the launchers the model loops call, with the arguments
+// the product entry points above do not expose (kv_start, per-row RoPE positions and cache slots, row strides, the argmax's position words).
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int omchat_op_attn_prefill_left(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Sq, int Skv, int Hq,
+                                           int Hkv, const int32_t* kv_len, const int32_t* kv_start, int causal, int q_pos0, float scale,
+                                           int fill_uniform, void* stream) {
+  OM_CHECK(q && k && v && out && kv_start, "null argument");
+  AttnArgs a{};
+  a.Q = q; a.q_sb = (int64_t)Sq * Hq * 128; a.q_sh = 128; a.q_sr = (int64_t)Hq * 128;
+  a.K = k; a.k_sb = (int64_t)Hkv * Skv * 128; a.k_sh = (int64_t)Skv * 128; a.k_sr = 128;
+  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = a.q_sb; a.o_sh = 128; a.o_sr = a.q_sr;
+  a.batch = b; a.q_heads = Hq; a.kv_heads = Hkv; a.Sq = Sq; a.Skv = Skv; a.kv_len = kv_len; a.kv_start = kv_start; a.causal = causal;
+  a.q_pos0 = q_pos0; a.scale = scale;
+  int rc = launch_attn_prefill(dtype, a, S(stream));
+  if (!rc && fill_uniform) rc = launch_attn_uniform_rows(dtype, a, S(stream));      // the order of the decoder layer (model.hip)
+  return rc;
+}
+
+// RoPE + KV append with the per-row position array and / or a cache slot that differs from the position (RopeArgs.pos / slot0): pos device int32
+// [b * S] or NULL (-> pos0 + s), slot0 = -1: the slot is the position.  The table holds max_pos positions.  Every position must be < max_pos and
+// every slot < cap: checked on the host (pos is copied back) before anything is launched.  Synchronises.
+extern "C" int omchat_op_rope_kv_pos(int dtype, void* qkv, int b, int Sq, int Hq, int Hkv, const int32_t* pos, int pos0, int slot0, int max_pos,
+                                     float theta, void* kcache, void* vcache, int cap, void* stream) {
+  OM_CHECK(qkv && kcache && vcache && b >= 1 && Sq >= 1 && Hq >= 1 && Hkv >= 1 && max_pos >= 1 && cap >= 1 && slot0 >= -1, "bad argument");
+  if (pos) {
+    std::vector<int32_t> hp((size_t)b * Sq);
+    OM_HIP(hipStreamSynchronize(S(stream)));
+    OM_HIP(hipMemcpy(hp.data(), pos, hp.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t p : hp) {
+      OM_CHECK(p >= 0 && p < max_pos, "position outside the RoPE table");
+      OM_CHECK(slot0 >= 0 || p < cap, "cache slot exceeds the capacity");
+    }
+  } else {
+    OM_CHECK(pos0 >= 0 && pos0 + Sq <= max_pos, "position outside the RoPE table");
+    OM_CHECK(slot0 >= 0 || pos0 + Sq <= cap, "cache slot exceeds the capacity");
+  }
+  OM_CHECK(slot0 < 0 || slot0 + Sq <= cap, "cache slot exceeds the capacity");
+  float* d = rope_table_device(max_pos, theta);
+  OM_CHECK(d, "rope table allocation failed");
+  RopeArgs r{qkv, (Hq + 2 * Hkv) * 128, b * Sq, Sq, Hq, Hkv, pos, pos0, d, max_pos, kcache, vcache, (int64_t)Hkv * cap * 128, (int64_t)cap * 128};
+  r.slot0 = slot0;
+  int rc = launch_rope_kv(dtype, r, S(stream));
+  hipStreamSynchronize(S(stream));
+  hipFree(d);
+  return rc;
+}
+
+// argmax over rows of stride ld >= V, with the optional position words of the decode step (adv_pos / adv_len device int32 [b] or NULL).  Synchronises.
+extern "C" int omchat_op_argmax_ld(const float* logits, int ld, int b, int V, int32_t* out, int32_t* adv_pos, int32_t* adv_len, void* stream) {
+  OM_CHECK(logits && out && b >= 1 && V >= 1 && ld >= V, "bad argument");
+  void* scratch = nullptr;
+  OM_HIP(hipMalloc(&scratch, argmax_scratch_bytes(b)));
+  int rc = launch_argmax(logits, ld, b, V, out, scratch, S(stream), adv_pos, adv_len);
+  hipStreamSynchronize(S(stream));
+  hipFree(scratch);
+  return rc;
+}
+
+extern "C" int omchat_op_im2col(int dtype, const void* pixels, void* cols, int B, int HW, int patch, int Kpad, void* stream) {
+  OM_CHECK(pixels && cols && B >= 0 && HW >= 1 && patch >= 1, "bad argument");
+  return launch_im2col(dtype, pixels, cols, B, HW, patch, Kpad, S(stream));
+}
+extern "C" int omchat_op_vit_assemble(int dtype, const void* pe, const void* cls, const void* pos, void* x, int B, int np, int C, void* stream) {
+  OM_CHECK(pe && cls && pos && x && B >= 0 && np >= 0, "bad argument");
+  return launch_vit_assemble(dtype, pe, cls, pos, x, B, np, C, S(stream));
+}
+extern "C" int omchat_op_gather_rows(int dtype, const int32_t* idx, const void* table, const void* feats, void* out, int rows, int H, void* stream) {
+  OM_CHECK(idx && out && rows >= 0, "bad argument");
+  return launch_gather_rows(dtype, idx, table, feats, out, rows, H, S(stream));
+}
+extern "C" int omchat_op_copy_rows(int dtype, const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int rows, int H, int group, int skip,
+                                   void* stream) {
+  OM_CHECK(src && dst && rows >= 0 && skip >= 0 && src_ld >= H && dst_ld >= H, "bad argument");
+  return launch_copy_rows(dtype, src, src_ld, dst, dst_ld, rows, H, group, skip, S(stream));
+}
+extern "C" int omchat_op_tp_finish(int dtype, const float* sum, const void* bias, const void* ls, const void* resid, void* out, int M, int N, int epi,
+                                   void* stream) {
+  return launch_tp_finish(dtype, sum, bias, ls, resid, out, M, N, epi, S(stream));
+}
+extern "C" int omchat_op_resid16_norm(int dtype, void* x, int ldx, const void* y, int ldy, const void* w, const void* b, void* xn, int ldn, int rows,
+                                      int H, float eps, void* stream) {
+  OM_CHECK(rows <= 0 || (x && y), "null argument");
+  return launch_resid16_norm(dtype, x, ldx, y, ldy, w, b, xn, ldn, rows, H, eps, S(stream));
+}
+extern "C" int omchat_op_cast_f32(int dtype, const void* src, float* dst, int64_t n, void* stream) {
+  OM_CHECK(n == 0 || (src && dst && n > 0), "bad argument");
+  return launch_cast_f32(dtype, src, dst, n, S(stream));
+}
+extern "C" int omchat_op_rmsnorm_ld(int dtype, const void* x, int ldx, const void* w, void* y, int ldy, int rows, int H, float eps, int pack_nb,
+                                    void* stream) {
+  OM_CHECK(x && w && y && rows >= 0 && ldx >= H && (pack_nb != 0 || ldy >= H), "bad argument");
+  return launch_rmsnorm(dtype, x, ldx, w, y, ldy, rows, H, eps, S(stream), pack_nb);
+}
+extern "C" int omchat_op_layernorm_ld(int dtype, const void* x, int ldx, const void* w, const void* b, void* y, int ldy, int rows, int H, float eps,
+                                      void* stream) {
+  OM_CHECK(x && y && rows >= 0 && ldx >= H && ldy >= H, "bad argument");
+  return launch_layernorm(dtype, x, ldx, w, b, y, ldy, rows, H, eps, S(stream));
+}

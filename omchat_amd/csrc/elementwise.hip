@@ -761,7 +761,10 @@ __global__ __launch_bounds__(256) void argmax_stage1_kernel(const float* logits,
   }
 }
 __global__ __launch_bounds__(64) void argmax_stage2_kernel(const float* pv, const int* pi, int* out, int* adv_pos, int* adv_len) {
-  if (adv_pos && threadIdx.x == 0) { adv_pos[blockIdx.x] += 1; adv_len[blockIdx.x] += 1; }
+  if (threadIdx.x == 0) {
+    if (adv_pos) adv_pos[blockIdx.x] += 1;
+    if (adv_len) adv_len[blockIdx.x] += 1;
+  }
   float best = pv[blockIdx.x * ARG_CHUNKS + threadIdx.x];
   int besti = pi[blockIdx.x * ARG_CHUNKS + threadIdx.x];
 #pragma unroll
@@ -818,6 +821,7 @@ void norm_set_wave(int v) { g_norm_wave = v; }
 int launch_layernorm(int dtype, const void* x, int ldx, const void* w, const void* b, void* y, int ldy, int rows, int H, float eps, hipStream_t s) {
   OM_CHECK(H % 8 == 0 && H <= NORM_THREADS * NORM_MAXC * 8 && ldx % 8 == 0 && ldy % 8 == 0, "H must be a multiple of 8 and <= 16384");
   OM_CHECK(w && b, "LayerNorm needs weight and bias");
+  if (rows == 0) return 0;
   DISPATCH(dtype, hipLaunchKernelGGL(layernorm_kernel<T>, dim3(rows), dim3(NORM_THREADS), 0, s, (const T*)x, ldx, (const T*)w, (const T*)b, (T*)y, ldy, H, eps));
   OM_LAUNCH_CHECK();
   return 0;
@@ -1027,7 +1031,7 @@ int launch_argmax(const float* logits, int ld, int b, int V, int* out, void* scr
   float* pv = (float*)scratch;
   int* pi = (int*)((char*)scratch + (size_t)b * ARG_CHUNKS * 4);
   hipLaunchKernelGGL(argmax_stage1_kernel, dim3(ARG_CHUNKS, b), dim3(256), 0, s, logits, ld, V, pv, pi);
-  hipLaunchKernelGGL(argmax_stage2_kernel, dim3(b), dim3(64), 0, s, pv, pi, out, adv_pos, adv_len ? adv_len : adv_pos);
+  hipLaunchKernelGGL(argmax_stage2_kernel, dim3(b), dim3(64), 0, s, pv, pi, out, adv_pos, adv_len);
   OM_LAUNCH_CHECK();
   return 0;
 }
