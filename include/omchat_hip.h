@@ -268,7 +268,7 @@ int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, int n, void*
 /* With on != 0, omchat_decode_step on a TP = 1 context (b <= 32) replays one captured graph per step instead of issuing its
  * ~230 kernel launches (same kernels, same results: tests compare bit for bit).  Captured on a context-owned stream that is
  * ordered after / before the caller's `stream` with events; re-captured when a sequence outgrows the captured split-KV grid
- * (every 1024 tokens) or the batch size / fp8 mode changes.  While profiling is enabled every 8th step runs eagerly so the
+ * (every 1024 tokens) or the batch size / fp8 / MXFP4 mode changes.  While profiling is enabled every 8th step runs eagerly so the
  * HIP-event brackets still sample the timed region.
  * Measured on ROCm 7.2 / MI355X (bench.py --graph): replay is SLOWER than the eager stream (3.21 vs 2.96 ms per token at
  * TP = 1: graph nodes are dispatched with a barrier packet each), so it is opt-in -- useful when the host, not the GPU,
@@ -284,6 +284,19 @@ int omchat_decode_graph_stats(omchat_ctx* ctx, long* steps, long* replays, long*
  * row reduction; prefill and b > 1 steps keep the 16-bit weights.  Not part of the reference (it has no quantised
  * path): parity is against the oracle run on the de-quantised weights. */
 int omchat_enable_fp8_decode(omchat_ctx* ctx, int on);
+
+/* ---- weight-only MXFP4 for decode ----------------------------------------------------------- */
+/* Builds (once) an MXFP4 replica (OCP Microscaling v1.0) of the same decode-streamed weights: per output row and per block of 32
+ * consecutive k one e8m0 scale byte, e = floor(log2(absmax)) - 2 (stored e + 127; 127 for a zero block), and e2m1 codes of w / 2^e,
+ * round to nearest, ties to the even code, saturating at 6; two codes per byte, the even k in the low nibble.  4.25 bits per weight:
+ * 3.76 GB streamed per token at Qwen2-7B width against 14.1 GB (16-bit) and 7.1 GB (e4m3).  With on != 0, batch-1 decode steps read
+ * the replica through gfx950's e2m1 -> 16-bit convert at scale 1 and apply 2^e to the lane's fp32 partial sum; prefill, b > 1 steps,
+ * the verify step and beam search keep the 16-bit weights.  After omchat_load_tensor the next step re-quantises in place.
+ * Refused: before the weights are loaded; while omchat_enable_fp8_decode is on (and the reverse: one weight format per step); on a
+ * tensor-parallel context; when a streamed K (hidden_size, heads x 128, intermediate_size) is not a multiple of 32.  The e4m3 KV cache
+ * and the fp8 x fp8 prefill GEMMs are independent of it.  Not part of the reference: parity is against the oracle run on the
+ * de-quantised weights (tests/test_gpu_mxfp4.py). */
+int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int on);
 
 /* ---- fp8 KV cache and fp8 x fp8 prefill GEMMs (BASELINE configs[4]: long video context, "fp8 MFMA weights") ------ */
 /* omchat_enable_fp8_kv: after the next prefill the decode steps read keys and values as OCP e4m3 bytes (57 344 -> 28 672 bytes per
@@ -459,6 +472,14 @@ int omchat_op_quant_rows_fp8(int dtype, const void* x, const void* norm_w, float
 int omchat_op_quant_fp8(int dtype, const void* W, int N, int K, void* W8, float* scale, void* stream);
 int omchat_op_gemv_fp8(int dtype, const void* X, const void* W8, const float* scale, void* Y, int N, int K, const void* bias,
                        const void* resid, int epi, int out_f32, int ksplit, void* stream);
+/* MXFP4 pieces (format: omchat_enable_mxfp4_decode above): W [N][K] (dtype), K % 32 == 0 -> W4 [N][K / 2] bytes + S [N][K / 32] e8m0 bytes;
+ * y[N] = epi(sum over blocks of 2^e (codes . x)), batch 1, the epilogues and ksplit of omchat_op_gemv_fp8; _norm: x is the RAW row and the
+ * RMSNorm runs in registers as in omchat_op_gemv_norm (K <= 4096, epi NONE / SWIGLU) */
+int omchat_op_quant_mxfp4(int dtype, const void* W, int N, int K, void* W4, void* S, void* stream);
+int omchat_op_gemv_mxfp4(int dtype, const void* X, const void* W4, const void* S, void* Y, int N, int K, const void* bias,
+                         const void* resid, int epi, int out_f32, int ksplit, void* stream);
+int omchat_op_gemv_mxfp4_norm(int dtype, const void* X, const void* W4, const void* S, void* Y, int N, int K, const void* norm_w, float eps,
+                              const void* bias, int epi, int out_f32, void* stream);
 int omchat_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int H, float eps, void* stream);
 /* the decode step's fused residual add + RMSNorm (modeling_qwen2.py:283-296 + 247-252): x[rows, H] = T(x + T(sum_s part[s])) in place,
  * part = fp32 split-K slices [ks][rows][H] of the projection, then xn = T(w * T(x * rsqrt(mean(x^2) + eps))) (w == NULL: skip);

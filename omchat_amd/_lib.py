@@ -99,6 +99,10 @@ _SIGS = {
     "omchat_decode_graph_stats": (_i, [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "omchat_op_quant_fp8": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_op_gemv_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "omchat_enable_mxfp4_decode": (_i, [_vp, _i]),
+    "omchat_op_quant_mxfp4": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
+    "omchat_op_gemv_mxfp4": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "omchat_op_gemv_mxfp4_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "omchat_op_rmsnorm": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "omchat_op_resid_rmsnorm": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "omchat_op_vit_qknorm": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _vp]),

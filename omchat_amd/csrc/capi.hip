@@ -625,6 +625,32 @@ extern "C" int omchat_op_gemv_fp8(int dtype, const void* X, const void* W8, cons
   return launch_gemv(dtype, g, S(stream));
 }
 
+// MXFP4 pieces (include/omchat_hip.h): W4 [N][K / 2] bytes, S [N][K / 32] e8m0 bytes
+extern "C" int omchat_op_quant_mxfp4(int dtype, const void* W, int N, int K, void* W4, void* S_, void* stream) {
+  OM_CHECK(K % 32 == 0, "MXFP4: K must be a multiple of 32 (one e8m0 scale per 32 consecutive k)");
+  return launch_quant_mxfp4_rows(dtype, W, K, N, K, W4, K / 2, (unsigned char*)S_, S(stream));
+}
+
+extern "C" int omchat_op_gemv_mxfp4(int dtype, const void* X, const void* W4, const void* S_, void* Y, int N, int K, const void* bias,
+                                    const void* resid, int epi, int out_f32, int ksplit, void* stream) {
+  OM_CHECK(X && W4 && S_ && Y, "null argument");
+  OM_CHECK(K % 32 == 0, "MXFP4: K must be a multiple of 32 (one e8m0 scale per 32 consecutive k)");
+  GemvArgs g{X, K, W4, K / 2, Y, N, 1, N, K, bias, resid, N, epi, out_f32, ksplit};
+  g.mx_scale = (const unsigned char*)S_;
+  return launch_gemv(dtype, g, S(stream));
+}
+
+// ... with the preceding RMSNorm in registers (omchat_op_gemv_norm on MXFP4 weights; K <= 4096, epilogue NONE / SWIGLU)
+extern "C" int omchat_op_gemv_mxfp4_norm(int dtype, const void* X, const void* W4, const void* S_, void* Y, int N, int K, const void* norm_w,
+                                         float eps, const void* bias, int epi, int out_f32, void* stream) {
+  OM_CHECK(X && W4 && S_ && Y && norm_w, "null argument");
+  OM_CHECK(K % 32 == 0, "MXFP4: K must be a multiple of 32 (one e8m0 scale per 32 consecutive k)");
+  GemvArgs g{X, K, W4, K / 2, Y, N, 1, N, K, bias, nullptr, 0, epi, out_f32};
+  g.norm_w = norm_w; g.norm_eps = eps;
+  g.mx_scale = (const unsigned char*)S_;
+  return launch_gemv(dtype, g, S(stream));
+}
+
 extern "C" int omchat_op_attn_prefill_d(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Sq, int Skv, int Hq,
                                         int Hkv, int D, const int32_t* kv_len, int causal, int q_pos0, float scale, void* stream) {
   AttnArgs a{};

@@ -114,6 +114,12 @@ struct omchat_ctx {
   bool pk_ready = false, pk_unavailable = false;
   void* t_lm8 = nullptr; float* t_lm8_s = nullptr;
   bool fp8_decode = false, fp8_stale = false;
+  // weight-only MXFP4 replica of the same weights (omchat_enable_mxfp4_decode): two e2m1 codes per byte [N][K / 2] + one
+  // e8m0 byte per 32 consecutive k [N][K / 32], in the op-level layout (the whole-row GEMV forms read a row's bytes contiguously already)
+  struct DecLayer4 { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; unsigned char *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr; };
+  std::vector<DecLayer4> dl4;
+  void* t_lm4 = nullptr; unsigned char* t_lm4_s = nullptr;
+  bool mxfp4_decode = false, mxfp4_stale = false;
   // BASELINE configs[4]: fp8 KV cache for decode (e4m3 bytes in the layout of the 16-bit cache + one fp32 scale per (layer, sequence,
   // kv head, position)) and fp8 x fp8 MFMA prefill GEMMs (qkv and gate|up: the activations come quantised per token from the RMSNorm)
   void *k8cache = nullptr, *v8cache = nullptr;
@@ -126,7 +132,7 @@ struct omchat_ctx {
   // buffers so that every kernel argument is replay-invariant; the split-KV attention grid is captured for `cap_len` keys
   // (empty splits exit at once) and the graph is re-captured when a sequence outgrows it.
   struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0; };
-  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 4 + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0)
+  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0)
   bool graph_on = false;
   hipStream_t graph_stream = nullptr;
   hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;

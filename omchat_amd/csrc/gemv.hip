@@ -24,10 +24,14 @@ struct GemvP {
   unsigned* dyn;                           // gemv_rows_norm_dyn_kernel: 8 pool counters + 1 completion counter (one 256-byte line each), zero before the first launch
   void* y_pack;                            // gemv_xs_kernel<EPI_RESID>: packed copy of the result rows
   unsigned long long* dbg;                 // experiments build: clock stamps (measurement of the out-of-order prototype), else null
+  const unsigned char* mx_s;               // non-null: W is MXFP4 (two e2m1 codes per byte, ldw in bytes) and mx_s [N][K / 32] holds the e8m0 block scales
 #if OMCHAT_EXPERIMENTS
   int xskew;                               // tuning key 28 < 256 (experiment): workgroups moved from every odd XCD's share to every even XCD's (gate|up non-loop form)
 #endif
 };
+// weight format of the whole-row batch-1 forms (template switch): 16-bit, OCP e4m3 bytes + one fp32 scale per row, MXFP4 (OCP Microscaling
+// v1.0: e2m1 codes, two per byte, + one e8m0 scale per 32 consecutive k)
+constexpr int WF_16 = 0, WF_E4M3 = 1, WF_MX4 = 2;
 // stamps: [0] merge end, [1] o_proj first start (stored inverted: max of ~t), [2] o_proj flags seen, [3] o_proj end, [4] gate|up first start (inverted), [5] gate|up end,
 // [6] down_proj first start (inverted), [7] down_proj end, [8] qkv first start (inverted), [9] qkv end, [10] attention first start (inverted), [11] attention end, [12] merge first start (inverted), [16 + x] gate|up end on XCD x
 #if OMCHAT_EXPERIMENTS
@@ -587,6 +591,59 @@ template <> __device__ __forceinline__ float rw_dot8_fp8<f16>(rw_u32x2 w, rw_u32
   return acc;
 }
 
+// weight-only MXFP4: 8 weights of a lane = 4 bytes, all inside one block of 32 (k = 512 c + 8 lane), so one e8m0 byte goes with them.
+// gfx950's v_cvt_scalef32_pk_{f16,bf16}_fp4 widens the two codes of a byte (low nibble first = the even k) to a packed 16-bit pair; the
+// convert runs at scale 1 (exact: every e2m1 value is representable) and the block scale 2^e multiplies the lane's fp32 partial sum --
+// folded into the convert a small 2^e underflows f16 and the result leaves the de-quantised reference.  4 converts + 4 dot2 per 8 weights,
+// as for e4m3, + one multiply-add per chunk.
+template <typename T> __device__ __forceinline__ float rw_dot8_fp4(unsigned w, rw_u32x4 x);
+template <> __device__ __forceinline__ float rw_dot8_fp4<bf16>(unsigned w, rw_u32x4 x) {
+  typedef bf16 v2 __attribute__((ext_vector_type(2)));
+  const unsigned x0 = x.x, x1 = x.y, x2 = x.z, x3 = x.w;
+  float acc = 0.f;
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 0), __builtin_bit_cast(v2, x0), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 1), __builtin_bit_cast(v2, x1), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 2), __builtin_bit_cast(v2, x2), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 3), __builtin_bit_cast(v2, x3), acc, false);
+  return acc;
+}
+template <> __device__ __forceinline__ float rw_dot8_fp4<f16>(unsigned w, rw_u32x4 x) {
+  typedef f16 v2 __attribute__((ext_vector_type(2)));
+  const unsigned x0 = x.x, x1 = x.y, x2 = x.z, x3 = x.w;
+  float acc = 0.f;
+  acc = __builtin_amdgcn_fdot2(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 0), __builtin_bit_cast(v2, x0), acc, false);
+  acc = __builtin_amdgcn_fdot2(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 1), __builtin_bit_cast(v2, x1), acc, false);
+  acc = __builtin_amdgcn_fdot2(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 2), __builtin_bit_cast(v2, x2), acc, false);
+  acc = __builtin_amdgcn_fdot2(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 3), __builtin_bit_cast(v2, x3), acc, false);
+  return acc;
+}
+// e8m0 byte -> 2^(byte - 127) (byte 0 = 2^-127 is an fp32 subnormal: ldexp, not a shift into the exponent field)
+__device__ __forceinline__ float mx_scale_of(unsigned byte) { return ldexpf(1.0f, (int)byte - 127); }
+
+// registers of a lane's 8 weights per format, their (non-temporal) load at element k of weight row `row`, and their dot product with 8 x
+template <int WF> struct RwW { typedef rw_u32x4 type; };
+template <> struct RwW<WF_E4M3> { typedef rw_u32x2 type; };
+template <> struct RwW<WF_MX4> { typedef rw_u32x2 type; };      // .x = the 8 codes, .y = the e8m0 byte of their block
+template <typename T, int WF>
+__device__ __forceinline__ typename RwW<WF>::type rw_ldw(const GemvP& p, size_t row, int k) {
+  if constexpr (WF == WF_E4M3) {
+    return __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + row * p.ldw + k));
+  } else if constexpr (WF == WF_MX4) {
+    rw_u32x2 w;
+    w.x = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>((const unsigned char*)p.W + row * p.ldw + (k >> 1)));
+    w.y = __builtin_nontemporal_load(p.mx_s + row * (size_t)(p.K >> 5) + (k >> 5));
+    return w;
+  } else {
+    return __builtin_nontemporal_load(reinterpret_cast<const rw_u32x4*>((const T*)p.W + row * p.ldw + k));
+  }
+}
+template <typename T, int WF>
+__device__ __forceinline__ float rw_dotw(typename RwW<WF>::type w, rw_u32x4 x, float acc) {
+  if constexpr (WF == WF_E4M3) return rw_dot8_fp8<T>(w, x, acc);
+  else if constexpr (WF == WF_MX4) return fmaf(rw_dot8_fp4<T>(w.x, x), mx_scale_of(w.y), acc);
+  else return rw_dot8<T>(w, x, acc);
+}
+
 // epilogue operands of a one-shot row GEMV, requested right BEHIND the weight rows (they return with them instead of costing a dependent L2
 // round trip after the reduction; in front of the weights a cold 2-byte load would hold the whole in-order queue): two 16-bit vectors
 // (bias, residual; a dummy valid pointer + index 0 when absent -- no branch around the loads)
@@ -595,39 +652,40 @@ template <typename T, int R> __device__ __forceinline__ void rw_tail_load(RwTail
 #pragma unroll
   for (int r = 0; r < R; ++r) { t.v0[r] = tof(t.p0[t.idx[r]]); t.v1[r] = tof(t.p1[t.idx[r]]); }
 }
-template <typename T, int R, int NCH>
-__device__ __forceinline__ void rw_rows_fp8(const unsigned char* W, int ldw, const int (&rows)[R], int k0, int K, int lane, const rw_u32x4 (&xr)[RW_MAXC],
-                                            const float* scale, float (&acc)[R], RwTail<T, R>& tail) {
-  rw_u32x2 w[R][NCH];
+// quantised rows (e4m3 / MXFP4) of the one-shot form
+template <typename T, int R, int NCH, int WF>
+__device__ __forceinline__ void rw_rows_q(const GemvP& p, const int (&rows)[R], int k0, int lane, const rw_u32x4 (&xr)[RW_MAXC], float (&acc)[R],
+                                          RwTail<T, R>& tail) {
+  typename RwW<WF>::type w[R][NCH];
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       int k = k0 + c * 512 + lane * 8;
-      k = k < K ? k : k0;
-      w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>(W + (size_t)rows[r] * ldw + k));
+      k = k < p.K ? k : k0;
+      w[r][c] = rw_ldw<T, WF>(p, (size_t)rows[r], k);
     }
   float sc[R];
 #pragma unroll
-  for (int r = 0; r < R; ++r) sc[r] = scale[rows[r]];
+  for (int r = 0; r < R; ++r) sc[r] = WF == WF_E4M3 ? p.w_scale[rows[r]] : 1.f;
   rw_tail_load<T, R>(tail);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     float a = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) a = rw_dot8_fp8<T>(w[r][c], xr[c], a);
+    for (int c = 0; c < NCH; ++c) a = rw_dotw<T, WF>(w[r][c], xr[c], a);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    acc[r] = a * sc[r];
+    acc[r] = WF == WF_E4M3 ? a * sc[r] : a;
   }
 }
 
-template <typename T, int R, int N>
-__device__ __forceinline__ void rw_dispatch_fp8(int nch, const unsigned char* W, int ldw, const int (&rows)[R], int k0, int K, int lane,
-                                                const rw_u32x4 (&xr)[RW_MAXC], const float* scale, float (&acc)[R], RwTail<T, R>& tail) {
+template <typename T, int R, int N, int WF>
+__device__ __forceinline__ void rw_dispatch_q(int nch, const GemvP& p, const int (&rows)[R], int k0, int lane, const rw_u32x4 (&xr)[RW_MAXC],
+                                              float (&acc)[R], RwTail<T, R>& tail) {
   if constexpr (N > 0) {
-    if (nch == N) rw_rows_fp8<T, R, N>(W, ldw, rows, k0, K, lane, xr, scale, acc, tail);
-    else rw_dispatch_fp8<T, R, N - 1>(nch, W, ldw, rows, k0, K, lane, xr, scale, acc, tail);
+    if (nch == N) rw_rows_q<T, R, N, WF>(p, rows, k0, lane, xr, acc, tail);
+    else rw_dispatch_q<T, R, N - 1, WF>(nch, p, rows, k0, lane, xr, acc, tail);
   }
 }
 
@@ -665,8 +723,8 @@ __device__ __forceinline__ void rw_dispatch(int nch, const T* W, int ldw, const 
   }
 }
 
-template <typename T, int EPI, int RR = 4, int WAVES = 4, bool F8 = false>
-__global__ __launch_bounds__(WAVES * 64) void gemv_rows_kernel(GemvP p) {
+template <typename T, int EPI, int RR, int WAVES, int F8>
+__device__ __forceinline__ void gemv_rows_body(const GemvP& p) {
   constexpr int R = EPI == EPI_SWIGLU ? 2 * RR : RR;      // SwiGLU: RR (gate, up) row pairs per group
   constexpr int OUT = RR;                                 // outputs per group
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -712,7 +770,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_kernel(GemvP p) {
       if (!hb) tail.p0 = tail.p1;      // (one of the two may be absent: read the other's element twice rather than element idx of x)
       if (!hr) tail.p1 = tail.p0;
     }
-    if constexpr (F8) rw_dispatch_fp8<T, R, RW_MAXC>(nch, (const unsigned char*)p.W, p.ldw, rows, k0, p.K, lane, xr, p.w_scale, acc, tail);
+    if constexpr (F8 != WF_16) rw_dispatch_q<T, R, RW_MAXC, F8>(nch, p, rows, k0, lane, xr, acc, tail);
     else rw_dispatch<T, R, RW_MAXC>(nch, W, p.ldw, rows, k0, p.K, lane, xr, acc, tail);
     if (lane == 0) {
 #pragma unroll
@@ -739,6 +797,13 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_kernel(GemvP p) {
   if constexpr (EPI == EPI_RESID && WAVES == 7) OM_DBG_MAX(3, (blockIdx.x & 7) == 0);
 }
 
+// the kernels of the form: 16-bit / e4m3 weights under the template switch they always had (profiles and tools/kernel_roles.py name these symbols),
+// MXFP4 as a kernel of its own over the same body
+template <typename T, int EPI, int RR = 4, int WAVES = 4, bool F8 = false>
+__global__ __launch_bounds__(WAVES * 64) void gemv_rows_kernel(GemvP p) { gemv_rows_body<T, EPI, RR, WAVES, F8 ? WF_E4M3 : WF_16>(p); }
+template <typename T, int EPI, int RR, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void gemv_rows_mx4_kernel(GemvP p) { gemv_rows_body<T, EPI, RR, WAVES, WF_MX4>(p); }
+
 // ---------------------------------------------------------------------------------------------------------
 // Whole-row GEMV with the RMSNorm that precedes the projection computed in registers (round 3; batch 1, no split-K, K = 512 NCH <= 4096):
 //   y = epi(W xn),  xn = T(w * T(x * rsqrt(mean(x^2) + eps)))      (Qwen2RMSNorm's rounding points, modeling_qwen2.py:247-252)
@@ -749,8 +814,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_kernel(GemvP p) {
 // weights were then half as many bytes through the CU as the weights).  All waves use the same sum (fixed order): the same bits.
 // It removes the residual + RMSNorm launch in front of the gate|up GEMV of a batch-1 decode step (o_proj then writes x + attn itself).
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int EPI, int RR, int NCH, bool F8, int WAVES = 4>
-__global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
+template <typename T, int EPI, int RR, int NCH, int F8, int WAVES>
+__device__ __forceinline__ void gemv_rows_norm_body(const GemvP& p) {
   typedef typename V8<T>::type v8;
   constexpr int R = EPI == EPI_SWIGLU ? 2 * RR : RR;
   __shared__ __attribute__((aligned(16))) T xs[NCH * 512];
@@ -815,7 +880,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
       rows[r] = n < p.N ? n : p.N - 1;
     }
   }
-  typedef typename std::conditional<F8, rw_u32x2, rw_u32x4>::type wreg_t;
+  typedef typename RwW<F8>::type wreg_t;
   wreg_t w[R][NCH];
 #pragma unroll
   for (int r = 0; r < R; ++r)
@@ -823,8 +888,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
     for (int c = 0; c < NCH; ++c) {
       int k = c * 512 + lane * 8;
       k = k < p.K ? k : 0;                      // ragged last chunk: clamp (x is zero there)
-      if constexpr (F8) w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + (size_t)rows[r] * p.ldw + k));
-      else w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x4*>((const T*)p.W + (size_t)rows[r] * p.ldw + k));
+      w[r][c] = rw_ldw<T, F8>(p, (size_t)rows[r], k);
     }
   // the epilogue's operands (bias, e4m3 row scales) are requested right BEHIND the weight rows: they come back with them instead of costing a
   // dependent L2 round trip after the reduction.  (In FRONT of the weights they measured slower: a cold 2-byte load at the head of the
@@ -844,7 +908,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) e_scale[r] = 1.f;
-    if constexpr (F8) {
+    if constexpr (F8 == WF_E4M3) {
 #pragma unroll
       for (int r = 0; r < R; ++r) e_scale[r] = p.w_scale[rows[r]];
     }
@@ -896,12 +960,11 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
     float a = 0.f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      if constexpr (F8) a = rw_dot8_fp8<T>(w[r][c], xr[c], a);
-      else a = rw_dot8<T>(w[r][c], xr[c], a);
+      a = rw_dotw<T, F8>(w[r][c], xr[c], a);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if constexpr (F8) a *= e_scale[r];
+    if constexpr (F8 == WF_E4M3) a *= e_scale[r];
     acc[r] = a;
   }
   if (lane == 0) {
@@ -923,6 +986,11 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
   if constexpr (EPI == EPI_NONE) OM_DBG_MAX(9, (blockIdx.x & 7) == 0);
 }
 
+template <typename T, int EPI, int RR, int NCH, bool F8, int WAVES = 4>
+__global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) { gemv_rows_norm_body<T, EPI, RR, NCH, F8 ? WF_E4M3 : WF_16, WAVES>(p); }
+template <typename T, int EPI, int RR, int NCH, int WAVES = 4>
+__global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_mx4_kernel(GemvP p) { gemv_rows_norm_body<T, EPI, RR, NCH, WF_MX4, WAVES>(p); }
+
 // ---------------------------------------------------------------------------------------------------------
 // Loop form of gemv_rows_norm_kernel (round 3): ONE resident round of workgroups (2 per CU), each owning a contiguous range of outputs
 // and every wave walking its share one output at a time (a row, or a (gate, up) pair) through a ring of three register buffers -- two
@@ -931,8 +999,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) {
 // every workgroup gets 37 outputs (waves 10 / 9 / 9 / 9) and the launch ends everywhere at once.  The norm prologue is the same and runs
 // once per workgroup.  Per output the arithmetic and its order are those of the one-shot form: the same bits.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int EPI, int NCH, bool F8>
-__global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int per_wg, unsigned skew) {
+template <typename T, int EPI, int NCH, int F8>
+__device__ __forceinline__ void gemv_rows_norm_loop_body(const GemvP& p, int per_wg, unsigned skew) {
   typedef typename V8<T>::type v8;
   constexpr int R = EPI == EPI_SWIGLU ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T xs[NCH * 512];
@@ -949,7 +1017,7 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int p
     o1 = o0 + per_wg + (int)((skew >> (4 * l)) & 15u) - 8;
     o1 = o1 < n_out ? o1 : n_out;
   }
-  typedef typename std::conditional<F8, rw_u32x2, rw_u32x4>::type wreg_t;
+  typedef typename RwW<F8>::type wreg_t;
   auto row_of = [&](int n, int r) { return EPI == EPI_SWIGLU ? 32 * (n >> 4) + (n & 15) + r * 16 : n; };
   auto load_w = [&](wreg_t (&w)[R][NCH], int n) {
 #pragma unroll
@@ -959,8 +1027,7 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int p
       for (int c = 0; c < NCH; ++c) {
         int k = c * 512 + lane * 8;
         k = k < p.K ? k : 0;                    // ragged last chunk: clamp (x is zero there)
-        if constexpr (F8) w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + row * p.ldw + k));
-        else w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x4*>((const T*)p.W + row * p.ldw + k));
+        w[r][c] = rw_ldw<T, F8>(p, row, k);
       }
     }
   };
@@ -1020,12 +1087,11 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int p
       float a = 0.f;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        if constexpr (F8) a = rw_dot8_fp8<T>(w[r][c], xr[c], a);
-        else a = rw_dot8<T>(w[r][c], xr[c], a);
+        a = rw_dotw<T, F8>(w[r][c], xr[c], a);
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-      if constexpr (F8) a *= p.w_scale[row_of(n, r)];
+      if constexpr (F8 == WF_E4M3) a *= p.w_scale[row_of(n, r)];
       acc[r] = a;
     }
     if (lane == 0) {
@@ -1057,6 +1123,15 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int p
   }
 }
 
+template <typename T, int EPI, int NCH, bool F8>
+__global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int per_wg, unsigned skew) {
+  gemv_rows_norm_loop_body<T, EPI, NCH, F8 ? WF_E4M3 : WF_16>(p, per_wg, skew);
+}
+template <typename T, int EPI, int NCH>
+__global__ __launch_bounds__(256) void gemv_rows_norm_loop_mx4_kernel(GemvP p, int per_wg, unsigned skew) {
+  gemv_rows_norm_loop_body<T, EPI, NCH, WF_MX4>(p, per_wg, skew);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Dynamic form of the loop kernel (round 4).  The loop form deals every workgroup the same number of outputs and ends when the SLOWEST
 // workgroup ends -- and the eight XCDs of this chip do not stream at the same rate: with equal shares the gate|up phase of a CU took
@@ -1073,8 +1148,8 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_loop_kernel(GemvP p, int p
 // ---------------------------------------------------------------------------------------------------------
 constexpr int DYN_CH = 2;
 constexpr int DYN_POOLS = 64;      // work counters per launch, one 256-byte line each (a counter then sees ~4 grabs per us)
-template <typename T, int EPI, int NCH, bool F8>
-__global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) {
+template <typename T, int EPI, int NCH, int F8>
+__device__ __forceinline__ void gemv_rows_norm_dyn_body(const GemvP& p) {
   typedef typename V8<T>::type v8;
   constexpr int R = EPI == EPI_SWIGLU ? 2 : 1;
   __shared__ __attribute__((aligned(16))) T xs[NCH * 512];
@@ -1082,7 +1157,7 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
   const int n_chunks = (n_out + DYN_CH - 1) / DYN_CH, pool_sz = (n_chunks + DYN_POOLS - 1) / DYN_POOLS;
-  typedef typename std::conditional<F8, rw_u32x2, rw_u32x4>::type wreg_t;
+  typedef typename RwW<F8>::type wreg_t;
   auto row_of = [&](int n, int r) { return EPI == EPI_SWIGLU ? 32 * (n >> 4) + (n & 15) + r * 16 : n; };
   auto load_w = [&](wreg_t (&w)[R][NCH], int n) {
 #pragma unroll
@@ -1092,8 +1167,7 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) {
       for (int c = 0; c < NCH; ++c) {
         int k = c * 512 + lane * 8;
         k = k < p.K ? k : 0;
-        if constexpr (F8) w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + row * p.ldw + k));
-        else w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x4*>((const T*)p.W + row * p.ldw + k));
+        w[r][c] = rw_ldw<T, F8>(p, row, k);
       }
     }
   };
@@ -1172,12 +1246,11 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) {
       float a = 0.f;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        if constexpr (F8) a = rw_dot8_fp8<T>(w[r][c], xr[c], a);
-        else a = rw_dot8<T>(w[r][c], xr[c], a);
+        a = rw_dotw<T, F8>(w[r][c], xr[c], a);
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-      if constexpr (F8) a *= p.w_scale[row_of(n, r)];
+      if constexpr (F8 == WF_E4M3) a *= p.w_scale[row_of(n, r)];
       acc[r] = a;
     }
     if (lane == 0) {
@@ -1229,6 +1302,11 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) {
   }
 }
 
+template <typename T, int EPI, int NCH, bool F8>
+__global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) { gemv_rows_norm_dyn_body<T, EPI, NCH, F8 ? WF_E4M3 : WF_16>(p); }
+template <typename T, int EPI, int NCH>
+__global__ __launch_bounds__(256) void gemv_rows_norm_dyn_mx4_kernel(GemvP p) { gemv_rows_norm_dyn_body<T, EPI, NCH, WF_MX4>(p); }
+
 // ---------------------------------------------------------------------------------------------------------
 // Whole-row GEMV for LONG K without split-K (round 3; batch 1: down_proj, K = 18944): y[n] = resid[n] + T(sum_k W[n][k] x[k]), in place.
 // The split-K form leaves fp32 slices that a residual + RMSNorm launch must sum; here a workgroup stages x (37 KB) in LDS once, every
@@ -1236,8 +1314,8 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_kernel(GemvP p) {
 // adds the residual: x + mlp is complete when the launch ends, and the NEXT projection normalises it in its own registers
 // (gemv_rows_norm_kernel).  Rows are dealt to 2 workgroups per CU, row r of a workgroup to wave r % 4.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, bool F8>
-__global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_per_wg) {
+template <typename T, int F8>
+__device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_per_wg) {
   extern __shared__ __attribute__((aligned(16))) char xs_raw[];
   T* xs = (T*)xs_raw;
   // one row per wave, rows_per_wg (<= 8) waves per workgroup: every wave of a workgroup streams the same number of bytes (7 rows per
@@ -1248,14 +1326,13 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
   const bool valid = n < p.N;
   const int row = valid ? n : p.N - 1;
   OM_DBG_MIN(6, blockIdx.x < 8);
-  typedef typename std::conditional<F8, rw_u32x2, rw_u32x4>::type wreg_t;
+  typedef typename RwW<F8>::type wreg_t;
   auto load_w = [&](wreg_t (&w)[8], int pass) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       int k = (pass * 8 + c) * 512 + lane * 8;
       k = k < p.K ? k : 0;                      // beyond K: any valid address (x is zero there)
-      if constexpr (F8) w[c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + (size_t)row * p.ldw + k));
-      else w[c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x4*>((const T*)p.W + (size_t)row * p.ldw + k));
+      w[c] = rw_ldw<T, F8>(p, (size_t)row, k);
     }
   };
   float acc = 0.f;
@@ -1263,8 +1340,7 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * 8 + c) * 512 + lane * 8);
-      if constexpr (F8) acc = rw_dot8_fp8<T>(w[c], xr, acc);
-      else acc = rw_dot8<T>(w[c], xr, acc);
+      acc = rw_dotw<T, F8>(w[c], xr, acc);
     }
   };
   wreg_t wa[8], wb[8], wc[8];
@@ -1277,7 +1353,7 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
   const float e_res_raw = tof(((const T*)(p.resid ? p.resid : p.X))[p.resid ? row : 0]);
   const float e_bias = p.bias ? e_bias_raw : 0.f, e_res = p.resid ? e_res_raw : 0.f;
   float e_scale = 1.f;
-  if constexpr (F8) e_scale = p.w_scale[row];
+  if constexpr (F8 == WF_E4M3) e_scale = p.w_scale[row];
   // x -> LDS (zero beyond K up to the last whole pass), once per workgroup, under the first passes' weight loads
   for (int i = threadIdx.x; i < npass * 8 * 64; i += blockDim.x) {
     const rw_u32x4 z = {0u, 0u, 0u, 0u};
@@ -1301,13 +1377,18 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
   float a = acc;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-  if constexpr (F8) a *= e_scale;
+  if constexpr (F8 == WF_E4M3) a *= e_scale;
   if (lane == 0 && valid) {
     const float y = rnd<T>(a + e_bias);
     ((T*)p.Y)[n] = fromf<T>(e_res + y);
   }
   OM_DBG_MAX(7, (blockIdx.x & 7) == 0);
 }
+
+template <typename T, bool F8>
+__global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, F8 ? WF_E4M3 : WF_16>(p, rows_per_wg); }
+template <typename T>
+__global__ __launch_bounds__(512) void gemv_rows_longk_mx4_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_MX4>(p, rows_per_wg); }
 
 #if OMCHAT_EXPERIMENTS
 // The same rows WITHOUT the LDS stage (round 5, tuning key 39): a wave streams one row and uses every x element once, so the LDS copy only saves L2
@@ -1316,21 +1397,20 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
 // made the one-pair-per-wave gate|up launch faster).  Same chunk order and the same dot products as the LDS form: bit-identical.
 // MEASURED SLOWER (same box, configs[1] decode ms per token): LDS form 2.605; this form as 1 / 2 / 4 waves per workgroup 2.700 / 2.707 / 2.712 -- the
 // x registers halve the waves per SIMD (204 VGPRs) and 3584 rows no longer fit one resident round.  Experiments build only.
-template <typename T, bool F8>
-__global__ __launch_bounds__(256) void gemv_rows_longk_direct_kernel(GemvP p) {
+template <typename T, int F8>
+__device__ __forceinline__ void gemv_rows_longk_direct_body(const GemvP& p) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nch = (p.K + 511) >> 9, npass = (nch + 7) >> 3;
   const int n = blockIdx.x * (int)(blockDim.x >> 6) + wave;
   if (n >= p.N) return;
   const int row = n;
-  typedef typename std::conditional<F8, rw_u32x2, rw_u32x4>::type wreg_t;
+  typedef typename RwW<F8>::type wreg_t;
   auto load_w = [&](wreg_t (&w)[8], int pass) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       int k = (pass * 8 + c) * 512 + lane * 8;
       k = k < p.K ? k : 0;
-      if constexpr (F8) w[c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + (size_t)row * p.ldw + k));
-      else w[c] = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x4*>((const T*)p.W + (size_t)row * p.ldw + k));
+      w[c] = rw_ldw<T, F8>(p, (size_t)row, k);
     }
   };
   auto load_x = [&](rw_u32x4 (&x)[8], int pass) {
@@ -1345,8 +1425,7 @@ __global__ __launch_bounds__(256) void gemv_rows_longk_direct_kernel(GemvP p) {
   auto dots = [&](wreg_t (&w)[8], rw_u32x4 (&x)[8]) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      if constexpr (F8) acc = rw_dot8_fp8<T>(w[c], x[c], acc);
-      else acc = rw_dot8<T>(w[c], x[c], acc);
+      acc = rw_dotw<T, F8>(w[c], x[c], acc);
     }
   };
   wreg_t wa[8], wb[8];
@@ -1358,7 +1437,7 @@ __global__ __launch_bounds__(256) void gemv_rows_longk_direct_kernel(GemvP p) {
   const float e_res_raw = tof(((const T*)(p.resid ? p.resid : p.X))[p.resid ? row : 0]);
   const float e_bias = p.bias ? e_bias_raw : 0.f, e_res = p.resid ? e_res_raw : 0.f;
   float e_scale = 1.f;
-  if constexpr (F8) e_scale = p.w_scale[row];
+  if constexpr (F8 == WF_E4M3) e_scale = p.w_scale[row];
   // two passes of weights and x in flight per wave (128 registers: three to four waves per SIMD); a buffer pair is refilled right after its dot products
   for (int ps = 0; ps < npass; ps += 2) {
     dots(wa, xa);
@@ -1371,12 +1450,17 @@ __global__ __launch_bounds__(256) void gemv_rows_longk_direct_kernel(GemvP p) {
   float a = acc;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-  if constexpr (F8) a *= e_scale;
+  if constexpr (F8 == WF_E4M3) a *= e_scale;
   if (lane == 0) {
     const float y = rnd<T>(a + e_bias);
     ((T*)p.Y)[n] = fromf<T>(e_res + y);
   }
 }
+
+template <typename T, bool F8>
+__global__ __launch_bounds__(256) void gemv_rows_longk_direct_kernel(GemvP p) { gemv_rows_longk_direct_body<T, F8 ? WF_E4M3 : WF_16>(p); }
+template <typename T>
+__global__ __launch_bounds__(256) void gemv_rows_longk_direct_mx4_kernel(GemvP p) { gemv_rows_longk_direct_body<T, WF_MX4>(p); }
 
 #endif
 int g_gemv_longk_direct = 0;   // omchat_op_set_tuning key 39 (experiments build): waves per workgroup (1, 2, 4) of the no-LDS long-K form; 0 = x through LDS (gemv_rows_longk_kernel)
@@ -1386,7 +1470,8 @@ int launch_rows_longk(const GemvP& p, hipStream_t s) {
 #if OMCHAT_EXPERIMENTS
   if (g_gemv_longk_direct > 0) {
     const int wpw = g_gemv_longk_direct > 4 ? 4 : g_gemv_longk_direct;
-    if (p.w_scale) hipLaunchKernelGGL((gemv_rows_longk_direct_kernel<T, true>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
+    if (p.mx_s) hipLaunchKernelGGL((gemv_rows_longk_direct_mx4_kernel<T>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
+    else if (p.w_scale) hipLaunchKernelGGL((gemv_rows_longk_direct_kernel<T, true>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
     else hipLaunchKernelGGL((gemv_rows_longk_direct_kernel<T, false>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
     return 0;
   }
@@ -1397,7 +1482,12 @@ int launch_rows_longk(const GemvP& p, hipStream_t s) {
   const int grid = cdiv(p.N, rpw);
   const int npass = (cdiv(p.K, 512) + 7) / 8;
   const size_t lds = (size_t)npass * 8 * 512 * 2;
-  if (p.w_scale) {
+  if (p.mx_s) {
+    static PerDeviceOnce set;
+    auto k = gemv_rows_longk_mx4_kernel<T>;
+    if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * rpw), lds, s, p, rpw);
+  } else if (p.w_scale) {
     auto k = gemv_rows_longk_kernel<T, true>;
     static PerDeviceOnce set;
     if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
@@ -1423,24 +1513,26 @@ int g_gemv_gu_rr = 1;
 int g_gemv_gu_rr8 = 1;          // the same for the e4m3 replica (key 38, value x 16): 1.700 -> 1.678 -> 1.658 ms per token at 4 / 2 / 1 pairs per wave
 int g_gemv_norm_loop = 0;      // omchat_op_set_tuning key 16: loop form (gemv_rows_norm_loop_kernel) of a batch-1 step's bit 0 = gate|up, 1 = qkv, 2 = e4m3 gate|up, 3 = lm_head
 
-template <typename T, int EPI, int RR, bool F8, int NCH>
+template <typename T, int EPI, int RR, int F8, int NCH>
 void launch_rows_norm_n(const GemvP& p, hipStream_t s) {
   const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
   if constexpr (NCH >= 4) {        // the decoder's hidden sizes only (K > 1536): keeps the instantiation count down
     // measured (profiles/r03_p): gate|up 44.3 -> 42.8 us (2.778 -> 2.738 ms per token); qkv 9.2 us either way; e4m3 gate|up 0.6 % slower
-    const bool want = EPI == EPI_SWIGLU ? (g_gemv_norm_loop & (F8 ? 4 : 1)) : (p.N < 32768 ? (g_gemv_norm_loop & 2) : (g_gemv_norm_loop & 8));
+    const bool want = EPI == EPI_SWIGLU ? (g_gemv_norm_loop & (F8 != WF_16 ? 4 : 1)) : (p.N < 32768 ? (g_gemv_norm_loop & 2) : (g_gemv_norm_loop & 8));
     const int n_cu = device_cus();
     // dynamic form: the outputs dealt by atomic counters instead of equal shares (the XCDs do not stream at the same rate); tuning key 24
 #if OMCHAT_EXPERIMENTS
     if (want && p.dyn && g_gemv_dyn && n_out >= 8 * n_cu) {
-      hipLaunchKernelGGL((gemv_rows_norm_dyn_kernel<T, EPI, NCH, F8>), dim3(2 * n_cu), dim3(256), 0, s, p);
+      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_dyn_mx4_kernel<T, EPI, NCH>), dim3(2 * n_cu), dim3(256), 0, s, p);
+      else hipLaunchKernelGGL((gemv_rows_norm_dyn_kernel<T, EPI, NCH, F8 == WF_E4M3>), dim3(2 * n_cu), dim3(256), 0, s, p);
       return;
     }
 #endif
     if (want && n_out >= 8 * n_cu) {
       const int per = cdiv(n_out, 2 * n_cu);
       const unsigned skew = (g_gemv_skew >= 256u && n_out == per * 2 * n_cu && (2 * n_cu) % 8 == 0) ? g_gemv_skew : 0u;
-      hipLaunchKernelGGL((gemv_rows_norm_loop_kernel<T, EPI, NCH, F8>), dim3(cdiv(n_out, per)), dim3(256), 0, s, p, per, skew);
+      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_loop_mx4_kernel<T, EPI, NCH>), dim3(cdiv(n_out, per)), dim3(256), 0, s, p, per, skew);
+      else hipLaunchKernelGGL((gemv_rows_norm_loop_kernel<T, EPI, NCH, F8 == WF_E4M3>), dim3(cdiv(n_out, per)), dim3(256), 0, s, p, per, skew);
       return;
     }
   }
@@ -1449,7 +1541,8 @@ void launch_rows_norm_n(const GemvP& p, hipStream_t s) {
     // instead of 576 workgroups of 8 rows on 4 waves (2.25 per CU)
     const int n_cu = device_cus();
     if (g_gemv_rows_balance && n_out == 9 * 2 * n_cu) {
-      hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, 1, NCH, F8, 9>), dim3(2 * n_cu), dim3(576), 0, s, p);
+      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_mx4_kernel<T, EPI, 1, NCH, 9>), dim3(2 * n_cu), dim3(576), 0, s, p);
+      else hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, 1, NCH, F8 == WF_E4M3, 9>), dim3(2 * n_cu), dim3(576), 0, s, p);
       return;
     }
   }
@@ -1460,14 +1553,16 @@ void launch_rows_norm_n(const GemvP& p, hipStream_t s) {
     const int nwg = cdiv(n_out, 4), xs = (int)(g_gemv_skew < 256u ? g_gemv_skew : 0u);
     if (xs > 0 && nwg % 8 == 0 && n_out % 4 == 0 && xs < nwg / 8) {
       GemvP q = p; q.xskew = xs;
-      hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, RR, NCH, F8>), dim3(8 * (nwg / 8 + xs)), dim3(256), 0, s, q);
+      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_mx4_kernel<T, EPI, RR, NCH>), dim3(8 * (nwg / 8 + xs)), dim3(256), 0, s, q);
+      else hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, RR, NCH, F8 == WF_E4M3>), dim3(8 * (nwg / 8 + xs)), dim3(256), 0, s, q);
       return;
     }
   }
 #endif
-  hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, RR, NCH, F8>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
+  if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_mx4_kernel<T, EPI, RR, NCH>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, RR, NCH, F8 == WF_E4M3>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
 }
-template <typename T, int EPI, int RR, bool F8>
+template <typename T, int EPI, int RR, int F8>
 void launch_rows_norm(const GemvP& p, hipStream_t s) {
   switch (cdiv(p.K, 512)) {
     case 1: launch_rows_norm_n<T, EPI, RR, F8, 1>(p, s); break;
@@ -1481,7 +1576,7 @@ void launch_rows_norm(const GemvP& p, hipStream_t s) {
   }
 }
 
-template <typename T, int EPI, int RR, bool F8>
+template <typename T, int EPI, int RR, int F8>
 void launch_rows_r(const GemvP& p, hipStream_t s) {
   const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
   if constexpr (RR == 1 && EPI == EPI_RESID) {
@@ -1489,49 +1584,54 @@ void launch_rows_r(const GemvP& p, hipStream_t s) {
     // 512 seven-wave workgroups every CU streams the same 14 rows (profiles/r03_r)
     const int n_cu = device_cus();
     if (g_gemv_rows_balance && p.ksplit == 1 && n_out == 7 * 2 * n_cu) {
-      hipLaunchKernelGGL((gemv_rows_kernel<T, EPI, 1, 7, F8>), dim3(2 * n_cu, 1), dim3(448), 0, s, p);
+      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_mx4_kernel<T, EPI, 1, 7>), dim3(2 * n_cu, 1), dim3(448), 0, s, p);
+      else hipLaunchKernelGGL((gemv_rows_kernel<T, EPI, 1, 7, F8 == WF_E4M3>), dim3(2 * n_cu, 1), dim3(448), 0, s, p);
       return;
     }
   }
   int grid = cdiv(cdiv(n_out, RR), 4);
   grid = grid > 2048 ? 2048 : grid;
-  hipLaunchKernelGGL((gemv_rows_kernel<T, EPI, RR, 4, F8>), dim3(grid, p.ksplit), dim3(256), 0, s, p);
+  if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_mx4_kernel<T, EPI, RR, 4>), dim3(grid, p.ksplit), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((gemv_rows_kernel<T, EPI, RR, 4, F8 == WF_E4M3>), dim3(grid, p.ksplit), dim3(256), 0, s, p);
 }
 // rows per wave-group from tools/experiments/tune_rows.hip (MI355X, r01): short outputs (fused qkv) are latency-bound and want the most
 // waves (R = 1: 7.8 vs 8.8 us), everything else is flat in R; 4 waves per workgroup beat 8.  fp8 rows are half as many
 // bytes: the wide lm_head takes 8 rows per group, the split-K shapes measured flat (o_proj slightly worse) and keep 4.
-template <typename T, int EPI>
-void launch_rows(const GemvP& p, hipStream_t s) {
-  if (p.w_scale) {
-    if constexpr (EPI == EPI_SWIGLU || EPI == EPI_NONE) {
-      if (p.norm_w) {
-        if (EPI == EPI_NONE && p.N < 32768) launch_rows_norm<T, EPI, 2, true>(p, s);
-        else if (EPI == EPI_SWIGLU && g_gemv_gu_rr8 == 2) launch_rows_norm<T, EPI, 2, true>(p, s);
-        else if (EPI == EPI_SWIGLU && g_gemv_gu_rr8 == 1) launch_rows_norm<T, EPI, 1, true>(p, s);
-        else launch_rows_norm<T, EPI, 4, true>(p, s);
-        return;
-      }
-    }
-    if ((EPI == EPI_NONE || EPI == EPI_RESID) && p.N < 32768) launch_rows_r<T, EPI, 1, true>(p, s);
-    else if (EPI == EPI_NONE) launch_rows_r<T, EPI, 8, true>(p, s);      // lm_head: 80.7 vs 82.3 us
-    else launch_rows_r<T, EPI, 4, true>(p, s);
-    return;
-  }
+// quantised weights (e4m3 rows are half as many bytes as 16-bit ones, MXFP4 a quarter): the same launch shapes for both
+template <typename T, int EPI, int WF>
+void launch_rows_q(const GemvP& p, hipStream_t s) {
   if constexpr (EPI == EPI_SWIGLU || EPI == EPI_NONE) {
-    if (p.norm_w) {          // the norm shared through LDS; 3 (gate, up) pairs per wave: 6 x 7 chunks of weights + the row fit 256 VGPRs
-      if (EPI == EPI_NONE && p.N < 32768) launch_rows_norm<T, EPI, 2, false>(p, s);      // qkv: 8 rows (56 KB) per workgroup against 14 KB of x + norm weights
-      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr == 2) launch_rows_norm<T, EPI, 2, false>(p, s);
-      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr == 3) launch_rows_norm<T, EPI, 3, false>(p, s);
-      else if (EPI == EPI_SWIGLU) launch_rows_norm<T, EPI, 1, false>(p, s);
-      else launch_rows_norm<T, EPI, 4, false>(p, s);
+    if (p.norm_w) {
+      if (EPI == EPI_NONE && p.N < 32768) launch_rows_norm<T, EPI, 2, WF>(p, s);
+      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr8 == 2) launch_rows_norm<T, EPI, 2, WF>(p, s);
+      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr8 == 1) launch_rows_norm<T, EPI, 1, WF>(p, s);
+      else launch_rows_norm<T, EPI, 4, WF>(p, s);
       return;
     }
   }
-  if ((EPI == EPI_NONE || EPI == EPI_RESID) && p.N < 32768) launch_rows_r<T, EPI, 1, false>(p, s);      // short outputs: one row per wave (latency-bound)
+  if ((EPI == EPI_NONE || EPI == EPI_RESID) && p.N < 32768) launch_rows_r<T, EPI, 1, WF>(p, s);
+  else if (EPI == EPI_NONE) launch_rows_r<T, EPI, 8, WF>(p, s);      // lm_head: 80.7 vs 82.3 us
+  else launch_rows_r<T, EPI, 4, WF>(p, s);
+}
+template <typename T, int EPI>
+void launch_rows(const GemvP& p, hipStream_t s) {
+  if (p.mx_s) { launch_rows_q<T, EPI, WF_MX4>(p, s); return; }
+  if (p.w_scale) { launch_rows_q<T, EPI, WF_E4M3>(p, s); return; }
+  if constexpr (EPI == EPI_SWIGLU || EPI == EPI_NONE) {
+    if (p.norm_w) {          // the norm shared through LDS; 3 (gate, up) pairs per wave: 6 x 7 chunks of weights + the row fit 256 VGPRs
+      if (EPI == EPI_NONE && p.N < 32768) launch_rows_norm<T, EPI, 2, WF_16>(p, s);      // qkv: 8 rows (56 KB) per workgroup against 14 KB of x + norm weights
+      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr == 2) launch_rows_norm<T, EPI, 2, WF_16>(p, s);
+      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr == 3) launch_rows_norm<T, EPI, 3, WF_16>(p, s);
+      else if (EPI == EPI_SWIGLU) launch_rows_norm<T, EPI, 1, WF_16>(p, s);
+      else launch_rows_norm<T, EPI, 4, WF_16>(p, s);
+      return;
+    }
+  }
+  if ((EPI == EPI_NONE || EPI == EPI_RESID) && p.N < 32768) launch_rows_r<T, EPI, 1, WF_16>(p, s);      // short outputs: one row per wave (latency-bound)
   // a tensor-parallel rank's gate|up shard (2368 pairs at TP = 8): 4 pairs per wave are 148 workgroups on 256 CUs; one pair per wave
   // gives every CU ~9 waves (round 5)
-  else if (EPI == EPI_SWIGLU && (g_gemv_shard & 4) && p.N / 2 < 16 * device_cus()) launch_rows_r<T, EPI, 1, false>(p, s);
-  else launch_rows_r<T, EPI, 4, false>(p, s);
+  else if (EPI == EPI_SWIGLU && (g_gemv_shard & 4) && p.N / 2 < 16 * device_cus()) launch_rows_r<T, EPI, 1, WF_16>(p, s);
+  else launch_rows_r<T, EPI, 4, WF_16>(p, s);
 }
 
 // Launch shapes measured with tools/experiments/tune_gemv.hip on MI355X (r01): plain loads beat non-temporal ones for this access
@@ -1540,7 +1640,7 @@ template <typename T>
 int launch_t(const GemvArgs& a, hipStream_t s) {
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
   GemvP p{a.X, a.W, a.Y, a.bias, a.resid, a.ldx, a.ldw, a.ldy, a.ldr, a.b, a.N, a.K, a.out_f32, ks, a.w_scale, a.y_packed, a.norm_w, a.norm_eps,
-          (unsigned*)a.dyn_ctr, a.y_pack, a.dbg};
+          (unsigned*)a.dyn_ctr, a.y_pack, a.dbg, a.mx_scale};
   if (a.norm_w && a.x_packed && !(a.w_packed && ks == 1 && (a.K >> 6) == 56 && a.epi == EPI_SWIGLU && a.N % 32 == 0 && !g_gemv_no_xs)) {
     omchat_set_error("launch_gemv: the in-register RMSNorm on packed x exists for the x-stationary gate|up form only (packed W, K = 3584, no split-K)");
     return 1;
@@ -1637,7 +1737,7 @@ int launch_t(const GemvArgs& a, hipStream_t s) {
     return 0;
   }
   if (a.b == 1 && !a.x_packed && a.epi == EPI_RESID && ks == 1 && !a.out_f32 && a.K > RW_MAXC * 512 && a.K % 8 == 0 && a.K <= 32768 &&
-      !a.force_mfma && !g_gemv_force_mfma) {
+      ((!a.force_mfma && !g_gemv_force_mfma) || a.mx_scale)) {
     const int rc = launch_rows_longk<T>(p, s);      // long K in one piece: x through LDS, the result complete when the launch ends
     if (rc) return rc;
     OM_LAUNCH_CHECK();
@@ -1648,8 +1748,8 @@ int launch_t(const GemvArgs& a, hipStream_t s) {
     omchat_set_error("launch_gemv: the in-register RMSNorm needs the whole-row batch-1 form without split-K (K <= 4096), epilogue NONE / SWIGLU");
     return 1;
   }
-  if (a.w_scale && !rows_ok) { omchat_set_error("launch_gemv: fp8 weights need b == 1 and <= 8 chunks of 512 per K slice"); return 1; }
-  if (rows_ok && (a.w_scale || (!a.force_mfma && !g_gemv_force_mfma))) {       // whole-row streaming form
+  if ((a.w_scale || a.mx_scale) && !rows_ok) { omchat_set_error("launch_gemv: fp8 / MXFP4 weights need b == 1 and <= 8 chunks of 512 per K slice"); return 1; }
+  if (rows_ok && (a.w_scale || a.mx_scale || (!a.force_mfma && !g_gemv_force_mfma))) {       // whole-row streaming form
     switch (a.epi) {
       case EPI_PARTIAL: launch_rows<T, EPI_PARTIAL>(p, s); break;
       case EPI_SWIGLU: launch_rows<T, EPI_SWIGLU>(p, s); break;
@@ -1740,6 +1840,55 @@ int launch_quant_fp8_rows(int dtype, const void* W, int ldw, int N, int K, void*
   if (dtype == OMCHAT_F16) hipLaunchKernelGGL(quant_fp8_rows_kernel<f16>, dim3(cdiv(N, 4)), dim3(256), 0, s, (const f16*)W, ldw, N, K, (unsigned char*)W8, ld8, scale);
   else if (dtype == OMCHAT_BF16) hipLaunchKernelGGL(quant_fp8_rows_kernel<bf16>, dim3(cdiv(N, 4)), dim3(256), 0, s, (const bf16*)W, ldw, N, K, (unsigned char*)W8, ld8, scale);
   else { omchat_set_error("launch_quant_fp8_rows: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+namespace {
+// MXFP4 quantiser (kernels.h: launch_quant_mxfp4_rows).  One wave per row, 8 weights per lane per step: the four lanes of a block of 32 share
+// the absmax.  The exponent comes from the bits of the fp32 absmax (no log2f): floor(log2(m)) = exponent field - 127 for a normal m; a
+// subnormal m lies below 2^-126, where e clamps to -127 anyway.  w / 2^e is exact (a power of two), and the code is the count of rounding
+// thresholds below |w| / 2^e -- the midpoints of {0, .5, 1, 1.5, 2, 3, 4, 6}, each tie going to the even code -- so 7 and above saturate at 6.
+template <typename T>
+__global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const T* __restrict__ W, int ldw, int N, int K, unsigned char* __restrict__ W4, int ld4,
+                                                               unsigned char* __restrict__ S) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const T* w = W + (size_t)n * ldw;
+  for (int k = lane * 8; k < K; k += 512) {      // K % 32 == 0: the four lanes of a block are in the loop together
+    const typename V8<T>::type v = ld8<T>(w + k);
+    float f[8], m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { f[j] = tof(v[j]); m = fmaxf(m, fabsf(f[j])); }
+    m = fmaxf(m, __shfl_xor(m, 1, 64));
+    m = fmaxf(m, __shfl_xor(m, 2, 64));
+    const int field = (int)((__float_as_uint(m) >> 23) & 0xffu);
+    int e = field - 127 - 2;
+    e = e < -127 ? -127 : e;
+    if (m == 0.f) e = 0;
+    const float inv = ldexpf(1.0f, -e);           // 2^-e, e in [-127, 125]: a normal fp32
+    unsigned codes = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float a = fabsf(f[j]) * inv;
+      const unsigned c = (unsigned)(a > 0.25f) + (unsigned)(a >= 0.75f) + (unsigned)(a > 1.25f) + (unsigned)(a >= 1.75f) + (unsigned)(a > 2.5f) +
+                         (unsigned)(a >= 3.5f) + (unsigned)(a > 5.0f);
+      const unsigned sgn = (c != 0u && f[j] < 0.f) ? 8u : 0u;
+      codes |= (c | sgn) << (4 * j);
+    }
+    *reinterpret_cast<unsigned*>(W4 + (size_t)n * ld4 + (k >> 1)) = codes;
+    if ((lane & 3) == 0) S[(size_t)n * (K >> 5) + (k >> 5)] = (unsigned char)(e + 127);
+  }
+}
+}  // namespace
+
+int launch_quant_mxfp4_rows(int dtype, const void* W, int ldw, int N, int K, void* W4, int ld4, unsigned char* S, hipStream_t s) {
+  OM_CHECK(W && W4 && S, "null argument");
+  OM_CHECK(N >= 1 && K >= 32 && K % 32 == 0, "MXFP4: K must be a multiple of 32 (one e8m0 scale per 32 consecutive k)");
+  OM_CHECK(ldw % 8 == 0 && ld4 % 4 == 0 && ld4 >= K / 2, "ldw % 8, ld4 (bytes) % 4 and >= K / 2");
+  if (dtype == OMCHAT_F16) hipLaunchKernelGGL(quant_mxfp4_rows_kernel<f16>, dim3(cdiv(N, 4)), dim3(256), 0, s, (const f16*)W, ldw, N, K, (unsigned char*)W4, ld4, S);
+  else if (dtype == OMCHAT_BF16) hipLaunchKernelGGL(quant_mxfp4_rows_kernel<bf16>, dim3(cdiv(N, 4)), dim3(256), 0, s, (const bf16*)W, ldw, N, K, (unsigned char*)W4, ld4, S);
+  else { omchat_set_error("launch_quant_mxfp4_rows: bad dtype"); return 1; }
   OM_LAUNCH_CHECK();
   return 0;
 }
@@ -1844,14 +1993,16 @@ int launch_gemv_wait(int dtype, const GemvArgs& a, const unsigned* flags, unsign
 
 int launch_gemv(int dtype, const GemvArgs& a, hipStream_t s) {
   OM_CHECK(a.b >= 1 && a.b <= 32, "batch must be 1..32 per call");
-  OM_CHECK(!a.x_packed || !a.w_scale, "packed x: 16-bit weights");      // (EPI_RESID: x-stationary form only, checked in launch_t)
+  OM_CHECK(!a.x_packed || (!a.w_scale && !a.mx_scale), "packed x: 16-bit weights");
+  OM_CHECK(!(a.w_scale && a.mx_scale), "one weight format per launch: e4m3 (w_scale) or MXFP4 (mx_scale)");      // (EPI_RESID: x-stationary form only, checked in launch_t)
   OM_CHECK(!a.w_packed || (a.x_packed && a.N % 16 == 0), "packed W needs packed x and N % 16 == 0");
   OM_CHECK(!a.y_packed || (a.x_packed && a.epi == EPI_SWIGLU), "packed y: SwiGLU epilogue of the packed kernel only");
-  OM_CHECK(a.K % 64 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0, "K % 64, ldw % 8, ldx % 8");
-  OM_CHECK(!a.w_scale || a.b == 1, "fp8 weights: batch 1 only");
+  if (a.mx_scale) OM_CHECK(a.K % 32 == 0 && a.ldw % 4 == 0 && a.ldx % 8 == 0, "MXFP4 weights: K % 32 == 0 (one e8m0 scale per 32 k), ldw (bytes) % 4, ldx % 8");
+  else OM_CHECK(a.K % 64 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0, "K % 64, ldw % 8, ldx % 8");
+  OM_CHECK((!a.w_scale && !a.mx_scale) || a.b == 1, "fp8 / MXFP4 weights: batch 1 only");
   OM_CHECK(a.epi == EPI_NONE || a.epi == EPI_RESID || a.epi == EPI_SWIGLU || a.epi == EPI_PARTIAL, "bad epilogue");
   OM_CHECK(a.ksplit <= 1 || a.epi == EPI_PARTIAL, "ksplit > 1 only with EPI_PARTIAL (fp32 slices)");
-  OM_CHECK(a.ksplit <= a.K / 64, "ksplit exceeds the number of 64-wide K chunks");
+  OM_CHECK(a.ksplit <= (a.K + 63) / 64, "ksplit exceeds the number of 64-wide K chunks");
   OM_CHECK(a.epi != EPI_RESID || a.resid, "resid missing");
   OM_CHECK(a.epi != EPI_SWIGLU || a.N % 32 == 0, "SwiGLU needs N % 32 == 0");
   OM_CHECK(!(a.out_f32 && a.epi != EPI_NONE), "fp32 output only with EPI_NONE");

@@ -113,6 +113,9 @@ struct GemvArgs {
   void* y_pack = nullptr;
   // experiments build, measurement only: 8 x 64-bit clock stamps of this launch's layer (see model.hip dbg_stamps)
   unsigned long long* dbg = nullptr;
+  // non-null: W is MXFP4 -- [N][ldw] bytes (ldw >= K / 2) of two OCP e2m1 codes each, the even k in the low nibble -- and mx_scale [N][K / 32]
+  // holds one e8m0 byte per 32 consecutive k (weight-only, b == 1 only, K % 32 == 0); not together with w_scale
+  const unsigned char* mx_scale = nullptr;
 };
 // row-major [rows <= 32][K] -> packed x (tests, tools); row-major W [N][ldw] -> packed replica (N % 16 == 0)
 int launch_pack_x(int dtype, const void* X, int ldx, int b, int K, void* out, hipStream_t s);
@@ -123,6 +126,10 @@ int launch_gemv_wait(int dtype, const GemvArgs& a, const unsigned* flags, unsign
 // per-row (output channel) symmetric quantisation of W [N][ldw] (T) to OCP e4m3: scale[n] = absmax_n / 448 (1 if the row is 0),
 // W8[n][k] = e4m3_rne(W[n][k] / scale[n])
 int launch_quant_fp8_rows(int dtype, const void* W, int ldw, int N, int K, void* W8, int ld8, float* scale, hipStream_t stream);
+// MXFP4 (OCP Microscaling v1.0) of W [N][ldw] (T), K % 32 == 0: per row and block of 32 k, e = floor(log2(absmax)) - 2 clamped to [-127, 127],
+// S[n][k / 32] = e + 127 (127 for a zero block), codes = e2m1 round-to-nearest (ties to the even code, saturating at 6) of w / 2^e, sign in
+// bit 3 (never on a zero code); W4 [N][ld4] bytes, the even k in the low nibble
+int launch_quant_mxfp4_rows(int dtype, const void* W, int ldw, int N, int K, void* W4, int ld4, unsigned char* S, hipStream_t stream);
 void gemv_set_force_mfma(int v);
 int gemv_get_force_mfma();
 void gemm_set_autotune(int v);

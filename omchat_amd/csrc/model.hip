@@ -350,6 +350,7 @@ extern "C" int omchat_load_tensor(omchat_ctx* ctx, const char* name, const void*
     OM_CHECK(split_ok, std::string("shape mismatch for ") + name + ": expected [" + std::to_string(r.rows) + ", " + std::to_string(r.cols) + "]");
   }
   if (!ctx->dl8.empty()) ctx->fp8_stale = true;      // the e4m3 replica no longer matches the 16-bit weights
+  if (!ctx->dl4.empty()) ctx->mxfp4_stale = true;    // nor does the MXFP4 replica
   ctx->pk_ready = false;                              // nor does the packed replica
   if (src_dtype == ctx->dt) return place(ctx, r, data);
   OM_CHECK(src_dtype == OMCHAT_F32, "source dtype must be the context dtype or OMCHAT_F32");
@@ -893,12 +894,13 @@ extern "C" int omchat_splice_gather(omchat_ctx* ctx, const int32_t* src_index, c
 // ---------------------------------------------------------------------------------------------------------
 // decoder
 // ---------------------------------------------------------------------------------------------------------
-static int lm_head_rows(omchat_ctx* ctx, const void* hidden, int n, float* logits, hipStream_t s, bool fp8 = false, bool packed = false) {
+static int lm_head_rows(omchat_ctx* ctx, const void* hidden, int n, float* logits, hipStream_t s, bool fp8 = false, bool packed = false, bool mx4 = false) {
   const int H = ctx->c.t_hidden, V = ctx->c.t_vocab;
   for (int r0 = 0; r0 < n; r0 += 32) {
     const int R = std::min(32, n - r0);
     GemvArgs g{(const char*)hidden + (size_t)r0 * H * 2, H, ctx->t_lm, H, logits + (size_t)r0 * V, V, R, V, H, nullptr, nullptr, 0, EPI_NONE, 1};
     if (fp8 && n == 1) { g.W = ctx->t_lm8; g.w_scale = ctx->t_lm8_s; }
+    if (mx4 && n == 1) { g.W = ctx->t_lm4; g.ldw = H / 2; g.mx_scale = ctx->t_lm4_s; }
     if (packed) {          // hidden is in the packed x layout (n <= 32)
       g.x_packed = 1;
       if (ctx->pk_ready) { g.W = ctx->t_lmP; g.w_packed = 1; }
@@ -939,8 +941,50 @@ extern "C" int omchat_enable_fp8_decode(omchat_ctx* ctx, int on) {
   OM_CHECK(ctx, "null context");
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
   if (!on) { ctx->fp8_decode = false; return 0; }
+  OM_CHECK(!ctx->mxfp4_decode, "MXFP4 decode is on: one weight format per step (omchat_enable_mxfp4_decode(ctx, 0) first)");
   TRY(ensure_fp8_weights(ctx));
   ctx->fp8_decode = true;
+  return 0;
+}
+
+// MXFP4 replica of the decode-streamed weights: built once, re-quantised in place (same device pointers: a captured graph stays valid) after
+// omchat_load_tensor
+static int ensure_mxfp4_weights(omchat_ctx* ctx) {
+  const omchat_config& c = ctx->c;
+  if (ctx->dl4.empty() || ctx->mxfp4_stale) {
+    OM_CHECK(omchat_weights_missing(ctx) == 0, "load the weights before quantising them");
+    const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
+    OM_CHECK(H % 32 == 0 && qd % 32 == 0 && It % 32 == 0, "MXFP4 decode: every streamed K (hidden_size, heads x 128, intermediate_size) must be a multiple of 32");
+    ctx->dl4.resize(c.t_layers);
+    auto quant = [&](const void* W, int N, int K, void** w4, unsigned char** sc) -> int {
+      if (!*w4) {
+        TRY(ctx->alloc(w4, (size_t)N * (K / 2)));
+        TRY(ctx->alloc((void**)sc, (size_t)N * (K / 32)));
+      }
+      return launch_quant_mxfp4_rows(ctx->dt, W, K, N, K, *w4, K / 2, *sc, nullptr);
+    };
+    for (int i = 0; i < c.t_layers; ++i) {
+      auto& L = ctx->dl[i]; auto& Q = ctx->dl4[i];
+      TRY(quant(L.wqkv, qkvd, H, &Q.wqkv, &Q.sqkv));
+      TRY(quant(L.wo, H, qd, &Q.wo, &Q.so));
+      TRY(quant(L.wgu, 2 * It, H, &Q.wgu, &Q.sgu));
+      TRY(quant(L.wd, H, It, &Q.wd, &Q.sd));
+    }
+    TRY(quant(ctx->t_lm, c.t_vocab, H, &ctx->t_lm4, &ctx->t_lm4_s));
+    OM_HIP(hipDeviceSynchronize());
+    ctx->mxfp4_stale = false;
+  }
+  return 0;
+}
+
+extern "C" int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int on) {
+  OM_CHECK(ctx, "null context");
+  OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
+  if (!on) { ctx->mxfp4_decode = false; return 0; }
+  OM_CHECK(!ctx->fp8_decode, "fp8 decode is on: one weight format per step (omchat_enable_fp8_decode(ctx, 0) first)");
+  OM_CHECK(ctx->tp_size == 1, "MXFP4 decode under tensor parallelism is not implemented");
+  TRY(ensure_mxfp4_weights(ctx));
+  ctx->mxfp4_decode = true;
   return 0;
 }
 
@@ -1240,33 +1284,38 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   TRY(launch_gather_rows(ctx->dt, tokens, ctx->t_embed, nullptr, x, b, H, s));      // embed_tokens
   // weight-only fp8 replica (omchat_enable_fp8_decode): batch-1 steps stream e4m3 bytes + per-row scales
   const bool f8 = ctx->fp8_decode && b == 1;      // under tensor parallelism every rank streams the e4m3 replica of its own shard (round 3)
+  // weight-only MXFP4 replica (omchat_enable_mxfp4_decode): batch-1 steps stream e2m1 codes + e8m0 block scales; never together with f8
+  const bool mx4 = ctx->mxfp4_decode && b == 1;
+  const bool wq = f8 || mx4;      // a quantised replica is streamed: the launches that exist for 16-bit weights only stay out
   // batched steps (2 <= b <= 32): the activations that feed a GEMV (tw_xn, tw_ao, tw_act) are produced in the packed x layout
   // (common.h) by their producers, and the weights come from the packed replica when it exists (ensure_packed)
   const int pk = (b > 1 && b <= 32 && H % 64 == 0 && qd % 64 == 0 && It % 64 == 0) ? (b > 16 ? 2 : 1) : 0;
   const bool wpk = pk && ctx->pk_ready;
   static const omchat_ctx::DecLayerP noneP{};
   auto gemv_args = [&](const void* X, int ldx, const void* W, int K, void* Y, int ldy, int R, int N, const void* bias, const void* resid, int epi,
-                       int ks, const void* W8, const float* sc, const void* WP, bool ypk) {
+                       int ks, const void* W8, const float* sc, const void* WP, bool ypk, const void* W4 = nullptr, const unsigned char* s4 = nullptr) {
     GemvArgs g{X, ldx, W, K, Y, ldy, R, N, K, bias, resid, H, epi, 0, ks};
     if (f8 && W8) { g.W = W8; g.w_scale = sc; }
+    if (mx4 && W4) { g.W = W4; g.ldw = K / 2; g.mx_scale = s4; }
     if (pk) { g.x_packed = 1; g.y_packed = ypk && epi == EPI_SWIGLU; if (wpk && WP) { g.W = WP; g.w_packed = 1; } }
     return g;
   };
   auto gemv = [&](const void* X, int ldx, const void* W, int K, void* Y, int ldy, int N, const void* bias, const void* resid, int epi,
-                  const void* W8 = nullptr, const float* sc = nullptr, const void* WP = nullptr, bool ypk = false) -> int {
+                  const void* W8 = nullptr, const float* sc = nullptr, const void* WP = nullptr, bool ypk = false, const void* W4 = nullptr,
+                  const unsigned char* s4 = nullptr) -> int {
     for (int r0 = 0; r0 < b; r0 += 32) {
       const int R = std::min(32, b - r0);
       const GemvArgs g = gemv_args((const char*)X + (size_t)r0 * ldx * 2, ldx, W, K, (char*)Y + (size_t)r0 * ldy * 2, ldy, R, N, bias,
-                                   resid ? (const char*)resid + (size_t)r0 * H * 2 : nullptr, epi, 0, W8, sc, WP, ypk);
+                                   resid ? (const char*)resid + (size_t)r0 * H * 2 : nullptr, epi, 0, W8, sc, WP, ypk, W4, s4);
       TRY(launch_gemv(ctx->dt, g, s));
     }
     return 0;
   };
   // split-K over workgroups: fp32 slices [ks][b][H], summed by the fused residual + RMSNorm kernel
   auto gemv_partial = [&](const void* X, int ldx, const void* W, int K, int ks, const void* W8 = nullptr, const float* sc = nullptr,
-                          const void* WP = nullptr) -> int {
+                          const void* WP = nullptr, const void* W4 = nullptr, const unsigned char* s4 = nullptr) -> int {
     OM_CHECK(b <= 32, "split-K decode path handles b <= 32");
-    const GemvArgs g = gemv_args(X, ldx, W, K, ctx->tw_part, H, b, H, nullptr, nullptr, EPI_PARTIAL, ks, W8, sc, WP, false);
+    const GemvArgs g = gemv_args(X, ldx, W, K, ctx->tw_part, H, b, H, nullptr, nullptr, EPI_PARTIAL, ks, W8, sc, WP, false, W4, s4);
     TRY(launch_gemv(ctx->dt, g, s));
     // tensor parallelism: the slices hold this rank's partial sums; reduce_resid_rmsnorm sums them over the ranks in fp32 (<= 3 x 3584
     // floats at batch 1, latency-bound like any small message) together with the residual + RMSNorm, identically on every rank
@@ -1301,7 +1350,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   const bool n1 = n2 && (g_norm_in_gemv & 2) && It <= 32768 && It % 8 == 0;
   // batched steps on one GPU (round 5, key 14 bit 2; -DOMCHAT_EXPERIMENTS=1 builds only: measured slower, gemv.hip): o_proj un-split in the x-stationary form writes x + attn itself (row-major in place AND the
   // packed raw copy), and the post-attention RMSNorm runs in the registers of the gate|up GEMV: seven launches per layer instead of eight
-  const bool nb2 = OMCHAT_EXPERIMENTS && (g_norm_in_gemv & 4) && fused && wpk && ctx->tp_size == 1 && !f8 && (qd >> 6) == 56 && (H >> 6) == 56 && qd % 64 == 0 &&
+  const bool nb2 = OMCHAT_EXPERIMENTS && (g_norm_in_gemv & 4) && fused && wpk && ctx->tp_size == 1 && !wq && (qd >> 6) == 56 && (H >> 6) == 56 && qd % 64 == 0 &&
                    H / 16 <= device_cus() && (2 * It) / 32 >= 4 * device_cus();
   if (fused && !n1) TRY(launch_rmsnorm(ctx->dt, x, H, ctx->dl[0].ln1, ctx->tw_xn, H, b, H, c.t_eps, s, pk));
 #if OMCHAT_EXPERIMENTS
@@ -1311,13 +1360,15 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     auto& L = ctx->dl[i];
     static const omchat_ctx::DecLayer8 none8{};
     const omchat_ctx::DecLayer8& Q = f8 ? ctx->dl8[i] : none8;
+    static const omchat_ctx::DecLayer4 none4{};
+    const omchat_ctx::DecLayer4& M = mx4 ? ctx->dl4[i] : none4;
     const omchat_ctx::DecLayerP& P = wpk ? ctx->dlp[i] : noneP;
     char* kc = (char*)ctx->kcache + (size_t)i * ctx->cache_layer_stride() * 2;
     char* vc = (char*)ctx->vcache + (size_t)i * ctx->cache_layer_stride() * 2;
     if (!fused) TRY(launch_rmsnorm(ctx->dt, x, H, L.ln1, ctx->tw_xn, H, b, H, c.t_eps, s));
     // batch 1, one GPU (round 4): the whole layer as ONE launch with in-launch hand-offs (decode_layer.hip; the same bits as the six
     // launches below).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
-    if (g_decode_layer && n1 && exact_len && !masked && !f8 && !(ctx->fp8_kv && ctx->kv8_valid) && ctx->dl_ws) {      // (the layer kernel has no key mask)
+    if (g_decode_layer && n1 && exact_len && !masked && !wq && !(ctx->fp8_kv && ctx->kv8_valid) && ctx->dl_ws) {      // (the layer kernel has no key mask)
       DecodeLayerArgs d{L.ln1, L.ln2, L.wqkv, L.bqkv, L.wo, L.wgu, L.wd, kc, vc, ctx->cache_sh(), x, H, qd, ctx->t_kvdim, It, c.t_heads, c.t_kv_heads, Lmax,
                         ctx->rope, c.max_seq, c.t_eps, 0.08838834764831845f, ctx->dl_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       if (decode_layer_ok(d)) {
@@ -1331,12 +1382,12 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       --ctx->fd_epoch;
     }
     if (n1) {
-      GemvArgs g = gemv_args(x, H, L.wqkv, H, ctx->tw_qkv, qkvd, 1, qkvd, L.bqkv, nullptr, EPI_NONE, 0, Q.wqkv, Q.sqkv, nullptr, false);
+      GemvArgs g = gemv_args(x, H, L.wqkv, H, ctx->tw_qkv, qkvd, 1, qkvd, L.bqkv, nullptr, EPI_NONE, 0, Q.wqkv, Q.sqkv, nullptr, false, M.wqkv, M.sqkv);
       g.norm_w = L.ln1; g.norm_eps = c.t_eps;
       if (OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else {
-      TRY(gemv(ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, qkvd, L.bqkv, nullptr, EPI_NONE, Q.wqkv, Q.sqkv, P.wqkv));
+      TRY(gemv(ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, qkvd, L.bqkv, nullptr, EPI_NONE, Q.wqkv, Q.sqkv, P.wqkv, false, M.wqkv, M.sqkv));
     }
     // RoPE + KV append are fused into the attention kernel (q rotated in registers, the split that owns the new
     // position rotates k and appends k / v)
@@ -1374,7 +1425,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     // batch 1, one GPU (round 4): attention + merge + o_proj (+ residual) as ONE launch with in-launch hand-offs (fused_decode.hip; the same
     // bits as the three launches).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     bool ao_oproj = false;
-    const bool fuse_ao = g_fuse_attn_oproj && n2 && exact_len && !f8 && a.rope && ctx->fd_ws && attn_oproj_fused_ok(a, H, qd);
+    const bool fuse_ao = g_fuse_attn_oproj && n2 && exact_len && !wq && a.rope && ctx->fd_ws && attn_oproj_fused_ok(a, H, qd);
     if (vL >= 0) {
       AttnVerifyArgs va{};
       va.Q = ctx->tw_qkv; va.q_sb = qkvd; va.q_sh = 128;
@@ -1394,7 +1445,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
 #if OMCHAT_EXPERIMENTS
       // tuning key 42 (prototype): o_proj out of order behind the merge, which publishes per-head completion flags (fd_ws doubles as the flag words:
       // key 22 and key 42 are not meant to be on together)
-      ao_oproj = (g_ao_oproj & 1) && n2 && !f8 && !masked && ctx->fd_ws && Lmax <= 4096 && H == 3584 && qd == 3584 && c.t_heads <= 64 && !ctx->graph_on;
+      ao_oproj = (g_ao_oproj & 1) && n2 && !wq && !masked && ctx->fd_ws && Lmax <= 4096 && H == 3584 && qd == 3584 && c.t_heads <= 64 && !ctx->graph_on;
       if (ao_oproj) { a.done_flags = (unsigned*)ctx->fd_ws; a.done_epoch = ++ctx->fd_epoch; a.done_mode = g_ao_oproj; }
       if ((g_ao_oproj & 16) && n2 && ctx->dbg_stamps) a.done_dbg = ctx->dbg_stamps + (size_t)i * 32;
 #endif
@@ -1408,18 +1459,18 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       GemvArgs g = gemv_args(ctx->tw_ao, qd, L.wo, qd, x, H, 1, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, nullptr, false);
       if ((g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv_wait(ctx->dt, g, (const unsigned*)ctx->fd_ws, ctx->fd_epoch, c.t_heads, ctx->fd_err, g_ao_oproj, s));
-    } else if (n2 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !f8) {
+    } else if (n2 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !wq) {
       GemvArgs g = gemv_args(ctx->tw_ao, qd, L.wo, qd, x, H, 1, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, nullptr, false);
       g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (n2) {
-      TRY(gemv(ctx->tw_ao, qd, L.wo, qd, x, H, H, nullptr, x, EPI_RESID, Q.wo, Q.so));
+      TRY(gemv(ctx->tw_ao, qd, L.wo, qd, x, H, H, nullptr, x, EPI_RESID, Q.wo, Q.so, nullptr, false, M.wo, M.so));
     } else if (nb2) {
       GemvArgs g = gemv_args(ctx->tw_ao, qd, L.wo, qd, x, H, b, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, P.wo, false);
       g.y_pack = ctx->tw_xn;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (fused) {
-      TRY(gemv_partial(ctx->tw_ao, qd, L.wo, qd, ks_o, Q.wo, Q.so, P.wo));
+      TRY(gemv_partial(ctx->tw_ao, qd, L.wo, qd, ks_o, Q.wo, Q.so, P.wo, M.wo, M.so));
       TRY(ctx->reduce_resid_rmsnorm(x, H, ctx->tw_part, ks_o, L.ln2, ctx->tw_xn, H, b, H, c.t_eps, pk, s));
     } else if (ctx->tp_size == 1) {
       TRY(gemv(ctx->tw_ao, qd, L.wo, qd, x, H, H, nullptr, x, EPI_RESID));
@@ -1434,7 +1485,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     const bool mark = allow_prof && i == c.t_layers / 2;
     if (mark) ctx->prof_mark(OMCHAT_PROF_DECODE_GATEUP, s);
     if (n2) {
-      GemvArgs g = gemv_args(x, H, L.wgu, H, ctx->tw_act, It, 1, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, Q.wgu, Q.sgu, nullptr, false);
+      GemvArgs g = gemv_args(x, H, L.wgu, H, ctx->tw_act, It, 1, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, Q.wgu, Q.sgu, nullptr, false, M.wgu, M.sgu);
       g.norm_w = L.ln2; g.norm_eps = c.t_eps;
       if (ctx->dyn_ctr && !ctx->graph_on) g.dyn_ctr = ctx->dyn_ctr + (size_t)i * 65 * 64;
       if (OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
@@ -1444,17 +1495,17 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       g.norm_w = L.ln2; g.norm_eps = c.t_eps;
       TRY(launch_gemv(ctx->dt, g, s));
     } else {
-      TRY(gemv(ctx->tw_xn, H, L.wgu, H, ctx->tw_act, It, 2 * It, nullptr, nullptr, EPI_SWIGLU, Q.wgu, Q.sgu, P.wgu, true));
+      TRY(gemv(ctx->tw_xn, H, L.wgu, H, ctx->tw_act, It, 2 * It, nullptr, nullptr, EPI_SWIGLU, Q.wgu, Q.sgu, P.wgu, true, M.wgu, M.sgu));
     }
     if (mark) ctx->prof_mark(OMCHAT_PROF_DECODE_GATEUP, s);
-    if (n1 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !f8) {
+    if (n1 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !wq) {
       GemvArgs g = gemv_args(ctx->tw_act, It, L.wd, It, x, H, 1, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, nullptr, false);
       g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (n1) {
-      TRY(gemv(ctx->tw_act, It, L.wd, It, x, H, H, nullptr, x, EPI_RESID, Q.wd, Q.sd));
+      TRY(gemv(ctx->tw_act, It, L.wd, It, x, H, H, nullptr, x, EPI_RESID, Q.wd, Q.sd, nullptr, false, M.wd, M.sd));
     } else if (fused) {
-      TRY(gemv_partial(ctx->tw_act, It, L.wd, It, ks_d, Q.wd, Q.sd, P.wd));
+      TRY(gemv_partial(ctx->tw_act, It, L.wd, It, ks_d, Q.wd, Q.sd, P.wd, M.wd, M.sd));
       const void* nw = i + 1 < c.t_layers ? ctx->dl[i + 1].ln1 : ctx->t_norm;      // next layer's input norm, or the final norm
       TRY(ctx->reduce_resid_rmsnorm(x, H, ctx->tw_part, ks_d, nw, ctx->tw_xn, H, b, H, c.t_eps, pk, s));
     } else if (ctx->tp_size == 1) {
@@ -1470,10 +1521,11 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   if (n1) {
     GemvArgs g{x, H, ctx->t_lm, H, lg, c.t_vocab, 1, c.t_vocab, H, nullptr, nullptr, 0, EPI_NONE, 1};
     if (f8) { g.W = ctx->t_lm8; g.w_scale = ctx->t_lm8_s; }
+    if (mx4) { g.W = ctx->t_lm4; g.ldw = H / 2; g.mx_scale = ctx->t_lm4_s; }
     g.norm_w = ctx->t_norm; g.norm_eps = c.t_eps;
     TRY(launch_gemv(ctx->dt, g, s));
   } else {
-    TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, f8, fused && pk));
+    TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, f8, fused && pk, mx4));
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
   if (vL >= 0) TRY(greedy_pick(ctx, lg, b, next_tokens, s));
@@ -1541,6 +1593,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   // a weight reload (omchat_load_tensor) leaves the e4m3 replica stale: re-quantise IN PLACE before streaming it (same device
   // pointers, so a captured decode graph stays valid and replays the fresh bytes)
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
+  if (ctx->mxfp4_decode && ctx->mxfp4_stale) TRY(ensure_mxfp4_weights(ctx));
   TRY(pick_admit(ctx, next_tokens != nullptr, true));
   ctx->graph_steps++;
   // graph replay needs replay-invariant arguments: single-GPU fused path only; with profiling on, every 8th step runs eagerly
@@ -1550,7 +1603,8 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
     TRY(decode_body(ctx, tokens, b, Lmax, logits, next_tokens, s, true, same_len));
   } else {
     const bool f8 = ctx->fp8_decode && b == 1;
-    omchat_ctx::DecodeGraph& g = ctx->graphs[b * 4 + (f8 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0)];
+    const bool mx4 = ctx->mxfp4_decode && b == 1;
+    omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (mx4 ? 4 : 0) + (f8 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0)];
     hipStream_t gs = ctx->graph_stream;
     OM_HIP(hipEventRecord(ctx->graph_ev_in, s));
     OM_HIP(hipStreamWaitEvent(gs, ctx->graph_ev_in, 0));
@@ -1634,6 +1688,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   // replicas first: a failure here must not leave host-to-device copies of caller / stack memory in flight
   if (b > 1 && b <= 32) TRY(ensure_packed(ctx));
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
+  if (ctx->mxfp4_decode && ctx->mxfp4_stale) TRY(ensure_mxfp4_weights(ctx));
   return 0;
 }
 

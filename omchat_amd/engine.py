@@ -161,6 +161,14 @@ class Engine:
         """Weight-only OCP e4m3 replica of the decode-streamed decoder weights (quantised on first call); batch-1 decode only."""
         check(self.lib.omchat_enable_fp8_decode(self.h, int(on)))
 
+    def enable_mxfp4_decode(self, on=True):
+        """Weight-only MXFP4 replica (OCP Microscaling: e2m1 codes + one e8m0 scale per 32 k, 4.25 bits per weight) of the decode-streamed
+        decoder weights, quantised on the first call and again after a weight reload; batch-1 decode steps only.  Batched steps, the
+        prompt-lookup verify step and beam search keep the 16-bit weights, as under enable_fp8_decode.  Refused before the weights are
+        loaded, together with enable_fp8_decode, and under tensor parallelism."""
+        check(self.lib.omchat_enable_mxfp4_decode(self.h, int(on)))
+        self._mxfp4_decode = bool(on)
+
     def enable_fp8_kv(self, on=True):
         """fp8 (e4m3 + per-position scale) KV cache for the decode steps that follow the NEXT prefill (BASELINE configs[4])"""
         check(self.lib.omchat_enable_fp8_kv(self.h, int(on)))

@@ -191,6 +191,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
 
     __call__ = forward
 
+    def enable_mxfp4_decode(self, on=True):
+        """Engine.enable_mxfp4_decode: batch-1 decode steps of generate() stream the MXFP4 replica of the decoder weights (greedy, sampling,
+        bans, logprobs, reuse_cache and the decode graph unchanged); batched steps and beam search keep the 16-bit weights, and
+        prompt_lookup_num_tokens is refused while it is on."""
+        self.engine.enable_mxfp4_decode(on)
+
     def _stage_buffer(self, steps, b):
         """pinned staging rows for the generated ids + the event that guards them: allocated once and grown on demand (a hipHostMalloc per
         generate() call was measurable)"""
@@ -257,6 +263,9 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise NotImplementedError("prompt-lookup decoding with num_beams > 1 is not implemented")
         if getattr(self.engine, "_fp8_kv", False):
             raise NotImplementedError("prompt-lookup decoding over the e4m3 KV cache is not implemented: enable_fp8_kv(False)")
+        if vars(self.engine).get("_mxfp4_decode", False):
+            raise NotImplementedError("prompt-lookup decoding with MXFP4 decode weights is not implemented: a verify step runs on the 16-bit "
+                                      "weights, so one generation would mix two weight sets: enable_mxfp4_decode(False)")
         if int(k) <= 0 or int(m) <= 0:
             raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")
         if int(k) > MAX_LOOKUP_TOKENS:
