@@ -159,6 +159,14 @@ int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tok
  * sampling off (greedy again).  A parameter change drops the captured decode graphs.  Synchronises. */
 int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
                         const int32_t* seen_ids, const int32_t* n_seen_per_row, void* stream);
+/* omchat_set_sampling_filters: HF's four warpers behind top-p for the sampling state omchat_set_sampling just configured, in HF's order and
+ * with min_tokens_to_keep = 1; each sees the softmax over the survivors of the ones before it.  min_p (negative = off): keeps p >= min_p *
+ * p_max.  typical_p (>= 1 = off): keeps the tokens with the smallest |-log p - H| (H = the entropy) whose mass first reaches typical_p, ties
+ * at the cut kept -- the top token can go.  epsilon_cutoff (>= 1 = off): keeps p >= epsilon.  eta_cutoff (>= 1 = off): keeps p >=
+ * min(eta, sqrt(eta) * exp(-H)).  Epsilon and eta always keep the largest surviving logit and its ties.  The kept set is a key interval
+ * [lo, hi] of the processed logits.  omchat_set_sampling alone leaves all four off, so call this after it.  top_k == 1 stays the greedy pick.
+ * Other values than the captured decode graphs hold drop them in front of the next step.  Refused while sampling is off. */
+int omchat_set_sampling_filters(omchat_ctx* ctx, double min_p, double typical_p, double epsilon_cutoff, double eta_cutoff, void* stream);
 /* the sampled counterpart of omchat_greedy (the first token after the prefill); omchat_greedy itself when sampling is off */
 int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream);
 /* ---- HF logits constraints (generate's no_repeat_ngram_size, bad_words_ids, min_new_tokens / min_length, suppress_tokens,
@@ -582,6 +590,11 @@ int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_len, const 
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */
 int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
                      const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream);
+/* omchat_op_sample with the four filters of omchat_set_sampling_filters (same "off" values).  thr_lo / thr_hi (device uint32 [b] or NULL, test
+ * hooks): both ends of the kept key interval; thr_lo as omchat_op_sample's thr_out, thr_hi = 0xFFFFFFFF when the row's top token is kept. */
+int omchat_op_sample_filtered(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                              double min_p, double typical_p, double epsilon_cutoff, double eta_cutoff, const int32_t* seen_ids,
+                              const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_lo, uint32_t* thr_hi, void* stream);
 /* context-free log-probability stage of omchat_set_logprobs (test hook): logits device fp32 [b][ld] (ld >= V), ids host int32 [b] (the picked
  * ids), ban device uint32 [b][(V + 31) / 32] or NULL (set bit = processed value -inf), seen ids as omchat_op_sample takes them (read when
  * rep_penalty != 1), newly_seen host int32 [b] or NULL (!= 0: the pick set its id's seen bit, so the id counts as unseen), thr device uint32 [b]
@@ -589,6 +602,11 @@ int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float tem
 int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
                             float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
                             const uint32_t* thr, float* raw_out, float* processed_out, void* stream);
+/* omchat_op_token_logprob over a kept interval: thr_lo / thr_hi device uint32 [b] or NULL (omchat_op_sample_filtered's; NULL = no bound on
+ * that side).  An id outside the interval records -inf as its processed value. */
+int omchat_op_token_logprob_interval(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
+                                     float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
+                                     const uint32_t* thr_lo, const uint32_t* thr_hi, float* raw_out, float* processed_out, void* stream);
 /* context-free beam step (test hook of omchat_beam_step's selection, TP = 1): logits fp32 [rows, V] (rows = b at t = 0, else b*N), step t
  * of max_new; state: device int32 [omchat_beam_state_words(b, N, max_new)] carried from call to call (initialised by the t = 0 call).
  * Outputs device int32: tokens [b*N], parents [b*N] (rows; a row's own index at t = 0 and for frozen prompts), done_word [1]. */

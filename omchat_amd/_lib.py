@@ -51,6 +51,7 @@ _SIGS = {
     "omchat_lm_head": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_greedy": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_set_sampling": (_i, [_vp, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _vp]),
+    "omchat_set_sampling_filters": (_i, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "omchat_sample": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_set_constraints": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
@@ -138,6 +139,9 @@ _SIGS = {
     "omchat_op_layernorm_ld": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_op_token_logprob": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "omchat_op_sample_filtered": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _i,
+                                       _vp, _vp, _vp, _vp]),
+    "omchat_op_token_logprob_interval": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_constrain": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "omchat_beam_state_words": (_sz, [_i, _i, _i]),
     "omchat_op_beam_select": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

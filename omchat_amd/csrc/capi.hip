@@ -372,8 +372,9 @@ extern "C" int omchat_op_argmax(const float* logits, int b, int V, int32_t* out,
   return rc;
 }
 
-extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
-                                const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream) {
+static int op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                     const SampleFilters& flt, const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out,
+                     uint32_t* hi_out, void* stream) {
   OM_CHECK(logits && out && b >= 1 && V >= 1, "bad argument");
   OM_CHECK(temperature > 0.f && top_k >= 0 && top_p > 0.0 && top_p <= 1.0 && rep_penalty > 0.f, "sampling parameters out of range");
   const int bmw = (V + 31) / 32;
@@ -401,16 +402,36 @@ extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed
   a.logits = logits; a.ld = V; a.b = b; a.V = V; a.V_total = V;
   a.seed = seed; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.penalty = rep_penalty;
   if (rep_penalty != 1.f) { a.bitmap = d_bm; a.bm_words = bmw; }
-  a.last_set = d_last; a.step = d_step; a.out = out; a.thr_out = thr_out; a.ws = mem;
+  a.last_set = d_last; a.step = d_step; a.out = out; a.thr_out = thr_out; a.hi_out = hi_out; a.ws = mem;
+  a.f = flt;
   int rc = launch_sample(a, S(stream));
   hipStreamSynchronize(S(stream));
   hipFree(mem);
   return rc;
 }
 
-extern "C" int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
-                                       float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
-                                       const uint32_t* thr, float* raw_out, float* processed_out, void* stream) {
+extern "C" int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
+                                const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_out, void* stream) {
+  return op_sample(logits, b, V, seed, temperature, top_k, top_p, rep_penalty, SampleFilters{}, seen_ids, n_seen_per_row, step, out, thr_out,
+                   nullptr, stream);
+}
+
+extern "C" int omchat_op_sample_filtered(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p,
+                                         float rep_penalty, double min_p, double typical_p, double epsilon_cutoff, double eta_cutoff,
+                                         const int32_t* seen_ids, const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_lo,
+                                         uint32_t* thr_hi, void* stream) {
+  OM_CHECK(!(min_p > 1.0) && min_p == min_p && typical_p > 0.0 && epsilon_cutoff > 0.0 && eta_cutoff > 0.0, "sampling filter parameters out of range");
+  SampleFilters f;
+  f.min_p = min_p < 0.0 ? -1.0 : min_p;
+  f.typical_p = typical_p < 1.0 ? typical_p : 1.0;
+  f.epsilon = epsilon_cutoff < 1.0 ? epsilon_cutoff : 1.0;
+  f.eta = eta_cutoff < 1.0 ? eta_cutoff : 1.0;
+  return op_sample(logits, b, V, seed, temperature, top_k, top_p, rep_penalty, f, seen_ids, n_seen_per_row, step, out, thr_lo, thr_hi, stream);
+}
+
+static int op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
+                            float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
+                            const uint32_t* thr, const uint32_t* thr_hi, float* raw_out, float* processed_out, void* stream) {
   OM_CHECK(logits && ids && raw_out && processed_out && b >= 1 && V >= 1 && ld >= V, "bad argument");
   OM_CHECK(temperature > 0.f && rep_penalty > 0.f, "sampling parameters out of range");
   const int bmw = (V + 31) / 32;
@@ -447,7 +468,7 @@ extern "C" int omchat_op_token_logprob(const float* logits, int b, int V, int ld
   LogprobArgs a;
   a.raw = logits; a.raw_ld = ld; a.b = b; a.V = V; a.ids = d_ids; a.ban = ban; a.bm_words = bmw;
   if (pen) { a.seen = d_bm; a.last_set = d_last; }
-  a.temperature = temperature; a.penalty = rep_penalty; a.thr = thr; a.thr_stride = 1;
+  a.temperature = temperature; a.penalty = rep_penalty; a.thr = thr; a.thr_hi = thr_hi; a.thr_stride = 1;
   a.ws = mem; a.rec = d_rec; a.cnt = d_cnt; a.max_new = 1; a.rec_ld = b;
   int rc = launch_logprob(a, s);
   if (!rc) {
@@ -457,6 +478,21 @@ extern "C" int omchat_op_token_logprob(const float* logits, int b, int V, int ld
   hipStreamSynchronize(s);
   hipFree(mem);
   return rc;
+}
+
+extern "C" int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
+                                       float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
+                                       const uint32_t* thr, float* raw_out, float* processed_out, void* stream) {
+  return op_token_logprob(logits, b, V, ld, ids, ban, temperature, rep_penalty, seen_ids, n_seen_per_row, newly_seen, thr, nullptr, raw_out,
+                          processed_out, stream);
+}
+
+extern "C" int omchat_op_token_logprob_interval(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban,
+                                                float temperature, float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row,
+                                                const int32_t* newly_seen, const uint32_t* thr_lo, const uint32_t* thr_hi, float* raw_out,
+                                                float* processed_out, void* stream) {
+  return op_token_logprob(logits, b, V, ld, ids, ban, temperature, rep_penalty, seen_ids, n_seen_per_row, newly_seen, thr_lo, thr_hi, raw_out,
+                          processed_out, stream);
 }
 
 static_assert(CON_NGRAM_MAX == OMCHAT_CON_MAX_NGRAM && CON_EOS_MAX == OMCHAT_CON_MAX_EOS && CON_SUPPRESS_MAX == OMCHAT_CON_MAX_SUPPRESS &&

@@ -36,6 +36,10 @@ struct PickState {
   // penalty's seen-token bitmap of this rank's vocabulary slice [max_batch][smp_bmw] and the local index of the bit each row's last pick set
   struct Sampling { bool on = false; uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f; };
   Sampling smp;
+  // the four filters behind top-p (omchat_set_sampling_filters; off after omchat_set_sampling).  They live in the kernel arguments of the
+  // captured decode graphs like the other parameters: smp_f_graph = what the graphs were captured with, compared in front of every step
+  // (pick_admit), so that the set_sampling + set_sampling_filters pair of a generate() call with unchanged values keeps the graphs
+  SampleFilters smp_f, smp_f_graph;
   void* smp_ws = nullptr;
   uint32_t* smp_bm = nullptr; int smp_bmw = 0;
   int *smp_last = nullptr, *smp_step = nullptr;

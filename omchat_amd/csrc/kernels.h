@@ -378,15 +378,28 @@ int launch_argmax(const float* logits, int ld, int b, int V, int* out, void* scr
 // on-device sampling (sample.hip): repetition penalty, temperature, top-k, top-p, Gumbel-max draw keyed by (seed, row, step[row], global
 // index); tests/sampling_ref.py restates it.  Rank-local logits [b, ld]; under tensor parallelism (tp > 1) the integer histograms and the final
 // (value, index) pairs go through xchg (the context's fp32 all-reduce) and `table` ([tp][b][2] fp32, the greedy exchange's).
+// HF's four warpers behind top-p, in HF's order: MinP, Typical, Epsilon, Eta (min_tokens_to_keep = 1).  Off: min_p < 0, the others >= 1.
+// With any of them the kept set is a key interval [lo, hi] of the processed logits (typical_p can cut the top): DESIGN.md section 9.
+struct SampleFilters {
+  double min_p = -1.0, typical_p = 1.0, epsilon = 1.0, eta = 1.0;
+  bool min_p_on() const { return min_p >= 0.0; }
+  bool typical_on() const { return typical_p < 1.0; }
+  bool epsilon_on() const { return epsilon < 1.0; }
+  bool eta_on() const { return eta < 1.0; }
+  bool any() const { return min_p_on() || typical_on() || epsilon_on() || eta_on(); }
+  bool operator==(const SampleFilters& o) const { return min_p == o.min_p && typical_p == o.typical_p && epsilon == o.epsilon && eta == o.eta; }
+};
 struct SampleArgs {
   const float* logits = nullptr; int ld = 0, b = 0, V = 0, V_total = 0;   // V: this rank's vocabulary slice
   int rank = 0, tp = 1;
   uint64_t seed = 0; float temperature = 1.f; int top_k = 0; double top_p = 1.0; float penalty = 1.f;
+  SampleFilters f;
   uint32_t* bitmap = nullptr; int bm_words = 0;     // [b][bm_words] seen tokens of this rank's slice (read when penalty != 1, picked id set)
   int* last_set = nullptr;                          // [b] local index whose bit the last pick set, -1 = none (omchat_kv_rewind)
   int* step = nullptr;                              // [b] device step counters, advanced by one
   int* adv_pos = nullptr; int* adv_len = nullptr;   // optional: decode positions advanced with the pick
   int* out = nullptr; uint32_t* thr_out = nullptr;  // picked ids [b]; optional threshold keys [b] (test hook)
+  uint32_t* hi_out = nullptr;                       // optional upper keys [b] (test hook): 0xFFFFFFFF when the top is kept
   void* ws = nullptr;                               // sample_ws_bytes(b)
   float* table = nullptr;
   int (*xchg)(void* user, float* buf, size_t count, hipStream_t s) = nullptr;
@@ -396,12 +409,15 @@ size_t sample_ws_bytes(int b);
 int launch_sample(const SampleArgs& a, hipStream_t s);
 // take back n picks: clears the bit the last pick set (n == 1), step -= n
 int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s);
-// where the last launch_sample on (ws, b) left row r's kept-set threshold key: words[r * *stride]; nullptr when the parameters keep every token
-const uint32_t* sample_thr_words(const void* ws, int b, int V_total, int top_k, double top_p, int* stride);
+// where the last launch_sample on (ws, b) left row r's kept-set threshold key: words[r * *stride]; nullptr when the parameters keep every token.
+// *hi: the upper key of the kept interval, same stride; nullptr when the parameters keep the top (typical_p off)
+const uint32_t* sample_thr_words(const void* ws, int b, int V_total, int top_k, double top_p, const SampleFilters& f, int* stride,
+                                 const uint32_t** hi);
 // per-token log-probabilities of picked ids (logprob.hip; tests/logprob_ref.py restates it).  Rank-local fp32 logits
 // [b, V]; raw = log_softmax(raw)[id], processed = log_softmax(scores)[id] with scores evaluated on the fly from `proc` (the banned copy of
 // the constraints, or raw): ban bitmap, repetition penalty over `seen` (the bit the pick itself set, last_set, not counted), / temperature,
-// kept iff smp_key(value) >= thr[row * thr_stride] (thr == nullptr: everything kept; top1: only the maxima are kept, the sampler's top_k == 1).
+// kept iff thr[row * thr_stride] <= smp_key(value) <= thr_hi[row * thr_stride] (thr == nullptr: no lower bound, thr_hi == nullptr: no upper
+// bound; top1: only the maxima are kept, the sampler's top_k == 1).
 // An id that is not among the maxima records -inf under top1, as any cut id does.
 // Both land in rec = float [2][max_new][rec_ld] at column `row`, line cnt[row], and cnt[row] advances.  tp > 1: one xchg of `table`.
 struct LogprobArgs {
@@ -412,7 +428,7 @@ struct LogprobArgs {
   const uint32_t* ban = nullptr;                     // optional [b][bm_words]
   const uint32_t* seen = nullptr; int bm_words = 0; const int* last_set = nullptr;
   float temperature = 1.f, penalty = 1.f;
-  const uint32_t* thr = nullptr; int thr_stride = 1; int top1 = 0;
+  const uint32_t* thr = nullptr; const uint32_t* thr_hi = nullptr; int thr_stride = 1; int top1 = 0;
   void* ws = nullptr;                                // logprob_ws_bytes(b)
   float* table = nullptr;                            // logprob_table_bytes(b, tp), tp > 1
   int (*xchg)(void* user, float* buf, size_t count, hipStream_t s) = nullptr;

@@ -1,6 +1,6 @@
 // Per-token log-probabilities of the ids generate() picks: for every row the raw value log_softmax(logits)[id] and the
 // processed value log_softmax(scores)[id], scores = what HF's processors leave (banned ids at -inf, repetition penalty, / T, ids outside the
-// top-k / top-p kept set at -inf).  The processed row is never materialised: every element is evaluated on the fly exactly as sample.hip
+// kept interval of top-k / top-p / min_p / typical_p / epsilon / eta at -inf).  The processed row is never materialised: every element is evaluated on the fly exactly as sample.hip
 // evaluates it.  One launch of (LP_CH, b) workgroups leaves an online (max, sum exp(x - max)) pair per statistic and slice, one wave per row
 // folds the LP_CH pairs in a fixed tree and writes x_id - (max + log sum).  No float atomics and no arrival-order folds: the same bits come out
 // of the eager step and of the captured graph.  tests/logprob_ref.py is the fp64 restatement.
@@ -49,21 +49,23 @@ struct LpK {
   const uint32_t* ban; const uint32_t* seen; int bmw;
   const int* last;
   float pen, T;
-  const uint32_t* thr; int thr_stride;
+  const uint32_t* thr; const uint32_t* thr_hi; int thr_stride;
   int top1;
 };
 // the processed value of local id i of a row
 struct LpProc {
-  const uint32_t *ban, *seen; int skip; float pen, T; uint32_t thr;
+  const uint32_t *ban, *seen; int skip; float pen, T; uint32_t thr, top;
   __device__ __forceinline__ LpProc(const LpK& a, int row)
       : ban(a.ban ? a.ban + (size_t)row * a.bmw : nullptr), seen(a.seen ? a.seen + (size_t)row * a.bmw : nullptr),
-        skip(a.seen && a.last ? a.last[row] : -1), pen(a.pen), T(a.T), thr(a.thr ? a.thr[(size_t)row * a.thr_stride] : 0u) {}
+        skip(a.seen && a.last ? a.last[row] : -1), pen(a.pen), T(a.T), thr(a.thr ? a.thr[(size_t)row * a.thr_stride] : 0u),
+        top(a.thr_hi ? a.thr_hi[(size_t)row * a.thr_stride] : 0xFFFFFFFFu) {}
   __device__ __forceinline__ float operator()(float x, int i) const {
     if (ban && ((ban[i >> 5] >> (i & 31)) & 1u)) return -INFINITY;
     // HF scores this step with the seen set from before the pick: the bit the pick itself set (`skip`) does not count
     if (seen && i != skip && ((seen[i >> 5] >> (i & 31)) & 1u)) x = smp_penalise(x, pen);
     x = __fdiv_rn(x, T);
-    return smp_key(x) < thr ? -INFINITY : x;
+    const uint32_t k = smp_key(x);
+    return k < thr || k > top ? -INFINITY : x;
   }
 };
 
@@ -189,11 +191,11 @@ int launch_logprob(const LogprobArgs& a, hipStream_t s) {
   OM_CHECK(a.raw && a.ids && a.ws && a.rec && a.cnt && a.b >= 1 && a.V >= 1 && a.max_new >= 1 && a.rec_ld >= a.b, "launch_logprob: bad argument");
   OM_CHECK(a.tp == 1 || (a.xchg && a.table), "log-probabilities under tensor parallelism need the exchange");
   const bool pen = a.seen && a.penalty != 1.f;
-  const bool two = a.proc != a.raw || a.ban || pen || a.temperature != 1.f || a.thr || a.top1;
+  const bool two = a.proc != a.raw || a.ban || pen || a.temperature != 1.f || a.thr || a.thr_hi || a.top1;
   LpK k;
   k.raw = a.raw; k.raw_ld = a.raw_ld; k.proc = a.proc ? a.proc : a.raw; k.proc_ld = a.proc ? a.proc_ld : a.raw_ld; k.V = a.V;
   k.ban = a.ban; k.seen = pen ? a.seen : nullptr; k.bmw = a.bm_words; k.last = a.last_set;
-  k.pen = a.penalty; k.T = a.temperature; k.thr = a.thr; k.thr_stride = a.thr_stride; k.top1 = a.top1;
+  k.pen = a.penalty; k.T = a.temperature; k.thr = a.thr; k.thr_hi = a.thr_hi; k.thr_stride = a.thr_stride; k.top1 = a.top1;
   float4* part = (float4*)a.ws;
   if (two) hipLaunchKernelGGL(lp_partial_kernel<1>, dim3(LP_CH, a.b), dim3(256), 0, s, k, part);
   else hipLaunchKernelGGL(lp_partial_kernel<0>, dim3(LP_CH, a.b), dim3(256), 0, s, k, part);

@@ -70,7 +70,7 @@ int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, c
     a.temperature = P.smp.temperature; a.penalty = P.smp.penalty;
     if (P.smp.penalty != 1.f) { a.seen = P.smp_bm; a.bm_words = P.smp_bmw; a.last_set = P.smp_last; }
     a.top1 = P.smp.top_k == 1;
-    a.thr = sample_thr_words(P.smp_ws, b, c.t_vocab_total, P.smp.top_k, P.smp.top_p, &a.thr_stride);
+    a.thr = sample_thr_words(P.smp_ws, b, c.t_vocab_total, P.smp.top_k, P.smp.top_p, P.smp_f, &a.thr_stride, &a.thr_hi);
   }
   a.ws = P.lp_ws; a.table = P.lp_table; a.xchg = smp_xchg; a.xchg_user = ctx;
   a.rec = (float*)P.lp_rec.p; a.cnt = P.lp_cnt; a.max_new = P.lp_cap; a.rec_ld = c.max_batch;
@@ -99,6 +99,11 @@ int pick_alloc(omchat_ctx* ctx, int rows) {
 }
 
 int pick_admit(omchat_ctx* ctx, bool picks, bool feeds) {
+  // the filters behind top-p are kernel arguments of the captured decode graphs: other values than they were captured with drop them
+  if (!(ctx->pick.smp_f == ctx->pick.smp_f_graph)) {
+    drop_decode_graphs(ctx);
+    ctx->pick.smp_f_graph = ctx->pick.smp_f;
+  }
   if (picks) TRY(lp_room(ctx));
   if (feeds) TRY(con_count_step(ctx));
   if (ctx->pick.lp.on && picks) ctx->pick.lp_picks += 1;
@@ -133,6 +138,7 @@ int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipS
   a.logits = lg; a.ld = c.t_vocab; a.b = b; a.V = c.t_vocab; a.V_total = c.t_vocab_total;
   a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
   a.seed = P.smp.seed; a.temperature = P.smp.temperature; a.top_k = P.smp.top_k; a.top_p = P.smp.top_p; a.penalty = P.smp.penalty;
+  a.f = P.smp_f;
   if (P.smp.penalty != 1.f) { a.bitmap = P.smp_bm; a.bm_words = P.smp_bmw; }
   a.last_set = P.smp_last; a.step = P.smp_step;
   if (advance) { a.adv_pos = ctx->d_pos; a.adv_len = ctx->d_len; }
@@ -212,6 +218,7 @@ extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float 
                     o.penalty == p.penalty;
   if (!same) drop_decode_graphs(ctx);
   P.smp = p;
+  P.smp_f = SampleFilters{};      // off until omchat_set_sampling_filters (the graphs are checked against them in front of the next step)
   if (!p.on) return 0;
   if (!P.smp_ws) {
     P.smp_bmw = (c.t_vocab + 31) / 32;
@@ -240,6 +247,24 @@ extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float 
   OM_HIP(hipMemsetAsync(P.smp_step, 0, (size_t)c.max_batch * 4, s));
   OM_HIP(hipMemsetAsync(P.smp_last, 0xFF, (size_t)c.max_batch * 4, s));
   OM_HIP(hipStreamSynchronize(s));     // host vector
+  return 0;
+}
+
+// HF's MinP / Typical / Epsilon / Eta warpers behind top-p for the sampling state omchat_set_sampling just configured (include/omchat_hip.h)
+extern "C" int omchat_set_sampling_filters(omchat_ctx* ctx, double min_p, double typical_p, double epsilon_cutoff, double eta_cutoff, void* stream) {
+  (void)stream;
+  OM_CHECK(ctx, "null ctx");
+  OM_CHECK(ctx->pick.smp.on, "sampling filters: sampling is off (omchat_set_sampling first)");
+  OM_CHECK(!(min_p > 1.0) && min_p == min_p, "sampling: min_p in [0, 1] (negative = off)");
+  OM_CHECK(typical_p > 0.0, "sampling: typical_p in (0, 1) (1 or more = off)");
+  OM_CHECK(epsilon_cutoff > 0.0, "sampling: epsilon_cutoff in (0, 1) (1 or more = off)");
+  OM_CHECK(eta_cutoff > 0.0, "sampling: eta_cutoff in (0, 1) (1 or more = off)");
+  SampleFilters f;
+  f.min_p = min_p < 0.0 ? -1.0 : min_p;
+  f.typical_p = typical_p < 1.0 ? typical_p : 1.0;
+  f.epsilon = epsilon_cutoff < 1.0 ? epsilon_cutoff : 1.0;
+  f.eta = eta_cutoff < 1.0 ? eta_cutoff : 1.0;
+  ctx->pick.smp_f = f;
   return 0;
 }
 

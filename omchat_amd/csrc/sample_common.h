@@ -18,3 +18,5 @@ __device__ __forceinline__ float smp_penalised(const float* row, const uint32_t*
   if (seen && ((seen[i >> 5] >> (i & 31)) & 1u)) l = smp_penalise(l, pen);
   return l;
 }
+// typical_p's distance of a processed logit from the entropy, |-log p - H| with -log p = L - x (L = max + log Z), in fp32 as HF computes it
+__device__ __forceinline__ float smp_typ_dist(float x, float L, float H) { return fabsf(__fsub_rn(__fsub_rn(L, x), H)); }

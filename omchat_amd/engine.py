@@ -483,16 +483,23 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ sampling (include/omchat_hip.h: omchat_set_sampling)
-    def set_sampling(self, b, seed=0, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seen=None):
-        """every following token pick of rows 0..b-1 samples (HF order: repetition penalty, temperature, top-k, top-p; Gumbel-max keyed by
-        (seed, row, step, global id)); seen: per-row lists of already-seen ids for the penalty (ids outside the vocabulary are ignored).
-        Resets the rows' step counters.  b = 0: greedy again."""
+    def set_sampling(self, b, seed=0, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seen=None, min_p=None, typical_p=None,
+                     epsilon_cutoff=None, eta_cutoff=None):
+        """every following token pick of rows 0..b-1 samples (HF order: repetition penalty, temperature, top-k, top-p, min_p, typical_p,
+        epsilon_cutoff, eta_cutoff; Gumbel-max keyed by (seed, row, step, global id)); seen: per-row lists of already-seen ids for the
+        penalty (ids outside the vocabulary are ignored).  The last four are on under HF's rules: min_p when not None, typical_p when < 1,
+        the cutoffs when in (0, 1).  Resets the rows' step counters.  b = 0: greedy again."""
         torch = _torch()
         seen = seen if seen is not None else [[] for _ in range(max(b, 0))]
         n = torch.tensor([len(r) for r in seen] or [0], dtype=torch.int32)
         flat = torch.tensor([int(i) for r in seen for i in r] or [0], dtype=torch.int32)
         check(self.lib.omchat_set_sampling(self.h, int(b), int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), int(top_k or 0),
                                            float(1.0 if top_p is None else top_p), float(repetition_penalty), ptr(flat), ptr(n), cur_stream()))
+        if int(b) > 0:
+            cut = lambda v: float(v) if v is not None and 0.0 < float(v) < 1.0 else 1.0
+            check(self.lib.omchat_set_sampling_filters(self.h, -1.0 if min_p is None else float(min_p),
+                                                       1.0 if typical_p is None or float(typical_p) >= 1.0 else float(typical_p),
+                                                       cut(epsilon_cutoff), cut(eta_cutoff), cur_stream()))
 
     def sampling_off(self):
         check(self.lib.omchat_set_sampling(self.h, 0, 0, 1.0, 0, 1.0, 1.0, None, None, cur_stream()))

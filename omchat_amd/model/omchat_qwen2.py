@@ -218,8 +218,9 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                              "attention_mask": attention_mask, "images": kwargs.get("images", None)})
         return model_inputs
 
-    def _sampling_params(self, temperature, top_k, top_p, repetition_penalty, seed, generator):
-        """HF's resolution of the sampling arguments (None -> generation_config), validated as HF's warpers validate them"""
+    def _sampling_params(self, temperature, top_k, top_p, repetition_penalty, seed, generator, kwargs=None):
+        """HF's resolution of the sampling arguments (None -> generation_config), validated as HF's warpers validate them.  min_p,
+        typical_p, epsilon_cutoff and eta_cutoff are popped from `kwargs`; they are on under the rules of HF's _get_logits_processor."""
         gc = self.generation_config
         pick = lambda v, name, d: v if v is not None else (getattr(gc, name, None) if getattr(gc, name, None) is not None else d)
         T = pick(temperature, "temperature", 1.0)
@@ -235,6 +236,18 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {p}")
         if not float(rp) > 0:
             raise ValueError(f"`penalty` has to be a strictly positive float, but is {rp}")
+        kwargs = kwargs if kwargs is not None else {}
+        flt = {name: pick(kwargs.pop(name, None), name, None) for name in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")}
+        if flt["min_p"] is not None and not 0 <= flt["min_p"] <= 1.0:
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {flt['min_p']}")
+        if flt["typical_p"] is not None and flt["typical_p"] < 1.0:
+            if not 0 < float(flt["typical_p"]) < 1:
+                raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {float(flt['typical_p'])}")
+        else:
+            flt["typical_p"] = None
+        for name in ("epsilon_cutoff", "eta_cutoff"):      # HF switches them on inside (0, 1) only
+            if flt[name] is None or not 0.0 < flt[name] < 1.0:
+                flt[name] = None
         if seed is None and generator is not None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator, dtype=torch.int64))
         if seed is None:
@@ -242,7 +255,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if seed is None:
             raise NotImplementedError("do_sample=True draws on the device from an explicit seed: pass seed=<int> or generator=<torch.Generator> "
                                       "(or set generation_config.seed); sampling from torch's global RNG state is not implemented")
-        return dict(seed=int(seed), temperature=float(T), top_k=int(k), top_p=float(p), repetition_penalty=float(rp))
+        return dict(seed=int(seed), temperature=float(T), top_k=int(k), top_p=float(p), repetition_penalty=float(rp),
+                    **{name: None if v is None else float(v) for name, v in flt.items()})
 
     def _lookup_params(self, input_ids, kwargs, do_sample, num_beams):
         """(k, m) of prompt-lookup decoding, or None when prompt_lookup_num_tokens is not set (argument or generation_config); every
@@ -280,7 +294,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
-        and the generated ones, temperature, top-k, top-p -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed.
+        and the generated ones, temperature, top-k, top-p, then min_p, typical_p, epsilon_cutoff, eta_cutoff (HF's warpers of those names,
+        taken from the call or generation_config) -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed.
         prompt_lookup_num_tokens=k (max_matching_ngram_size=m, default 2; both also read from generation_config): HF's prompt-lookup
         decoding for b = 1, greedy (omchat_amd/lookup.py): drafts of up to k ids copied from the prompt + generated ids are verified in
         one verify step each.  Exactness: the verify rows go through the batched (MFMA-form) GEMVs and plain steps through the batch-1
@@ -297,7 +312,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         output_logprobs=True with return_dict_in_generate=True (also read from generation_config): returns a
         GenerateOutput whose .sequences is what the call returns otherwise, .logprobs [b, new] the log-probability of every generated id
         under the model's raw distribution and .processed_logprobs [b, new] under the distribution the pick was made from (bans, repetition
-        penalty, temperature, top-k / top-p); recorded by the pick on the device, read back once at the end.  Positions behind a row's EOS,
+        penalty, temperature, top-k / top-p and the four filters behind them); recorded by the pick on the device, read back once at the end.  Positions behind a row's EOS,
         where the sequence holds pad, are 0.  Refused with num_beams > 1 (sequences_scores) and with prompt_lookup_num_tokens."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
@@ -327,6 +342,10 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         eos_ids = eos_token_id if eos_token_id is not None else gc.eos_token_id
         eos_ids = list(eos_ids) if isinstance(eos_ids, (list, tuple)) else ([eos_ids] if eos_ids is not None else [])
         con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None)
+        # the sampling arguments are resolved and refused here too, before the sticky state below is touched (beam search refuses do_sample itself)
+        smp = self._sampling_params(temperature, top_k, top_p, repetition_penalty, seed, generator, kwargs) if do_sample and nb == 1 else None
+        for name in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"):      # do_sample=False (or beam search): ignored, as HF ignores them
+            kwargs.pop(name, None)
         if con is None:                                               # sticky context state, like the sampler: off unless this call sets it
             self.engine.constraints_off()                             # (set below, after the prefill; equal parameters keep the decode graphs)
         if not olp and getattr(self.engine, "_logprobs_on", False):   # sticky too: a call without the keyword records nothing
@@ -335,7 +354,6 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
                                        return_dict_in_generate)
-        smp = self._sampling_params(temperature, top_k, top_p, repetition_penalty, seed, generator) if do_sample else None
         if max_new_tokens is None:
             max_new_tokens = self.generation_config.max_new_tokens or 20
         eos = eos_token_id if eos_token_id is not None else self.generation_config.eos_token_id

@@ -11,7 +11,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SETS = [("T", dict(temperature=0.8)), ("T,k=50", dict(temperature=0.8, top_k=50)),
         ("T,k=50,p=0.9", dict(temperature=0.8, top_k=50, top_p=0.9)), ("T,p=0.9", dict(temperature=0.8, top_p=0.9)),
-        ("T,k=50,p=0.9,rep=1.3", dict(temperature=0.8, top_k=50, top_p=0.9, repetition_penalty=1.3))]
+        ("T,k=50,p=0.9,rep=1.3", dict(temperature=0.8, top_k=50, top_p=0.9, repetition_penalty=1.3)),
+        ("T,min_p=0.05", dict(temperature=0.8, min_p=0.05)), ("T,typical_p=0.9", dict(temperature=0.8, typical_p=0.9)),
+        ("T,eta=3e-4", dict(temperature=0.8, eta_cutoff=3e-4)),
+        ("T,k=50,p=0.9,min_p,typical,eps,eta", dict(temperature=0.8, top_k=50, top_p=0.9, min_p=0.05, typical_p=0.9, epsilon_cutoff=3e-4,
+                                                    eta_cutoff=3e-4))]
 
 
 def main():
