@@ -297,14 +297,24 @@ int omchat_enable_fp8_decode(omchat_ctx* ctx, int on);
 /* Builds (once) an MXFP4 replica (OCP Microscaling v1.0) of the same decode-streamed weights: per output row and per block of 32
  * consecutive k one e8m0 scale byte, e = floor(log2(absmax)) - 2 (stored e + 127; 127 for a zero block), and e2m1 codes of w / 2^e,
  * round to nearest, ties to the even code, saturating at 6; two codes per byte, the even k in the low nibble.  4.25 bits per weight:
- * 3.76 GB streamed per token at Qwen2-7B width against 14.1 GB (16-bit) and 7.1 GB (e4m3).  With on != 0, batch-1 decode steps read
- * the replica through gfx950's e2m1 -> 16-bit convert at scale 1 and apply 2^e to the lane's fp32 partial sum; prefill, b > 1 steps,
- * the verify step and beam search keep the 16-bit weights.  After omchat_load_tensor the next step re-quantises in place.
- * Refused: before the weights are loaded; while omchat_enable_fp8_decode is on (and the reverse: one weight format per step); on a
- * tensor-parallel context; when a streamed K (hidden_size, heads x 128, intermediate_size) is not a multiple of 32.  The e4m3 KV cache
- * and the fp8 x fp8 prefill GEMMs are independent of it.  Not part of the reference: parity is against the oracle run on the
- * de-quantised weights (tests/test_gpu_mxfp4.py). */
-int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int on);
+ * 3.76 GB streamed per token at Qwen2-7B width against 14.1 GB (16-bit) and 7.1 GB (e4m3).
+ * mode 0: off.
+ * mode 1: batch-1 decode steps read the replica through gfx950's e2m1 -> 16-bit convert at scale 1 and apply 2^e to the lane's fp32
+ *   partial sum; prefill, b > 1 steps, the verify step and beam search keep the 16-bit weights.
+ * mode 2: as mode 1, and every decode-side pass with 2 <= b <= 32 rows -- batched steps, omchat_decode_step_masked*, beam steps,
+ *   omchat_decode_verify -- reads a PACKED copy of the same codes and scales (a byte shuffle of the replica into the fragment order of
+ *   the packed batched GEMVs; + N K (1/2 + 1/32) bytes per matrix, about + 3.8 GB at Qwen2-7B width) through MFMA forms: the codes are
+ *   widened at scale 1, each 16-row x 32-k unit runs one MFMA from a zero accumulator, and 2^e of the row's block is applied to the
+ *   fp32 result.  One weight format per generation: a step of more than 32 rows is refused while mode 2 is on, never run on 16 bits.
+ *   The 16-bit packed replica of batched decode is not built for steps that stream the MXFP4 one.
+ * After omchat_load_tensor the next step re-quantises (and re-packs) in place: the device pointers, and so a captured graph, stay valid.
+ * Refused, with the mode left as it was: before the weights are loaded; while omchat_enable_fp8_decode is on (and the reverse: one
+ * weight format per step); on a tensor-parallel context; when a streamed K (hidden_size, heads x 128, intermediate_size) is not a
+ * multiple of 32; mode 2 also when one of those three is not a multiple of 64, when the qkv width, hidden_size or vocab_size is not a
+ * multiple of 16, or when the packed copy does not fit in device memory.  The e4m3 KV cache and the fp8 x fp8 prefill GEMMs are
+ * independent of it.  Not part of the reference: parity is against the oracle run on the de-quantised weights
+ * (tests/test_gpu_mxfp4.py, tests/test_gpu_mxfp4_batched.py). */
+int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int mode);
 
 /* ---- fp8 KV cache and fp8 x fp8 prefill GEMMs (BASELINE configs[4]: long video context, "fp8 MFMA weights") ------ */
 /* omchat_enable_fp8_kv: after the next prefill the decode steps read keys and values as OCP e4m3 bytes (57 344 -> 28 672 bytes per
@@ -488,6 +498,21 @@ int omchat_op_gemv_mxfp4(int dtype, const void* X, const void* W4, const void* S
                          const void* resid, int epi, int out_f32, int ksplit, void* stream);
 int omchat_op_gemv_mxfp4_norm(int dtype, const void* X, const void* W4, const void* S, void* Y, int N, int K, const void* norm_w, float eps,
                               const void* bias, int epi, int out_f32, void* stream);
+/* MXFP4 under b rows.  _rows: row-major operands -- b == 1 is omchat_op_gemv_mxfp4 without a residual, b > 1 is refused (MXFP4 at b > 1
+ * exists on the packed operands only).  _packed: omchat_op_gemv_packed on MXFP4 weights, 1 <= b <= 32, K % 64 == 0, N % 16 == 0: X [b, K]
+ * row-major and the row-major replica W4 / S are packed into scratch, then Y = epi(X dequant(W)^T); epi EPI_NONE (T or fp32 out) |
+ * EPI_SWIGLU (y_packed) | EPI_PARTIAL.  The packed layout itself is internal (csrc/common.h: packed_w4_index / packed_s4_index). */
+int omchat_op_gemv_mxfp4_rows(int dtype, const void* X, int ldx, const void* W4, const void* S, void* Y, int ldy, int b, int N, int K,
+                              const void* bias, int epi, int out_f32, int ksplit, void* stream);
+int omchat_op_gemv_mxfp4_packed(int dtype, const void* X, int ldx, const void* W4, const void* S, void* Y, int ldy, int b, int N, int K,
+                                const void* bias, int epi, int out_f32, int ksplit, int y_packed, void* stream);
+/* pack once, launch many times (tools/bench_mxfp4.py): omchat_op_pack_w: W [N, K] -> packed 16-bit replica (N K elements);
+ * omchat_op_pack_w4: W4 / S -> packed MXFP4 replica W4P (N K / 2 bytes), SP (N K / 32 bytes); omchat_op_gemv_prepacked: the launch alone on
+ * XP (omchat_op_pack_x) and WP, with SP = NULL for 16-bit weights; no allocation, no synchronisation */
+int omchat_op_pack_w(int dtype, const void* W, int ldw, int N, int K, void* out, void* stream);
+int omchat_op_pack_w4(const void* W4, const void* S, int N, int K, void* W4P, void* SP, void* stream);
+int omchat_op_gemv_prepacked(int dtype, const void* XP, const void* WP, const void* SP, void* Y, int ldy, int b, int N, int K, const void* bias,
+                             int epi, int out_f32, int ksplit, int y_packed, void* stream);
 int omchat_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int H, float eps, void* stream);
 /* the decode step's fused residual add + RMSNorm (modeling_qwen2.py:283-296 + 247-252): x[rows, H] = T(x + T(sum_s part[s])) in place,
  * part = fp32 split-K slices [ks][rows][H] of the projection, then xn = T(w * T(x * rsqrt(mean(x^2) + eps))) (w == NULL: skip);

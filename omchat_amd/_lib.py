@@ -103,6 +103,11 @@ _SIGS = {
     "omchat_enable_mxfp4_decode": (_i, [_vp, _i]),
     "omchat_op_quant_mxfp4": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_op_gemv_mxfp4": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "omchat_op_gemv_mxfp4_rows": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "omchat_op_gemv_mxfp4_packed": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "omchat_op_pack_w": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
+    "omchat_op_pack_w4": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "omchat_op_gemv_prepacked": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "omchat_op_gemv_mxfp4_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "omchat_op_rmsnorm": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "omchat_op_resid_rmsnorm": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),

@@ -676,6 +676,63 @@ extern "C" int omchat_op_gemv_mxfp4(int dtype, const void* X, const void* W4, co
   return launch_gemv(dtype, g, S(stream));
 }
 
+// the same weights under b rows of row-major x (no packed operands): b == 1 runs as omchat_op_gemv_mxfp4 does, b > 1 is refused by launch_gemv --
+// MXFP4 at b > 1 exists on the packed operands only (omchat_op_gemv_mxfp4_packed)
+extern "C" int omchat_op_gemv_mxfp4_rows(int dtype, const void* X, int ldx, const void* W4, const void* S_, void* Y, int ldy, int b, int N, int K,
+                                         const void* bias, int epi, int out_f32, int ksplit, void* stream) {
+  OM_CHECK(X && W4 && S_ && Y, "null argument");
+  OM_CHECK(K % 32 == 0, "MXFP4: K must be a multiple of 32 (one e8m0 scale per 32 consecutive k)");
+  GemvArgs g{X, ldx, W4, K / 2, Y, ldy, b, N, K, bias, nullptr, 0, epi, out_f32, ksplit};
+  g.mx_scale = (const unsigned char*)S_;
+  return launch_gemv(dtype, g, S(stream));
+}
+
+// packed-operand batched GEMV on MXFP4 weights (gemv.hip: gemv_pk_mx4_kernel / gemv_xs_mx4_kernel / gemv_xs_split_mx4_kernel): X row-major [b, K]
+// and the row-major replica W4 [N][K / 2], S [N][K / 32] are packed into scratch here (launch_pack_x / launch_pack_w4), then Y = epi(X dequant(W)^T)
+// as omchat_op_gemv_packed computes it on 16-bit weights.  Every refusal comes before anything is enqueued.
+extern "C" int omchat_op_gemv_mxfp4_packed(int dtype, const void* X, int ldx, const void* W4, const void* S_, void* Y, int ldy, int b, int N, int K,
+                                           const void* bias, int epi, int out_f32, int ksplit, int y_packed, void* stream) {
+  OM_CHECK(X && W4 && S_ && Y, "null argument");
+  OM_CHECK(b >= 1 && b <= 32, "packed MXFP4 GEMV: 1 <= b <= 32 rows per call");
+  OM_CHECK(K >= 64 && K % 64 == 0, "packed MXFP4 GEMV: K % 64 == 0 (64-wide K chunks of the packed layout)");
+  OM_CHECK(N >= 16 && N % 16 == 0, "packed MXFP4 GEMV: N % 16 == 0 (16-row weight tiles of the packed layout)");
+  OM_CHECK(epi == EPI_NONE || epi == EPI_SWIGLU || epi == EPI_PARTIAL, "packed MXFP4 GEMV: epilogue NONE / SWIGLU / PARTIAL");
+  OM_CHECK(dtype == OMCHAT_F16 || dtype == OMCHAT_BF16, "bad dtype");
+  const int NB = b > 16 ? 2 : 1;
+  void *xp = nullptr, *wp = nullptr, *sp = nullptr;
+  auto drop = [&]() { if (xp) hipFree(xp); if (wp) hipFree(wp); if (sp) hipFree(sp); };
+  if (hipMalloc(&xp, (size_t)NB * 16 * K * 2) != hipSuccess || hipMalloc(&wp, (size_t)N * (K / 2)) != hipSuccess ||
+      hipMalloc(&sp, (size_t)N * (K / 32)) != hipSuccess) {
+    (void)hipGetLastError(); drop(); omchat_set_error("hipMalloc failed"); return 2;
+  }
+  int rc = launch_pack_x(dtype, X, ldx, b, K, xp, S(stream));
+  if (rc == 0) rc = launch_pack_w4(W4, (const unsigned char*)S_, N, K, wp, (unsigned char*)sp, S(stream));
+  if (rc == 0) {
+    GemvArgs g{xp, K, wp, K / 2, Y, ldy, b, N, K, bias, nullptr, 0, epi, out_f32, ksplit, 0, nullptr, 1, 1, y_packed};
+    g.mx_scale = (const unsigned char*)sp;
+    rc = launch_gemv(dtype, g, S(stream));
+  }
+  hipStreamSynchronize(S(stream));
+  drop();
+  return rc;
+}
+
+// The pieces of the two packed entries for callers that pack once and launch many times (tools/bench_mxfp4.py times the launch alone): the packers,
+// and the launch on PRE-PACKED operands -- XP from omchat_op_pack_x; WP from omchat_op_pack_w with SP = NULL (16-bit weights), or WP / SP from
+// omchat_op_pack_w4 (MXFP4).  Nothing is allocated or synchronised here.
+extern "C" int omchat_op_pack_w(int dtype, const void* W, int ldw, int N, int K, void* out, void* stream) { return launch_pack_w(dtype, W, ldw, N, K, out, S(stream)); }
+extern "C" int omchat_op_pack_w4(const void* W4, const void* S_, int N, int K, void* W4P, void* SP, void* stream) {
+  return launch_pack_w4(W4, (const unsigned char*)S_, N, K, W4P, (unsigned char*)SP, S(stream));
+}
+extern "C" int omchat_op_gemv_prepacked(int dtype, const void* XP, const void* WP, const void* SP, void* Y, int ldy, int b, int N, int K, const void* bias,
+                                        int epi, int out_f32, int ksplit, int y_packed, void* stream) {
+  OM_CHECK(XP && WP && Y, "null argument");
+  OM_CHECK(b >= 1 && b <= 32 && K >= 64 && K % 64 == 0 && N >= 16 && N % 16 == 0, "pre-packed GEMV: 1 <= b <= 32, K % 64 == 0, N % 16 == 0");
+  GemvArgs g{XP, K, WP, SP ? K / 2 : K, Y, ldy, b, N, K, bias, nullptr, 0, epi, out_f32, ksplit, 0, nullptr, 1, 1, y_packed};
+  g.mx_scale = (const unsigned char*)SP;
+  return launch_gemv(dtype, g, S(stream));
+}
+
 // ... with the preceding RMSNorm in registers (omchat_op_gemv_norm on MXFP4 weights; K <= 4096, epilogue NONE / SWIGLU)
 extern "C" int omchat_op_gemv_mxfp4_norm(int dtype, const void* X, const void* W4, const void* S_, void* Y, int N, int K, const void* norm_w,
                                          float eps, const void* bias, int epi, int out_f32, void* stream) {

@@ -129,6 +129,20 @@ __host__ __device__ __forceinline__ size_t packed_x_index(int row, int k, int NB
 __host__ __device__ __forceinline__ size_t packed_w_index(int row, int k, int K) {
   return ((((size_t)(row >> 4) * (K >> 6) + (k >> 6)) * 2 + ((k >> 5) & 1)) * 64 + (row & 15) + 16 * ((k >> 3) & 3)) * 8 + (k & 7);
 }
+// Packed MXFP4 replica (weights of the same batched forms; gemv.hip WF_MX4, written by launch_pack_w4 only).  The codes follow the packed 16-bit
+// layout with a DWORD (8 codes, the even k in the low nibble) where that has 8 elements; the e8m0 scales of a (tile, chunk) are 32 bytes:
+//   codes  [N/16 tiles][K/64 chunks][2 halves][64 lanes] dwords   lane l holds weight row 16*tile + (l & 15), k = 64*chunk + 32*half + 8*(l >> 4) .. + 7
+//   scales [N/16 tiles][K/64 chunks][4 lane groups][2 halves][4]  bytes   group g, half h, byte r: row 16*tile + 4*g + r, block 2*chunk + h
+// A wave loads the 256 contiguous bytes of a (tile, chunk, half) as one dword per lane, and the 32 contiguous scale bytes of a (tile, chunk) as
+// one aligned 8-byte load per lane (lane group g = l >> 4 reads its own 8): the four rows 4 g .. 4 g + 3 are the rows the lane's MFMA
+// accumulator registers hold, first for half 0, then for half 1.
+// packed_w4_index: dword that holds code (row, k), in nibble k & 7; packed_s4_index: byte of (row, block of 32 k).
+__host__ __device__ __forceinline__ size_t packed_w4_index(int row, int k, int K) {
+  return (((size_t)(row >> 4) * (K >> 6) + (k >> 6)) * 2 + ((k >> 5) & 1)) * 64 + (row & 15) + 16 * ((k >> 3) & 3);
+}
+__host__ __device__ __forceinline__ size_t packed_s4_index(int row, int blk, int K) {
+  return ((((size_t)(row >> 4) * (K >> 6) + (blk >> 1)) * 4 + ((row & 15) >> 2)) * 2 + (blk & 1)) * 4 + (row & 3);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // host side

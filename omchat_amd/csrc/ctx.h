@@ -124,6 +124,15 @@ struct omchat_ctx {
   std::vector<DecLayer4> dl4;
   void* t_lm4 = nullptr; unsigned char* t_lm4_s = nullptr;
   bool mxfp4_decode = false, mxfp4_stale = false;
+  // mode 2 of omchat_enable_mxfp4_decode: the same codes and scales once more in the packed layout of the batched GEMV forms (common.h:
+  // packed_w4_index / packed_s4_index; launch_pack_w4 shuffles the row-major replica, the quantiser stays the one source of the codes).
+  // Steps with 2 <= b <= 32 rows (batched, masked, beam, verify) stream it; built all-or-nothing, re-packed in place after omchat_load_tensor
+  std::vector<DecLayer4> dl4p;
+  void* t_lm4P = nullptr; unsigned char* t_lm4P_s = nullptr;
+  bool mxfp4_batched = false, mxfp4p_stale = false;
+  // the weight format of a decode step of b rows: MXFP4 at b == 1 in both modes, at 2 <= b <= 32 in mode 2
+  bool mx4_rows_ok(int b) const { return !(mxfp4_decode && mxfp4_batched && b > 32); }
+  bool mx4_step(int b) const { return mxfp4_decode && (b == 1 || (mxfp4_batched && b >= 2 && b <= 32)); }
   // BASELINE configs[4]: fp8 KV cache for decode (e4m3 bytes in the layout of the 16-bit cache + one fp32 scale per (layer, sequence,
   // kv head, position)) and fp8 x fp8 MFMA prefill GEMMs (qkv and gate|up: the activations come quantised per token from the RMSNorm)
   void *k8cache = nullptr, *v8cache = nullptr;
@@ -218,6 +227,28 @@ struct omchat_ctx {
     if (e != hipSuccess) { omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e)); return 2; }
     allocs.push_back(*p);
     bytes += n;
+    return 0;
+  }
+  // a group of buffers or none: sizes[i] bytes into *slots[i]; when one hipMalloc fails the ones already taken are freed, nothing is recorded
+  // and every slot is null again (a half-built table must never reach a launch)
+  int alloc_group(const std::vector<void**>& slots, const std::vector<size_t>& sizes) {
+    std::vector<void*> got;
+    size_t total = 0;
+    for (size_t i = 0; i < slots.size(); ++i) {
+      const size_t n = sizes[i] ? sizes[i] : 16;
+      const hipError_t e = hipMalloc(slots[i], n);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* p : got) (void)hipFree(p);
+        for (void** s : slots) *s = nullptr;
+        omchat_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
+        return 2;
+      }
+      got.push_back(*slots[i]);
+      total += n;
+    }
+    for (void* p : got) allocs.push_back(p);
+    bytes += total;
     return 0;
   }
   size_t esz() const { return 2; }

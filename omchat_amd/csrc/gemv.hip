@@ -200,6 +200,47 @@ __global__ __launch_bounds__(GV_WAVES * 64) void gemv_kernel(GemvP p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// MXFP4 weights in the packed batched forms below (WF_MX4; common.h: packed_w4_index / packed_s4_index).  One (tile, chunk, half) unit = 16
+// weight rows x 32 consecutive k = one MX block per row = one A operand of mfma16: a lane's dword holds its 8 codes, four
+// v_cvt_scalef32_pk_{f16,bf16}_fp4 at scale 1 widen them (exact), the MFMA runs from a ZERO C operand, and its four results per lane
+// (weight rows 4 fg + r) are folded into the running fp32 accumulators by 2^e of those rows -- one fmaf each.  The scale stays out of the
+// convert for the reason given at rw_dot8_fp4: folded in, a 2^e near 2^-22 underflows f16.
+// ---------------------------------------------------------------------------------------------------------
+typedef unsigned int rw_u32x2 __attribute__((ext_vector_type(2)));
+// e8m0 byte -> 2^(byte - 127) (byte 0 = 2^-127 is an fp32 subnormal: ldexp, not a shift into the exponent field)
+__device__ __forceinline__ float mx_scale_of(unsigned byte) { return ldexpf(1.0f, (int)byte - 127); }
+template <typename T> __device__ __forceinline__ typename V8<T>::type mx4_frag(unsigned w);
+template <> __device__ __forceinline__ f16x8 mx4_frag<f16>(unsigned w) {
+  const rw_u32x4 v = {__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 0)),
+                      __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 1)),
+                      __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 2)),
+                      __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 3))};
+  return __builtin_bit_cast(f16x8, v);
+}
+template <> __device__ __forceinline__ bf16x8 mx4_frag<bf16>(unsigned w) {
+  const rw_u32x4 v = {__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 0)),
+                      __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 1)),
+                      __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 2)),
+                      __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, 3))};
+  return __builtin_bit_cast(bf16x8, v);
+}
+// the four e8m0 bytes of weight rows 4 fg .. 4 fg + 3 (one aligned dword) -> 2^e
+__device__ __forceinline__ void mx4_scales(unsigned s4, float (&sc)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) sc[r] = mx_scale_of((s4 >> (8 * r)) & 0xffu);
+}
+// acc += 2^e (rows) * (A x): one unit against one batch tile
+template <typename F>
+__device__ __forceinline__ f32x4 mx4_fold(F a, F x, const float (&sc)[4], f32x4 acc) {
+  const f32x4 t = mfma16(a, x, (f32x4){0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = fmaf(t[r], sc[r], acc[r]);
+  return acc;
+}
+// a wave's registers for one MXFP4 weight tile over its NCH chunks (x-stationary forms): the codes per half, the 2 x 4 scale bytes of a chunk
+template <int NCH> struct XsMx4 { unsigned c[NCH][2]; rw_u32x2 s[NCH]; };
+
 
 // ---------------------------------------------------------------------------------------------------------
 // Batched decode (2 <= b <= 32) with PACKED operands (common.h: packed_x_index / packed_w_index).  The kernel above loads
@@ -228,9 +269,11 @@ __global__ __launch_bounds__(GV_WAVES * 64) void gemv_kernel(GemvP p) {
 // precedes the projection (transformers modeling_qwen2.py:247-252) runs here, on the registers that keep x for the whole launch: per-row sum
 // of squares over the wave's chunks, over the four lanes of a row and over the eight waves (LDS), then T(T(x * rstd) * w) with the reference's
 // two roundings.  Every workgroup repeats it (x is read by every workgroup anyway); the residual + RMSNorm launch in front of gate|up goes away.
-template <typename T, int EPI, int NB, int NCH, bool NORM = false>
+template <typename T, int EPI, int NB, int NCH, bool NORM = false, int WF = WF_16>
 __device__ __forceinline__ void gemv_xs_body(const GemvP& p, float (&red)[2][8][NB][256], int c_base, int slice) {
   typedef typename V8<T>::type frag_t;
+  static_assert(WF == WF_16 || (WF == WF_MX4 && !NORM && EPI != EPI_RESID), "MXFP4: the plain, SwiGLU and split-K epilogues");
+  typedef typename std::conditional<WF == WF_MX4, XsMx4<NCH>, frag_t[NCH][2]>::type wtile_t;
   constexpr int WAVES = 8;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
@@ -297,12 +340,24 @@ __device__ __forceinline__ void gemv_xs_body(const GemvP& p, float (&red)[2][8][
       }
     }
   }
-  auto load_w = [&](frag_t (&wf)[NCH][2], int tile) {
-    const T* base = W + ((size_t)tile * nchunk_all + c_base) * 1024 + lane * 8;
+  auto load_w = [&](wtile_t& wf, int tile) {
+    if constexpr (WF == WF_MX4) {
+      // (tile, chunk): 2 x 64 code dwords, 4 x 8 scale bytes (lane group fg: half 0 rows 4 fg .. 4 fg + 3, then half 1)
+      const unsigned* cb = (const unsigned*)p.W + ((size_t)tile * nchunk_all + c_base) * 128 + lane;
+      const rw_u32x2* sb = (const rw_u32x2*)p.mx_s + ((size_t)tile * nchunk_all + c_base) * 4 + fg;
 #pragma unroll
-    for (int i = 0; i < NCH; ++i)
+      for (int i = 0; i < NCH; ++i) {
 #pragma unroll
-      for (int h = 0; h < 2; ++h) wf[i][h] = __builtin_nontemporal_load(reinterpret_cast<const frag_t*>(base + (size_t)(wave + WAVES * i) * 1024 + h * 512));
+        for (int h = 0; h < 2; ++h) wf.c[i][h] = __builtin_nontemporal_load(cb + (size_t)(wave + WAVES * i) * 128 + h * 64);
+        wf.s[i] = __builtin_nontemporal_load(sb + (size_t)(wave + WAVES * i) * 4);
+      }
+    } else {
+      const T* base = W + ((size_t)tile * nchunk_all + c_base) * 1024 + lane * 8;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) wf[i][h] = __builtin_nontemporal_load(reinterpret_cast<const frag_t*>(base + (size_t)(wave + WAVES * i) * 1024 + h * 512));
+    }
   };
   // j-th tile of this workgroup: SwiGLU walks (gate, up) pairs, the others single tiles
   const int n_units = EPI == EPI_SWIGLU ? n_tiles >> 1 : n_tiles;
@@ -325,18 +380,31 @@ __device__ __forceinline__ void gemv_xs_body(const GemvP& p, float (&red)[2][8][
     return tof(rsrc[has_res ? (size_t)(bi < p.b ? bi : 0) * p.ldr + (n < p.N ? n : p.N - 1) : 0]);
   };
   float bias_a = 0.f, bias_b = 0.f;
-  auto finish = [&](frag_t (&wf)[NCH][2], int j, float bias_v) {
+  auto finish = [&](wtile_t& wf, int j, float bias_v) {
     const int tile = tile_of(j), par = j & 1;
     f32x4 acc[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if constexpr (WF == WF_MX4) {
 #pragma unroll
-    for (int i = 0; i < NCH; ++i)
+      for (int i = 0; i < NCH; ++i)
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        acc[nb] = mfma16(wf[i][0], xf[i][nb][0], acc[nb]);
-        acc[nb] = mfma16(wf[i][1], xf[i][nb][1], acc[nb]);
-      }
+        for (int h = 0; h < 2; ++h) {
+          float sc[4];
+          mx4_scales(h ? wf.s[i].y : wf.s[i].x, sc);
+          const frag_t a = mx4_frag<T>(wf.c[i][h]);
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) acc[nb] = mx4_fold(a, xf[i][nb][h], sc, acc[nb]);
+        }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          acc[nb] = mfma16(wf[i][0], xf[i][nb][0], acc[nb]);
+          acc[nb] = mfma16(wf[i][1], xf[i][nb][1], acc[nb]);
+        }
+    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -373,7 +441,7 @@ __device__ __forceinline__ void gemv_xs_body(const GemvP& p, float (&red)[2][8][
       }
     }
   };
-  frag_t wa[NCH][2], wb[NCH][2];
+  wtile_t wa, wb;
   auto pre_of = [&](int j) { if constexpr (EPI == EPI_RESID) return res_of(j); else return bias_of(j); };
   if (my_tiles > 0) { load_w(wa, tile_of(0)); bias_a = pre_of(0); }
   for (int j = 0; j < my_tiles; j += 2) {
@@ -403,10 +471,25 @@ __global__ __launch_bounds__(512) void gemv_xs_split_kernel(GemvP p, int n5) {
   else gemv_xs_body<T, EPI_PARTIAL, NB, 2>(p, red, n5 * 40 + (y - n5) * 16, y);
 }
 
-template <typename T, int NTILE, int EPI, int WAVES, int UNROLL, int NB, bool WPACK>
-__global__ __launch_bounds__(WAVES * 64) void gemv_pk_kernel(GemvP p) {
+// the same two forms on the packed MXFP4 replica (same launch shapes, same chunk -> wave deal, same reduction order)
+template <typename T, int EPI, int NB, int NCH>
+__global__ __launch_bounds__(512) void gemv_xs_mx4_kernel(GemvP p) {
+  __shared__ float red[2][8][NB][256];
+  gemv_xs_body<T, EPI, NB, NCH, false, WF_MX4>(p, red, 0, 0);
+}
+template <typename T, int NB>
+__global__ __launch_bounds__(512) void gemv_xs_split_mx4_kernel(GemvP p, int n5) {
+  __shared__ float red[2][8][NB][256];
+  const int y = blockIdx.y;
+  if (y < n5) gemv_xs_body<T, EPI_PARTIAL, NB, 5, false, WF_MX4>(p, red, y * 40, y);
+  else gemv_xs_body<T, EPI_PARTIAL, NB, 2, false, WF_MX4>(p, red, n5 * 40 + (y - n5) * 16, y);
+}
+
+template <typename T, int NTILE, int EPI, int WAVES, int UNROLL, int NB, bool WPACK, int WF>
+__device__ __forceinline__ void gemv_pk_body(const GemvP p, float (&red)[WAVES][NTILE * NB][256]) {
   typedef typename V8<T>::type frag_t;
-  __shared__ float red[WAVES][NTILE * NB][256];
+  static_assert(WF == WF_16 || (WF == WF_MX4 && WPACK), "MXFP4: the packed replica only");
+  typedef typename std::conditional<WF == WF_MX4, unsigned, frag_t>::type wreg_t;      // a lane's 8 weights of one (chunk, half)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int tile0 = blockIdx.x * NTILE;
@@ -416,10 +499,15 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_pk_kernel(GemvP p) {
 
   const T* W = (const T*)p.W;
   const T* wbase[NTILE];
+  const unsigned* cbase[NTILE];          // MXFP4: (tile, chunk) = 2 x 64 code dwords, 4 x 8 scale bytes (lane group fg: half 0's four rows, then half 1's)
+  const rw_u32x2* sbase[NTILE];
 #pragma unroll
   for (int t = 0; t < NTILE; ++t) {
     const int tl = tile0 + t < n_tiles ? tile0 + t : n_tiles - 1;
-    if constexpr (WPACK) wbase[t] = W + (size_t)tl * nchunk_all * 1024 + lane * 8;
+    if constexpr (WF == WF_MX4) {
+      cbase[t] = (const unsigned*)p.W + (size_t)tl * nchunk_all * 128 + lane;
+      sbase[t] = (const rw_u32x2*)p.mx_s + (size_t)tl * nchunk_all * 4 + fg;
+    } else if constexpr (WPACK) wbase[t] = W + (size_t)tl * nchunk_all * 1024 + lane * 8;
     else { int r = tl * 16 + fr; r = r < p.N ? r : p.N - 1; wbase[t] = W + (size_t)r * p.ldw + fg * 8; }
   }
   const T* xbase = (const T*)p.X + lane * 8;
@@ -436,17 +524,26 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_pk_kernel(GemvP p) {
     for (int nb = 0; nb < NB; ++nb) acc[t][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   for (int c0 = c_lo + wave * UNROLL; c0 < c_hi; c0 += WAVES * UNROLL) {
-    frag_t wf[UNROLL][NTILE][2], xf[UNROLL][NB][2];
+    wreg_t wf[UNROLL][NTILE][2];
+    frag_t xf[UNROLL][NB][2];
+    rw_u32x2 ws[UNROLL][NTILE];                                 // MXFP4: the 2 x 4 scale bytes of (tile, chunk) for this lane group
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const int c = c0 + u < c_hi ? c0 + u : c_hi - 1;          // ragged last group: re-load the last chunk, skip its MFMAs below
 #pragma unroll
-      for (int t = 0; t < NTILE; ++t)
+      for (int t = 0; t < NTILE; ++t) {
+        if constexpr (WF == WF_MX4) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const T* q = WPACK ? wbase[t] + (size_t)c * 1024 + h * 512 : wbase[t] + c * 64 + h * 32;
-          wf[u][t][h] = __builtin_nontemporal_load(reinterpret_cast<const frag_t*>(q));
+          for (int h = 0; h < 2; ++h) wf[u][t][h] = __builtin_nontemporal_load(cbase[t] + (size_t)c * 128 + h * 64);
+          ws[u][t] = __builtin_nontemporal_load(sbase[t] + (size_t)c * 4);
+        } else {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const T* q = WPACK ? wbase[t] + (size_t)c * 1024 + h * 512 : wbase[t] + c * 64 + h * 32;
+            wf[u][t][h] = __builtin_nontemporal_load(reinterpret_cast<const frag_t*>(q));
+          }
         }
+      }
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -460,13 +557,26 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_pk_kernel(GemvP p) {
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       if (c0 + u < c_hi) {                                      // wave-uniform
+        if constexpr (WF == WF_MX4) {
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
+          for (int t = 0; t < NTILE; ++t)
 #pragma unroll
-          for (int t = 0; t < NTILE; ++t) {
-            acc[t][nb] = mfma16(wf[u][t][0], xf[u][nb][0], acc[t][nb]);
-            acc[t][nb] = mfma16(wf[u][t][1], xf[u][nb][1], acc[t][nb]);
-          }
+            for (int h = 0; h < 2; ++h) {
+              float sc[4];
+              mx4_scales(h ? ws[u][t].y : ws[u][t].x, sc);
+              const frag_t a = mx4_frag<T>(wf[u][t][h]);
+#pragma unroll
+              for (int nb = 0; nb < NB; ++nb) acc[t][nb] = mx4_fold(a, xf[u][nb][h], sc, acc[t][nb]);
+            }
+        } else {
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int t = 0; t < NTILE; ++t) {
+              acc[t][nb] = mfma16(wf[u][t][0], xf[u][nb][0], acc[t][nb]);
+              acc[t][nb] = mfma16(wf[u][t][1], xf[u][nb][1], acc[t][nb]);
+            }
+        }
       }
     }
   }
@@ -523,6 +633,17 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_pk_kernel(GemvP p) {
   }
 }
 
+template <typename T, int NTILE, int EPI, int WAVES, int UNROLL, int NB, bool WPACK>
+__global__ __launch_bounds__(WAVES * 64) void gemv_pk_kernel(GemvP p) {
+  __shared__ float red[WAVES][NTILE * NB][256];
+  gemv_pk_body<T, NTILE, EPI, WAVES, UNROLL, NB, WPACK, WF_16>(p, red);
+}
+template <typename T, int NTILE, int EPI, int WAVES, int UNROLL, int NB>
+__global__ __launch_bounds__(WAVES * 64) void gemv_pk_mx4_kernel(GemvP p) {
+  __shared__ float red[WAVES][NTILE * NB][256];
+  gemv_pk_body<T, NTILE, EPI, WAVES, UNROLL, NB, true, WF_MX4>(p, red);
+}
+
 // row-major -> packed (model load time / tests)
 template <typename T>
 __global__ void pack_x_kernel(const T* X, int ldx, int b, int K, T* out, int NB) {
@@ -551,6 +672,22 @@ __global__ void pack_w_kernel(const T* W, int ldw, int N, int K, T* out) {
     st8<T>(out + piece * 8, ld8<T>(W + (size_t)row * ldw + k));
   }
 }
+// row-major MXFP4 replica (W4 [N][K / 2] bytes, S [N][K / 32] e8m0 bytes) -> the packed one (common.h: packed_w4_index / packed_s4_index): a
+// byte shuffle, the quantiser stays the single source of the codes.  Thread i writes code dword i of the packed image and moves scale byte i.
+__global__ void pack_w4_kernel(const unsigned char* W4, const unsigned char* S, int N, int K, unsigned* W4P, unsigned char* SP) {
+  const long n8 = (long)N * (K >> 3), ns = (long)N * (K >> 5);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    const int lane = (int)(i & 63), half = (int)((i >> 6) & 1);
+    const long tc = i >> 7;
+    const int chunk = (int)(tc % (K >> 6)), tile = (int)(tc / (K >> 6));
+    const int row = tile * 16 + (lane & 15), k = chunk * 64 + half * 32 + (lane >> 4) * 8;
+    W4P[i] = *reinterpret_cast<const unsigned*>(W4 + (size_t)row * (K >> 1) + (k >> 1));
+    if (i < ns) {
+      const int srow = (int)(i / (K >> 5)), blk = (int)(i % (K >> 5));
+      SP[packed_s4_index(srow, blk, K)] = S[i];
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // b = 1: whole-row streaming + packed dot products.  Measured on MI355X (tools/experiments/tune_rowdot.hip): 6.5-6.8 TB/s on the
@@ -570,7 +707,6 @@ constexpr int RW_MAXC = 8;
 // weight-only fp8 (OCP e4m3): 8 weights of a lane = 8 bytes.  gfx950's v_cvt_scalef32_pk_{bf16,f16}_fp8 widens two e4m3
 // values to a packed 16-bit pair in one instruction (exact: 3 mantissa bits), which then feeds the same v_dot2 as the
 // 16-bit kernel with x still packed in registers: 4 converts + 4 dot2 per 8 weights.
-typedef unsigned int rw_u32x2 __attribute__((ext_vector_type(2)));
 template <typename T> __device__ __forceinline__ float rw_dot8_fp8(rw_u32x2 w, rw_u32x4 x, float acc);
 template <> __device__ __forceinline__ float rw_dot8_fp8<bf16>(rw_u32x2 w, rw_u32x4 x, float acc) {
   typedef bf16 v2 __attribute__((ext_vector_type(2)));
@@ -617,8 +753,7 @@ template <> __device__ __forceinline__ float rw_dot8_fp4<f16>(unsigned w, rw_u32
   acc = __builtin_amdgcn_fdot2(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 3), __builtin_bit_cast(v2, x3), acc, false);
   return acc;
 }
-// e8m0 byte -> 2^(byte - 127) (byte 0 = 2^-127 is an fp32 subnormal: ldexp, not a shift into the exponent field)
-__device__ __forceinline__ float mx_scale_of(unsigned byte) { return ldexpf(1.0f, (int)byte - 127); }
+// (mx_scale_of, the e8m0 byte -> 2^(byte - 127), is defined with the packed batched forms above)
 
 // registers of a lane's 8 weights per format, their (non-temporal) load at element k of weight row `row`, and their dot product with 8 x
 template <int WF> struct RwW { typedef rw_u32x4 type; };
@@ -1654,13 +1789,19 @@ int launch_t(const GemvArgs& a, hipStream_t s) {
 #define OM_PK(NT_, EPI_, WV_, UN_)                                                                                                  \
   do {                                                                                                                              \
     const dim3 grid(cdiv(cdiv(a.N, 16), NT_), ks);                                                                                  \
-    if (a.b > 16) { if (a.w_packed) hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 2, true>), grid, dim3(WV_ * 64), 0, s, p);   \
+    if (a.mx_scale) { if (a.b > 16) hipLaunchKernelGGL((gemv_pk_mx4_kernel<T, NT_, EPI_, WV_, UN_, 2>), grid, dim3(WV_ * 64), 0, s, p);     \
+                      else hipLaunchKernelGGL((gemv_pk_mx4_kernel<T, NT_, EPI_, WV_, UN_, 1>), grid, dim3(WV_ * 64), 0, s, p); }             \
+    else if (a.b > 16) { if (a.w_packed) hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 2, true>), grid, dim3(WV_ * 64), 0, s, p);   \
                     else hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 2, false>), grid, dim3(WV_ * 64), 0, s, p); }            \
     else { if (a.w_packed) hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 1, true>), grid, dim3(WV_ * 64), 0, s, p);            \
            else hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 1, false>), grid, dim3(WV_ * 64), 0, s, p); }                     \
   } while (0)
     // long launches with K = 64 * 8 * 7 (= 3584: gate|up, lm_head): x-stationary persistent form, one workgroup per CU, >= 4 units each
     const int n_cu = device_cus();
+    if (a.mx_scale && (a.norm_w || a.epi == EPI_RESID)) {
+      omchat_set_error("launch_gemv: the batched norm-in-GEMV / residual forms read 16-bit weights only (no MXFP4 instantiation)");
+      return 1;
+    }
     // (units = what one workgroup walks: (gate, up) tile pairs or single tiles; fewer than 4 per workgroup leaves the last round too empty)
 #if !OMCHAT_EXPERIMENTS
     // the seven-launch batched layer (un-split o_proj + residual, RMSNorm in the gate|up GEMV's registers; round 5) measured SLOWER than the eight
@@ -1690,7 +1831,15 @@ int launch_t(const GemvArgs& a, hipStream_t s) {
         else hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 1, 7, true>), grid, dim3(512), 0, s, p);
       } else
 #endif
-      if (a.epi == EPI_SWIGLU) {
+      if (a.mx_scale) {
+        if (a.epi == EPI_SWIGLU) {
+          if (a.b > 16) hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_SWIGLU, 2, 7>), grid, dim3(512), 0, s, p);
+          else hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_SWIGLU, 1, 7>), grid, dim3(512), 0, s, p);
+        } else {
+          if (a.b > 16) hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_NONE, 2, 7>), grid, dim3(512), 0, s, p);
+          else hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_NONE, 1, 7>), grid, dim3(512), 0, s, p);
+        }
+      } else if (a.epi == EPI_SWIGLU) {
         if (a.b > 16) hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 2, 7>), grid, dim3(512), 0, s, p);
         else hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 1, 7>), grid, dim3(512), 0, s, p);
       } else {
@@ -1713,7 +1862,10 @@ int launch_t(const GemvArgs& a, hipStream_t s) {
       if (tiles < 4 * gx && tiles % 2 == 0 && (long)tiles * ks >= n_cu2 && (long)tiles * ks <= 2L * n_cu2) gx = tiles / 2;
       if (a5 >= 0 && (tiles >= 4 * gx || gx == tiles / 2)) {
         const dim3 grid(gx, ks);
-        if (a.b > 16) hipLaunchKernelGGL((gemv_xs_split_kernel<T, 2>), grid, dim3(512), 0, s, p, a5);
+        if (a.mx_scale) {
+          if (a.b > 16) hipLaunchKernelGGL((gemv_xs_split_mx4_kernel<T, 2>), grid, dim3(512), 0, s, p, a5);
+          else hipLaunchKernelGGL((gemv_xs_split_mx4_kernel<T, 1>), grid, dim3(512), 0, s, p, a5);
+        } else if (a.b > 16) hipLaunchKernelGGL((gemv_xs_split_kernel<T, 2>), grid, dim3(512), 0, s, p, a5);
         else hipLaunchKernelGGL((gemv_xs_split_kernel<T, 1>), grid, dim3(512), 0, s, p, a5);
         OM_LAUNCH_CHECK();
         return 0;
@@ -1904,6 +2056,17 @@ int launch_pack_x(int dtype, const void* X, int ldx, int b, int K, void* out, hi
   return 0;
 }
 
+int launch_pack_w4(const void* W4, const unsigned char* S, int N, int K, void* W4P, unsigned char* SP, hipStream_t s) {
+  OM_CHECK(W4 && S && W4P && SP, "null argument");
+  OM_CHECK(N >= 16 && N % 16 == 0, "pack_w4: N % 16 == 0 (16-row weight tiles)");
+  OM_CHECK(K >= 64 && K % 64 == 0, "pack_w4: K % 64 == 0 (64-wide K chunks)");
+  const long n8 = (long)N * (K / 8);
+  const int grid = (int)(cdiv64(n8, 256) > 8192 ? 8192 : cdiv64(n8, 256));
+  hipLaunchKernelGGL(pack_w4_kernel, dim3(grid), dim3(256), 0, s, (const unsigned char*)W4, S, N, K, (unsigned*)W4P, SP);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_pack_w(int dtype, const void* W, int ldw, int N, int K, void* out, hipStream_t s) {
   OM_CHECK(N % 16 == 0 && K % 64 == 0 && ldw % 8 == 0, "pack_w: N % 16, K % 64, ldw % 8");
   const long n8 = (long)N * (K / 8);
@@ -1993,13 +2156,14 @@ int launch_gemv_wait(int dtype, const GemvArgs& a, const unsigned* flags, unsign
 
 int launch_gemv(int dtype, const GemvArgs& a, hipStream_t s) {
   OM_CHECK(a.b >= 1 && a.b <= 32, "batch must be 1..32 per call");
-  OM_CHECK(!a.x_packed || (!a.w_scale && !a.mx_scale), "packed x: 16-bit weights");
+  OM_CHECK(!a.x_packed || !a.w_scale, "packed x: 16-bit or MXFP4 weights");
+  OM_CHECK(!(a.x_packed && a.mx_scale) || (a.w_packed && a.K % 64 == 0), "packed x with MXFP4 weights: the packed MXFP4 replica (w_packed), K % 64 == 0");
   OM_CHECK(!(a.w_scale && a.mx_scale), "one weight format per launch: e4m3 (w_scale) or MXFP4 (mx_scale)");      // (EPI_RESID: x-stationary form only, checked in launch_t)
   OM_CHECK(!a.w_packed || (a.x_packed && a.N % 16 == 0), "packed W needs packed x and N % 16 == 0");
   OM_CHECK(!a.y_packed || (a.x_packed && a.epi == EPI_SWIGLU), "packed y: SwiGLU epilogue of the packed kernel only");
   if (a.mx_scale) OM_CHECK(a.K % 32 == 0 && a.ldw % 4 == 0 && a.ldx % 8 == 0, "MXFP4 weights: K % 32 == 0 (one e8m0 scale per 32 k), ldw (bytes) % 4, ldx % 8");
   else OM_CHECK(a.K % 64 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0, "K % 64, ldw % 8, ldx % 8");
-  OM_CHECK((!a.w_scale && !a.mx_scale) || a.b == 1, "fp8 / MXFP4 weights: batch 1 only");
+  OM_CHECK((!a.w_scale && !(a.mx_scale && !a.x_packed)) || a.b == 1, "fp8 / MXFP4 weights: batch 1 only (MXFP4 at b > 1: packed x and the packed MXFP4 replica)");
   OM_CHECK(a.epi == EPI_NONE || a.epi == EPI_RESID || a.epi == EPI_SWIGLU || a.epi == EPI_PARTIAL, "bad epilogue");
   OM_CHECK(a.ksplit <= 1 || a.epi == EPI_PARTIAL, "ksplit > 1 only with EPI_PARTIAL (fp32 slices)");
   OM_CHECK(a.ksplit <= (a.K + 63) / 64, "ksplit exceeds the number of 64-wide K chunks");

@@ -114,12 +114,17 @@ struct GemvArgs {
   // experiments build, measurement only: 8 x 64-bit clock stamps of this launch's layer (see model.hip dbg_stamps)
   unsigned long long* dbg = nullptr;
   // non-null: W is MXFP4 -- [N][ldw] bytes (ldw >= K / 2) of two OCP e2m1 codes each, the even k in the low nibble -- and mx_scale [N][K / 32]
-  // holds one e8m0 byte per 32 consecutive k (weight-only, b == 1 only, K % 32 == 0); not together with w_scale
+  // holds one e8m0 byte per 32 consecutive k (weight-only, b == 1 only, K % 32 == 0); not together with w_scale.
+  // With x_packed && w_packed (1 <= b <= 32, K % 64 == 0, N % 16 == 0): W / mx_scale are the PACKED MXFP4 replica that launch_pack_w4 writes
+  // (common.h: packed_w4_index / packed_s4_index; ldw ignored) and the packed batched forms run on it; epilogues NONE / SWIGLU / PARTIAL
   const unsigned char* mx_scale = nullptr;
 };
 // row-major [rows <= 32][K] -> packed x (tests, tools); row-major W [N][ldw] -> packed replica (N % 16 == 0)
 int launch_pack_x(int dtype, const void* X, int ldx, int b, int K, void* out, hipStream_t s);
 int launch_pack_w(int dtype, const void* W, int ldw, int N, int K, void* out, hipStream_t s);
+// row-major MXFP4 (W4 [N][K / 2] bytes, S [N][K / 32] e8m0 bytes: what launch_quant_mxfp4_rows writes) -> packed replica W4P (N K / 2 bytes),
+// SP (N K / 32 bytes); a byte shuffle.  N % 16 == 0, K % 64 == 0
+int launch_pack_w4(const void* W4, const unsigned char* S, int N, int K, void* W4P, unsigned char* SP, hipStream_t s);
 int launch_gemv(int dtype, const GemvArgs& a, hipStream_t stream);
 // experiments build (tuning key 42): the batch-1 o_proj GEMV launched out of order behind the split-KV merge, waiting on its per-head completion flags
 int launch_gemv_wait(int dtype, const GemvArgs& a, const unsigned* flags, unsigned epoch, int nflags, unsigned* err, int mode, hipStream_t s);

@@ -351,6 +351,7 @@ extern "C" int omchat_load_tensor(omchat_ctx* ctx, const char* name, const void*
   }
   if (!ctx->dl8.empty()) ctx->fp8_stale = true;      // the e4m3 replica no longer matches the 16-bit weights
   if (!ctx->dl4.empty()) ctx->mxfp4_stale = true;    // nor does the MXFP4 replica
+  if (!ctx->dl4p.empty()) ctx->mxfp4p_stale = true;  // nor its packed twin
   ctx->pk_ready = false;                              // nor does the packed replica
   if (src_dtype == ctx->dt) return place(ctx, r, data);
   OM_CHECK(src_dtype == OMCHAT_F32, "source dtype must be the context dtype or OMCHAT_F32");
@@ -903,7 +904,8 @@ static int lm_head_rows(omchat_ctx* ctx, const void* hidden, int n, float* logit
     if (mx4 && n == 1) { g.W = ctx->t_lm4; g.ldw = H / 2; g.mx_scale = ctx->t_lm4_s; }
     if (packed) {          // hidden is in the packed x layout (n <= 32)
       g.x_packed = 1;
-      if (ctx->pk_ready) { g.W = ctx->t_lmP; g.w_packed = 1; }
+      if (mx4) { g.W = ctx->t_lm4P; g.ldw = H / 2; g.mx_scale = ctx->t_lm4P_s; g.w_packed = 1; }      // mode 2: the packed MXFP4 replica
+      else if (ctx->pk_ready) { g.W = ctx->t_lmP; g.w_packed = 1; }
     }
     TRY(launch_gemv(ctx->dt, g, s));
   }
@@ -949,7 +951,9 @@ extern "C" int omchat_enable_fp8_decode(omchat_ctx* ctx, int on) {
 
 // MXFP4 replica of the decode-streamed weights: built once, re-quantised in place (same device pointers: a captured graph stays valid) after
 // omchat_load_tensor
-static int ensure_mxfp4_weights(omchat_ctx* ctx) {
+// packed: also (re)build the packed twin that steps of 2 <= b <= 32 rows stream in mode 2 -- a byte shuffle of the row-major replica, which is
+// therefore brought up to date first.  Its buffers are taken all or nothing: a half-built table must never reach a launch.
+static int ensure_mxfp4_weights(omchat_ctx* ctx, bool packed = false) {
   const omchat_config& c = ctx->c;
   if (ctx->dl4.empty() || ctx->mxfp4_stale) {
     OM_CHECK(omchat_weights_missing(ctx) == 0, "load the weights before quantising them");
@@ -974,17 +978,63 @@ static int ensure_mxfp4_weights(omchat_ctx* ctx) {
     OM_HIP(hipDeviceSynchronize());
     ctx->mxfp4_stale = false;
   }
+  if (packed && (ctx->dl4p.empty() || ctx->mxfp4p_stale)) {
+    const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim, V = c.t_vocab;
+    if (ctx->dl4p.empty()) {
+      std::vector<omchat_ctx::DecLayer4> fresh(c.t_layers);
+      void* lmP = nullptr; unsigned char* lmS = nullptr;
+      std::vector<void**> slots;
+      std::vector<size_t> sizes;
+      auto want = [&](void** w, unsigned char** sc, int N, int K) {
+        slots.push_back(w); sizes.push_back((size_t)N * (K / 2));
+        slots.push_back((void**)sc); sizes.push_back((size_t)N * (K / 32));
+      };
+      for (auto& P : fresh) { want(&P.wqkv, &P.sqkv, qkvd, H); want(&P.wo, &P.so, H, qd); want(&P.wgu, &P.sgu, 2 * It, H); want(&P.wd, &P.sd, H, It); }
+      want(&lmP, &lmS, V, H);
+      if (ctx->alloc_group(slots, sizes)) {
+        omchat_set_error("omchat_enable_mxfp4_decode: the packed MXFP4 replica of mode 2 does not fit in device memory (hipMalloc failed)");
+        return 2;
+      }
+      ctx->dl4p.swap(fresh);
+      ctx->t_lm4P = lmP; ctx->t_lm4P_s = lmS;
+    }
+    for (int i = 0; i < c.t_layers; ++i) {
+      auto& Q = ctx->dl4[i]; auto& P = ctx->dl4p[i];
+      TRY(launch_pack_w4(Q.wqkv, Q.sqkv, qkvd, H, P.wqkv, P.sqkv, nullptr));
+      TRY(launch_pack_w4(Q.wo, Q.so, H, qd, P.wo, P.so, nullptr));
+      TRY(launch_pack_w4(Q.wgu, Q.sgu, 2 * It, H, P.wgu, P.sgu, nullptr));
+      TRY(launch_pack_w4(Q.wd, Q.sd, H, It, P.wd, P.sd, nullptr));
+    }
+    TRY(launch_pack_w4(ctx->t_lm4, ctx->t_lm4_s, V, H, ctx->t_lm4P, ctx->t_lm4P_s, nullptr));
+    OM_HIP(hipDeviceSynchronize());
+    ctx->mxfp4p_stale = false;
+  }
+  return 0;
+}
+// a weight reload (omchat_load_tensor) leaves the replicas stale: rebuild IN PLACE before a step streams them
+static int refresh_mxfp4_weights(omchat_ctx* ctx) {
+  if (ctx->mxfp4_decode && (ctx->mxfp4_stale || (ctx->mxfp4_batched && ctx->mxfp4p_stale))) TRY(ensure_mxfp4_weights(ctx, ctx->mxfp4_batched));
   return 0;
 }
 
-extern "C" int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int on) {
+// mode: 0 = off, 1 = batch-1 steps stream the MXFP4 replica, 2 = steps of 2 <= b <= 32 rows as well (the packed replica)
+extern "C" int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int mode) {
   OM_CHECK(ctx, "null context");
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
-  if (!on) { ctx->mxfp4_decode = false; return 0; }
+  OM_CHECK(mode >= 0 && mode <= 2, "mode: 0 = off, 1 = batch-1 steps, 2 = steps of up to 32 rows as well");
+  if (!mode) { ctx->mxfp4_decode = false; ctx->mxfp4_batched = false; return 0; }
   OM_CHECK(!ctx->fp8_decode, "fp8 decode is on: one weight format per step (omchat_enable_fp8_decode(ctx, 0) first)");
   OM_CHECK(ctx->tp_size == 1, "MXFP4 decode under tensor parallelism is not implemented");
-  TRY(ensure_mxfp4_weights(ctx));
+  if (mode == 2) {
+    const omchat_config& c = ctx->c;
+    OM_CHECK(c.t_hidden % 64 == 0 && ctx->t_qdim % 64 == 0 && c.t_mlp % 64 == 0,
+             "MXFP4 decode mode 2: the packed path needs hidden_size, heads x 128 and intermediate_size each a multiple of 64");
+    OM_CHECK(ctx->t_qkvdim % 16 == 0 && c.t_hidden % 16 == 0 && c.t_vocab % 16 == 0,
+             "MXFP4 decode mode 2: the packed path needs the qkv width, hidden_size and vocab_size each a multiple of 16");
+  }
+  TRY(ensure_mxfp4_weights(ctx, mode == 2));
   ctx->mxfp4_decode = true;
+  ctx->mxfp4_batched = mode == 2;
   return 0;
 }
 
@@ -1268,6 +1318,10 @@ static int ensure_packed(omchat_ctx* ctx) {
   return 0;
 }
 
+// mode 2 of the MXFP4 decode: one weight format per generation, so a step that the packed forms cannot take (b > 32) is refused by the step
+// entries before they touch any state or enqueue anything, never run on 16 bits
+static const char* const MX4_ROWS_MSG = "MXFP4 decode mode 2 streams steps of at most 32 rows (omchat_enable_mxfp4_decode(ctx, 0 or 1) first)";
+
 // One decode step on stream s.  Lmax = upper bound of the key count (sizes the split-KV grid; the kernels read the true
 // lengths from d_len).  Every argument is a context pointer or a step-invariant scalar when called for graph capture.
 // exact_len: every sequence holds exactly Lmax keys after this step (eager launches only): the attention launches then take the length
@@ -1284,20 +1338,27 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   TRY(launch_gather_rows(ctx->dt, tokens, ctx->t_embed, nullptr, x, b, H, s));      // embed_tokens
   // weight-only fp8 replica (omchat_enable_fp8_decode): batch-1 steps stream e4m3 bytes + per-row scales
   const bool f8 = ctx->fp8_decode && b == 1;      // under tensor parallelism every rank streams the e4m3 replica of its own shard (round 3)
-  // weight-only MXFP4 replica (omchat_enable_mxfp4_decode): batch-1 steps stream e2m1 codes + e8m0 block scales; never together with f8
-  const bool mx4 = ctx->mxfp4_decode && b == 1;
+  // weight-only MXFP4 replica (omchat_enable_mxfp4_decode): batch-1 steps stream e2m1 codes + e8m0 block scales; never together with f8.
+  // Mode 2: steps of 2 <= b <= 32 rows stream the PACKED replica through the packed batched forms (the activations arrive packed already)
+  const bool mx4 = ctx->mx4_step(b);
   const bool wq = f8 || mx4;      // a quantised replica is streamed: the launches that exist for 16-bit weights only stay out
   // batched steps (2 <= b <= 32): the activations that feed a GEMV (tw_xn, tw_ao, tw_act) are produced in the packed x layout
   // (common.h) by their producers, and the weights come from the packed replica when it exists (ensure_packed)
   const int pk = (b > 1 && b <= 32 && H % 64 == 0 && qd % 64 == 0 && It % 64 == 0) ? (b > 16 ? 2 : 1) : 0;
   const bool wpk = pk && ctx->pk_ready;
+  const bool mpk = pk && mx4;      // (mode 2 is refused for a geometry without pk: b >= 2 with mx4 implies pk)
+  OM_CHECK(!mx4 || b == 1 || mpk, "MXFP4 decode mode 2: geometry outside the packed path");
   static const omchat_ctx::DecLayerP noneP{};
   auto gemv_args = [&](const void* X, int ldx, const void* W, int K, void* Y, int ldy, int R, int N, const void* bias, const void* resid, int epi,
                        int ks, const void* W8, const float* sc, const void* WP, bool ypk, const void* W4 = nullptr, const unsigned char* s4 = nullptr) {
     GemvArgs g{X, ldx, W, K, Y, ldy, R, N, K, bias, resid, H, epi, 0, ks};
     if (f8 && W8) { g.W = W8; g.w_scale = sc; }
     if (mx4 && W4) { g.W = W4; g.ldw = K / 2; g.mx_scale = s4; }
-    if (pk) { g.x_packed = 1; g.y_packed = ypk && epi == EPI_SWIGLU; if (wpk && WP) { g.W = WP; g.w_packed = 1; } }
+    if (pk) {
+      g.x_packed = 1; g.y_packed = ypk && epi == EPI_SWIGLU;
+      if (mpk) g.w_packed = 1;      // W4 / s4 are the packed MXFP4 replica
+      else if (wpk && WP) { g.W = WP; g.w_packed = 1; }
+    }
     return g;
   };
   auto gemv = [&](const void* X, int ldx, const void* W, int K, void* Y, int ldy, int N, const void* bias, const void* resid, int epi,
@@ -1333,7 +1394,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   // is 4 b H bytes that the residual + RMSNorm launch (under TP: the peer exchange) has to read
   auto ks_short = [&](int K) { return std::max(1, std::min(DEC_KS_MAX, (K / 64) / 16)); };
   const bool shard_ks = (gemv_get_shard_shapes() & 2) != 0;
-  const int ks_o = b == 1 ? ks_rows(qd) : (wpk && qd == 3584 ? 2 : (shard_ks && qd / 64 <= 64) ? ks_short(qd) :
+  const int ks_o = b == 1 ? ks_rows(qd) : ((wpk || mpk) && qd == 3584 ? 2 : (shard_ks && qd / 64 <= 64) ? ks_short(qd) :
                                            std::max(1, std::min(DEC_KS_MAX, std::min(qd / 64, cdiv(512, cdiv(H, 16))))));
   const int ks_d = b == 1 ? ks_rows(It) : (shard_ks && It / 64 <= 64) ? ks_short(It) :
                                           std::max(1, std::min(DEC_KS_MAX, std::min(It / 64, 3 * cdiv(512, cdiv(H, 16)))));
@@ -1361,7 +1422,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     static const omchat_ctx::DecLayer8 none8{};
     const omchat_ctx::DecLayer8& Q = f8 ? ctx->dl8[i] : none8;
     static const omchat_ctx::DecLayer4 none4{};
-    const omchat_ctx::DecLayer4& M = mx4 ? ctx->dl4[i] : none4;
+    const omchat_ctx::DecLayer4& M = mx4 ? (mpk ? ctx->dl4p[i] : ctx->dl4[i]) : none4;
     const omchat_ctx::DecLayerP& P = wpk ? ctx->dlp[i] : noneP;
     char* kc = (char*)ctx->kcache + (size_t)i * ctx->cache_layer_stride() * 2;
     char* vc = (char*)ctx->vcache + (size_t)i * ctx->cache_layer_stride() * 2;
@@ -1577,6 +1638,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(b >= 1 && b <= c.max_batch, "batch exceeds max_batch");
+  OM_CHECK(ctx->mx4_rows_ok(b), MX4_ROWS_MSG);
   int Lmax = 0;
   OM_CHECK(!ctx->left_padded, "per-sequence decode after a left-padded prefill: use omchat_decode_step_masked (the reference positions such a "
                               "batch with sum(mask) - 1 and a per-row key mask, omchat_arch.py:61-70; DESIGN.md section 7)");
@@ -1589,11 +1651,12 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   }
   OM_CHECK(Lmax <= c.max_seq, "KV cache full (max_seq)");
   hipStream_t s = (hipStream_t)stream;
-  if (b > 1 && b <= 32) TRY(ensure_packed(ctx));      // first batched step (or after a weight reload): build the packed replica
+  // first batched step (or after a weight reload): build the packed replica -- unless the step streams the packed MXFP4 one instead
+  if (b > 1 && b <= 32 && !ctx->mx4_step(b)) TRY(ensure_packed(ctx));
   // a weight reload (omchat_load_tensor) leaves the e4m3 replica stale: re-quantise IN PLACE before streaming it (same device
   // pointers, so a captured decode graph stays valid and replays the fresh bytes)
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
-  if (ctx->mxfp4_decode && ctx->mxfp4_stale) TRY(ensure_mxfp4_weights(ctx));
+  TRY(refresh_mxfp4_weights(ctx));
   TRY(pick_admit(ctx, next_tokens != nullptr, true));
   ctx->graph_steps++;
   // graph replay needs replay-invariant arguments: single-GPU fused path only; with profiling on, every 8th step runs eagerly
@@ -1603,7 +1666,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
     TRY(decode_body(ctx, tokens, b, Lmax, logits, next_tokens, s, true, same_len));
   } else {
     const bool f8 = ctx->fp8_decode && b == 1;
-    const bool mx4 = ctx->mxfp4_decode && b == 1;
+    const bool mx4 = ctx->mx4_step(b);
     omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (mx4 ? 4 : 0) + (f8 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0)];
     hipStream_t gs = ctx->graph_stream;
     OM_HIP(hipEventRecord(ctx->graph_ev_in, s));
@@ -1654,7 +1717,8 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(L >= 1, "decode before prefill");
   OM_CHECK(L + T <= c.max_seq, "KV cache full (max_seq)");
   hipStream_t s = (hipStream_t)stream;
-  TRY(ensure_packed(ctx));      // the first verify step (like the first batched step) builds the packed weight replica
+  if (!ctx->mx4_step(T)) TRY(ensure_packed(ctx));      // the first verify step (like the first batched step) builds the packed weight replica
+  TRY(refresh_mxfp4_weights(ctx));
   TRY(decode_body(ctx, tokens, T, L + T, logits, picks, s, false, false, false, L));
   hipLaunchKernelGGL(verify_accept_kernel, dim3(1), dim3(64), 0, s, tokens, picks, T, L, (flags & OMCHAT_VERIFY_KEEP_ALL) ? 1 : 0,
                      ctx->d_pos, ctx->d_len, ctx->d_verify_n);
@@ -1678,6 +1742,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(ctx->pre_S >= 1 && b == ctx->pre_b, "masked decode: the batch of the last prefill, all rows");
+  OM_CHECK(ctx->mx4_rows_ok(b), MX4_ROWS_MSG);
   OM_CHECK(ctx->dec_mode != 1, "omchat_decode_step_masked after omchat_decode_step on the same prefill: the two place the cache rows differently");
   OM_CHECK(ctx->tp_size == 1, "masked decode: one GPU (under tensor parallelism right-padded batches take the per-sequence step)");
   OM_CHECK(ctx->pre_S + ctx->masked_steps + 1 <= c.max_seq, "KV cache full (max_seq)");
@@ -1686,9 +1751,9 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
     TRY(ctx->alloc((void**)&ctx->d_mask, (size_t)c.max_batch * ctx->mask_sb));
   }
   // replicas first: a failure here must not leave host-to-device copies of caller / stack memory in flight
-  if (b > 1 && b <= 32) TRY(ensure_packed(ctx));
+  if (b > 1 && b <= 32 && !ctx->mx4_step(b)) TRY(ensure_packed(ctx));
   if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
-  if (ctx->mxfp4_decode && ctx->mxfp4_stale) TRY(ensure_mxfp4_weights(ctx));
+  TRY(refresh_mxfp4_weights(ctx));
   return 0;
 }
 

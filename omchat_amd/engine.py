@@ -161,13 +161,17 @@ class Engine:
         """Weight-only OCP e4m3 replica of the decode-streamed decoder weights (quantised on first call); batch-1 decode only."""
         check(self.lib.omchat_enable_fp8_decode(self.h, int(on)))
 
-    def enable_mxfp4_decode(self, on=True):
+    def enable_mxfp4_decode(self, on=True, batched=False):
         """Weight-only MXFP4 replica (OCP Microscaling: e2m1 codes + one e8m0 scale per 32 k, 4.25 bits per weight) of the decode-streamed
-        decoder weights, quantised on the first call and again after a weight reload; batch-1 decode steps only.  Batched steps, the
-        prompt-lookup verify step and beam search keep the 16-bit weights, as under enable_fp8_decode.  Refused before the weights are
-        loaded, together with enable_fp8_decode, and under tensor parallelism."""
-        check(self.lib.omchat_enable_mxfp4_decode(self.h, int(on)))
+        decoder weights, quantised on the first call and again after a weight reload.  batched=False: batch-1 decode steps only; batched
+        steps, the prompt-lookup verify step and beam search keep the 16-bit weights, as under enable_fp8_decode.  batched=True: every
+        step of 2 <= b <= 32 rows (batched, padded-batch, beam and verify steps) streams a packed copy of the same codes as well, so one
+        generation reads one weight format; a step of more than 32 rows is then refused.  Refused before the weights are loaded, together
+        with enable_fp8_decode, under tensor parallelism, and (batched) for a geometry outside the packed GEMV path or when the packed
+        copy does not fit; a refusal leaves the mode as it was."""
+        check(self.lib.omchat_enable_mxfp4_decode(self.h, (2 if batched else 1) if on else 0))
         self._mxfp4_decode = bool(on)
+        self._mxfp4_batched = bool(on) and bool(batched)
 
     def enable_fp8_kv(self, on=True):
         """fp8 (e4m3 + per-position scale) KV cache for the decode steps that follow the NEXT prefill (BASELINE configs[4])"""

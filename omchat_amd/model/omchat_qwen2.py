@@ -191,11 +191,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
 
     __call__ = forward
 
-    def enable_mxfp4_decode(self, on=True):
+    def enable_mxfp4_decode(self, on=True, batched=False):
         """Engine.enable_mxfp4_decode: batch-1 decode steps of generate() stream the MXFP4 replica of the decoder weights (greedy, sampling,
         bans, logprobs, reuse_cache and the decode graph unchanged); batched steps and beam search keep the 16-bit weights, and
-        prompt_lookup_num_tokens is refused while it is on."""
-        self.engine.enable_mxfp4_decode(on)
+        prompt_lookup_num_tokens is refused while it is on.  batched=True: batched and padded batches (up to 32 rows), beam search and the
+        prompt-lookup verify step stream the packed MXFP4 copy as well, and prompt_lookup_num_tokens is accepted."""
+        self.engine.enable_mxfp4_decode(on, batched)
 
     def _stage_buffer(self, steps, b):
         """pinned staging rows for the generated ids + the event that guards them: allocated once and grown on demand (a hipHostMalloc per
@@ -277,7 +278,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise NotImplementedError("prompt-lookup decoding with num_beams > 1 is not implemented")
         if getattr(self.engine, "_fp8_kv", False):
             raise NotImplementedError("prompt-lookup decoding over the e4m3 KV cache is not implemented: enable_fp8_kv(False)")
-        if vars(self.engine).get("_mxfp4_decode", False):
+        if vars(self.engine).get("_mxfp4_decode", False) and not vars(self.engine).get("_mxfp4_batched", False):
             raise NotImplementedError("prompt-lookup decoding with MXFP4 decode weights is not implemented: a verify step runs on the 16-bit "
                                       "weights, so one generation would mix two weight sets: enable_mxfp4_decode(False)")
         if int(k) <= 0 or int(m) <= 0:

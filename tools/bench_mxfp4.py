@@ -10,7 +10,16 @@ Prints JSON lines:
                   format) so that no launch finds its rows in the L2 / the memory-side cache, as in a real step.  form "plain": x arrives
                   normalised; form "norm": the RMSNorm runs in the GEMV's registers (what a step launches for qkv, gate|up and lm_head;
                   the e4m3 format has no op-level entry for it).
-  {"drift": ...}  relative difference of the first decode step's logits against the 16-bit step on the same prefill."""
+  {"drift": ...}  relative difference of the first decode step's logits against the 16-bit step on the same prefill.
+Batched section (--sections batched; MXFP4 mode 2, Engine.enable_mxfp4_decode(True, batched=True)): one context with 32 cache rows, the 16-bit
+packed path and the packed MXFP4 path alternating:
+  {"batched_step": ...}    ms per decode step at b = 8 and b = 32, eager and as the captured graph, windows as above
+  {"verify": ...}          ms per prompt-lookup verify step of T = 8 tokens (host clock: the call ends in a device synchronise)
+  {"batched_role": ...}    the five GEMV roles alone at b = 8 and b = 32 on PRE-PACKED operands (omchat_op_gemv_prepacked: the launch a step
+                           makes, nothing packed or allocated in the timed loop), o_proj and down_proj with the step's split-K slice counts
+                           (2 and 8), microseconds per launch and GB/s of weight bytes, rotating copies as above; --batched-iters launches per
+                           window (default 1000: 10 to 200 ms of work), median, min and max over the windows
+  {"batched_drift": ...}   relative difference of a b = 32 step's logits against the 16-bit packed step on the same prefill."""
 import argparse
 import json
 import os
@@ -27,7 +36,10 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--layers", type=int, default=28)
     ap.add_argument("--prompt", type=int, default=64)
+    ap.add_argument("--batched-iters", type=int, default=1000, help="launches per timed window of a batched role (10 to 200 us each)")
+    ap.add_argument("--sections", default="batch1,batched", help="comma list of: batch1, batched")
     args = ap.parse_args()
+    sections = set(args.sections.split(","))
     import torch
     from omchat_amd import _lib
     from omchat_amd._lib import check, ptr
@@ -38,6 +50,10 @@ def main():
     cfg = omchat13b()
     cfg.text["num_hidden_layers"] = args.layers
     H, It, V = cfg.text["hidden_size"], cfg.text["intermediate_size"], cfg.text["vocab_size"]
+    if "batched" in sections:
+        batched(args, cfg, lib)
+    if "batch1" not in sections:
+        return
     e = Engine(cfg, dtype="bf16", max_seq=args.prompt + args.steps + 64, max_batch=1, vision=False)
     e.fill_synthetic(0)
     x = (torch.randn(1, args.prompt, H, generator=torch.Generator().manual_seed(1)) * 0.5).bfloat16()
@@ -153,6 +169,140 @@ def main():
             out[f"{fmt}/{form}"] = dict(us=round(us, 2), min=round(min(times), 2), max=round(max(times), 2), GBps=round(byts[fmt] / us / 1e3, 1))
         print(json.dumps(dict(role=name, N=N, K=K, weight_MB={k: round(v / 2 ** 20, 1) for k, v in byts.items()}, **out)), flush=True)
         del sets, w, w8, w4
+        torch.cuda.empty_cache()
+
+
+def batched(args, cfg, lib):
+    import time
+    import torch
+    from omchat_amd import _lib
+    from omchat_amd._lib import check, ptr
+    from omchat_amd.engine import Engine
+    H, It, V = cfg.text["hidden_size"], cfg.text["intermediate_size"], cfg.text["vocab_size"]
+    B = 32
+    e = Engine(cfg, dtype="bf16", max_seq=args.prompt + max(args.steps, 8 * 24) + 64, max_batch=B, vision=False)
+    e.fill_synthetic(0)
+    x = (torch.randn(B, args.prompt, H, generator=torch.Generator().manual_seed(1)) * 0.5).bfloat16()
+    FORMATS = ["bf16", "mxfp4"]
+
+    def select(fmt):
+        e.enable_mxfp4_decode(fmt == "mxfp4", batched=True)
+
+    logits = {}
+    for fmt in FORMATS:
+        select(fmt)
+        e.prefill(x)
+        _, lg = e.decode_step(torch.arange(3, 3 + B), want_logits=True)
+        torch.cuda.synchronize()
+        logits[fmt] = lg.double().cpu()
+    d = float((logits["mxfp4"] - logits["bf16"]).norm() / logits["bf16"].norm())
+    print(json.dumps(dict(batched_drift=dict(mxfp4=round(d, 5), argmax_equal_rows=int((logits["mxfp4"].argmax(1) == logits["bf16"].argmax(1)).sum()),
+                                             rows=B))), flush=True)
+
+    def window(b, n):
+        e.prefill(x[:b].contiguous())
+        tok = torch.arange(3, 3 + b, dtype=torch.int32, device="cuda")
+        for _ in range(8):
+            tok, _ = e.decode_step(tok)
+        torch.cuda.synchronize()
+        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            tok, _ = e.decode_step(tok)
+        z.record()
+        z.synchronize()
+        return a.elapsed_time(z) / n
+
+    table, spread = {}, 0.0
+    for graph in (False, True):
+        e.enable_decode_graph(graph)
+        for b in (8, 32):
+            cells = {f: [] for f in FORMATS}
+            for _ in range(args.repeats):
+                for fmt in FORMATS:
+                    select(fmt)
+                    cells[fmt].append(window(b, args.steps))
+            for fmt in FORMATS:
+                v = cells[fmt]
+                table[f"b{b}/{fmt}/{'graph' if graph else 'eager'}"] = dict(ms=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4))
+                spread = max(spread, max(v) - min(v))
+    e.enable_decode_graph(False)
+    print(json.dumps(dict(batched_step=table, spread_ms=round(spread, 4), layers=args.layers, steps=args.steps, repeats=args.repeats)), flush=True)
+
+    # ---- one verify step of T = 8 tokens (keep_all: every call appends 8 positions; 24 calls per window, the first 4 not timed)
+    T, calls = 8, 24
+    toks = torch.arange(5, 5 + T, dtype=torch.int32)
+    cells = {f: [] for f in FORMATS}
+    for _ in range(args.repeats):
+        for fmt in FORMATS:
+            select(fmt)
+            e.prefill(x[:1].contiguous())
+            for i in range(calls):
+                if i == 4:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                e.decode_verify(toks, keep_all=True)
+            torch.cuda.synchronize()
+            cells[fmt].append((time.perf_counter() - t0) * 1e3 / (calls - 4))
+    print(json.dumps(dict(verify={f: dict(ms=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4)) for f, v in cells.items()},
+                          T=T, layers=args.layers)), flush=True)
+    select("bf16")
+    e.close()
+
+    # ---- the five GEMV roles alone, pre-packed operands, the launches a batched step makes
+    BF16, NONE, SWIGLU, PARTIAL = _lib.BF16, _lib.EPI_NONE, _lib.EPI_SWIGLU, 5
+    qkvd = (cfg.text["num_attention_heads"] + 2 * cfg.text["num_key_value_heads"]) * 128
+    ROLES = [("qkv", qkvd, H, NONE, 1, False), ("o_proj", H, H, PARTIAL, 2, False), ("gate|up", 2 * It, H, SWIGLU, 1, False),
+             ("down_proj", H, It, PARTIAL, 8, False), ("lm_head", V, H, NONE, 1, True)]
+    g = torch.Generator(device="cuda").manual_seed(2)
+    for name, N, K, epi, ks, f32 in ROLES:
+        w = (torch.randn(N, K, device="cuda", generator=g) * 0.02).bfloat16()
+        w4 = torch.empty(N, K // 2, dtype=torch.uint8, device="cuda"); s4 = torch.empty(N, K // 32, dtype=torch.uint8, device="cuda")
+        check(lib.omchat_op_quant_mxfp4(BF16, ptr(w), N, K, ptr(w4), ptr(s4), None))
+        wp = torch.empty_like(w); w4p = torch.empty_like(w4); s4p = torch.empty_like(s4)
+        check(lib.omchat_op_pack_w(BF16, ptr(w), K, N, K, ptr(wp), None))
+        check(lib.omchat_op_pack_w4(ptr(w4), ptr(s4), N, K, ptr(w4p), ptr(s4p), None))
+        torch.cuda.synchronize()
+        del w, w4, s4
+        byts = dict(bf16=N * K * 2, mxfp4=N * K // 2 + N * K // 32)
+        bias = torch.zeros(N, device="cuda", dtype=torch.bfloat16) if name == "qkv" else None
+
+        def copies(ts, nbytes):
+            n = max(2, -(-768 * 2 ** 20 // nbytes))
+            return [tuple(t.clone() for t in ts) for _ in range(n)]
+        sets = dict(bf16=copies((wp,), byts["bf16"]), mxfp4=copies((w4p, s4p), byts["mxfp4"]))
+        out = {}
+        for b in (8, 32):
+            NB = 2 if b > 16 else 1
+            xr = (torch.randn(b, K, device="cuda", generator=g) * 0.5).bfloat16()
+            xp = torch.empty(NB * 16 * K, device="cuda", dtype=torch.bfloat16)
+            check(lib.omchat_op_pack_x(BF16, ptr(xr), K, b, K, ptr(xp), None))
+            n_y = N // 2 if epi == SWIGLU else N
+            y = torch.zeros(ks * NB * 16 * n_y, device="cuda", dtype=torch.float32 if (f32 or epi == PARTIAL) else torch.bfloat16)
+
+            def launch(fmt, c):
+                return lib.omchat_op_gemv_prepacked(BF16, ptr(xp), ptr(c[0]), ptr(c[1]) if fmt == "mxfp4" else None, ptr(y), n_y, b, N, K, ptr(bias),
+                                                    epi, int(f32), ks, int(epi == SWIGLU), None)
+            times = {f: [] for f in FORMATS}
+            for r in range(args.repeats):
+                for fmt in FORMATS:
+                    cs = sets[fmt]
+                    for i in range(len(cs)):
+                        check(launch(fmt, cs[i]))
+                    torch.cuda.synchronize()
+                    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for i in range(args.batched_iters):
+                        check(launch(fmt, cs[i % len(cs)]))
+                    z.record()
+                    z.synchronize()
+                    times[fmt].append(a.elapsed_time(z) * 1e3 / args.batched_iters)
+            for fmt in FORMATS:
+                us = statistics.median(times[fmt])
+                out[f"b{b}/{fmt}"] = dict(us=round(us, 2), min=round(min(times[fmt]), 2), max=round(max(times[fmt]), 2),
+                                          GBps=round(byts[fmt] / us / 1e3, 1))
+        print(json.dumps(dict(batched_role=name, N=N, K=K, ksplit=ks, weight_MB={k: round(v / 2 ** 20, 1) for k, v in byts.items()}, **out)), flush=True)
+        del sets, wp, w4p, s4p
         torch.cuda.empty_cache()
 
 
