@@ -209,6 +209,9 @@ int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream);
 /* host copy of the record of rows 0..b-1: raw / processed host fp32 [b][max_len] (entries behind a row's count are left as they are),
  * counts host int32 [b] = picks recorded per row.  Synchronises the device. */
 int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* processed, int32_t* counts, int max_len);
+/* test accessor: the step counter of `row` and (seen_words host uint32 [(t_vocab + 31) / 32], may be NULL) its seen bitmap over this rank's
+ * vocabulary slice, bit i of word w = local id 32 w + i.  Refused while sampling is off.  Synchronises the device. */
+int omchat_read_sampling_state(omchat_ctx* ctx, int row, int* step, uint32_t* seen_words);
 int omchat_kv_lengths(omchat_ctx* ctx, int32_t* out, int b);      /* host copy of the current KV lengths */
 /* take back the last n decode steps of sequences 0..b-1 (generate() enqueues step k + 1 before it has read token k on the host, as the
  * reference's HF loop cannot; when token k ends the generation -- EOS, a stopping criterion -- that step is forgotten).  Synchronises. */
@@ -238,6 +241,7 @@ int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t
 
 /* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=k)) -------------------------- */
 #define OMCHAT_VERIFY_KEEP_ALL 1
+#define OMCHAT_VERIFY_SAMPLE 2
 /* T >= 2 tokens of sequence 0 on top of its cache (b = 1 context state, after omchat_prefill):
  * tokens device int32 [T] = the last emitted token (not yet cached) followed by T - 1 draft tokens.
  * Appends T slots at L..L+T-1.
@@ -249,7 +253,17 @@ int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t
  * Refused while sampling or a beam search is active, with the e4m3 cache, and when L + T > max_seq.
  * T <= 16 and T * (t_heads / t_kv_heads) <= 128 (the query rows of one kv head in the attention kernel), checked before anything is enqueued.  The rows go through the batched decode path (packed-operand GEMVs: the first verify step builds the packed weight replica, as
  * the first batched omchat_decode_step does) and the multi-query attention of omchat_op_attn_verify; never captured in the decode graph.
- * Synchronises (the host needs n). */
+ * Synchronises (the host needs n).
+ * flags & OMCHAT_VERIFY_SAMPLE: the sampled form (HF's assisted decoding with do_sample=True and a drafter without logits).  Sampling must be
+ * on (omchat_set_sampling; every parameter and the four filters of omchat_set_sampling_filters apply).  picks[j] is then the id a plain
+ * omchat_decode_step of sequence 0 would sample at that position: drawn with row 0's key at step s + j (s = sequence 0's step counter) from
+ * logits processed with the seen set of sequence 0 plus tokens[1..j].  n is computed as above.  The n + 1 emitted picks picks[0..n] are then
+ * committed to sequence 0 on the device: their seen bits set, the step counter advanced by n + 1; a rejected draft leaves no trace.
+ * omchat_kv_rewind(ctx, 1, r) straight after it takes back the last r <= n + 1 of these picks (slots, step counter and the seen bits they
+ * newly set), also with the repetition penalty on; once a prefill or any decode step ran, the one-step rule of omchat_kv_rewind holds again.
+ * Without the flag nothing changes: the call is still refused while sampling is on.  With it the call is refused while sampling is off,
+ * together with OMCHAT_VERIFY_KEEP_ALL, and -- as without it -- while constraints, logprobs or a beam search are on and with the e4m3 cache.
+ * The first sampled verify step with the penalty on allocates 16 seen bitmaps (counted in omchat_device_bytes). */
 int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int T, float* logits, int32_t* picks,
                          int* n_accept, int flags, void* stream);
 
@@ -620,6 +634,16 @@ int omchat_op_sample(const float* logits, int b, int V, uint64_t seed, float tem
 int omchat_op_sample_filtered(const float* logits, int b, int V, uint64_t seed, float temperature, int top_k, double top_p, float rep_penalty,
                               double min_p, double typical_p, double epsilon_cutoff, double eta_cutoff, const int32_t* seen_ids,
                               const int32_t* n_seen_per_row, int step, int32_t* out, uint32_t* thr_lo, uint32_t* thr_hi, void* stream);
+/* context-free verify form of the sampler (omchat_decode_verify with OMCHAT_VERIFY_SAMPLE; test hook): logits device fp32 [T][ld] (ld >= V)
+ * of the vocabulary slice of `rank` (V ids out of V_total; rank = 0, V_total = V for the whole vocabulary), tokens device int32 [T] = the last
+ * emitted id and the T - 1 drafts, 2 <= T <= 16.  Row j is drawn with row 0's key at step base_step + j; with rep_penalty != 1 it sees
+ * seen_ids (host int32 [n_seen], GLOBAL ids of sequence 0's seen set) plus tokens[1..j]; ids outside [0, V_total) or the slice are ignored.
+ * Parameters and filters as omchat_op_sample_filtered.  out device int32 [T] (global ids; the slice's winner, no exchange), thr_lo / thr_hi
+ * as there.  Synchronises. */
+int omchat_op_sample_verify(const float* logits, int T, int V, int ld, const int32_t* tokens, uint64_t seed, int base_step, float temperature,
+                            int top_k, double top_p, float rep_penalty, double min_p, double typical_p, double epsilon_cutoff, double eta_cutoff,
+                            const int32_t* seen_ids, int n_seen, int rank, int V_total, int32_t* out, uint32_t* thr_lo, uint32_t* thr_hi,
+                            void* stream);
 /* context-free log-probability stage of omchat_set_logprobs (test hook): logits device fp32 [b][ld] (ld >= V), ids host int32 [b] (the picked
  * ids), ban device uint32 [b][(V + 31) / 32] or NULL (set bit = processed value -inf), seen ids as omchat_op_sample takes them (read when
  * rep_penalty != 1), newly_seen host int32 [b] or NULL (!= 0: the pick set its id's seen bit, so the id counts as unseen), thr device uint32 [b]

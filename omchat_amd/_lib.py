@@ -146,6 +146,9 @@ _SIGS = {
     "omchat_op_token_logprob": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_sample_filtered": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _i,
                                        _vp, _vp, _vp, _vp]),
+    "omchat_op_sample_verify": (_i, [_vp, _i, _i, _i, _vp, _u64, _i, _f, _i, C.c_double, _f, C.c_double, C.c_double, C.c_double, C.c_double, _vp,
+                                     _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "omchat_read_sampling_state": (_i, [_vp, _i, _vp, _vp]),
     "omchat_op_token_logprob_interval": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_constrain": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "omchat_beam_state_words": (_sz, [_i, _i, _i]),

@@ -429,6 +429,47 @@ extern "C" int omchat_op_sample_filtered(const float* logits, int b, int V, uint
   return op_sample(logits, b, V, seed, temperature, top_k, top_p, rep_penalty, f, seen_ids, n_seen_per_row, step, out, thr_lo, thr_hi, stream);
 }
 
+extern "C" int omchat_op_sample_verify(const float* logits, int T, int V, int ld, const int32_t* tokens, uint64_t seed, int base_step,
+                                       float temperature, int top_k, double top_p, float rep_penalty, double min_p, double typical_p,
+                                       double epsilon_cutoff, double eta_cutoff, const int32_t* seen_ids, int n_seen, int rank, int V_total,
+                                       int32_t* out, uint32_t* thr_lo, uint32_t* thr_hi, void* stream) {
+  OM_CHECK(logits && tokens && out && T >= 2 && T <= SMP_VERIFY_ROWS && V >= 1 && ld >= V, "bad argument");
+  OM_CHECK(rank >= 0 && V_total >= V && (int64_t)rank * V + V <= (int64_t)V_total, "the slice must lie inside the vocabulary");
+  OM_CHECK(temperature > 0.f && top_k >= 0 && top_p > 0.0 && top_p <= 1.0 && rep_penalty > 0.f, "sampling parameters out of range");
+  OM_CHECK(!(min_p > 1.0) && min_p == min_p && typical_p > 0.0 && epsilon_cutoff > 0.0 && eta_cutoff > 0.0, "sampling filter parameters out of range");
+  OM_CHECK(n_seen >= 0 && (n_seen == 0 || seen_ids), "bad argument");
+  SampleFilters f;
+  f.min_p = min_p < 0.0 ? -1.0 : min_p;
+  f.typical_p = typical_p < 1.0 ? typical_p : 1.0;
+  f.epsilon = epsilon_cutoff < 1.0 ? epsilon_cutoff : 1.0;
+  f.eta = eta_cutoff < 1.0 ? eta_cutoff : 1.0;
+  const int bmw = (V + 31) / 32;
+  std::vector<uint32_t> bm(bmw, 0u);
+  const int64_t lo = (int64_t)rank * V;
+  for (int j = 0; j < n_seen; ++j) {
+    const int64_t li = (int64_t)seen_ids[j] - lo;
+    if (seen_ids[j] >= 0 && seen_ids[j] < V_total && li >= 0 && li < V) bm[li >> 5] |= 1u << (li & 31);
+  }
+  const size_t ws_bytes = sample_ws_bytes(T), bmb = (size_t)bmw * 4;
+  char* mem = nullptr;
+  OM_HIP(hipMalloc(&mem, ws_bytes + bmb * (1 + SMP_VERIFY_ROWS) + 16));
+  uint32_t* d_bm = (uint32_t*)(mem + ws_bytes);
+  uint32_t* d_vseen = d_bm + bmw;
+  int* d_step = (int*)(d_vseen + (size_t)SMP_VERIFY_ROWS * bmw);
+  hipMemcpyAsync(d_bm, bm.data(), bmb, hipMemcpyHostToDevice, S(stream));
+  hipMemcpyAsync(d_step, &base_step, 4, hipMemcpyHostToDevice, S(stream));
+  SampleArgs a;
+  a.logits = logits; a.ld = ld; a.b = T; a.V = V; a.V_total = V_total; a.rank = rank;
+  a.seed = seed; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.penalty = rep_penalty;
+  if (rep_penalty != 1.f) { a.bitmap = d_bm; a.bm_words = bmw; a.vseen = d_vseen; }
+  a.step = d_step; a.vtokens = tokens; a.out = out; a.thr_out = thr_lo; a.hi_out = thr_hi; a.ws = mem;
+  a.f = f;
+  int rc = launch_sample(a, S(stream));
+  hipStreamSynchronize(S(stream));
+  hipFree(mem);
+  return rc;
+}
+
 static int op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
                             float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
                             const uint32_t* thr, const uint32_t* thr_hi, float* raw_out, float* processed_out, void* stream) {

@@ -43,6 +43,12 @@ struct PickState {
   void* smp_ws = nullptr;
   uint32_t* smp_bm = nullptr; int smp_bmw = 0;
   int *smp_last = nullptr, *smp_step = nullptr;
+  // sampled verify step (omchat_decode_verify with OMCHAT_VERIFY_SAMPLE): the per-row seen bitmaps [16][smp_bmw] (allocated by the first such
+  // step with the penalty on), the local indices of the bits its committed picks newly set (device [16], -1 = none: the verify counterpart of
+  // smp_last) and how many of those picks omchat_kv_rewind can still take back (host; 0 once any other pick ran)
+  uint32_t* smp_vseen = nullptr;
+  int* smp_vlast = nullptr;
+  int smp_vcommit = 0;
   // HF logits constraints (omchat_set_constraints; constrain.hip): uniform parameters, the rows' token history as HF's processors see it
   // [max_batch][con_ld] with device lengths, the id lists, the ban bitmap of this rank's vocabulary slice (all-zero between picks) and the
   // banned copy of the logits the pick runs on.  con_fed: decode steps fed since the begin (host bound for the history's capacity).
@@ -360,6 +366,12 @@ int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, h
 // pick after the prefill)
 int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance = false, const int32_t* fed = nullptr,
              bool force_greedy = false);
+// the picks of a verify step's T rows (tokens = what the rows were fed): bare argmax, or with `sample` the sampler's verify form, which
+// commits nothing (pick_verify_committed follows the acceptance)
+int pick_verify(omchat_ctx* ctx, const float* lg, int T, const int32_t* tokens, int32_t* picks, hipStream_t s, bool sample);
+const char* pick_verify_refusal(omchat_ctx* ctx, int flags);      // why the sampler's state does not go with omchat_decode_verify's flags, or NULL
+int pick_verify_prepare(omchat_ctx* ctx);      // allocations of a sampled verify step, before anything is enqueued
+void pick_verify_committed(omchat_ctx* ctx, int n_picks);      // the acceptance committed n_picks sampled picks to sequence 0
 int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s);      // a step that picks nothing still feeds the history
 const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n);      // why the pick state cannot go back n steps, or NULL
 int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s);

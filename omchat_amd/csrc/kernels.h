@@ -407,13 +407,23 @@ struct SampleArgs {
   uint32_t* hi_out = nullptr;                       // optional upper keys [b] (test hook): 0xFFFFFFFF when the top is kept
   void* ws = nullptr;                               // sample_ws_bytes(b)
   float* table = nullptr;
+  // verify form (omchat_decode_verify with OMCHAT_VERIFY_SAMPLE): vtokens (device int32 [b], 2 <= b <= 16) = the last
+  // emitted id and the drafts of sequence 0.  Row j draws with the key of row 0 at step[0] + j and, under the penalty, sees bitmap row 0 plus
+  // vtokens[1..j] (built into vseen, scratch [SMP_VERIFY_ROWS][bm_words]).  Every other per-row state stays indexed by j.  Nothing is
+  // committed: out[j] only; bitmap, last_set, step and the decode positions are left to the acceptance.
+  const int32_t* vtokens = nullptr;
+  uint32_t* vseen = nullptr;
   int (*xchg)(void* user, float* buf, size_t count, hipStream_t s) = nullptr;
   void* xchg_user = nullptr;
 };
+constexpr int SMP_VERIFY_ROWS = VERIFY_MAX_T;
 size_t sample_ws_bytes(int b);
 int launch_sample(const SampleArgs& a, hipStream_t s);
 // take back n picks: clears the bit the last pick set (n == 1), step -= n
 int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s);
+// take back the last r of the cnt picks a sampled verify step committed to sequence 0: clears the bits vlast[cnt - r .. cnt) recorded as
+// newly set (bitmap: row 0, or nullptr without the penalty), step[0] -= r
+int launch_sample_rewind_verify(uint32_t* bitmap, int* vlast, int* step, int cnt, int r, hipStream_t s);
 // where the last launch_sample on (ws, b) left row r's kept-set threshold key: words[r * *stride]; nullptr when the parameters keep every token.
 // *hi: the upper key of the kept interval, same stride; nullptr when the parameters keep the top (typical_p off)
 const uint32_t* sample_thr_words(const void* ws, int b, int V_total, int top_k, double top_p, const SampleFilters& f, int* stride,

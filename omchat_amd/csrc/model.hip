@@ -41,6 +41,31 @@ __global__ void verify_accept_kernel(const int32_t* tokens, const int32_t* picks
   pos[0] = L + kept; len[0] = L + kept + 1;
   n_out[0] = n;
 }
+// the sampled form (OMCHAT_VERIFY_SAMPLE): the same n, and the n + 1 emitted picks are committed to sequence 0's sampler state as n + 1 plain
+// steps would have: seen bits in pick order (this rank's shard; bm = nullptr without the penalty), each newly set bit recorded in vlast
+// [16] for omchat_kv_rewind, the step counter advanced by n + 1.  smp_last[0] no longer names the last pick's bit.
+__global__ void verify_accept_sample_kernel(const int32_t* tokens, const int32_t* picks, int T, int L, int* pos, int* len, int* n_out,
+                                            uint32_t* bm, int gbase, int V, int* vlast, int* last, int* step) {
+  if (threadIdx.x != 0) return;
+  int n = 0;
+  while (n < T - 1 && tokens[n + 1] == picks[n]) ++n;
+  for (int i = 0; i < VERIFY_MAX_T; ++i) {
+    int set = -1;
+    if (bm && i <= n) {
+      const int id = picks[i];
+      const int li = id >= gbase ? id - gbase : -1;
+      if (id >= 0 && li >= 0 && li < V) {
+        const uint32_t bit = 1u << (li & 31);
+        if (!(bm[li >> 5] & bit)) { bm[li >> 5] |= bit; set = li; }
+      }
+    }
+    vlast[i] = set;
+  }
+  last[0] = -1;
+  step[0] += n + 1;
+  pos[0] = L + n + 1; len[0] = L + n + 2;
+  n_out[0] = n;
+}
 __global__ void last_row_index_kernel(const int* len, int S, int b, int* idx, int keep) {      // (keep: cached rows in front of the S prefilled ones)
   const int i = threadIdx.x;
   if (i < b) idx[i] = i * S + len[i] - keep - 1;
@@ -1122,6 +1147,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   }
   ctx->left_padded = left;
   ctx->pre_S = keep + S; ctx->pre_b = b; ctx->masked_steps = 0; ctx->dec_mode = 0; ctx->mask_on_device = false;
+  ctx->pick.smp_vcommit = 0;      // the slots of a sampled verify step's picks are gone: omchat_kv_rewind's one-step rule holds again
   // d_len holds the valid key range end during prefill; switched to (len + 1, pos = len) for the decode steps at the end
   OM_HIP(hipMemcpyAsync(ctx->d_len, klen.data(), (size_t)b * 4, hipMemcpyHostToDevice, s));
   if (left) OM_HIP(hipMemcpyAsync(ctx->d_start, kstart.data(), (size_t)b * 4, hipMemcpyHostToDevice, s));
@@ -1329,7 +1355,7 @@ static const char* const MX4_ROWS_MSG = "MXFP4 decode mode 2 streams steps of at
 // vL >= 0: prompt-lookup verify step (omchat_decode_verify) -- the b rows are consecutive tokens of sequence 0 at positions vL .. vL + b - 1
 // (multi-query attention, launch_attn_verify), and next_tokens receives the greedy pick of every row without moving any position.
 static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, float* logits, int32_t* next_tokens, hipStream_t s, bool allow_prof,
-                       bool exact_len = false, bool masked = false, int vL = -1) {
+                       bool exact_len = false, bool masked = false, int vL = -1, bool vsample = false) {
   const omchat_config& c = ctx->c;
   const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
   const bool lead = ctx->tp_rank == 0;
@@ -1589,7 +1615,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, f8, fused && pk, mx4));
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
-  if (vL >= 0) TRY(greedy_pick(ctx, lg, b, next_tokens, s));
+  if (vL >= 0) TRY(pick_verify(ctx, lg, b, tokens, next_tokens, s, vsample));
   else if (next_tokens) TRY(pick_run(ctx, lg, b, next_tokens, s, true, tokens));
   else {
     hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
@@ -1708,7 +1734,9 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(T >= 2 && T <= VERIFY_MAX_T, "2 <= T <= 16 tokens (T = 1 is omchat_decode_step)");
   OM_CHECK(c.t_kv_heads > 0 && T * (c.t_heads / c.t_kv_heads) <= 128, "T * (q heads per kv head) must be <= 128 (the verify attention's query rows)");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "after a padded-batch prefill or masked decode steps");
-  OM_CHECK(!ctx->pick.sampling_on(), "sampling is on: prompt-lookup decoding is greedy only");
+  const bool vsample = (flags & OMCHAT_VERIFY_SAMPLE) != 0;
+  const char* why = pick_verify_refusal(ctx, flags);
+  OM_CHECK(!why, why);
   OM_CHECK(!ctx->pick.constraints_on(), "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
   OM_CHECK(!ctx->beam.on(), "a beam search is active");
   OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
@@ -1719,14 +1747,22 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   hipStream_t s = (hipStream_t)stream;
   if (!ctx->mx4_step(T)) TRY(ensure_packed(ctx));      // the first verify step (like the first batched step) builds the packed weight replica
   TRY(refresh_mxfp4_weights(ctx));
-  TRY(decode_body(ctx, tokens, T, L + T, logits, picks, s, false, false, false, L));
-  hipLaunchKernelGGL(verify_accept_kernel, dim3(1), dim3(64), 0, s, tokens, picks, T, L, (flags & OMCHAT_VERIFY_KEEP_ALL) ? 1 : 0,
-                     ctx->d_pos, ctx->d_len, ctx->d_verify_n);
+  if (vsample) TRY(pick_verify_prepare(ctx));
+  TRY(decode_body(ctx, tokens, T, L + T, logits, picks, s, false, false, false, L, vsample));
+  if (vsample) {
+    const PickState& P = ctx->pick;
+    hipLaunchKernelGGL(verify_accept_sample_kernel, dim3(1), dim3(64), 0, s, tokens, picks, T, L, ctx->d_pos, ctx->d_len, ctx->d_verify_n,
+                       P.smp.penalty != 1.f ? P.smp_bm : nullptr, ctx->tp_rank * c.t_vocab, c.t_vocab, P.smp_vlast, P.smp_last, P.smp_step);
+  } else {
+    hipLaunchKernelGGL(verify_accept_kernel, dim3(1), dim3(64), 0, s, tokens, picks, T, L, (flags & OMCHAT_VERIFY_KEEP_ALL) ? 1 : 0,
+                       ctx->d_pos, ctx->d_len, ctx->d_verify_n);
+  }
   OM_LAUNCH_CHECK();
   int n = 0;
   OM_HIP(hipMemcpyAsync(&n, ctx->d_verify_n, 4, hipMemcpyDeviceToHost, s));
   OM_HIP(hipStreamSynchronize(s));
   *n_accept = n;
+  if (vsample) pick_verify_committed(ctx, n + 1);
   ctx->h_len[0] = L + ((flags & OMCHAT_VERIFY_KEEP_ALL) ? T : n + 1);
   ctx->dec_mode = 1;
   return 0;

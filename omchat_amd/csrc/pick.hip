@@ -106,6 +106,7 @@ int pick_admit(omchat_ctx* ctx, bool picks, bool feeds) {
   }
   if (picks) TRY(lp_room(ctx));
   if (feeds) TRY(con_count_step(ctx));
+  ctx->pick.smp_vcommit = 0;      // a sampled verify step's picks are no longer the last thing the cache holds
   if (ctx->pick.lp.on && picks) ctx->pick.lp_picks += 1;
   return 0;
 }
@@ -148,6 +149,41 @@ int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipS
   return logprob_stage(ctx, raw, lg, b, next_tokens, s);
 }
 
+const char* pick_verify_refusal(omchat_ctx* ctx, int flags) {
+  const PickState& P = ctx->pick;
+  if (!(flags & OMCHAT_VERIFY_SAMPLE)) {
+    if (P.smp.on) return "sampling is on: prompt-lookup decoding is greedy only";
+  } else {
+    if (!P.smp.on) return "OMCHAT_VERIFY_SAMPLE: sampling is off (omchat_set_sampling first)";
+    if (flags & OMCHAT_VERIFY_KEEP_ALL) return "OMCHAT_VERIFY_SAMPLE with OMCHAT_VERIFY_KEEP_ALL: the slots behind a rejected draw are not the sampled sequence's";
+  }
+  return nullptr;
+}
+
+int pick_verify_prepare(omchat_ctx* ctx) {
+  PickState& P = ctx->pick;
+  if (P.smp.penalty != 1.f && !P.smp_vseen) TRY(ctx->alloc((void**)&P.smp_vseen, (size_t)SMP_VERIFY_ROWS * P.smp_bmw * 4));
+  return 0;
+}
+
+int pick_verify(omchat_ctx* ctx, const float* lg, int T, const int32_t* tokens, int32_t* picks, hipStream_t s, bool sample) {
+  if (!sample) return greedy_pick(ctx, lg, T, picks, s);
+  const PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  SampleArgs a;
+  a.logits = lg; a.ld = c.t_vocab; a.b = T; a.V = c.t_vocab; a.V_total = c.t_vocab_total;
+  a.rank = ctx->tp_rank; a.tp = ctx->tp_size;
+  a.seed = P.smp.seed; a.temperature = P.smp.temperature; a.top_k = P.smp.top_k; a.top_p = P.smp.top_p; a.penalty = P.smp.penalty;
+  a.f = P.smp_f;
+  if (P.smp.penalty != 1.f) { a.bitmap = P.smp_bm; a.bm_words = P.smp_bmw; a.vseen = P.smp_vseen; }
+  a.step = P.smp_step; a.vtokens = tokens;
+  a.out = picks; a.ws = P.smp_ws; a.table = P.tp_table;
+  a.xchg = smp_xchg; a.xchg_user = ctx;
+  return launch_sample(a, s);
+}
+
+void pick_verify_committed(omchat_ctx* ctx, int n_picks) { ctx->pick.smp_vcommit = n_picks; }
+
 // (rows beyond those the constraints are on for are not the history's: no refusal here, unlike the ban stage of a step that picks)
 int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s) {
   const PickState& P = ctx->pick;
@@ -158,13 +194,19 @@ int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s) {
 const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n) {
   const PickState& P = ctx->pick;
   if (P.lp.on && b < P.lp.b) return "rewind of fewer rows than omchat_set_logprobs switched on: the rows' records would fall out of step";
+  if (P.smp.on && b == 1 && P.smp_vcommit > 0 && n <= P.smp_vcommit) return nullptr;      // the picks of a sampled verify step
   if (P.smp.on && n != 1 && P.smp.penalty != 1.f) return "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded";
   return nullptr;
 }
 
 int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s) {
   PickState& P = ctx->pick;
-  if (P.smp.on) {
+  if (P.smp.on && b == 1 && P.smp_vcommit > 0 && n <= P.smp_vcommit) {
+    // the last picks are a sampled verify step's: each recorded the bit it newly set
+    TRY(launch_sample_rewind_verify(P.smp.penalty != 1.f ? P.smp_bm : nullptr, P.smp_vlast, P.smp_step, P.smp_vcommit, n, s));
+    P.smp_vcommit -= n;
+  } else if (P.smp.on) {
+    P.smp_vcommit = 0;
     // the sampler's step counters go back with the slots, and the seen bit the last pick set is cleared (only that pick is recorded)
     TRY(launch_sample_rewind(P.smp.penalty != 1.f ? P.smp_bm : nullptr, P.smp_bmw, P.smp_last, P.smp_step, b, n, s));
   }
@@ -218,11 +260,13 @@ extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float 
                     o.penalty == p.penalty;
   if (!same) drop_decode_graphs(ctx);
   P.smp = p;
+  P.smp_vcommit = 0;
   P.smp_f = SampleFilters{};      // off until omchat_set_sampling_filters (the graphs are checked against them in front of the next step)
   if (!p.on) return 0;
   if (!P.smp_ws) {
     P.smp_bmw = (c.t_vocab + 31) / 32;
-    TRY(ctx->alloc(&P.smp_ws, sample_ws_bytes(c.max_batch)));
+    TRY(ctx->alloc(&P.smp_ws, sample_ws_bytes(std::max(c.max_batch, SMP_VERIFY_ROWS))));      // (a verify step picks up to 16 rows)
+    TRY(ctx->alloc((void**)&P.smp_vlast, (size_t)SMP_VERIFY_ROWS * 4));
     TRY(ctx->alloc((void**)&P.smp_bm, (size_t)c.max_batch * P.smp_bmw * 4));
     TRY(ctx->alloc((void**)&P.smp_last, (size_t)c.max_batch * 4));
     TRY(ctx->alloc((void**)&P.smp_step, (size_t)c.max_batch * 4));
@@ -246,7 +290,20 @@ extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float 
   OM_HIP(hipMemcpyAsync(P.smp_bm, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, s));
   OM_HIP(hipMemsetAsync(P.smp_step, 0, (size_t)c.max_batch * 4, s));
   OM_HIP(hipMemsetAsync(P.smp_last, 0xFF, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipMemsetAsync(P.smp_vlast, 0xFF, (size_t)SMP_VERIFY_ROWS * 4, s));
   OM_HIP(hipStreamSynchronize(s));     // host vector
+  return 0;
+}
+
+// test accessor (include/omchat_hip.h): a row's step counter and its rank-local seen bitmap
+extern "C" int omchat_read_sampling_state(omchat_ctx* ctx, int row, int* step, uint32_t* seen_words) {
+  OM_CHECK(ctx && step, "null argument");
+  const PickState& P = ctx->pick;
+  OM_CHECK(P.smp.on && P.smp_ws, "omchat_read_sampling_state: sampling is off");
+  OM_CHECK(row >= 0 && row < ctx->c.max_batch, "omchat_read_sampling_state: row out of range");
+  OM_HIP(hipDeviceSynchronize());
+  OM_HIP(hipMemcpy(step, P.smp_step + row, 4, hipMemcpyDeviceToHost));
+  if (seen_words) OM_HIP(hipMemcpy(seen_words, P.smp_bm + (size_t)row * P.smp_bmw, (size_t)P.smp_bmw * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -340,13 +340,14 @@ __global__ __launch_bounds__(64) void smp_filter_kernel(uint64_t* hist, const fl
 // argmax of the penalised logits without noise or temperature, i.e. greedy_pick's id.
 __global__ __launch_bounds__(256) void smp_race_kernel(const float* logits, int ld, int V, const uint32_t* seen, int bmw, float pen, float T,
                                                        const int64_t* st, int use_thr, int use_hi, int greedy, uint64_t seed, const int* step,
-                                                       int gbase, float* pv, int* pi) {
+                                                       int vfy, int gbase, float* pv, int* pi) {
   const int row = blockIdx.y;
   const float* lg = logits + (size_t)row * ld;
   const uint32_t* sn = seen ? seen + (size_t)row * bmw : nullptr;
   const uint32_t thr = use_thr ? (uint32_t)st[(size_t)row * SMP_ST + ST_THR] : 0u;
   const uint32_t top = use_hi ? (uint32_t)st[(size_t)row * SMP_ST + ST_HI] : 0xFFFFFFFFu;
-  const uint64_t rk = smp_row_key(seed, row, step[row]);
+  // verify form: row j is sequence 0 at step[0] + j, so it draws what a plain step of sequence 0 draws there
+  const uint64_t rk = vfy ? smp_row_key(seed, 0, step[0] + row) : smp_row_key(seed, row, step[row]);
   const int per = (V + SMP_RACE_CH - 1) / SMP_RACE_CH;
   const int lo = blockIdx.x * per, hi = min(lo + per, V);
   float best = -INFINITY;
@@ -370,6 +371,22 @@ __global__ __launch_bounds__(256) void smp_race_kernel(const float* logits, int 
     pv[row * SMP_RACE_CH + blockIdx.x] = best;
     pi[row * SMP_RACE_CH + blockIdx.x] = besti;
   }
+}
+
+// verify form, repetition penalty: the seen set of row j = sequence 0's bitmap + tokens[1..j] (the drafts in front of the row), this rank's
+// bits only; ids outside [0, V_total) or the shard are ignored.  One thread per word of a row's bitmap: out [T][bmw]
+__global__ __launch_bounds__(256) void smp_verify_seen_kernel(const uint32_t* base, const int32_t* tokens, int gbase, int V, int V_total,
+                                                              int bmw, uint32_t* out) {
+  const int w = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
+  if (w >= bmw) return;
+  uint32_t v = base[w];
+  for (int t = 1; t <= row; ++t) {
+    const int id = tokens[t];
+    if (id < gbase || id >= V_total) continue;      // (gbase >= 0: a negative id goes here too)
+    const int li = id - gbase;
+    if (li < V && (li >> 5) == w) v |= 1u << (li & 31);
+  }
+  out[(size_t)row * bmw + w] = v;
 }
 
 // the picked id of a row: record it in the repetition bitmap (its own shard's bit; `last` remembers a newly set bit for omchat_kv_rewind),
@@ -396,7 +413,7 @@ __device__ __forceinline__ void smp_commit(int row, int id, int gbase, int V, ui
 // the greedy exchange uses (pick.hip: tp_argmax_scatter_kernel's layout)
 __global__ __launch_bounds__(64) void smp_final_kernel(const float* pv, const int* pi, int b, int tp, int rank, float* table, int gbase, int V,
                                                        uint32_t* bm, int bmw, int* last, int* step, int* adv_pos, int* adv_len, int* out,
-                                                       const int64_t* st, uint32_t* thr_out, uint32_t* hi_out, int use_hi) {
+                                                       const int64_t* st, uint32_t* thr_out, uint32_t* hi_out, int use_hi, int commit) {
   const int row = blockIdx.x;
   float best = pv[row * SMP_RACE_CH + threadIdx.x];
   int besti = pi[row * SMP_RACE_CH + threadIdx.x];
@@ -413,12 +430,13 @@ __global__ __launch_bounds__(64) void smp_final_kernel(const float* pv, const in
     table[((size_t)rank * b + row) * 2 + 1] = besti == INT_MAX ? -1.f : (float)besti;
     return;
   }
+  if (!commit) { out[row] = besti == INT_MAX ? 0 : besti; return; }      // verify form: the acceptance commits (model.hip)
   smp_commit(row, besti == INT_MAX ? 0 : besti, gbase, V, bm, bmw, last, step, adv_pos, adv_len, out);
 }
 
 // after the exchange: ranks hold ascending index ranges, so strict > keeps the first index on ties (pick.hip: tp_argmax_pick_kernel's rule)
 __global__ void smp_tp_pick_kernel(const float* table, int b, int tp, int gbase, int V, uint32_t* bm, int bmw, int* last, int* step,
-                                   int* adv_pos, int* adv_len, int* out) {
+                                   int* adv_pos, int* adv_len, int* out, int commit) {
   const int i = threadIdx.x;
   if (i >= b) return;
   float best = table[(size_t)i * 2];
@@ -427,6 +445,7 @@ __global__ void smp_tp_pick_kernel(const float* table, int b, int tp, int gbase,
     const float v = table[((size_t)r * b + i) * 2];
     if (v > best) { best = v; bi = (int)table[((size_t)r * b + i) * 2 + 1]; }
   }
+  if (!commit) { out[i] = bi < 0 ? 0 : bi; return; }
   smp_commit(i, bi < 0 ? 0 : bi, gbase, V, bm, bmw, last, step, adv_pos, adv_len, out);
 }
 
@@ -436,6 +455,16 @@ __global__ void smp_rewind_kernel(uint32_t* bm, int bmw, int* last, int* step, i
   if (bm && last[i] >= 0) bm[(size_t)i * bmw + (last[i] >> 5)] &= ~(1u << (last[i] & 31));
   if (bm) last[i] = -1;
   step[i] -= n;
+}
+
+// take back the last r of the cnt picks a sampled verify step committed to sequence 0: their newly set bits (vlast) and the step counter
+__global__ void smp_rewind_verify_kernel(uint32_t* bm, int* vlast, int* step, int cnt, int r) {
+  if (threadIdx.x != 0) return;
+  for (int i = cnt - r; i < cnt; ++i) {
+    if (bm && vlast[i] >= 0) bm[vlast[i] >> 5] &= ~(1u << (vlast[i] & 31));
+    vlast[i] = -1;
+  }
+  step[0] -= r;
 }
 
 }  // namespace
@@ -465,6 +494,8 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
   OM_CHECK(a.tp >= 1 && a.tp <= 8, "sampling: the limb exchange holds at most 8 ranks");
   OM_CHECK(!(a.f.min_p > 1.0) && !(a.f.typical_p <= 0.0) && !(a.f.epsilon <= 0.0) && !(a.f.eta <= 0.0), "sampling: filter parameters out of range");
   const int b = a.b, V = a.V;
+  const bool vfy = a.vtokens != nullptr;
+  OM_CHECK(!vfy || (b >= 2 && b <= SMP_VERIFY_ROWS), "sampling, verify form: 2 <= rows <= 16");
   char* w = (char*)a.ws;
   uint64_t* hist = (uint64_t*)w;                 w += (size_t)b * SMP_BINS * 8;
   int64_t* st = (int64_t*)w;                     w += (size_t)b * SMP_ST * 8;
@@ -473,7 +504,11 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
   int* pi = (int*)w;
   const int gbase = a.rank * V;
   const bool pen = a.bitmap && a.penalty != 1.f;
-  const uint32_t* seen = pen ? a.bitmap : nullptr;
+  OM_CHECK(!(vfy && pen) || a.vseen, "sampling, verify form: the repetition penalty needs the bitmap scratch");
+  const uint32_t* seen = pen ? (vfy ? a.vseen : a.bitmap) : nullptr;
+  if (vfy && pen)
+    hipLaunchKernelGGL(smp_verify_seen_kernel, dim3((a.bm_words + 255) / 256, b), dim3(256), 0, s, a.bitmap, a.vtokens, gbase, V, a.V_total,
+                       a.bm_words, a.vseen);
   const bool greedy = a.top_k == 1;
   const bool use_k = !greedy && a.top_k > 1 && a.top_k < a.V_total;
   const bool use_p = !greedy && a.top_p < 1.0;
@@ -537,16 +572,16 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
   }
   if (a.tp > 1) OM_HIP(hipMemsetAsync(a.table, 0, (size_t)a.tp * b * 2 * 4, s));
   hipLaunchKernelGGL(smp_race_kernel, dim3(SMP_RACE_CH, b), dim3(256), 0, s, a.logits, a.ld, V, seen, a.bm_words, a.penalty, a.temperature,
-                     st, (int)(use_k || use_p || use_f), (int)use_hi, (int)greedy, a.seed, a.step, gbase, pv, pi);
-  uint32_t* bm = pen ? a.bitmap : nullptr;
+                     st, (int)(use_k || use_p || use_f), (int)use_hi, (int)greedy, a.seed, a.step, (int)vfy, gbase, pv, pi);
+  uint32_t* bm = pen && !vfy ? a.bitmap : nullptr;
   hipLaunchKernelGGL(smp_final_kernel, dim3(b), dim3(64), 0, s, pv, pi, b, a.tp, a.rank, a.table, gbase, V, bm, a.bm_words, a.last_set, a.step,
-                     a.adv_pos, a.adv_len, a.out, st, (use_k || use_p || use_f) ? a.thr_out : nullptr, a.hi_out, (int)use_hi);
+                     a.adv_pos, a.adv_len, a.out, st, (use_k || use_p || use_f) ? a.thr_out : nullptr, a.hi_out, (int)use_hi, (int)!vfy);
   if (a.tp > 1) {
     // the greedy exchange: zeroed table, one slot per rank, summed
     OM_LAUNCH_CHECK();
     if (int rc = a.xchg(a.xchg_user, a.table, (size_t)a.tp * b * 2, s)) return rc;
     hipLaunchKernelGGL(smp_tp_pick_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, a.table, b, a.tp, gbase, V, bm, a.bm_words, a.last_set, a.step,
-                       a.adv_pos, a.adv_len, a.out);
+                       a.adv_pos, a.adv_len, a.out, (int)!vfy);
   }
   OM_LAUNCH_CHECK();
   return 0;
@@ -554,6 +589,13 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
 
 int launch_sample_rewind(uint32_t* bitmap, int bm_words, int* last_set, int* step, int b, int n, hipStream_t s) {
   hipLaunchKernelGGL(smp_rewind_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, bitmap, bm_words, last_set, step, b, n);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_sample_rewind_verify(uint32_t* bitmap, int* vlast, int* step, int cnt, int r, hipStream_t s) {
+  OM_CHECK(vlast && step && r >= 0 && r <= cnt && cnt <= SMP_VERIFY_ROWS, "launch_sample_rewind_verify: bad argument");
+  hipLaunchKernelGGL(smp_rewind_verify_kernel, dim3(1), dim3(64), 0, s, bitmap, vlast, step, cnt, r);
   OM_LAUNCH_CHECK();
   return 0;
 }

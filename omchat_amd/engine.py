@@ -376,17 +376,20 @@ class Engine:
         check(self.lib.omchat_decode_step(self.h, ptr(tk), b, ptr(logits), ptr(nxt), cur_stream()))
         return nxt, logits
 
-    def decode_verify(self, tokens, keep_all=False, want_logits=False):
+    def decode_verify(self, tokens, keep_all=False, want_logits=False, sample=False):
         """Prompt-lookup verify step (include/omchat_hip.h: omchat_decode_verify): tokens = [last emitted token, draft...] (2..16 ids) of
         sequence 0 through the decoder at once.  -> (picks int32 [T] on the device, n accepted drafts); the cache keeps L + 1 + n slots
-        (all T with keep_all).  want_logits: -> (picks, n, rank-local logits fp32 [T, V / tp])."""
+        (all T with keep_all).  want_logits: -> (picks, n, rank-local logits fp32 [T, V / tp]).  sample=True (set_sampling on): the picks
+        are the ids plain sampled steps of sequence 0 would draw at those positions, and the n + 1 emitted ones are committed to its
+        step counter and seen set; kv_rewind(1, r) straight afterwards takes the last r <= n + 1 of them back."""
         torch = _torch()
         tk = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous().view(-1)
         T = tk.shape[0]
         logits = torch.empty(T, self.c.t_vocab, dtype=torch.float32, device=self.device) if want_logits else None
         picks = torch.empty(T, dtype=torch.int32, device=self.device)
         n = C.c_int(0)
-        check(self.lib.omchat_decode_verify(self.h, ptr(tk), T, ptr(logits), ptr(picks), C.byref(n), 1 if keep_all else 0, cur_stream()))
+        check(self.lib.omchat_decode_verify(self.h, ptr(tk), T, ptr(logits), ptr(picks), C.byref(n), (1 if keep_all else 0) | (2 if sample else 0),
+                                            cur_stream()))
         st = self._lookup_st
         st["verify_steps"] += 1; st["drafted"] += T - 1; st["accepted"] += n.value
         return (picks, n.value, logits) if want_logits else (picks, n.value)
@@ -507,6 +510,17 @@ class Engine:
 
     def sampling_off(self):
         check(self.lib.omchat_set_sampling(self.h, 0, 0, 1.0, 0, 1.0, 1.0, None, None, cur_stream()))
+
+    def sampling_state(self, row=0):
+        """(step counter, sorted seen ids) of a row while set_sampling is on; the ids are this rank's slice of the seen set, as global
+        ids (test accessor; synchronises)"""
+        torch = _torch()
+        step = C.c_int(0)
+        words = torch.zeros((self.c.t_vocab + 31) // 32, dtype=torch.int32)
+        check(self.lib.omchat_read_sampling_state(self.h, int(row), C.byref(step), ptr(words)))
+        base = self.tp_rank * self.c.t_vocab
+        seen = [base + 32 * w + i for w, v in enumerate(words.tolist()) if v for i in range(32) if (v >> i) & 1]
+        return step.value, seen
 
     def sample(self, logits):
         """the sampled counterpart of argmax (first token after the prefill): rank-local logits [b, V / tp] -> int32 [b]"""

@@ -57,13 +57,15 @@ class PromptLookupDrafter:
 
 
 def lookup_loop(engine, input_ids, tok, max_new_tokens, eos, num_tokens, max_ngram, vocab, streamer=None, stopping_criteria=None,
-                draft_hook=None, max_verify=MAX_LOOKUP_TOKENS + 1):
+                draft_hook=None, max_verify=MAX_LOOKUP_TOKENS + 1, sample=False):
     """Batch 1, after the prefill and the first pick `tok` (int): returns the generated ids (list of int), the same ids the greedy loop
     of generate() returns, EOS kept.  Each step drafts from the ids so far; a non-empty draft is verified in one Engine.decode_verify
     (the emitted tokens are the picks up to and including the first rejected position), an empty one takes a plain decode_step.  The
     emitted tokens go to EOS handling / stopping_criteria / streamer one by one; at the first stop the rest of the step is dropped and
     the cache trimmed to match (kv_rewind), as the greedy loop leaves it.  max_verify: the most tokens one verify step takes (the draft is
-    cut to max_verify - 1; Engine.verify_max_tokens).  draft_hook(ids, k) -> list replaces the drafter (measurement)."""
+    cut to max_verify - 1; Engine.verify_max_tokens).  draft_hook(ids, k) -> list replaces the drafter (measurement).  sample=True (the
+    engine's sampler is on and `tok` came from it): the verify steps take their sampled form, whose picks are the ids plain sampled steps
+    would draw, so the loop returns the ids of the plain sampled loop with the same seed; nothing else changes."""
     prompt = input_ids.detach().cpu()
     drafter = PromptLookupDrafter(prompt[0].tolist(), num_tokens, max_ngram, eos, vocab)
     max_length = prompt.shape[1] + max_new_tokens
@@ -92,7 +94,8 @@ def lookup_loop(engine, input_ids, tok, max_new_tokens, eos, num_tokens, max_ngr
             draft = draft_hook(drafter.ids, budget) if draft_hook is not None else drafter.candidates(max_length)
             draft = draft[:budget]
         if draft:
-            picks, n = engine.decode_verify([new[-1]] + [int(d) for d in draft])
+            tokens = [new[-1]] + [int(d) for d in draft]
+            picks, n = engine.decode_verify(tokens, sample=True) if sample else engine.decode_verify(tokens)
             pending = [int(x) for x in picks[:n + 1].tolist()]
         else:
             nxt, _ = engine.decode_step(torch.tensor([new[-1]], dtype=torch.int32))

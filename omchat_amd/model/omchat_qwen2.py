@@ -260,20 +260,25 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                     **{name: None if v is None else float(v) for name, v in flt.items()})
 
     def _lookup_params(self, input_ids, kwargs, do_sample, num_beams):
-        """(k, m) of prompt-lookup decoding, or None when prompt_lookup_num_tokens is not set (argument or generation_config); every
+        """(k, m, sample) of prompt-lookup decoding, or None when prompt_lookup_num_tokens is not set (argument or generation_config); every
         refusal is raised here, before any work is enqueued"""
         from ..lookup import MAX_LOOKUP_TOKENS
         gc = self.generation_config
         k = kwargs.pop("prompt_lookup_num_tokens", None)
         m = kwargs.pop("max_matching_ngram_size", None)
+        smp = kwargs.pop("prompt_lookup_sample", None)
         k = k if k is not None else getattr(gc, "prompt_lookup_num_tokens", None)
         if k is None:
             return None
         m = m if m is not None else (getattr(gc, "max_matching_ngram_size", None) or 2)
+        smp = bool(smp if smp is not None else getattr(gc, "prompt_lookup_sample", False))
         if input_ids.shape[0] > 1:
             raise ValueError("assisted generate is only supported for batch_size = 1")
-        if do_sample:
-            raise NotImplementedError("prompt-lookup decoding with do_sample=True is not implemented: it verifies greedy picks only")
+        if num_beams > 1 and smp:
+            raise NotImplementedError("prompt_lookup_sample=True with num_beams > 1 is not implemented: prompt-lookup decoding has no beams")
+        if do_sample and not smp:
+            raise NotImplementedError("prompt-lookup decoding with do_sample=True is not implemented without prompt_lookup_sample=True: it "
+                                      "verifies greedy picks only unless that keyword asks for the sampled verify step")
         if num_beams > 1:
             raise NotImplementedError("prompt-lookup decoding with num_beams > 1 is not implemented")
         if getattr(self.engine, "_fp8_kv", False):
@@ -285,7 +290,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")
         if int(k) > MAX_LOOKUP_TOKENS:
             raise ValueError(f"prompt_lookup_num_tokens={k} exceeds the limit of {MAX_LOOKUP_TOKENS} draft tokens per verify step")
-        return int(k), int(m)
+        return int(k), int(m), bool(do_sample and smp)
 
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
@@ -299,7 +304,9 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         taken from the call or generation_config) -- keyed by `seed` (or one drawn from `generator`); same ids for the same seed.
         prompt_lookup_num_tokens=k (max_matching_ngram_size=m, default 2; both also read from generation_config): HF's prompt-lookup
         decoding for b = 1, greedy (omchat_amd/lookup.py): drafts of up to k ids copied from the prompt + generated ids are verified in
-        one verify step each.  Exactness: the verify rows go through the batched (MFMA-form) GEMVs and plain steps through the batch-1
+        one verify step each.  With do_sample=True it needs prompt_lookup_sample=True (also read from generation_config; no effect when
+        greedy): every verify row is then sampled on the device with the key and seen set the plain sampled loop would have at that
+        position, so the call returns the ids of the same call without prompt_lookup_num_tokens ("Sampling").  Exactness: the verify rows go through the batched (MFMA-form) GEMVs and plain steps through the batch-1
         whole-row forms, so a position's logits can differ in the last bits and the ids can differ from greedy only at near-ties, as in
         HF's assisted decoding in fp16.
         reuse_cache=True (also read from generation_config; b = 1, num_beams = 1, no padding): multi-turn chat.  The
@@ -399,7 +406,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             from ..lookup import lookup_loop
             gen = lookup_loop(self.engine, input_ids, int(tok.view(-1)[0]), max_new_tokens, eos, lookup[0], lookup[1],
                               self.engine.c.t_vocab_total, streamer, stopping_criteria, getattr(self, "_lookup_draft_hook", None),
-                              self.engine.verify_max_tokens())
+                              self.engine.verify_max_tokens(), sample=lookup[2])
             if streamer is not None:
                 streamer.end()
             self._record_prefix(prompt_slots, gen)
