@@ -330,6 +330,27 @@ int omchat_enable_fp8_decode(omchat_ctx* ctx, int on);
  * (tests/test_gpu_mxfp4.py, tests/test_gpu_mxfp4_batched.py). */
 int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int mode);
 
+/* ---- the weight format of a decode step ---------------------------------------------------------------------------- */
+/* The formats a decode-side pass can stream its five projections in (qkv, o_proj, gate|up, down_proj, lm_head). */
+enum omchat_weight_format {
+  OMCHAT_WFMT_16 = 0,             /* the 16-bit weights, row-major */
+  OMCHAT_WFMT_16_PACKED = 1,      /* their packed replica for batched steps */
+  OMCHAT_WFMT_E4M3 = 2,           /* omchat_enable_fp8_decode */
+  OMCHAT_WFMT_MXFP4 = 3,          /* omchat_enable_mxfp4_decode, row-major */
+  OMCHAT_WFMT_MXFP4_PACKED = 4,   /* its packed copy (mode 2) */
+  OMCHAT_WFMT_COUNT = 5
+};
+/* The one rule (host-only, no context): the format a step of `rows` rows streams, and in *x_pack_nb (may be NULL) the block count of the
+ * packed activation layout its GEMVs run on (0 = row-major activations, 1, or 2 for rows > 16).  fp8_on / mxfp4_mode: what the two enable
+ * calls set (never both); packed16_ready: the 16-bit packed replica is built and current; geometry_ok: hidden_size, heads x 128 and
+ * intermediate_size are each a multiple of 64.
+ *   rows == 1:        e4m3 if fp8_on, else MXFP4 if mxfp4_mode >= 1, else 16-bit
+ *   2 <= rows <= 32:  packed activations when geometry_ok; the weights packed MXFP4 in mode 2, else 16-bit packed if that replica is
+ *                     ready and the activations are packed, else 16-bit.  (Mode 2 without geometry_ok -- refused by the enable call --
+ *                     answers packed MXFP4 with *x_pack_nb = 0, which every step refuses.)
+ *   rows > 32:        16-bit, row-major activations (with mode 2 on, the step entries refuse such a step up front) */
+int omchat_decode_weight_format(int rows, int fp8_on, int mxfp4_mode, int packed16_ready, int geometry_ok, int* x_pack_nb);
+
 /* ---- fp8 KV cache and fp8 x fp8 prefill GEMMs (BASELINE configs[4]: long video context, "fp8 MFMA weights") ------ */
 /* omchat_enable_fp8_kv: after the next prefill the decode steps read keys and values as OCP e4m3 bytes (57 344 -> 28 672 bytes per
  * cached token, + 2 x 4 kv heads x 28 layers fp32 scales) with one scale per (layer, sequence, kv head, position) = absmax / 448; the

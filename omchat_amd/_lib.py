@@ -101,6 +101,7 @@ _SIGS = {
     "omchat_op_quant_fp8": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_op_gemv_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "omchat_enable_mxfp4_decode": (_i, [_vp, _i]),
+    "omchat_decode_weight_format": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
     "omchat_op_quant_mxfp4": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_op_gemv_mxfp4": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "omchat_op_gemv_mxfp4_rows": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),

@@ -112,33 +112,30 @@ struct omchat_ctx {
   // weights (device, compute dtype)
   struct VitLayer { void *ls1, *ls2, *n1, *n2, *n1b, *n2b, *wqkv, *qn, *kn, *wproj, *bproj, *w1, *b1, *w2, *b2; };
   struct DecLayer { void *ln1, *ln2, *wqkv, *bqkv, *wo, *wgu, *wd; };
-  // weight-only fp8 replica of the decode-streamed decoder weights (omchat_enable_fp8_decode): OCP e4m3 bytes + one fp32
-  // scale per output row; batch-1 decode steps stream these instead of the 16-bit weights, prefill keeps the 16-bit ones
-  struct DecLayer8 { void *wqkv, *wo, *wgu, *wd; float *sqkv, *so, *sgu, *sd; };
-  std::vector<DecLayer8> dl8;
-  // packed replica of the same weights for BATCHED decode steps (2 <= b <= 32): MFMA fragment order, every wave load 1 KiB contiguous
-  // (gemv.hip: gemv_pk_kernel; +14 GB at OmChat-13B, built on the first batched step; omchat_op_set_tuning key 6 = 0 disables it)
-  struct DecLayerP { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; };
-  std::vector<DecLayerP> dlp;
-  void* t_lmP = nullptr;
-  bool pk_ready = false, pk_unavailable = false;
-  void* t_lm8 = nullptr; float* t_lm8_s = nullptr;
-  bool fp8_decode = false, fp8_stale = false;
-  // weight-only MXFP4 replica of the same weights (omchat_enable_mxfp4_decode): two e2m1 codes per byte [N][K / 2] + one
-  // e8m0 byte per 32 consecutive k [N][K / 32], in the op-level layout (the whole-row GEMV forms read a row's bytes contiguously already)
-  struct DecLayer4 { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; unsigned char *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr; };
-  std::vector<DecLayer4> dl4;
-  void* t_lm4 = nullptr; unsigned char* t_lm4_s = nullptr;
-  bool mxfp4_decode = false, mxfp4_stale = false;
-  // mode 2 of omchat_enable_mxfp4_decode: the same codes and scales once more in the packed layout of the batched GEMV forms (common.h:
-  // packed_w4_index / packed_s4_index; launch_pack_w4 shuffles the row-major replica, the quantiser stays the one source of the codes).
-  // Steps with 2 <= b <= 32 rows (batched, masked, beam, verify) stream it; built all-or-nothing, re-packed in place after omchat_load_tensor
-  std::vector<DecLayer4> dl4p;
-  void* t_lm4P = nullptr; unsigned char* t_lm4P_s = nullptr;
-  bool mxfp4_batched = false, mxfp4p_stale = false;
-  // the weight format of a decode step of b rows: MXFP4 at b == 1 in both modes, at 2 <= b <= 32 in mode 2
-  bool mx4_rows_ok(int b) const { return !(mxfp4_decode && mxfp4_batched && b > 32); }
-  bool mx4_step(int b) const { return mxfp4_decode && (b == 1 || (mxfp4_batched && b >= 2 && b <= 32)); }
+  // The decode step streams five projections per pass -- qkv, o_proj, gate|up, down_proj of every layer and the lm_head -- and can read each
+  // of them in one of the formats of omchat_weight_format (include/omchat_hip.h).  wt[format] is that format's table: layers * 4 + 1
+  // references in layer order, the lm_head last, plus the replica's state.
+  //   16-bit         a view of dl[] / t_lm filled at context build: never stale.  Prefill and the experiments launches read dl[] itself
+  //   16-bit packed  MFMA fragment order for BATCHED steps (2 <= b <= 32), every wave load 1 KiB contiguous (gemv.hip: gemv_pk_kernel; +14 GB at
+  //                  OmChat-13B, built on the first batched step; omchat_op_set_tuning key 6 = 0 disables it).  Optional: when it does not
+  //                  fit, the context remembers that (W_UNAVAILABLE) and batched steps keep streaming the row-major weights
+  //   e4m3           omchat_enable_fp8_decode: OCP e4m3 bytes + one fp32 scale per output row (batch-1 steps; the fp8 x fp8 prefill GEMMs too)
+  //   MXFP4          omchat_enable_mxfp4_decode: two e2m1 codes per byte [N][K / 2] + one e8m0 byte per 32 consecutive
+  //                  k [N][K / 32], row-major (batch-1 steps)
+  //   MXFP4 packed   mode 2: the same codes and scales in the packed layout of the batched GEMV forms (common.h: packed_w4_index /
+  //                  packed_s4_index; launch_pack_w4 shuffles the row-major replica, the quantiser stays the one source of the codes)
+  // A replica's buffers are taken all or nothing (alloc_group) and rebuilt IN PLACE after omchat_load_tensor: same device pointers, so a
+  // captured decode graph stays valid (model.hip: build_replica).
+  enum Proj { P_QKV = 0, P_O = 1, P_GU = 2, P_DOWN = 3, P_LM = 4 };      // P_LM: the one entry behind the layers
+  struct WRef { void* W = nullptr; int ldw = 0; float* w_scale = nullptr; unsigned char* mx_scale = nullptr; int packed = 0; };
+  enum WState { W_ABSENT = 0, W_BUILT, W_STALE, W_UNAVAILABLE };      // (W_UNAVAILABLE: the 16-bit packed replica did not fit, stop trying)
+  struct WTable { std::vector<WRef> e; int state = W_ABSENT; };
+  WTable wt[OMCHAT_WFMT_COUNT];
+  const WRef* layer_w(int fmt, int layer) const { return &wt[fmt].e[(size_t)layer * 4]; }      // [P_QKV .. P_DOWN]
+  const WRef& lm_w(int fmt) const { return wt[fmt].e.back(); }
+  bool built(int fmt) const { return wt[fmt].state == W_BUILT; }
+  bool fp8_decode = false;
+  int mxfp4_mode = 0;      // omchat_enable_mxfp4_decode: 0 = off, 1 = batch-1 steps, 2 = steps of 2 <= b <= 32 rows as well
   // BASELINE configs[4]: fp8 KV cache for decode (e4m3 bytes in the layout of the 16-bit cache + one fp32 scale per (layer, sequence,
   // kv head, position)) and fp8 x fp8 MFMA prefill GEMMs (qkv and gate|up: the activations come quantised per token from the RMSNorm)
   void *k8cache = nullptr, *v8cache = nullptr;
@@ -151,7 +148,7 @@ struct omchat_ctx {
   // buffers so that every kernel argument is replay-invariant; the split-KV attention grid is captured for `cap_len` keys
   // (empty splits exit at once) and the graph is re-captured when a sequence outgrows it.
   struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0; };
-  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0)
+  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0), the weights by the step's format
   bool graph_on = false;
   hipStream_t graph_stream = nullptr;
   hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;
@@ -351,6 +348,11 @@ struct omchat_ctx {
   int allreduce(void* buf, size_t count, hipStream_t s) { return allreduce_any(buf, count, dt, s); }
   int allreduce_f32(float* buf, size_t count, hipStream_t s) { return allreduce_any(buf, count, OMCHAT_F32, s); }
 };
+
+// the weight operand of a GEMV from a table reference: W, ldw, the scales and w_packed -- nothing else
+inline void use_weight(GemvArgs& g, const omchat_ctx::WRef& w) {
+  g.W = w.W; g.ldw = w.ldw; g.w_scale = w.w_scale; g.mx_scale = w.mx_scale; g.w_packed = w.packed;
+}
 
 // ---- model.hip
 void drop_decode_graphs(omchat_ctx* ctx);      // pick parameters live in the kernel arguments of the captured decode graphs: a change drops them

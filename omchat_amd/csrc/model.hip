@@ -113,6 +113,21 @@ int add_route(omchat_ctx* ctx, const std::string& name, void** slot, int64_t row
   return 0;
 }
 
+// the five projections a decode step streams, as W [N][K]: the only place their shapes are written
+struct ProjShape { int N, K; };
+ProjShape proj_shape(const omchat_ctx* ctx, int which) {
+  const int H = ctx->c.t_hidden, It = ctx->c.t_mlp;
+  switch (which) {
+    case omchat_ctx::P_QKV: return {ctx->t_qkvdim, H};
+    case omchat_ctx::P_O: return {H, ctx->t_qdim};
+    case omchat_ctx::P_GU: return {2 * It, H};
+    case omchat_ctx::P_DOWN: return {H, It};
+    default: return {ctx->c.t_vocab, H};      // P_LM
+  }
+}
+// entry j of a format's table (layers * 4 + 1 of them) is projection j % 4 of layer j / 4; the last one is the lm_head
+ProjShape entry_shape(const omchat_ctx* ctx, size_t j) { return proj_shape(ctx, j == (size_t)ctx->c.t_layers * 4 ? omchat_ctx::P_LM : (int)(j % 4)); }
+
 int build(omchat_ctx* ctx) {
   const omchat_config& c = ctx->c;
   const int C = c.v_hidden, I = c.v_mlp;
@@ -193,6 +208,12 @@ int build(omchat_ctx* ctx) {
       TRY(add_route(ctx, P + "input_layernorm.weight", &L.ln1, 1, H, 0.05f, 1.f));
       TRY(add_route(ctx, P + "post_attention_layernorm.weight", &L.ln2, 1, H, 0.05f, 1.f));
     }
+    // the 16-bit entry of the weight-format table: a view of the above
+    omchat_ctx::WTable& w16 = ctx->wt[OMCHAT_WFMT_16];
+    for (auto& L : ctx->dl) for (void* w : {L.wqkv, L.wo, L.wgu, L.wd}) w16.e.push_back({w});
+    w16.e.push_back({ctx->t_lm});
+    for (size_t j = 0; j < w16.e.size(); ++j) w16.e[j].ldw = entry_shape(ctx, j).K;
+    w16.state = omchat_ctx::W_BUILT;
     // RoPE table: Qwen2RotaryEmbedding (modeling_qwen2.py:64-102): inv_freq and angles in fp32, cos/sin fp32
     std::vector<float> tab((size_t)c.max_seq * 128);
     for (int i = 0; i < 64; ++i) {
@@ -374,10 +395,8 @@ extern "C" int omchat_load_tensor(omchat_ctx* ctx, const char* name, const void*
     for (int i = 0; i < ndim && !split_ok; ++i) { lead *= shape[i]; split_ok = lead == r.rows; }
     OM_CHECK(split_ok, std::string("shape mismatch for ") + name + ": expected [" + std::to_string(r.rows) + ", " + std::to_string(r.cols) + "]");
   }
-  if (!ctx->dl8.empty()) ctx->fp8_stale = true;      // the e4m3 replica no longer matches the 16-bit weights
-  if (!ctx->dl4.empty()) ctx->mxfp4_stale = true;    // nor does the MXFP4 replica
-  if (!ctx->dl4p.empty()) ctx->mxfp4p_stale = true;  // nor its packed twin
-  ctx->pk_ready = false;                              // nor does the packed replica
+  for (int f = 0; f < OMCHAT_WFMT_COUNT; ++f)      // no replica matches the 16-bit weights any more (the 16-bit entry is a view of them)
+    if (f != OMCHAT_WFMT_16 && ctx->built(f)) ctx->wt[f].state = omchat_ctx::W_STALE;
   if (src_dtype == ctx->dt) return place(ctx, r, data);
   OM_CHECK(src_dtype == OMCHAT_F32, "source dtype must be the context dtype or OMCHAT_F32");
   TRY(ensure_stage(ctx, (size_t)n * 4, (size_t)n * 2));
@@ -920,47 +939,62 @@ extern "C" int omchat_splice_gather(omchat_ctx* ctx, const int32_t* src_index, c
 // ---------------------------------------------------------------------------------------------------------
 // decoder
 // ---------------------------------------------------------------------------------------------------------
-static int lm_head_rows(omchat_ctx* ctx, const void* hidden, int n, float* logits, hipStream_t s, bool fp8 = false, bool packed = false, bool mx4 = false) {
+// hidden [n][H] -> logits through the lm_head reference of the caller's format; x_packed: hidden is in the packed x layout (n <= 32)
+static int lm_head_rows(omchat_ctx* ctx, const void* hidden, int n, float* logits, hipStream_t s, const omchat_ctx::WRef& lm, bool x_packed = false) {
   const int H = ctx->c.t_hidden, V = ctx->c.t_vocab;
   for (int r0 = 0; r0 < n; r0 += 32) {
     const int R = std::min(32, n - r0);
-    GemvArgs g{(const char*)hidden + (size_t)r0 * H * 2, H, ctx->t_lm, H, logits + (size_t)r0 * V, V, R, V, H, nullptr, nullptr, 0, EPI_NONE, 1};
-    if (fp8 && n == 1) { g.W = ctx->t_lm8; g.w_scale = ctx->t_lm8_s; }
-    if (mx4 && n == 1) { g.W = ctx->t_lm4; g.ldw = H / 2; g.mx_scale = ctx->t_lm4_s; }
-    if (packed) {          // hidden is in the packed x layout (n <= 32)
-      g.x_packed = 1;
-      if (mx4) { g.W = ctx->t_lm4P; g.ldw = H / 2; g.mx_scale = ctx->t_lm4P_s; g.w_packed = 1; }      // mode 2: the packed MXFP4 replica
-      else if (ctx->pk_ready) { g.W = ctx->t_lmP; g.w_packed = 1; }
-    }
+    GemvArgs g{(const char*)hidden + (size_t)r0 * H * 2, H, nullptr, 0, logits + (size_t)r0 * V, V, R, V, H, nullptr, nullptr, 0, EPI_NONE, 1};
+    use_weight(g, lm);
+    g.x_packed = x_packed;
     TRY(launch_gemv(ctx->dt, g, s));
   }
   return 0;
 }
 
-static int ensure_fp8_weights(omchat_ctx* ctx) {
-  const omchat_config& c = ctx->c;
-  if (ctx->dl8.empty() || ctx->fp8_stale) {
-    OM_CHECK(omchat_weights_missing(ctx) == 0, "load the weights before quantising them");
-    const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
-    ctx->dl8.resize(c.t_layers);
-    auto quant = [&](const void* W, int N, int K, void** w8, float** sc) -> int {
-      if (!*w8) {      // first build allocates; a rebuild after omchat_load_tensor re-quantises in place
-        TRY(ctx->alloc(w8, (size_t)N * K));
-        TRY(ctx->alloc((void**)sc, (size_t)N * 4));
-      }
-      return launch_quant_fp8_rows(ctx->dt, W, K, N, K, *w8, K, *sc, nullptr);
-    };
-    for (int i = 0; i < c.t_layers; ++i) {
-      auto& L = ctx->dl[i]; auto& Q = ctx->dl8[i];
-      TRY(quant(L.wqkv, qkvd, H, &Q.wqkv, &Q.sqkv));
-      TRY(quant(L.wo, H, qd, &Q.wo, &Q.so));
-      TRY(quant(L.wgu, 2 * It, H, &Q.wgu, &Q.sgu));
-      TRY(quant(L.wd, H, It, &Q.wd, &Q.sd));
+// (Re)build one replica of the decode-streamed weights: the layers * 4 + 1 entries of its table, by proj_shape.  The first build takes every
+// buffer or none and commits the table only then (a half-built table must never reach a launch); a rebuild after omchat_load_tensor fills
+// the same buffers in place (same device pointers: a captured graph stays valid).  Synchronous, never inside a graph capture.
+// The packed MXFP4 replica is a byte shuffle of the row-major one, which is therefore brought up to date first.
+static int build_replica(omchat_ctx* ctx, int fmt) {
+  omchat_ctx::WTable& T = ctx->wt[fmt];
+  if (T.state == omchat_ctx::W_BUILT) return 0;
+  const bool f8 = fmt == OMCHAT_WFMT_E4M3, mx = fmt == OMCHAT_WFMT_MXFP4, mxp = fmt == OMCHAT_WFMT_MXFP4_PACKED, p16 = fmt == OMCHAT_WFMT_16_PACKED;
+  if (f8 || mx) OM_CHECK(omchat_weights_missing(ctx) == 0, "load the weights before quantising them");
+  if (mx) OM_CHECK(ctx->c.t_hidden % 32 == 0 && ctx->t_qdim % 32 == 0 && ctx->c.t_mlp % 32 == 0,
+                   "MXFP4 decode: every streamed K (hidden_size, heads x 128, intermediate_size) must be a multiple of 32");
+  if (mxp) TRY(build_replica(ctx, OMCHAT_WFMT_MXFP4));
+  const std::vector<omchat_ctx::WRef>& src = ctx->wt[mxp ? OMCHAT_WFMT_MXFP4 : OMCHAT_WFMT_16].e;
+  if (T.e.empty()) {
+    std::vector<omchat_ctx::WRef> fresh(src.size());
+    std::vector<void**> slots;
+    std::vector<size_t> sizes;
+    for (size_t j = 0; j < fresh.size(); ++j) {
+      const size_t N = entry_shape(ctx, j).N, K = entry_shape(ctx, j).K;
+      omchat_ctx::WRef& r = fresh[j];
+      r.ldw = (int)(mx || mxp ? K / 2 : K);
+      r.packed = p16 || mxp;
+      slots.push_back(&r.W); sizes.push_back(p16 ? N * K * 2 : f8 ? N * K : N * (K / 2));
+      if (f8) { slots.push_back((void**)&r.w_scale); sizes.push_back(N * 4); }
+      if (mx || mxp) { slots.push_back((void**)&r.mx_scale); sizes.push_back(N * (K / 32)); }
     }
-    TRY(quant(ctx->t_lm, c.t_vocab, H, &ctx->t_lm8, (float**)&ctx->t_lm8_s));
-    OM_HIP(hipDeviceSynchronize());
-    ctx->fp8_stale = false;
+    if (ctx->alloc_group(slots, sizes)) {
+      if (p16) { T.state = omchat_ctx::W_UNAVAILABLE; return 0; }      // optional: batched steps keep streaming the row-major weights
+      if (mxp) omchat_set_error("omchat_enable_mxfp4_decode: the packed MXFP4 replica of mode 2 does not fit in device memory (hipMalloc failed)");
+      return 2;
+    }
+    T.e.swap(fresh);
   }
+  for (size_t j = 0; j < T.e.size(); ++j) {
+    const int N = entry_shape(ctx, j).N, K = entry_shape(ctx, j).K;
+    const omchat_ctx::WRef& w = src[j]; const omchat_ctx::WRef& r = T.e[j];
+    if (f8) TRY(launch_quant_fp8_rows(ctx->dt, w.W, K, N, K, r.W, K, r.w_scale, nullptr));
+    else if (mx) TRY(launch_quant_mxfp4_rows(ctx->dt, w.W, K, N, K, r.W, K / 2, r.mx_scale, nullptr));
+    else if (mxp) TRY(launch_pack_w4(w.W, w.mx_scale, N, K, r.W, r.mx_scale, nullptr));
+    else TRY(launch_pack_w(ctx->dt, w.W, K, N, K, r.W, nullptr));
+  }
+  OM_HIP(hipDeviceSynchronize());
+  T.state = omchat_ctx::W_BUILT;
   return 0;
 }
 
@@ -968,77 +1002,9 @@ extern "C" int omchat_enable_fp8_decode(omchat_ctx* ctx, int on) {
   OM_CHECK(ctx, "null context");
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
   if (!on) { ctx->fp8_decode = false; return 0; }
-  OM_CHECK(!ctx->mxfp4_decode, "MXFP4 decode is on: one weight format per step (omchat_enable_mxfp4_decode(ctx, 0) first)");
-  TRY(ensure_fp8_weights(ctx));
+  OM_CHECK(!ctx->mxfp4_mode, "MXFP4 decode is on: one weight format per step (omchat_enable_mxfp4_decode(ctx, 0) first)");
+  TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));
   ctx->fp8_decode = true;
-  return 0;
-}
-
-// MXFP4 replica of the decode-streamed weights: built once, re-quantised in place (same device pointers: a captured graph stays valid) after
-// omchat_load_tensor
-// packed: also (re)build the packed twin that steps of 2 <= b <= 32 rows stream in mode 2 -- a byte shuffle of the row-major replica, which is
-// therefore brought up to date first.  Its buffers are taken all or nothing: a half-built table must never reach a launch.
-static int ensure_mxfp4_weights(omchat_ctx* ctx, bool packed = false) {
-  const omchat_config& c = ctx->c;
-  if (ctx->dl4.empty() || ctx->mxfp4_stale) {
-    OM_CHECK(omchat_weights_missing(ctx) == 0, "load the weights before quantising them");
-    const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
-    OM_CHECK(H % 32 == 0 && qd % 32 == 0 && It % 32 == 0, "MXFP4 decode: every streamed K (hidden_size, heads x 128, intermediate_size) must be a multiple of 32");
-    ctx->dl4.resize(c.t_layers);
-    auto quant = [&](const void* W, int N, int K, void** w4, unsigned char** sc) -> int {
-      if (!*w4) {
-        TRY(ctx->alloc(w4, (size_t)N * (K / 2)));
-        TRY(ctx->alloc((void**)sc, (size_t)N * (K / 32)));
-      }
-      return launch_quant_mxfp4_rows(ctx->dt, W, K, N, K, *w4, K / 2, *sc, nullptr);
-    };
-    for (int i = 0; i < c.t_layers; ++i) {
-      auto& L = ctx->dl[i]; auto& Q = ctx->dl4[i];
-      TRY(quant(L.wqkv, qkvd, H, &Q.wqkv, &Q.sqkv));
-      TRY(quant(L.wo, H, qd, &Q.wo, &Q.so));
-      TRY(quant(L.wgu, 2 * It, H, &Q.wgu, &Q.sgu));
-      TRY(quant(L.wd, H, It, &Q.wd, &Q.sd));
-    }
-    TRY(quant(ctx->t_lm, c.t_vocab, H, &ctx->t_lm4, &ctx->t_lm4_s));
-    OM_HIP(hipDeviceSynchronize());
-    ctx->mxfp4_stale = false;
-  }
-  if (packed && (ctx->dl4p.empty() || ctx->mxfp4p_stale)) {
-    const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim, V = c.t_vocab;
-    if (ctx->dl4p.empty()) {
-      std::vector<omchat_ctx::DecLayer4> fresh(c.t_layers);
-      void* lmP = nullptr; unsigned char* lmS = nullptr;
-      std::vector<void**> slots;
-      std::vector<size_t> sizes;
-      auto want = [&](void** w, unsigned char** sc, int N, int K) {
-        slots.push_back(w); sizes.push_back((size_t)N * (K / 2));
-        slots.push_back((void**)sc); sizes.push_back((size_t)N * (K / 32));
-      };
-      for (auto& P : fresh) { want(&P.wqkv, &P.sqkv, qkvd, H); want(&P.wo, &P.so, H, qd); want(&P.wgu, &P.sgu, 2 * It, H); want(&P.wd, &P.sd, H, It); }
-      want(&lmP, &lmS, V, H);
-      if (ctx->alloc_group(slots, sizes)) {
-        omchat_set_error("omchat_enable_mxfp4_decode: the packed MXFP4 replica of mode 2 does not fit in device memory (hipMalloc failed)");
-        return 2;
-      }
-      ctx->dl4p.swap(fresh);
-      ctx->t_lm4P = lmP; ctx->t_lm4P_s = lmS;
-    }
-    for (int i = 0; i < c.t_layers; ++i) {
-      auto& Q = ctx->dl4[i]; auto& P = ctx->dl4p[i];
-      TRY(launch_pack_w4(Q.wqkv, Q.sqkv, qkvd, H, P.wqkv, P.sqkv, nullptr));
-      TRY(launch_pack_w4(Q.wo, Q.so, H, qd, P.wo, P.so, nullptr));
-      TRY(launch_pack_w4(Q.wgu, Q.sgu, 2 * It, H, P.wgu, P.sgu, nullptr));
-      TRY(launch_pack_w4(Q.wd, Q.sd, H, It, P.wd, P.sd, nullptr));
-    }
-    TRY(launch_pack_w4(ctx->t_lm4, ctx->t_lm4_s, V, H, ctx->t_lm4P, ctx->t_lm4P_s, nullptr));
-    OM_HIP(hipDeviceSynchronize());
-    ctx->mxfp4p_stale = false;
-  }
-  return 0;
-}
-// a weight reload (omchat_load_tensor) leaves the replicas stale: rebuild IN PLACE before a step streams them
-static int refresh_mxfp4_weights(omchat_ctx* ctx) {
-  if (ctx->mxfp4_decode && (ctx->mxfp4_stale || (ctx->mxfp4_batched && ctx->mxfp4p_stale))) TRY(ensure_mxfp4_weights(ctx, ctx->mxfp4_batched));
   return 0;
 }
 
@@ -1047,7 +1013,7 @@ extern "C" int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int mode) {
   OM_CHECK(ctx, "null context");
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
   OM_CHECK(mode >= 0 && mode <= 2, "mode: 0 = off, 1 = batch-1 steps, 2 = steps of up to 32 rows as well");
-  if (!mode) { ctx->mxfp4_decode = false; ctx->mxfp4_batched = false; return 0; }
+  if (!mode) { ctx->mxfp4_mode = 0; return 0; }
   OM_CHECK(!ctx->fp8_decode, "fp8 decode is on: one weight format per step (omchat_enable_fp8_decode(ctx, 0) first)");
   OM_CHECK(ctx->tp_size == 1, "MXFP4 decode under tensor parallelism is not implemented");
   if (mode == 2) {
@@ -1057,9 +1023,8 @@ extern "C" int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int mode) {
     OM_CHECK(ctx->t_qkvdim % 16 == 0 && c.t_hidden % 16 == 0 && c.t_vocab % 16 == 0,
              "MXFP4 decode mode 2: the packed path needs the qkv width, hidden_size and vocab_size each a multiple of 16");
   }
-  TRY(ensure_mxfp4_weights(ctx, mode == 2));
-  ctx->mxfp4_decode = true;
-  ctx->mxfp4_batched = mode == 2;
+  TRY(build_replica(ctx, mode == 2 ? OMCHAT_WFMT_MXFP4_PACKED : OMCHAT_WFMT_MXFP4));
+  ctx->mxfp4_mode = mode;
   return 0;
 }
 
@@ -1085,7 +1050,7 @@ extern "C" int omchat_enable_fp8_prefill(omchat_ctx* ctx, int on) {
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   if (!on) { ctx->fp8_prefill = false; return 0; }
   OM_CHECK(c.t_hidden % 128 == 0, "fp8 x fp8 prefill GEMMs need hidden_size % 128 == 0");
-  TRY(ensure_fp8_weights(ctx));
+  TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));
   if (!ctx->tw_q8) {
     const size_t R = std::max<size_t>(32, (size_t)(c.max_prefill_rows > c.max_batch ? c.max_prefill_rows : c.max_batch));
     TRY(ctx->alloc(&ctx->tw_q8, R * c.t_hidden));
@@ -1098,7 +1063,8 @@ extern "C" int omchat_enable_fp8_prefill(omchat_ctx* ctx, int on) {
 
 extern "C" int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float* logits, void* stream) {
   OM_CHECK(ctx && hidden && logits, "null argument");
-  return lm_head_rows(ctx, hidden, n, logits, (hipStream_t)stream);
+  OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
+  return lm_head_rows(ctx, hidden, n, logits, (hipStream_t)stream, ctx->lm_w(OMCHAT_WFMT_16));
 }
 
 // Attention form of omchat_prefill_extend (measured with tools/bench_extend.py, LOG.md).  The prefill kernel issues
@@ -1131,7 +1097,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   OM_CHECK(omchat_weights_missing(ctx) == 0, std::string(omchat_last_error()));
   for (int i = 0; i < b; ++i) OM_CHECK(lengths[i] >= 1 && lengths[i] <= S, "lengths must be in [1, S]");
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->fp8_prefill && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));      // weights were reloaded: re-quantise in place
+  if (ctx->fp8_prefill) TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));      // weights were reloaded: re-quantise in place
   const int H = c.t_hidden, It = c.t_mlp, rows = b * S, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
   const bool lead = ctx->tp_rank == 0;
 
@@ -1156,22 +1122,23 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   void* y = ctx->tw_x2;
   OM_HIP(hipMemcpyAsync(x, embeds, (size_t)rows * H * 2, hipMemcpyDeviceToDevice, s));
   // sequence-parallel norms (gemm_sp): not with the fp8 prefill (its norm writes e4m3 + scales) nor with fp32 partial sums (tuning key 29)
-  const bool sp = g_tp_sp && ctx->tp_size > 1 && !g_tp_f32 && !(ctx->fp8_prefill && !ctx->dl8.empty() && !ctx->fp8_stale);
+  const bool sp = g_tp_sp && ctx->tp_size > 1 && !g_tp_f32 && !(ctx->fp8_prefill && ctx->built(OMCHAT_WFMT_E4M3));
   for (int i = 0; i < c.t_layers; ++i) {
     auto& L = ctx->dl[i];
     char* kc = (char*)ctx->kcache + (size_t)i * ctx->cache_layer_stride() * 2;
     char* vc = (char*)ctx->vcache + (size_t)i * ctx->cache_layer_stride() * 2;
     // Qwen2DecoderLayer.forward (modeling_qwen2.py:269-298)
-    const bool f8p = ctx->fp8_prefill && !ctx->dl8.empty() && !ctx->fp8_stale;
+    const bool f8p = ctx->fp8_prefill && ctx->built(OMCHAT_WFMT_E4M3);
+    const omchat_ctx::WRef* W8 = f8p ? ctx->layer_w(OMCHAT_WFMT_E4M3, i) : nullptr;
     // fp8 x fp8 MFMA for the two column-parallel GEMMs (BASELINE configs[4]): the RMSNorm writes e4m3 + one scale per token, the
     // weights are the e4m3 replica with one scale per output row; o_proj / down_proj keep the 16-bit operands
-    auto gemm_f8 = [&](const void* W8, const float* sw, void* Cb, int ldc, int N, const void* bias, int epi) -> int {
-      GemmArgs g{ctx->tw_q8, H, W8, H, Cb, ldc, rows, N, H, bias, nullptr, nullptr, 0, epi, 0, nullptr, 0, -1, 1, ctx->tw_q8s, sw};
+    auto gemm_f8 = [&](const omchat_ctx::WRef& w, void* Cb, int ldc, int N, const void* bias, int epi) -> int {
+      GemmArgs g{ctx->tw_q8, H, w.W, H, Cb, ldc, rows, N, H, bias, nullptr, nullptr, 0, epi, 0, nullptr, 0, -1, 1, ctx->tw_q8s, w.w_scale};
       return launch_gemm(ctx->dt, g, s);
     };
     if (f8p) {
       TRY(launch_rmsnorm_q8(ctx->dt, x, H, L.ln1, ctx->tw_q8, H, ctx->tw_q8s, rows, H, c.t_eps, s));
-      TRY(gemm_f8(ctx->dl8[i].wqkv, ctx->dl8[i].sqkv, ctx->tw_qkv, qkvd, qkvd, L.bqkv, EPI_NONE));
+      TRY(gemm_f8(W8[omchat_ctx::P_QKV], ctx->tw_qkv, qkvd, qkvd, L.bqkv, EPI_NONE));
     } else {
       if (!sp || i == 0) TRY(launch_rmsnorm(ctx->dt, x, H, L.ln1, ctx->tw_xn, H, rows, H, c.t_eps, s));      // (sequence-parallel: down_proj of layer i - 1 left it)
       if (sp) TRY(gemm_after_sp(ctx, ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, rows, qkvd, H, L.bqkv, EPI_NONE, s));
@@ -1213,7 +1180,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     if (f8p) TRY(launch_rmsnorm_q8(ctx->dt, x, H, L.ln2, ctx->tw_q8, H, ctx->tw_q8s, rows, H, c.t_eps, s));
     else if (!sp) TRY(launch_rmsnorm(ctx->dt, x, H, L.ln2, ctx->tw_xn, H, rows, H, c.t_eps, s));
     ctx->prof_mark(OMCHAT_PROF_PREFILL_GATEUP, s);
-    if (f8p) TRY(gemm_f8(ctx->dl8[i].wgu, ctx->dl8[i].sgu, ctx->tw_act, It, 2 * It, nullptr, EPI_SWIGLU));
+    if (f8p) TRY(gemm_f8(W8[omchat_ctx::P_GU], ctx->tw_act, It, 2 * It, nullptr, EPI_SWIGLU));
     else if (sp) TRY(gemm_after_sp(ctx, ctx->tw_xn, H, L.wgu, H, ctx->tw_act, It, rows, 2 * It, H, nullptr, EPI_SWIGLU, s));
     else TRY(gemm(ctx, ctx->tw_xn, H, L.wgu, H, ctx->tw_act, It, rows, 2 * It, H, nullptr, nullptr, nullptr, 0, EPI_SWIGLU, s));
     ctx->prof_mark(OMCHAT_PROF_PREFILL_GATEUP, s);
@@ -1235,7 +1202,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     hipLaunchKernelGGL(last_row_index_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_len, S, b, ctx->d_idx, keep);
     TRY(launch_gather_rows(ctx->dt, ctx->d_idx, x, nullptr, ctx->tw_last, b, H, s));
     TRY(launch_rmsnorm(ctx->dt, ctx->tw_last, H, ctx->t_norm, ctx->tw_last, H, b, H, c.t_eps, s));
-    TRY(lm_head_rows(ctx, ctx->tw_last, b, logits_last, s));
+    TRY(lm_head_rows(ctx, ctx->tw_last, b, logits_last, s, ctx->lm_w(OMCHAT_WFMT_16)));
   }
   ctx->kv8_valid = false;
   ctx->beam.end();         // a prefill ends any beam search
@@ -1296,57 +1263,42 @@ extern "C" int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, i
   return 0;
 }
 
-// (re)build the packed weight replica of the decode-streamed decoder weights; synchronous, never inside a graph capture.
-// The replica is optional (+14 GB at OmChat-13B): when it does not fit, the context remembers that (pk_unavailable) and batched decode
-// keeps streaming the row-major weights (w_packed = 0), which every kernel still supports.
-static int ensure_packed(omchat_ctx* ctx) {
-  if (!g_pack_replica || ctx->pk_ready || ctx->pk_unavailable) return 0;
+// The weight format of a decode step and the packed-x block count of its GEMVs: the whole rule (include/omchat_hip.h states it)
+extern "C" int omchat_decode_weight_format(int rows, int fp8_on, int mxfp4_mode, int packed16_ready, int geometry_ok, int* x_pack_nb) {
+  const bool batched = rows >= 2 && rows <= 32;
+  const int nb = batched && geometry_ok ? (rows > 16 ? 2 : 1) : 0;
+  if (x_pack_nb) *x_pack_nb = nb;
+  if (rows == 1) return fp8_on ? OMCHAT_WFMT_E4M3 : mxfp4_mode >= 1 ? OMCHAT_WFMT_MXFP4 : OMCHAT_WFMT_16;
+  if (batched && mxfp4_mode == 2) return OMCHAT_WFMT_MXFP4_PACKED;      // (nb == 0: refused at enable time, and by the step)
+  return nb && packed16_ready ? OMCHAT_WFMT_16_PACKED : OMCHAT_WFMT_16;
+}
+// ... of a step of `rows` rows on this context; assume_packed16: as if the 16-bit packed replica were ready (does the step want it built?)
+static int step_format(const omchat_ctx* ctx, int rows, int* x_pack_nb = nullptr, bool assume_packed16 = false) {
   const omchat_config& c = ctx->c;
-  const int H = c.t_hidden, It = c.t_mlp, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
-  if (qkvd % 16 || H % 16 || c.t_vocab % 16) return 0;          // odd geometry: stay on the row-major weights
-  if (ctx->dlp.empty()) {
-    // allocate into locals and commit only when every buffer exists: a half-built table must never reach launch_pack_w
-    std::vector<omchat_ctx::DecLayerP> fresh(c.t_layers);
-    std::vector<void*> got;
-    void* lmP = nullptr;
-    auto grab = [&](void** p, size_t n) -> bool {
-      if (hipMalloc(p, n) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-      got.push_back(*p);
-      return true;
-    };
-    bool ok = true;
-    for (auto& P : fresh) {
-      ok = ok && grab(&P.wqkv, (size_t)qkvd * H * 2) && grab(&P.wo, (size_t)H * qd * 2) && grab(&P.wgu, (size_t)2 * It * H * 2) &&
-           grab(&P.wd, (size_t)H * It * 2);
-      if (!ok) break;
-    }
-    ok = ok && grab(&lmP, (size_t)c.t_vocab * H * 2);
-    if (!ok) {
-      for (void* p : got) (void)hipFree(p);
-      ctx->pk_unavailable = true;
-      return 0;
-    }
-    for (void* p : got) ctx->allocs.push_back(p);
-    ctx->bytes += (size_t)c.t_layers * ((size_t)qkvd * H + (size_t)H * qd + (size_t)2 * It * H + (size_t)H * It) * 2 + (size_t)c.t_vocab * H * 2;
-    ctx->dlp.swap(fresh);
-    ctx->t_lmP = lmP;
-  }
-  for (int i = 0; i < c.t_layers; ++i) {
-    auto& L = ctx->dl[i]; auto& P = ctx->dlp[i];
-    TRY(launch_pack_w(ctx->dt, L.wqkv, H, qkvd, H, P.wqkv, nullptr));
-    TRY(launch_pack_w(ctx->dt, L.wo, qd, H, qd, P.wo, nullptr));
-    TRY(launch_pack_w(ctx->dt, L.wgu, H, 2 * It, H, P.wgu, nullptr));
-    TRY(launch_pack_w(ctx->dt, L.wd, It, H, It, P.wd, nullptr));
-  }
-  TRY(launch_pack_w(ctx->dt, ctx->t_lm, H, c.t_vocab, H, ctx->t_lmP, nullptr));
-  OM_HIP(hipDeviceSynchronize());
-  ctx->pk_ready = true;
+  return omchat_decode_weight_format(rows, ctx->fp8_decode, ctx->mxfp4_mode, assume_packed16 || ctx->built(OMCHAT_WFMT_16_PACKED),
+                                     c.t_hidden % 64 == 0 && ctx->t_qdim % 64 == 0 && c.t_mlp % 64 == 0, x_pack_nb);
+}
+static bool is_mxfp4(int fmt) { return fmt == OMCHAT_WFMT_MXFP4 || fmt == OMCHAT_WFMT_MXFP4_PACKED; }
+
+// Every replica a step of `rows` rows may stream is built and current -- called by the step entries before pick_admit, before any
+// host-to-device copy and before anything is enqueued (a failure must leave nothing in flight).
+//  - the 16-bit packed replica is built by the first step whose format wants it (and re-packed after a weight reload), unless tuning key 6 = 0,
+//    the geometry is odd (stay on the row-major weights) or it did not fit before
+//  - an enabled replica that omchat_load_tensor left stale is rebuilt IN PLACE (same device pointers: a captured graph replays the fresh bytes)
+static int step_weights_ready(omchat_ctx* ctx, int rows) {
+  const omchat_config& c = ctx->c;
+  if (step_format(ctx, rows, nullptr, true) == OMCHAT_WFMT_16_PACKED && g_pack_replica && ctx->wt[OMCHAT_WFMT_16_PACKED].state != omchat_ctx::W_UNAVAILABLE &&
+      !(ctx->t_qkvdim % 16 || c.t_hidden % 16 || c.t_vocab % 16))
+    TRY(build_replica(ctx, OMCHAT_WFMT_16_PACKED));
+  if (ctx->fp8_decode) TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));
+  if (ctx->mxfp4_mode) TRY(build_replica(ctx, ctx->mxfp4_mode == 2 ? OMCHAT_WFMT_MXFP4_PACKED : OMCHAT_WFMT_MXFP4));
   return 0;
 }
 
 // mode 2 of the MXFP4 decode: one weight format per generation, so a step that the packed forms cannot take (b > 32) is refused by the step
 // entries before they touch any state or enqueue anything, never run on 16 bits
 static const char* const MX4_ROWS_MSG = "MXFP4 decode mode 2 streams steps of at most 32 rows (omchat_enable_mxfp4_decode(ctx, 0 or 1) first)";
+static bool mx4_rows_ok(const omchat_ctx* ctx, int rows) { return ctx->mxfp4_mode != 2 || is_mxfp4(step_format(ctx, rows)); }
 
 // One decode step on stream s.  Lmax = upper bound of the key count (sizes the split-KV grid; the kernels read the true
 // lengths from d_len).  Every argument is a context pointer or a step-invariant scalar when called for graph capture.
@@ -1362,47 +1314,38 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   void* x = ctx->tw_x;
   void* y = ctx->tw_x2;
   TRY(launch_gather_rows(ctx->dt, tokens, ctx->t_embed, nullptr, x, b, H, s));      // embed_tokens
-  // weight-only fp8 replica (omchat_enable_fp8_decode): batch-1 steps stream e4m3 bytes + per-row scales
-  const bool f8 = ctx->fp8_decode && b == 1;      // under tensor parallelism every rank streams the e4m3 replica of its own shard (round 3)
-  // weight-only MXFP4 replica (omchat_enable_mxfp4_decode): batch-1 steps stream e2m1 codes + e8m0 block scales; never together with f8.
-  // Mode 2: steps of 2 <= b <= 32 rows stream the PACKED replica through the packed batched forms (the activations arrive packed already)
-  const bool mx4 = ctx->mx4_step(b);
-  const bool wq = f8 || mx4;      // a quantised replica is streamed: the launches that exist for 16-bit weights only stay out
-  // batched steps (2 <= b <= 32): the activations that feed a GEMV (tw_xn, tw_ao, tw_act) are produced in the packed x layout
-  // (common.h) by their producers, and the weights come from the packed replica when it exists (ensure_packed)
-  const int pk = (b > 1 && b <= 32 && H % 64 == 0 && qd % 64 == 0 && It % 64 == 0) ? (b > 16 ? 2 : 1) : 0;
-  const bool wpk = pk && ctx->pk_ready;
-  const bool mpk = pk && mx4;      // (mode 2 is refused for a geometry without pk: b >= 2 with mx4 implies pk)
-  OM_CHECK(!mx4 || b == 1 || mpk, "MXFP4 decode mode 2: geometry outside the packed path");
-  static const omchat_ctx::DecLayerP noneP{};
-  auto gemv_args = [&](const void* X, int ldx, const void* W, int K, void* Y, int ldy, int R, int N, const void* bias, const void* resid, int epi,
-                       int ks, const void* W8, const float* sc, const void* WP, bool ypk, const void* W4 = nullptr, const unsigned char* s4 = nullptr) {
-    GemvArgs g{X, ldx, W, K, Y, ldy, R, N, K, bias, resid, H, epi, 0, ks};
-    if (f8 && W8) { g.W = W8; g.w_scale = sc; }
-    if (mx4 && W4) { g.W = W4; g.ldw = K / 2; g.mx_scale = s4; }
-    if (pk) {
-      g.x_packed = 1; g.y_packed = ypk && epi == EPI_SWIGLU;
-      if (mpk) g.w_packed = 1;      // W4 / s4 are the packed MXFP4 replica
-      else if (wpk && WP) { g.W = WP; g.w_packed = 1; }
-    }
+  // One weight format per step (omchat_decode_weight_format): e4m3 or MXFP4 at b == 1 (under tensor parallelism every rank streams the e4m3
+  // replica of its own shard), and on batched steps (2 <= b <= 32) the packed MXFP4 replica in mode 2, else the 16-bit packed one once it
+  // exists.  pk: the activations that feed a GEMV of a batched step (tw_xn, tw_ao, tw_act) are produced in the packed x layout (common.h)
+  // by their producers, in pk blocks of 16 rows.
+  int pk = 0;
+  const int fmt = step_format(ctx, b, &pk);
+  OM_CHECK(fmt != OMCHAT_WFMT_MXFP4_PACKED || pk, "MXFP4 decode mode 2: geometry outside the packed path");
+  const bool wq = fmt == OMCHAT_WFMT_E4M3 || is_mxfp4(fmt);      // a quantised replica is streamed: the launches that exist for 16-bit weights only stay out
+  const bool wpk = fmt == OMCHAT_WFMT_16_PACKED, mpk = fmt == OMCHAT_WFMT_MXFP4_PACKED;
+  using WRef = omchat_ctx::WRef;
+  enum { QKV = omchat_ctx::P_QKV, O = omchat_ctx::P_O, GU = omchat_ctx::P_GU, DOWN = omchat_ctx::P_DOWN };
+  auto gemv_args = [&](const void* X, int ldx, const WRef& W, int K, void* Y, int ldy, int R, int N, const void* bias, const void* resid, int epi,
+                       int ks, bool ypk) {
+    GemvArgs g{X, ldx, nullptr, 0, Y, ldy, R, N, K, bias, resid, H, epi, 0, ks};
+    use_weight(g, W);
+    if (pk) { g.x_packed = 1; g.y_packed = ypk && epi == EPI_SWIGLU; }
     return g;
   };
-  auto gemv = [&](const void* X, int ldx, const void* W, int K, void* Y, int ldy, int N, const void* bias, const void* resid, int epi,
-                  const void* W8 = nullptr, const float* sc = nullptr, const void* WP = nullptr, bool ypk = false, const void* W4 = nullptr,
-                  const unsigned char* s4 = nullptr) -> int {
+  auto gemv = [&](const void* X, int ldx, const WRef& W, int K, void* Y, int ldy, int N, const void* bias, const void* resid, int epi,
+                  bool ypk = false) -> int {
     for (int r0 = 0; r0 < b; r0 += 32) {
       const int R = std::min(32, b - r0);
       const GemvArgs g = gemv_args((const char*)X + (size_t)r0 * ldx * 2, ldx, W, K, (char*)Y + (size_t)r0 * ldy * 2, ldy, R, N, bias,
-                                   resid ? (const char*)resid + (size_t)r0 * H * 2 : nullptr, epi, 0, W8, sc, WP, ypk, W4, s4);
+                                   resid ? (const char*)resid + (size_t)r0 * H * 2 : nullptr, epi, 0, ypk);
       TRY(launch_gemv(ctx->dt, g, s));
     }
     return 0;
   };
   // split-K over workgroups: fp32 slices [ks][b][H], summed by the fused residual + RMSNorm kernel
-  auto gemv_partial = [&](const void* X, int ldx, const void* W, int K, int ks, const void* W8 = nullptr, const float* sc = nullptr,
-                          const void* WP = nullptr, const void* W4 = nullptr, const unsigned char* s4 = nullptr) -> int {
+  auto gemv_partial = [&](const void* X, int ldx, const WRef& W, int K, int ks) -> int {
     OM_CHECK(b <= 32, "split-K decode path handles b <= 32");
-    const GemvArgs g = gemv_args(X, ldx, W, K, ctx->tw_part, H, b, H, nullptr, nullptr, EPI_PARTIAL, ks, W8, sc, WP, false, W4, s4);
+    const GemvArgs g = gemv_args(X, ldx, W, K, ctx->tw_part, H, b, H, nullptr, nullptr, EPI_PARTIAL, ks, false);
     TRY(launch_gemv(ctx->dt, g, s));
     // tensor parallelism: the slices hold this rank's partial sums; reduce_resid_rmsnorm sums them over the ranks in fp32 (<= 3 x 3584
     // floats at batch 1, latency-bound like any small message) together with the residual + RMSNorm, identically on every rank
@@ -1444,19 +1387,16 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   if ((g_ao_oproj & 16) && ctx->dbg_stamps) OM_HIP(hipMemsetAsync(ctx->dbg_stamps, 0, (size_t)c.t_layers * 256, s));      // measurement: the stamps of THIS step only
 #endif
   for (int i = 0; i < c.t_layers; ++i) {
-    auto& L = ctx->dl[i];
-    static const omchat_ctx::DecLayer8 none8{};
-    const omchat_ctx::DecLayer8& Q = f8 ? ctx->dl8[i] : none8;
-    static const omchat_ctx::DecLayer4 none4{};
-    const omchat_ctx::DecLayer4& M = mx4 ? (mpk ? ctx->dl4p[i] : ctx->dl4[i]) : none4;
-    const omchat_ctx::DecLayerP& P = wpk ? ctx->dlp[i] : noneP;
+    auto& L = ctx->dl[i];      // the norms and the bias
+    const WRef* W = ctx->layer_w(fmt, i);                    // the four projections in the step's format
+    const WRef* W16 = ctx->layer_w(OMCHAT_WFMT_16, i);       // ... and as 16-bit row-major, for the launches that exist for those only (!wq, b == 1)
     char* kc = (char*)ctx->kcache + (size_t)i * ctx->cache_layer_stride() * 2;
     char* vc = (char*)ctx->vcache + (size_t)i * ctx->cache_layer_stride() * 2;
     if (!fused) TRY(launch_rmsnorm(ctx->dt, x, H, L.ln1, ctx->tw_xn, H, b, H, c.t_eps, s));
     // batch 1, one GPU (round 4): the whole layer as ONE launch with in-launch hand-offs (decode_layer.hip; the same bits as the six
     // launches below).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     if (g_decode_layer && n1 && exact_len && !masked && !wq && !(ctx->fp8_kv && ctx->kv8_valid) && ctx->dl_ws) {      // (the layer kernel has no key mask)
-      DecodeLayerArgs d{L.ln1, L.ln2, L.wqkv, L.bqkv, L.wo, L.wgu, L.wd, kc, vc, ctx->cache_sh(), x, H, qd, ctx->t_kvdim, It, c.t_heads, c.t_kv_heads, Lmax,
+      DecodeLayerArgs d{L.ln1, L.ln2, W16[QKV].W, L.bqkv, W16[O].W, W16[GU].W, W16[DOWN].W, kc, vc, ctx->cache_sh(), x, H, qd, ctx->t_kvdim, It, c.t_heads, c.t_kv_heads, Lmax,
                         ctx->rope, c.max_seq, c.t_eps, 0.08838834764831845f, ctx->dl_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       if (decode_layer_ok(d)) {
         const bool mark_l = allow_prof && i == c.t_layers / 2;      // HIP-event bracket on one layer per token (bench.py roofline)
@@ -1469,12 +1409,12 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       --ctx->fd_epoch;
     }
     if (n1) {
-      GemvArgs g = gemv_args(x, H, L.wqkv, H, ctx->tw_qkv, qkvd, 1, qkvd, L.bqkv, nullptr, EPI_NONE, 0, Q.wqkv, Q.sqkv, nullptr, false, M.wqkv, M.sqkv);
+      GemvArgs g = gemv_args(x, H, W[QKV], H, ctx->tw_qkv, qkvd, 1, qkvd, L.bqkv, nullptr, EPI_NONE, 0, false);
       g.norm_w = L.ln1; g.norm_eps = c.t_eps;
       if (OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else {
-      TRY(gemv(ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, qkvd, L.bqkv, nullptr, EPI_NONE, Q.wqkv, Q.sqkv, P.wqkv, false, M.wqkv, M.sqkv));
+      TRY(gemv(ctx->tw_xn, H, W[QKV], H, ctx->tw_qkv, qkvd, qkvd, L.bqkv, nullptr, EPI_NONE));
     }
     // RoPE + KV append are fused into the attention kernel (q rotated in registers, the split that owns the new
     // position rotates k and appends k / v)
@@ -1525,7 +1465,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       va.o_pack_nb = a.o_pack_nb;
       TRY(launch_attn_verify(ctx->dt, va, s));
     } else if (fuse_ao) {
-      FusedDecodeArgs fa{L.wo, qd, x, H, qd, ctx->fd_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
+      FusedDecodeArgs fa{W16[O].W, qd, x, H, qd, ctx->fd_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       TRY(launch_attn_oproj_fused(ctx->dt, a, fa, s));
       ++ctx->n_fused_launches;
     } else {
@@ -1543,26 +1483,26 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     if (fuse_ao) {
       // x + attn is already in place
     } else if (ao_oproj) {
-      GemvArgs g = gemv_args(ctx->tw_ao, qd, L.wo, qd, x, H, 1, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, nullptr, false);
+      GemvArgs g = gemv_args(ctx->tw_ao, qd, W16[O], qd, x, H, 1, H, nullptr, x, EPI_RESID, 0, false);
       if ((g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv_wait(ctx->dt, g, (const unsigned*)ctx->fd_ws, ctx->fd_epoch, c.t_heads, ctx->fd_err, g_ao_oproj, s));
     } else if (n2 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !wq) {
-      GemvArgs g = gemv_args(ctx->tw_ao, qd, L.wo, qd, x, H, 1, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, nullptr, false);
+      GemvArgs g = gemv_args(ctx->tw_ao, qd, W16[O], qd, x, H, 1, H, nullptr, x, EPI_RESID, 0, false);
       g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (n2) {
-      TRY(gemv(ctx->tw_ao, qd, L.wo, qd, x, H, H, nullptr, x, EPI_RESID, Q.wo, Q.so, nullptr, false, M.wo, M.so));
+      TRY(gemv(ctx->tw_ao, qd, W[O], qd, x, H, H, nullptr, x, EPI_RESID));
     } else if (nb2) {
-      GemvArgs g = gemv_args(ctx->tw_ao, qd, L.wo, qd, x, H, b, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, P.wo, false);
+      GemvArgs g = gemv_args(ctx->tw_ao, qd, W[O], qd, x, H, b, H, nullptr, x, EPI_RESID, 0, false);      // (nb2 holds wpk: the 16-bit packed reference)
       g.y_pack = ctx->tw_xn;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (fused) {
-      TRY(gemv_partial(ctx->tw_ao, qd, L.wo, qd, ks_o, Q.wo, Q.so, P.wo, M.wo, M.so));
+      TRY(gemv_partial(ctx->tw_ao, qd, W[O], qd, ks_o));
       TRY(ctx->reduce_resid_rmsnorm(x, H, ctx->tw_part, ks_o, L.ln2, ctx->tw_xn, H, b, H, c.t_eps, pk, s));
     } else if (ctx->tp_size == 1) {
-      TRY(gemv(ctx->tw_ao, qd, L.wo, qd, x, H, H, nullptr, x, EPI_RESID));
+      TRY(gemv(ctx->tw_ao, qd, W[O], qd, x, H, H, nullptr, x, EPI_RESID));
     } else {
-      TRY(gemv(ctx->tw_ao, qd, L.wo, qd, y, H, H, nullptr, lead ? x : nullptr, lead ? EPI_RESID : EPI_NONE));
+      TRY(gemv(ctx->tw_ao, qd, W[O], qd, y, H, H, nullptr, lead ? x : nullptr, lead ? EPI_RESID : EPI_NONE));
       TRY(ctx->allreduce(y, (size_t)b * H, s));
       std::swap(x, y);
     }
@@ -1572,33 +1512,33 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     const bool mark = allow_prof && i == c.t_layers / 2;
     if (mark) ctx->prof_mark(OMCHAT_PROF_DECODE_GATEUP, s);
     if (n2) {
-      GemvArgs g = gemv_args(x, H, L.wgu, H, ctx->tw_act, It, 1, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, Q.wgu, Q.sgu, nullptr, false, M.wgu, M.sgu);
+      GemvArgs g = gemv_args(x, H, W[GU], H, ctx->tw_act, It, 1, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, false);
       g.norm_w = L.ln2; g.norm_eps = c.t_eps;
       if (ctx->dyn_ctr && !ctx->graph_on) g.dyn_ctr = ctx->dyn_ctr + (size_t)i * 65 * 64;
       if (OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (nb2) {
-      GemvArgs g = gemv_args(ctx->tw_xn, H, L.wgu, H, ctx->tw_act, It, b, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, nullptr, nullptr, P.wgu, true);
+      GemvArgs g = gemv_args(ctx->tw_xn, H, W[GU], H, ctx->tw_act, It, b, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, true);
       g.norm_w = L.ln2; g.norm_eps = c.t_eps;
       TRY(launch_gemv(ctx->dt, g, s));
     } else {
-      TRY(gemv(ctx->tw_xn, H, L.wgu, H, ctx->tw_act, It, 2 * It, nullptr, nullptr, EPI_SWIGLU, Q.wgu, Q.sgu, P.wgu, true, M.wgu, M.sgu));
+      TRY(gemv(ctx->tw_xn, H, W[GU], H, ctx->tw_act, It, 2 * It, nullptr, nullptr, EPI_SWIGLU, true));
     }
     if (mark) ctx->prof_mark(OMCHAT_PROF_DECODE_GATEUP, s);
     if (n1 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !wq) {
-      GemvArgs g = gemv_args(ctx->tw_act, It, L.wd, It, x, H, 1, H, nullptr, x, EPI_RESID, 0, nullptr, nullptr, nullptr, false);
+      GemvArgs g = gemv_args(ctx->tw_act, It, W16[DOWN], It, x, H, 1, H, nullptr, x, EPI_RESID, 0, false);
       g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (n1) {
-      TRY(gemv(ctx->tw_act, It, L.wd, It, x, H, H, nullptr, x, EPI_RESID, Q.wd, Q.sd, nullptr, false, M.wd, M.sd));
+      TRY(gemv(ctx->tw_act, It, W[DOWN], It, x, H, H, nullptr, x, EPI_RESID));
     } else if (fused) {
-      TRY(gemv_partial(ctx->tw_act, It, L.wd, It, ks_d, Q.wd, Q.sd, P.wd, M.wd, M.sd));
+      TRY(gemv_partial(ctx->tw_act, It, W[DOWN], It, ks_d));
       const void* nw = i + 1 < c.t_layers ? ctx->dl[i + 1].ln1 : ctx->t_norm;      // next layer's input norm, or the final norm
       TRY(ctx->reduce_resid_rmsnorm(x, H, ctx->tw_part, ks_d, nw, ctx->tw_xn, H, b, H, c.t_eps, pk, s));
     } else if (ctx->tp_size == 1) {
-      TRY(gemv(ctx->tw_act, It, L.wd, It, x, H, H, nullptr, x, EPI_RESID));
+      TRY(gemv(ctx->tw_act, It, W[DOWN], It, x, H, H, nullptr, x, EPI_RESID));
     } else {
-      TRY(gemv(ctx->tw_act, It, L.wd, It, y, H, H, nullptr, lead ? x : nullptr, lead ? EPI_RESID : EPI_NONE));
+      TRY(gemv(ctx->tw_act, It, W[DOWN], It, y, H, H, nullptr, lead ? x : nullptr, lead ? EPI_RESID : EPI_NONE));
       TRY(ctx->allreduce(y, (size_t)b * H, s));
       std::swap(x, y);
     }
@@ -1606,13 +1546,12 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   if (!fused)   TRY(launch_rmsnorm(ctx->dt, x, H, ctx->t_norm, ctx->tw_xn, H, b, H, c.t_eps, s));
   float* lg = logits ? logits : ctx->tw_logits;
   if (n1) {
-    GemvArgs g{x, H, ctx->t_lm, H, lg, c.t_vocab, 1, c.t_vocab, H, nullptr, nullptr, 0, EPI_NONE, 1};
-    if (f8) { g.W = ctx->t_lm8; g.w_scale = ctx->t_lm8_s; }
-    if (mx4) { g.W = ctx->t_lm4; g.ldw = H / 2; g.mx_scale = ctx->t_lm4_s; }
+    GemvArgs g{x, H, nullptr, 0, lg, c.t_vocab, 1, c.t_vocab, H, nullptr, nullptr, 0, EPI_NONE, 1};
+    use_weight(g, ctx->lm_w(fmt));
     g.norm_w = ctx->t_norm; g.norm_eps = c.t_eps;
     TRY(launch_gemv(ctx->dt, g, s));
   } else {
-    TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, f8, fused && pk, mx4));
+    TRY(lm_head_rows(ctx, ctx->tw_xn, b, lg, s, ctx->lm_w(fmt), fused && pk));
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
   if (vL >= 0) TRY(pick_verify(ctx, lg, b, tokens, next_tokens, s, vsample));
@@ -1664,7 +1603,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(b >= 1 && b <= c.max_batch, "batch exceeds max_batch");
-  OM_CHECK(ctx->mx4_rows_ok(b), MX4_ROWS_MSG);
+  OM_CHECK(mx4_rows_ok(ctx, b), MX4_ROWS_MSG);
   int Lmax = 0;
   OM_CHECK(!ctx->left_padded, "per-sequence decode after a left-padded prefill: use omchat_decode_step_masked (the reference positions such a "
                               "batch with sum(mask) - 1 and a per-row key mask, omchat_arch.py:61-70; DESIGN.md section 7)");
@@ -1677,12 +1616,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   }
   OM_CHECK(Lmax <= c.max_seq, "KV cache full (max_seq)");
   hipStream_t s = (hipStream_t)stream;
-  // first batched step (or after a weight reload): build the packed replica -- unless the step streams the packed MXFP4 one instead
-  if (b > 1 && b <= 32 && !ctx->mx4_step(b)) TRY(ensure_packed(ctx));
-  // a weight reload (omchat_load_tensor) leaves the e4m3 replica stale: re-quantise IN PLACE before streaming it (same device
-  // pointers, so a captured decode graph stays valid and replays the fresh bytes)
-  if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
-  TRY(refresh_mxfp4_weights(ctx));
+  TRY(step_weights_ready(ctx, b));
   TRY(pick_admit(ctx, next_tokens != nullptr, true));
   ctx->graph_steps++;
   // graph replay needs replay-invariant arguments: single-GPU fused path only; with profiling on, every 8th step runs eagerly
@@ -1691,9 +1625,8 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   if (!graph) {
     TRY(decode_body(ctx, tokens, b, Lmax, logits, next_tokens, s, true, same_len));
   } else {
-    const bool f8 = ctx->fp8_decode && b == 1;
-    const bool mx4 = ctx->mx4_step(b);
-    omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (mx4 ? 4 : 0) + (f8 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0)];
+    const int fmt = step_format(ctx, b);
+    omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (is_mxfp4(fmt) ? 4 : 0) + (fmt == OMCHAT_WFMT_E4M3 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0)];
     hipStream_t gs = ctx->graph_stream;
     OM_HIP(hipEventRecord(ctx->graph_ev_in, s));
     OM_HIP(hipStreamWaitEvent(gs, ctx->graph_ev_in, 0));
@@ -1745,8 +1678,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(L >= 1, "decode before prefill");
   OM_CHECK(L + T <= c.max_seq, "KV cache full (max_seq)");
   hipStream_t s = (hipStream_t)stream;
-  if (!ctx->mx4_step(T)) TRY(ensure_packed(ctx));      // the first verify step (like the first batched step) builds the packed weight replica
-  TRY(refresh_mxfp4_weights(ctx));
+  TRY(step_weights_ready(ctx, T));      // (the first verify step, like the first batched step, builds the packed weight replica)
   if (vsample) TRY(pick_verify_prepare(ctx));
   TRY(decode_body(ctx, tokens, T, L + T, logits, picks, s, false, false, false, L, vsample));
   if (vsample) {
@@ -1778,7 +1710,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(ctx->pre_S >= 1 && b == ctx->pre_b, "masked decode: the batch of the last prefill, all rows");
-  OM_CHECK(ctx->mx4_rows_ok(b), MX4_ROWS_MSG);
+  OM_CHECK(mx4_rows_ok(ctx, b), MX4_ROWS_MSG);
   OM_CHECK(ctx->dec_mode != 1, "omchat_decode_step_masked after omchat_decode_step on the same prefill: the two place the cache rows differently");
   OM_CHECK(ctx->tp_size == 1, "masked decode: one GPU (under tensor parallelism right-padded batches take the per-sequence step)");
   OM_CHECK(ctx->pre_S + ctx->masked_steps + 1 <= c.max_seq, "KV cache full (max_seq)");
@@ -1787,9 +1719,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
     TRY(ctx->alloc((void**)&ctx->d_mask, (size_t)c.max_batch * ctx->mask_sb));
   }
   // replicas first: a failure here must not leave host-to-device copies of caller / stack memory in flight
-  if (b > 1 && b <= 32 && !ctx->mx4_step(b)) TRY(ensure_packed(ctx));
-  if (ctx->fp8_decode && ctx->fp8_stale) TRY(ensure_fp8_weights(ctx));
-  TRY(refresh_mxfp4_weights(ctx));
+  TRY(step_weights_ready(ctx, b));
   return 0;
 }
 
