@@ -239,6 +239,22 @@ int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* ne
  * beam search the cache rows hold running beams, not the returned hypotheses; omchat_kv_rewind leaves the beam state alone. */
 int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t* lengths, float* scores, int max_len);
 
+/* ---- sampled groups (HF generate with do_sample and num_return_sequences = N > 1) --------------------------------- */
+/* omchat_group_begin: after the prefill of b prompts into rows 0..b-1, every row prompt_len cache slots long (equal lengths, no padding),
+ * make them b * N rows, prompt-major (rows i*N .. i*N+N-1 belong to prompt i), every row prompt_len keys long on the host and the device.
+ * share = 0: prompt i's slots [0, prompt_len) are copied into its N rows (the e4m3 bytes and scales too); from there the rows are an ordinary
+ * batch for omchat_decode_step(b * N) in every mode it has, and no mode of the context is on.
+ * share = 1: only row i*N receives the prompt (one row copy for i > 0); the other rows hold nothing below slot prompt_len.  While this
+ * mode is on, omchat_decode_step takes exactly b * N rows and its attention reads the prompt keys once per group (omchat_op_attn_shared);
+ * omchat_decode_verify, omchat_prefill_extend, the masked steps and omchat_beam_begin are refused.  Needs the 16-bit KV cache, tp_size == 1,
+ * N <= 16 and N * (q heads per kv head) <= 128; any weight format of the batched step.  It ends with any prefill or with b = 0 (which
+ * does nothing else).  A captured decode graph is bound to (b, N, prompt_len).
+ * Refused before any state is touched: a beam search in progress, a left-padded or masked-decode state, rows of other lengths than
+ * prompt_len, b * N > max_batch.  No host sync. */
+int omchat_group_begin(omchat_ctx* ctx, int b, int N, int prompt_len, int share, void* stream);
+/* 1 when omchat_group_begin(ctx, ., N, ., 1) is available on this context (the conditions above), else 0 */
+int omchat_group_share_available(omchat_ctx* ctx, int N);
+
 /* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=k)) -------------------------- */
 #define OMCHAT_VERIFY_KEEP_ALL 1
 #define OMCHAT_VERIFY_SAMPLE 2
@@ -580,6 +596,13 @@ int omchat_op_attn_verify_tpw(int keys, int Hkv);
  * ws of omchat_op_attn_extend_ws(Sq, Hq, Hkv, L) bytes (never more than omchat_op_attn_decode_ws(Sq, Hq, L + Sq)).  Hq / Hkv <= 8. */
 size_t omchat_op_attn_extend_ws(int Sq, int Hq, int Hkv, int L);
 int omchat_op_attn_extend(int dtype, const void* q, const void* k, const void* v, void* out, int Sq, int Hq, int Hkv, int cap, int L,
+                          float scale, void* ws, size_t ws_bytes, void* stream);
+/* Shared-prompt decode attention of a sampled group (omchat_group_begin with share = 1): G groups of N consecutive rows,
+ * one query token per row.  q [G*N,Hq,128] already rotated; k / v [G*N rows,Hkv,cap,128] complete: the keys [0, P) of a group are read from
+ * its first row only (never its slots >= P), the keys [P, L) of every row from that row's own cache.  out [G*N,Hq,128]; ws of
+ * omchat_op_attn_shared_ws(G, N, Hq, Hkv, P, L) bytes.  1 <= P < L <= cap, N <= 16, N * Hq / Hkv <= 128. */
+size_t omchat_op_attn_shared_ws(int G, int N, int Hq, int Hkv, int P, int L);
+int omchat_op_attn_shared(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L,
                           float scale, void* ws, size_t ws_bytes, void* stream);
 /* the same with the RoPE + append fused in, as the verify step runs it: qkv [T][(Hq + 2 Hkv) * 128] raw projections (not modified);
  * q / k rotated at positions L .. L + T - 1 (table of omchat_op_rope_kv), k / v appended to rows L .. L + T - 1 of the cache

@@ -58,6 +58,8 @@ _SIGS = {
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
     "omchat_set_logprobs": (_i, [_vp, _i, _i, _vp]),
     "omchat_read_logprobs": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "omchat_group_begin": (_i, [_vp, _i, _i, _i, _i, _vp]),
+    "omchat_group_share_available": (_i, [_vp, _i]),
     "omchat_beam_begin": (_i, [_vp, _i, _i, _f, _i, _vp, _i, _i, _i, _vp]),
     "omchat_beam_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_beam_result": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
@@ -121,6 +123,8 @@ _SIGS = {
     "omchat_op_attn_verify_tpw": (_i, [_i, _i]),
     "omchat_op_attn_verify": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "omchat_op_attn_extend_ws": (_sz, [_i, _i, _i, _i]),
+    "omchat_op_attn_shared_ws": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "omchat_op_attn_shared": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "omchat_op_attn_extend": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "omchat_prefill_extend": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_extend_attn_form": (_i, [_i, _i, _i]),

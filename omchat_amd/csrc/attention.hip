@@ -2033,29 +2033,49 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
 // EXT (split-KV block attention of omchat_prefill_extend, launch_attn_extend): blockIdx.z = chunk of 16 query tokens of
 // a block of p.Sq rows at positions p.q_pos0 ..; chunk c owns tokens 16 c .. min(16 c + 15, Sq - 1) and walks keys up to its last row's
 // bound only (a split that starts beyond it leaves the neutral partial without loading a tile).  q is rotated and the cache holds every key.
-template <typename T, int NW, bool EXT = false>
+// SHR (shared-prompt decode attention of a sampled group, launch_attn_shared): blockIdx.z = group of p.Sq sibling rows
+// z p.Sq .. z p.Sq + p.Sq - 1 that share the prompt keys [0, p.Skv) held by the group's first row only.  Workgroups x < p.shr_nsp are the
+// prefix splits: "token" t is sibling t, all p.Sq x n_rep query rows over the leader's keys below p.Skv -- exactly p.Skv, whatever the leader's
+// length: its slots beyond are its own suffix.  The others are one sibling's suffix splits of one tile: its n_rep query rows over its own
+// keys [p.Skv, len).  q is rotated at len - 1; the suffix split that holds key len - 1 takes it from k_new / v_new and appends it to the
+// row's own cache (one writer; no workgroup reads that slot).  A split without keys leaves the neutral partial.  No causal bound.
+template <typename T, int NW, bool EXT = false, bool SHR = false>
 __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   typedef typename V8<T>::type frag_t;
   constexpr int PER = 16 / NW;                // row groups of 4 loaded per wave and tile
   __shared__ __attribute__((aligned(256))) char Ks[KV_TILE * 256];
   __shared__ __attribute__((aligned(256))) char Vs[KV_TILE * 256];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fc = lane & 15, fg = lane >> 4;
-  const int split = blockIdx.x, kvh = blockIdx.y;
+  const int kvh = blockIdx.y;
   const int n_rep = p.q_heads / p.kv_heads, hq0 = kvh * n_rep;
-  const int t0 = EXT ? (int)blockIdx.z * 16 : 0;                  // first token of this chunk
-  const int NT = EXT ? min(16, p.Sq - t0) : p.Sq, L = p.q_pos0 + t0, Lt = EXT ? L + NT : p.Skv;
+  int split = blockIdx.x;
+  int t0 = EXT ? (int)blockIdx.z * 16 : 0;                  // first token of this chunk
+  int NT = EXT ? min(16, p.Sq - t0) : p.Sq, L = p.q_pos0 + t0, Lt = EXT ? L + NT : p.Skv;
+  int key_base = split * KV_TILE * p.tpw, ntile = p.tpw;
+  int64_t row_off_k = 0, row_off_v = 0, row_off_new = 0;
+  if constexpr (SHR) {
+    const int nss = p.nsplit - p.shr_nsp, x = (int)blockIdx.x - p.shr_nsp;      // nss >= 1 (launch_attn_shared)
+    const bool pre = x < 0;
+    const int j = pre ? 0 : x / nss, ss = pre ? 0 : x - j * nss;
+    t0 = (int)blockIdx.z * p.Sq + j;          // first row: the leader (prefix) or the sibling whose suffix this is
+    NT = pre ? p.Sq : 1;
+    const int len = p.kv_len ? p.kv_len[t0] : p.shr_L;
+    if (!pre) { split = p.shr_nsp + ss; key_base = p.Skv + ss * KV_TILE; ntile = 1; }
+    Lt = pre ? p.Skv : len;
+    L = pre ? 0x3fffffff : len - 1;           // the first key that comes from k_new: none in the prefix
+    row_off_k = t0 * p.k_sb; row_off_v = t0 * p.v_sb; row_off_new = t0 * p.new_sb;
+  }
   const int R = NT * n_rep;
   const bool active = 16 * w < R;             // wave-uniform
   const int r = min(16 * w + fc, R - 1), t = r / n_rep, hh = r - t * n_rep;
-  const int qpos = L + t;
-  const int key_base = split * KV_TILE * p.tpw;
+  const int qpos = SHR ? (p.kv_len ? p.kv_len[t0 + t] : p.shr_L) - 1 : L + t;
   float* wsb = p.ws + ((size_t)((t0 + t) * p.q_heads + hq0 + hh) * p.nsplit + split) * WS_STRIDE;
   const bool own = active && 16 * w + fc < R;
   const bool fuse = !EXT && p.rope != nullptr;
-  const T* Kg = (const T*)p.K + kvh * p.k_sh;
-  const T* Vg = (const T*)p.V + kvh * p.v_sh;
-  const T* kn = fuse ? (const T*)p.k_new + kvh * 128 : nullptr;
-  const T* vn = fuse ? (const T*)p.v_new + kvh * 128 : nullptr;
+  const T* Kg = (const T*)p.K + row_off_k + kvh * p.k_sh;
+  const T* Vg = (const T*)p.V + row_off_v + kvh * p.v_sh;
+  const T* kn = fuse ? (const T*)p.k_new + row_off_new + kvh * 128 : nullptr;
+  const T* vn = fuse ? (const T*)p.v_new + row_off_new + kvh * 128 : nullptr;
 
   frag_t qf[4];
   {
@@ -2081,7 +2101,7 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   const int vrow_lo = 4 * fg + tq;
   const int vswz = ((vrow_lo & 7) << 1);
 
-  for (int tt = 0; tt < p.tpw; ++tt) {
+  for (int tt = 0; tt < ntile; ++tt) {
     const int key0 = key_base + tt * KV_TILE;
     if (key0 >= Lt) break;                    // uniform
     // ---- K and V rows of the tile: every load in flight at once
@@ -2110,8 +2130,8 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
           const frag_t rot = rope_chunk<T>(kr[i], __builtin_bit_cast(frag_t, oth), cs, fc >= 8);
           if (key >= L && key < Lt) {
             kr[i] = rot;
-            st8<T>((T*)p.k_cache_w + kvh * p.k_sh + (int64_t)key * p.k_sr + fc * 8, rot);
-            st8<T>((T*)p.v_cache_w + kvh * p.v_sh + (int64_t)key * p.v_sr + fc * 8, vr[i]);
+            st8<T>((T*)p.k_cache_w + row_off_k + kvh * p.k_sh + (int64_t)key * p.k_sr + fc * 8, rot);
+            st8<T>((T*)p.v_cache_w + row_off_v + kvh * p.v_sh + (int64_t)key * p.v_sr + fc * 8, vr[i]);
           }
         }
       }
@@ -2135,12 +2155,13 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
 #pragma unroll
       for (int ds = 0; ds < 4; ++ds) s[kt] = mfma16(kf[ds], qf[ds], s[kt]);
     }
-    if (key0 + KV_TILE > L + 1) {             // the tile holds keys beyond L: causal bound per column (uniform)
+    const int kbound = SHR ? Lt - 1 : qpos;   // SHR: every column sees every key of the part, so only the part's end bounds it
+    if (SHR ? key0 + KV_TILE > Lt : key0 + KV_TILE > L + 1) {      // the tile holds keys beyond L: causal bound per column (uniform)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          if (key0 + kt * 16 + 4 * fg + q > qpos) s[kt][q] = NEG_BIG;
+          if (key0 + kt * 16 + 4 * fg + q > kbound) s[kt][q] = NEG_BIG;
     }
     float mx = NEG_BIG;
 #pragma unroll
@@ -2295,6 +2316,63 @@ int launch_attn_extend(int dtype, const AttnExtendArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, true>), grid, dim3(256), 0, s, p);
     launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, a.Sq, Lt, p.c, (bf16*)a.O, a.o_sb, a.o_sh, 0, split_keys, s);
   } else { omchat_set_error("launch_attn_extend: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Shared-prompt decode attention (omchat_group_begin with share = 1): G groups of N sibling rows, one new token per row.
+// attn_verify_kernel<SHR>: the prompt keys [0, P) of a group are read once for its N x n_rep query rows, each row's own keys [P, len) by
+// one-tile splits of its own.  Prefix splits: about two workgroups per CU whatever G and N are (the extend plan's rule).  The suffix grid
+// covers L - P keys per row; with kv_len the rows' true lengths come from the device and splits beyond them leave neutral partials, so a
+// launch captured for L keys replays for any shorter length with the same partial layout -- and the same bits as an eager launch given
+// the same L.  Partials [G N][q_heads][nsp + nss], folded by the decode merge.
+// ---------------------------------------------------------------------------------------------------------
+static void attn_shared_plan(int G, int P, int L, int kv_heads, int* tpw, int* nsp, int* nss) {
+  const int tiles = cdiv(P, KV_TILE);
+  const int want = std::max(1, 2 * device_cus() / std::max(1, G * kv_heads));
+  *tpw = std::max(1, cdiv(tiles, want));
+  *nsp = cdiv(tiles, *tpw);
+  *nss = cdiv(L - P, KV_TILE);
+}
+size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L) {
+  if (G < 1 || N < 1 || P < 1 || L <= P || kv_heads < 1) return 0;
+  int tpw, nsp, nss;
+  attn_shared_plan(G, P, L, kv_heads, &tpw, &nsp, &nss);
+  return (size_t)G * N * q_heads * (nsp + nss) * WS_STRIDE * sizeof(float);
+}
+
+int launch_attn_shared(int dtype, const AttnSharedArgs& a, hipStream_t s) {
+  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
+  const int n_rep = a.q_heads / a.kv_heads;
+  OM_CHECK(a.G >= 1 && a.N >= 1 && a.N <= VERIFY_MAX_T && a.N * n_rep <= 128, "shared attention: 1 <= N <= 16 and N * n_rep <= 128 query rows");
+  OM_CHECK(a.P >= 1 && a.L > a.P, "shared attention: a prompt of P >= 1 keys and at least one own key per row (L > P)");
+  OM_CHECK(!a.rope || (a.k_new && a.v_new && a.L <= a.rope_max), "fused RoPE needs k_new / v_new and a table covering L positions");
+  OM_CHECK(a.o_pack_nb == 0 || (a.G * a.N <= 16 * a.o_pack_nb && a.o_sh == 128), "packed output: rows <= 16 * NB, head stride 128");
+  int tpw, nsp, nss;
+  attn_shared_plan(a.G, a.P, a.L, a.kv_heads, &tpw, &nsp, &nss);
+  const int nsplit = nsp + nss, rows = a.G * a.N;
+  OM_CHECK(a.ws && a.ws_bytes >= attn_shared_ws_bytes(a.G, a.N, a.q_heads, a.kv_heads, a.P, a.L), "workspace too small");
+  AttnP p{};
+  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
+  p.K = a.K; p.k_sb = a.k_sb; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
+  p.V = a.V; p.v_sb = a.v_sb; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
+  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.N; p.Skv = a.P; p.nsplit = nsplit; p.shr_nsp = nsp; p.shr_L = a.L; p.kv_len = a.kv_len;
+  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
+  p.rope = a.rope; p.rope_max = a.rope_max; p.k_new = a.k_new; p.v_new = a.v_new; p.new_sb = a.new_sb;
+  p.k_cache_w = a.K; p.v_cache_w = a.V;
+  const bool wide = a.N * n_rep > 64;
+  const dim3 grid(nsp + a.N * nss, a.kv_heads, a.G);
+  // every split writes its partial (neutral when it holds no key), so the merge folds all nsplit of them: one "key" per split
+  if (dtype == OMCHAT_F16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8, false, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4, false, true>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, 1, s);
+  } else if (dtype == OMCHAT_BF16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8, false, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, false, true>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, 1, s);
+  } else { omchat_set_error("launch_attn_shared: bad dtype"); return 1; }
   OM_LAUNCH_CHECK();
   return 0;
 }

@@ -439,6 +439,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   const int ns = beam_slices(c.t_vocab_total, ctx->tp_size);
   OM_CHECK(ns >= 1, "beam search: the vocabulary cannot be cut into equal slices of <= 20480 ids for this TP degree");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "beam search: a left-padded or masked-decode batch (pad equal or use b = 1)");
+  OM_CHECK(!ctx->group.on(), "beam search: a sampled group shares its prompt (omchat_group_begin with b = 0 first)");
   BeamState::Search& B = ctx->beam.cur;
   B = BeamState::Search{};
   B.b = b; B.N = N; B.KB = KB; B.max_new = max_new; B.P = prompt_tok_len; B.es = early_stopping; B.ns = ns; B.lp = length_penalty;
@@ -459,6 +460,48 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_HIP(hipMemcpyAsync(ctx->beam.dn.p, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s));
   OM_HIP(hipStreamSynchronize(s));      // host vector
   B.on = true;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// sampled groups (include/omchat_hip.h: omchat_group_begin)
+// ---------------------------------------------------------------------------------------------------------
+static const char* group_share_refusal(const omchat_ctx* ctx, int N) {
+  const omchat_config& c = ctx->c;
+  if (ctx->fp8_kv) return "shared-prompt mode: the e4m3 KV cache is not implemented (DESIGN.md section 7): share = 0, or omchat_enable_fp8_kv(ctx, 0)";
+  if (ctx->tp_size != 1) return "shared-prompt mode: tensor-parallel contexts are not implemented (DESIGN.md section 7): share = 0";
+  if (c.t_kv_heads < 1 || c.t_heads % c.t_kv_heads) return "shared-prompt mode: q heads must be a multiple of kv heads";
+  if (N < 2 || N > VERIFY_MAX_T || N * (c.t_heads / c.t_kv_heads) > 128)
+    return "shared-prompt mode: 2 <= N <= 16 and N * (q heads per kv head) <= 128 (the shared attention's query rows): share = 0";
+  return nullptr;
+}
+
+extern "C" int omchat_group_share_available(omchat_ctx* ctx, int N) { return ctx && ctx->c.t_layers > 0 && !group_share_refusal(ctx, N); }
+
+extern "C" int omchat_group_begin(omchat_ctx* ctx, int b, int N, int prompt_len, int share, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  if (b == 0) { ctx->group.end(); return 0; }
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(b >= 1 && N >= 1, "sampled group: b >= 1 prompts, N >= 1 rows each");
+  OM_CHECK(!ctx->beam.on(), "sampled group: a beam search is active");
+  OM_CHECK(b * N <= c.max_batch, "sampled group: b * N exceeds max_batch");
+  OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "sampled group: a left-padded or masked-decode batch (pad equal or use b = 1)");
+  OM_CHECK(prompt_len >= 1 && prompt_len < c.max_seq, "sampled group: prompt_len outside [1, max_seq)");
+  for (int i = 0; i < b; ++i) OM_CHECK(ctx->h_len[i] == prompt_len, "sampled group: rows 0..b-1 must hold exactly prompt_len keys (pad equal or use b = 1)");
+  if (share) { const char* why = group_share_refusal(ctx, N); OM_CHECK(!why, why); }
+  hipStream_t s = (hipStream_t)stream;
+  GroupState& G = ctx->group;
+  const int P = prompt_len, bN = b * N;
+  // last prompt first: its target rows lie above every source row not yet read.  share: only the group's first row takes the prompt
+  const KvGatherArgs g = beam_kv_args(ctx, false);
+  for (int i = b - 1; i >= (share ? 1 : 0); --i) TRY(launch_kv_gather(g, nullptr, i * N, share ? 1 : N, i, 0, P, s));
+  G.hpos.assign(bN, P);
+  G.hlen.assign(bN, P + 1);
+  for (int r = 0; r < bN; ++r) ctx->h_len[r] = P;
+  OM_HIP(hipMemcpyAsync(ctx->d_pos, G.hpos.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(ctx->d_len, G.hlen.data(), (size_t)bN * 4, hipMemcpyHostToDevice, s));
+  G.share = share != 0; G.b = b; G.N = N; G.P = P;
   return 0;
 }
 

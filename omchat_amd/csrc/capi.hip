@@ -278,6 +278,21 @@ extern "C" int omchat_op_attn_extend(int dtype, const void* q, const void* k, co
   return launch_attn_extend(dtype, a, S(stream));
 }
 
+extern "C" size_t omchat_op_attn_shared_ws(int G, int N, int Hq, int Hkv, int P, int L) { return attn_shared_ws_bytes(G, N, Hq, Hkv, P, L); }
+
+extern "C" int omchat_op_attn_shared(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L,
+                                     float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(q && k && v && out && ws, "null argument");
+  OM_CHECK(Hkv > 0 && P >= 1 && L > P && L <= cap, "1 <= P < L <= cap");
+  AttnSharedArgs a{};
+  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
+  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.G = G; a.N = N; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  return launch_attn_shared(dtype, a, S(stream));
+}
+
 extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,
                                             int L, float scale, void* ws, size_t ws_bytes, void* stream) {
   OM_CHECK(qkv && k && v && out && ws, "null argument");

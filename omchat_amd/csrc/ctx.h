@@ -96,6 +96,17 @@ struct BeamState {
   void release() { for (Grown* g : {&state, &table, &dn, &parents, &stash}) g->release(); }
 };
 
+// sampled groups (omchat_group_begin; beam.hip): the shared-prompt mode of the decode step -- b prompts x N sibling rows whose prompt keys
+// [0, P) only the group's first row holds -- and the partials of its attention (grown on demand)
+struct GroupState {
+  bool share = false; int b = 0, N = 0, P = 0;
+  Grown ws;
+  std::vector<int> hpos, hlen;      // host sources of the begin's device lengths (alive until the next begin)
+  bool on() const { return share; }
+  void end() { share = false; }
+  void release() { ws.release(); }
+};
+
 struct omchat_ctx {
   omchat_config c;
   int dt = OMCHAT_BF16;
@@ -147,8 +158,10 @@ struct omchat_ctx {
   // context-owned stream (the caller's may be the legacy null stream, which cannot capture) with context-owned token / logits
   // buffers so that every kernel argument is replay-invariant; the split-KV attention grid is captured for `cap_len` keys
   // (empty splits exit at once) and the graph is re-captured when a sequence outgrows it.
-  struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0; };
-  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0), the weights by the step's format
+  // (shared-prompt mode of a sampled group: N, P and the workspace are kernel arguments too, so the graph remembers them and is captured again
+  // when they change; its cap_len is the suffix bucket the eager step would take, so both issue the same launches)
+  struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0, grp_N = 0, grp_P = 0; const void* grp_ws = nullptr; };
+  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0), the weights by the step's format; + (1 << 20) in the shared-prompt mode
   bool graph_on = false;
   hipStream_t graph_stream = nullptr;
   hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;
@@ -194,6 +207,7 @@ struct omchat_ctx {
   int* d_verify_n = nullptr;      // omchat_decode_verify: accepted drafts of the last verify step
   PickState pick;
   BeamState beam;
+  GroupState group;
   Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
   int grow(Grown& g, size_t n) {
     if (n <= g.cap) return 0;

@@ -302,6 +302,28 @@ struct AttnExtendArgs {
 size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L);
 int launch_attn_extend(int dtype, const AttnExtendArgs& a, hipStream_t s);
 
+// Shared-prompt decode attention (omchat_group_begin with share = 1): G groups of N consecutive rows, one query token per
+// row.  The rows of a group share the keys [0, P), which only its first row (the leader, row g N) holds; every row holds its own keys
+// [P, len) in its own cache row.  The prefix is read once per group for the N x n_rep query rows, never beyond P; the suffix per row.
+// L = keys per row counting the new one; with kv_len (device [G N]: the true lengths, all <= L) L only sizes the grid and the workspace.
+// rope != null: q is rotated at len - 1, the new key (k_new / v_new row of the sequence) is rotated and appended at slot len - 1 of the row's
+// own cache; rope == null: Q is rotated and the caches are complete.  N <= 16, N n_rep <= 128.
+struct AttnSharedArgs {
+  const void* Q; int64_t q_sb, q_sh;            // [G N, q_heads, 128] (row stride q_sb)
+  void* K; int64_t k_sb, k_sh, k_sr;            // caches [G N rows, kv_heads, cap, 128]
+  void* V; int64_t v_sb, v_sh, v_sr;
+  void* O; int64_t o_sb, o_sh;                  // [G N, q_heads, 128]
+  int G, N, q_heads, kv_heads, P, L;
+  const int* kv_len;
+  float scale;
+  float* ws; size_t ws_bytes;                   // attn_shared_ws_bytes(G, N, q_heads, kv_heads, P, L)
+  const float* rope; int rope_max;
+  const void* k_new; const void* v_new; int64_t new_sb;   // raw k / v rows [G N][kv_heads * 128], row stride new_sb
+  int o_pack_nb;
+};
+size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L);
+int launch_attn_shared(int dtype, const AttnSharedArgs& a, hipStream_t s);
+
 // batch-1 decode on one GPU (fused_decode.hip, round 4): launch_attn_decode + the o_proj GEMV with EPI_RESID as ONE launch, same bits.
 // x [H] is the residual stream (read, x + o_proj(attn) written in place), Wo [H][qd] row-major; ws = fused_decode_ws_bytes(q_heads) bytes
 // of zero-initialised device memory owned by the caller and used by no other launch at the same time; epoch: a value that no earlier launch

@@ -374,7 +374,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  ctx->beam.release(); ctx->ext_ws.release(); ctx->pick.release();
+  ctx->beam.release(); ctx->group.release(); ctx->ext_ws.release(); ctx->pick.release();
   delete ctx;
 }
 
@@ -1206,6 +1206,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   }
   ctx->kv8_valid = false;
   ctx->beam.end();         // a prefill ends any beam search
+  ctx->group.end();        // ... and the shared-prompt mode of a sampled group
   if (ctx->fp8_kv) {      // fp8 KV cache for the decode steps: quantise what this prefill wrote -- ALL S slots of every row: the masked decode
                           // of a padded batch exposes padded slots too (omchat_arch.py:61-70), and the per-sequence step overwrites them as it appends
     for (int i = 0; i < c.t_layers; ++i) {
@@ -1244,6 +1245,7 @@ extern "C" int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_
   OM_CHECK(!ctx->left_padded, "prefill_extend: the cache holds a left-padded batch");
   OM_CHECK(ctx->dec_mode != 2, "prefill_extend: the cache holds a masked-decode (padded batch) state");
   OM_CHECK(!ctx->beam.on(), "prefill_extend: a beam search is active");
+  OM_CHECK(!ctx->group.on(), "prefill_extend: a sampled group shares its prompt (omchat_group_begin with b = 0 first): sequence 0 has sibling rows");
   OM_CHECK(ctx->pre_b >= 1 && ctx->h_len[0] >= 1, "prefill_extend: no live sequence-0 state (omchat_prefill with b = 1 first)");
   OM_CHECK(ctx->pre_b == 1, "prefill_extend: the cache holds a b > 1 state");
   OM_CHECK(keep >= 0 && keep <= ctx->h_len[0], "prefill_extend: keep outside [0, current length]");
@@ -1453,7 +1455,21 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     // bits as the three launches).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     bool ao_oproj = false;
     const bool fuse_ao = g_fuse_attn_oproj && n2 && exact_len && !wq && a.rope && ctx->fd_ws && attn_oproj_fused_ok(a, H, qd);
-    if (vL >= 0) {
+    if (vL < 0 && ctx->group.on()) {
+      // sampled group sharing its prompt (omchat_group_begin): the prompt keys once per group, each row's own keys per row; the lengths come
+      // from the device, Lmax (the suffix bucket, omchat_decode_step) sizes the grid -- the same launch eager and captured
+      const GroupState& G = ctx->group;
+      AttnSharedArgs sa{};
+      sa.Q = ctx->tw_qkv; sa.q_sb = qkvd; sa.q_sh = 128;
+      sa.K = kc; sa.k_sb = ctx->cache_sb(); sa.k_sh = ctx->cache_sh(); sa.k_sr = 128;
+      sa.V = vc; sa.v_sb = sa.k_sb; sa.v_sh = sa.k_sh; sa.v_sr = 128;
+      sa.O = ctx->tw_ao; sa.o_sb = qd; sa.o_sh = 128;
+      sa.G = G.b; sa.N = G.N; sa.q_heads = c.t_heads; sa.kv_heads = c.t_kv_heads; sa.P = G.P; sa.L = Lmax; sa.kv_len = ctx->d_len; sa.scale = a.scale;
+      sa.ws = (float*)G.ws.p; sa.ws_bytes = G.ws.cap;
+      sa.rope = ctx->rope; sa.rope_max = c.max_seq; sa.k_new = a.k_new; sa.v_new = a.v_new; sa.new_sb = qkvd;
+      sa.o_pack_nb = a.o_pack_nb;
+      TRY(launch_attn_shared(ctx->dt, sa, s));
+    } else if (vL >= 0) {
       AttnVerifyArgs va{};
       va.Q = ctx->tw_qkv; va.q_sb = qkvd; va.q_sh = 128;
       va.K = kc; va.k_sh = ctx->cache_sh(); va.k_sr = 128;
@@ -1616,6 +1632,16 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   }
   OM_CHECK(Lmax <= c.max_seq, "KV cache full (max_seq)");
   hipStream_t s = (hipStream_t)stream;
+  GroupState& G = ctx->group;
+  const bool grp = G.on();
+  if (grp) {
+    OM_CHECK(b == G.b * G.N && same_len, "a sampled group shares its prompt: a step takes all its b * N rows, of one length (omchat_group_begin with b = 0 first)");
+    OM_CHECK(ctx->tp_size == 1 && !(ctx->fp8_kv && ctx->kv8_valid), "shared-prompt mode: one GPU, 16-bit KV cache");
+    // the suffix grid in buckets of 256 keys: eager and captured steps issue the same launches, and a graph lasts 256 steps
+    Lmax = std::min(c.max_seq, G.P + (Lmax - G.P + 255) / 256 * 256);
+    const size_t need = attn_shared_ws_bytes(G.b, G.N, c.t_heads, c.t_kv_heads, G.P, Lmax);
+    if (need > G.ws.cap) TRY(ctx->grow(G.ws, attn_shared_ws_bytes(G.b, G.N, c.t_heads, c.t_kv_heads, G.P, std::min(c.max_seq, Lmax + 768))));
+  }
   TRY(step_weights_ready(ctx, b));
   TRY(pick_admit(ctx, next_tokens != nullptr, true));
   ctx->graph_steps++;
@@ -1623,17 +1649,18 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   // so that the HIP-event brackets of the dominant kernel are still recorded inside the timed region
   const bool graph = ctx->graph_on && ctx->tp_size == 1 && b <= 32 && !(ctx->prof_on && ctx->graph_steps % 8 == 0);
   if (!graph) {
-    TRY(decode_body(ctx, tokens, b, Lmax, logits, next_tokens, s, true, same_len));
+    TRY(decode_body(ctx, tokens, b, Lmax, logits, next_tokens, s, true, same_len && !grp));
   } else {
     const int fmt = step_format(ctx, b);
-    omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (is_mxfp4(fmt) ? 4 : 0) + (fmt == OMCHAT_WFMT_E4M3 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0)];
+    omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (is_mxfp4(fmt) ? 4 : 0) + (fmt == OMCHAT_WFMT_E4M3 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0) +
+                                             (grp ? (1 << 20) : 0)];
     hipStream_t gs = ctx->graph_stream;
     OM_HIP(hipEventRecord(ctx->graph_ev_in, s));
     OM_HIP(hipStreamWaitEvent(gs, ctx->graph_ev_in, 0));
     OM_HIP(hipMemcpyAsync(ctx->d_tok_in, tokens, (size_t)b * 4, hipMemcpyDeviceToDevice, gs));
-    if (!g.exec || Lmax > g.cap_len) {
+    if (!g.exec || Lmax > g.cap_len || (grp && (Lmax != g.cap_len || G.N != g.grp_N || G.P != g.grp_P || G.ws.p != g.grp_ws))) {
       destroy_graph(g);
-      const int cap = std::min(c.max_seq, (Lmax + 1024 + 63) / 64 * 64);
+      const int cap = grp ? Lmax : std::min(c.max_seq, (Lmax + 1024 + 63) / 64 * 64);
       OM_HIP(hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal));
       const int rc = decode_body(ctx, ctx->d_tok_in, b, cap, ctx->tw_logits, ctx->d_tok_out, gs, false);
       hipGraph_t graph_h = nullptr;
@@ -1643,6 +1670,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
       g.graph = graph_h;
       OM_HIP(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
       g.cap_len = cap;
+      if (grp) { g.grp_N = G.N; g.grp_P = G.P; g.grp_ws = G.ws.p; }
       ctx->graph_captures++;
     }
     OM_HIP(hipGraphLaunch(g.exec, gs));
@@ -1672,6 +1700,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(!why, why);
   OM_CHECK(!ctx->pick.constraints_on(), "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
   OM_CHECK(!ctx->beam.on(), "a beam search is active");
+  OM_CHECK(!ctx->group.on(), "a sampled group shares its prompt: a verify step runs one sequence (omchat_group_begin with b = 0 first)");
   OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
   OM_CHECK(!(ctx->fp8_kv && ctx->kv8_valid), "the e4m3 KV cache is not implemented");
   const int L = ctx->h_len[0];
@@ -1713,6 +1742,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   OM_CHECK(mx4_rows_ok(ctx, b), MX4_ROWS_MSG);
   OM_CHECK(ctx->dec_mode != 1, "omchat_decode_step_masked after omchat_decode_step on the same prefill: the two place the cache rows differently");
   OM_CHECK(ctx->tp_size == 1, "masked decode: one GPU (under tensor parallelism right-padded batches take the per-sequence step)");
+  OM_CHECK(!ctx->group.on(), "masked decode: a sampled group shares its prompt, and the shared attention has no key mask (omchat_group_begin with b = 0 first)");
   OM_CHECK(ctx->pre_S + ctx->masked_steps + 1 <= c.max_seq, "KV cache full (max_seq)");
   if (!ctx->d_mask) {
     ctx->mask_sb = (int64_t)cdiv(c.max_seq, 64) * 64;

@@ -15,6 +15,24 @@ def _torch():
     return torch
 
 
+# generate(num_return_sequences=N, share_prompt=None): the shared-prompt decode step is taken from this prompt length on (cache slots), where
+# tools/bench_group.py measured it faster than the forked rows at every N by more than the pass-to-pass spread (slower
+# at 64 slots, inside the spread at 1 024 for N = 4); None would mean that no such length exists: forked by default, shared opt-in
+GROUP_SHARE_P_MIN = 2048
+
+
+def group_share_refusal(fp8_kv, tp_size, q_heads, kv_heads, N):
+    """why omchat_group_begin(share = 1) is not available for N rows per prompt (the library's own conditions, restated on the host so that
+    generate() can refuse before any work), or None"""
+    if fp8_kv:
+        return "the e4m3 KV cache"
+    if tp_size != 1:
+        return "tensor parallelism"
+    if not 2 <= N <= 16 or N * (q_heads // max(1, kv_heads)) > 128:
+        return "N outside 2 <= N <= 16 and N * (q heads per kv head) <= 128"
+    return None
+
+
 class Engine:
     def __init__(self, cfg: OmChatConfig, dtype="bf16", max_seq=4096, max_batch=1, max_tiles=4, max_prefill_rows=None,
                  tp_rank=0, tp_size=1, comm=None, device=None, vision=True, text=True):
@@ -57,6 +75,7 @@ class Engine:
         self._tile_key_next = 0
         self._ext_st = dict(kept_slots=0, prefilled_rows=0, tiles_encoded=0, tiles_reused=0)
         self._lp_max_new, self._logprobs_on = 0, False      # set_logprobs
+        self._enc_st = dict(calls=0, tiles=0)               # encode_images
 
     def close(self):
         if getattr(self, "h", None):
@@ -244,6 +263,14 @@ class Engine:
         n = px.shape[0]
         out = torch.empty(n, self.ntok, self.cfg.text["hidden_size"], dtype=self.torch_dtype, device=self.device)
         check(self.lib.omchat_encode_images(self.h, ptr(px), n, select_layer, ptr(out), cur_stream()))
+        self._enc_st["calls"] += 1; self._enc_st["tiles"] += n
+        return out
+
+    def encode_stats(self, reset=False):
+        """counters of encode_images since the engine was made (or the last reset): calls and tiles run through the tower + projector"""
+        out = dict(self._enc_st)
+        if reset:
+            self._enc_st = dict(calls=0, tiles=0)
         return out
 
     # ------------------------------------------------------------------ splice
@@ -578,6 +605,26 @@ class Engine:
 
     def constraints_off(self):
         check(self.lib.omchat_set_constraints(self.h, 0, 0, 0, 0, None, 0, None, 0, None, 0, None, None, 0, None, None, 0, cur_stream()))
+
+    # ------------------------------------------------------------------ sampled groups (include/omchat_hip.h: omchat_group_begin)
+    def group_share_refusal(self, N):
+        """why the shared-prompt form is not available for N rows per prompt on this engine, or None (host data only)"""
+        return group_share_refusal(getattr(self, "_fp8_kv", False), self.tp_size, self.c.t_heads, self.c.t_kv_heads, int(N))
+
+    def group_share_default(self, N, prompt_len):
+        """the engine's rule for share_prompt=None: available and prompt_len >= GROUP_SHARE_P_MIN (None: never)"""
+        return self.group_share_refusal(N) is None and GROUP_SHARE_P_MIN is not None and int(prompt_len) >= GROUP_SHARE_P_MIN
+
+    def group_begin(self, b, N, prompt_len=None, share=False):
+        """after the prefill of b equal-length prompts: b * N rows, prompt-major, every row prompt_len keys long.  share=False: the prompt's
+        slots are forked into every row and decode_step(b * N) runs as on any batch; share=True: only each group's first row holds the
+        prompt and decode_step reads it once per group until the next prefill (or group_end)."""
+        P = prompt_len if prompt_len is not None else self.kv_lengths(b)[0]
+        check(self.lib.omchat_group_begin(self.h, int(b), int(N), int(P), int(bool(share)), cur_stream()))
+        self._prefix = None      # the rows changed hands
+
+    def group_end(self):
+        check(self.lib.omchat_group_begin(self.h, 0, 0, 0, 0, cur_stream()))
 
     # ------------------------------------------------------------------ beam search (include/omchat_hip.h: omchat_beam_begin)
     def beam_begin(self, b, num_beams, length_penalty=1.0, early_stopping=False, eos=(), max_new=20, prompt_len=None):

@@ -296,7 +296,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
                  repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
-                 num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, output_logprobs=None, **kwargs):
+                 num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, output_logprobs=None, share_prompt=None,
+                 **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
@@ -321,7 +322,14 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         GenerateOutput whose .sequences is what the call returns otherwise, .logprobs [b, new] the log-probability of every generated id
         under the model's raw distribution and .processed_logprobs [b, new] under the distribution the pick was made from (bans, repetition
         penalty, temperature, top-k / top-p and the four filters behind them); recorded by the pick on the device, read back once at the end.  Positions behind a row's EOS,
-        where the sequence holds pad, are 0.  Refused with num_beams > 1 (sequences_scores) and with prompt_lookup_num_tokens."""
+        where the sequence holds pad, are 0.  Refused with num_beams > 1 (sequences_scores) and with prompt_lookup_num_tokens.
+        num_return_sequences=N with do_sample=True and num_beams == 1 (also read from generation_config): returns
+        [b * N, T + new], prompt-major (rows i*N .. i*N+N-1 belong to prompt i, HF's _expand_inputs_for_generation order); log-prob fields
+        [b * N, new].  Each prompt is prefilled ONCE -- every sibling sees its own prompt's tiles, as under beam search -- and row i*N + j
+        samples with its own row key from the first token on.  share_prompt: False = the prompt's cache slots are forked into the N rows and
+        the plain batched step runs; True = the rows of a prompt share its slots and the decode step's attention reads them once per prompt
+        (16-bit KV cache, one GPU, N <= 16; NotImplementedError otherwise); None = the engine's rule (Engine.group_share_default).  Refused:
+        padded or ragged batches, reuse_cache=True, prompt_lookup_num_tokens and a streamer when b * N > 1."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -335,6 +343,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 raise NotImplementedError("reuse_cache=True with the e4m3 KV cache, fp8 x fp8 prefill GEMMs or tensor parallelism is not "
                                           "implemented (DESIGN.md section 7)")
         lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
+        group = self._group_params(input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer)
         olp = bool(output_logprobs if output_logprobs is not None else getattr(gc, "output_logprobs", False))
         if olp:      # every refusal before any work
             if not return_dict_in_generate:
@@ -379,6 +388,20 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         # then the (max, index) exchange the decode step uses (pick.hip: greedy_pick); no torch re-statement on the gathered logits.
         # Sampling: the same seam with the sampler (omchat_sample); the decode steps below then sample too, the penalty's seen set growing
         # on the device.  HF drives the processors with input_ids (the prompt, pads included) + the generated ids.
+        local_logits = out.local_logits
+        if group is not None:
+            # one prefill per prompt, then b * N rows, prompt-major: from here on the call is the sampled loop of the expanded batch
+            N, share = group
+            lens = self.engine.kv_lengths(b)
+            if getattr(self, "_padded_batch", False) or len(set(lens)) > 1:
+                raise NotImplementedError("num_return_sequences > 1 over rows of different spliced length is not implemented: pad the prompts "
+                                          "to equal length or use b = 1")
+            if share is None:
+                share = self.engine.group_share_default(N, lens[0])
+            self.engine.group_begin(b, N, lens[0], share)
+            local_logits = local_logits.repeat_interleave(N, dim=0)
+            input_ids = input_ids.repeat_interleave(N, dim=0)
+            b = b * N
         if con is not None:
             # the history HF's processors see: the prompt rows as passed (-200 sentinels and pads included) + the ids every step is fed
             self.engine.set_constraints(b, input_ids.tolist(), max_new_tokens, **con)
@@ -387,10 +410,10 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if smp is not None:
             seen = [[int(i) for i in row if int(i) >= 0] for row in input_ids.tolist()]
             self.engine.set_sampling(b, seen=seen, **smp)
-            tok = self.engine.sample(out.local_logits)
+            tok = self.engine.sample(local_logits)
         else:
             self.engine.sampling_off()
-            tok = self.engine.argmax(out.local_logits)
+            tok = self.engine.argmax(local_logits)
         padded = getattr(self, "_padded_batch", False)
         # The KV cache is context-owned with a fixed capacity (the reference's DynamicCache grows without bound): generate as
         # many tokens as fit and stop cleanly, returning what was produced, instead of failing mid-stream with 'KV cache full'.
@@ -472,6 +495,46 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         keep = ~torch.stack(padded_out, dim=1)
         zero = torch.zeros((), dtype=torch.float32)
         return GenerateOutput(seqs, torch.where(keep, raw, zero), torch.where(keep, proc, zero))
+
+    def _group_params(self, input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer):
+        """(N, share_prompt) of generate(do_sample=True, num_return_sequences=N > 1) with num_beams == 1, or None for N == 1 (and under beam
+        search, which reads the argument itself); every refusal is raised here, from host data alone, before any work is enqueued"""
+        gc = self.generation_config
+        N = num_return_sequences if num_return_sequences is not None else (getattr(gc, "num_return_sequences", None) or 1)
+        if nb > 1:
+            return None
+        if not (isinstance(N, int) and N >= 1):
+            raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {N}")
+        if N == 1:
+            return None
+        if not do_sample:
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {N}).")
+        b = input_ids.shape[0]
+        e = self.engine
+        if b * N > e.c.max_batch:
+            raise ValueError(f"num_return_sequences needs b * num_return_sequences = {b * N} cache rows: create the model with max_batch >= "
+                             f"{b * N} (it has {e.c.max_batch})")
+        if attention_mask is not None and bool((attention_mask == 0).any()):
+            raise NotImplementedError("num_return_sequences > 1 over a padded batch (attention_mask with zeros) is not implemented: pad the "
+                                      "prompts to equal length or use b = 1")
+        ids_cpu = input_ids.detach().cpu()
+        if b > 1 and bool((ids_cpu == IMAGE_TOKEN_INDEX).any()) and len(set(self._spliced_lengths(ids_cpu, images))) > 1:
+            raise NotImplementedError("num_return_sequences > 1 over rows of different spliced length is not implemented: pad the prompts "
+                                      "to equal length or use b = 1")
+        if reuse:
+            raise NotImplementedError("num_return_sequences > 1 with reuse_cache=True is not implemented: the cache rows end as siblings, "
+                                      "not as one conversation")
+        if lookup is not None:
+            raise NotImplementedError("num_return_sequences > 1 with prompt_lookup_num_tokens is not implemented: a verify step runs one sequence")
+        if streamer is not None:
+            raise ValueError("`streamer` cannot be used with num_return_sequences > 1: it takes one sequence (b * num_return_sequences = "
+                             f"{b * N})")
+        if share_prompt:
+            from ..engine import group_share_refusal
+            why = group_share_refusal(getattr(e, "_fp8_kv", False), e.tp_size, e.c.t_heads, e.c.t_kv_heads, N)
+            if why is not None:
+                raise NotImplementedError(f"share_prompt=True is not available here ({why}): use share_prompt=False (DESIGN.md section 7)")
+        return N, (None if share_prompt is None else bool(share_prompt))
 
     def _forward_reuse(self, input_ids, images):
         """The prefill of generate(reuse_cache=True), b = 1: keeps the slots of sequence 0's cache that the new prompt shares with the
