@@ -209,6 +209,28 @@ int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream);
 /* host copy of the record of rows 0..b-1: raw / processed host fp32 [b][max_len] (entries behind a row's count are left as they are),
  * counts host int32 [b] = picks recorded per row.  Synchronises the device. */
 int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* processed, int32_t* counts, int max_len);
+/* omchat_set_logprobs_ex: omchat_set_logprobs, and next to the two numbers every pick also records, at the same device counter (so
+ * omchat_kv_rewind, the step enqueued ahead and the captured graph treat all records as one):
+ *   top alternatives  top_n pairs (global id, log-probability), 0 <= top_n <= OMCHAT_LP_MAX_TOP (0 = none), the top_n entries of
+ *                     log_softmax(logits) over the whole vocabulary under the RAW distribution -- the caller's logits before bans, penalty
+ *                     and temperature -- ordered by value descending, then by global id ascending.  -0.0 and +0.0 compare equal; an id whose
+ *                     logit is -inf has log-probability -inf and ranks behind every finite one.  The selection is exact (comparisons only).
+ *   scored ids        the raw log-probability of each of the n_score distinct global ids score_ids (host int32, 0 <= n_score <=
+ *                     OMCHAT_LP_MAX_SCORED, one list for all rows, fixed until the next call).
+ * Every value is x - (max + log sum) with the very (max, sum) of the picked id's raw value: where the picked id is among the alternatives or
+ * the scored ids, its entry is bit-equal to the raw record.  Switching the extras on changes no bit of the raw / processed record.  Refused
+ * before anything is enqueued: top_n outside 0..20 or beyond the whole vocabulary, more than 32 ids, a duplicate id, an id outside
+ * [0, t_vocab_total), under tensor parallelism a vocabulary of 2^24 ids or more (ids cross the exchange as fp32; still one all-reduce).
+ * top_n = 0 and n_score = 0 is omchat_set_logprobs: the same launches, no further allocation, no further graph node.  Another top_n or id
+ * list drops the captured decode graphs.  The extras' record grows with max_new (max_batch * (2 top_n + n_score) * 4 bytes a pick) and is
+ * counted in omchat_device_bytes.  Alternatives under the processed distribution, per-row id lists, beams and verify rows: not recorded. */
+#define OMCHAT_LP_MAX_TOP 20
+#define OMCHAT_LP_MAX_SCORED 32
+int omchat_set_logprobs_ex(omchat_ctx* ctx, int b, int max_new, int top_n, const int32_t* score_ids, int n_score, void* stream);
+/* host copy of the extras of rows 0..b-1: top_vals host fp32 [b][max_len][top_n], top_ids host int32 [b][max_len][top_n], scored host fp32
+ * [b][max_len][n_score] (each may be NULL; entries behind a row's count are left as they are), counts host int32 [b].  Refused while the
+ * extras are off.  Synchronises the device. */
+int omchat_read_logprob_extras(omchat_ctx* ctx, int b, float* top_vals, int32_t* top_ids, float* scored, int32_t* counts, int max_len);
 /* test accessor: the step counter of `row` and (seen_words host uint32 [(t_vocab + 31) / 32], may be NULL) its seen bitmap over this rank's
  * vocabulary slice, bit i of word w = local id 32 w + i.  Refused while sampling is off.  Synchronises the device. */
 int omchat_read_sampling_state(omchat_ctx* ctx, int row, int* step, uint32_t* seen_words);
@@ -700,6 +722,11 @@ int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int
 int omchat_op_token_logprob_interval(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
                                      float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
                                      const uint32_t* thr_lo, const uint32_t* thr_hi, float* raw_out, float* processed_out, void* stream);
+/* context-free extras of omchat_set_logprobs_ex (test hook, TP = 1): logits device fp32 [b][ld] (ld >= V); score_ids host int32 [n_score]
+ * or NULL; outputs device: top_vals fp32 [b][top_n], top_ids int32 [b][top_n], scored fp32 [b][n_score] (NULL where its count is 0).  The
+ * contract, the caps and the tie rule (value descending, -0 == +0, then id ascending) are omchat_set_logprobs_ex's.  Synchronises. */
+int omchat_op_top_logprobs(const float* logits, int b, int V, int ld, int top_n, const int32_t* score_ids, int n_score, float* top_vals,
+                           int32_t* top_ids, float* scored, void* stream);
 /* context-free beam step (test hook of omchat_beam_step's selection, TP = 1): logits fp32 [rows, V] (rows = b at t = 0, else b*N), step t
  * of max_new; state: device int32 [omchat_beam_state_words(b, N, max_new)] carried from call to call (initialised by the t = 0 call).
  * Outputs device int32: tokens [b*N], parents [b*N] (rows; a row's own index at t = 0 and for frozen prompts), done_word [1]. */

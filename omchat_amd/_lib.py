@@ -58,6 +58,8 @@ _SIGS = {
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
     "omchat_set_logprobs": (_i, [_vp, _i, _i, _vp]),
     "omchat_read_logprobs": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "omchat_set_logprobs_ex": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
+    "omchat_read_logprob_extras": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i]),
     "omchat_group_begin": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "omchat_group_share_available": (_i, [_vp, _i]),
     "omchat_beam_begin": (_i, [_vp, _i, _i, _f, _i, _vp, _i, _i, _i, _vp]),
@@ -149,6 +151,7 @@ _SIGS = {
     "omchat_op_layernorm_ld": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_op_token_logprob": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "omchat_op_top_logprobs": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "omchat_op_sample_filtered": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _i,
                                        _vp, _vp, _vp, _vp]),
     "omchat_op_sample_verify": (_i, [_vp, _i, _i, _i, _vp, _u64, _i, _f, _i, C.c_double, _f, C.c_double, C.c_double, C.c_double, C.c_double, _vp,

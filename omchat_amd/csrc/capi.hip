@@ -551,6 +551,38 @@ extern "C" int omchat_op_token_logprob_interval(const float* logits, int b, int 
                           processed_out, stream);
 }
 
+extern "C" int omchat_op_top_logprobs(const float* logits, int b, int V, int ld, int top_n, const int32_t* score_ids, int n_score, float* top_vals,
+                                      int32_t* top_ids, float* scored, void* stream) {
+  OM_CHECK(logits && b >= 1 && V >= 1 && ld >= V, "bad argument");
+  OM_CHECK(top_n >= 0 && top_n <= OMCHAT_LP_MAX_TOP && top_n <= V, "0 <= top_n <= 20, at most the vocabulary");
+  OM_CHECK(n_score >= 0 && n_score <= OMCHAT_LP_MAX_SCORED && (top_n > 0 || n_score > 0), "0 <= n_score <= 32, and one of the two extras");
+  OM_CHECK((!top_n || (top_vals && top_ids)) && (!n_score || (score_ids && scored)), "an extra without its output");
+  for (int i = 0; i < n_score; ++i) {
+    OM_CHECK(score_ids[i] >= 0 && score_ids[i] < V, "scored id outside the vocabulary");
+    for (int j = 0; j < i; ++j) OM_CHECK(score_ids[j] != score_ids[i], "scored ids must be distinct");
+  }
+  hipStream_t s = S(stream);
+  const size_t wsb = logprob_ws_bytes(b), xwb = (logprob_top_ws_bytes(b, top_n) + 15) / 16 * 16, rb = ((size_t)b * 4 + 15) / 16 * 16;
+  char* mem = nullptr;
+  OM_HIP(hipMalloc(&mem, wsb + xwb + 4 * rb + (size_t)OMCHAT_LP_MAX_SCORED * 4));
+  int* d_ids = (int*)(mem + wsb + xwb);      // the picked id of every row: 0 (its record is not read)
+  int* d_cnt = (int*)(mem + wsb + xwb + rb);
+  float* d_rec = (float*)(mem + wsb + xwb + 2 * rb);      // [2][1][b]
+  int* d_sid = (int*)(mem + wsb + xwb + 4 * rb);
+  hipMemsetAsync(d_ids, 0, 2 * rb, s);
+  if (n_score) hipMemcpyAsync(d_sid, score_ids, (size_t)n_score * 4, hipMemcpyHostToDevice, s);
+  LogprobArgs a;
+  a.raw = logits; a.raw_ld = ld; a.b = b; a.V = V; a.ids = d_ids;
+  a.ws = mem; a.rec = d_rec; a.cnt = d_cnt; a.max_new = 1; a.rec_ld = b;
+  a.top_n = top_n; a.n_score = n_score; a.score_ids = d_sid; a.top_ws = mem + wsb;
+  a.top_vals = top_vals; a.top_ids = top_ids; a.scored = scored;      // line 0 of a one-line record is the output's layout
+  int rc = launch_logprob(a, s);
+  hipStreamSynchronize(s);
+  hipFree(mem);
+  return rc;
+}
+
+static_assert(LP_MAX_TOP == OMCHAT_LP_MAX_TOP && LP_MAX_SCORED == OMCHAT_LP_MAX_SCORED, "log-prob extras caps: kernels.h and omchat_hip.h");
 static_assert(CON_NGRAM_MAX == OMCHAT_CON_MAX_NGRAM && CON_EOS_MAX == OMCHAT_CON_MAX_EOS && CON_SUPPRESS_MAX == OMCHAT_CON_MAX_SUPPRESS &&
               CON_BAD_WORDS_MAX == OMCHAT_CON_MAX_BAD_WORDS && CON_BAD_WORD_IDS_MAX == OMCHAT_CON_MAX_BAD_WORD_IDS, "constraint caps: kernels.h and omchat_hip.h");
 

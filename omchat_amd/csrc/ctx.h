@@ -70,6 +70,23 @@ struct PickState {
   // begin (host bound for the record's capacity)
   struct Logprobs { bool on = false; int b = 0, max_new = 0; };
   Logprobs lp;
+  // extras of the record (omchat_set_logprobs_ex; nothing of this is allocated before they are asked for): top_n alternatives and the
+  // n_score scored ids of every pick.  lp_xrec = [vals float | ids int32][lp_cap][max_batch][top_n] then scored float
+  // [lp_cap][max_batch][n_score], written at the same device counters as lp_rec; lp_xws the slices' candidates, lp_sid the scored ids
+  // (device), lp_xtable the exchange table with room for them (it replaces lp_table while they are on)
+  struct Extras {
+    int top_n = 0, n_score = 0; std::vector<int32_t> ids;
+    bool on() const { return top_n > 0 || n_score > 0; }
+    bool operator==(const Extras& o) const { return top_n == o.top_n && n_score == o.n_score && ids == o.ids; }
+  };
+  Extras lpx;
+  void* lp_xws = nullptr;
+  int32_t* lp_sid = nullptr;
+  float* lp_xtable = nullptr;
+  Grown lp_xrec;
+  float* lpx_vals() const { return (float*)lp_xrec.p; }
+  int32_t* lpx_ids(int cap, int mb) const { return (int32_t*)lp_xrec.p + (size_t)cap * mb * lpx.top_n; }
+  float* lpx_scored(int cap, int mb) const { return (float*)lp_xrec.p + (size_t)2 * cap * mb * lpx.top_n; }
   int lp_picks = 0;
   int lp_cap = 0;      // lines per plane of the record as allocated (>= lp.max_new; grown, never shrunk): the stride the kernels are given
   int* lp_cnt = nullptr;
@@ -80,7 +97,7 @@ struct PickState {
   bool sampling_on() const { return smp.on; }
   bool constraints_on() const { return con.on; }
   bool logprobs_on() const { return lp.on; }
-  void release() { con_hist.release(); lp_rec.release(); }
+  void release() { con_hist.release(); lp_rec.release(); lp_xrec.release(); }
 };
 
 // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand

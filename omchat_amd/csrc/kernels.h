@@ -471,9 +471,21 @@ struct LogprobArgs {
   int (*xchg)(void* user, float* buf, size_t count, hipStream_t s) = nullptr;
   void* xchg_user = nullptr;
   float* rec = nullptr; int* cnt = nullptr; int max_new = 0, rec_ld = 0;
+  // extras (both 0: the launches above and nothing else): the top_n <= 20 best (log_softmax(raw) value, global id) pairs of every row, by
+  // value descending (-0 == +0) then id ascending, into top_vals / top_ids [max_new][rec_ld][top_n], and the raw log-probability of the
+  // n_score <= 32 global ids score_ids (device) into scored [max_new][rec_ld][n_score] -- line cnt[row], before it advances; the values are
+  // lp_value(x, m0, s0) with the (m0, s0) of the picked id's raw value.  top_ws: logprob_top_ws_bytes(b, top_n); tp > 1: table is
+  // logprob_table_bytes_ex(b, tp, top_n, n_score), still one xchg, and V * tp < 2^24 (ids cross as fp32)
+  int top_n = 0, n_score = 0;                       // <= LP_MAX_TOP, <= LP_MAX_SCORED
+  const int* score_ids = nullptr;
+  void* top_ws = nullptr;
+  float* top_vals = nullptr; int* top_ids = nullptr; float* scored = nullptr;
 };
+constexpr int LP_MAX_TOP = 20, LP_MAX_SCORED = 32;      // the public header's OMCHAT_LP_MAX_* (capi.hip asserts they agree)
 size_t logprob_ws_bytes(int b);
 size_t logprob_table_bytes(int b, int tp);
+size_t logprob_top_ws_bytes(int b, int top_n);
+size_t logprob_table_bytes_ex(int b, int tp, int top_n, int n_score);
 int launch_logprob(const LogprobArgs& a, hipStream_t s);
 int launch_logprob_rewind(int* cnt, int b, int n, hipStream_t s);      // cnt[i] -= n for rows < b
 // HF logits constraints (constrain.hip; tests/constraints_ref.py restates the ban set).  The caps are the public

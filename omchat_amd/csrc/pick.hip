@@ -74,6 +74,11 @@ int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, c
   }
   a.ws = P.lp_ws; a.table = P.lp_table; a.xchg = smp_xchg; a.xchg_user = ctx;
   a.rec = (float*)P.lp_rec.p; a.cnt = P.lp_cnt; a.max_new = P.lp_cap; a.rec_ld = c.max_batch;
+  if (P.lpx.on()) {      // the same counters, the same lines: nothing of its own to rewind or to bound
+    a.top_n = P.lpx.top_n; a.n_score = P.lpx.n_score; a.score_ids = P.lp_sid; a.top_ws = P.lp_xws;
+    a.top_vals = P.lpx_vals(); a.top_ids = P.lpx_ids(P.lp_cap, c.max_batch); a.scored = P.lpx_scored(P.lp_cap, c.max_batch);
+    if (ctx->tp_size > 1) a.table = P.lp_xtable;
+  }
   return launch_logprob(a, s);
 }
 
@@ -397,12 +402,18 @@ extern "C" int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngra
 // Per-token log-probabilities (include/omchat_hip.h).  The record and its geometry live in the kernel arguments of the captured decode graphs:
 // switching on or off, another b / max_new or a record that had to grow drops them.
 extern "C" int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* stream) {
+  return omchat_set_logprobs_ex(ctx, b, max_new, 0, nullptr, 0, stream);
+}
+
+// (the extras -- top_n and the scored ids -- are kernel arguments of the same graphs: a change of either, or of a buffer's address, drops them)
+extern "C" int omchat_set_logprobs_ex(omchat_ctx* ctx, int b, int max_new, int top_n, const int32_t* score_ids, int n_score, void* stream) {
   OM_CHECK(ctx, "null ctx");
   PickState& P = ctx->pick;
   const omchat_config& c = ctx->c;
   if (b <= 0) {
     if (P.lp.on) drop_decode_graphs(ctx);
     P.lp = PickState::Logprobs{};
+    P.lpx = PickState::Extras{};
     P.lp_picks = 0;
     return 0;
   }
@@ -410,22 +421,47 @@ extern "C" int omchat_set_logprobs(omchat_ctx* ctx, int b, int max_new, void* st
   OM_CHECK(b <= c.max_batch, "logprobs: batch exceeds max_batch");
   OM_CHECK(max_new >= 1, "logprobs: max_new >= 1");
   OM_CHECK(!ctx->beam.on(), "logprobs: a beam search is active (it reports sequences_scores)");
+  PickState::Extras x;
+  OM_CHECK(top_n >= 0 && top_n <= OMCHAT_LP_MAX_TOP, "logprobs: 0 <= top_n <= 20 (0 = no alternatives)");
+  OM_CHECK(top_n <= c.t_vocab_total, "logprobs: top_n exceeds the vocabulary");
+  OM_CHECK(n_score >= 0 && n_score <= OMCHAT_LP_MAX_SCORED && (n_score == 0 || score_ids), "logprobs: 0 <= n_score <= 32 scored ids");
+  x.top_n = top_n; x.n_score = n_score;
+  if (n_score) x.ids.assign(score_ids, score_ids + n_score);
+  for (int i = 0; i < n_score; ++i) {
+    OM_CHECK(x.ids[i] >= 0 && x.ids[i] < c.t_vocab_total, "logprobs: scored id outside the vocabulary");
+    for (int j = 0; j < i; ++j) OM_CHECK(x.ids[j] != x.ids[i], "logprobs: scored ids must be distinct");
+  }
+  OM_CHECK(!x.on() || ctx->tp_size == 1 || c.t_vocab_total < (1 << 24), "logprobs: under tensor parallelism the alternatives' ids cross the exchange as fp32 (vocabulary < 2^24)");
   if (!P.lp_cnt) {
     TRY(ctx->alloc((void**)&P.lp_cnt, (size_t)c.max_batch * 4));
     TRY(ctx->alloc(&P.lp_ws, logprob_ws_bytes(c.max_batch)));
     if (ctx->tp_size > 1) TRY(ctx->alloc((void**)&P.lp_table, logprob_table_bytes(c.max_batch, ctx->tp_size)));
   }
+  // the extras' fixed buffers at their caps, each when it is first asked for
+  if (x.top_n && !P.lp_xws) TRY(ctx->alloc(&P.lp_xws, logprob_top_ws_bytes(c.max_batch, OMCHAT_LP_MAX_TOP)));
+  if (x.n_score && !P.lp_sid) TRY(ctx->alloc((void**)&P.lp_sid, (size_t)OMCHAT_LP_MAX_SCORED * 4));
+  if (x.on() && ctx->tp_size > 1 && !P.lp_xtable)
+    TRY(ctx->alloc((void**)&P.lp_xtable, logprob_table_bytes_ex(c.max_batch, ctx->tp_size, OMCHAT_LP_MAX_TOP, OMCHAT_LP_MAX_SCORED)));
   // the captured graphs hold the record's address, its capacity (the stride of the processed plane) and b: another max_new within the
   // capacity keeps them (the host refuses the picks beyond it)
   void* old = P.lp_rec.p;
+  void* oldx = P.lp_xrec.p;
+  const int old_cap = P.lp_cap;
   if (max_new > P.lp_cap) {
     TRY(ctx->grow(P.lp_rec, (size_t)2 * max_new * c.max_batch * 4));
     P.lp_cap = max_new;
   }
-  if (!P.lp.on || P.lp.b != b || old != P.lp_rec.p) drop_decode_graphs(ctx);
+  if (x.on()) TRY(ctx->grow(P.lp_xrec, (size_t)P.lp_cap * c.max_batch * (2 * x.top_n + x.n_score) * 4));
+  if (!P.lp.on || P.lp.b != b || old != P.lp_rec.p || old_cap != P.lp_cap || !(x == P.lpx) || (x.on() && oldx != P.lp_xrec.p)) drop_decode_graphs(ctx);
   P.lp.on = true; P.lp.b = b; P.lp.max_new = max_new;
+  P.lpx = x;
   P.lp_picks = 0;
-  OM_HIP(hipMemsetAsync(P.lp_cnt, 0, (size_t)c.max_batch * 4, (hipStream_t)stream));
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemsetAsync(P.lp_cnt, 0, (size_t)c.max_batch * 4, s));
+  if (n_score) {
+    OM_HIP(hipMemcpyAsync(P.lp_sid, P.lpx.ids.data(), (size_t)n_score * 4, hipMemcpyHostToDevice, s));
+    OM_HIP(hipStreamSynchronize(s));     // host vector
+  }
   return 0;
 }
 
@@ -448,5 +484,36 @@ extern "C" int omchat_read_logprobs(omchat_ctx* ctx, int b, float* raw, float* p
       processed[(size_t)i * max_len + t] = rec[((size_t)mn + t) * mb + i];
     }
   }
+  return 0;
+}
+
+extern "C" int omchat_read_logprob_extras(omchat_ctx* ctx, int b, float* top_vals, int32_t* top_ids, float* scored, int32_t* counts, int max_len) {
+  OM_CHECK(ctx && counts, "null argument");
+  const PickState& P = ctx->pick;
+  OM_CHECK(P.lp.on && P.lpx.on(), "omchat_read_logprob_extras: the extras are off (omchat_set_logprobs_ex with top_n or scored ids first)");
+  OM_CHECK(b >= 1 && b <= P.lp.b, "omchat_read_logprob_extras: rows that omchat_set_logprobs_ex switched on");
+  const int mb = ctx->c.max_batch, mn = P.lp_cap, tn = P.lpx.top_n, ns = P.lpx.n_score;
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<int> cnt(mb);
+  OM_HIP(hipMemcpy(cnt.data(), P.lp_cnt, cnt.size() * 4, hipMemcpyDeviceToHost));
+  int lines = 0;
+  for (int i = 0; i < b; ++i) {
+    counts[i] = std::min(std::max(cnt[i], 0), P.lp.max_new);
+    OM_CHECK(counts[i] <= max_len, "omchat_read_logprob_extras: max_len too small");
+    lines = std::max(lines, counts[i]);
+  }
+  // the first `lines` lines of a plane [lp_cap][max_batch][w] -> host [b][max_len][w]
+  auto plane = [&](const void* dev, void* host, int w) -> int {
+    if (!host || !w || !lines) return 0;
+    std::vector<uint32_t> h((size_t)lines * mb * w);
+    OM_HIP(hipMemcpy(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < b; ++i)
+      for (int t = 0; t < counts[i]; ++t)
+        std::copy_n(&h[((size_t)t * mb + i) * w], w, (uint32_t*)host + ((size_t)i * max_len + t) * w);
+    return 0;
+  };
+  TRY(plane(P.lpx_vals(), top_vals, tn));
+  TRY(plane(P.lpx_ids(mn, mb), top_ids, tn));
+  TRY(plane(P.lpx_scored(mn, mb), scored, ns));
   return 0;
 }

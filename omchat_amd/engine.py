@@ -74,7 +74,7 @@ class Engine:
         self._prefix = None
         self._tile_key_next = 0
         self._ext_st = dict(kept_slots=0, prefilled_rows=0, tiles_encoded=0, tiles_reused=0)
-        self._lp_max_new, self._logprobs_on = 0, False      # set_logprobs
+        self._lp_max_new, self._logprobs_on, self._lp_extras = 0, False, (0, 0)      # set_logprobs
         self._enc_st = dict(calls=0, tiles=0)               # encode_images
 
     def close(self):
@@ -557,17 +557,37 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ per-token log-probabilities (include/omchat_hip.h: omchat_set_logprobs)
-    def set_logprobs(self, b, max_new):
+    def set_logprobs(self, b, max_new, top_n=0, score_token_ids=None):
         """every following token pick of rows 0..b-1 (argmax or sampler, eager or in the decode graph) records the raw and the processed
         log-probability of its id on the device; at most max_new picks.  Resets the rows' counters.  Sticky until
-        logprobs_off() (or b = 0)."""
-        check(self.lib.omchat_set_logprobs(self.h, int(b), int(max_new), cur_stream()))
+        logprobs_off() (or b = 0).  top_n (1..20) / score_token_ids (1..32 distinct ids): the extras of omchat_set_logprobs_ex -- the top_n
+        alternatives and the listed ids' log-probabilities under the raw distribution, at every pick (read_logprob_extras)."""
+        ids = [int(i) for i in (score_token_ids if score_token_ids is not None else [])]
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        check(self.lib.omchat_set_logprobs_ex(self.h, int(b), int(max_new), int(top_n), arr if ids else None, len(ids), cur_stream()))
         self._lp_max_new = int(max_new)
         self._logprobs_on = int(b) > 0
+        self._lp_extras = (int(top_n), len(ids)) if int(b) > 0 else (0, 0)
 
     def logprobs_off(self):
         check(self.lib.omchat_set_logprobs(self.h, 0, 0, cur_stream()))
         self._logprobs_on = False
+        self._lp_extras = (0, 0)
+
+    def read_logprob_extras(self, b):
+        """one synchronising copy of the extras' record -> (top_vals fp32 [b, m, top_n], top_ids int64 [b, m, top_n], scored fp32
+        [b, m, n_score], counts list); m = the longest row's count, entries behind a row's own count are 0 / -1 / 0.  Refused by the
+        library when the extras are off."""
+        torch = _torch()
+        n, (tn, ns) = max(self._lp_max_new, 1), self._lp_extras
+        vals = torch.zeros(b, n, tn, dtype=torch.float32)
+        ids = torch.full((b, n, tn), -1, dtype=torch.int32)
+        sc = torch.zeros(b, n, ns, dtype=torch.float32)
+        cnt = torch.zeros(b, dtype=torch.int32)
+        check(self.lib.omchat_read_logprob_extras(self.h, int(b), ptr(vals) if tn else None, ptr(ids) if tn else None, ptr(sc) if ns else None,
+                                                  ptr(cnt), n))
+        m = int(cnt.max()) if b else 0
+        return vals[:, :m].contiguous(), ids[:, :m].to(torch.int64).contiguous(), sc[:, :m].contiguous(), [int(x) for x in cnt]
 
     def read_logprobs(self, b):
         """one synchronising copy of the record (the whole device record, every row and line, whatever b: a few KB) -> (raw fp32 [b, n],

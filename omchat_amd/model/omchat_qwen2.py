@@ -297,7 +297,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
                  repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
                  num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, output_logprobs=None, share_prompt=None,
-                 **kwargs):
+                 top_logprobs=None, score_token_ids=None, **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
@@ -323,6 +323,11 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         under the model's raw distribution and .processed_logprobs [b, new] under the distribution the pick was made from (bans, repetition
         penalty, temperature, top-k / top-p and the four filters behind them); recorded by the pick on the device, read back once at the end.  Positions behind a row's EOS,
         where the sequence holds pad, are 0.  Refused with num_beams > 1 (sequences_scores) and with prompt_lookup_num_tokens.
+        top_logprobs=n (1..20) and score_token_ids=[...] (1..32 distinct ids of the vocabulary), each with output_logprobs=True (also read
+        from generation_config): the output also carries .top_logprobs / .top_token_ids [b, new, n] -- the n most likely ids of every
+        position under the raw distribution, by log-probability descending, then id ascending -- and .scored_logprobs [b, new, k], the raw
+        log-probability of the listed ids at every position (multiple-choice scoring); selected and recorded on the device like the two
+        numbers above.  Behind a row's EOS: 0.0 / -1 / 0.0.
         num_return_sequences=N with do_sample=True and num_beams == 1 (also read from generation_config): returns
         [b * N, T + new], prompt-major (rows i*N .. i*N+N-1 belong to prompt i, HF's _expand_inputs_for_generation order); log-prob fields
         [b * N, new].  Each prompt is prefilled ONCE -- every sibling sees its own prompt's tiles, as under beam search -- and row i*N + j
@@ -345,6 +350,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
         group = self._group_params(input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer)
         olp = bool(output_logprobs if output_logprobs is not None else getattr(gc, "output_logprobs", False))
+        top_n, score_ids = resolve_logprob_extras(gc, olp, top_logprobs, score_token_ids, self.engine.c.t_vocab_total)
         if olp:      # every refusal before any work
             if not return_dict_in_generate:
                 raise ValueError("output_logprobs=True needs return_dict_in_generate=True: the log-probabilities come back as fields of a "
@@ -406,7 +412,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             # the history HF's processors see: the prompt rows as passed (-200 sentinels and pads included) + the ids every step is fed
             self.engine.set_constraints(b, input_ids.tolist(), max_new_tokens, **con)
         if olp:
-            self.engine.set_logprobs(b, max_new_tokens)               # the prefill's pick below is record 0
+            self.engine.set_logprobs(b, max_new_tokens, top_n, score_ids)      # the prefill's pick below is record 0
         if smp is not None:
             seen = [[int(i) for i in row if int(i) >= 0] for row in input_ids.tolist()]
             self.engine.set_sampling(b, seen=seen, **smp)
@@ -494,7 +500,18 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise RuntimeError(f"log-probability record out of step with the generated tokens: {counts} records for {len(new)} tokens")
         keep = ~torch.stack(padded_out, dim=1)
         zero = torch.zeros((), dtype=torch.float32)
-        return GenerateOutput(seqs, torch.where(keep, raw, zero), torch.where(keep, proc, zero))
+        res = GenerateOutput(seqs, torch.where(keep, raw, zero), torch.where(keep, proc, zero))
+        if top_n or score_ids:
+            tv, ti, sc, xcounts = self.engine.read_logprob_extras(b)
+            if xcounts != counts:
+                raise RuntimeError(f"log-probability extras out of step with the record: {xcounts} against {counts}")
+            k3 = keep.unsqueeze(-1)
+            if top_n:
+                res.add("top_logprobs", torch.where(k3, tv, zero))
+                res.add("top_token_ids", torch.where(k3, ti, torch.full((), -1, dtype=torch.int64)))
+            if score_ids:
+                res.add("scored_logprobs", torch.where(k3, sc, zero))
+        return res
 
     def _group_params(self, input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer):
         """(N, share_prompt) of generate(do_sample=True, num_return_sequences=N > 1) with num_beams == 1, or None for N == 1 (and under beam
@@ -699,8 +716,39 @@ class GenerateOutput(dict):
     """generate(output_logprobs=True, return_dict_in_generate=True): `.sequences` [b, T + new] as the plain call returns them, `.logprobs`
     [b, new] = log_softmax(logits)[token] of every generated token (HF: compute_transition_scores on out.logits with normalize_logits=True)
     and `.processed_logprobs` [b, new] = the same under the processed scores the pick was made from (on out.scores); full-vocabulary
-    `scores` / `logits` tuples are not kept"""
+    `scores` / `logits` tuples are not kept.  Present only when asked for (top_logprobs=n / score_token_ids=[...]): `.top_logprobs`
+    [b, new, n] fp32 with `.top_token_ids` [b, new, n] int64, and `.scored_logprobs` [b, new, k] fp32, all under the raw distribution"""
 
     def __init__(self, sequences, logprobs, processed_logprobs):
         super().__init__(sequences=sequences, logprobs=logprobs, processed_logprobs=processed_logprobs)
         self.sequences, self.logprobs, self.processed_logprobs = sequences, logprobs, processed_logprobs
+
+    def add(self, name, value):
+        self[name] = value
+        setattr(self, name, value)
+
+
+def resolve_logprob_extras(gc, olp, top_logprobs, score_token_ids, vocab):
+    """generate()'s top_logprobs / score_token_ids (the call's, else generation_config's) -> (top_n, ids list), (0, []) when neither is
+    given; every refusal is a ValueError raised from host data alone"""
+    n = top_logprobs if top_logprobs is not None else getattr(gc, "top_logprobs", None)
+    ids = score_token_ids if score_token_ids is not None else getattr(gc, "score_token_ids", None)
+    if n is None and ids is None:
+        return 0, []
+    if not olp:
+        raise ValueError("top_logprobs / score_token_ids need output_logprobs=True (and return_dict_in_generate=True): they are fields of "
+                         "the same record")
+    if n is not None and not (isinstance(n, int) and not isinstance(n, bool) and 1 <= n <= 20):
+        raise ValueError(f"`top_logprobs` has to be an integer in 1..20, but is {n}")
+    if n is not None and n > vocab:
+        raise ValueError(f"`top_logprobs` ({n}) exceeds the vocabulary ({vocab})")
+    if ids is not None:
+        ids = [int(i) for i in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+        if not 1 <= len(ids) <= 32:
+            raise ValueError(f"`score_token_ids` has to hold 1..32 ids, but holds {len(ids)}")
+        if len(set(ids)) != len(ids):
+            raise ValueError("`score_token_ids` has to hold distinct ids")
+        bad = [i for i in ids if not 0 <= i < vocab]
+        if bad:
+            raise ValueError(f"`score_token_ids` outside the vocabulary [0, {vocab}): {bad}")
+    return int(n or 0), list(ids or [])

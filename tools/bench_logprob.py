@@ -2,8 +2,9 @@
 context:
     python tools/bench_logprob.py [--iters 200] [--repeats 5]
 Prints one JSON line per (batch, pick): microseconds per pick (GPU time of a back-to-back loop, events around it; median and spread over the
-repeats) with logprobs off and on, and the added microseconds.  On a commit without Engine.set_logprobs only the "off" column is measured:
-run it there for the parent's column."""
+repeats) with logprobs off and on, and the added microseconds; then with the record's extras on -- top_n = 5, top_n = 20, 4 scored ids --
+and what each adds to "on".  On a commit without Engine.set_logprobs only the "off" column is measured (run it there for the parent's
+column); on one without the extras the three further columns are left out."""
 import argparse
 import json
 import os
@@ -27,6 +28,8 @@ def main():
     cfg = tiny(vocab=152064)
     e = Engine(cfg, dtype="bf16", max_seq=16, max_batch=32, max_tiles=1, vision=False)
     has = hasattr(e, "set_logprobs")
+    extras = hasattr(e, "read_logprob_extras")
+    EXTRAS = [("top5", dict(top_n=5)), ("top20", dict(top_n=20)), ("scored4", dict(score_token_ids=[32, 33, 34, 35]))]
 
     def timed(fn, arm):
         out = []
@@ -58,6 +61,10 @@ def main():
             if has:
                 row["on"] = timed(fn, lambda: e.set_logprobs(b, args.iters + 10))
                 row["added_us"] = round(row["on"]["us"] - off["us"], 2)
+            if has and extras:
+                for col, kw in EXTRAS:
+                    row[col] = timed(fn, lambda: e.set_logprobs(b, args.iters + 10, **kw))
+                    row[col + "_added_us"] = round(row[col]["us"] - row["on"]["us"], 2)
             print(json.dumps(row))
     if has:
         e.logprobs_off()
