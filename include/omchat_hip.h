@@ -335,6 +335,10 @@ int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, int n, void*
  * bounds the step (small per-rank kernels under tensor parallelism, a busy Python thread). */
 int omchat_enable_decode_graph(omchat_ctx* ctx, int on);
 int omchat_decode_graph_stats(omchat_ctx* ctx, long* steps, long* replays, long* captures);
+/* bf16x12: *roles = the roles tuning key 50 selects now (bit 0 gate|up, 1 down_proj, 2 lm_head); launches[3] = coded launches
+ * enqueued so far per role by eager steps and graph captures; coded[3] = tensors of the role that are coded (built, under the patch cap).
+ * Any pointer may be NULL. */
+int omchat_bf16x12_stats(omchat_ctx* ctx, int* roles, long* launches, int* coded);
 
 /* ---- weight-only fp8 for decode (BASELINE configs[4]) -------------------------------------------- */
 /* Builds (once) an OCP e4m3 replica of the decoder weights that a decode step streams (fused qkv, o, gate|up, down,
@@ -579,6 +583,14 @@ int omchat_op_gemv_mxfp4_rows(int dtype, const void* X, int ldx, const void* W4,
                               const void* bias, int epi, int out_f32, int ksplit, void* stream);
 int omchat_op_gemv_mxfp4_packed(int dtype, const void* X, int ldx, const void* W4, const void* S, void* Y, int ldy, int b, int N, int K,
                                 const void* bias, int epi, int out_f32, int ksplit, int y_packed, void* stream);
+/* bf16x12 pieces: the lossless 12-bit coding of bf16 rows that the long batch-1 decode GEMVs stream (DESIGN.md section 17;
+ * tests/bf16x12_ref.py defines the format).  _encode: W bf16 [N][K], K % 512 == 0 -> coded [N][K * 3 / 2] bytes, top [N] bytes, cnt [N] bytes
+ * (min(misses, 33)), patch [N][32] uint32; *over (device int, zeroed by the caller) becomes 1 when a row needs more than 32 patches -- such a
+ * matrix is not coded.  _gemv: y = the bits of the 16-bit launch on the same matrix, batch 1, for norm_w != NULL with EPI_SWIGLU / EPI_NONE
+ * (omchat_op_gemv_norm, K <= 4096) and for EPI_RESID with resid on 4096 < K <= 32768 (omchat_op_gemv) */
+int omchat_op_encode_bf16x12(const void* W, int N, int K, void* coded, void* top, void* cnt, void* patch, void* over, void* stream);
+int omchat_op_gemv_bf16x12(const void* X, const void* coded, const void* top, const void* cnt, const void* patch, void* Y, int N, int K,
+                           const void* norm_w, float eps, const void* resid, int epi, int out_f32, void* stream);
 /* pack once, launch many times (tools/bench_mxfp4.py): omchat_op_pack_w: W [N, K] -> packed 16-bit replica (N K elements);
  * omchat_op_pack_w4: W4 / S -> packed MXFP4 replica W4P (N K / 2 bytes), SP (N K / 32 bytes); omchat_op_gemv_prepacked: the launch alone on
  * XP (omchat_op_pack_x) and WP, with SP = NULL for 16-bit weights; no allocation, no synchronisation */

@@ -101,6 +101,7 @@ _SIGS = {
     "omchat_enable_fp8_kv": (_i, [_vp, _i]),
     "omchat_enable_fp8_prefill": (_i, [_vp, _i]),
     "omchat_enable_decode_graph": (_i, [_vp, _i]),
+    "omchat_bf16x12_stats": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_long), C.POINTER(_i)]),
     "omchat_decode_graph_stats": (_i, [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "omchat_op_quant_fp8": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_op_gemv_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
@@ -113,6 +114,8 @@ _SIGS = {
     "omchat_op_pack_w": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "omchat_op_pack_w4": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_op_gemv_prepacked": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "omchat_op_encode_bf16x12": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "omchat_op_gemv_bf16x12": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "omchat_op_gemv_mxfp4_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "omchat_op_rmsnorm": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "omchat_op_resid_rmsnorm": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),

@@ -104,6 +104,7 @@ extern "C" int omchat_op_set_tuning(int key, int value) {
   if (key == 47) { attn_set_kv8_tpw(value); return 0; }
   if (key == 48) { attn_set_kv8_fuse(value); return 0; }
   if (key == 49) { model_set_extend_attn(value); return 0; }
+  if (key == 50) { model_set_x12_roles(value); return 0; }
   if (key == 38) { gemv_set_gu_rr(value); return 0; }
   if (key == 39) { gemv_set_longk_direct(value); return 0; }
   if (key == 40) { norm_set_wave(value); return 0; }
@@ -830,6 +831,20 @@ extern "C" int omchat_op_gemv_mxfp4_norm(int dtype, const void* X, const void* W
   g.norm_w = norm_w; g.norm_eps = eps;
   g.mx_scale = (const unsigned char*)S_;
   return launch_gemv(dtype, g, S(stream));
+}
+
+// bf16x12 pieces (include/omchat_hip.h): the encoder into caller-provided buffers, and the three batch-1 roles on coded operands --
+// norm_w with EPI_SWIGLU (gate|up) or EPI_NONE (lm_head form), or EPI_RESID with resid (down_proj, long K)
+extern "C" int omchat_op_encode_bf16x12(const void* W, int N, int K, void* coded, void* top, void* cnt, void* patch, void* over, void* stream) {
+  return launch_encode_bf16x12(W, K, N, K, coded, (unsigned char*)top, (unsigned char*)cnt, (unsigned*)patch, (int*)over, S(stream));
+}
+extern "C" int omchat_op_gemv_bf16x12(const void* X, const void* coded, const void* top, const void* cnt, const void* patch, void* Y, int N, int K,
+                                      const void* norm_w, float eps, const void* resid, int epi, int out_f32, void* stream) {
+  OM_CHECK(X && coded && top && cnt && patch && Y, "null argument");
+  GemvArgs g{X, K, coded, K / 2 * 3, Y, N, 1, N, K, nullptr, resid, N, epi, out_f32};
+  g.norm_w = norm_w; g.norm_eps = eps;
+  g.x12_top = (const unsigned char*)top; g.x12_cnt = (const unsigned char*)cnt; g.x12_patch = (const unsigned*)patch;
+  return launch_gemv(OMCHAT_BF16, g, S(stream));
 }
 
 extern "C" int omchat_op_attn_prefill_d(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Sq, int Skv, int Hq,

@@ -162,6 +162,17 @@ struct omchat_ctx {
   const WRef* layer_w(int fmt, int layer) const { return &wt[fmt].e[(size_t)layer * 4]; }      // [P_QKV .. P_DOWN]
   const WRef& lm_w(int fmt) const { return wt[fmt].e.back(); }
   bool built(int fmt) const { return wt[fmt].state == W_BUILT; }
+  // bf16x12: the lossless 12-bit coding of the three long batch-1 launches' bf16 rows -- another encoding of the
+  // OMCHAT_WFMT_16 weights, bit for bit, so a table of its own and no value of the public enum.  One table per role (gate|up and down_proj of
+  // every layer, the lm_head), each taken all or nothing and built by the first batch-1 step that will use it; an entry whose tensor has a
+  // row over the patch cap is not coded (ok = false) and its projection keeps the 16-bit launch.  W_UNAVAILABLE: no room, or a K the forms
+  // do not take -- nothing is retried.  Re-encoded in place after omchat_load_tensor.
+  enum X12Role { X12_GU = 0, X12_DOWN = 1, X12_LM = 2, X12_ROLES = 3 };
+  struct X12Ref { void* W = nullptr; unsigned char* top = nullptr; unsigned char* cnt = nullptr; unsigned* patch = nullptr; bool ok = false; };
+  struct X12Table { std::vector<X12Ref> e; int state = W_ABSENT; };
+  X12Table x12[X12_ROLES];
+  int* x12_over = nullptr;      // device: one flag per entry of the role being encoded
+  long x12_launches[X12_ROLES] = {0, 0, 0};      // coded launches enqueued by eager steps and captures, per role (omchat_bf16x12_stats: the tests ask which launch a projection took)
   bool fp8_decode = false;
   int mxfp4_mode = 0;      // omchat_enable_mxfp4_decode: 0 = off, 1 = batch-1 steps, 2 = steps of 2 <= b <= 32 rows as well
   // BASELINE configs[4]: fp8 KV cache for decode (e4m3 bytes in the layout of the 16-bit cache + one fp32 scale per (layer, sequence,
@@ -383,6 +394,12 @@ struct omchat_ctx {
 // the weight operand of a GEMV from a table reference: W, ldw, the scales and w_packed -- nothing else
 inline void use_weight(GemvArgs& g, const omchat_ctx::WRef& w) {
   g.W = w.W; g.ldw = w.ldw; g.w_scale = w.w_scale; g.mx_scale = w.mx_scale; g.w_packed = w.packed;
+}
+
+// ... and from its bf16x12 coding (K = the projection's reduction length)
+inline void use_weight_x12(GemvArgs& g, const omchat_ctx::X12Ref& r, int K) {
+  g.W = r.W; g.ldw = K / 2 * 3; g.w_scale = nullptr; g.mx_scale = nullptr; g.w_packed = 0;
+  g.x12_top = r.top; g.x12_cnt = r.cnt; g.x12_patch = r.patch;
 }
 
 // ---- model.hip

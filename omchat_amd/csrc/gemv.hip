@@ -25,13 +25,17 @@ struct GemvP {
   void* y_pack;                            // gemv_xs_kernel<EPI_RESID>: packed copy of the result rows
   unsigned long long* dbg;                 // experiments build: clock stamps (measurement of the out-of-order prototype), else null
   const unsigned char* mx_s;               // non-null: W is MXFP4 (two e2m1 codes per byte, ldw in bytes) and mx_s [N][K / 32] holds the e8m0 block scales
+  const unsigned char* x12_top;            // non-null: W is bf16x12 (coded rows of ldw = K * 3 / 2 bytes) with x12_top [N], x12_cnt [N], x12_patch [N][32]
+  const unsigned char* x12_cnt;
+  const unsigned* x12_patch;
 #if OMCHAT_EXPERIMENTS
   int xskew;                               // tuning key 28 < 256 (experiment): workgroups moved from every odd XCD's share to every even XCD's (gate|up non-loop form)
 #endif
 };
 // weight format of the whole-row batch-1 forms (template switch): 16-bit, OCP e4m3 bytes + one fp32 scale per row, MXFP4 (OCP Microscaling
 // v1.0: e2m1 codes, two per byte, + one e8m0 scale per 32 consecutive k)
-constexpr int WF_16 = 0, WF_E4M3 = 1, WF_MX4 = 2;
+// ... and bf16x12, the lossless 12-bit coding of bf16 rows (below: "bf16x12"): the same weights bit for bit, three quarters of the bytes
+constexpr int WF_16 = 0, WF_E4M3 = 1, WF_MX4 = 2, WF_X12 = 3;
 // stamps: [0] merge end, [1] o_proj first start (stored inverted: max of ~t), [2] o_proj flags seen, [3] o_proj end, [4] gate|up first start (inverted), [5] gate|up end,
 // [6] down_proj first start (inverted), [7] down_proj end, [8] qkv first start (inverted), [9] qkv end, [10] attention first start (inverted), [11] attention end, [12] merge first start (inverted), [16 + x] gate|up end on XCD x
 #if OMCHAT_EXPERIMENTS
@@ -759,8 +763,97 @@ template <> __device__ __forceinline__ float rw_dot8_fp4<f16>(unsigned w, rw_u32
 template <int WF> struct RwW { typedef rw_u32x4 type; };
 template <> struct RwW<WF_E4M3> { typedef rw_u32x2 type; };
 template <> struct RwW<WF_MX4> { typedef rw_u32x2 type; };      // .x = the 8 codes, .y = the e8m0 byte of their block
+// ---------------------------------------------------------------------------------------------------------
+// bf16x12: bf16 rows coded losslessly in 12 bits per weight (tests/bf16x12_ref.py is the definition).  A record of 512
+// weights is 512 low bytes (e[0] + mantissa, untouched) and 256 nibble bytes (sign << 3 | code; code 0: e[7:1] = 0, code c: e[7:1] = top - 7 + c,
+// top = the row's largest e[7:1]); lane l of chunk c reads the 8 low bytes and the nibble word of weights k = 512 c + 8 l .. + 7 and rebuilds the
+// four registers the 16-bit load delivers -- the dot products behind it are the 16-bit kernel's, in its order: the same bits.  The rare
+// elements outside the code (<= 32 per row, k-sorted [N][32] list of k << 16 | bits) are written over the decoded registers by their lane.
+// Decode of 8 weights: 3 and/shift for the codes, 2 v_perm against the row's 8-entry table (two registers), 3 for the signs, 4 v_perm to
+// interleave high and low bytes.
+// ---------------------------------------------------------------------------------------------------------
+struct X12W { rw_u32x2 lo; unsigned nib; };
+template <> struct RwW<WF_X12> { typedef X12W type; };
+struct X12Row {
+  unsigned top_raw, cnt_raw;      // as loaded (uniform over the wave)
+  unsigned pv;                    // lane j < 32: patch entry j of the row
+  unsigned tlo, thi;              // code -> high byte (without the sign), entries 0..3 and 4..7
+  int cnt, pi;                    // wave-uniform: patches of the row, the next one to apply
+};
+// (row and chunk are the same in every lane of a wave: the record's address is scalar, a lane adds its two 32-bit offsets)
+__device__ __forceinline__ X12W x12_ldw(const GemvP& p, size_t row, int chunk, int lane) {
+  const unsigned char* rec = (const unsigned char*)p.W + row * (size_t)p.ldw + (size_t)chunk * 768;
+  const unsigned lo_off = 8u * (unsigned)lane, nib_off = 512u + 4u * (unsigned)lane;
+  X12W w;
+  w.lo = __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>(rec + lo_off));
+  w.nib = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(rec + nib_off));
+  return w;
+}
+// the row's top, patch count and patch entries: requested with the weight loads ...
+__device__ __forceinline__ void x12_row_load(X12Row& s, const GemvP& p, size_t row, int lane) {
+  s.top_raw = p.x12_top[row];
+  s.cnt_raw = p.x12_cnt[row];
+  s.pv = p.x12_patch[row * 32 + (lane & 31)];
+}
+// ... and turned into the table once they are in (scalar work: the values are the same in every lane)
+__device__ __forceinline__ void x12_row_finish(X12Row& s) {
+  const int t = __builtin_amdgcn_readfirstlane((int)s.top_raw) - 7;
+  s.cnt = __builtin_amdgcn_readfirstlane((int)s.cnt_raw);
+  s.pi = 0;
+  s.tlo = ((unsigned)((t + 1) & 0x7f) << 8) | ((unsigned)((t + 2) & 0x7f) << 16) | ((unsigned)((t + 3) & 0x7f) << 24);
+  s.thi = (unsigned)((t + 4) & 0x7f) | ((unsigned)((t + 5) & 0x7f) << 8) | ((unsigned)((t + 6) & 0x7f) << 16) | ((unsigned)((t + 7) & 0x7f) << 24);
+}
+__device__ __forceinline__ rw_u32x4 x12_decode(const X12W& w, const X12Row& s) {
+  const unsigned n = w.nib;
+  const unsigned c0 = n & 0x07070707u, c1 = (n >> 4) & 0x07070707u;
+  unsigned h0 = __builtin_amdgcn_perm(s.thi, s.tlo, c0), h1 = __builtin_amdgcn_perm(s.thi, s.tlo, c1);
+  h0 |= (n & 0x08080808u) << 4;
+  h1 |= n & 0x80808080u;
+  rw_u32x4 r;
+  r.x = __builtin_amdgcn_perm(h0, w.lo.x, 0x05010400u);
+  r.y = __builtin_amdgcn_perm(h0, w.lo.x, 0x07030602u);
+  r.z = __builtin_amdgcn_perm(h1, w.lo.y, 0x05010400u);
+  r.w = __builtin_amdgcn_perm(h1, w.lo.y, 0x07030602u);
+  return r;
+}
+__device__ __forceinline__ void x12_apply(rw_u32x4& w, unsigned e, int lane) {
+  const unsigned k = e >> 16, i = k & 7u, sh = (i & 1u) * 16u;
+  const unsigned keep = ~(0xffffu << sh), ins = (e & 0xffffu) << sh;
+  const bool mine = lane == (int)((k >> 3) & 63u);
+  w.x = (mine && (i >> 1) == 0u) ? ((w.x & keep) | ins) : w.x;
+  w.y = (mine && (i >> 1) == 1u) ? ((w.y & keep) | ins) : w.y;
+  w.z = (mine && (i >> 1) == 2u) ? ((w.z & keep) | ins) : w.z;
+  w.w = (mine && (i >> 1) == 3u) ? ((w.w & keep) | ins) : w.w;
+}
+// A group of G consecutive chunks of one row, chunk0 first, decoded into the 16-bit kernel's registers.  Straight-line but for one
+// wave-uniform test: does the row's next patch lie in this group?  Rarely: then the patches of the group go over the decoded registers in k
+// order and the cursor moves on (groups come in rising chunk order).  A chunk at or beyond nch reads weights 0..7 of the row in EVERY lane
+// against zeros of x, as the 16-bit kernel's clamped address does (long-K form, last pass): every lane takes the patches at k < 8.
+template <int G>
+__device__ __forceinline__ void x12_group(rw_u32x4 (&wd)[G], const X12W* w, X12Row& s, int chunk0, int nch, int lane) {
+#pragma unroll
+  for (int i = 0; i < G; ++i) wd[i] = x12_decode(w[i], s);
+  while (s.pi < s.cnt) {
+    const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)s.pv, s.pi);
+    const int ch = (int)(e >> 25) - chunk0;
+    if (ch >= G) break;
+#pragma unroll
+    for (int i = 0; i < G; ++i) if (ch == i) x12_apply(wd[i], e, lane);
+    ++s.pi;
+  }
+  if (chunk0 + G > nch) {
+    for (int j = 0; j < s.cnt; ++j) {
+      const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)s.pv, j);
+      if ((e >> 19) != 0u) break;      // k >= 8
+#pragma unroll
+      for (int i = 0; i < G; ++i) if (chunk0 + i >= nch) x12_apply(wd[i], e, 0);
+    }
+  }
+}
+
 template <typename T, int WF>
 __device__ __forceinline__ typename RwW<WF>::type rw_ldw(const GemvP& p, size_t row, int k) {
+  if constexpr (WF == WF_X12) return x12_ldw(p, row, k >> 9, (k >> 3) & 63); else
   if constexpr (WF == WF_E4M3) {
     return __builtin_nontemporal_load(reinterpret_cast<const rw_u32x2*>((const unsigned char*)p.W + row * p.ldw + k));
   } else if constexpr (WF == WF_MX4) {
@@ -1023,7 +1116,8 @@ __device__ __forceinline__ void gemv_rows_norm_body(const GemvP& p) {
     for (int c = 0; c < NCH; ++c) {
       int k = c * 512 + lane * 8;
       k = k < p.K ? k : 0;                      // ragged last chunk: clamp (x is zero there)
-      w[r][c] = rw_ldw<T, F8>(p, (size_t)rows[r], k);
+      if constexpr (F8 == WF_X12) w[r][c] = x12_ldw(p, (size_t)rows[r], c, lane);      // (K = 512 NCH: no ragged chunk)
+      else w[r][c] = rw_ldw<T, F8>(p, (size_t)rows[r], k);
     }
   // the epilogue's operands (bias, e4m3 row scales) are requested right BEHIND the weight rows: they come back with them instead of costing a
   // dependent L2 round trip after the reduction.  (In FRONT of the weights they measured slower: a cold 2-byte load at the head of the
@@ -1047,6 +1141,11 @@ __device__ __forceinline__ void gemv_rows_norm_body(const GemvP& p) {
 #pragma unroll
       for (int r = 0; r < R; ++r) e_scale[r] = p.w_scale[rows[r]];
     }
+  }
+  X12Row xst[F8 == WF_X12 ? R : 1];      // bf16x12: each row's top, patch count and patches, behind its weights like the operands above
+  if constexpr (F8 == WF_X12) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) x12_row_load(xst[r], p, (size_t)rows[r], lane);
   }
   // ---- 2. the norm, shared by the workgroup: wave w normalises chunks w, w + WAVES, ... (x and the norm weights are read ONCE per
   // workgroup: 2 x 7 KB instead of 7 KB of xn per wave), the normalised row goes to LDS, every wave reads it back.  The plain loads above
@@ -1093,9 +1192,25 @@ __device__ __forceinline__ void gemv_rows_norm_body(const GemvP& p) {
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     float a = 0.f;
+    if constexpr (F8 == WF_X12) x12_row_finish(xst[r]);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      a = rw_dotw<T, F8>(w[r][c], xr[c], a);
+      if constexpr (F8 != WF_X12) a = rw_dotw<T, F8>(w[r][c], xr[c], a);
+    }
+    if constexpr (F8 == WF_X12) {      // the same dot products in the same order on the decoded registers, in groups of up to four chunks
+      constexpr int G0 = NCH < 4 ? NCH : 4, G1 = NCH - G0;
+      {
+        rw_u32x4 wd[G0];
+        x12_group<G0>(wd, &w[r][0], xst[r], 0, NCH, lane);
+#pragma unroll
+        for (int c = 0; c < G0; ++c) a = rw_dot8<T>(wd[c], xr[c], a);
+      }
+      if constexpr (G1 > 0) {
+        rw_u32x4 wd[G1];
+        x12_group<G1>(wd, &w[r][G0], xst[r], G0, NCH, lane);
+#pragma unroll
+        for (int c = 0; c < G1; ++c) a = rw_dot8<T>(wd[c], xr[G0 + c], a);
+      }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
@@ -1125,6 +1240,9 @@ template <typename T, int EPI, int RR, int NCH, bool F8, int WAVES = 4>
 __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_kernel(GemvP p) { gemv_rows_norm_body<T, EPI, RR, NCH, F8 ? WF_E4M3 : WF_16, WAVES>(p); }
 template <typename T, int EPI, int RR, int NCH, int WAVES = 4>
 __global__ __launch_bounds__(WAVES * 64) void gemv_rows_norm_mx4_kernel(GemvP p) { gemv_rows_norm_body<T, EPI, RR, NCH, WF_MX4, WAVES>(p); }
+// bf16x12 rows: the batch-1 step's gate|up (EPI_SWIGLU, one pair per wave) and lm_head (EPI_NONE, four rows per wave) launches
+template <typename T, int EPI, int RR, int NCH>
+__global__ __launch_bounds__(256) void gemv_rows_norm_x12_kernel(GemvP p) { gemv_rows_norm_body<T, EPI, RR, NCH, WF_X12, 4>(p); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Loop form of gemv_rows_norm_kernel (round 3): ONE resident round of workgroups (2 per CU), each owning a contiguous range of outputs
@@ -1467,19 +1585,36 @@ __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_pe
     for (int c = 0; c < 8; ++c) {
       int k = (pass * 8 + c) * 512 + lane * 8;
       k = k < p.K ? k : 0;                      // beyond K: any valid address (x is zero there)
-      w[c] = rw_ldw<T, F8>(p, (size_t)row, k);
+      if constexpr (F8 == WF_X12) w[c] = x12_ldw(p, (size_t)row, pass * 8 + c < nch ? pass * 8 + c : 0, pass * 8 + c < nch ? lane : 0);
+      else w[c] = rw_ldw<T, F8>(p, (size_t)row, k);
     }
   };
   float acc = 0.f;
+  X12Row xst;
   auto dots = [&](wreg_t (&w)[8], int pass) {
+    if constexpr (F8 == WF_X12) {      // the 16-bit kernel's dot products in its order, on registers decoded G chunks at a time
+      constexpr int G = 2;      // chunks per group (no group size fits the 128 VGPRs at which two workgroups share a CU without spilling: LOG.md)
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * 8 + c) * 512 + lane * 8);
-      acc = rw_dotw<T, F8>(w[c], xr, acc);
+      for (int h = 0; h < 8 / G; ++h) {
+        rw_u32x4 wd[G];
+        x12_group<G>(wd, &w[G * h], xst, pass * 8 + G * h, nch, lane);
+#pragma unroll
+        for (int c = 0; c < G; ++c) {
+          const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * 8 + G * h + c) * 512 + lane * 8);
+          acc = rw_dot8<T>(wd[c], xr, acc);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * 8 + c) * 512 + lane * 8);
+        acc = rw_dotw<T, F8>(w[c], xr, acc);
+      }
     }
   };
   wreg_t wa[8], wb[8], wc[8];
   load_w(wa, 0);
+  if constexpr (F8 == WF_X12) x12_row_load(xst, p, (size_t)row, lane);      // bf16x12: the row's top and patches right behind the first pass, which needs them
   if (npass > 1) load_w(wb, 1);
   if (npass > 2) load_w(wc, 2);      // all three buffers are on their way before x is staged (round 4: the third used to wait for the barrier below)
   // the epilogue's operands (bias, residual -- which may alias Y: only this wave writes element n --, the e4m3 row scale) right behind the first
@@ -1496,6 +1631,7 @@ __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_pe
     *reinterpret_cast<rw_u32x4*>(xs + i * 8) = v;
   }
   __syncthreads();
+  if constexpr (F8 == WF_X12) x12_row_finish(xst);
   // three register buffers: the weights of passes ps + 1 and ps + 2 are in flight under the dot products of pass ps (24 KB per wave)
   for (int ps = 0; ps < npass; ps += 3) {
     if (ps > 0 && ps + 2 < npass) load_w(wc, ps + 2);
@@ -1524,6 +1660,8 @@ template <typename T, bool F8>
 __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, F8 ? WF_E4M3 : WF_16>(p, rows_per_wg); }
 template <typename T>
 __global__ __launch_bounds__(512) void gemv_rows_longk_mx4_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_MX4>(p, rows_per_wg); }
+template <typename T>
+__global__ __launch_bounds__(512) void gemv_rows_longk_x12_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_X12>(p, rows_per_wg); }
 
 #if OMCHAT_EXPERIMENTS
 // The same rows WITHOUT the LDS stage (round 5, tuning key 39): a wave streams one row and uses every x element once, so the LDS copy only saves L2
@@ -1617,7 +1755,14 @@ int launch_rows_longk(const GemvP& p, hipStream_t s) {
   const int grid = cdiv(p.N, rpw);
   const int npass = (cdiv(p.K, 512) + 7) / 8;
   const size_t lds = (size_t)npass * 8 * 512 * 2;
-  if (p.mx_s) {
+  if (p.x12_top) {
+    if constexpr (std::is_same<T, bf16>::value) {
+      static PerDeviceOnce set;
+      auto k = gemv_rows_longk_x12_kernel<T>;
+      if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+      hipLaunchKernelGGL(k, dim3(grid), dim3(64 * rpw), lds, s, p, rpw);
+    }
+  } else if (p.mx_s) {
     static PerDeviceOnce set;
     auto k = gemv_rows_longk_mx4_kernel<T>;
     if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
@@ -1711,6 +1856,27 @@ void launch_rows_norm(const GemvP& p, hipStream_t s) {
   }
 }
 
+// bf16x12 rows in the default (non-loop) norm form, on the 16-bit launch's grid: gate|up one pair per wave, everything else four rows per wave
+template <int EPI, int NCH>
+void launch_rows_norm_x12_n(const GemvP& p, hipStream_t s) {
+  constexpr int RR = EPI == EPI_SWIGLU ? 1 : 4;
+  const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
+  hipLaunchKernelGGL((gemv_rows_norm_x12_kernel<bf16, EPI, RR, NCH>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
+}
+template <int EPI>
+void launch_rows_norm_x12(const GemvP& p, hipStream_t s) {
+  switch (p.K / 512) {
+    case 1: launch_rows_norm_x12_n<EPI, 1>(p, s); break;
+    case 2: launch_rows_norm_x12_n<EPI, 2>(p, s); break;
+    case 3: launch_rows_norm_x12_n<EPI, 3>(p, s); break;
+    case 4: launch_rows_norm_x12_n<EPI, 4>(p, s); break;
+    case 5: launch_rows_norm_x12_n<EPI, 5>(p, s); break;
+    case 6: launch_rows_norm_x12_n<EPI, 6>(p, s); break;
+    case 7: launch_rows_norm_x12_n<EPI, 7>(p, s); break;
+    default: launch_rows_norm_x12_n<EPI, 8>(p, s); break;
+  }
+}
+
 template <typename T, int EPI, int RR, int F8>
 void launch_rows_r(const GemvP& p, hipStream_t s) {
   const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
@@ -1775,7 +1941,7 @@ template <typename T>
 int launch_t(const GemvArgs& a, hipStream_t s) {
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
   GemvP p{a.X, a.W, a.Y, a.bias, a.resid, a.ldx, a.ldw, a.ldy, a.ldr, a.b, a.N, a.K, a.out_f32, ks, a.w_scale, a.y_packed, a.norm_w, a.norm_eps,
-          (unsigned*)a.dyn_ctr, a.y_pack, a.dbg, a.mx_scale};
+          (unsigned*)a.dyn_ctr, a.y_pack, a.dbg, a.mx_scale, a.x12_top, a.x12_cnt, a.x12_patch};
   if (a.norm_w && a.x_packed && !(a.w_packed && ks == 1 && (a.K >> 6) == 56 && a.epi == EPI_SWIGLU && a.N % 32 == 0 && !g_gemv_no_xs)) {
     omchat_set_error("launch_gemv: the in-register RMSNorm on packed x exists for the x-stationary gate|up form only (packed W, K = 3584, no split-K)");
     return 1;
@@ -1888,6 +2054,21 @@ int launch_t(const GemvArgs& a, hipStream_t s) {
     OM_LAUNCH_CHECK();
     return 0;
   }
+  if (a.x12_top) {      // bf16x12 rows: the three long launches of the batch-1 step, nothing else
+    const bool ok = std::is_same<T, bf16>::value && a.b == 1 && !a.x_packed && !a.w_packed && ks == 1 && a.K >= 512 && a.K % 512 == 0 &&
+                    a.ldw == a.K / 2 * 3 && a.x12_cnt && a.x12_patch && !a.w_scale && !a.mx_scale && !a.force_mfma && !g_gemv_force_mfma;
+    const bool norm = ok && a.norm_w && (a.epi == EPI_SWIGLU || a.epi == EPI_NONE) && a.K <= RW_MAXC * 512;
+    const bool longk = ok && !a.norm_w && a.epi == EPI_RESID && !a.out_f32 && a.K > RW_MAXC * 512 && a.K <= 32768;
+    if (!norm && !longk) {
+      omchat_set_error("launch_gemv: bf16x12 weights: bf16, b == 1, K % 512 == 0, and norm_w with EPI_SWIGLU / EPI_NONE (K <= 4096) or EPI_RESID on 4096 < K <= 32768");
+      return 1;
+    }
+    if (longk) { const int rc = launch_rows_longk<T>(p, s); if (rc) return rc; }
+    else if (a.epi == EPI_SWIGLU) launch_rows_norm_x12<EPI_SWIGLU>(p, s);
+    else launch_rows_norm_x12<EPI_NONE>(p, s);
+    OM_LAUNCH_CHECK();
+    return 0;
+  }
   if (a.b == 1 && !a.x_packed && a.epi == EPI_RESID && ks == 1 && !a.out_f32 && a.K > RW_MAXC * 512 && a.K % 8 == 0 && a.K <= 32768 &&
       ((!a.force_mfma && !g_gemv_force_mfma) || a.mx_scale)) {
     const int rc = launch_rows_longk<T>(p, s);      // long K in one piece: x through LDS, the result complete when the launch ends
@@ -1952,6 +2133,9 @@ void gemv_set_dyn(int v) { g_gemv_dyn = v; }
 void gemv_set_longk_direct(int v) { g_gemv_longk_direct = v; }
 void gemv_set_skew(int v) { g_gemv_skew = (unsigned)v; }
 void gemv_set_rows_balance(int v) { g_gemv_rows_balance = v; }
+int gemv_x12_default_forms() {
+  return ((g_gemv_norm_loop & 1) == 0 && g_gemv_gu_rr == 1 && g_gemv_skew == 0u ? 1 : 0) | (g_gemv_longk_direct == 0 ? 2 : 0) | ((g_gemv_norm_loop & 8) == 0 ? 4 : 0);
+}
 
 namespace {
 // one wave per row: absmax, then e4m3 (round to nearest even) of w / scale, 8 weights per lane per step
@@ -2041,6 +2225,84 @@ int launch_quant_mxfp4_rows(int dtype, const void* W, int ldw, int N, int K, voi
   if (dtype == OMCHAT_F16) hipLaunchKernelGGL(quant_mxfp4_rows_kernel<f16>, dim3(cdiv(N, 4)), dim3(256), 0, s, (const f16*)W, ldw, N, K, (unsigned char*)W4, ld4, S);
   else if (dtype == OMCHAT_BF16) hipLaunchKernelGGL(quant_mxfp4_rows_kernel<bf16>, dim3(cdiv(N, 4)), dim3(256), 0, s, (const bf16*)W, ldw, N, K, (unsigned char*)W4, ld4, S);
   else { omchat_set_error("launch_quant_mxfp4_rows: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+namespace {
+// bf16x12 encoder (kernels.h: launch_encode_bf16x12; tests/bf16x12_ref.py is the definition).  One workgroup of one wave per row: the
+// row's top, then per chunk of 512 the lane's 8 low bytes and its nibble word; the misses of a chunk (rare) take their slots of the patch
+// list in k order through a scan over the lanes.
+__global__ __launch_bounds__(64) void encode_bf16x12_kernel(const unsigned short* __restrict__ W, int ldw, int N, int K, unsigned char* __restrict__ coded,
+                                                            unsigned char* __restrict__ top, unsigned char* __restrict__ cnt, unsigned* __restrict__ patch,
+                                                            int* __restrict__ over) {
+  const int lane = threadIdx.x, n = blockIdx.x;
+  const unsigned short* w = W + (size_t)n * ldw;
+  int t = 0;
+  for (int k = lane * 8; k < K; k += 512) {
+    const rw_u32x4 v = *reinterpret_cast<const rw_u32x4*>(w + k);
+    const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = (int)((u[i >> 1] >> (16 * (i & 1) + 7)) & 0xffu);
+      if (e != 0xff) t = max(t, e >> 1);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t = max(t, __shfl_xor(t, o, 64));
+  unsigned char* row = coded + (size_t)n * (size_t)(K / 512) * 768;
+  int total = 0;
+  for (int c = 0; c < K / 512; ++c) {
+    const int k0 = c * 512 + lane * 8;
+    const rw_u32x4 v = *reinterpret_cast<const rw_u32x4*>(w + k0);
+    const unsigned u[4] = {v.x, v.y, v.z, v.w};
+    unsigned lo0 = 0, lo1 = 0, nib = 0, mm = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const unsigned h = (u[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+      const int e = (int)((h >> 7) & 0xffu), e71 = e >> 1, cc = e71 - (t - 7);
+      const bool hit = e != 0xff && (e71 == 0 || cc >= 1);
+      const unsigned code = e71 == 0 ? 0u : (unsigned)cc;
+      if (hit) {
+        if (i < 4) lo0 |= (h & 0xffu) << (8 * i); else lo1 |= (h & 0xffu) << (8 * (i - 4));
+        nib |= (((h >> 15) << 3) | code) << (8 * (i & 3) + 4 * (i >> 2));
+      } else {
+        mm |= 1u << i;
+      }
+    }
+    const rw_u32x2 lo = {lo0, lo1};
+    *reinterpret_cast<rw_u32x2*>(row + (size_t)c * 768 + lane * 8) = lo;
+    *reinterpret_cast<unsigned*>(row + (size_t)c * 768 + 512 + lane * 4) = nib;
+    if (__ballot(mm != 0u)) {
+      const int pc = __popc(mm);
+      int inc = pc;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(inc, o, 64); if (lane >= o) inc += y; }
+      int off = total + inc - pc;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if ((mm >> i) & 1u) {
+          const unsigned h = (u[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+          if (off < 32) patch[(size_t)n * 32 + off] = ((unsigned)(k0 + i) << 16) | h;
+          ++off;
+        }
+      }
+      total += __shfl(inc, 63, 64);
+    }
+  }
+  if (lane < 32 && lane >= total) patch[(size_t)n * 32 + lane] = 0u;      // the unused slots read zero
+  if (lane == 0) {
+    top[n] = (unsigned char)t;
+    cnt[n] = (unsigned char)(total > 32 ? 33 : total);
+    if (total > 32) *over = 1;
+  }
+}
+}  // namespace
+
+int launch_encode_bf16x12(const void* W, int ldw, int N, int K, void* coded, unsigned char* top, unsigned char* cnt, unsigned* patch, int* over, hipStream_t s) {
+  OM_CHECK(W && coded && top && cnt && patch && over, "null argument");
+  OM_CHECK(N >= 1 && K >= 512 && K % 512 == 0 && K < 65536 && ldw % 8 == 0 && ldw >= K, "bf16x12: K a multiple of 512 below 65536, ldw % 8 == 0");
+  hipLaunchKernelGGL(encode_bf16x12_kernel, dim3(N), dim3(64), 0, s, (const unsigned short*)W, ldw, N, K, (unsigned char*)coded, top, cnt, patch, over);
   OM_LAUNCH_CHECK();
   return 0;
 }

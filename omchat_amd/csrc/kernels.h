@@ -118,7 +118,18 @@ struct GemvArgs {
   // With x_packed && w_packed (1 <= b <= 32, K % 64 == 0, N % 16 == 0): W / mx_scale are the PACKED MXFP4 replica that launch_pack_w4 writes
   // (common.h: packed_w4_index / packed_s4_index; ldw ignored) and the packed batched forms run on it; epilogues NONE / SWIGLU / PARTIAL
   const unsigned char* mx_scale = nullptr;
+  // non-null: W is the bf16x12 coding of a bf16 [N][K] matrix (launch_encode_bf16x12: rows of ldw = K * 3 / 2 bytes) with x12_top [N],
+  // x12_cnt [N] (every count <= 32) and x12_patch [N][32]; the launch gives the bits of the same launch on the 16-bit matrix.  bf16, b == 1,
+  // K % 512 == 0, and one of the three long batch-1 forms: norm_w with EPI_SWIGLU / EPI_NONE (K <= 4096), or EPI_RESID without split-K
+  // on 4096 < K <= 32768
+  const unsigned char* x12_top = nullptr;
+  const unsigned char* x12_cnt = nullptr;
+  const unsigned* x12_patch = nullptr;
 };
+// bf16x12 (tests/bf16x12_ref.py is the definition): W bf16 [N][ldw] -> coded [N][K * 3 / 2] bytes, top [N], cnt [N] (min(misses, 33)),
+// patch [N][32] (k << 16 | bits, sorted by k); *over (device, zeroed by the caller) is set to 1 when a row needs more than 32 patches.  K % 512 == 0
+int launch_encode_bf16x12(const void* W, int ldw, int N, int K, void* coded, unsigned char* top, unsigned char* cnt, unsigned* patch, int* over,
+                          hipStream_t stream);
 // row-major [rows <= 32][K] -> packed x (tests, tools); row-major W [N][ldw] -> packed replica (N % 16 == 0)
 int launch_pack_x(int dtype, const void* X, int ldx, int b, int K, void* out, hipStream_t s);
 int launch_pack_w(int dtype, const void* W, int ldw, int N, int K, void* out, hipStream_t s);
@@ -212,6 +223,8 @@ void attn_set_peel(int v);    // tuning key 46
 void attn_set_kv8_tpw(int v); // tuning key 47
 void attn_set_kv8_fuse(int v); // tuning key 48
 void model_set_extend_attn(int v); // tuning key 49
+void model_set_x12_roles(int v);   // tuning key 50
+int gemv_x12_default_forms();      // bit per bf16x12 role (1 gate|up, 2 down_proj, 4 lm_head) whose 16-bit launch is in its default form (no tuning key moved it)
 bool attn_decode_kv8_fuses_rope(int batch, int kv_heads, int L, bool masked);
 void attn_set_merge_mid_min(int v);
 void attn_set_merge_dg(int v);

@@ -397,6 +397,7 @@ extern "C" int omchat_load_tensor(omchat_ctx* ctx, const char* name, const void*
   }
   for (int f = 0; f < OMCHAT_WFMT_COUNT; ++f)      // no replica matches the 16-bit weights any more (the 16-bit entry is a view of them)
     if (f != OMCHAT_WFMT_16 && ctx->built(f)) ctx->wt[f].state = omchat_ctx::W_STALE;
+  for (auto& t : ctx->x12) if (t.state == omchat_ctx::W_BUILT) t.state = omchat_ctx::W_STALE;      // ... nor does a bf16x12 coding
   if (src_dtype == ctx->dt) return place(ctx, r, data);
   OM_CHECK(src_dtype == OMCHAT_F32, "source dtype must be the context dtype or OMCHAT_F32");
   TRY(ensure_stage(ctx, (size_t)n * 4, (size_t)n * 2));
@@ -998,6 +999,65 @@ static int build_replica(omchat_ctx* ctx, int fmt) {
   return 0;
 }
 
+// omchat_op_set_tuning key 50: the roles of a batch-1 step that stream the bf16x12 coding of their bf16 rows: bit 0 = gate|up, bit 1 =
+// down_proj, bit 2 = lm_head; 0 = the 16-bit launches exactly (A/B: the same bits either way).  The default is what tools/bench_bf16x12.py measured:
+// gate|up 41.1 -> 33.7 us and lm_head 160.3 -> 126.0 us are on; the long-K down_proj form measured 23.3 -> 28.1 us (its three register buffers
+// plus the decoded registers take 136 VGPRs, over the 128 of two workgroups per CU) and stays on 16 bits (LOG.md)
+int g_x12_roles = 5;
+void model_set_x12_roles(int v) { g_x12_roles = v & 7; }
+
+// The roles a step of `rows` rows would stream coded, by everything but the state of the copies: the step's format is 16-bit at b == 1 on one
+// GPU in bf16, and the role's 16-bit launch is in its default form
+static int x12_step_mask(const omchat_ctx* ctx, int rows, int fmt) {
+  if (rows != 1 || fmt != OMCHAT_WFMT_16 || ctx->dt != OMCHAT_BF16 || ctx->tp_size != 1) return 0;
+  return g_x12_roles & gemv_x12_default_forms();
+}
+
+// (Re)build the bf16x12 coding of one role (ctx.h): every buffer of the role or none; an allocation that fails or a K outside the forms leaves
+// the role on 16 bits for good.  A rebuild after omchat_load_tensor encodes into the same buffers (a captured graph stays valid); if that
+// moves a tensor over or under the patch cap, the launch it needs is another one and the captured graphs are dropped.
+static int build_x12(omchat_ctx* ctx, int role) {
+  omchat_ctx::X12Table& T = ctx->x12[role];
+  if (T.state == omchat_ctx::W_BUILT || T.state == omchat_ctx::W_UNAVAILABLE) return 0;
+  const omchat_config& c = ctx->c;
+  const int H = c.t_hidden, It = c.t_mlp, L = c.t_layers;
+  const bool lm = role == omchat_ctx::X12_LM, down = role == omchat_ctx::X12_DOWN;
+  const size_t N = lm ? c.t_vocab : down ? H : 2 * (size_t)It, K = down ? It : H, n = lm ? 1 : L;
+  const bool k_ok = K % 512 == 0 && (down ? (K > 4096 && K <= 32768) : K <= 4096);
+  if (!k_ok || omchat_weights_missing(ctx) != 0) { if (!k_ok) T.state = omchat_ctx::W_UNAVAILABLE; return 0; }
+  if (T.e.empty()) {
+    std::vector<omchat_ctx::X12Ref> fresh(n);
+    std::vector<void**> slots;
+    std::vector<size_t> sizes;
+    for (auto& r : fresh) {
+      slots.push_back(&r.W); sizes.push_back(N * (K / 2 * 3));
+      slots.push_back((void**)&r.top); sizes.push_back(N);
+      slots.push_back((void**)&r.cnt); sizes.push_back(N);
+      slots.push_back((void**)&r.patch); sizes.push_back(N * 32 * 4);
+    }
+    int* over = nullptr;
+    if (!ctx->x12_over) { slots.push_back((void**)&over); sizes.push_back((size_t)std::max(L, 1) * 4); }
+    if (ctx->alloc_group(slots, sizes)) { T.state = omchat_ctx::W_UNAVAILABLE; return 0; }      // stays 16-bit; nothing is retried
+    if (over) ctx->x12_over = over;
+    T.e.swap(fresh);
+  }
+  OM_HIP(hipDeviceSynchronize());      // as build_replica: whatever still writes the 16-bit weights, on any stream, is done before they are read
+  OM_HIP(hipMemset(ctx->x12_over, 0, n * 4));
+  for (size_t j = 0; j < n; ++j) {
+    const void* W = lm ? ctx->lm_w(OMCHAT_WFMT_16).W : ctx->layer_w(OMCHAT_WFMT_16, (int)j)[down ? omchat_ctx::P_DOWN : omchat_ctx::P_GU].W;
+    const omchat_ctx::X12Ref& r = T.e[j];
+    TRY(launch_encode_bf16x12(W, (int)K, (int)N, (int)K, r.W, r.top, r.cnt, r.patch, ctx->x12_over + j, nullptr));
+  }
+  OM_HIP(hipDeviceSynchronize());      // (never inside a graph capture)
+  std::vector<int> over(n);
+  OM_HIP(hipMemcpy(over.data(), ctx->x12_over, n * 4, hipMemcpyDeviceToHost));
+  bool moved = false;
+  for (size_t j = 0; j < n; ++j) { moved = moved || (T.state == omchat_ctx::W_STALE && T.e[j].ok != !over[j]); T.e[j].ok = !over[j]; }
+  if (moved) drop_decode_graphs(ctx);
+  T.state = omchat_ctx::W_BUILT;
+  return 0;
+}
+
 extern "C" int omchat_enable_fp8_decode(omchat_ctx* ctx, int on) {
   OM_CHECK(ctx, "null context");
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
@@ -1294,6 +1354,8 @@ static int step_weights_ready(omchat_ctx* ctx, int rows) {
     TRY(build_replica(ctx, OMCHAT_WFMT_16_PACKED));
   if (ctx->fp8_decode) TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));
   if (ctx->mxfp4_mode) TRY(build_replica(ctx, ctx->mxfp4_mode == 2 ? OMCHAT_WFMT_MXFP4_PACKED : OMCHAT_WFMT_MXFP4));
+  const int x12m = x12_step_mask(ctx, rows, step_format(ctx, rows));      // built by the first batch-1 step that will use it
+  for (int role = 0; role < omchat_ctx::X12_ROLES; ++role) if (x12m >> role & 1) TRY(build_x12(ctx, role));
   return 0;
 }
 
@@ -1384,6 +1446,13 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   // packed raw copy), and the post-attention RMSNorm runs in the registers of the gate|up GEMV: seven launches per layer instead of eight
   const bool nb2 = OMCHAT_EXPERIMENTS && (g_norm_in_gemv & 4) && fused && wpk && ctx->tp_size == 1 && !wq && (qd >> 6) == 56 && (H >> 6) == 56 && qd % 64 == 0 &&
                    H / 16 <= device_cus() && (2 * It) / 32 >= 4 * device_cus();
+  // bf16x12 (tuning key 50): the three long launches of the six-launch layer stream the 12-bit coding of their rows where it is built and the
+  // tensor is coded -- the same bits as the 16-bit launch, three quarters of the bytes
+  const int x12m = n1 ? x12_step_mask(ctx, b, fmt) : 0;
+  auto x12_of = [&](int role, size_t j) -> const omchat_ctx::X12Ref* {
+    const omchat_ctx::X12Table& T = ctx->x12[role];
+    return ((x12m >> role) & 1) && T.state == omchat_ctx::W_BUILT && T.e[j].ok ? &T.e[j] : nullptr;
+  };
   if (fused && !n1) TRY(launch_rmsnorm(ctx->dt, x, H, ctx->dl[0].ln1, ctx->tw_xn, H, b, H, c.t_eps, s, pk));
 #if OMCHAT_EXPERIMENTS
   if ((g_ao_oproj & 16) && ctx->dbg_stamps) OM_HIP(hipMemsetAsync(ctx->dbg_stamps, 0, (size_t)c.t_layers * 256, s));      // measurement: the stamps of THIS step only
@@ -1530,6 +1599,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     if (n2) {
       GemvArgs g = gemv_args(x, H, W[GU], H, ctx->tw_act, It, 1, 2 * It, nullptr, nullptr, EPI_SWIGLU, 0, false);
       g.norm_w = L.ln2; g.norm_eps = c.t_eps;
+      if (const auto* r = x12_of(omchat_ctx::X12_GU, i)) { use_weight_x12(g, *r, H); ++ctx->x12_launches[omchat_ctx::X12_GU]; }
       if (ctx->dyn_ctr && !ctx->graph_on) g.dyn_ctr = ctx->dyn_ctr + (size_t)i * 65 * 64;
       if (OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps) g.dbg = ctx->dbg_stamps + (size_t)i * 32;
       TRY(launch_gemv(ctx->dt, g, s));
@@ -1544,6 +1614,11 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     if (n1 && OMCHAT_EXPERIMENTS && (g_ao_oproj & 16) && ctx->dbg_stamps && !wq) {
       GemvArgs g = gemv_args(ctx->tw_act, It, W16[DOWN], It, x, H, 1, H, nullptr, x, EPI_RESID, 0, false);
       g.dbg = ctx->dbg_stamps + (size_t)i * 32;
+      TRY(launch_gemv(ctx->dt, g, s));
+    } else if (n1 && x12_of(omchat_ctx::X12_DOWN, i)) {
+      GemvArgs g = gemv_args(ctx->tw_act, It, W[DOWN], It, x, H, 1, H, nullptr, x, EPI_RESID, 0, false);
+      use_weight_x12(g, *x12_of(omchat_ctx::X12_DOWN, i), It);
+      ++ctx->x12_launches[omchat_ctx::X12_DOWN];
       TRY(launch_gemv(ctx->dt, g, s));
     } else if (n1) {
       TRY(gemv(ctx->tw_act, It, W[DOWN], It, x, H, H, nullptr, x, EPI_RESID));
@@ -1564,6 +1639,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   if (n1) {
     GemvArgs g{x, H, nullptr, 0, lg, c.t_vocab, 1, c.t_vocab, H, nullptr, nullptr, 0, EPI_NONE, 1};
     use_weight(g, ctx->lm_w(fmt));
+    if (const auto* r = x12_of(omchat_ctx::X12_LM, 0)) { use_weight_x12(g, *r, H); ++ctx->x12_launches[omchat_ctx::X12_LM]; }
     g.norm_w = ctx->t_norm; g.norm_eps = c.t_eps;
     TRY(launch_gemv(ctx->dt, g, s));
   } else {
@@ -1603,6 +1679,20 @@ extern "C" int omchat_enable_decode_graph(omchat_ctx* ctx, int on) {
     TRY(ctx->alloc((void**)&ctx->d_tok_out, (size_t)ctx->c.max_batch * 4));
   }
   ctx->graph_on = on != 0;
+  return 0;
+}
+
+// bf16x12, for tests and tools: the roles tuning key 50 selects at the moment, and per role (gate|up, down_proj, lm_head)
+// the coded launches enqueued so far by eager steps and graph captures and the number of its tensors that are coded (built and under the patch cap)
+extern "C" int omchat_bf16x12_stats(omchat_ctx* ctx, int* roles, long* launches, int* coded) {
+  OM_CHECK(ctx, "null context");
+  if (roles) *roles = g_x12_roles;
+  for (int r = 0; r < omchat_ctx::X12_ROLES; ++r) {
+    if (launches) launches[r] = ctx->x12_launches[r];
+    int n = 0;
+    if (ctx->x12[r].state == omchat_ctx::W_BUILT) for (const auto& e : ctx->x12[r].e) n += e.ok ? 1 : 0;
+    if (coded) coded[r] = n;
+  }
   return 0;
 }
 
@@ -1653,7 +1743,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   } else {
     const int fmt = step_format(ctx, b);
     omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (is_mxfp4(fmt) ? 4 : 0) + (fmt == OMCHAT_WFMT_E4M3 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0) +
-                                             (grp ? (1 << 20) : 0)];
+                                             (grp ? (1 << 20) : 0) + (x12_step_mask(ctx, b, fmt) << 21)];      // (+ the bf16x12 roles of tuning key 50: switching captures again)
     hipStream_t gs = ctx->graph_stream;
     OM_HIP(hipEventRecord(ctx->graph_ev_in, s));
     OM_HIP(hipStreamWaitEvent(gs, ctx->graph_ev_in, 0));

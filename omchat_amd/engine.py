@@ -217,6 +217,13 @@ class Engine:
         check(self.lib.omchat_decode_graph_stats(self.h, C.byref(st), C.byref(rp), C.byref(cp)))
         return dict(steps=st.value, replays=rp.value, captures=cp.value)
 
+    def bf16x12_stats(self):
+        """bf16x12 rows of the batch-1 step: the roles in use (tuning key 50), and per role (gate|up, down_proj, lm_head)
+        the coded launches enqueued so far and the tensors that are coded"""
+        roles, launches, coded = C.c_int(0), (C.c_long * 3)(), (C.c_int * 3)()
+        check(self.lib.omchat_bf16x12_stats(self.h, C.byref(roles), launches, coded))
+        return dict(roles=roles.value, launches=list(launches), coded=list(coded))
+
     def prof_enable(self, on=True):
         check(self.lib.omchat_prof_enable(self.h, int(on)))
 

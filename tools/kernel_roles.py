@@ -7,7 +7,8 @@ Patterns are substrings of the MANGLED symbol (what rocprofv3 --pmc reports in K
 the template argument list) and the run of `Li<n>E` / `Lb<n>E` integer / bool arguments that selects the instantiation."""
 
 # kernel families, longest / most specific first (a dispatch belongs to the first family whose name occurs in its symbol)
-FAMILIES = ("gemm8p_kernel", "gemm8_kernel", "gemm_kernel", "gemv_rows_norm_loop_kernel", "gemv_rows_norm_kernel", "gemv_rows_longk_kernel",
+FAMILIES = ("gemm8p_kernel", "gemm8_kernel", "gemm_kernel", "gemv_rows_norm_loop_kernel", "gemv_rows_norm_x12_kernel", "gemv_rows_norm_kernel",
+            "gemv_rows_longk_x12_kernel", "gemv_rows_longk_kernel",
             "gemv_rows_kernel", "gemv_xs_split_kernel", "gemv_xs_kernel", "gemv_pk_kernel", "gemv_xs_split_mx4_kernel", "gemv_xs_mx4_kernel",
             "gemv_pk_mx4_kernel", "gemv_kernel", "attn_decode_dma_kernel",
             "attn_decode_multi_kernel", "attn_decode_kv8_walk_kernel", "attn_decode_kernel", "attn_merge_mid_kernel", "attn_merge_kernel", "attn2_kernel", "attn_kernel", "vit_qknorm_kernel",
@@ -20,8 +21,12 @@ EPI_SWIGLU = 4
 
 def decode_gate_up_b1():
     """batch-1 decode gate|up launch (the bench line's dominant kernel): the default form first, then the forms behind tuning keys 38 / 16 / 14.
-    gemv_rows_norm_kernel<T, EPI, RR (pairs per wave), NCH (K chunks per lane: 3584 / 512), F8, WAVES>"""
-    return [["gemv_rows_norm_kernelI", f"Li{EPI_SWIGLU}ELi1ELi7ELb0E"],
+    gemv_rows_norm_x12_kernel<T, EPI, RR (pairs per wave), NCH (K chunks per lane: 3584 / 512)>: the bf16x12 rows, 204 MB
+    per launch -- no PMC pass of it is committed yet, so `roofline.traffic` reads null; the 16-bit one-pair-per-wave form it replaced
+    (gemv_rows_norm_kernel<.., 1, 7, false>, 271.9 MB per launch in the r06 counters, now behind tuning key 50 = 0) is NOT a fallback here: its
+    counters must not be attached to a launch that moves three quarters of its bytes.
+    gemv_rows_norm_kernel<T, EPI, RR, NCH, F8, WAVES>"""
+    return [["gemv_rows_norm_x12_kernelI", f"Li{EPI_SWIGLU}ELi1ELi7E"],
             ["gemv_rows_norm_loop_kernelI", f"Li{EPI_SWIGLU}ELi7ELb0E"],
             ["gemv_rows_norm_kernelI", f"Li{EPI_SWIGLU}ELi3ELi7ELb0E"],
             ["gemv_rows_kernelI", f"Li{EPI_SWIGLU}ELi4ELi4E"]]

@@ -38,6 +38,9 @@ def kind_of(name):
             elif fam == "gemv_rows_norm_kernel":
                 m = re.search(r"gemv_rows_norm_kernelI[A-Za-z0-9_]+?Li(\d)E", name)
                 epi = int(m.group(1)) if m else None
+            elif fam == "gemv_rows_norm_x12_kernel":
+                m = re.search(r"gemv_rows_norm_x12_kernelI[A-Za-z0-9_]+?Li(\d)E", name)
+                epi = int(m.group(1)) if m else None
             elif fam == "attn2_kernel":
                 m = re.search(r"attn2_kernelI\w+?Li(\d)ELb(\d)E", name)
                 epi = int(m.group(2)) if m else None           # 1 = causal (decoder prefill), 0 = the ViT
@@ -97,6 +100,10 @@ def label(seq):
             out[i] = "decode gate|up GEMV (+RMSNorm)"
         elif f == "gemv_rows_longk_kernel":
             out[i] = "decode down_proj GEMV"
+        elif f == "gemv_rows_longk_x12_kernel":               # the bf16x12 rows: priced with the 12-bit bytes they move
+            out[i] = "decode down_proj GEMV (bf16x12 rows)"
+        elif f == "gemv_rows_norm_x12_kernel":
+            out[i] = "decode gate|up GEMV (+RMSNorm, bf16x12 rows)" if e == 4 else "lm_head GEMV (+final norm, bf16x12 rows)"
         elif f == "gemv_rows_norm_kernel":
             if e == 4:                                          # EPI_SWIGLU: the non-loop gate|up form (round 5 default)
                 out[i] = "decode gate|up GEMV (+RMSNorm)"
@@ -130,6 +137,8 @@ def work(tiles, text, gen):
         "decode qkv GEMV (+RMSNorm)": (B, qkvd * H * 2.0), "decode o_proj GEMV": (B, H * qd * 2.0), "decode gate|up GEMV (+RMSNorm)": (B, 2.0 * It * H * 2),
         "decode down_proj GEMV": (B, H * It * 2.0), "decode attention (split-KV)": (B, L * 2048.0), "decode attention merge": (B, None),
         "lm_head GEMV (+final norm)": (B, V * H * 2.0),
+        "decode gate|up GEMV (+RMSNorm, bf16x12 rows)": (B, 2.0 * It * H * 1.5), "decode down_proj GEMV (bf16x12 rows)": (B, H * It * 1.5),
+        "lm_head GEMV (+final norm, bf16x12 rows)": (B, V * H * 1.5),
     }
 
 
