@@ -146,6 +146,18 @@ int omchat_fused_status(omchat_ctx* ctx, long* launches, unsigned* timeout_bits)
 int omchat_has_experiments(void);
 /* lm_head on arbitrary hidden rows (Qwen2ForCausalLM.forward :462-465): hidden [n, t_hidden] -> fp32 [n, t_vocab] */
 int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float* logits, void* stream);
+/* Teacher-forced scoring (Qwen2ForCausalLM.forward's shifted cross-entropy, modeling_qwen2.py): hidden [rows, t_hidden]
+ * final-normed rows of b sequences of S slots each (what omchat_prefill's hidden_out holds), labels device int32 [rows], ALREADY SHIFTED
+ * (labels[i * S + t] is the token that follows slot t; -100 = not scored; the caller keeps every other label inside [0, t_vocab) -- the
+ * kernels stay in bounds and score a label outside it NaN).  logprob device fp32 [rows]: log_softmax(hidden[r] lm_head^T)[labels[r]] under
+ * the raw fp32 distribution of omchat_lm_head, 0 where the label is -100.  out device fp32 [2 + 2 b]: loss_sum = -sum of the scored rows'
+ * logprob, their count, then every sequence's sum of logprob and its count.  The [rows, t_vocab] logits are never stored: an MFMA GEMM on
+ * the 16-bit lm_head whose epilogue keeps per-row (max, sum exp) partials (8 bytes a row and 64 vocabulary columns of workspace, owned
+ * and grown by the context before anything is enqueued).  A pure function of `hidden`: cache, positions and pick state are untouched.
+ * Deterministic (fixed reduction orders).  Errors, each before any work: a tensor-parallel context (the lm_head is vocabulary-parallel and
+ * no exchange of the partials is built), missing weights, rows > max_prefill_rows, b * S != rows. */
+int omchat_score_hidden(omchat_ctx* ctx, const void* hidden, int rows, const int32_t* labels, int b, int S, float* logprob, float* out,
+                        void* stream);
 /* greedy pick (HF generate with do_sample=False: argmax of the last position, first index wins): logits fp32
  * [b, t_vocab] (rank-local slice under tensor parallelism; the (max, index) pairs are exchanged) -> int32 [b] */
 int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream);
@@ -729,6 +741,15 @@ int omchat_op_sample_verify(const float* logits, int T, int V, int ld, const int
 int omchat_op_token_logprob(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,
                             float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row, const int32_t* newly_seen,
                             const uint32_t* thr, float* raw_out, float* processed_out, void* stream);
+/* logprob[m] = log_softmax(A[m] W^T)[labels[m]] and lse[m] = logsumexp(A[m] W^T) over N columns WITHOUT storing the [M, N] products (DESIGN.md
+ * section 18): the MFMA GEMM with the EPI_LSE epilogue -- fp32 accumulators used raw, per-row (max, sum exp) pairs per 64-column slot, the
+ * label's accumulator -- then one wave per row folds the slots in a fixed order.  Contract of omchat_op_gemm: K % 64 == 0, N % 4 == 0,
+ * lda / ldw % 8 == 0, A / W 16-byte aligned.  labels device int32 [M]: -100 (logprob 0) or an id in [0, N); anything else is an error,
+ * checked on the host before the launch.  logprob device fp32 [M]; lse device fp32 [M] or NULL; ws: omchat_op_lse_label_ws(M, N) bytes,
+ * 16-byte aligned.  Two runs give the same bits.  Synchronises (the label check). */
+size_t omchat_op_lse_label_ws(int M, int N);
+int omchat_op_lse_label(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const int32_t* labels, float* logprob,
+                        float* lse, void* ws, size_t ws_bytes, void* stream);
 /* omchat_op_token_logprob over a kept interval: thr_lo / thr_hi device uint32 [b] or NULL (omchat_op_sample_filtered's; NULL = no bound on
  * that side).  An id outside the interval records -inf as its processed value. */
 int omchat_op_token_logprob_interval(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban, float temperature,

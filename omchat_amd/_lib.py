@@ -49,6 +49,7 @@ _SIGS = {
     "omchat_prefill_left": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "omchat_decode_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_lm_head": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "omchat_score_hidden": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_greedy": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_set_sampling": (_i, [_vp, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _vp]),
     "omchat_set_sampling_filters": (_i, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
@@ -154,6 +155,8 @@ _SIGS = {
     "omchat_op_layernorm_ld": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "omchat_op_sample": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_op_token_logprob": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "omchat_op_lse_label_ws": (_sz, [_i, _i]),
+    "omchat_op_lse_label": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "omchat_op_top_logprobs": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "omchat_op_sample_filtered": (_i, [_vp, _i, _i, _u64, _f, _i, C.c_double, _f, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _i,
                                        _vp, _vp, _vp, _vp]),

@@ -544,6 +544,20 @@ extern "C" int omchat_op_token_logprob(const float* logits, int b, int V, int ld
                           processed_out, stream);
 }
 
+extern "C" size_t omchat_op_lse_label_ws(int M, int N) { return M >= 1 && N >= 1 ? score_ws_bytes(M, N) : 0; }
+
+extern "C" int omchat_op_lse_label(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const int32_t* labels,
+                                   float* logprob, float* lse, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(A && W && labels && logprob && ws, "null argument");
+  OM_CHECK(M >= 1 && N >= 1 && K >= 1, "empty problem");
+  OM_CHECK(N % 4 == 0 && K % 64 == 0, "N must be a multiple of 4 and K a multiple of 64 (omchat_op_gemm's contract)");
+  std::vector<int32_t> h((size_t)M);
+  OM_HIP(hipMemcpyAsync(h.data(), labels, (size_t)M * 4, hipMemcpyDeviceToHost, S(stream)));
+  OM_HIP(hipStreamSynchronize(S(stream)));
+  for (int i = 0; i < M; ++i) OM_CHECK(h[i] == -100 || (h[i] >= 0 && h[i] < N), "label outside {-100} and [0, N)");
+  return launch_score(dtype, A, lda, W, ldw, M, N, K, labels, logprob, lse, ws, ws_bytes, S(stream));
+}
+
 extern "C" int omchat_op_token_logprob_interval(const float* logits, int b, int V, int ld, const int32_t* ids, const uint32_t* ban,
                                                 float temperature, float rep_penalty, const int32_t* seen_ids, const int32_t* n_seen_per_row,
                                                 const int32_t* newly_seen, const uint32_t* thr_lo, const uint32_t* thr_hi, float* raw_out,

@@ -96,6 +96,15 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// online log-sum-exp pairs (m = max, s = sum exp(x - m)) of teacher-forced scoring (gemm.hip EPI_LSE, score.hip): (m2, s2) joins (m, s).
+// The guarded combine of logprob.hip's lp_merge: an empty pair is (-inf, 0) and never reaches exp(-inf - -inf).  Symmetric in its two pairs
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) { s = 0.f; return; }
+  s = __fadd_rn(__fmul_rn(s, expf(m - M)), __fmul_rn(s2, expf(m2 - M)));
+  m = M;
+}
+
 // 16-byte global load / store of 8 16-bit elements
 template <typename T> __device__ __forceinline__ typename V8<T>::type ld8(const T* p) {
   return *reinterpret_cast<const typename V8<T>::type*>(p);

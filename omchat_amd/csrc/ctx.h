@@ -237,6 +237,7 @@ struct omchat_ctx {
   BeamState beam;
   GroupState group;
   Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
+  Grown score_ws;    // (max, sum) planes and target logits of teacher-forced scoring (omchat_score_hidden)
   int grow(Grown& g, size_t n) {
     if (n <= g.cap) return 0;
     if (g.p) { hipFree(g.p); bytes -= g.cap; g.p = nullptr; g.cap = 0; }

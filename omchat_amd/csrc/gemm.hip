@@ -37,6 +37,7 @@ struct GemmP {
   // computed once per tile into LDS after the K loop (no finishing launch between the producing GEMM and this one); slot-major: rs_stats[s * rs_ld + m]
   const float* rs_stats; int rs_ld, rs_nslots; float rs_inv_dim, rs_eps;
   int rs_dma;                                      // 1: the tile's slots are fetched by LDS-DMA BEFORE the K loop into the LDS behind the stage buffers
+  const int* lse_labels; float* lse_tgt;           // EPI_LSE: [M] labels, [M] the label's raw accumulator (stats = the (max, sum) planes); last: no other mode reads them
 };
 
 // Workgroup -> tile.  (1) bijective XCD remap: hardware deals consecutive workgroup ids round-robin over the 8 XCDs, so
@@ -141,6 +142,53 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[MR][N
 #pragma unroll
         for (int i = 0; i < MR; ++i)
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), frs, f_lane + (colu + j * 16) * 4 + i * 16 * p.ldc * 4, 0, 0);
+      }
+    }
+    return;
+  }
+  if constexpr (EPI == EPI_LSE) {
+    // Teacher-forced scoring: the wave tile's rows reduced over its valid columns to online (max, sum exp(x - max)) pairs of
+    // the raw accumulators -- the fp32 logits of omchat_lm_head, no bias, no rounding -- and the label's own accumulator; no logit is stored.
+    // A lane holds NR x 4 columns of a row per fragment row: lane first (columns ascending), then the four fg lanes of the row by two xor steps
+    // (fixed order, guarded: a lane whose columns all lie beyond N carries (-inf, 0)).  Lane fg == 0 writes the pair to the slot's two planes
+    // (slot-major as the statistics epilogues: 16 rows are one 64-byte run); the ONE lane that owns column label writes tgt[row]: a plain
+    // vector store with a single writer.  Columns >= N contribute neither a max nor an exp; a label outside [0, N) matches no valid column.
+    static_assert(NR == 4, "one slot per 64 columns (score_ws_bytes)");
+    if (colu >= p.N) return;                                                     // wave-uniform: no slot
+    const int slot = colu >> 6;
+    float* const pm = p.stats + (size_t)(2 * slot) * p.stats_ld;
+    float* const ps = pm + p.stats_ld;
+    const int col0 = colu + 4 * fg;
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+      const int row = rowu + i * 16 + fr;
+      const int lab = p.lse_labels[row < p.M ? row : p.M - 1];
+      float m = -INFINITY, t = 0.f;
+      bool hit = false;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        if (col0 + j * 16 < p.N) {                                               // the lane's four columns of a block are valid together (N % 4 == 0)
+          const int d = lab - (col0 + j * 16);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            m = fmaxf(m, acc[i][j][r]);
+            if (d == r) { t = acc[i][j][r]; hit = true; }
+          }
+        }
+      }
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        if (col0 + j * 16 < p.N) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s = __fadd_rn(s, expf(acc[i][j][r] - m));
+        }
+      }
+      lse_merge(m, s, __shfl_xor(m, 16), __shfl_xor(s, 16));
+      lse_merge(m, s, __shfl_xor(m, 32), __shfl_xor(s, 32));
+      if (row < p.M) {
+        if (fg == 0) { pm[row] = m; ps[row] = s; }
+        if (hit) p.lse_tgt[row] = t;
       }
     }
     return;
@@ -817,6 +865,7 @@ int launch_cfg8(const GemmArgs& a, hipStream_t stream) {
     OM_HIP(hipFuncSetAttribute((const void*)kern_sk, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
   }
   GemmP p{a.A, a.W, a.C, a.bias, a.ls, a.resid, a.lda, a.ldw, a.ldc, a.ldr, a.M, a.N, a.K, nullptr, nullptr, g_gemm_wide_store, g_gemm_skip_dead, a.row_scale, a.stats, a.stats_ld, a.rs_stats, a.rs_ld, a.rs_nslots, a.rs_dim > 0 ? 1.0f / (float)a.rs_dim : 0.f, a.rs_eps, 0};
+  p.lse_labels = a.lse_labels; p.lse_tgt = a.lse_tgt;
   const int tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
   if (a.stats_nslots) *a.stats_nslots = cdiv(a.N, 64);      // one slot per 64-column wave tile
   // row statistics through LDS-DMA when the tile's slots fit behind the stage buffers (160 KiB per workgroup): 29 slots x 256 rows = 29 KiB
@@ -873,6 +922,7 @@ int launch_cfg(const GemmArgs& a, hipStream_t stream) {
   constexpr int LDS_MAX = LDS + 32 * 1024 <= 160 * 1024 ? LDS + 32 * 1024 : 160 * 1024;
   if (attr_set.first()) OM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
   GemmP p{a.A, a.W, a.C, a.bias, a.ls, a.resid, a.lda, a.ldw, a.ldc, a.ldr, a.M, a.N, a.K, nullptr, nullptr, g_gemm_wide_store, g_gemm_skip_dead, a.row_scale, a.stats, a.stats_ld, a.rs_stats, a.rs_ld, a.rs_nslots, a.rs_dim > 0 ? 1.0f / (float)a.rs_dim : 0.f, a.rs_eps, 0};
+  p.lse_labels = a.lse_labels; p.lse_tgt = a.lse_tgt;
   const int grid = cdiv(a.M, BM) * cdiv(a.N, BN);
   if (a.stats_nslots) *a.stats_nslots = cdiv(a.N, BN / WN);      // one slot per wave tile
   const int rs_bytes = a.rs_stats ? a.rs_nslots * ((BM + 63) / 64 * 64) * 4 : 0;      // row statistics prefetched by LDS-DMA behind the two stages
@@ -972,6 +1022,7 @@ int launch_t(const GemmArgs& a, hipStream_t stream) {
     case EPI_RESID: return launch_epi<T, EPI_RESID>(a, stream);
     case EPI_SWIGLU: return launch_epi<T, EPI_SWIGLU>(a, stream);
     case EPI_F32OUT: return a.force_tile == 1 ? launch_cfg<T, 128, 128, 2, 2, EPI_F32OUT>(a, stream) : launch_cfg8<T, EPI_F32OUT>(a, stream);
+    case EPI_LSE: return a.force_tile == 1 ? launch_cfg<T, 128, 128, 2, 2, EPI_LSE>(a, stream) : launch_cfg8<T, EPI_LSE>(a, stream);
   }
   omchat_set_error("launch_gemm: bad epilogue");
   return 1;
@@ -1155,6 +1206,11 @@ int launch_gemm(int dtype, const GemmArgs& a, hipStream_t stream) {
   GemmArgs b = a;
   if (a.epi == EPI_F32OUT) {      // fp32 output (numerics option of the tensor-parallel path): 256^2 staggered kernel, 128^2 for small problems; no tuning
     OM_CHECK(a.ldc % 4 == 0 && ((uintptr_t)a.C & 15) == 0 && !a.bias && !a.resid, "fp32-output GEMM: C 16-byte aligned, ldc % 4 == 0, no bias / residual");
+    b.force_tile = (long)cdiv(a.M, 256) * cdiv(a.N, 256) < 64 ? 1 : 2;
+    b.stream_k = -1;
+  } else if (a.epi == EPI_LSE) {      // teacher-forced scoring: no output matrix; the same two kernels, chosen by the same rule; no tuning
+    OM_CHECK(a.stats && a.stats_ld >= a.M && a.lse_labels && a.lse_tgt && !a.bias && !a.resid && !a.row_scale && !a.rs_stats,
+             "log-sum-exp GEMM: (max, sum) planes [2 * cdiv(N, 64)][stats_ld >= M], labels and target logits; no bias / residual / row scale");
     b.force_tile = (long)cdiv(a.M, 256) * cdiv(a.N, 256) < 64 ? 1 : 2;
     b.stream_k = -1;
   } else

@@ -43,6 +43,12 @@ enum {
   // consumer (the next GEMM's row scale, the ViT q / k norm) sums a row's slots in slot order: a fixed order, so the statistics are deterministic
   EPI_LS_RESID_STATS = 7,
   EPI_NONE_STATS = 8,
+  // teacher-forced scoring: NOTHING is stored to C.  Every wave tile reduces each of its rows over its valid columns to an
+  // online pair (m = max, s = sum exp(x - m)) of the raw fp32 accumulators and leaves it in GemmArgs.stats, slot-major as the statistics above with
+  // two planes per slot: stats[(2 * slot) * stats_ld + row] = m, stats[(2 * slot + 1) * stats_ld + row] = s, slot = first column of the wave tile / 64
+  // (cdiv(N, 64) slots: both kernels this mode runs on have 64-column wave tiles).  The one lane that owns column lse_labels[row] also writes that
+  // accumulator to lse_tgt[row] (labels outside [0, N) write nothing).  Finished by launch_score_finish (score.hip)
+  EPI_LSE = 9,
 };
 struct GemmArgs {
   const void* A; int lda;
@@ -70,6 +76,8 @@ struct GemmArgs {
   const float* rs_stats = nullptr; int rs_ld = 0, rs_nslots = 0, rs_dim = 0; float rs_eps = 0.f;
   // EPI_*_STATS: per-row partial sums of squares of the stored outputs (slot-major); *stats_nslots receives the number of slots the launch(es) wrote
   float* stats = nullptr; int stats_ld = 0; int* stats_nslots = nullptr;
+  // EPI_LSE: device int32 [M] labels and the fp32 [M] target logits
+  const int* lse_labels = nullptr; float* lse_tgt = nullptr;
 };
 int launch_gemm(int dtype, const GemmArgs& a, hipStream_t stream);
 // finishes the per-slot partials of an EPI_*_STATS GEMM (or of launch_row_sumsq); statistics are SLOT-MAJOR, stats[slot * ld + m], ld >= rows:
@@ -501,6 +509,18 @@ size_t logprob_top_ws_bytes(int b, int top_n);
 size_t logprob_table_bytes_ex(int b, int tp, int top_n, int n_score);
 int launch_logprob(const LogprobArgs& a, hipStream_t s);
 int launch_logprob_rewind(int* cnt, int b, int n, hipStream_t s);      // cnt[i] -= n for rows < b
+
+// ------------------------------------------------------------------------------------------------ teacher-forced scoring (score.hip)
+// logprob[row] = log_softmax(A[row] W^T)[labels[row]] without the logits: launch_gemm with EPI_LSE leaves the (max, sum) pairs of every 64-column
+// slot and the label's logit in the workspace, launch_score_finish folds a row's slots in a fixed order (one wave per row).  A row whose label
+// is -100 gets 0; a label outside {-100} u [0, N) is the caller's to refuse before the launch (the kernels stay in bounds and write NaN).
+// ws: score_ws_bytes(M, N) bytes, 16-byte aligned.  lse [M] may be null.
+size_t score_ws_bytes(int M, int N);
+int launch_score(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const int* labels, float* logprob, float* lse,
+                 void* ws, size_t ws_bytes, hipStream_t s);
+// out[0] = -sum logprob over the rows with label >= 0, out[1] = their number, out[2 + i] = sum logprob of sequence i (rows [i * S, (i + 1) * S)),
+// out[2 + b + i] = its number of scored rows.  One workgroup, fixed trees: the same bits every run
+int launch_score_reduce(const float* logprob, const int* labels, int b, int S, float* out, hipStream_t s);
 // HF logits constraints (constrain.hip; tests/constraints_ref.py restates the ban set).  The caps are the public
 // header's OMCHAT_CON_* (capi.hip asserts they agree).
 constexpr int CON_NGRAM_MAX = 64, CON_EOS_MAX = 16, CON_SUPPRESS_MAX = 1024, CON_BAD_WORDS_MAX = 1024, CON_BAD_WORD_IDS_MAX = 8192;

@@ -374,7 +374,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  ctx->beam.release(); ctx->group.release(); ctx->ext_ws.release(); ctx->pick.release();
+  ctx->beam.release(); ctx->group.release(); ctx->ext_ws.release(); ctx->score_ws.release(); ctx->pick.release();
   delete ctx;
 }
 
@@ -1125,6 +1125,22 @@ extern "C" int omchat_lm_head(omchat_ctx* ctx, const void* hidden, int n, float*
   OM_CHECK(ctx && hidden && logits, "null argument");
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
   return lm_head_rows(ctx, hidden, n, logits, (hipStream_t)stream, ctx->lm_w(OMCHAT_WFMT_16));
+}
+// Teacher-forced scoring: a pure function of `hidden` -- no cache, position or pick state is read or written
+extern "C" int omchat_score_hidden(omchat_ctx* ctx, const void* hidden, int rows, const int32_t* labels, int b, int S, float* logprob, float* out,
+                                   void* stream) {
+  OM_CHECK(ctx && hidden && labels && logprob && out, "null argument");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(ctx->tp_size == 1, "scoring under tensor parallelism is not implemented: the lm_head is vocabulary-parallel and no exchange of the (max, sum) partials is built");
+  OM_CHECK(omchat_weights_missing(ctx) == 0, "scoring needs the weights: " + std::string(omchat_last_error()));
+  OM_CHECK(rows >= 1 && rows <= c.max_prefill_rows, "rows exceeds max_prefill_rows");
+  OM_CHECK(b >= 1 && S >= 1 && (int64_t)b * S == rows, "b * S != rows");
+  TRY(ctx->grow(ctx->score_ws, score_ws_bytes(rows, c.t_vocab)));      // before anything is enqueued
+  hipStream_t s = (hipStream_t)stream;
+  const omchat_ctx::WRef& lm = ctx->lm_w(OMCHAT_WFMT_16);
+  TRY(launch_score(ctx->dt, hidden, c.t_hidden, lm.W, lm.ldw, rows, c.t_vocab, c.t_hidden, labels, logprob, nullptr, ctx->score_ws.p, ctx->score_ws.cap, s));
+  return launch_score_reduce(logprob, labels, b, S, out, s);
 }
 
 // Attention form of omchat_prefill_extend (measured with tools/bench_extend.py, LOG.md).  The prefill kernel issues

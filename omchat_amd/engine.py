@@ -281,9 +281,10 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ splice
-    def splice(self, input_ids, attention_mask, feats, padding_side="right", max_length=None):
+    def splice(self, input_ids, attention_mask, feats, padding_side="right", max_length=None, return_plan=False):
         """input_ids int64 [b,T] (CPU or CUDA), attention_mask [b,T] or None, feats [n_tiles, ntok, H] CUDA or None.
-        Returns (inputs_embeds [b,S,H] CUDA, lengths list, valid-mask bool [b,S] CPU)."""
+        Returns (inputs_embeds [b,S,H] CUDA, lengths list, valid-mask bool [b,S] CPU); with return_plan also the host plan src_index
+        int32 [b,S] (>= 0: a token slot; what omchat_amd/scoring.py splices labels with)."""
         torch = _torch()
         ids = input_ids.detach().to("cpu", torch.int64).contiguous()
         b, T = ids.shape
@@ -301,7 +302,8 @@ class Engine:
         f = None if feats is None else feats.to(device=self.device, dtype=self.torch_dtype).contiguous()
         out = torch.empty(b, S.value, self.cfg.text["hidden_size"], dtype=self.torch_dtype, device=self.device)
         check(self.lib.omchat_splice_gather(self.h, ptr(idx_d), ptr(f), ptr(out), b * S.value, cur_stream()))
-        return out, [int(x) for x in lens], idx.ne(_lib.PAD_ROW)
+        res = (out, [int(x) for x in lens], idx.ne(_lib.PAD_ROW))
+        return res + (idx,) if return_plan else res
 
     # ------------------------------------------------------------------ decoder
     def prefill(self, embeds, lengths=None, want_hidden=False, want_logits=True, padding_side="right"):
@@ -490,6 +492,31 @@ class Engine:
         out = torch.empty(*h.shape[:-1], self.c.t_vocab, dtype=torch.float32, device=self.device)
         check(self.lib.omchat_lm_head(self.h, ptr(h), n, ptr(out), cur_stream()))
         return out
+
+    def score_hidden(self, hidden, shifted_labels):
+        """Teacher-forced scoring (include/omchat_hip.h: omchat_score_hidden).  hidden [b, S, H]: the final-normed rows
+        of prefill(want_hidden=True); shifted_labels int [b, S] (CPU or CUDA): the token that follows each slot, -100 = not scored.
+        -> (logprob fp32 [b, S] with 0 where the label is -100, loss 0-dim fp32 = mean of -logprob over the scored slots (NaN if none),
+        seq_sum fp32 [b] = every sequence's sum of logprob, seq_count fp32 [b]), all on the device, no synchronisation.  The [b, S, V]
+        logits are never materialised.  Refused under tensor parallelism.  Labels on the CPU (what the model's splice hands over) are
+        range-checked here, before the launch: anything but -100 or an id in [0, V) is a ValueError.  Labels already on the device are
+        NOT read back (that would synchronise): the kernels stay in bounds and a label outside the range scores NaN, in its row and in
+        the loss -- check such labels before uploading them."""
+        torch = _torch()
+        from .scoring import check_labels
+        if self.tp_size > 1:
+            raise NotImplementedError("scoring under tensor parallelism: the lm_head is vocabulary-parallel and no exchange of the partials is built")
+        h = hidden.to(device=self.device, dtype=self.torch_dtype).contiguous()
+        if h.dim() != 3 or tuple(shifted_labels.shape) != tuple(h.shape[:2]):
+            raise ValueError("score_hidden: hidden [b, S, H] and shifted_labels [b, S]")
+        b, S, _ = h.shape
+        if shifted_labels.device.type == "cpu":
+            check_labels(shifted_labels, self.c.t_vocab)      # host labels (the model's splice): no synchronisation
+        lab = shifted_labels.to(device=self.device, dtype=torch.int32).contiguous()
+        logprob = torch.empty(b, S, dtype=torch.float32, device=self.device)
+        out = torch.empty(2 + 2 * b, dtype=torch.float32, device=self.device)
+        check(self.lib.omchat_score_hidden(self.h, ptr(h), b * S, ptr(lab), b, S, ptr(logprob), ptr(out), cur_stream()))
+        return logprob, out[0] / out[1], out[2:2 + b], out[2 + b:]
 
     def full_logits(self, logits):
         """[b, V / tp] rank-local vocabulary shard -> [b, V] on every rank (HF-style consumers of `out.logits` must not see a

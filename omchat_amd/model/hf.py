@@ -68,10 +68,14 @@ class OmChatForConditionalGeneration:
     def eval(self):
         return self
 
-    def forward(self, input_ids=None, images=None, **kw):
-        return self._m.forward(input_ids=input_ids, images=images, **kw)
+    def forward(self, input_ids=None, images=None, labels=None, **kw):
+        """labels: teacher-forced scoring on the same path as the native class (OmChatQwen2ForCausalLM.forward)"""
+        return self._m.forward(input_ids=input_ids, images=images, labels=labels, **kw)
 
     __call__ = forward
+
+    def score(self, input_ids, images=None, attention_mask=None, labels=None):
+        return self._m.score(input_ids, images=images, attention_mask=attention_mask, labels=labels)
 
     def generate(self, input_ids=None, images=None, **kw):
         """hf_example.py:16: model.generate(**inputs, max_new_tokens, do_sample, eos_token_id, pad_token_id)."""

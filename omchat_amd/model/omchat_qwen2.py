@@ -6,6 +6,7 @@ from ..constants import IMAGE_TOKEN_INDEX
 from ..config import OmChatConfig
 from .vision_tower import build_vision_tower
 from .projector import build_vision_projector
+from ..scoring import check_labels, shift_labels, splice_labels
 
 
 class OmChatQwen2Config(OmChatConfig):
@@ -40,6 +41,10 @@ class CausalLMOutputWithPast(dict):
         super().__init__(logits=logits, past_key_values=past_key_values, loss=None)
         self.logits, self.past_key_values, self.loss = logits, past_key_values, None
 
+    def add(self, name, value):
+        self[name] = value
+        setattr(self, name, value)
+
 
 class _GenerationConfig(types.SimpleNamespace):
     pass
@@ -59,8 +64,10 @@ class OmChatMetaForCausalLM:
         return self.engine.encode_images(images, t.select_layer).to(images.dtype)
 
     def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels, images):
-        """omchat_arch.py:55-209 for inference (labels pass through as None).  Returns the reference's 6-tuple
-        (input_ids|None, position_ids, attention_mask, past_key_values, inputs_embeds|None, labels)."""
+        """omchat_arch.py:55-209.  Returns the reference's 6-tuple
+        (input_ids|None, position_ids, attention_mask, past_key_values, inputs_embeds|None, labels).  Given labels come back as the
+        reference's `new_labels` [b, S] (int64, CPU): filtered by the mask, image-token positions dropped, -100 on feature rows, padding
+        (either side) and beyond tokenizer_model_max_length (:112-199; omchat_amd/scoring.py on top of the splice plan)."""
         vision_tower = self.get_vision_tower()
         if vision_tower is None or images is None or input_ids.shape[1] == 1:
             if past_key_values is not None and vision_tower is not None and images is not None and input_ids.shape[1] == 1:
@@ -81,7 +88,7 @@ class OmChatMetaForCausalLM:
         feats = self.encode_images(images)
         side = getattr(self.config, "tokenizer_padding_side", "right")
         maxlen = getattr(self.config, "tokenizer_model_max_length", None)
-        embeds, lengths, valid = self.engine.splice(input_ids, attention_mask, feats, side, maxlen)
+        embeds, lengths, valid, plan = self.engine.splice(input_ids, attention_mask, feats, side, maxlen, return_plan=True)
         self._last_lengths = lengths
         new_mask = None if attention_mask is None else valid.to(dtype=attention_mask.dtype, device=attention_mask.device)   # :201-204
         new_pos = None                                                                 # :206-207 (None unless the caller passed one)
@@ -93,6 +100,8 @@ class OmChatMetaForCausalLM:
                     new_pos[i, S - n:] = torch.arange(n, dtype=position_ids.dtype)
                 else:
                     new_pos[i, :n] = torch.arange(n, dtype=position_ids.dtype)
+        if labels is not None:
+            labels = splice_labels(plan, input_ids, attention_mask, labels)
         return None, new_pos, new_mask, past_key_values, embeds, labels
 
 
@@ -128,15 +137,42 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, images=None, return_dict=None):
+        """labels (int [b, T] beside input_ids, or [b, S] beside inputs_embeds; -100 = not scored) on a prefill call: teacher-forced scoring
+        (DESIGN.md section 18).  The output then carries `loss` (fp32 device scalar: Qwen2's shifted cross-entropy over the spliced
+        sequence, mean over the labels that are not ignored, NaN if there are none), `token_logprobs` fp32 [b, S] (column t >= 1:
+        log p(labels[:, t] | slots < t) under the raw fp32 distribution; 0 where the label is ignored and in column 0) and `labels` (the
+        spliced labels [b, S]).  The full [b, S, V] logits the reference returns are NOT materialised: `logits` stays [b, 1, V] of the
+        last valid position, as without labels.  Text-only calls compact a row's unmasked tokens (Engine.splice), and so its labels:
+        a label at a masked position is not scored.  labels on a decode call: ValueError; under tensor parallelism: NotImplementedError."""
         if output_attentions:
             raise NotImplementedError("attention maps are never materialised by the flash kernels")
+        if labels is not None:
+            if self.engine.tp_size > 1:      # before the tower runs
+                raise NotImplementedError("forward(labels=...) under tensor parallelism: the lm_head is vocabulary-parallel and no exchange of "
+                                          "the scoring partials is built")
+            if inputs_embeds is None and (past_key_values is not None or input_ids is None):
+                raise ValueError("forward(labels=...) scores a prefill call (inputs_embeds, or input_ids without a cache), not a decode step")
+            # shape and range on the raw labels, before any work and before any state of an earlier prefill changes (the splice only moves
+            # values and inserts -100; labels at image-token and masked positions drop out in it, so they are not looked at)
+            want = tuple(input_ids.shape) if inputs_embeds is None else tuple(inputs_embeds.shape[:2])
+            if tuple(labels.shape) != want:
+                raise ValueError(f"labels {tuple(labels.shape)} must have the shape {want} of the call's {'input_ids' if inputs_embeds is None else 'inputs_embeds rows'}")
+            host = labels.detach().to("cpu", torch.int64)
+            if inputs_embeds is None:
+                keep = input_ids.detach().to("cpu").ne(IMAGE_TOKEN_INDEX)
+                if attention_mask is not None and tuple(attention_mask.shape) == want:
+                    keep &= attention_mask.detach().to("cpu").ne(0)
+                host = host[keep]
+            check_labels(host, self.vocab_size)
         if inputs_embeds is None:
             (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds, labels) = \
                 self.prepare_inputs_labels_for_multimodal(input_ids, position_ids, attention_mask, past_key_values, labels, images)
         if inputs_embeds is None and past_key_values is None:
             # text-only prefill: embed_tokens through the same gather kernel
-            inputs_embeds, lengths, _ = self.engine.splice(input_ids, attention_mask, None)
+            inputs_embeds, lengths, _, plan = self.engine.splice(input_ids, attention_mask, None, return_plan=True)
             self._last_lengths = lengths
+            if labels is not None:
+                labels = splice_labels(plan, input_ids, attention_mask, labels)
         if inputs_embeds is not None:
             b, S, _ = inputs_embeds.shape
             lengths = self._last_lengths if self._last_lengths is not None and len(self._last_lengths) == b else [S] * b
@@ -163,13 +199,23 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 raise NotImplementedError("left-padded ragged batch: the masked decode step runs at tp_size == 1 only; pad on the right")
             self._padded_batch = ragged and can_mask
             self._prefill_slots = S                                   # the common cache slot a padded batch's decode steps append at
-            logits_last, hidden = self.engine.prefill(inputs_embeds, lengths, want_hidden=bool(output_hidden_states), padding_side=side)
+            if labels is not None:
+                new_labels = labels.detach().to("cpu", torch.int64)
+            logits_last, hidden = self.engine.prefill(inputs_embeds, lengths, want_hidden=bool(output_hidden_states) or labels is not None,
+                                                      padding_side=side)
             local = logits_last                                       # this rank's vocabulary shard (the whole vocabulary at TP = 1)
             logits_last = self.engine.full_logits(logits_last)        # vocab-parallel lm_head: gather the rank-local shards
             out = CausalLMOutputWithPast(logits_last.unsqueeze(1), KVHandle(self.engine, b))
             out.local_logits = local
             if output_hidden_states:
                 out["hidden_states"] = (hidden,); out.hidden_states = (hidden,)
+            if labels is not None:
+                # slot t's row predicts the label of slot t + 1 (Qwen2ForCausalLM.forward: logits[..., :-1, :] against labels[..., 1:])
+                lp, loss, seq_sum, seq_count = self.engine.score_hidden(hidden, shift_labels(new_labels))
+                tl = torch.zeros_like(lp)
+                tl[:, 1:] = lp[:, :-1]
+                out.add("loss", loss); out.add("token_logprobs", tl); out.add("labels", new_labels)
+                out.add("sequence_logprobs", seq_sum); out.add("num_tokens", seq_count)
             return out
         if input_ids.shape[1] != 1:
             raise ValueError("decode steps take exactly one token per sequence")
@@ -190,6 +236,20 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         return out
 
     __call__ = forward
+
+    def score(self, input_ids, images=None, attention_mask=None, labels=None):
+        """Teacher-forced scoring of given text: forward(labels=...) with labels = input_ids by default -- the image
+        placeholders drop out in the splice, so every text token but a row's first is scored.  -> dict: `loss` (fp32 scalar, mean negative
+        log-probability of the scored tokens), `token_logprobs` fp32 [b, S] and `labels` int64 [b, S] as forward(labels=...) returns them,
+        `sequence_logprobs` fp32 [b] (sum over a row's scored tokens), `num_tokens` int64 [b] and `perplexity` fp32 [b] =
+        exp(-sequence_logprobs / num_tokens) (NaN for a row without scored tokens); all but `labels` on the device.  One host
+        synchronisation, at the end."""
+        out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, labels=input_ids if labels is None else labels)
+        n = out.num_tokens
+        res = dict(loss=out.loss, token_logprobs=out.token_logprobs, labels=out.labels, sequence_logprobs=out.sequence_logprobs,
+                   num_tokens=n.to(torch.int64), perplexity=torch.exp(-out.sequence_logprobs / n))
+        torch.cuda.current_stream().synchronize()
+        return res
 
     def enable_mxfp4_decode(self, on=True, batched=False):
         """Engine.enable_mxfp4_decode: batch-1 decode steps of generate() stream the MXFP4 replica of the decoder weights (greedy, sampling,
