@@ -1567,52 +1567,58 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_mx4_kernel(GemvP p) { 
 // adds the residual: x + mlp is complete when the launch ends, and the NEXT projection normalises it in its own registers
 // (gemv_rows_norm_kernel).  Rows are dealt to 2 workgroups per CU, row r of a workgroup to wave r % 4.
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int F8>
+// CP chunks per pass and, for the bf16x12 rows, G chunks per decode group are compile-time: a lane adds chunk after chunk into one accumulator,
+// so how the chunks are grouped into passes changes no bit.  CP divides 8, so the passes cover exactly the 16-bit form's ceil8(nch)
+// chunks: those in [nch, ceil8(nch)) read weights 0..7 against zeros of x (the clamped address) and there is none beyond -- with
+// K % 4096 == 0 no w * 0 term exists, and a row with an infinite weight among its first eight stays infinite at every CP.
+// 16-bit, e4m3 and MXFP4 rows: 8 chunks (24 KB per wave in the three buffers).  bf16x12: 4 chunks -- 68 VGPRs, where 8 take 136 and
+// leave one workgroup per CU.
+template <typename T, int F8, int CP = 8, int G = 2>
 __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_per_wg) {
+  static_assert(8 % CP == 0 && CP % G == 0, "whole passes cover ceil8(nch) chunks, whole decode groups a pass");
   extern __shared__ __attribute__((aligned(16))) char xs_raw[];
   T* xs = (T*)xs_raw;
   // one row per wave, rows_per_wg (<= 8) waves per workgroup: every wave of a workgroup streams the same number of bytes (7 rows per
   // workgroup at N = 3584 on 2 x 256 workgroups; two rows per wave on 4 waves left the fourth wave idle half the time: 26.0 us)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nch = (p.K + 511) >> 9, npass = (nch + 7) >> 3;
+  const int nch = (p.K + 511) >> 9, npass8 = (nch + 7) >> 3, npass = npass8 * (8 / CP);
   const int n = blockIdx.x * rows_per_wg + wave;
   const bool valid = n < p.N;
   const int row = valid ? n : p.N - 1;
   OM_DBG_MIN(6, blockIdx.x < 8);
   typedef typename RwW<F8>::type wreg_t;
-  auto load_w = [&](wreg_t (&w)[8], int pass) {
+  auto load_w = [&](wreg_t (&w)[CP], int pass) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      int k = (pass * 8 + c) * 512 + lane * 8;
+    for (int c = 0; c < CP; ++c) {
+      int k = (pass * CP + c) * 512 + lane * 8;
       k = k < p.K ? k : 0;                      // beyond K: any valid address (x is zero there)
-      if constexpr (F8 == WF_X12) w[c] = x12_ldw(p, (size_t)row, pass * 8 + c < nch ? pass * 8 + c : 0, pass * 8 + c < nch ? lane : 0);
+      if constexpr (F8 == WF_X12) w[c] = x12_ldw(p, (size_t)row, pass * CP + c < nch ? pass * CP + c : 0, pass * CP + c < nch ? lane : 0);
       else w[c] = rw_ldw<T, F8>(p, (size_t)row, k);
     }
   };
   float acc = 0.f;
   X12Row xst;
-  auto dots = [&](wreg_t (&w)[8], int pass) {
+  auto dots = [&](wreg_t (&w)[CP], int pass) {
     if constexpr (F8 == WF_X12) {      // the 16-bit kernel's dot products in its order, on registers decoded G chunks at a time
-      constexpr int G = 2;      // chunks per group (no group size fits the 128 VGPRs at which two workgroups share a CU without spilling: LOG.md)
 #pragma unroll
-      for (int h = 0; h < 8 / G; ++h) {
+      for (int h = 0; h < CP / G; ++h) {
         rw_u32x4 wd[G];
-        x12_group<G>(wd, &w[G * h], xst, pass * 8 + G * h, nch, lane);
+        x12_group<G>(wd, &w[G * h], xst, pass * CP + G * h, nch, lane);
 #pragma unroll
         for (int c = 0; c < G; ++c) {
-          const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * 8 + G * h + c) * 512 + lane * 8);
+          const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * CP + G * h + c) * 512 + lane * 8);
           acc = rw_dot8<T>(wd[c], xr, acc);
         }
       }
     } else {
 #pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * 8 + c) * 512 + lane * 8);
+      for (int c = 0; c < CP; ++c) {
+        const rw_u32x4 xr = *reinterpret_cast<const rw_u32x4*>(xs + (pass * CP + c) * 512 + lane * 8);
         acc = rw_dotw<T, F8>(w[c], xr, acc);
       }
     }
   };
-  wreg_t wa[8], wb[8], wc[8];
+  wreg_t wa[CP], wb[CP], wc[CP];
   load_w(wa, 0);
   if constexpr (F8 == WF_X12) x12_row_load(xst, p, (size_t)row, lane);      // bf16x12: the row's top and patches right behind the first pass, which needs them
   if (npass > 1) load_w(wb, 1);
@@ -1624,15 +1630,15 @@ __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_pe
   const float e_bias = p.bias ? e_bias_raw : 0.f, e_res = p.resid ? e_res_raw : 0.f;
   float e_scale = 1.f;
   if constexpr (F8 == WF_E4M3) e_scale = p.w_scale[row];
-  // x -> LDS (zero beyond K up to the last whole pass), once per workgroup, under the first passes' weight loads
-  for (int i = threadIdx.x; i < npass * 8 * 64; i += blockDim.x) {
+  // x -> LDS (zero beyond K up to the last whole pass of 8), once per workgroup, under the first passes' weight loads
+  for (int i = threadIdx.x; i < npass8 * 8 * 64; i += blockDim.x) {
     const rw_u32x4 z = {0u, 0u, 0u, 0u};
     const rw_u32x4 v = i * 8 < p.K ? *reinterpret_cast<const rw_u32x4*>((const T*)p.X + i * 8) : z;
     *reinterpret_cast<rw_u32x4*>(xs + i * 8) = v;
   }
   __syncthreads();
   if constexpr (F8 == WF_X12) x12_row_finish(xst);
-  // three register buffers: the weights of passes ps + 1 and ps + 2 are in flight under the dot products of pass ps (24 KB per wave)
+  // three register buffers: the weights of passes ps + 1 and ps + 2 are in flight under the dot products of pass ps
   for (int ps = 0; ps < npass; ps += 3) {
     if (ps > 0 && ps + 2 < npass) load_w(wc, ps + 2);
     dots(wa, ps);
@@ -1661,7 +1667,7 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
 template <typename T>
 __global__ __launch_bounds__(512) void gemv_rows_longk_mx4_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_MX4>(p, rows_per_wg); }
 template <typename T>
-__global__ __launch_bounds__(512) void gemv_rows_longk_x12_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_X12>(p, rows_per_wg); }
+__global__ __launch_bounds__(512) void gemv_rows_longk_x12_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_X12, 4>(p, rows_per_wg); }
 
 #if OMCHAT_EXPERIMENTS
 // The same rows WITHOUT the LDS stage (round 5, tuning key 39): a wave streams one row and uses every x element once, so the LDS copy only saves L2

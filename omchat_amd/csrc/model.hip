@@ -1001,9 +1001,9 @@ static int build_replica(omchat_ctx* ctx, int fmt) {
 
 // omchat_op_set_tuning key 50: the roles of a batch-1 step that stream the bf16x12 coding of their bf16 rows: bit 0 = gate|up, bit 1 =
 // down_proj, bit 2 = lm_head; 0 = the 16-bit launches exactly (A/B: the same bits either way).  The default is what tools/bench_bf16x12.py measured:
-// gate|up 41.1 -> 33.7 us and lm_head 160.3 -> 126.0 us are on; the long-K down_proj form measured 23.3 -> 28.1 us (its three register buffers
-// plus the decoded registers take 136 VGPRs, over the 128 of two workgroups per CU) and stays on 16 bits (LOG.md)
-int g_x12_roles = 5;
+// gate|up 41.1 -> 33.7 us, lm_head 160.3 -> 126.0 us, and the long-K down_proj form in passes of four chunks (68 VGPRs: both workgroups of
+// a CU resident) 22.8 -> 21.9 us; in the 16-bit form's passes of eight it took 136 VGPRs and measured 27.3 us (LOG.md)
+int g_x12_roles = 7;
 void model_set_x12_roles(int v) { g_x12_roles = v & 7; }
 
 // The roles a step of `rows` rows would stream coded, by everything but the state of the copies: the step's format is 16-bit at b == 1 on one
