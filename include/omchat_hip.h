@@ -279,7 +279,8 @@ int omchat_beam_result(omchat_ctx* ctx, int num_return, int32_t* tokens, int32_t
  * share = 0: prompt i's slots [0, prompt_len) are copied into its N rows (the e4m3 bytes and scales too); from there the rows are an ordinary
  * batch for omchat_decode_step(b * N) in every mode it has, and no mode of the context is on.
  * share = 1: only row i*N receives the prompt (one row copy for i > 0); the other rows hold nothing below slot prompt_len.  While this
- * mode is on, omchat_decode_step takes exactly b * N rows and its attention reads the prompt keys once per group (omchat_op_attn_shared);
+ * mode is on, omchat_decode_step takes exactly b * N rows -- of any lengths >= prompt_len (they differ after omchat_prefill_suffixes) -- and
+ * its attention reads the prompt keys once per group (omchat_op_attn_shared, omchat_op_attn_shared_lens);
  * omchat_decode_verify, omchat_prefill_extend, the masked steps and omchat_beam_begin are refused.  Needs the 16-bit KV cache, tp_size == 1,
  * N <= 16 and N * (q heads per kv head) <= 128; any weight format of the batched step.  It ends with any prefill or with b = 0 (which
  * does nothing else).  A captured decode graph is bound to (b, N, prompt_len).
@@ -335,6 +336,29 @@ int omchat_extend_attn_form(int S_new, int keep, int Hkv);
 /* test hook: rows [pos0, pos0 + n) of sequence 0's 16-bit K (which = 0) or V (which = 1) cache of decoder layer `layer`, copied to
  * out [t_kv_heads, n, 128] (device, context dtype) */
 int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, int n, void* out, void* stream);
+/* the same for cache row `row` < max_batch (the sibling rows of a group) */
+int omchat_kv_read_row(omchat_ctx* ctx, int row, int layer, int which, int pos0, int n, void* out, void* stream);
+
+/* ---- shared-prefix batches: N suffixes over one prefilled prompt -------------------------------------------------- */
+/* omchat_prefill_suffixes: rows 0 .. N - 1 each hold exactly `keep` slots of ONE prompt on the host and the device -- the ordinary rows that
+ * omchat_group_begin(ctx, 1, N, keep, 0) leaves, the shared-prompt state of omchat_group_begin(ctx, 1, N, keep, 1), or for N == 1 simply the
+ * b = 1 state with keep slots.  embeds [N, S_max, t_hidden] (device, context dtype), row j valid in [0, lengths[j]) (host lengths, 1 .. S_max);
+ * the other rows are padding: they may be computed, and they write no cache slot.  Row (j, t) runs through the layers at position keep + t
+ * over the prompt keys [0, keep) of row 0 and row j's own keys [keep, keep + t]; its K / V are appended at slot keep + t of row j's own cache.
+ * No slot outside [keep, keep + lengths[j]) of any row is written, row 0's slots < keep never.  The lengths end as keep + lengths[j] on the
+ * host and the device, positions and the pick state as omchat_prefill leaves them; a shared-prompt group stays on, and omchat_decode_step
+ * then takes its N rows of different lengths.  logits_last: device fp32 [N, t_vocab], row j = the logits of (j, lengths[j] - 1) (or NULL);
+ * hidden_out: optional [N, S_max, t_hidden] post-final-norm rows.  The attention is omchat_op_attn_suffix; over forked rows tuning key 51 = 0
+ * takes the batched prefill kernel with q_pos0 = keep instead (omchat_suffix_attn_form).  Refused before anything is enqueued: no such
+ * state (a row that does not hold keep slots, a group of another shape), keep < 1, lengths outside [1, S_max], N > max_batch,
+ * N * S_max > max_prefill_rows or > 65535, keep + S_max > max_seq, an active beam search, a left-padded or masked-decode state, the e4m3 KV
+ * cache, fp8 x fp8 prefill GEMMs, tensor-parallel contexts, and more than 8 query heads per kv head over a shared
+ * prompt.  Synchronises. */
+int omchat_prefill_suffixes(omchat_ctx* ctx, const void* embeds, int N, int S_max, const int32_t* lengths, int keep, float* logits_last,
+                            void* hidden_out, void* stream);
+/* the attention form omchat_prefill_suffixes takes (shared: over a shared prompt; n_rep = q heads per kv head): 1 = the suffix kernel,
+ * 0 = the batched prefill kernel with q_pos0 = keep */
+int omchat_suffix_attn_form(int shared, int n_rep);
 
 /* ---- decode step as a hipGraph ------------------------------------------------------------------------------------ */
 /* With on != 0, omchat_decode_step on a TP = 1 context (b <= 32) replays one captured graph per step instead of issuing its
@@ -650,6 +674,22 @@ int omchat_op_attn_extend(int dtype, const void* q, const void* k, const void* v
 size_t omchat_op_attn_shared_ws(int G, int N, int Hq, int Hkv, int P, int L);
 int omchat_op_attn_shared(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L,
                           float scale, void* ws, size_t ws_bytes, void* stream);
+/* the same over rows of different lengths: kv_len device int32 [G*N], row r holds kv_len[r] keys (P < kv_len[r] <= L) and its query sits at
+ * position kv_len[r] - 1; L only sizes the grid and the workspace.  A suffix tile beyond a row's length leaves the neutral partial.  With
+ * every kv_len[r] == L it gives the bits of omchat_op_attn_shared. */
+int omchat_op_attn_shared_lens(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L,
+                               const int* kv_len, float scale, void* ws, size_t ws_bytes, void* stream);
+/* Suffix-pass attention of omchat_prefill_suffixes: N rows of S query tokens each, q / out [N,S,Hq,128] (q already
+ * rotated), k / v [N rows,Hkv,cap,128] complete; lengths host int32 [N], 1 .. S: the valid tokens of row j.  Query (j, t) sees the keys
+ * [0, P) of row 0 and the keys [P, P + t] of row j.  Only out rows t < lengths[j] are defined by the contract (the others are computed from
+ * the row's valid keys).  Never read: row 0's slots >= P through the prefix, slots < P of rows j > 0, slots >= P + lengths[j] of any row.
+ * kv_len_dev: N ints of device memory that receive P + lengths[j] (one synchronising copy); lengths == NULL: kv_len_dev already holds
+ * them -- the lengths come from the device, nothing synchronises, and a value outside [P + 1, P + S] reads no slot beyond P + S (a row
+ * without own keys gets the prompt's keys only).  ws of omchat_op_attn_suffix_ws(N, S, Hq, Hkv, P) bytes.  One attention launch and one
+ * merge whatever N is.  P >= 1, P + S <= cap, Hq / Hkv <= 8, N * S <= 65535. */
+size_t omchat_op_attn_suffix_ws(int N, int S, int Hq, int Hkv, int P);
+int omchat_op_attn_suffix(int dtype, const void* q, const void* k, const void* v, void* out, int N, int S, int Hq, int Hkv, int cap, int P,
+                          const int32_t* lengths, int* kv_len_dev, float scale, void* ws, size_t ws_bytes, void* stream);
 /* the same with the RoPE + append fused in, as the verify step runs it: qkv [T][(Hq + 2 Hkv) * 128] raw projections (not modified);
  * q / k rotated at positions L .. L + T - 1 (table of omchat_op_rope_kv), k / v appended to rows L .. L + T - 1 of the cache
  * (the bytes omchat_op_rope_kv writes).  Synchronises. */

@@ -135,6 +135,12 @@ _SIGS = {
     "omchat_prefill_extend": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "omchat_extend_attn_form": (_i, [_i, _i, _i]),
     "omchat_kv_read": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "omchat_kv_read_row": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "omchat_prefill_suffixes": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "omchat_suffix_attn_form": (_i, [_i, _i]),
+    "omchat_op_attn_shared_lens": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
+    "omchat_op_attn_suffix_ws": (_sz, [_i, _i, _i, _i, _i]),
+    "omchat_op_attn_suffix": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_verify_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _sz, _vp]),

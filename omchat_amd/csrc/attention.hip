@@ -2039,7 +2039,14 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
 // length: its slots beyond are its own suffix.  The others are one sibling's suffix splits of one tile: its n_rep query rows over its own
 // keys [p.Skv, len).  q is rotated at len - 1; the suffix split that holds key len - 1 takes it from k_new / v_new and appends it to the
 // row's own cache (one writer; no workgroup reads that slot).  A split without keys leaves the neutral partial.  No causal bound.
-template <typename T, int NW, bool EXT = false, bool SHR = false>
+// SFX (suffix pass of omchat_prefill_suffixes, launch_attn_suffix): N sibling rows of p.Sq query tokens each (b-major,
+// p.shr_L = N p.Sq flat query rows, row j valid below p.kv_len[j] - p.Skv) at positions p.Skv .. over the prompt keys [0, p.Skv) of the
+// leader (row 0) and each sibling's own keys from slot p.Skv on.  Workgroups x < p.shr_nsp are the prefix splits: blockIdx.z = chunk of 16
+// FLAT query rows (every row sees every prompt key, so sibling borders do not matter), p.tpw tiles of the leader's keys, bounded by exactly
+// p.Skv.  The others are suffix splits: blockIdx.z = (sibling j, chunk c of its tokens 16 c ..), p.q_pos0 tiles of row j's own keys from
+// slot p.Skv on, causal, bounded by the chunk's last row and by the sibling's length -- no slot >= p.kv_len[j] is loaded.  q is rotated and
+// the caches hold every key (launch_rope_kv in front).  Every split writes its partial (neutral without keys): [flat row][head][nsp + nss].
+template <typename T, int NW, bool EXT = false, bool SHR = false, bool SFX = false>
 __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   typedef typename V8<T>::type frag_t;
   constexpr int PER = 16 / NW;                // row groups of 4 loaded per wave and tile
@@ -2065,13 +2072,30 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
     L = pre ? 0x3fffffff : len - 1;           // the first key that comes from k_new: none in the prefix
     row_off_k = t0 * p.k_sb; row_off_v = t0 * p.v_sb; row_off_new = t0 * p.new_sb;
   }
+  if constexpr (SFX) {
+    const int x = (int)blockIdx.x - p.shr_nsp;
+    if (x < 0) {                              // prefix split: 16 flat rows over the leader's keys below p.Skv
+      t0 = (int)blockIdx.z * 16;
+      if (t0 >= p.shr_L) return;              // uniform (the grid's z covers the suffix chunks, which are at least as many)
+      NT = min(16, p.shr_L - t0);
+      Lt = p.Skv; L = 0x3fffffff;
+    } else {                                  // suffix split: one sibling's chunk over its own keys from slot p.Skv on
+      const int cps = (p.Sq + 15) >> 4, j = (int)blockIdx.z / cps, c16 = ((int)blockIdx.z - j * cps) * 16;
+      t0 = j * p.Sq + c16;
+      NT = min(16, p.Sq - c16);
+      L = p.Skv + c16;
+      Lt = min(L + NT, p.kv_len[j]);          // never beyond the block; a row without own keys (Lt <= p.Skv) leaves the tile loop at once
+      split = p.shr_nsp + x; key_base = p.Skv + x * KV_TILE * p.q_pos0; ntile = p.q_pos0;
+      row_off_k = j * p.k_sb; row_off_v = j * p.v_sb;
+    }
+  }
   const int R = NT * n_rep;
   const bool active = 16 * w < R;             // wave-uniform
   const int r = min(16 * w + fc, R - 1), t = r / n_rep, hh = r - t * n_rep;
   const int qpos = SHR ? (p.kv_len ? p.kv_len[t0 + t] : p.shr_L) - 1 : L + t;
   float* wsb = p.ws + ((size_t)((t0 + t) * p.q_heads + hq0 + hh) * p.nsplit + split) * WS_STRIDE;
   const bool own = active && 16 * w + fc < R;
-  const bool fuse = !EXT && p.rope != nullptr;
+  const bool fuse = !EXT && !SFX && p.rope != nullptr;
   const T* Kg = (const T*)p.K + row_off_k + kvh * p.k_sh;
   const T* Vg = (const T*)p.V + row_off_v + kvh * p.v_sh;
   const T* kn = fuse ? (const T*)p.k_new + row_off_new + kvh * 128 : nullptr;
@@ -2155,8 +2179,9 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
 #pragma unroll
       for (int ds = 0; ds < 4; ++ds) s[kt] = mfma16(kf[ds], qf[ds], s[kt]);
     }
-    const int kbound = SHR ? Lt - 1 : qpos;   // SHR: every column sees every key of the part, so only the part's end bounds it
-    if (SHR ? key0 + KV_TILE > Lt : key0 + KV_TILE > L + 1) {      // the tile holds keys beyond L: causal bound per column (uniform)
+    // SHR: every column sees every key of the part, so only the part's end bounds it.  SFX: the part's end and (suffix splits) the row's position
+    const int kbound = SHR ? Lt - 1 : (SFX ? min(qpos, Lt - 1) : qpos);
+    if (SHR ? key0 + KV_TILE > Lt : (SFX ? key0 + KV_TILE > min(L + 1, Lt) : key0 + KV_TILE > L + 1)) {      // the tile holds keys beyond L: causal bound per column (uniform)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -2373,6 +2398,60 @@ int launch_attn_shared(int dtype, const AttnSharedArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, false, true>), grid, dim3(256), 0, s, p);
     launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, 1, s);
   } else { omchat_set_error("launch_attn_shared: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Suffix-pass attention (omchat_prefill_suffixes): N sibling rows of S query tokens each over the prompt keys [0, P) of
+// the leader (row 0) and each sibling's own keys [P, P + t].  attn_verify_kernel<SFX>, one launch whatever N is: prefix splits over 16-row
+// chunks of the N S flat query rows (about two workgroups per CU, the extend plan's rule), suffix splits per (sibling, 16-token chunk) over
+// at most SFX_SPLITS splits of the S own keys.  Partials [N S][q_heads][nsp + nss], folded by the decode merge.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int SFX_SPLITS = 4;
+static void attn_suffix_plan(int N, int S, int P, int kv_heads, int* tpw, int* nsp, int* tps, int* nss) {
+  const int chunks = cdiv(N * S, 16), tiles = cdiv(P, KV_TILE), stiles = cdiv(S, KV_TILE);
+  const int want = std::max(1, 2 * device_cus() / std::max(1, chunks * kv_heads));
+  *tpw = std::max(1, cdiv(tiles, want));
+  *nsp = cdiv(tiles, *tpw);
+  *tps = std::max(1, cdiv(stiles, SFX_SPLITS));
+  *nss = cdiv(stiles, *tps);
+}
+size_t attn_suffix_ws_bytes(int N, int S, int q_heads, int kv_heads, int P) {
+  if (N < 1 || S < 1 || P < 1 || kv_heads < 1) return 0;
+  int tpw, nsp, tps, nss;
+  attn_suffix_plan(N, S, P, kv_heads, &tpw, &nsp, &tps, &nss);
+  return (size_t)N * S * q_heads * (nsp + nss) * WS_STRIDE * sizeof(float);
+}
+
+int launch_attn_suffix(int dtype, const AttnSuffixArgs& a, hipStream_t s) {
+  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
+  const int n_rep = a.q_heads / a.kv_heads;
+  OM_CHECK(n_rep <= 8, "suffix attention: at most 8 query heads per kv head (16 tokens x n_rep <= 128 query rows per workgroup)");
+  OM_CHECK(a.N >= 1 && a.S >= 1 && a.P >= 1 && a.kv_len, "suffix attention: N >= 1 rows of S >= 1 tokens over P >= 1 prompt keys, and the rows' lengths");
+  OM_CHECK((int64_t)a.N * a.S <= 65535, "suffix attention: more than 65535 query rows");
+  int tpw, nsp, tps, nss;
+  attn_suffix_plan(a.N, a.S, a.P, a.kv_heads, &tpw, &nsp, &tps, &nss);
+  const int nsplit = nsp + nss, rows = a.N * a.S;
+  OM_CHECK(a.ws && a.ws_bytes >= attn_suffix_ws_bytes(a.N, a.S, a.q_heads, a.kv_heads, a.P), "workspace too small");
+  AttnP p{};
+  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
+  p.K = a.K; p.k_sb = a.k_sb; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
+  p.V = a.V; p.v_sb = a.v_sb; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
+  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.S; p.Skv = a.P; p.nsplit = nsplit; p.shr_nsp = nsp; p.shr_L = rows; p.kv_len = a.kv_len;
+  p.q_pos0 = tps;
+  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
+  const bool wide = 16 * n_rep > 64;
+  const dim3 grid(nsplit, a.kv_heads, a.N * cdiv(a.S, 16));
+  if (dtype == OMCHAT_F16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8, false, false, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4, false, false, true>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (f16*)a.O, a.o_sb, a.o_sh, 0, 1, s);
+  } else if (dtype == OMCHAT_BF16) {
+    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8, false, false, true>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, false, false, true>), grid, dim3(256), 0, s, p);
+    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (bf16*)a.O, a.o_sb, a.o_sh, 0, 1, s);
+  } else { omchat_set_error("launch_attn_suffix: bad dtype"); return 1; }
   OM_LAUNCH_CHECK();
   return 0;
 }

@@ -105,6 +105,7 @@ extern "C" int omchat_op_set_tuning(int key, int value) {
   if (key == 48) { attn_set_kv8_fuse(value); return 0; }
   if (key == 49) { model_set_extend_attn(value); return 0; }
   if (key == 50) { model_set_x12_roles(value); return 0; }
+  if (key == 51) { model_set_suffix_attn(value); return 0; }
   if (key == 38) { gemv_set_gu_rr(value); return 0; }
   if (key == 39) { gemv_set_longk_direct(value); return 0; }
   if (key == 40) { norm_set_wave(value); return 0; }
@@ -292,6 +293,46 @@ extern "C" int omchat_op_attn_shared(int dtype, const void* q, void* k, void* v,
   a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
   a.G = G; a.N = N; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
   return launch_attn_shared(dtype, a, S(stream));
+}
+
+// omchat_op_attn_shared with the rows' true lengths (device [G N], each in [P + 1, L]): L only sizes the grid and the workspace
+extern "C" int omchat_op_attn_shared_lens(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L,
+                                          const int* kv_len, float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(q && k && v && out && ws && kv_len, "null argument");
+  OM_CHECK(Hkv > 0 && P >= 1 && L > P && L <= cap, "1 <= P < L <= cap");
+  AttnSharedArgs a{};
+  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
+  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.G = G; a.N = N; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.L = L; a.kv_len = kv_len; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  return launch_attn_shared(dtype, a, S(stream));
+}
+
+extern "C" size_t omchat_op_attn_suffix_ws(int N, int S, int Hq, int Hkv, int P) { return attn_suffix_ws_bytes(N, S, Hq, Hkv, P); }
+
+// Suffix-pass attention: q / out [N, S, Hq, 128] (q rotated), complete caches [N, Hkv, cap, 128], host lengths[N] of the
+// suffixes (1 .. S); kv_len_dev is N ints of device scratch that receive P + lengths[j] for the kernel
+extern "C" int omchat_op_attn_suffix(int dtype, const void* q, const void* k, const void* v, void* out, int N, int S, int Hq, int Hkv, int cap, int P,
+                                     const int32_t* lengths, int* kv_len_dev, float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(q && k && v && out && ws && kv_len_dev, "null argument");
+  OM_CHECK(Hkv > 0 && N >= 1 && S >= 1 && P >= 1 && (int64_t)P + S <= cap, "P + S exceeds the cache capacity");
+  if (lengths) {      // host lengths: checked and uploaded; null = kv_len_dev already holds P + lengths[j] (the kernel clamps them to P + S)
+    std::vector<int> kl(N);
+    for (int j = 0; j < N; ++j) {
+      OM_CHECK(lengths[j] >= 1 && lengths[j] <= S, "suffix attention: lengths must be in [1, S]");
+      kl[j] = P + lengths[j];
+    }
+    OM_HIP(hipMemcpyAsync(kv_len_dev, kl.data(), (size_t)N * 4, hipMemcpyHostToDevice, S(stream)));
+    OM_HIP(hipStreamSynchronize(S(stream)));      // host vector
+  }
+  AttnSuffixArgs a{};
+  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
+  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.N = N; a.S = S; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.kv_len = kv_len_dev; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  return launch_attn_suffix(dtype, a, S(stream));
 }
 
 extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,

@@ -232,6 +232,7 @@ void attn_set_kv8_tpw(int v); // tuning key 47
 void attn_set_kv8_fuse(int v); // tuning key 48
 void model_set_extend_attn(int v); // tuning key 49
 void model_set_x12_roles(int v);   // tuning key 50
+void model_set_suffix_attn(int v); // tuning key 51
 int gemv_x12_default_forms();      // bit per bf16x12 role (1 gate|up, 2 down_proj, 4 lm_head) whose 16-bit launch is in its default form (no tuning key moved it)
 bool attn_decode_kv8_fuses_rope(int batch, int kv_heads, int L, bool masked);
 void attn_set_merge_mid_min(int v);
@@ -345,6 +346,24 @@ struct AttnSharedArgs {
 size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L);
 int launch_attn_shared(int dtype, const AttnSharedArgs& a, hipStream_t s);
 
+// Suffix-pass attention of omchat_prefill_suffixes: N rows of S query tokens each (Q already rotated, b-major), row j valid
+// below kv_len[j] - P.  Query (j, t) sees the keys [0, P) of row 0 (the leader) and the keys [P, P + t] of row j's own cache; no slot >= P of
+// the leader is read through the prefix, no slot < P of a sibling j > 0, no slot >= kv_len[j] of any row.  One attention launch and one
+// merge whatever N is.  Rows t >= kv_len[j] - P are padding: computed from the row's valid keys, finite when the padding q is.
+// q_heads / kv_heads <= 8, N S <= 65535.
+struct AttnSuffixArgs {
+  const void* Q; int64_t q_sb, q_sh;            // [N S, q_heads, 128] (row stride q_sb)
+  const void* K; int64_t k_sb, k_sh, k_sr;      // caches [N rows, kv_heads, cap, 128]
+  const void* V; int64_t v_sb, v_sh, v_sr;
+  void* O; int64_t o_sb, o_sh;                  // [N S, q_heads, 128]
+  int N, S, q_heads, kv_heads, P;
+  const int* kv_len;                            // device [N]: keys row j holds counting its suffix, in [P + 1, P + S]
+  float scale;
+  float* ws; size_t ws_bytes;                   // attn_suffix_ws_bytes(N, S, q_heads, kv_heads, P)
+};
+size_t attn_suffix_ws_bytes(int N, int S, int q_heads, int kv_heads, int P);
+int launch_attn_suffix(int dtype, const AttnSuffixArgs& a, hipStream_t s);
+
 // batch-1 decode on one GPU (fused_decode.hip, round 4): launch_attn_decode + the o_proj GEMV with EPI_RESID as ONE launch, same bits.
 // x [H] is the residual stream (read, x + o_proj(attn) written in place), Wo [H][qd] row-major; ws = fused_decode_ws_bytes(q_heads) bytes
 // of zero-initialised device memory owned by the caller and used by no other launch at the same time; epoch: a value that no earlier launch
@@ -404,6 +423,9 @@ struct RopeArgs {
   // cache slot of row r when it differs from the RoPE position (masked decode of a padded batch: every row appends at the COMMON slot and
   // rotates to its own position, omchat_arch.py:61-70): slot0 + (r % S); -1 = the position itself
   int slot0 = -1;
+  // suffix pass (omchat_prefill_suffixes): device [b] end of each sequence's valid slots; a k / v row whose slot is >= kv_end[row / S] is a
+  // padding row and is not stored (q is still rotated).  null = every row is stored
+  const int* kv_end = nullptr;
 };
 int launch_rope_kv(int dtype, const RopeArgs& a, hipStream_t s);
 

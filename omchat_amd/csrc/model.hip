@@ -1161,9 +1161,24 @@ static bool extend_attn_split(int S, int keep, int kv_heads) {
 }
 extern "C" int omchat_extend_attn_form(int S_new, int keep, int Hkv) { return extend_attn_split(S_new, keep, Hkv) ? 1 : 0; }
 
+// Attention form of omchat_prefill_suffixes.  Over forked rows both the suffix kernel (launch_attn_suffix: the leader's
+// prompt keys once per 16 flat query rows) and the batched prefill kernel with q_pos0 = keep (every row walks its own copy) are correct; over
+// a shared prompt only the first is.  Measured alone with tools/bench_suffix.py (28 / 4 heads, bf16, 3584 prompt keys, 32-token suffixes; LOG.md): the
+// suffix kernel + merge 34 / 59 / 97 us at N = 4 / 8 / 16, the prefill kernel 103 - 104 us at all three (its cdiv(S, 32) kv_heads N workgroups walk
+// every key serially and fit the GPU) -- so the suffix kernel is the default at every N; longer suffixes and N > 16 were not measured.
+int g_suffix_attn = -1;      // omchat_op_set_tuning key 51: attention form of omchat_prefill_suffixes over forked rows: -1 = by the rule, 0 = prefill kernel, 1 = suffix kernel (A/B)
+void model_set_suffix_attn(int v) { g_suffix_attn = v; }
+static bool suffix_attn_kernel(bool shared, int n_rep) {
+  if (shared) return true;
+  if (n_rep > 8) return false;
+  return g_suffix_attn != 0;
+}
+
 // keep > 0 (omchat_prefill_extend, b = 1, right-aligned): the S rows sit at positions keep .. keep + S - 1 on top of keep cached slots
+// sfx (omchat_prefill_suffixes): b sibling rows that each hold keep slots of one prompt (forked copies, or shared: only row 0 holds them);
+// row i's lengths[i] suffix rows sit at positions keep .. on top of them, its padding rows leave the cache alone, and a group stays on
 static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const int32_t* lengths, float* logits_last, void* hidden_out,
-                        void* stream, bool left, int keep = 0) {
+                        void* stream, bool left, int keep = 0, bool sfx = false) {
   OM_CHECK(ctx && embeds && lengths, "null argument");
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
@@ -1177,7 +1192,9 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   const int H = c.t_hidden, It = c.t_mlp, rows = b * S, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
   const bool lead = ctx->tp_rank == 0;
 
-  const bool split_attn = extend_attn_split(S, keep, c.t_kv_heads) && c.t_heads / c.t_kv_heads <= 8;
+  const bool split_attn = !sfx && extend_attn_split(S, keep, c.t_kv_heads) && c.t_heads / c.t_kv_heads <= 8;
+  const bool sfx_attn = sfx && suffix_attn_kernel(ctx->group.on(), c.t_heads / c.t_kv_heads);
+  if (sfx_attn) TRY(ctx->grow(ctx->ext_ws, attn_suffix_ws_bytes(b, S, c.t_heads, c.t_kv_heads, keep)));      // before anything is enqueued
   if (split_attn) TRY(ctx->grow(ctx->ext_ws, attn_extend_ws_bytes(S, c.t_heads, c.t_kv_heads, keep)));      // before anything is enqueued
   std::vector<int> pos(b), len1(b), klen(b), kstart(b);
   // left-padded batch (omchat_arch.py:176-184): row i holds its n_i tokens at [S - n_i, S); the reference drops position_ids
@@ -1221,7 +1238,18 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
       else TRY(gemm(ctx, ctx->tw_xn, H, L.wqkv, H, ctx->tw_qkv, qkvd, rows, qkvd, H, L.bqkv, nullptr, nullptr, 0, EPI_NONE, s));
     }
     RopeArgs r{ctx->tw_qkv, qkvd, rows, S, c.t_heads, c.t_kv_heads, nullptr, keep, ctx->rope, c.max_seq, kc, vc, ctx->cache_sb(), ctx->cache_sh()};
+    if (sfx) r.kv_end = ctx->d_len;      // (keep + lengths[i] at this point)
     TRY(launch_rope_kv(ctx->dt, r, s));
+    if (sfx_attn) {
+      AttnSuffixArgs e{};
+      e.Q = ctx->tw_qkv; e.q_sb = qkvd; e.q_sh = 128;
+      e.K = kc; e.k_sb = ctx->cache_sb(); e.k_sh = ctx->cache_sh(); e.k_sr = 128;
+      e.V = vc; e.v_sb = e.k_sb; e.v_sh = e.k_sh; e.v_sr = 128;
+      e.O = ctx->tw_ao; e.o_sb = qd; e.o_sh = 128;
+      e.N = b; e.S = S; e.q_heads = c.t_heads; e.kv_heads = c.t_kv_heads; e.P = keep; e.kv_len = ctx->d_len; e.scale = 0.08838834764831845f;
+      e.ws = (float*)ctx->ext_ws.p; e.ws_bytes = ctx->ext_ws.cap;
+      TRY(launch_attn_suffix(ctx->dt, e, s));
+    }
     if (split_attn) {      // few new rows over many cached keys: the keys split across workgroups (launch_attn_extend)
       AttnExtendArgs e{};
       e.Q = ctx->tw_qkv; e.q_sb = qkvd; e.q_sh = 128;
@@ -1240,7 +1268,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     a.batch = b; a.q_heads = c.t_heads; a.kv_heads = c.t_kv_heads; a.Sq = S; a.Skv = keep + S; a.kv_len = ctx->d_len; a.causal = 1; a.q_pos0 = keep;
     a.kv_start = left ? ctx->d_start : nullptr;
     a.scale = 0.08838834764831845f;
-    if (!split_attn) TRY(launch_attn_prefill(ctx->dt, a, s));
+    if (!split_attn && !sfx_attn) TRY(launch_attn_prefill(ctx->dt, a, s));
     // left-padded batch: a padded query row sees no key at all; the reference's eager attention (the CPU path) then attends EVERY key of
     // the sequence with weight 1 / S (all scores are finfo.min -> softmax uniform, future keys included), and these rows' K / V in the
     // next layers are what a masked decode step exposes (omchat_arch.py:61-70).  The flash kernel leaves exactly 0 there; fill them.
@@ -1282,7 +1310,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   }
   ctx->kv8_valid = false;
   ctx->beam.end();         // a prefill ends any beam search
-  ctx->group.end();        // ... and the shared-prompt mode of a sampled group
+  if (!sfx) ctx->group.end();        // ... and the shared-prompt mode of a sampled group (the suffix pass runs inside it)
   if (ctx->fp8_kv) {      // fp8 KV cache for the decode steps: quantise what this prefill wrote -- ALL S slots of every row: the masked decode
                           // of a padded batch exposes padded slots too (omchat_arch.py:61-70), and the per-sequence step overwrites them as it appends
     for (int i = 0; i < c.t_layers; ++i) {
@@ -1329,6 +1357,47 @@ extern "C" int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_
   OM_CHECK((int64_t)keep + S_new <= c.max_seq, "prefill_extend: keep + S_new > max_seq");
   const int32_t len = S_new;
   return prefill_impl(ctx, embeds, 1, S_new, &len, logits_last, hidden_out, stream, false, keep);
+}
+
+extern "C" int omchat_suffix_attn_form(int shared, int n_rep) { return suffix_attn_kernel(shared != 0, n_rep) ? 1 : 0; }
+
+extern "C" int omchat_prefill_suffixes(omchat_ctx* ctx, const void* embeds, int N, int S_max, const int32_t* lengths, int keep, float* logits_last,
+                                       void* hidden_out, void* stream) {
+  OM_CHECK(ctx && embeds && lengths, "null argument");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(ctx->tp_size == 1, "prefill_suffixes: tensor-parallel contexts are not implemented (DESIGN.md section 7)");
+  OM_CHECK(!ctx->fp8_kv, "prefill_suffixes: the e4m3 KV cache is not implemented (DESIGN.md section 7): omchat_enable_fp8_kv(ctx, 0)");
+  OM_CHECK(!ctx->fp8_prefill, "prefill_suffixes: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
+  OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "prefill_suffixes: the cache holds a left-padded or masked-decode (padded batch) state");
+  OM_CHECK(!ctx->beam.on(), "prefill_suffixes: a beam search is active");
+  OM_CHECK(N >= 1 && N <= c.max_batch, "prefill_suffixes: N outside [1, max_batch]");
+  OM_CHECK(S_max >= 1, "prefill_suffixes: S_max < 1");
+  for (int j = 0; j < N; ++j) OM_CHECK(lengths[j] >= 1 && lengths[j] <= S_max, "prefill_suffixes: lengths must be in [1, S_max]");
+  OM_CHECK((int64_t)N * S_max <= c.max_prefill_rows, "prefill_suffixes: N * S_max > max_prefill_rows");
+  OM_CHECK((int64_t)N * S_max <= 65535, "prefill_suffixes: N * S_max > 65535 query rows");
+  OM_CHECK(keep >= 1, "prefill_suffixes: keep < 1 (no prompt to share: omchat_prefill)");
+  OM_CHECK((int64_t)keep + S_max <= c.max_seq, "prefill_suffixes: keep + S_max > max_seq");
+  const GroupState& G = ctx->group;
+  OM_CHECK(ctx->pre_b >= 1, "prefill_suffixes: no live state (omchat_prefill with b = 1, then omchat_group_begin(ctx, 1, N, keep, share))");
+  for (int j = 0; j < N; ++j)
+    OM_CHECK(ctx->h_len[j] == keep, "prefill_suffixes: rows 0 .. N - 1 must each hold exactly keep slots (omchat_group_begin(ctx, 1, N, keep, share) first)");
+  OM_CHECK(!G.on() || (G.b == 1 && G.N == N && G.P == keep), "prefill_suffixes: the shared-prompt group is not one prompt of keep slots with N rows");
+  OM_CHECK(!G.on() || c.t_heads / c.t_kv_heads <= 8, "prefill_suffixes: the suffix attention takes at most 8 query heads per kv head (share = 0)");
+  return prefill_impl(ctx, embeds, N, S_max, lengths, logits_last, hidden_out, stream, false, keep, true);
+}
+
+// omchat_kv_read for a cache row other than 0 (tests of the sibling rows of a group)
+extern "C" int omchat_kv_read_row(omchat_ctx* ctx, int row, int layer, int which, int pos0, int n, void* out, void* stream) {
+  OM_CHECK(ctx && out, "null argument");
+  const omchat_config& c = ctx->c;
+  OM_CHECK(row >= 0 && row < c.max_batch && layer >= 0 && layer < c.t_layers && (which == 0 || which == 1) && pos0 >= 0 && n >= 1 && pos0 + n <= c.max_seq,
+           "bad argument");
+  const char* src = (const char*)(which ? ctx->vcache : ctx->kcache) +
+                    ((size_t)layer * ctx->cache_layer_stride() + (size_t)row * ctx->cache_sb() + (size_t)pos0 * 128) * 2;
+  OM_HIP(hipMemcpy2DAsync(out, (size_t)n * 256, src, (size_t)ctx->cache_sh() * 2, (size_t)n * 256, (size_t)c.t_kv_heads, hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+  return 0;
 }
 
 extern "C" int omchat_kv_read(omchat_ctx* ctx, int layer, int which, int pos0, int n, void* out, void* stream) {
@@ -1731,9 +1800,11 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
                               "batch with sum(mask) - 1 and a per-row key mask, omchat_arch.py:61-70; DESIGN.md section 7)");
   OM_CHECK(ctx->dec_mode != 2, "omchat_decode_step after omchat_decode_step_masked on the same prefill: the two place the cache rows differently");
   bool same_len = true;
+  int Lmin = c.max_seq;
   for (int i = 0; i < b; ++i) {
     OM_CHECK(ctx->h_len[i] >= 1, "decode before prefill");
     Lmax = std::max(Lmax, ctx->h_len[i] + 1);
+    Lmin = std::min(Lmin, ctx->h_len[i]);
     same_len = same_len && ctx->h_len[i] == ctx->h_len[0];
   }
   OM_CHECK(Lmax <= c.max_seq, "KV cache full (max_seq)");
@@ -1741,7 +1812,8 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   GroupState& G = ctx->group;
   const bool grp = G.on();
   if (grp) {
-    OM_CHECK(b == G.b * G.N && same_len, "a sampled group shares its prompt: a step takes all its b * N rows, of one length (omchat_group_begin with b = 0 first)");
+    // the rows may differ in length (omchat_prefill_suffixes): the shared attention reads each row's own length from the device
+    OM_CHECK(b == G.b * G.N && Lmin >= G.P, "a sampled group shares its prompt: a step takes all its b * N rows, none shorter than the prompt (omchat_group_begin with b = 0 first)");
     OM_CHECK(ctx->tp_size == 1 && !(ctx->fp8_kv && ctx->kv8_valid), "shared-prompt mode: one GPU, 16-bit KV cache");
     // the suffix grid in buckets of 256 keys: eager and captured steps issue the same launches, and a graph lasts 256 steps
     Lmax = std::min(c.max_seq, G.P + (Lmax - G.P + 255) / 256 * 256);

@@ -76,6 +76,7 @@ class Engine:
         self._ext_st = dict(kept_slots=0, prefilled_rows=0, tiles_encoded=0, tiles_reused=0)
         self._lp_max_new, self._logprobs_on, self._lp_extras = 0, False, (0, 0)      # set_logprobs
         self._enc_st = dict(calls=0, tiles=0)               # encode_images
+        self._sfx_st = dict(tiles_encoded=0, prompt_rows=0, suffix_rows=0, shared=False)      # generate(suffixes=...)
 
     def close(self):
         if getattr(self, "h", None):
@@ -345,6 +346,41 @@ class Engine:
         torch = _torch()
         out = torch.empty(self.c.t_kv_heads, n, 128, dtype=self.torch_dtype, device=self.device)
         check(self.lib.omchat_kv_read(self.h, int(layer), int(which), int(pos0), int(n), ptr(out), cur_stream()))
+        return out
+
+    def prefill_suffixes(self, embeds, lengths, keep, want_hidden=False, want_logits=True):
+        """N suffixes over one prefilled prompt (include/omchat_hip.h: omchat_prefill_suffixes): rows 0 .. N - 1 each
+        hold `keep` slots of the prompt (group_begin(1, N, keep, share) first; N == 1: the b = 1 state itself).  embeds [N, S_max, H], row j
+        valid in [0, lengths[j]).  -> (logits fp32 [N, V] of every row's last valid position, hidden [N, S_max, H] or None)"""
+        torch = _torch()
+        e = embeds.to(device=self.device, dtype=self.torch_dtype).contiguous()
+        if e.dim() != 3 or len(lengths) != e.shape[0]:
+            raise ValueError("prefill_suffixes: embeds [N, S_max, H] and N lengths")
+        N, S, _ = e.shape
+        lens = torch.tensor([int(x) for x in lengths], dtype=torch.int32)
+        logits = torch.empty(N, self.c.t_vocab, dtype=torch.float32, device=self.device) if want_logits else None
+        hidden = torch.empty(N, S, self.cfg.text["hidden_size"], dtype=self.torch_dtype, device=self.device) if want_hidden else None
+        check(self.lib.omchat_prefill_suffixes(self.h, ptr(e), N, S, ptr(lens), int(keep), ptr(logits), ptr(hidden), cur_stream()))
+        self._prefix = None      # the rows are siblings now, not one conversation
+        return logits, hidden
+
+    def suffix_attn_form(self, shared):
+        """1 = prefill_suffixes takes the suffix attention kernel, 0 = the batched prefill kernel with q_pos0 = keep (forked rows only)"""
+        return int(self.lib.omchat_suffix_attn_form(int(bool(shared)), self.c.t_heads // max(1, self.c.t_kv_heads)))
+
+    def kv_read_row(self, row, layer, which, pos0, n):
+        """test hook: kv_read for cache row `row` (the sibling rows of a group)"""
+        torch = _torch()
+        out = torch.empty(self.c.t_kv_heads, n, 128, dtype=self.torch_dtype, device=self.device)
+        check(self.lib.omchat_kv_read_row(self.h, int(row), int(layer), int(which), int(pos0), int(n), ptr(out), cur_stream()))
+        return out
+
+    def suffix_stats(self, reset=False):
+        """the last generate(suffixes=...) / score(suffixes=...) call: tiles run through the tower, prompt rows prefilled (once), suffix rows
+        prefilled (the sum of the suffix lengths) and whether the rows share the prompt's slots"""
+        out = dict(self._sfx_st)
+        if reset:
+            self._sfx_st = dict(tiles_encoded=0, prompt_rows=0, suffix_rows=0, shared=False)
         return out
 
     def extend_stats(self, reset=False):

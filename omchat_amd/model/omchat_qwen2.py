@@ -237,13 +237,22 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
 
     __call__ = forward
 
-    def score(self, input_ids, images=None, attention_mask=None, labels=None):
+    def score(self, input_ids, images=None, attention_mask=None, labels=None, suffixes=None, share_prompt=None):
         """Teacher-forced scoring of given text: forward(labels=...) with labels = input_ids by default -- the image
         placeholders drop out in the splice, so every text token but a row's first is scored.  -> dict: `loss` (fp32 scalar, mean negative
         log-probability of the scored tokens), `token_logprobs` fp32 [b, S] and `labels` int64 [b, S] as forward(labels=...) returns them,
         `sequence_logprobs` fp32 [b] (sum over a row's scored tokens), `num_tokens` int64 [b] and `perplexity` fp32 [b] =
         exp(-sequence_logprobs / num_tokens) (NaN for a row without scored tokens); all but `labels` on the device.  One host
-        synchronisation, at the end."""
+        synchronisation, at the end.
+        suffixes=[ids_0, ..., ids_{N-1}]: multiple-choice scoring of N candidate continuations of ONE prompt
+        (input_ids [1, T]).  The tower and the prompt's prefill run once, the N suffixes go through the decoder in one pass.  -> dict over the
+        SUFFIX tokens only: `token_logprobs` fp32 [N, S_max] (0 behind a row's end), `sequence_logprobs` fp32 [N], `num_tokens` int64 [N],
+        `perplexity` fp32 [N]; row j's numbers are those of score() on input_ids[0] + suffixes[j] restricted to the suffix, to rounding.
+        share_prompt and the refusals are generate(suffixes=)'s; `labels` cannot be combined with it."""
+        if suffixes is not None:
+            if labels is not None:
+                raise ValueError("score(suffixes=...) scores the suffix tokens themselves: `labels` cannot be combined with it")
+            return self._score_suffixes(input_ids, images, attention_mask, suffixes, share_prompt)
         out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, labels=input_ids if labels is None else labels)
         n = out.num_tokens
         res = dict(loss=out.loss, token_logprobs=out.token_logprobs, labels=out.labels, sequence_logprobs=out.sequence_logprobs,
@@ -357,7 +366,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
                  repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
                  num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, output_logprobs=None, share_prompt=None,
-                 top_logprobs=None, score_token_ids=None, **kwargs):
+                 top_logprobs=None, score_token_ids=None, suffixes=None, **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
@@ -394,7 +403,25 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         samples with its own row key from the first token on.  share_prompt: False = the prompt's cache slots are forked into the N rows and
         the plain batched step runs; True = the rows of a prompt share its slots and the decode step's attention reads them once per prompt
         (16-bit KV cache, one GPU, N <= 16; NotImplementedError otherwise); None = the engine's rule (Engine.group_share_default).  Refused:
-        padded or ragged batches, reuse_cache=True, prompt_lookup_num_tokens and a streamer when b * N > 1."""
+        padded or ragged batches, reuse_cache=True, prompt_lookup_num_tokens and a streamer when b * N > 1.
+        suffixes=[ids_0, ..., ids_{N-1}] with input_ids [1, T]: one prompt, N >= 1 text-id suffixes of any lengths
+        S_j >= 1 (lists or 1-D tensors).  Row j stands for the sequence input_ids[0] + suffixes[j], and its result is that of generate() on
+        that concatenated prompt alone at b = 1 -- no pads in the cache, positions 0 .. P + S_j - 1, the image tiles seen by every row -- to
+        rounding (ids can differ at near-ties only, as under reuse_cache).  This is NOT what HF computes for the same rows as a padded
+        batch (pads in the cache, positions from the mask arithmetic): rows that only differ in their question want the b = 1 result.  The
+        tower, the splice and the prompt's prefill run ONCE, the N suffixes are prefilled in one pass over the weights
+        (Engine.prefill_suffixes), then the ordinary decode loop runs over N rows of different lengths.  Returns [N, new]: the generated
+        ids only (the rows have no common prompt length), the pad id behind a row's EOS; with return_dict_in_generate=True that is
+        .sequences and the log-prob fields keep their [N, new, ...] shapes.  Greedy and do_sample=True (row j samples with the key of row
+        j; the repetition penalty's seen set and the ban history of row j are prompt + suffix_j), all sampling parameters and filters, the
+        token-banning arguments, output_logprobs / top_logprobs / score_token_ids, the decode graph and MXFP4 decode.  stopping_criteria are
+        handed the per-row full sequences prompt + suffix_j + generated_j, right-padded with the pad id (0 without one) to the longest row.
+        share_prompt as for sampled groups: False = the prompt's slots are forked into the N rows, True = shared (16-bit cache, one GPU,
+        N <= 16, N * n_rep <= 128; NotImplementedError otherwise), None = Engine.group_share_default.  Refused from host data, before
+        anything is enqueued: input_ids of more than one row, an attention_mask with zeros, an empty list or suffix, an id < 0 or >= the
+        vocabulary, N > max_batch, N * max S_j > max_prefill_rows, num_beams > 1, num_return_sequences > 1, prompt_lookup_num_tokens,
+        reuse_cache=True, a streamer when N > 1, the e4m3 KV cache / fp8 prefill GEMMs / tensor parallelism (NotImplementedError); and
+        P + max S_j + 1 > max_seq right after the splice plan, before the tower runs."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -407,8 +434,11 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             if getattr(self.engine, "_fp8_kv", False) or getattr(self.engine, "_fp8_prefill", False) or self.engine.tp_size > 1:
                 raise NotImplementedError("reuse_cache=True with the e4m3 KV cache, fp8 x fp8 prefill GEMMs or tensor parallelism is not "
                                           "implemented (DESIGN.md section 7)")
+        sfx = None
+        if suffixes is not None:      # every refusal that host data decides, before any work (and before the other modes' own refusals)
+            sfx = self._suffix_params(input_ids, images, attention_mask, suffixes, nb, num_return_sequences, share_prompt, reuse, kwargs, streamer)
         lookup = self._lookup_params(input_ids, kwargs, do_sample, nb)
-        group = self._group_params(input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer)
+        group = None if sfx is not None else self._group_params(input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer)
         olp = bool(output_logprobs if output_logprobs is not None else getattr(gc, "output_logprobs", False))
         top_n, score_ids = resolve_logprob_extras(gc, olp, top_logprobs, score_token_ids, self.engine.c.t_vocab_total)
         if olp:      # every refusal before any work
@@ -443,10 +473,17 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         eos = set(eos) if isinstance(eos, (list, tuple)) else ({eos} if eos is not None else set())
         pad = pad_token_id if pad_token_id is not None else self.generation_config.pad_token_id
         b = input_ids.shape[0]
+        hist = None      # generate(suffixes=): row j's history, prompt + suffix_j
+        if sfx is not None:
+            from ..suffix import histories, padded_sequences
+            hist = histories(input_ids[0].tolist(), sfx[0])
         if streamer is not None:
-            streamer.put(input_ids.cpu())
+            streamer.put(input_ids.cpu() if hist is None else torch.tensor(hist, dtype=torch.int64))      # (a streamer: N == 1)
         prompt_slots = None
-        if reuse:
+        if sfx is not None:
+            out = self._forward_suffixes(input_ids, images, attention_mask, sfx[0], sfx[1])
+            b = len(sfx[0])
+        elif reuse:
             out, prompt_slots = self._forward_reuse(input_ids, images)
         else:
             out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
@@ -470,11 +507,11 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             b = b * N
         if con is not None:
             # the history HF's processors see: the prompt rows as passed (-200 sentinels and pads included) + the ids every step is fed
-            self.engine.set_constraints(b, input_ids.tolist(), max_new_tokens, **con)
+            self.engine.set_constraints(b, input_ids.tolist() if hist is None else hist, max_new_tokens, **con)
         if olp:
             self.engine.set_logprobs(b, max_new_tokens, top_n, score_ids)      # the prefill's pick below is record 0
         if smp is not None:
-            seen = [[int(i) for i in row if int(i) >= 0] for row in input_ids.tolist()]
+            seen = [[int(i) for i in row if int(i) >= 0] for row in (input_ids.tolist() if hist is None else hist)]
             self.engine.set_sampling(b, seen=seen, **smp)
             tok = self.engine.sample(local_logits)
         else:
@@ -541,7 +578,10 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             done = done | torch.tensor([int(x) in eos for x in t_cpu])
             stop = bool(done.all()) or last
             if not stop and stopping_criteria:                        # HF StoppingCriteriaList semantics: any criterion stops the batch
-                so_far = torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+                if hist is None:
+                    so_far = torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+                else:
+                    so_far = torch.tensor(padded_sequences(input_ids[0].tolist(), sfx[0], torch.stack(new, dim=1).tolist(), pad), dtype=torch.int64)
                 stop = any(bool(c(so_far, None)) for c in stopping_criteria)
             if stop:
                 if ahead is not None:
@@ -551,7 +591,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if streamer is not None:
             streamer.end()
         self._record_prefix(prompt_slots, [int(t[0]) for t in new])
-        seqs = torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1)
+        seqs = torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1) if hist is None else torch.stack(new, dim=1)
         if not olp:
             return seqs
         # the step enqueued ahead was taken back with its record: exactly one record per generated token
@@ -612,6 +652,70 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             if why is not None:
                 raise NotImplementedError(f"share_prompt=True is not available here ({why}): use share_prompt=False (DESIGN.md section 7)")
         return N, (None if share_prompt is None else bool(share_prompt))
+
+    def _suffix_params(self, input_ids, images, attention_mask, suffixes, nb, num_return_sequences, share_prompt, reuse, kwargs, streamer):
+        """(suffix id lists, share_prompt) of generate(suffixes=...); every refusal that host data decides is raised here, each with its own
+        message, before any work is enqueued (omchat_amd/suffix.py: check_suffix_args); last the room in the cache, which needs the splice
+        plan (host integers) for the prompt's slot count -- before the tower runs and before any sticky state of the engine changes"""
+        from ..suffix import check_suffix_args, check_room
+        gc = self.generation_config
+        e = self.engine
+        nret = num_return_sequences if num_return_sequences is not None else (getattr(gc, "num_return_sequences", None) or 1)
+        k = kwargs.get("prompt_lookup_num_tokens", None)
+        k = k if k is not None else getattr(gc, "prompt_lookup_num_tokens", None)
+        rows = check_suffix_args(input_ids.shape[0], attention_mask is not None and bool((attention_mask == 0).any()), suffixes, e.c.t_vocab_total,
+                                 e.c.max_batch, e.c.max_prefill_rows, nb, int(nret), k is not None, reuse, streamer is not None,
+                                 vars(e).get("_fp8_kv", False), vars(e).get("_fp8_prefill", False), e.tp_size, e.c.t_heads, e.c.t_kv_heads, share_prompt)
+        check_room(self._spliced_lengths(input_ids.detach().cpu(), images)[0], rows, e.c.max_seq)
+        return rows, (None if share_prompt is None else bool(share_prompt))
+
+    def _forward_suffixes(self, input_ids, images, attention_mask, rows, share, want_hidden=False):
+        """The prefill of generate(suffixes=...) / score(suffixes=...) (the arguments went through _suffix_params): the prompt's forward at b = 1, the fork / share of its slots among the N rows and the suffix pass.  -> forward()'s output with the N rows' last
+        logits (`local_logits` [N, V]); with want_hidden also `.prompt_hidden` [1, P, H] and `.suffix_hidden` [N, S_max, H]"""
+        from .. import _lib
+        from ..suffix import check_room, share_refusal, suffix_token_table
+        e = self.engine
+        N, lens = len(rows), [len(r) for r in rows]
+        tiles0 = e.encode_stats()["tiles"]
+        out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True, output_hidden_states=want_hidden)
+        P = e.kv_lengths(1)[0]
+        check_room(P, rows, e.c.max_seq)
+        if share is None:
+            share = N > 1 and e.group_share_default(N, P) and share_refusal(False, 1, e.c.t_heads, e.c.t_kv_heads, N) is None
+        share = bool(share) and N > 1                 # one row shares with nobody: the b = 1 state is the state
+        if N > 1:
+            e.group_begin(1, N, P, share)
+        idx = torch.tensor(suffix_token_table(rows, _lib.PAD_ROW), dtype=torch.int32).view(-1)
+        emb = e.gather_rows(idx, None).view(N, max(lens), -1)
+        logits, hidden = e.prefill_suffixes(emb, lens, P, want_hidden=want_hidden)
+        e._sfx_st = dict(tiles_encoded=e.encode_stats()["tiles"] - tiles0, prompt_rows=P, suffix_rows=sum(lens), shared=share)
+        self._padded_batch = False
+        res = CausalLMOutputWithPast(e.full_logits(logits).unsqueeze(1), KVHandle(e, N))
+        res.local_logits = logits
+        if want_hidden:
+            res.prompt_hidden, res.suffix_hidden = out.hidden_states[0], hidden
+        return res
+
+    def _score_suffixes(self, input_ids, images, attention_mask, suffixes, share_prompt):
+        """score(suffixes=...): token 0 of every suffix from the prompt's last position, tokens 1 .. S_j - 1 from the suffix pass's hidden
+        rows, both through omchat_score_hidden; no [N, S, V] tensor exists"""
+        from ..suffix import score_labels
+        e = self.engine
+        rows, share = self._suffix_params(input_ids, images, attention_mask, suffixes, 1, 1, share_prompt, False, {}, None)
+        out = self._forward_suffixes(input_ids, images, attention_mask, rows, share, want_hidden=True)
+        N, S_max = len(rows), max(len(r) for r in rows)
+        first, lab = score_labels(rows)
+        last = out.prompt_hidden[:, -1:, :].expand(N, 1, -1).contiguous()
+        lp0, _, _, _ = e.score_hidden(last, torch.tensor(first, dtype=torch.int64).view(N, 1))
+        lp, _, _, _ = e.score_hidden(out.suffix_hidden, torch.tensor(lab, dtype=torch.int64))
+        tl = torch.cat([lp0, lp[:, :S_max - 1]], dim=1)
+        n = torch.tensor([len(r) for r in rows], dtype=torch.int64, device=tl.device)
+        seq = tl.sum(dim=1)
+        if N > 1:
+            e.group_end()
+        res = dict(token_logprobs=tl, sequence_logprobs=seq, num_tokens=n, perplexity=torch.exp(-seq / n))
+        torch.cuda.current_stream().synchronize()
+        return res
 
     def _forward_reuse(self, input_ids, images):
         """The prefill of generate(reuse_cache=True), b = 1: keeps the slots of sequence 0's cache that the new prompt shares with the
