@@ -204,6 +204,34 @@ int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngram_size, int
                            const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
                            const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
                            const int32_t* prompt_len, int max_new, void* stream);
+/* ---- finite-state token constraints (generate(token_fsm=)) ----------------------------------------------------------- */
+/* A token FSM has n_states states; state s owns the edges off[s] .. off[s + 1] - 1 of tok / nxt (host int32; CSR), sorted by token without
+ * duplicates, every tok in [0, t_vocab_total), every nxt in [0, n_states).  The tokens of a state's edges are the ids allowed there; EOS ids are
+ * ordinary tokens.  One extra state, OMCHAT_FSM_DEAD: a row goes there when the token it is fed has no edge from its state (the pad fed to an
+ * ended row, an EOS without an edge), and in it the logits pass through unmasked -- no row is ever all -inf.
+ * The caps keep every index in int32.  A table costs (n_states + 1 + 2 E) * 4 bytes of device memory, every rank holding all of it: 4 MiB of
+ * offsets and 512 MiB of edges at the caps; 1.2 MB for one state with an edge for every id of a 152 064-id vocabulary. */
+#define OMCHAT_FSM_MAX_STATES (1 << 20)
+#define OMCHAT_FSM_MAX_EDGES (1 << 26)
+#define OMCHAT_FSM_DEAD (-1)
+/* omchat_fsm_load: validates and uploads a table; it stays until it is replaced or unloaded (n_states = 0, which also switches the stage off)
+ * and counts in omchat_device_bytes.  Refused, with nothing changed: a table above the caps, unsorted or duplicate tokens, ids or targets
+ * out of range, a state that some edge leads to and that has no edge (the message names it; add an EOS edge), a beam search in progress.  A
+ * load drops the captured decode graphs and switches the stage off: omchat_fsm_begin follows.  Synchronises. */
+int omchat_fsm_load(omchat_ctx* ctx, int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, void* stream);
+/* omchat_fsm_begin: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both masked
+ * steps, the captured decode graph -- first advances the row's state over the token the decode step is fed (not at the first pick after the
+ * prefill), then runs on the context-owned copy of the logits with every id that is no edge of the row's state at -inf (behind the bans of
+ * omchat_set_constraints when both are on); logits handed in or returned stay raw.  A decode step that picks nothing only advances.
+ * start_states host int32 [b], each in range and with an edge; max_new: the most decode steps that will follow (a step beyond it is refused
+ * before it is enqueued).  The rows' states are kept as a trail of max_batch * (max_new + 1) * 4 bytes, grown on demand, never shrunk,
+ * counted in omchat_device_bytes; omchat_kv_rewind takes the states back with the slots.  b = 0 switches the stage off: no launch, no graph
+ * node remains.  Sticky like the sampler and the constraints.  Refused: no table, a beam search in progress; omchat_decode_verify and
+ * omchat_beam_begin refuse while it is on.  Switching on or off, another b or a trail that had to grow drops the captured decode graphs.
+ * Synchronises. */
+int omchat_fsm_begin(omchat_ctx* ctx, int b, const int32_t* start_states, int max_new, void* stream);
+/* the current states of rows 0..b-1 (host int32 [b]; OMCHAT_FSM_DEAD included).  Synchronises the device. */
+int omchat_fsm_states(omchat_ctx* ctx, int b, int32_t* out, void* stream);
 /* ---- per-token log-probabilities of the picked ids (generate(output_logprobs=True)) ---------------------------------- */
 /* omchat_set_logprobs: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both
  * masked steps, the captured decode graph -- also records two fp32 numbers on the device, without a host sync: raw = log_softmax(logits)[id]
@@ -754,6 +782,12 @@ int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_len, const 
                         int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* eos_ids, int n_eos, const int32_t* suppress_ids,
                         int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress, const int32_t* bad_word_ids,
                         const int32_t* bad_word_offsets, int n_bad_words, uint32_t* ban_out, void* stream);
+/* context-free mark + apply passes of omchat_fsm_begin (test hook): a table as omchat_fsm_load takes it (validated the same way), states host
+ * int32 [b] (OMCHAT_FSM_DEAD allowed), fed host int32 [b] = the global ids a decode step is fed, or NULL (no advance); logits device fp32
+ * [b][V] = the vocabulary slice of `rank` out of V_total (left as they are).  out device fp32 [b][V] = the masked copy, new_states host
+ * int32 [b] = the rows' states after the advance.  Synchronises. */
+int omchat_op_fsm(int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, const int32_t* states, const int32_t* fed, int b, int V,
+                  int V_total, int rank, const float* logits, float* out, int32_t* new_states, void* stream);
 
 /* context-free sampler over logits fp32 [b, V] with the parameters of omchat_set_sampling; every row at step `step`.  thr_out (device uint32 [b]
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */

@@ -55,6 +55,10 @@ _SIGS = {
     "omchat_set_sampling_filters": (_i, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "omchat_sample": (_i, [_vp, _vp, _i, _vp, _vp]),
     "omchat_set_constraints": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "omchat_fsm_load": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "omchat_fsm_begin": (_i, [_vp, _i, _vp, _i, _vp]),
+    "omchat_fsm_states": (_i, [_vp, _i, _vp, _vp]),
+    "omchat_op_fsm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
     "omchat_set_logprobs": (_i, [_vp, _i, _i, _vp]),

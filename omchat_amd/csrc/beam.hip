@@ -428,6 +428,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_CHECK(b >= 1 && N >= 2 && N <= BEAM_NMAX, "beam search: b >= 1 and 2 <= num_beams <= 16");
   OM_CHECK(!ctx->pick.constraints_on(), "beam search: constraints are on (omchat_set_constraints with b = 0 first); HF applies them to log-softmax scores there");
   OM_CHECK(!ctx->pick.logprobs_on(), "beam search: logprobs are on (omchat_set_logprobs with b = 0 first); a beam search reports sequences_scores");
+  OM_CHECK(!ctx->pick.fsm_on(), "beam search: a token FSM is on (omchat_fsm_begin with b = 0 first); each beam row would need its parent's state");
   OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
   OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
   const int KB = std::max(2, 1 + n_eos) * N;

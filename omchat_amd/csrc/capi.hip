@@ -693,6 +693,63 @@ extern "C" int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_
   return rc;
 }
 
+static_assert(FSM_MAX_STATES == OMCHAT_FSM_MAX_STATES && FSM_MAX_EDGES == OMCHAT_FSM_MAX_EDGES && FSM_DEAD == OMCHAT_FSM_DEAD, "token FSM caps: kernels.h and omchat_hip.h");
+
+extern "C" int omchat_op_fsm(int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, const int32_t* states, const int32_t* fed,
+                             int b, int V, int V_total, int rank, const float* logits, float* out, int32_t* new_states, void* stream) {
+  OM_CHECK(states && logits && out && new_states && b >= 1 && V >= 1 && V_total >= V && rank >= 0 && (int64_t)(rank + 1) * V <= V_total, "bad argument");
+  if (int rc = fsm_validate(n_states, off, tok, nxt, V_total)) return rc;
+  for (int i = 0; i < b; ++i) {
+    OM_CHECK(states[i] == FSM_DEAD || (states[i] >= 0 && states[i] < n_states), "state outside the table");
+    OM_CHECK(states[i] == FSM_DEAD || off[states[i] + 1] > off[states[i]], "state without an edge: every id would be -inf; add an EOS edge");
+  }
+  const size_t E = (size_t)off[n_states];
+  const size_t n_off = ((size_t)n_states + 1 + 3) / 4 * 4, n_tok = (E + 3) / 4 * 4 + 4, rb = ((size_t)b + 3) / 4 * 4;
+  const int bmw = (V + 31) / 32;
+  // the rows as the context keeps them: a trail of two slots, the given state in slot 0
+  std::vector<int32_t> trail((size_t)b * 2, 0);
+  for (int i = 0; i < b; ++i) trail[(size_t)i * 2] = states[i];
+  hipStream_t s = S(stream);
+  int32_t* mem = nullptr;
+  const size_t words = n_off + n_tok + E + 4 + 2 * rb + 3 * rb + (size_t)b * bmw;
+  OM_HIP(hipMalloc(&mem, words * 4));
+  int32_t* d_off = mem;
+  int32_t* d_tok = mem + n_off;
+  int32_t* d_nxt = d_tok + n_tok;
+  int32_t* d_trail = d_nxt + E + 4;
+  int32_t* d_cnt = d_trail + 2 * rb;
+  int32_t* d_cur = d_cnt + rb;
+  int32_t* d_fed = d_cur + rb;
+  uint32_t* d_bm = (uint32_t*)(d_fed + rb);
+  hipMemsetAsync(mem, 0, words * 4, s);
+  hipMemcpyAsync(d_off, off, ((size_t)n_states + 1) * 4, hipMemcpyHostToDevice, s);
+  if (E) {
+    hipMemcpyAsync(d_tok, tok, E * 4, hipMemcpyHostToDevice, s);
+    hipMemcpyAsync(d_nxt, nxt, E * 4, hipMemcpyHostToDevice, s);
+  }
+  hipMemcpyAsync(d_trail, trail.data(), trail.size() * 4, hipMemcpyHostToDevice, s);
+  if (fed) hipMemcpyAsync(d_fed, fed, (size_t)b * 4, hipMemcpyHostToDevice, s);
+  FsmTable T;
+  T.off = d_off; T.tok = d_tok; T.nxt = d_nxt; T.n_states = n_states;
+  FsmArgs a;
+  a.trail = d_trail; a.cap = 2; a.cnt = d_cnt; a.cur = d_cur; a.fed = fed ? d_fed : nullptr;
+  a.b = b; a.V = V; a.gbase = rank * V; a.bm = d_bm; a.bmw = bmw;
+  int rc = launch_fsm_mark(T, a, s);
+  if (!rc) rc = launch_fsm_apply(logits, V, a, out, fed != nullptr, s);
+  // the states as omchat_fsm_states reads them: trail[cnt]
+  std::vector<int32_t> cnt(b, 0);
+  if (!rc && hipMemcpyAsync(cnt.data(), d_cnt, (size_t)b * 4, hipMemcpyDeviceToHost, s) != hipSuccess) rc = 2;
+  if (!rc && hipMemcpyAsync(trail.data(), d_trail, trail.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess) rc = 2;
+  hipStreamSynchronize(s);
+  hipFree(mem);
+  if (!rc)
+    for (int i = 0; i < b; ++i) {
+      OM_CHECK(cnt[i] == (fed ? 1 : 0), "omchat_op_fsm: the count did not follow the fed token");
+      new_states[i] = trail[(size_t)i * 2 + cnt[i]];
+    }
+  return rc;
+}
+
 extern "C" size_t omchat_beam_state_words(int b, int N, int max_new) { return beam_state_words(b, N, max_new); }
 
 extern "C" int omchat_op_beam_select(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty,

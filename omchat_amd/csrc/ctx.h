@@ -94,10 +94,24 @@ struct PickState {
   float* lp_table = nullptr;
   Grown con_hist;    // token history of the logits constraints (omchat_set_constraints)
   Grown lp_rec;      // record of the per-token log-probabilities (omchat_set_logprobs)
+  // finite-state token constraints (omchat_fsm_load / omchat_fsm_begin; fsm.hip): the table [off | tok | nxt] in one buffer, sticky until
+  // replaced; the rows' state trail [max_batch][fsm_cap] with device counts, the state of the current pick, the allowed bitmap of this
+  // rank's vocabulary slice (all-zero between picks).  The masked copy is con_logits, shared with the ban stage (allocated by whichever
+  // setter comes first).  fsm_fed: decode steps fed since the begin (host bound for the trail's room)
+  struct Fsm { bool on = false; int b = 0, max_new = 0; };
+  Fsm fsm;
+  FsmTable fsm_tab;
+  std::vector<int32_t> fsm_off_host;      // the table's offsets on the host: the begin checks that a start state has an edge
+  Grown fsm_mem, fsm_trail;
+  int fsm_cap = 0, fsm_fed = 0;
+  int *fsm_cnt = nullptr;
+  int32_t* fsm_cur = nullptr;
+  uint32_t* fsm_bm = nullptr; int fsm_bmw = 0;
   bool sampling_on() const { return smp.on; }
   bool constraints_on() const { return con.on; }
   bool logprobs_on() const { return lp.on; }
-  void release() { con_hist.release(); lp_rec.release(); lp_xrec.release(); }
+  bool fsm_on() const { return fsm.on; }
+  void release() { con_hist.release(); lp_rec.release(); lp_xrec.release(); fsm_mem.release(); fsm_trail.release(); }
 };
 
 // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand

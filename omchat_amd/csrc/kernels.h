@@ -565,6 +565,26 @@ int launch_constrain_rewind(int* len, const int* plen, int b, int n, hipStream_t
 int constrain_pack_lists(const int32_t* eos, int n_eos, const int32_t* sup, int n_sup, const int32_t* bsup, int n_bsup, const int32_t* bw_ids,
                          const int32_t* bw_off, int n_bw, int32_t* out, ConstrainArgs& a);      // out: [CON_LIST_WORDS], host
 void constrain_bind_lists(const int32_t* d_lists, ConstrainArgs& a);
+// finite-state token constraints (fsm.hip; tests/fsm_ref.py restates them).  The caps are the public header's
+// OMCHAT_FSM_* (capi.hip asserts they agree): every index of the table stays in int32.
+constexpr int FSM_MAX_STATES = 1 << 20, FSM_MAX_EDGES = 1 << 26, FSM_DEAD = -1;
+struct FsmTable {      // CSR in device memory; tok 16-byte aligned and allocated up to a multiple of four ids behind the last edge
+  const int32_t* off = nullptr; const int32_t* tok = nullptr; const int32_t* nxt = nullptr; int n_states = 0;
+};
+struct FsmArgs {
+  int32_t* trail = nullptr; int cap = 0;          // [b][cap] the row's state after k fed tokens at trail[row][k]
+  int* cnt = nullptr;                             // [b] fed tokens so far
+  int32_t* cur = nullptr;                         // [b] the state this pick masks with (written by the mark pass, read by the apply pass)
+  const int32_t* fed = nullptr;                   // [b] the token the decode step is fed, or NULL (first pick after the prefill: no advance)
+  int b = 0, V = 0, gbase = 0;                    // rank-local slice [gbase, gbase + V)
+  uint32_t* bm = nullptr; int bmw = 0;            // [b][bmw] allowed bitmap, all-zero on entry and again behind the apply pass
+};
+int launch_fsm_mark(const FsmTable& T, const FsmArgs& a, hipStream_t s);
+// out [b][V] = logits with the ids whose bit is clear at -inf (DEAD rows pass through; logits == out allowed); clears the bitmap; advance: cnt += 1
+int launch_fsm_apply(const float* logits, int ld, const FsmArgs& a, float* out, bool advance, hipStream_t s);
+int launch_fsm_advance(const FsmTable& T, const FsmArgs& a, hipStream_t s);      // a step that picks nothing: trail and cnt move, no mask
+int launch_fsm_rewind(int* cnt, int b, int n, hipStream_t s);                    // cnt = max(cnt - n, 0)
+int fsm_validate(int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, int V_total);      // host arrays; sets the error
 // beam search (beam.hip; tests/beam_ref.py restates it).  The vocabulary is cut into beam_slices(V, tp) equal slices
 // of at most BEAM_SLICE_CAP ids, the same at every TP degree; a rank owns ns / tp whole slices.  Exchange table: [rows][ns][4 + 2K] fp32.
 constexpr int BEAM_KMAX = 32;            // candidates kept per step and prompt: max(2, 1 + n_eos) * N

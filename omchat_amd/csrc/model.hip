@@ -1877,6 +1877,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   const char* why = pick_verify_refusal(ctx, flags);
   OM_CHECK(!why, why);
   OM_CHECK(!ctx->pick.constraints_on(), "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
+  OM_CHECK(!ctx->pick.fsm_on(), "a token FSM is on: each verify row would need its own state (omchat_fsm_begin with b = 0 first)");
   OM_CHECK(!ctx->beam.on(), "a beam search is active");
   OM_CHECK(!ctx->group.on(), "a sampled group shares its prompt: a verify step runs one sequence (omchat_group_begin with b = 0 first)");
   OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");

@@ -1,5 +1,5 @@
-// The token pick of a step, with its state (PickState, ctx.h): the ban stage of the logits constraints (constrain.hip), the argmax
-// (elementwise.hip) or the sampler (sample.hip), the record stage of the per-token log-probabilities (logprob.hip) -- their order, the
+// The token pick of a step, with its state (PickState, ctx.h): the ban stage of the logits constraints (constrain.hip), the automaton
+// stage of the token FSM (fsm.hip), the argmax (elementwise.hip) or the sampler (sample.hip), the record stage of the per-token log-probabilities (logprob.hip) -- their order, the
 // refusals and host counters in front of a step, their setters and their rewind.  model.hip sees the functions ctx.h declares.  Host C++.
 #include "ctx.h"
 #include <math.h>
@@ -56,6 +56,28 @@ int ban_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fed, hipS
   return 0;
 }
 
+FsmArgs fsm_args(omchat_ctx* ctx, int b, const int32_t* fed) {
+  const PickState& P = ctx->pick;
+  FsmArgs a;
+  a.trail = (int32_t*)P.fsm_trail.p; a.cap = P.fsm_cap; a.cnt = P.fsm_cnt; a.cur = P.fsm_cur; a.fed = fed;
+  a.b = b; a.V = ctx->c.t_vocab; a.gbase = ctx->tp_rank * ctx->c.t_vocab;
+  a.bm = P.fsm_bm; a.bmw = P.fsm_bmw;
+  return a;
+}
+
+// The automaton stage behind the ban stage (omchat_fsm_begin; nothing when it is off): the rows' states advance over `fed`, then every id
+// that is no edge of a row's state goes to -inf in the context's copy -- in place when the ban stage already wrote it.
+int fsm_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fed, hipStream_t s) {
+  const PickState& P = ctx->pick;
+  if (!P.fsm.on) return 0;
+  OM_CHECK(b <= P.fsm.b, "the token FSM is on for fewer rows than this pick has (omchat_fsm_begin)");
+  const FsmArgs a = fsm_args(ctx, b, fed);
+  TRY(launch_fsm_mark(P.fsm_tab, a, s));
+  TRY(launch_fsm_apply(*lg, ctx->c.t_vocab, a, P.con_logits, fed != nullptr, s));
+  *lg = P.con_logits;
+  return 0;
+}
+
 // The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits, proc = what the pick ran on (the
 // banned copy when constraints are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
 int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, const int32_t* ids, hipStream_t s) {
@@ -96,6 +118,13 @@ int con_count_step(omchat_ctx* ctx) {
   return 0;
 }
 
+// ... and the trail of the token FSM (max_new of omchat_fsm_begin)
+int fsm_count_step(omchat_ctx* ctx) {
+  if (!ctx->pick.fsm.on) return 0;
+  OM_CHECK(ctx->pick.fsm_fed < ctx->pick.fsm.max_new, "token FSM: more decode steps than the max_new given to omchat_fsm_begin");
+  return 0;
+}
+
 }  // namespace
 
 int pick_alloc(omchat_ctx* ctx, int rows) {
@@ -110,7 +139,9 @@ int pick_admit(omchat_ctx* ctx, bool picks, bool feeds) {
     ctx->pick.smp_f_graph = ctx->pick.smp_f;
   }
   if (picks) TRY(lp_room(ctx));
+  if (feeds) TRY(fsm_count_step(ctx));      // (checked in front of the history's counter: a refusal leaves both counters as they are)
   if (feeds) TRY(con_count_step(ctx));
+  if (feeds && ctx->pick.fsm.on) ctx->pick.fsm_fed += 1;
   ctx->pick.smp_vcommit = 0;      // a sampled verify step's picks are no longer the last thing the cache holds
   if (ctx->pick.lp.on && picks) ctx->pick.lp_picks += 1;
   return 0;
@@ -135,6 +166,7 @@ int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipS
   const PickState& P = ctx->pick;
   const float* raw = lg;
   TRY(ban_stage(ctx, &lg, b, fed, s));
+  TRY(fsm_stage(ctx, &lg, b, fed, s));
   if (force_greedy || !P.smp.on) {
     TRY(greedy_pick(ctx, lg, b, next_tokens, s, advance));
     return logprob_stage(ctx, raw, lg, b, next_tokens, s);
@@ -193,6 +225,7 @@ void pick_verify_committed(omchat_ctx* ctx, int n_picks) { ctx->pick.smp_vcommit
 int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s) {
   const PickState& P = ctx->pick;
   if (P.con.on && b <= P.con.b) TRY(launch_constrain_append((int32_t*)P.con_hist.p, P.con_ld, P.con_len, fed, b, s));
+  if (P.fsm.on && b <= P.fsm.b) TRY(launch_fsm_advance(P.fsm_tab, fsm_args(ctx, b, fed), s));
   return 0;
 }
 
@@ -224,6 +257,11 @@ int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s) {
     // the history forgets the fed ids with the slots
     TRY(launch_constrain_rewind(P.con_len, P.con_plen, std::min(b, P.con.b), n, s));
     P.con_fed = std::max(0, P.con_fed - n);
+  }
+  if (P.fsm.on) {
+    // the trail keeps every state: going back is the counts alone
+    TRY(launch_fsm_rewind(P.fsm_cnt, std::min(b, P.fsm.b), n, s));
+    P.fsm_fed = std::max(0, P.fsm_fed - n);
   }
   return 0;
 }
@@ -515,5 +553,100 @@ extern "C" int omchat_read_logprob_extras(omchat_ctx* ctx, int b, float* top_val
   TRY(plane(P.lpx_vals(), top_vals, tn));
   TRY(plane(P.lpx_ids(mn, mb), top_ids, tn));
   TRY(plane(P.lpx_scored(mn, mb), scored, ns));
+  return 0;
+}
+
+// ---- finite-state token constraints (include/omchat_hip.h)
+// The table's addresses and the trail's are kernel arguments of the captured decode graphs: a new table, a buffer that had to grow, or
+// switching the stage on, off or to another b drops them; the same table and the same b on the next call keep them.
+extern "C" int omchat_fsm_load(omchat_ctx* ctx, int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  OM_CHECK(!ctx->beam.on(), "token FSM: a beam search is active");
+  if (n_states <= 0) {      // unload: the stage goes off with its table (the buffer stays, counted, for the next table)
+    if (P.fsm.on || P.fsm_tab.n_states) drop_decode_graphs(ctx);
+    P.fsm = PickState::Fsm{};
+    P.fsm_tab = FsmTable{};
+    P.fsm_off_host.clear();
+    return 0;
+  }
+  OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
+  TRY(fsm_validate(n_states, off, tok, nxt, ctx->c.t_vocab_total));
+  const size_t E = (size_t)off[n_states];
+  const size_t n_off = ((size_t)n_states + 1 + 3) / 4 * 4, n_tok = (E + 3) / 4 * 4 + 4;      // tok 16-byte aligned, whole int4 pieces behind the last edge
+  TRY(ctx->grow(P.fsm_mem, (n_off + n_tok + E + 4) * 4));
+  drop_decode_graphs(ctx);
+  P.fsm = PickState::Fsm{};      // rows begin again on the new table (omchat_fsm_begin)
+  int32_t* base = (int32_t*)P.fsm_mem.p;
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemcpyAsync(base, off, ((size_t)n_states + 1) * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(base + n_off, 0, n_tok * 4, s));
+  if (E) {
+    OM_HIP(hipMemcpyAsync(base + n_off, tok, E * 4, hipMemcpyHostToDevice, s));
+    OM_HIP(hipMemcpyAsync(base + n_off + n_tok, nxt, E * 4, hipMemcpyHostToDevice, s));
+  }
+  OM_HIP(hipStreamSynchronize(s));     // the caller's arrays
+  P.fsm_off_host.assign(off, off + n_states + 1);
+  P.fsm_tab.off = base; P.fsm_tab.tok = base + n_off; P.fsm_tab.nxt = base + n_off + n_tok; P.fsm_tab.n_states = n_states;
+  return 0;
+}
+
+extern "C" int omchat_fsm_begin(omchat_ctx* ctx, int b, const int32_t* start_states, int max_new, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  if (b <= 0) {
+    if (P.fsm.on) drop_decode_graphs(ctx);
+    P.fsm = PickState::Fsm{};
+    return 0;
+  }
+  // every refusal before anything is enqueued or changed
+  OM_CHECK(P.fsm_tab.n_states > 0, "token FSM: no table is loaded (omchat_fsm_load first)");
+  OM_CHECK(b <= c.max_batch, "token FSM: batch exceeds max_batch");
+  OM_CHECK(start_states && max_new >= 1, "token FSM: start states and max_new >= 1");
+  OM_CHECK(!ctx->beam.on(), "token FSM: a beam search is active (the processors act on log-softmax scores there)");
+  hipStream_t s = (hipStream_t)stream;
+  // a start state must have an edge, as every state a row can reach has (omchat_fsm_load)
+  for (int i = 0; i < b; ++i) {
+    OM_CHECK(start_states[i] >= 0 && start_states[i] < P.fsm_tab.n_states, "token FSM: start state outside the table");
+    OM_CHECK(P.fsm_off_host[start_states[i] + 1] > P.fsm_off_host[start_states[i]],
+             "token FSM: start state " + std::to_string(start_states[i]) + " has no edge: every row there would be -inf; add an EOS edge");
+  }
+  void* old_trail = P.fsm_trail.p;
+  void* old_copy = P.con_logits;
+  if (!P.fsm_cnt) {
+    P.fsm_bmw = (c.t_vocab + 31) / 32;
+    TRY(ctx->alloc((void**)&P.fsm_cnt, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&P.fsm_cur, (size_t)c.max_batch * 4));
+    TRY(ctx->alloc((void**)&P.fsm_bm, (size_t)c.max_batch * P.fsm_bmw * 4));
+    OM_HIP(hipMemsetAsync(P.fsm_bm, 0, (size_t)c.max_batch * P.fsm_bmw * 4, s));
+  }
+  if (!P.con_logits) TRY(ctx->alloc((void**)&P.con_logits, (size_t)c.max_batch * c.t_vocab * 4));
+  // the trail: one state per fed token and the start state, grown on demand and never shrunk
+  if (max_new + 1 > P.fsm_cap) {
+    TRY(ctx->grow(P.fsm_trail, (size_t)c.max_batch * (max_new + 1) * 4));
+    P.fsm_cap = max_new + 1;
+  }
+  if (!P.fsm.on || P.fsm.b != b || old_trail != P.fsm_trail.p || old_copy != P.con_logits) drop_decode_graphs(ctx);
+  P.fsm.on = true; P.fsm.b = b; P.fsm.max_new = max_new;
+  P.fsm_fed = 0;
+  OM_HIP(hipMemsetAsync(P.fsm_cnt, 0, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipMemcpy2DAsync(P.fsm_trail.p, (size_t)P.fsm_cap * 4, start_states, 4, 4, (size_t)b, hipMemcpyHostToDevice, s));
+  OM_HIP(hipStreamSynchronize(s));     // the caller's states
+  return 0;
+}
+
+extern "C" int omchat_fsm_states(omchat_ctx* ctx, int b, int32_t* out, void* stream) {
+  OM_CHECK(ctx && out, "null argument");
+  const PickState& P = ctx->pick;
+  OM_CHECK(P.fsm.on && b >= 1 && b <= P.fsm.b, "omchat_fsm_states: rows that omchat_fsm_begin switched on");
+  (void)stream;
+  // (as the other accessors read: the device idle, then blocking copies -- the counts and the rows' trails)
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<int> cnt(b);
+  std::vector<int32_t> trail((size_t)b * P.fsm_cap);
+  OM_HIP(hipMemcpy(cnt.data(), P.fsm_cnt, (size_t)b * 4, hipMemcpyDeviceToHost));
+  OM_HIP(hipMemcpy(trail.data(), P.fsm_trail.p, trail.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < b; ++i) out[i] = trail[(size_t)i * P.fsm_cap + std::min(std::max(cnt[i], 0), P.fsm_cap - 1)];
   return 0;
 }

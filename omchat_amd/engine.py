@@ -696,6 +696,45 @@ class Engine:
     def constraints_off(self):
         check(self.lib.omchat_set_constraints(self.h, 0, 0, 0, 0, None, 0, None, 0, None, 0, None, None, 0, None, None, 0, cur_stream()))
 
+    # ------------------------------------------------------------------ finite-state token constraints (include/omchat_hip.h: omchat_fsm_load)
+    def load_token_fsm(self, fsm):
+        """uploads the table of an omchat_amd.fsm.TokenFSM (None: unloads).  The object loaded last is remembered: handing it over again keeps
+        the table and the captured decode graphs."""
+        torch = _torch()
+        if fsm is vars(self).get("_fsm"):
+            return
+        if fsm is None:
+            check(self.lib.omchat_fsm_load(self.h, 0, None, None, None, cur_stream()))
+        else:
+            i32 = lambda xs: torch.tensor(xs or [0], dtype=torch.int32)
+            off, tok, nxt = (i32(a) for a in fsm.arrays())
+            check(self.lib.omchat_fsm_load(self.h, int(fsm.n_states), ptr(off), ptr(tok), ptr(nxt), cur_stream()))
+        self._fsm = fsm
+        self._fsm_on = False
+
+    def token_fsm_begin(self, b, start, max_new):
+        """every following token pick of rows 0..b-1 (argmax or sampler, eager or in the decode graph) allows only the ids that are edges of
+        the row's state in the loaded table; every decode step first advances the states over the tokens it is fed.  start: one state or
+        one per row; max_new: the most decode steps that follow.  Sticky until token_fsm_off()."""
+        torch = _torch()
+        st = torch.tensor([int(start)] * int(b) if isinstance(start, int) else [int(s) for s in start], dtype=torch.int32)
+        if st.numel() != int(b):
+            raise ValueError(f"token_fsm_begin: {st.numel()} start states for {b} rows")
+        check(self.lib.omchat_fsm_begin(self.h, int(b), ptr(st), int(max_new), cur_stream()))
+        self._fsm_on = True
+
+    def token_fsm_off(self):
+        if vars(self).get("_fsm_on", False):
+            check(self.lib.omchat_fsm_begin(self.h, 0, None, 0, cur_stream()))
+        self._fsm_on = False
+
+    def token_fsm_states(self, b):
+        """the current states of rows 0..b-1 (omchat_amd.fsm.DEAD included); synchronises"""
+        torch = _torch()
+        out = torch.zeros(int(b), dtype=torch.int32)
+        check(self.lib.omchat_fsm_states(self.h, int(b), ptr(out), cur_stream()))
+        return [int(x) for x in out]
+
     # ------------------------------------------------------------------ sampled groups (include/omchat_hip.h: omchat_group_begin)
     def group_share_refusal(self, N):
         """why the shared-prompt form is not available for N rows per prompt on this engine, or None (host data only)"""

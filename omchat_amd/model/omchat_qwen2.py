@@ -366,7 +366,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
                  repetition_penalty=None, seed=None, generator=None, num_beams=None, length_penalty=None, early_stopping=None,
                  num_return_sequences=None, return_dict_in_generate=False, reuse_cache=None, output_logprobs=None, share_prompt=None,
-                 top_logprobs=None, score_token_ids=None, suffixes=None, **kwargs):
+                 top_logprobs=None, score_token_ids=None, suffixes=None, token_fsm=None, fsm_start=None, **kwargs):
         """The loop HF GenerationMixin drives for single_inference.py:53-62, stop on EOS (kept in the output) or max_new_tokens; returns
         prompt + new ids [b, T + new].  Greedy: argmax of the last position (first index wins).  do_sample=True: the on-device sampler
         (omchat_set_sampling) with HF's order and defaults -- repetition penalty over the prompt's ids (the -200 image sentinel never counts)
@@ -421,7 +421,17 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         anything is enqueued: input_ids of more than one row, an attention_mask with zeros, an empty list or suffix, an id < 0 or >= the
         vocabulary, N > max_batch, N * max S_j > max_prefill_rows, num_beams > 1, num_return_sequences > 1, prompt_lookup_num_tokens,
         reuse_cache=True, a streamer when N > 1, the e4m3 KV cache / fp8 prefill GEMMs / tensor parallelism (NotImplementedError); and
-        P + max S_j + 1 > max_seq right after the splice plan, before the tower runs."""
+        P + max S_j + 1 > max_seq right after the splice plan, before the tower runs.
+        token_fsm=TokenFSM (omchat_amd/fsm.py): a deterministic automaton over token ids -- the index a grammar or regex
+        compiler builds -- constrains the form of the answer on the device: row r is in one state, only the ids that are edges of that
+        state can be picked (greedy or sampled, in front of the warpers like HF's PrefixConstrainedLogitsProcessor, behind the token-banning
+        arguments when both are given), and every decode step moves the state over the token it is fed.  fsm_start: the start state -- one
+        int, or a list with one per prompt (repeated for the siblings of num_return_sequences / suffixes=) or one per row of the expanded
+        batch; default 0.  A row that is fed a token without an edge (the pad behind its EOS) is no longer masked.  With
+        return_dict_in_generate=True the output carries .fsm_states [rows]: omchat_amd.fsm.DEAD (-1) for a row that ended with an EOS, else
+        the state the row stopped in (an answer cut by max_new_tokens).  Refused with num_beams > 1 and with prompt_lookup_num_tokens
+        (NotImplementedError), and for a start state out of range or without an edge (ValueError).  HF's prefix_allowed_tokens_fn itself
+        stays refused: TokenFSM.as_prefix_allowed_tokens_fn gives the callback that computes the same constraint there."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -455,6 +465,11 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         eos_ids = eos_token_id if eos_token_id is not None else gc.eos_token_id
         eos_ids = list(eos_ids) if isinstance(eos_ids, (list, tuple)) else ([eos_ids] if eos_ids is not None else [])
         con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None)
+        # the token automaton (omchat_amd/fsm.py): one start state per row of the expanded batch, refused here too
+        from ..fsm import resolve_token_fsm
+        n_prompts = input_ids.shape[0]
+        n_rows = len(sfx[0]) if sfx is not None else n_prompts * (group[0] if group is not None else 1)
+        fsm_rows = resolve_token_fsm(token_fsm, fsm_start, n_prompts, n_rows, self.engine.c.t_vocab_total, nb, lookup is not None)
         # the sampling arguments are resolved and refused here too, before the sticky state below is touched (beam search refuses do_sample itself)
         smp = self._sampling_params(temperature, top_k, top_p, repetition_penalty, seed, generator, kwargs) if do_sample and nb == 1 else None
         for name in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"):      # do_sample=False (or beam search): ignored, as HF ignores them
@@ -463,6 +478,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             self.engine.constraints_off()                             # (set below, after the prefill; equal parameters keep the decode graphs)
         if not olp and getattr(self.engine, "_logprobs_on", False):   # sticky too: a call without the keyword records nothing
             self.engine.logprobs_off()
+        if fsm_rows is None and vars(self.engine).get("_fsm_on", False):      # sticky too: a call without the keyword is unconstrained
+            self.engine.token_fsm_off()
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -508,6 +525,9 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if con is not None:
             # the history HF's processors see: the prompt rows as passed (-200 sentinels and pads included) + the ids every step is fed
             self.engine.set_constraints(b, input_ids.tolist() if hist is None else hist, max_new_tokens, **con)
+        if fsm_rows is not None:
+            self.engine.load_token_fsm(token_fsm)                     # (the same object as last time: the table and the graphs stay)
+            self.engine.token_fsm_begin(b, fsm_rows, max_new_tokens)
         if olp:
             self.engine.set_logprobs(b, max_new_tokens, top_n, score_ids)      # the prefill's pick below is record 0
         if smp is not None:
@@ -592,8 +612,19 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             streamer.end()
         self._record_prefix(prompt_slots, [int(t[0]) for t in new])
         seqs = torch.cat([input_ids.cpu(), torch.stack(new, dim=1)], dim=1) if hist is None else torch.stack(new, dim=1)
+        fsm_states = None
+        if fsm_rows is not None and return_dict_in_generate:
+            # the device holds the rows' states after every token that was fed: all but the last one emitted (the step enqueued ahead of an
+            # EOS was taken back with its state).  A row that ended is DEAD by definition; the others take the last transition here
+            from ..fsm import DEAD
+            dev = self.engine.token_fsm_states(b)
+            fsm_states = torch.tensor([DEAD if bool(done[r]) else token_fsm.next(dev[r], int(new[-1][r])) for r in range(b)], dtype=torch.int64)
         if not olp:
-            return seqs
+            if fsm_states is None:
+                return seqs
+            res = GenerateOutput(seqs, None, None)
+            res.add("fsm_states", fsm_states)
+            return res
         # the step enqueued ahead was taken back with its record: exactly one record per generated token
         raw, proc, counts = self.engine.read_logprobs(b)
         if counts != [len(new)] * b:
@@ -611,6 +642,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 res.add("top_token_ids", torch.where(k3, ti, torch.full((), -1, dtype=torch.int64)))
             if score_ids:
                 res.add("scored_logprobs", torch.where(k3, sc, zero))
+        if fsm_states is not None:
+            res.add("fsm_states", fsm_states)
         return res
 
     def _group_params(self, input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer):
