@@ -267,7 +267,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_kernel(AttnP p) {
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------
 // Prefill kernel, second generation (head_dim 128): 32x32x16 MFMA, one wave = 32 queries of one head.
 //
@@ -1903,6 +1902,48 @@ bool attn_decode_kv8_fuses_rope(int batch, int kv_heads, int L, bool masked) {
   return g_attn_kv8_fuse && tpw == 3 && waves <= 4L * device_cus();
 }
 
+// The split-KV merge of every launcher in this file: `rows` rows of `nsplit` partials each, row r holding kv_len[r] keys (null: L) cut into
+// splits of split_keys.  done (experiments build, launch_attn_decode only): completion flags, which the one-round-trip form alone publishes.
+struct MergeDone { unsigned* flags = nullptr; unsigned epoch = 0; int mode = 0; unsigned long long* dbg = nullptr; };
+template <typename T>
+static void launch_merge(const float* ws, int nsplit, int q_heads, int rows, const int* kv_len, int L, float c, void* O, int64_t o_sb, int64_t o_sh,
+                         int pack_nb, int split_keys, hipStream_t s, const MergeDone& done = MergeDone{}) {
+  const dim3 mgrid(q_heads, rows);
+  if (nsplit > g_merge_mid_min && nsplit <= 256) {
+    if (g_merge_dg == 2) hipLaunchKernelGGL((attn_merge_mid_kernel<T, 4, 2>), dim3(q_heads, rows, 2), dim3(512), 0, s, ws, nsplit, q_heads, kv_len, L, c, (T*)O, o_sb, o_sh, pack_nb, split_keys);
+    else hipLaunchKernelGGL((attn_merge_mid_kernel<T, 4, 1>), mgrid, dim3(512), 0, s, ws, nsplit, q_heads, kv_len, L, c, (T*)O, o_sb, o_sh, pack_nb, split_keys);
+  } else if (nsplit > 256 && nsplit <= 1024) {
+    if (g_merge_dg >= 1) hipLaunchKernelGGL((attn_merge_mid_kernel<T, 8, 4>), dim3(q_heads, rows, 4), dim3(1024), 0, s, ws, nsplit, q_heads, kv_len, L, c, (T*)O, o_sb, o_sh, pack_nb, split_keys);
+    else hipLaunchKernelGGL((attn_merge_mid_kernel<T, 8, 1>), mgrid, dim3(1024), 0, s, ws, nsplit, q_heads, kv_len, L, c, (T*)O, o_sb, o_sh, pack_nb, split_keys);
+  } else {
+    hipLaunchKernelGGL(attn_merge_kernel<T>, mgrid, dim3(128), 0, s, ws, nsplit, q_heads, kv_len, L, c, (T*)O, o_sb, o_sh, pack_nb, split_keys,
+                       done.flags, done.epoch, done.mode, done.dbg);
+  }
+}
+
+// what launch_attn_decode's plan decided; launch_decode_form turns it into the attention kernel (first match wins) and the merge
+struct DecodeForm { bool masked, kv8, kv8_fuse, dma; int tpw, kv8_nw, dma_lds, nsplit, split_keys; };
+template <typename T>
+static void launch_decode_form(const AttnDecodeArgs& a, const DecodeForm& f, dim3 grid, const AttnP& p, hipStream_t s) {
+  if (f.masked && f.kv8) hipLaunchKernelGGL((attn_decode_kernel<T, true, true>), grid, dim3(64), 0, s, p);
+  else if (f.masked) hipLaunchKernelGGL((attn_decode_kernel<T, false, true>), grid, dim3(64), 0, s, p);
+  else if (f.kv8 && f.tpw == 2) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<T, 2, 1>), grid, dim3(64), 0, s, p);
+  else if (f.kv8_fuse && f.kv8_nw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<T, 3, 4, true>), grid, dim3(256), 0, s, p);
+  else if (f.kv8_fuse) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<T, 3, 1, true>), grid, dim3(64), 0, s, p);
+  else if (f.kv8 && f.tpw == 3 && f.kv8_nw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<T, 3, 4>), grid, dim3(256), 0, s, p);
+  else if (f.kv8 && f.tpw == 3) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<T, 3, 1>), grid, dim3(64), 0, s, p);
+  else if (f.kv8 && f.tpw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<T, 4, 1>), grid, dim3(64), 0, s, p);
+  else if (f.kv8) hipLaunchKernelGGL((attn_decode_kernel<T, true>), grid, dim3(64), 0, s, p);
+  else if (f.dma && g_attn_dma_stages == 2) hipLaunchKernelGGL((attn_decode_dma_kernel<T, 2>), grid, dim3(64), f.dma_lds, s, p);
+  else if (f.dma && g_attn_dma_stages == 3) hipLaunchKernelGGL((attn_decode_dma_kernel<T, 3>), grid, dim3(64), f.dma_lds, s, p);
+  else if (f.dma) hipLaunchKernelGGL((attn_decode_dma_kernel<T, 4>), grid, dim3(64), f.dma_lds, s, p);
+  else if (f.tpw > 1 && g_attn_klds) hipLaunchKernelGGL((attn_decode_multi_kernel<T, true>), grid, dim3(64), 0, s, p);
+  else if (f.tpw > 1) hipLaunchKernelGGL((attn_decode_multi_kernel<T, false>), grid, dim3(64), 0, s, p);
+  else hipLaunchKernelGGL((attn_decode_kernel<T, false>), grid, dim3(64), 0, s, p);
+  launch_merge<T>(a.ws, f.nsplit, a.q_heads, a.batch, a.kv_len, a.L, p.c, a.O, a.o_sb, a.o_sh, a.o_pack_nb, f.split_keys, s,
+                  MergeDone{a.done_flags, a.done_epoch, a.done_mode, a.done_dbg});
+}
+
 int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
   OM_CHECK(a.q_heads % a.kv_heads == 0 && a.q_heads / a.kv_heads <= 16, "group size must be <= 16");
   OM_CHECK(a.L > 0 && a.batch > 0, "empty attention");
@@ -1961,57 +2002,11 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
   // for that many; a CU that took more would leave another one short)
   const int dma_lds = std::min(65536, std::max(g_attn_dma_stages * 16384, (160 / dma_slots) * 1024));
   dim3 grid(nsplit, a.kv_heads, a.batch);
-  dim3 mgrid(a.q_heads, a.batch);
   if (a.done_flags && (a.batch != 1 || nsplit > 64 || nsplit > g_merge_mid_min)) { omchat_set_error("launch_attn_decode: completion flags exist for the one-round-trip merge only (batch 1, <= 64 splits)"); return 1; }
-  if (dtype == OMCHAT_F16) {
-    if (a.key_mask && kv8) hipLaunchKernelGGL((attn_decode_kernel<f16, true, true>), grid, dim3(64), 0, s, p);
-    else if (a.key_mask) hipLaunchKernelGGL((attn_decode_kernel<f16, false, true>), grid, dim3(64), 0, s, p);
-    else if (kv8 && tpw == 2) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<f16, 2, 1>), grid, dim3(64), 0, s, p);
-    else if (kv8_fuse && kv8_nw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<f16, 3, 4, true>), grid, dim3(256), 0, s, p);
-    else if (kv8_fuse) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<f16, 3, 1, true>), grid, dim3(64), 0, s, p);
-    else if (kv8 && tpw == 3 && kv8_nw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<f16, 3, 4>), grid, dim3(256), 0, s, p);
-    else if (kv8 && tpw == 3) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<f16, 3, 1>), grid, dim3(64), 0, s, p);
-    else if (kv8 && tpw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<f16, 4, 1>), grid, dim3(64), 0, s, p);
-    else if (kv8) hipLaunchKernelGGL((attn_decode_kernel<f16, true>), grid, dim3(64), 0, s, p);
-    else if (dma && g_attn_dma_stages == 2) hipLaunchKernelGGL((attn_decode_dma_kernel<f16, 2>), grid, dim3(64), dma_lds, s, p);
-    else if (dma && g_attn_dma_stages == 3) hipLaunchKernelGGL((attn_decode_dma_kernel<f16, 3>), grid, dim3(64), dma_lds, s, p);
-    else if (dma) hipLaunchKernelGGL((attn_decode_dma_kernel<f16, 4>), grid, dim3(64), dma_lds, s, p);
-    else if (tpw > 1 && g_attn_klds) hipLaunchKernelGGL((attn_decode_multi_kernel<f16, true>), grid, dim3(64), 0, s, p);
-    else if (tpw > 1) hipLaunchKernelGGL((attn_decode_multi_kernel<f16, false>), grid, dim3(64), 0, s, p);
-    else hipLaunchKernelGGL((attn_decode_kernel<f16, false>), grid, dim3(64), 0, s, p);
-    if (nsplit > g_merge_mid_min && nsplit <= 256) {
-      if (g_merge_dg == 2) hipLaunchKernelGGL((attn_merge_mid_kernel<f16, 4, 2>), dim3(a.q_heads, a.batch, 2), dim3(512), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-      else hipLaunchKernelGGL((attn_merge_mid_kernel<f16, 4, 1>), mgrid, dim3(512), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-    } else if (nsplit > 256 && nsplit <= 1024) {
-      if (g_merge_dg >= 1) hipLaunchKernelGGL((attn_merge_mid_kernel<f16, 8, 4>), dim3(a.q_heads, a.batch, 4), dim3(1024), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-      else hipLaunchKernelGGL((attn_merge_mid_kernel<f16, 8, 1>), mgrid, dim3(1024), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-    }
-    else hipLaunchKernelGGL(attn_merge_kernel<f16>, mgrid, dim3(128), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, a.done_flags, a.done_epoch, a.done_mode, a.done_dbg);
-  } else if (dtype == OMCHAT_BF16) {
-    if (a.key_mask && kv8) hipLaunchKernelGGL((attn_decode_kernel<bf16, true, true>), grid, dim3(64), 0, s, p);
-    else if (a.key_mask) hipLaunchKernelGGL((attn_decode_kernel<bf16, false, true>), grid, dim3(64), 0, s, p);
-    else if (kv8 && tpw == 2) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<bf16, 2, 1>), grid, dim3(64), 0, s, p);
-    else if (kv8_fuse && kv8_nw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<bf16, 3, 4, true>), grid, dim3(256), 0, s, p);
-    else if (kv8_fuse) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<bf16, 3, 1, true>), grid, dim3(64), 0, s, p);
-    else if (kv8 && tpw == 3 && kv8_nw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<bf16, 3, 4>), grid, dim3(256), 0, s, p);
-    else if (kv8 && tpw == 3) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<bf16, 3, 1>), grid, dim3(64), 0, s, p);
-    else if (kv8 && tpw == 4) hipLaunchKernelGGL((attn_decode_kv8_walk_kernel<bf16, 4, 1>), grid, dim3(64), 0, s, p);
-    else if (kv8) hipLaunchKernelGGL((attn_decode_kernel<bf16, true>), grid, dim3(64), 0, s, p);
-    else if (dma && g_attn_dma_stages == 2) hipLaunchKernelGGL((attn_decode_dma_kernel<bf16, 2>), grid, dim3(64), dma_lds, s, p);
-    else if (dma && g_attn_dma_stages == 3) hipLaunchKernelGGL((attn_decode_dma_kernel<bf16, 3>), grid, dim3(64), dma_lds, s, p);
-    else if (dma) hipLaunchKernelGGL((attn_decode_dma_kernel<bf16, 4>), grid, dim3(64), dma_lds, s, p);
-    else if (tpw > 1 && g_attn_klds) hipLaunchKernelGGL((attn_decode_multi_kernel<bf16, true>), grid, dim3(64), 0, s, p);
-    else if (tpw > 1) hipLaunchKernelGGL((attn_decode_multi_kernel<bf16, false>), grid, dim3(64), 0, s, p);
-    else hipLaunchKernelGGL((attn_decode_kernel<bf16, false>), grid, dim3(64), 0, s, p);
-    if (nsplit > g_merge_mid_min && nsplit <= 256) {
-      if (g_merge_dg == 2) hipLaunchKernelGGL((attn_merge_mid_kernel<bf16, 4, 2>), dim3(a.q_heads, a.batch, 2), dim3(512), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-      else hipLaunchKernelGGL((attn_merge_mid_kernel<bf16, 4, 1>), mgrid, dim3(512), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-    } else if (nsplit > 256 && nsplit <= 1024) {
-      if (g_merge_dg >= 1) hipLaunchKernelGGL((attn_merge_mid_kernel<bf16, 8, 4>), dim3(a.q_heads, a.batch, 4), dim3(1024), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-      else hipLaunchKernelGGL((attn_merge_mid_kernel<bf16, 8, 1>), mgrid, dim3(1024), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys);
-    }
-    else hipLaunchKernelGGL(attn_merge_kernel<bf16>, mgrid, dim3(128), 0, s, a.ws, nsplit, a.q_heads, a.kv_len, a.L, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, a.done_flags, a.done_epoch, a.done_mode, a.done_dbg);
-  } else { omchat_set_error("launch_attn_decode: bad dtype"); return 1; }
+  const DecodeForm f{a.key_mask != nullptr, kv8, kv8_fuse, dma, tpw, kv8_nw, dma_lds, nsplit, split_keys};
+  if (dtype == OMCHAT_F16) launch_decode_form<f16>(a, f, grid, p, s);
+  else if (dtype == OMCHAT_BF16) launch_decode_form<bf16>(a, f, grid, p, s);
+  else { omchat_set_error("launch_attn_decode: bad dtype"); return 1; }
   OM_LAUNCH_CHECK();
   return 0;
 }
@@ -2030,16 +2025,16 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
 // (k rotated here: rope_chunk, rope_kv_kernel's arithmetic), and the lane group that loads such a row also appends it to the cache.  No
 // workgroup ever reads a cache slot >= L, so the appends race with nothing.
 // ---------------------------------------------------------------------------------------------------------
-// EXT (split-KV block attention of omchat_prefill_extend, launch_attn_extend): blockIdx.z = chunk of 16 query tokens of
+// EXT (split-KV block attention of omchat_prefill_extend, launch_attn_block ATTN_EXTEND): blockIdx.z = chunk of 16 query tokens of
 // a block of p.Sq rows at positions p.q_pos0 ..; chunk c owns tokens 16 c .. min(16 c + 15, Sq - 1) and walks keys up to its last row's
 // bound only (a split that starts beyond it leaves the neutral partial without loading a tile).  q is rotated and the cache holds every key.
-// SHR (shared-prompt decode attention of a sampled group, launch_attn_shared): blockIdx.z = group of p.Sq sibling rows
+// SHR (shared-prompt decode attention of a sampled group, launch_attn_block ATTN_SHARED): blockIdx.z = group of p.Sq sibling rows
 // z p.Sq .. z p.Sq + p.Sq - 1 that share the prompt keys [0, p.Skv) held by the group's first row only.  Workgroups x < p.shr_nsp are the
 // prefix splits: "token" t is sibling t, all p.Sq x n_rep query rows over the leader's keys below p.Skv -- exactly p.Skv, whatever the leader's
 // length: its slots beyond are its own suffix.  The others are one sibling's suffix splits of one tile: its n_rep query rows over its own
 // keys [p.Skv, len).  q is rotated at len - 1; the suffix split that holds key len - 1 takes it from k_new / v_new and appends it to the
 // row's own cache (one writer; no workgroup reads that slot).  A split without keys leaves the neutral partial.  No causal bound.
-// SFX (suffix pass of omchat_prefill_suffixes, launch_attn_suffix): N sibling rows of p.Sq query tokens each (b-major,
+// SFX (suffix pass of omchat_prefill_suffixes, launch_attn_block ATTN_SUFFIX): N sibling rows of p.Sq query tokens each (b-major,
 // p.shr_L = N p.Sq flat query rows, row j valid below p.kv_len[j] - p.Skv) at positions p.Skv .. over the prompt keys [0, p.Skv) of the
 // leader (row 0) and each sibling's own keys from slot p.Skv on.  Workgroups x < p.shr_nsp are the prefix splits: blockIdx.z = chunk of 16
 // FLAT query rows (every row sees every prompt key, so sibling borders do not matter), p.tpw tiles of the leader's keys, bounded by exactly
@@ -2061,7 +2056,7 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   int key_base = split * KV_TILE * p.tpw, ntile = p.tpw;
   int64_t row_off_k = 0, row_off_v = 0, row_off_new = 0;
   if constexpr (SHR) {
-    const int nss = p.nsplit - p.shr_nsp, x = (int)blockIdx.x - p.shr_nsp;      // nss >= 1 (launch_attn_shared)
+    const int nss = p.nsplit - p.shr_nsp, x = (int)blockIdx.x - p.shr_nsp;      // nss >= 1 (launch_attn_block: L > P)
     const bool pre = x < 0;
     const int j = pre ? 0 : x / nss, ss = pre ? 0 : x - j * nss;
     t0 = (int)blockIdx.z * p.Sq + j;          // first row: the leader (prefix) or the sibling whose suffix this is
@@ -2240,61 +2235,10 @@ __global__ __launch_bounds__(NW * 64) void attn_verify_kernel(AttnP p) {
   }
 }
 
-// the split-KV merge of launch_attn_decode's 16-bit path, for `rows` rows of `nsplit` partials each (every row holds L keys)
-template <typename T>
-static void launch_merge_rows(const float* ws, int nsplit, int q_heads, int rows, int L, float c, T* O, int64_t o_sb, int64_t o_sh, int pack_nb,
-                              int split_keys, hipStream_t s) {
-  const dim3 mgrid(q_heads, rows);
-  if (nsplit > g_merge_mid_min && nsplit <= 256) {
-    if (g_merge_dg == 2) hipLaunchKernelGGL((attn_merge_mid_kernel<T, 4, 2>), dim3(q_heads, rows, 2), dim3(512), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
-    else hipLaunchKernelGGL((attn_merge_mid_kernel<T, 4, 1>), mgrid, dim3(512), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
-  } else if (nsplit > 256 && nsplit <= 1024) {
-    if (g_merge_dg >= 1) hipLaunchKernelGGL((attn_merge_mid_kernel<T, 8, 4>), dim3(q_heads, rows, 4), dim3(1024), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
-    else hipLaunchKernelGGL((attn_merge_mid_kernel<T, 8, 1>), mgrid, dim3(1024), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys);
-  } else {
-    hipLaunchKernelGGL(attn_merge_kernel<T>, mgrid, dim3(128), 0, s, ws, nsplit, q_heads, nullptr, L, c, O, o_sb, o_sh, pack_nb, split_keys,
-                       nullptr, 0u, 0, nullptr);
-  }
-}
-
 // tiles per split: one while the grid is short of two workgroups per CU (latency: one sequence at a few thousand keys), more for long
 // contexts so that the partials written here and read by the merge stay few
 int attn_verify_tpw(int keys, int kv_heads) {
   return std::max(1, std::min(8, cdiv(cdiv(keys, KV_TILE) * kv_heads, 2 * device_cus())));
-}
-
-int launch_attn_verify(int dtype, const AttnVerifyArgs& a, hipStream_t s) {
-  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
-  const int n_rep = a.q_heads / a.kv_heads;
-  OM_CHECK(a.T >= 1 && a.T <= VERIFY_MAX_T && a.T * n_rep <= 128, "verify attention: 1 <= T <= 16 and T * n_rep <= 128 query rows");
-  OM_CHECK(a.L >= 0, "negative cache length");
-  OM_CHECK(!a.rope || (a.k_new && a.v_new && a.L + a.T <= a.rope_max), "fused RoPE needs k_new / v_new and a table covering L + T positions");
-  OM_CHECK(a.o_pack_nb == 0 || (a.T <= 16 * a.o_pack_nb && a.o_sh == 128), "packed output: T <= 16 * NB, head stride 128");
-  const int Lt = a.L + a.T;
-  const int tpw = attn_verify_tpw(Lt, a.kv_heads);
-  const int split_keys = KV_TILE * tpw, nsplit = cdiv(Lt, split_keys);
-  OM_CHECK(a.ws && a.ws_bytes >= attn_decode_ws_bytes(a.T, a.q_heads, Lt), "workspace too small");
-  AttnP p{};
-  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
-  p.K = a.K; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
-  p.V = a.V; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
-  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.T; p.Skv = Lt; p.q_pos0 = a.L; p.nsplit = nsplit;
-  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
-  p.rope = a.rope; p.rope_max = a.rope_max; p.k_new = a.k_new; p.v_new = a.v_new; p.new_sb = a.new_sb;
-  p.k_cache_w = a.K; p.v_cache_w = a.V;
-  const bool wide = a.T * n_rep > 64;
-  const dim3 grid(nsplit, a.kv_heads);
-  if (dtype == OMCHAT_F16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, a.T, Lt, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, s);
-  } else if (dtype == OMCHAT_BF16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, a.T, Lt, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, s);
-  } else { omchat_set_error("launch_attn_verify: bad dtype"); return 1; }
-  OM_LAUNCH_CHECK();
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2307,42 +2251,6 @@ static void attn_extend_plan(int Sq, int keys, int kv_heads, int* tpw, int* nspl
   const int want = std::max(1, 2 * device_cus() / std::max(1, chunks * kv_heads));      // splits for ~2 workgroups per CU
   *tpw = std::max(1, cdiv(tiles, want));
   *nsplit = cdiv(tiles, *tpw);
-}
-size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L) {
-  int tpw, nsplit;
-  attn_extend_plan(Sq, L + Sq, kv_heads, &tpw, &nsplit);
-  return (size_t)Sq * q_heads * nsplit * WS_STRIDE * sizeof(float);
-}
-
-int launch_attn_extend(int dtype, const AttnExtendArgs& a, hipStream_t s) {
-  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
-  const int n_rep = a.q_heads / a.kv_heads;
-  OM_CHECK(n_rep <= 8, "extend attention: at most 8 query heads per kv head (16 tokens x n_rep <= 128 query rows per workgroup)");
-  OM_CHECK(a.Sq >= 1 && a.L >= 0, "extend attention: Sq >= 1, L >= 0");
-  const int Lt = a.L + a.Sq;
-  int tpw, nsplit;
-  attn_extend_plan(a.Sq, Lt, a.kv_heads, &tpw, &nsplit);
-  OM_CHECK(a.ws && a.ws_bytes >= attn_extend_ws_bytes(a.Sq, a.q_heads, a.kv_heads, a.L), "workspace too small");
-  AttnP p{};
-  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
-  p.K = a.K; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
-  p.V = a.V; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
-  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.Sq; p.Skv = Lt; p.q_pos0 = a.L; p.nsplit = nsplit;
-  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
-  const bool wide = 16 * n_rep > 64;
-  const dim3 grid(nsplit, a.kv_heads, cdiv(a.Sq, 16));
-  const int split_keys = KV_TILE * tpw;
-  if (dtype == OMCHAT_F16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4, true>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, a.Sq, Lt, p.c, (f16*)a.O, a.o_sb, a.o_sh, 0, split_keys, s);
-  } else if (dtype == OMCHAT_BF16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, true>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, a.Sq, Lt, p.c, (bf16*)a.O, a.o_sb, a.o_sh, 0, split_keys, s);
-  } else { omchat_set_error("launch_attn_extend: bad dtype"); return 1; }
-  OM_LAUNCH_CHECK();
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2360,47 +2268,6 @@ static void attn_shared_plan(int G, int P, int L, int kv_heads, int* tpw, int* n
   *nsp = cdiv(tiles, *tpw);
   *nss = cdiv(L - P, KV_TILE);
 }
-size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L) {
-  if (G < 1 || N < 1 || P < 1 || L <= P || kv_heads < 1) return 0;
-  int tpw, nsp, nss;
-  attn_shared_plan(G, P, L, kv_heads, &tpw, &nsp, &nss);
-  return (size_t)G * N * q_heads * (nsp + nss) * WS_STRIDE * sizeof(float);
-}
-
-int launch_attn_shared(int dtype, const AttnSharedArgs& a, hipStream_t s) {
-  OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
-  const int n_rep = a.q_heads / a.kv_heads;
-  OM_CHECK(a.G >= 1 && a.N >= 1 && a.N <= VERIFY_MAX_T && a.N * n_rep <= 128, "shared attention: 1 <= N <= 16 and N * n_rep <= 128 query rows");
-  OM_CHECK(a.P >= 1 && a.L > a.P, "shared attention: a prompt of P >= 1 keys and at least one own key per row (L > P)");
-  OM_CHECK(!a.rope || (a.k_new && a.v_new && a.L <= a.rope_max), "fused RoPE needs k_new / v_new and a table covering L positions");
-  OM_CHECK(a.o_pack_nb == 0 || (a.G * a.N <= 16 * a.o_pack_nb && a.o_sh == 128), "packed output: rows <= 16 * NB, head stride 128");
-  int tpw, nsp, nss;
-  attn_shared_plan(a.G, a.P, a.L, a.kv_heads, &tpw, &nsp, &nss);
-  const int nsplit = nsp + nss, rows = a.G * a.N;
-  OM_CHECK(a.ws && a.ws_bytes >= attn_shared_ws_bytes(a.G, a.N, a.q_heads, a.kv_heads, a.P, a.L), "workspace too small");
-  AttnP p{};
-  p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
-  p.K = a.K; p.k_sb = a.k_sb; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
-  p.V = a.V; p.v_sb = a.v_sb; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
-  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.N; p.Skv = a.P; p.nsplit = nsplit; p.shr_nsp = nsp; p.shr_L = a.L; p.kv_len = a.kv_len;
-  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
-  p.rope = a.rope; p.rope_max = a.rope_max; p.k_new = a.k_new; p.v_new = a.v_new; p.new_sb = a.new_sb;
-  p.k_cache_w = a.K; p.v_cache_w = a.V;
-  const bool wide = a.N * n_rep > 64;
-  const dim3 grid(nsp + a.N * nss, a.kv_heads, a.G);
-  // every split writes its partial (neutral when it holds no key), so the merge folds all nsplit of them: one "key" per split
-  if (dtype == OMCHAT_F16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8, false, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4, false, true>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (f16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, 1, s);
-  } else if (dtype == OMCHAT_BF16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8, false, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, false, true>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (bf16*)a.O, a.o_sb, a.o_sh, a.o_pack_nb, 1, s);
-  } else { omchat_set_error("launch_attn_shared: bad dtype"); return 1; }
-  OM_LAUNCH_CHECK();
-  return 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // Suffix-pass attention (omchat_prefill_suffixes): N sibling rows of S query tokens each over the prompt keys [0, P) of
@@ -2417,41 +2284,131 @@ static void attn_suffix_plan(int N, int S, int P, int kv_heads, int* tpw, int* n
   *tps = std::max(1, cdiv(stiles, SFX_SPLITS));
   *nss = cdiv(stiles, *tps);
 }
-size_t attn_suffix_ws_bytes(int N, int S, int q_heads, int kv_heads, int P) {
-  if (N < 1 || S < 1 || P < 1 || kv_heads < 1) return 0;
-  int tpw, nsp, tps, nss;
-  attn_suffix_plan(N, S, P, kv_heads, &tpw, &nsp, &tps, &nss);
-  return (size_t)N * S * q_heads * (nsp + nss) * WS_STRIDE * sizeof(float);
+
+// ---------------------------------------------------------------------------------------------------------
+// The one launcher of attn_verify_kernel's four modes (kernels.h: AttnBlockArgs): the mode's plan, its partials and its launch + merge.
+// ---------------------------------------------------------------------------------------------------------
+// nsp splits of tpw tiles -- all of them (verify, extend) or the prefix splits (shared, suffix) -- and nss suffix splits of one (shared) or tps
+// (suffix) tiles
+struct BlockPlan { int tpw = 1, nsp = 0, nss = 0, tps = 0; };
+static BlockPlan attn_block_plan(const AttnBlockArgs& a) {
+  BlockPlan pl;
+  switch (a.mode) {
+    case ATTN_VERIFY: pl.tpw = attn_verify_tpw(a.L + a.S, a.kv_heads); pl.nsp = cdiv(a.L + a.S, KV_TILE * pl.tpw); break;
+    case ATTN_EXTEND: attn_extend_plan(a.S, a.L + a.S, a.kv_heads, &pl.tpw, &pl.nsp); break;
+    case ATTN_SHARED: attn_shared_plan(a.G, a.P, a.L, a.kv_heads, &pl.tpw, &pl.nsp, &pl.nss); break;
+    case ATTN_SUFFIX: attn_suffix_plan(a.N, a.S, a.P, a.kv_heads, &pl.tpw, &pl.nsp, &pl.tps, &pl.nss); break;
+  }
+  return pl;
+}
+size_t attn_block_ws_bytes(const AttnBlockArgs& a) {
+  size_t rows = a.S;
+  switch (a.mode) {
+    case ATTN_VERIFY: return attn_decode_ws_bytes(a.S, a.q_heads, a.L + a.S);      // a batch of T decode rows: one partial per 64 keys whatever tpw is
+    case ATTN_EXTEND: break;
+    case ATTN_SHARED: if (a.G < 1 || a.N < 1 || a.P < 1 || a.L <= a.P || a.kv_heads < 1) return 0; rows = (size_t)a.G * a.N; break;
+    case ATTN_SUFFIX: if (a.N < 1 || a.S < 1 || a.P < 1 || a.kv_heads < 1) return 0; rows = (size_t)a.N * a.S; break;
+    default: return 0;
+  }
+  const BlockPlan pl = attn_block_plan(a);
+  return rows * a.q_heads * (pl.nsp + pl.nss) * WS_STRIDE * sizeof(float);
+}
+static size_t block_ws_bytes(int mode, int G, int N, int S, int q_heads, int kv_heads, int P, int L) {
+  AttnBlockArgs a{};
+  a.mode = mode; a.G = G; a.N = N; a.S = S; a.q_heads = q_heads; a.kv_heads = kv_heads; a.P = P; a.L = L;
+  return attn_block_ws_bytes(a);
+}
+size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L) { return block_ws_bytes(ATTN_EXTEND, 0, 0, Sq, q_heads, kv_heads, 0, L); }
+size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L) { return block_ws_bytes(ATTN_SHARED, G, N, 0, q_heads, kv_heads, P, L); }
+size_t attn_suffix_ws_bytes(int N, int S, int q_heads, int kv_heads, int P) { return block_ws_bytes(ATTN_SUFFIX, 0, N, S, q_heads, kv_heads, P, 0); }
+
+// the mode's kernel in its 4- or 8-wave form (wide: more than 64 query rows per workgroup)
+template <typename T, bool EXT, bool SHR, bool SFX>
+static void launch_block_kernel(bool wide, dim3 grid, const AttnP& p, hipStream_t s) {
+  if (wide) hipLaunchKernelGGL((attn_verify_kernel<T, 8, EXT, SHR, SFX>), grid, dim3(512), 0, s, p);
+  else hipLaunchKernelGGL((attn_verify_kernel<T, 4, EXT, SHR, SFX>), grid, dim3(256), 0, s, p);
+}
+// ... and the merge of its partials: `rows` rows of merge_L "keys" in splits of split_keys
+template <typename T>
+static void launch_block_mode(const AttnBlockArgs& a, bool wide, dim3 grid, const AttnP& p, int rows, int merge_L, int split_keys, hipStream_t s) {
+  switch (a.mode) {
+    case ATTN_VERIFY: launch_block_kernel<T, false, false, false>(wide, grid, p, s); break;
+    case ATTN_EXTEND: launch_block_kernel<T, true, false, false>(wide, grid, p, s); break;
+    case ATTN_SHARED: launch_block_kernel<T, false, true, false>(wide, grid, p, s); break;
+    case ATTN_SUFFIX: launch_block_kernel<T, false, false, true>(wide, grid, p, s); break;
+  }
+  launch_merge<T>(a.ws, p.nsplit, a.q_heads, rows, nullptr, merge_L, p.c, a.O, a.o_sb, a.o_sh, a.o_pack_nb, split_keys, s);
 }
 
-int launch_attn_suffix(int dtype, const AttnSuffixArgs& a, hipStream_t s) {
+int launch_attn_block(int dtype, const AttnBlockArgs& a, hipStream_t s) {
   OM_CHECK(a.kv_heads > 0 && a.q_heads % a.kv_heads == 0, "q_heads must be a multiple of kv_heads");
   const int n_rep = a.q_heads / a.kv_heads;
-  OM_CHECK(n_rep <= 8, "suffix attention: at most 8 query heads per kv head (16 tokens x n_rep <= 128 query rows per workgroup)");
-  OM_CHECK(a.N >= 1 && a.S >= 1 && a.P >= 1 && a.kv_len, "suffix attention: N >= 1 rows of S >= 1 tokens over P >= 1 prompt keys, and the rows' lengths");
-  OM_CHECK((int64_t)a.N * a.S <= 65535, "suffix attention: more than 65535 query rows");
-  int tpw, nsp, tps, nss;
-  attn_suffix_plan(a.N, a.S, a.P, a.kv_heads, &tpw, &nsp, &tps, &nss);
-  const int nsplit = nsp + nss, rows = a.N * a.S;
-  OM_CHECK(a.ws && a.ws_bytes >= attn_suffix_ws_bytes(a.N, a.S, a.q_heads, a.kv_heads, a.P), "workspace too small");
+  switch (a.mode) {      // the mode's refusals
+    case ATTN_VERIFY:
+      OM_CHECK(a.S >= 1 && a.S <= VERIFY_MAX_T && a.S * n_rep <= 128, "verify attention: 1 <= T <= 16 and T * n_rep <= 128 query rows");
+      OM_CHECK(a.L >= 0, "negative cache length");
+      OM_CHECK(!a.rope || (a.k_new && a.v_new && a.L + a.S <= a.rope_max), "fused RoPE needs k_new / v_new and a table covering L + T positions");
+      OM_CHECK(a.o_pack_nb == 0 || (a.S <= 16 * a.o_pack_nb && a.o_sh == 128), "packed output: T <= 16 * NB, head stride 128");
+      break;
+    case ATTN_EXTEND:
+      OM_CHECK(n_rep <= 8, "extend attention: at most 8 query heads per kv head (16 tokens x n_rep <= 128 query rows per workgroup)");
+      OM_CHECK(a.S >= 1 && a.L >= 0, "extend attention: Sq >= 1, L >= 0");
+      OM_CHECK(!a.rope && a.o_pack_nb == 0, "extend attention: Q comes rotated and O is never packed (rope == null, o_pack_nb == 0)");
+      break;
+    case ATTN_SHARED:
+      OM_CHECK(a.G >= 1 && a.N >= 1 && a.N <= VERIFY_MAX_T && a.N * n_rep <= 128, "shared attention: 1 <= N <= 16 and N * n_rep <= 128 query rows");
+      OM_CHECK(a.P >= 1 && a.L > a.P, "shared attention: a prompt of P >= 1 keys and at least one own key per row (L > P)");
+      OM_CHECK(!a.rope || (a.k_new && a.v_new && a.L <= a.rope_max), "fused RoPE needs k_new / v_new and a table covering L positions");
+      OM_CHECK(a.o_pack_nb == 0 || (a.G * a.N <= 16 * a.o_pack_nb && a.o_sh == 128), "packed output: rows <= 16 * NB, head stride 128");
+      break;
+    case ATTN_SUFFIX:
+      OM_CHECK(n_rep <= 8, "suffix attention: at most 8 query heads per kv head (16 tokens x n_rep <= 128 query rows per workgroup)");
+      OM_CHECK(a.N >= 1 && a.S >= 1 && a.P >= 1 && a.kv_len, "suffix attention: N >= 1 rows of S >= 1 tokens over P >= 1 prompt keys, and the rows' lengths");
+      OM_CHECK((int64_t)a.N * a.S <= 65535, "suffix attention: more than 65535 query rows");
+      OM_CHECK(!a.rope && a.o_pack_nb == 0, "suffix attention: Q comes rotated and O is never packed (rope == null, o_pack_nb == 0)");
+      break;
+    default: OM_CHECK(false, "bad mode");
+  }
+  const BlockPlan pl = attn_block_plan(a);
+  const int nsplit = pl.nsp + pl.nss;
+  OM_CHECK(a.ws && a.ws_bytes >= attn_block_ws_bytes(a), "workspace too small");
+  OM_CHECK(dtype == OMCHAT_F16 || dtype == OMCHAT_BF16, "bad dtype");
   AttnP p{};
   p.Q = a.Q; p.q_sb = a.q_sb; p.q_sh = a.q_sh;
-  p.K = a.K; p.k_sb = a.k_sb; p.k_sh = a.k_sh; p.k_sr = a.k_sr;
+  p.K = a.K; p.k_sb = a.k_sb; p.k_sh = a.k_sh; p.k_sr = a.k_sr;      // (k_sb / v_sb: read by the shared and suffix modes only)
   p.V = a.V; p.v_sb = a.v_sb; p.v_sh = a.v_sh; p.v_sr = a.v_sr;
-  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.Sq = a.S; p.Skv = a.P; p.nsplit = nsplit; p.shr_nsp = nsp; p.shr_L = rows; p.kv_len = a.kv_len;
-  p.q_pos0 = tps;
-  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = tpw;
-  const bool wide = 16 * n_rep > 64;
-  const dim3 grid(nsplit, a.kv_heads, a.N * cdiv(a.S, 16));
-  if (dtype == OMCHAT_F16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<f16, 8, false, false, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<f16, 4, false, false, true>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<f16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (f16*)a.O, a.o_sb, a.o_sh, 0, 1, s);
-  } else if (dtype == OMCHAT_BF16) {
-    if (wide) hipLaunchKernelGGL((attn_verify_kernel<bf16, 8, false, false, true>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_verify_kernel<bf16, 4, false, false, true>), grid, dim3(256), 0, s, p);
-    launch_merge_rows<bf16>(a.ws, nsplit, a.q_heads, rows, nsplit, p.c, (bf16*)a.O, a.o_sb, a.o_sh, 0, 1, s);
-  } else { omchat_set_error("launch_attn_suffix: bad dtype"); return 1; }
+  p.q_heads = a.q_heads; p.kv_heads = a.kv_heads; p.nsplit = nsplit;
+  p.c = a.scale * 1.4426950408889634f; p.ws = a.ws; p.tpw = pl.tpw;
+  // what the merge folds: verify / extend `rows` rows of Lt keys in splits of 64 tpw; shared / suffix write every one of the nsplit partials
+  // (neutral when a split holds no key), so the merge is given one "key" per split
+  int rows = a.S, merge_L = nsplit, split_keys = 1;
+  bool wide = 16 * n_rep > 64;
+  dim3 grid(nsplit, a.kv_heads);
+  switch (a.mode) {
+    case ATTN_VERIFY:
+    case ATTN_EXTEND:
+      p.Sq = a.S; p.Skv = merge_L = a.L + a.S; p.q_pos0 = a.L; split_keys = KV_TILE * pl.tpw;
+      if (a.mode == ATTN_VERIFY) wide = a.S * n_rep > 64;
+      else grid.z = cdiv(a.S, 16);
+      break;
+    case ATTN_SHARED:
+      rows = a.G * a.N;
+      p.Sq = a.N; p.Skv = a.P; p.shr_nsp = pl.nsp; p.shr_L = a.L; p.kv_len = a.kv_len;
+      wide = a.N * n_rep > 64;
+      grid = dim3(pl.nsp + a.N * pl.nss, a.kv_heads, a.G);
+      break;
+    case ATTN_SUFFIX:
+      rows = a.N * a.S;
+      p.Sq = a.S; p.Skv = a.P; p.shr_nsp = pl.nsp; p.shr_L = rows; p.kv_len = a.kv_len; p.q_pos0 = pl.tps;
+      grid.z = a.N * cdiv(a.S, 16);
+      break;
+  }
+  if (a.mode == ATTN_VERIFY || a.mode == ATTN_SHARED) {      // the modes with the fused RoPE + append
+    p.rope = a.rope; p.rope_max = a.rope_max; p.k_new = a.k_new; p.v_new = a.v_new; p.new_sb = a.new_sb;
+    p.k_cache_w = (void*)a.K; p.v_cache_w = (void*)a.V;
+  }
+  if (dtype == OMCHAT_F16) launch_block_mode<f16>(a, wide, grid, p, rows, merge_L, split_keys, s);
+  else launch_block_mode<bf16>(a, wide, grid, p, rows, merge_L, split_keys, s);
   OM_LAUNCH_CHECK();
   return 0;
 }

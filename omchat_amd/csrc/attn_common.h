@@ -34,9 +34,9 @@ struct AttnP {
   // epilogue left (gemm.hip EPI_NONE_STATS -> launch_stats_finish).  null = Q is used as stored.
   const float* qn_sumsq = nullptr; int qn_stride = 0, qn_dim = 0; const void* qn_w = nullptr; float qn_eps = 0.f, qn_scale = 1.f;
   int peel_last = 0;      // prefill, MHA: a key count of whole tiles + 1 folds the last key into the online softmax's initial state (attn2_kernel)
-  // shared-prompt decode attention (attn_verify_kernel<SHR>, launch_attn_shared): the first shr_nsp of a row's nsplit partials are the prefix
+  // shared-prompt decode attention (attn_verify_kernel<SHR>, launch_attn_block ATTN_SHARED): the first shr_nsp of a row's nsplit partials are the prefix
   // splits of its group, the rest its own suffix splits; shr_L = keys per row counting the new one when kv_len == null
-  // suffix-pass attention (attn_verify_kernel<SFX>, launch_attn_suffix): Sq = tokens per sibling, Skv = prompt keys P, kv_len[j] = keys of row j,
+  // suffix-pass attention (attn_verify_kernel<SFX>, launch_attn_block ATTN_SUFFIX): Sq = tokens per sibling, Skv = prompt keys P, kv_len[j] = keys of row j,
   // shr_nsp = prefix splits of tpw tiles, shr_L = N Sq flat query rows, q_pos0 = tiles per suffix split
   int shr_nsp = 0, shr_L = 0;
 #if OMCHAT_EXPERIMENTS

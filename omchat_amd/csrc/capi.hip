@@ -210,14 +210,27 @@ extern "C" int omchat_op_attn_prefill(int dtype, const void* q, const void* k, c
 
 extern "C" size_t omchat_op_attn_decode_ws(int b, int Hq, int L) { return attn_decode_ws_bytes(b, Hq, L); }
 
+// The dense layout of the split-KV attention hooks: q / out [rows, Hq, 128] and caches [b, Hkv, cap, 128] (strides in cache elements; = bytes
+// for the e4m3 cache).  qkv_rows: q is the q columns of rows of raw [q | k | v] projections (the _append hooks).
+static void bind_dense(AttnOperands& a, const void* q, bool qkv_rows, const void* k, const void* v, void* out, int Hq, int Hkv, int cap, float scale,
+                       void* ws, size_t ws_bytes) {
+  a.Q = q; a.q_sb = (int64_t)(qkv_rows ? Hq + 2 * Hkv : Hq) * 128; a.q_sh = 128;
+  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
+  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
+  a.q_heads = Hq; a.kv_heads = Hkv; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+}
+// ... and the fused-append view of such qkv rows: the raw k / v columns behind q's, rotated by the table `tab` of rope_max positions
+static void bind_new_rows(AttnOperands& a, const float* tab, int rope_max) {
+  a.rope = tab; a.rope_max = rope_max; a.new_sb = a.q_sb;
+  a.k_new = (const char*)a.Q + (size_t)a.q_heads * 128 * 2; a.v_new = (const char*)a.Q + (size_t)(a.q_heads + a.kv_heads) * 128 * 2;
+}
+
 extern "C" int omchat_op_attn_decode(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Hq, int Hkv, int cap, int L,
                                      const int32_t* kv_len, float scale, void* ws, size_t ws_bytes, void* stream) {
   AttnDecodeArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = a.q_sb; a.o_sh = 128;
-  a.batch = b; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.kv_len = kv_len; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  bind_dense(a, q, false, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  a.batch = b; a.L = L; a.kv_len = kv_len;
   return launch_attn_decode(dtype, a, S(stream));
 }
 
@@ -225,12 +238,9 @@ extern "C" int omchat_op_attn_decode_kv8(int dtype, const void* q, const void* k
                                          int Hq, int Hkv, int cap, int L, const int32_t* kv_len, float scale, void* ws, size_t ws_bytes, void* stream) {
   if (!k8 || !v8 || !ks || !vs) { omchat_set_error("omchat_op_attn_decode_kv8: null cache or scale pointer"); return 1; }
   AttnDecodeArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k8; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;      // strides in cache elements = bytes
-  a.V = v8; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  bind_dense(a, q, false, k8, v8, out, Hq, Hkv, cap, scale, ws, ws_bytes);
   a.k_scale = ks; a.v_scale = vs; a.scale_sb = (int64_t)Hkv * cap; a.scale_sh = cap;
-  a.O = out; a.o_sb = a.q_sb; a.o_sh = 128;
-  a.batch = b; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.kv_len = kv_len; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  a.batch = b; a.L = L; a.kv_len = kv_len;
   return launch_attn_decode(dtype, a, S(stream));
 }
 
@@ -256,13 +266,10 @@ extern "C" int omchat_op_attn_verify(int dtype, const void* q, void* k, void* v,
                                      void* ws, size_t ws_bytes, void* stream) {
   OM_CHECK(q && k && v && out && ws, "null argument");
   OM_CHECK(Hkv > 0 && L >= 0 && L + T <= cap, "L + T exceeds the cache capacity");
-  AttnVerifyArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.T = T; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
-  return launch_attn_verify(dtype, a, S(stream));
+  AttnBlockArgs a{};
+  bind_dense(a, q, false, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  a.mode = ATTN_VERIFY; a.S = T; a.L = L;
+  return launch_attn_block(dtype, a, S(stream));
 }
 
 extern "C" size_t omchat_op_attn_extend_ws(int Sq, int Hq, int Hkv, int L) { return attn_extend_ws_bytes(Sq, Hq, Hkv, L); }
@@ -271,28 +278,28 @@ extern "C" int omchat_op_attn_extend(int dtype, const void* q, const void* k, co
                                      float scale, void* ws, size_t ws_bytes, void* stream) {
   OM_CHECK(q && k && v && out && ws, "null argument");
   OM_CHECK(Hkv > 0 && L >= 0 && Sq >= 1 && L + Sq <= cap, "L + Sq exceeds the cache capacity");
-  AttnExtendArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.Sq = Sq; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
-  return launch_attn_extend(dtype, a, S(stream));
+  AttnBlockArgs a{};
+  bind_dense(a, q, false, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  a.mode = ATTN_EXTEND; a.S = Sq; a.L = L;
+  return launch_attn_block(dtype, a, S(stream));
 }
 
 extern "C" size_t omchat_op_attn_shared_ws(int G, int N, int Hq, int Hkv, int P, int L) { return attn_shared_ws_bytes(G, N, Hq, Hkv, P, L); }
+
+// the two shared-prompt hooks behind their own checks: kv_len = null, every row holds exactly L keys
+static int op_attn_shared(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L, const int* kv_len,
+                          float scale, void* ws, size_t ws_bytes, void* stream) {
+  AttnBlockArgs a{};
+  bind_dense(a, q, false, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  a.mode = ATTN_SHARED; a.G = G; a.N = N; a.P = P; a.L = L; a.kv_len = kv_len;
+  return launch_attn_block(dtype, a, S(stream));
+}
 
 extern "C" int omchat_op_attn_shared(int dtype, const void* q, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap, int P, int L,
                                      float scale, void* ws, size_t ws_bytes, void* stream) {
   OM_CHECK(q && k && v && out && ws, "null argument");
   OM_CHECK(Hkv > 0 && P >= 1 && L > P && L <= cap, "1 <= P < L <= cap");
-  AttnSharedArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.G = G; a.N = N; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
-  return launch_attn_shared(dtype, a, S(stream));
+  return op_attn_shared(dtype, q, k, v, out, G, N, Hq, Hkv, cap, P, L, nullptr, scale, ws, ws_bytes, stream);
 }
 
 // omchat_op_attn_shared with the rows' true lengths (device [G N], each in [P + 1, L]): L only sizes the grid and the workspace
@@ -300,13 +307,7 @@ extern "C" int omchat_op_attn_shared_lens(int dtype, const void* q, void* k, voi
                                           const int* kv_len, float scale, void* ws, size_t ws_bytes, void* stream) {
   OM_CHECK(q && k && v && out && ws && kv_len, "null argument");
   OM_CHECK(Hkv > 0 && P >= 1 && L > P && L <= cap, "1 <= P < L <= cap");
-  AttnSharedArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.G = G; a.N = N; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.L = L; a.kv_len = kv_len; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
-  return launch_attn_shared(dtype, a, S(stream));
+  return op_attn_shared(dtype, q, k, v, out, G, N, Hq, Hkv, cap, P, L, kv_len, scale, ws, ws_bytes, stream);
 }
 
 extern "C" size_t omchat_op_attn_suffix_ws(int N, int S, int Hq, int Hkv, int P) { return attn_suffix_ws_bytes(N, S, Hq, Hkv, P); }
@@ -326,13 +327,10 @@ extern "C" int omchat_op_attn_suffix(int dtype, const void* q, const void* k, co
     OM_HIP(hipMemcpyAsync(kv_len_dev, kl.data(), (size_t)N * 4, hipMemcpyHostToDevice, S(stream)));
     OM_HIP(hipStreamSynchronize(S(stream)));      // host vector
   }
-  AttnSuffixArgs a{};
-  a.Q = q; a.q_sb = (int64_t)Hq * 128; a.q_sh = 128;
-  a.K = k; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.N = N; a.S = S; a.q_heads = Hq; a.kv_heads = Hkv; a.P = P; a.kv_len = kv_len_dev; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
-  return launch_attn_suffix(dtype, a, S(stream));
+  AttnBlockArgs a{};
+  bind_dense(a, q, false, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  a.mode = ATTN_SUFFIX; a.N = N; a.S = S; a.P = P; a.kv_len = kv_len_dev;
+  return launch_attn_block(dtype, a, S(stream));
 }
 
 extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,
@@ -341,16 +339,11 @@ extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float th
   OM_CHECK(Hkv > 0 && L >= 0 && T >= 1 && L + T <= cap, "L + T exceeds the cache capacity");
   float* tab = rope_table_device(L + T, theta);
   OM_CHECK(tab, "rope table allocation failed");
-  const int64_t qkvd = (int64_t)(Hq + 2 * Hkv) * 128;
-  AttnVerifyArgs a{};
-  a.Q = qkv; a.q_sb = qkvd; a.q_sh = 128;
-  a.K = k; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v; a.v_sh = a.k_sh; a.v_sr = 128;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.T = T; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
-  a.rope = tab; a.rope_max = L + T;
-  a.k_new = (const char*)qkv + (size_t)Hq * 128 * 2; a.v_new = (const char*)qkv + (size_t)(Hq + Hkv) * 128 * 2; a.new_sb = qkvd;
-  const int rc = launch_attn_verify(dtype, a, S(stream));
+  AttnBlockArgs a{};
+  bind_dense(a, qkv, true, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  bind_new_rows(a, tab, L + T);
+  a.mode = ATTN_VERIFY; a.S = T; a.L = L;
+  const int rc = launch_attn_block(dtype, a, S(stream));
   hipStreamSynchronize(S(stream));
   hipFree(tab);
   return rc;
@@ -371,16 +364,12 @@ extern "C" int omchat_op_attn_decode_kv8_append(int dtype, void* qkv, float thet
   OM_CHECK(tab, "rope table allocation failed");
   const int qkvd = (Hq + 2 * Hkv) * 128;
   AttnDecodeArgs a{};
-  a.Q = qkv; a.q_sb = qkvd; a.q_sh = 128;
-  a.K = k8; a.k_sb = (int64_t)Hkv * cap * 128; a.k_sh = (int64_t)cap * 128; a.k_sr = 128;
-  a.V = v8; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+  bind_dense(a, qkv, true, k8, v8, out, Hq, Hkv, cap, scale, ws, ws_bytes);
   a.k_scale = ks; a.v_scale = vs; a.scale_sb = (int64_t)Hkv * cap; a.scale_sh = cap;
-  a.O = out; a.o_sb = (int64_t)Hq * 128; a.o_sh = 128;
-  a.batch = b; a.q_heads = Hq; a.kv_heads = Hkv; a.L = L; a.kv_len = kv_len; a.scale = scale; a.ws = (float*)ws; a.ws_bytes = ws_bytes;
+  a.batch = b; a.L = L; a.kv_len = kv_len;
   int rc = 0;
   if (attn_decode_kv8_fuses_rope(b, Hkv, L, false)) {
-    a.rope = tab; a.rope_max = L;
-    a.k_new = (const char*)qkv + (size_t)Hq * 128 * 2; a.v_new = (const char*)qkv + (size_t)(Hq + Hkv) * 128 * 2; a.new_sb = qkvd;
+    bind_new_rows(a, tab, L);
     a.k16_w = k16; a.v16_w = v16;
   } else {
     RopeArgs r{qkv, qkvd, b, 1, Hq, Hkv, pos, L - 1, tab, L, k16, v16, (int64_t)Hkv * cap * 128, (int64_t)cap * 128};

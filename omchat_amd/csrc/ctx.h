@@ -315,6 +315,20 @@ struct omchat_ctx {
   int64_t cache_layer_stride() const { return (int64_t)c.max_batch * c.t_kv_heads * c.max_seq * 128; }
   int64_t cache_sb() const { return (int64_t)c.t_kv_heads * c.max_seq * 128; }
   int64_t cache_sh() const { return (int64_t)c.max_seq * 128; }
+  static constexpr float T_ATTN_SCALE = 0.08838834764831845f;      // the decoder's softmax scale: head_dim ** -0.5, head dim 128
+  // The operands of layer i's split-KV attention (launch_attn_decode, launch_attn_block): Q = the q columns of tw_qkv, one row per token;
+  // K / V = the layer's cache planes; O = tw_ao.  new_rows: with the fused-append view -- the rope table and the raw k / v columns of tw_qkv.
+  // The caller chooses the workspace, o_pack_nb and the launch's own integers.
+  void bind_attn(AttnOperands& a, int i, bool new_rows) const {
+    a.Q = tw_qkv; a.q_sb = t_qkvdim; a.q_sh = 128;
+    a.K = (char*)kcache + (size_t)i * cache_layer_stride() * 2; a.k_sb = cache_sb(); a.k_sh = cache_sh(); a.k_sr = 128;
+    a.V = (char*)vcache + (size_t)i * cache_layer_stride() * 2; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
+    a.O = tw_ao; a.o_sb = t_qdim; a.o_sh = 128;
+    a.q_heads = c.t_heads; a.kv_heads = c.t_kv_heads; a.scale = T_ATTN_SCALE;
+    if (!new_rows) return;
+    a.rope = rope; a.rope_max = c.max_seq; a.new_sb = t_qkvdim;
+    a.k_new = (const char*)tw_qkv + (size_t)t_qdim * 2; a.v_new = (const char*)tw_qkv + (size_t)(t_qdim + t_kvdim) * 2;
+  }
 
   omchat_allreduce_fn hook = nullptr;
   void* hook_user = nullptr;

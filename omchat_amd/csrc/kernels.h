@@ -249,23 +249,31 @@ void norm_set_wave(int v);              // tuning key 40
 void model_set_ao_oproj(int v);         // tuning key 42
 int gemv_get_shard_shapes();
 
-// decode: one query token per sequence, q heads grouped per kv head; split-KV partials + merge.
-struct AttnDecodeArgs {
-  const void* Q; int64_t q_sb, q_sh;            // [b, q_heads, 128]
-  const void* K; int64_t k_sb, k_sh, k_sr;      // cache [b, kv_heads, L, 128]
+// what every split-KV attention launch shares (launch_attn_decode, launch_attn_block): the operands with their strides in elements, the heads,
+// the workspace of the partials and the optional fused-append view.  Which strides a launch reads, and what a row of Q / O is, is the
+// launch's own contract (below).
+struct AttnOperands {
+  const void* Q; int64_t q_sb, q_sh;            // [rows, q_heads, 128] (row stride q_sb)
+  const void* K; int64_t k_sb, k_sh, k_sr;      // cache [rows, kv_heads, cap, 128]; written through (cast) by the fused appends
   const void* V; int64_t v_sb, v_sh, v_sr;
-  void* O; int64_t o_sb, o_sh;                  // [b, q_heads, 128]
-  int batch, q_heads, kv_heads;
-  int L;                                        // kv length used when kv_len == null
-  const int* kv_len;                            // optional device [batch]; null = every sequence holds exactly L keys (one dependent load less)
+  void* O; int64_t o_sb, o_sh;                  // [rows, q_heads, 128]
+  int q_heads, kv_heads;
   float scale;
   float* ws; size_t ws_bytes;                   // workspace for partials
-  // optional fused RoPE + KV append of the token being decoded (replaces rope_kv for S = 1): q is rotated in registers,
-  // the split that owns position pos[b] rotates k, appends k/v to the cache and uses them from LDS
   const float* rope; int rope_max;              // cos/sin table [max_pos][64][2] or null (= q, K, V already rotated/appended)
+  const void* k_new; const void* v_new; int64_t new_sb;   // raw k / v of the new tokens: [rows][kv_heads*128] views, row stride new_sb
+  int o_pack_nb;                                // != 0: O is written as packed x ([rows][q_heads*128] rows, common.h) for the o_proj GEMV
+};
+
+// decode: one query token per sequence, q heads grouped per kv head; split-KV partials + merge.
+// Operands: Q / O [b, q_heads, 128], K / V cache [b, kv_heads, L, 128].
+// rope != null: optional fused RoPE + KV append of the token being decoded (replaces rope_kv for S = 1): q is rotated in registers,
+// the split that owns position pos[b] rotates k, appends k/v to the cache and uses them from LDS
+struct AttnDecodeArgs : AttnOperands {
+  int batch;
+  int L;                                        // kv length used when kv_len == null
+  const int* kv_len;                            // optional device [batch]; null = every sequence holds exactly L keys (one dependent load less)
   const int* pos;                               // device [batch]; kv_len[b] must be pos[b] + 1
-  const void* k_new; const void* v_new; int64_t new_sb;   // raw k / v of the new token: [b][kv_heads*128] views, batch stride
-  int o_pack_nb;                                // != 0: O is written as packed x ([b][q_heads*128] rows, common.h) for the o_proj GEMV
   // fp8 KV cache (BASELINE configs[4]): K / V point at OCP e4m3 bytes in the SAME [b, kv_heads, L, 128] layout (strides in elements),
   // with one fp32 scale per (sequence, kv head, key): k_scale / v_scale [b][kv_heads][scale_cap]; rope must be null (the new token is
   // rotated, appended and quantised before the call)
@@ -293,76 +301,41 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s);
 // rope != null: q and the new k rows are rotated at positions L .. L + T - 1 and k / v are appended to the cache (rope_kv_kernel's bytes);
 // the raw new rows are read from k_new / v_new, never from the cache slots being written.  rope == null: Q is rotated and the cache already
 // holds L + T keys.  Partials go to ws as a batch of T rows (attn_decode_ws_bytes(T, q_heads, L + T)), merged by the decode merge.
-struct AttnVerifyArgs {
-  const void* Q; int64_t q_sb, q_sh;            // [T, q_heads, 128] (row stride q_sb)
-  void* K; int64_t k_sh, k_sr;                  // cache of the sequence [kv_heads, cap, 128]
-  void* V; int64_t v_sh, v_sr;
-  void* O; int64_t o_sb, o_sh;                  // [T, q_heads, 128]
-  int T, q_heads, kv_heads, L;
-  float scale;
-  float* ws; size_t ws_bytes;
-  const float* rope; int rope_max;              // cos/sin table [max_pos][64][2] or null
-  const void* k_new; const void* v_new; int64_t new_sb;   // raw k / v rows [T][kv_heads * 128], row stride new_sb
-  int o_pack_nb;                                // != 0: O in the packed x layout (common.h) for the batched o_proj GEMV
-};
-constexpr int VERIFY_MAX_T = 16;
-int launch_attn_verify(int dtype, const AttnVerifyArgs& a, hipStream_t s);
-int attn_verify_tpw(int keys, int kv_heads);      // 64-key tiles per split of launch_attn_verify over `keys` keys
-
+// ATTN_VERIFY: S = T <= 16 with T n_rep <= 128, L; Q / O [T, q_heads, 128], K / V the cache of the sequence [kv_heads, cap, 128] (k_sb / v_sb unread).
+//
 // Split-KV block attention of omchat_prefill_extend: Sq new query rows of ONE sequence at positions L .. L + Sq - 1 (Q already
 // rotated) over the L + Sq keys its cache already holds; row t sees keys 0 .. L + t.  The keys are split over workgroups for any Sq (16-token
 // query chunks x key splits), partials in ws (attn_extend_ws_bytes), folded by the decode merge.  q_heads / kv_heads <= 8.
-struct AttnExtendArgs {
-  const void* Q; int64_t q_sb, q_sh;            // [Sq, q_heads, 128] (row stride q_sb)
-  const void* K; int64_t k_sh, k_sr;            // cache of the sequence [kv_heads, cap, 128]
-  const void* V; int64_t v_sh, v_sr;
-  void* O; int64_t o_sb, o_sh;                  // [Sq, q_heads, 128]
-  int Sq, q_heads, kv_heads, L;
-  float scale;
-  float* ws; size_t ws_bytes;
-};
-size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L);
-int launch_attn_extend(int dtype, const AttnExtendArgs& a, hipStream_t s);
-
+// ATTN_EXTEND: S = Sq, L; Q / O [Sq, q_heads, 128], K / V as for ATTN_VERIFY; rope must be null and o_pack_nb 0.
+//
 // Shared-prompt decode attention (omchat_group_begin with share = 1): G groups of N consecutive rows, one query token per
 // row.  The rows of a group share the keys [0, P), which only its first row (the leader, row g N) holds; every row holds its own keys
 // [P, len) in its own cache row.  The prefix is read once per group for the N x n_rep query rows, never beyond P; the suffix per row.
 // L = keys per row counting the new one; with kv_len (device [G N]: the true lengths, all <= L) L only sizes the grid and the workspace.
 // rope != null: q is rotated at len - 1, the new key (k_new / v_new row of the sequence) is rotated and appended at slot len - 1 of the row's
 // own cache; rope == null: Q is rotated and the caches are complete.  N <= 16, N n_rep <= 128.
-struct AttnSharedArgs {
-  const void* Q; int64_t q_sb, q_sh;            // [G N, q_heads, 128] (row stride q_sb)
-  void* K; int64_t k_sb, k_sh, k_sr;            // caches [G N rows, kv_heads, cap, 128]
-  void* V; int64_t v_sb, v_sh, v_sr;
-  void* O; int64_t o_sb, o_sh;                  // [G N, q_heads, 128]
-  int G, N, q_heads, kv_heads, P, L;
-  const int* kv_len;
-  float scale;
-  float* ws; size_t ws_bytes;                   // attn_shared_ws_bytes(G, N, q_heads, kv_heads, P, L)
-  const float* rope; int rope_max;
-  const void* k_new; const void* v_new; int64_t new_sb;   // raw k / v rows [G N][kv_heads * 128], row stride new_sb
-  int o_pack_nb;
-};
-size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L);
-int launch_attn_shared(int dtype, const AttnSharedArgs& a, hipStream_t s);
-
+// ATTN_SHARED: G, N, P, L, kv_len (optional); Q / O [G N, q_heads, 128], K / V caches [G N rows, kv_heads, cap, 128]; ws of attn_shared_ws_bytes.
+//
 // Suffix-pass attention of omchat_prefill_suffixes: N rows of S query tokens each (Q already rotated, b-major), row j valid
 // below kv_len[j] - P.  Query (j, t) sees the keys [0, P) of row 0 (the leader) and the keys [P, P + t] of row j's own cache; no slot >= P of
 // the leader is read through the prefix, no slot < P of a sibling j > 0, no slot >= kv_len[j] of any row.  One attention launch and one
 // merge whatever N is.  Rows t >= kv_len[j] - P are padding: computed from the row's valid keys, finite when the padding q is.
 // q_heads / kv_heads <= 8, N S <= 65535.
-struct AttnSuffixArgs {
-  const void* Q; int64_t q_sb, q_sh;            // [N S, q_heads, 128] (row stride q_sb)
-  const void* K; int64_t k_sb, k_sh, k_sr;      // caches [N rows, kv_heads, cap, 128]
-  const void* V; int64_t v_sb, v_sh, v_sr;
-  void* O; int64_t o_sb, o_sh;                  // [N S, q_heads, 128]
-  int N, S, q_heads, kv_heads, P;
-  const int* kv_len;                            // device [N]: keys row j holds counting its suffix, in [P + 1, P + S]
-  float scale;
-  float* ws; size_t ws_bytes;                   // attn_suffix_ws_bytes(N, S, q_heads, kv_heads, P)
+// ATTN_SUFFIX: N, S, P, kv_len (device [N]: keys row j holds counting its suffix, in [P + 1, P + S]); Q / O [N S, q_heads, 128], K / V caches
+// [N rows, kv_heads, cap, 128]; ws of attn_suffix_ws_bytes; rope must be null and o_pack_nb 0.
+enum AttnBlockMode { ATTN_VERIFY = 0, ATTN_EXTEND, ATTN_SHARED, ATTN_SUFFIX };
+struct AttnBlockArgs : AttnOperands {
+  int mode;                                     // AttnBlockMode: which of the four contracts above holds; the integers it does not name are ignored
+  int G, N, S, P, L;
+  const int* kv_len;
 };
+constexpr int VERIFY_MAX_T = 16;
+size_t attn_block_ws_bytes(const AttnBlockArgs& a);      // bytes of partials the launch needs: reads the mode, its integers and the heads only
+int launch_attn_block(int dtype, const AttnBlockArgs& a, hipStream_t s);
+int attn_verify_tpw(int keys, int kv_heads);      // 64-key tiles per split of an ATTN_VERIFY launch over `keys` keys
+size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L);
+size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L);
 size_t attn_suffix_ws_bytes(int N, int S, int q_heads, int kv_heads, int P);
-int launch_attn_suffix(int dtype, const AttnSuffixArgs& a, hipStream_t s);
 
 // batch-1 decode on one GPU (fused_decode.hip, round 4): launch_attn_decode + the o_proj GEMV with EPI_RESID as ONE launch, same bits.
 // x [H] is the residual stream (read, x + o_proj(attn) written in place), Wo [H][qd] row-major; ws = fused_decode_ws_bytes(q_heads) bytes

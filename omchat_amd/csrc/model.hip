@@ -1161,7 +1161,7 @@ static bool extend_attn_split(int S, int keep, int kv_heads) {
 }
 extern "C" int omchat_extend_attn_form(int S_new, int keep, int Hkv) { return extend_attn_split(S_new, keep, Hkv) ? 1 : 0; }
 
-// Attention form of omchat_prefill_suffixes.  Over forked rows both the suffix kernel (launch_attn_suffix: the leader's
+// Attention form of omchat_prefill_suffixes.  Over forked rows both the suffix kernel (launch_attn_block ATTN_SUFFIX: the leader's
 // prompt keys once per 16 flat query rows) and the batched prefill kernel with q_pos0 = keep (every row walks its own copy) are correct; over
 // a shared prompt only the first is.  Measured alone with tools/bench_suffix.py (28 / 4 heads, bf16, 3584 prompt keys, 32-token suffixes; LOG.md): the
 // suffix kernel + merge 34 / 59 / 97 us at N = 4 / 8 / 16, the prefill kernel 103 - 104 us at all three (its cdiv(S, 32) kv_heads N workgroups walk
@@ -1240,25 +1240,14 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     RopeArgs r{ctx->tw_qkv, qkvd, rows, S, c.t_heads, c.t_kv_heads, nullptr, keep, ctx->rope, c.max_seq, kc, vc, ctx->cache_sb(), ctx->cache_sh()};
     if (sfx) r.kv_end = ctx->d_len;      // (keep + lengths[i] at this point)
     TRY(launch_rope_kv(ctx->dt, r, s));
-    if (sfx_attn) {
-      AttnSuffixArgs e{};
-      e.Q = ctx->tw_qkv; e.q_sb = qkvd; e.q_sh = 128;
-      e.K = kc; e.k_sb = ctx->cache_sb(); e.k_sh = ctx->cache_sh(); e.k_sr = 128;
-      e.V = vc; e.v_sb = e.k_sb; e.v_sh = e.k_sh; e.v_sr = 128;
-      e.O = ctx->tw_ao; e.o_sb = qd; e.o_sh = 128;
-      e.N = b; e.S = S; e.q_heads = c.t_heads; e.kv_heads = c.t_kv_heads; e.P = keep; e.kv_len = ctx->d_len; e.scale = 0.08838834764831845f;
+    if (sfx_attn || split_attn) {      // split_attn: few new rows over many cached keys, the keys split across workgroups (ATTN_EXTEND)
+      AttnBlockArgs e{};
+      ctx->bind_attn(e, i, false);
       e.ws = (float*)ctx->ext_ws.p; e.ws_bytes = ctx->ext_ws.cap;
-      TRY(launch_attn_suffix(ctx->dt, e, s));
-    }
-    if (split_attn) {      // few new rows over many cached keys: the keys split across workgroups (launch_attn_extend)
-      AttnExtendArgs e{};
-      e.Q = ctx->tw_qkv; e.q_sb = qkvd; e.q_sh = 128;
-      e.K = kc; e.k_sh = ctx->cache_sh(); e.k_sr = 128;
-      e.V = vc; e.v_sh = e.k_sh; e.v_sr = 128;
-      e.O = ctx->tw_ao; e.o_sb = qd; e.o_sh = 128;
-      e.Sq = S; e.q_heads = c.t_heads; e.kv_heads = c.t_kv_heads; e.L = keep; e.scale = 0.08838834764831845f;
-      e.ws = (float*)ctx->ext_ws.p; e.ws_bytes = ctx->ext_ws.cap;
-      TRY(launch_attn_extend(ctx->dt, e, s));
+      e.S = S;
+      if (sfx_attn) { e.mode = ATTN_SUFFIX; e.N = b; e.P = keep; e.kv_len = ctx->d_len; }
+      else { e.mode = ATTN_EXTEND; e.L = keep; }
+      TRY(launch_attn_block(ctx->dt, e, s));
     }
     AttnArgs a{};
     a.Q = ctx->tw_qkv; a.q_sb = (int64_t)S * qkvd; a.q_sh = 128; a.q_sr = qkvd;
@@ -1267,7 +1256,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     a.O = ctx->tw_ao; a.o_sb = (int64_t)S * qd; a.o_sh = 128; a.o_sr = qd;
     a.batch = b; a.q_heads = c.t_heads; a.kv_heads = c.t_kv_heads; a.Sq = S; a.Skv = keep + S; a.kv_len = ctx->d_len; a.causal = 1; a.q_pos0 = keep;
     a.kv_start = left ? ctx->d_start : nullptr;
-    a.scale = 0.08838834764831845f;
+    a.scale = omchat_ctx::T_ATTN_SCALE;
     if (!split_attn && !sfx_attn) TRY(launch_attn_prefill(ctx->dt, a, s));
     // left-padded batch: a padded query row sees no key at all; the reference's eager attention (the CPU path) then attends EVERY key of
     // the sequence with weight 1 / S (all scores are finfo.min -> softmax uniform, future keys included), and these rows' K / V in the
@@ -1454,7 +1443,7 @@ static bool mx4_rows_ok(const omchat_ctx* ctx, int rows) { return ctx->mxfp4_mod
 // exact_len: every sequence holds exactly Lmax keys after this step (eager launches only): the attention launches then take the length
 // as a kernel argument instead of loading d_len first -- one dependent memory round trip less in two latency-bound launches per layer.
 // vL >= 0: prompt-lookup verify step (omchat_decode_verify) -- the b rows are consecutive tokens of sequence 0 at positions vL .. vL + b - 1
-// (multi-query attention, launch_attn_verify), and next_tokens receives the greedy pick of every row without moving any position.
+// (multi-query attention, launch_attn_block ATTN_VERIFY), and next_tokens receives the greedy pick of every row without moving any position.
 static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, float* logits, int32_t* next_tokens, hipStream_t s, bool allow_prof,
                        bool exact_len = false, bool masked = false, int vL = -1, bool vsample = false) {
   const omchat_config& c = ctx->c;
@@ -1553,7 +1542,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     // launches below).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     if (g_decode_layer && n1 && exact_len && !masked && !wq && !(ctx->fp8_kv && ctx->kv8_valid) && ctx->dl_ws) {      // (the layer kernel has no key mask)
       DecodeLayerArgs d{L.ln1, L.ln2, W16[QKV].W, L.bqkv, W16[O].W, W16[GU].W, W16[DOWN].W, kc, vc, ctx->cache_sh(), x, H, qd, ctx->t_kvdim, It, c.t_heads, c.t_kv_heads, Lmax,
-                        ctx->rope, c.max_seq, c.t_eps, 0.08838834764831845f, ctx->dl_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
+                        ctx->rope, c.max_seq, c.t_eps, omchat_ctx::T_ATTN_SCALE, ctx->dl_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       if (decode_layer_ok(d)) {
         const bool mark_l = allow_prof && i == c.t_layers / 2;      // HIP-event bracket on one layer per token (bench.py roofline)
         if (mark_l) ctx->prof_mark(OMCHAT_PROF_DECODE_GATEUP, s);
@@ -1575,15 +1564,10 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     // RoPE + KV append are fused into the attention kernel (q rotated in registers, the split that owns the new
     // position rotates k and appends k / v)
     AttnDecodeArgs a{};
-    a.Q = ctx->tw_qkv; a.q_sb = qkvd; a.q_sh = 128;
-    a.K = kc; a.k_sb = ctx->cache_sb(); a.k_sh = ctx->cache_sh(); a.k_sr = 128;
-    a.V = vc; a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_sr = 128;
-    a.O = ctx->tw_ao; a.o_sb = qd; a.o_sh = 128;
-    a.batch = b; a.q_heads = c.t_heads; a.kv_heads = c.t_kv_heads; a.L = Lmax; a.kv_len = ctx->d_len; a.scale = 0.08838834764831845f;
+    ctx->bind_attn(a, i, true);
     a.ws = ctx->tw_attn_ws; a.ws_bytes = ctx->tw_attn_ws_bytes;
-    a.rope = ctx->rope; a.rope_max = c.max_seq; a.pos = ctx->d_pos;
-    a.k_new = (const char*)ctx->tw_qkv + (size_t)qd * 2; a.v_new = (const char*)ctx->tw_qkv + (size_t)(qd + ctx->t_kvdim) * 2; a.new_sb = qkvd;
-    if (exact_len) a.kv_len = nullptr;
+    a.o_pack_nb = fused ? pk : 0;
+    a.batch = b; a.L = Lmax; a.kv_len = exact_len ? nullptr : ctx->d_len; a.pos = ctx->d_pos;
     if (masked) { a.key_mask = ctx->d_mask; a.mask_sb = ctx->mask_sb; }      // d_pos holds the given RoPE positions, every row has Lmax keys
     if (ctx->fp8_kv && ctx->kv8_valid) {
       // fp8 KV cache: rotate q / k and append to the 16-bit cache with the prefill's kernel, quantise the new row, then attend over e4m3
@@ -1604,7 +1588,6 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       a.K = (char*)ctx->k8cache + off; a.V = (char*)ctx->v8cache + off;
       a.k_scale = ctx->ks8 + so; a.v_scale = ctx->vs8 + so; a.scale_sb = (int64_t)c.t_kv_heads * c.max_seq; a.scale_sh = c.max_seq;
     }
-    a.o_pack_nb = fused ? pk : 0;
     // batch 1, one GPU (round 4): attention + merge + o_proj (+ residual) as ONE launch with in-launch hand-offs (fused_decode.hip; the same
     // bits as the three launches).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     bool ao_oproj = false;
@@ -1613,27 +1596,16 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       // sampled group sharing its prompt (omchat_group_begin): the prompt keys once per group, each row's own keys per row; the lengths come
       // from the device, Lmax (the suffix bucket, omchat_decode_step) sizes the grid -- the same launch eager and captured
       const GroupState& G = ctx->group;
-      AttnSharedArgs sa{};
-      sa.Q = ctx->tw_qkv; sa.q_sb = qkvd; sa.q_sh = 128;
-      sa.K = kc; sa.k_sb = ctx->cache_sb(); sa.k_sh = ctx->cache_sh(); sa.k_sr = 128;
-      sa.V = vc; sa.v_sb = sa.k_sb; sa.v_sh = sa.k_sh; sa.v_sr = 128;
-      sa.O = ctx->tw_ao; sa.o_sb = qd; sa.o_sh = 128;
-      sa.G = G.b; sa.N = G.N; sa.q_heads = c.t_heads; sa.kv_heads = c.t_kv_heads; sa.P = G.P; sa.L = Lmax; sa.kv_len = ctx->d_len; sa.scale = a.scale;
+      AttnBlockArgs sa{};
+      static_cast<AttnOperands&>(sa) = a;      // the step's binding (16-bit cache: omchat_decode_step refuses this mode over the e4m3 one)
       sa.ws = (float*)G.ws.p; sa.ws_bytes = G.ws.cap;
-      sa.rope = ctx->rope; sa.rope_max = c.max_seq; sa.k_new = a.k_new; sa.v_new = a.v_new; sa.new_sb = qkvd;
-      sa.o_pack_nb = a.o_pack_nb;
-      TRY(launch_attn_shared(ctx->dt, sa, s));
+      sa.mode = ATTN_SHARED; sa.G = G.b; sa.N = G.N; sa.P = G.P; sa.L = Lmax; sa.kv_len = ctx->d_len;
+      TRY(launch_attn_block(ctx->dt, sa, s));
     } else if (vL >= 0) {
-      AttnVerifyArgs va{};
-      va.Q = ctx->tw_qkv; va.q_sb = qkvd; va.q_sh = 128;
-      va.K = kc; va.k_sh = ctx->cache_sh(); va.k_sr = 128;
-      va.V = vc; va.v_sh = ctx->cache_sh(); va.v_sr = 128;
-      va.O = ctx->tw_ao; va.o_sb = qd; va.o_sh = 128;
-      va.T = b; va.q_heads = c.t_heads; va.kv_heads = c.t_kv_heads; va.L = vL; va.scale = a.scale;
-      va.ws = ctx->tw_attn_ws; va.ws_bytes = ctx->tw_attn_ws_bytes;
-      va.rope = ctx->rope; va.rope_max = c.max_seq; va.k_new = a.k_new; va.v_new = a.v_new; va.new_sb = qkvd;
-      va.o_pack_nb = a.o_pack_nb;
-      TRY(launch_attn_verify(ctx->dt, va, s));
+      AttnBlockArgs va{};
+      static_cast<AttnOperands&>(va) = a;      // ... as does omchat_decode_verify
+      va.mode = ATTN_VERIFY; va.S = b; va.L = vL;
+      TRY(launch_attn_block(ctx->dt, va, s));
     } else if (fuse_ao) {
       FusedDecodeArgs fa{W16[O].W, qd, x, H, qd, ctx->fd_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       TRY(launch_attn_oproj_fused(ctx->dt, a, fa, s));

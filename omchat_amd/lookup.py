@@ -7,7 +7,7 @@ handling, the stopping criteria and the streamer one by one, as the greedy loop 
 (decode_step, decode_verify, kv_rewind), so tests drive the loop with a fake one."""
 import torch
 
-MAX_LOOKUP_TOKENS = 15      # a verify step runs at most 16 rows (the last emitted token + 15 drafts; launch_attn_verify)
+MAX_LOOKUP_TOKENS = 15      # a verify step runs at most 16 rows (the last emitted token + 15 drafts; launch_attn_block, ATTN_VERIFY)
 
 
 class PromptLookupDrafter:

@@ -84,7 +84,7 @@ def test_op_verify_attention(gpu_lib, dt, Hq, Hkv):
 
 @pytest.mark.parametrize("Hq,Hkv,T,L", [(28, 4, 8, 32764), (28, 4, 16, 32956), (28, 4, 2, 33000), (7, 1, 9, 40000), (7, 1, 16, 4090)])
 def test_op_verify_long_context(gpu_lib, Hq, Hkv, T, L):
-    """long contexts take several 64-key tiles per split (launch_attn_verify's tpw > 1: the tile loop, the LDS hand-over between tiles, the
+    """long contexts take several 64-key tiles per split (launch_attn_block's ATTN_VERIFY plan, tpw > 1: the tile loop, the LDS hand-over between tiles, the
     rescale of the online softmax, the merge over splits of 64 tpw keys); the new rows straddle a tile inside a split (32764 + 8) and a split
     boundary (32956 + 16 at 5 tiles per split on 256 CUs), with the fused RoPE + append checked against rope_kv's bytes"""
     dt = "bf16"

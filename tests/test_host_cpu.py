@@ -704,3 +704,50 @@ def test_pmc_symbol_patterns_match_the_built_library():
     optional = {"vit_qk_sumsq_kernel", "gemv_kernel", "attn_kernel", "gemm8p_kernel"}
     for fam in kernel_roles.FAMILIES:
         assert fam in optional or any(fam + "I" in s or fam + "E" in s or fam in s for s in stubs), fam
+
+
+# (entry point omchat_op_attn_<name>, arguments, bytes -- or tiles per split) as a library built before the four block-attention launchers were
+# folded into launch_attn_block answered, at the 256 compute units that the sizing falls back to without a device (the MI355X's own count).
+# Each plan takes tiles-per-split 1 and > 1; the inputs that size nothing answer 0.
+_ATTN_WS_TABLE = [
+    ("decode_ws", (3, 28, 4000), 2794176),
+    ("decode_ws", (1, 28, 1), 14784),
+    ("decode_ws", (16, 40, 65), 675840),
+    ("decode_ws", (0, 28, 100), 0),
+    ("decode_ws", (2, 28, 0), 0),
+    ("verify_tpw", (40000, 4), 5),
+    ("verify_tpw", (3000, 4), 1),
+    ("verify_tpw", (32769, 4), 5),
+    ("verify_tpw", (1000000, 8), 8),
+    ("verify_tpw", (0, 4), 1),
+    ("extend_ws", (40, 28, 4, 9000), 21288960),
+    ("extend_ws", (16, 28, 4, 1000), 3784704),
+    ("extend_ws", (700, 28, 4, 100), 20697600),
+    ("extend_ws", (1, 40, 8, 0), 21120),
+    ("extend_ws", (0, 28, 4, 100), 0),
+    ("extend_ws", (5, 28, 0, 300), 369600),
+    ("shared_ws", (2, 4, 28, 4, 3000, 3300), 6150144),
+    ("shared_ws", (8, 4, 28, 4, 20000, 20100), 8515584),
+    ("shared_ws", (1, 16, 28, 4, 1, 2), 473088),
+    ("shared_ws", (0, 4, 28, 4, 100, 200), 0),
+    ("shared_ws", (2, 0, 28, 4, 100, 200), 0),
+    ("shared_ws", (2, 4, 28, 4, 300, 300), 0),
+    ("shared_ws", (2, 4, 28, 4, 0, 200), 0),
+    ("shared_ws", (2, 4, 28, 0, 100, 200), 0),
+    ("suffix_ws", (5, 70, 28, 4, 3000), 36220800),
+    ("suffix_ws", (2, 5, 28, 4, 500), 1330560),
+    ("suffix_ws", (3, 600, 28, 4, 1000), 133056000),
+    ("suffix_ws", (0, 5, 28, 4, 500), 0),
+    ("suffix_ws", (2, 0, 28, 4, 500), 0),
+    ("suffix_ws", (2, 5, 28, 4, 0), 0),
+    ("suffix_ws", (2, 5, 28, 0, 500), 0),
+]
+
+
+@pytest.mark.parametrize("name,args,want", _ATTN_WS_TABLE, ids=[f"{n}{a}".replace(" ", "") for n, a, _ in _ATTN_WS_TABLE])
+def test_split_kv_workspace_sizing_is_pinned(name, args, want):
+    """the workspace sizes and the verify plan that model.hip, the op hooks and the tests allocate by: one sizing function serves the four
+    block-attention modes (attn_block_ws_bytes), and what it answers must stay what each mode's own function answered"""
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the table is recorded for 256 compute units")
+    assert getattr(_lib.lib(), "omchat_op_attn_" + name)(*args) == want
