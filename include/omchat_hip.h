@@ -232,6 +232,23 @@ int omchat_fsm_load(omchat_ctx* ctx, int n_states, const int32_t* off, const int
 int omchat_fsm_begin(omchat_ctx* ctx, int b, const int32_t* start_states, int max_new, void* stream);
 /* the current states of rows 0..b-1 (host int32 [b]; OMCHAT_FSM_DEAD included).  Synchronises the device. */
 int omchat_fsm_states(omchat_ctx* ctx, int b, int32_t* out, void* stream);
+/* ---- classifier-free guidance (generate(guidance_scale=)) ------------------------------------------------------------- */
+/* omchat_set_guidance: from now on rows 0..b-1 of this context are the conditional rows and rows b..2b-1 their twins, which hold the negative
+ * prompt.  omchat_greedy, omchat_sample and omchat_decode_step then take exactly 2b rows (of logits / of tokens) and pick b ids from
+ *   scores[r] = scale * (lc - lu) + lu,   lc = log_softmax(logits[r]), lu = log_softmax(logits[b + r])
+ * (HF's UnbatchedClassifierFreeGuidanceLogitsProcessor), written to the context-owned copy in front of the bans of omchat_set_constraints and
+ * the automaton of omchat_fsm_begin; where either logit is -inf the score is -inf (HF's formula has NaN there).  next_tokens has 2b entries:
+ * the twins get their rows' ids, written on the device, and a decode step moves the positions of all 2b rows.  Sampling state, ban history,
+ * automaton states and the log-prob record belong to the b conditional rows: their setters keep taking b.  The record's raw number is the
+ * conditional row's raw log-softmax; the processed one is that of the guided scores as the pick saw them.  omchat_kv_rewind(ctx, 2b, n)
+ * takes back 2b cache rows and b rows of pick state.  Any other row count is refused before anything is enqueued, as are, while guidance
+ * is on, omchat_beam_begin, omchat_decode_verify, omchat_group_begin and the masked decode steps.  Refused here: a tensor-parallel context
+ * (the exchange of the two log-sum-exps is not built), 2b > max_batch, a scale that is not finite, a beam search or a sampled group in
+ * progress.  b = 0 switches the stage off: no launch, no graph node remains.  Sticky like the sampler's state.  b, the scale and the
+ * buffers are kernel arguments of the captured decode graphs: a change drops them, the same b and scale keep them.  The workspace
+ * (max_batch rows of tile partials) and the copy are context-owned and counted in omchat_device_bytes.  Deterministic: the same logits
+ * give the same scores, bit for bit, eager or in a graph. */
+int omchat_set_guidance(omchat_ctx* ctx, int b, float scale, void* stream);
 /* ---- per-token log-probabilities of the picked ids (generate(output_logprobs=True)) ---------------------------------- */
 /* omchat_set_logprobs: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both
  * masked steps, the captured decode graph -- also records two fp32 numbers on the device, without a host sync: raw = log_softmax(logits)[id]
@@ -788,6 +805,13 @@ int omchat_op_constrain(const int32_t* hist_ids, const int32_t* hist_len, const 
  * int32 [b] = the rows' states after the advance.  Synchronises. */
 int omchat_op_fsm(int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, const int32_t* states, const int32_t* fed, int b, int V,
                   int V_total, int rank, const float* logits, float* out, int32_t* new_states, void* stream);
+
+/* context-free guidance stage of omchat_set_guidance (test hook): logits device fp32 [2b][ld], rows [0, b) conditional, rows [b, 2b) their
+ * twins, V <= ld ids per row (any V; 16-byte accesses when ld % 4 == 0 and the base is aligned, scalar ones otherwise); out device fp32
+ * [b][ld_out], ld_out >= V; ws device memory of omchat_op_guidance_ws(b, V) bytes, 8-byte aligned.  Enqueues two launches, does not
+ * synchronise. */
+size_t omchat_op_guidance_ws(int b, int V);
+int omchat_op_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, void* stream);
 
 /* context-free sampler over logits fp32 [b, V] with the parameters of omchat_set_sampling; every row at step `step`.  thr_out (device uint32 [b]
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */

@@ -59,6 +59,9 @@ _SIGS = {
     "omchat_fsm_begin": (_i, [_vp, _i, _vp, _i, _vp]),
     "omchat_fsm_states": (_i, [_vp, _i, _vp, _vp]),
     "omchat_op_fsm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "omchat_set_guidance": (_i, [_vp, _i, _f, _vp]),
+    "omchat_op_guidance_ws": (_sz, [_i, _i]),
+    "omchat_op_guidance": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
     "omchat_set_logprobs": (_i, [_vp, _i, _i, _vp]),

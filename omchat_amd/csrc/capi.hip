@@ -739,6 +739,12 @@ extern "C" int omchat_op_fsm(int n_states, const int32_t* off, const int32_t* to
   return rc;
 }
 
+extern "C" size_t omchat_op_guidance_ws(int b, int V) { return b >= 1 && V >= 1 ? guidance_ws_bytes(b, V) : 0; }
+
+extern "C" int omchat_op_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, void* stream) {
+  return launch_guidance(logits, ld, b, V, scale, ws, out, ld_out, S(stream));
+}
+
 extern "C" size_t omchat_beam_state_words(int b, int N, int max_new) { return beam_state_words(b, N, max_new); }
 
 extern "C" int omchat_op_beam_select(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty,

@@ -28,7 +28,8 @@ struct Grown {
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-// The token pick of a step (pick.hip): ban stage, argmax or sampler, record stage -- with everything the three stages keep between picks.
+// The token pick of a step (pick.hip): guidance stage, ban stage, automaton stage, argmax or sampler, record stage -- with everything the
+// stages keep between picks.
 struct PickState {
   void* arg_scratch = nullptr;      // partials of the two-stage argmax
   float* tp_table = nullptr;        // (max, index) / sampler exchange table under tensor parallelism
@@ -107,6 +108,14 @@ struct PickState {
   int *fsm_cnt = nullptr;
   int32_t* fsm_cur = nullptr;
   uint32_t* fsm_bm = nullptr; int fsm_bmw = 0;
+  // classifier-free guidance (omchat_set_guidance; guidance.hip): while it is on for b rows a pick is handed 2b rows of logits -- rows
+  // [b, 2b) the twins over the negative prompt -- and picks b ids from the guided scores, which the stage writes to con_logits (shared
+  // with the two stages behind it); every other piece of pick state keeps b rows.  gd_ws: the tile partials of the two log-sum-exps
+  struct Guidance { bool on = false; int b = 0; float scale = 1.f; };
+  Guidance gd;
+  void* gd_ws = nullptr;
+  bool guidance_on() const { return gd.on; }
+  int pick_rows(int rows) const { return gd.on ? rows / 2 : rows; }      // the rows that pick, of the rows a step runs
   bool sampling_on() const { return smp.on; }
   bool constraints_on() const { return con.on; }
   bool logprobs_on() const { return lp.on; }
@@ -454,3 +463,5 @@ void pick_verify_committed(omchat_ctx* ctx, int n_picks);      // the acceptance
 int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s);      // a step that picks nothing still feeds the history
 const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n);      // why the pick state cannot go back n steps, or NULL
 int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s);
+// while guidance is on for b rows a step, a pick or a rewind takes exactly 2b rows: why `rows` will not do, or NULL (NULL when it is off)
+const char* pick_rows_refusal(omchat_ctx* ctx, int rows);

@@ -558,6 +558,14 @@ int launch_fsm_apply(const float* logits, int ld, const FsmArgs& a, float* out, 
 int launch_fsm_advance(const FsmTable& T, const FsmArgs& a, hipStream_t s);      // a step that picks nothing: trail and cnt move, no mask
 int launch_fsm_rewind(int* cnt, int b, int n, hipStream_t s);                    // cnt = max(cnt - n, 0)
 int fsm_validate(int n_states, const int32_t* off, const int32_t* tok, const int32_t* nxt, int V_total);      // host arrays; sets the error
+// classifier-free guidance (guidance.hip; tests/guidance_ref.py restates it): logits fp32 [2b][ld], rows [0, b)
+// conditional, rows [b, 2b) their twins; out [b][ld_out] = scale * (lc - lu) + lu over the V ids of a row (ld, ld_out >= V), lc / lu the two
+// log-softmaxes; -inf wherever either logit is -inf.  ws: guidance_ws_bytes(b, V) bytes, written and read by the two launches of one call.
+// Deterministic (fixed reduction orders, no atomics).
+size_t guidance_ws_bytes(int b, int V);
+int launch_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, hipStream_t s);
+// behind the pick: next_tokens[b + r] = next_tokens[r]; with pos / len (both or neither) pos += 1, len += 1 for all 2b rows
+int launch_guidance_twin(int32_t* next_tokens, int b, int* pos, int* len, hipStream_t s);
 // beam search (beam.hip; tests/beam_ref.py restates it).  The vocabulary is cut into beam_slices(V, tp) equal slices
 // of at most BEAM_SLICE_CAP ids, the same at every TP degree; a rank owns ns / tp whole slices.  Exchange table: [rows][ns][4 + 2K] fp32.
 constexpr int BEAM_KMAX = 32;            // candidates kept per step and prompt: max(2, 1 + n_eos) * N

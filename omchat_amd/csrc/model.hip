@@ -1767,6 +1767,7 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(b >= 1 && b <= c.max_batch, "batch exceeds max_batch");
   OM_CHECK(mx4_rows_ok(ctx, b), MX4_ROWS_MSG);
+  if (const char* why = pick_rows_refusal(ctx, b)) OM_CHECK(false, why);
   int Lmax = 0;
   OM_CHECK(!ctx->left_padded, "per-sequence decode after a left-padded prefill: use omchat_decode_step_masked (the reference positions such a "
                               "batch with sum(mask) - 1 and a per-row key mask, omchat_arch.py:61-70; DESIGN.md section 7)");
@@ -1850,6 +1851,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(!why, why);
   OM_CHECK(!ctx->pick.constraints_on(), "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
   OM_CHECK(!ctx->pick.fsm_on(), "a token FSM is on: each verify row would need its own state (omchat_fsm_begin with b = 0 first)");
+  OM_CHECK(!ctx->pick.guidance_on(), "guidance is on: each verify row would need its twin (omchat_set_guidance with b = 0 first)");
   OM_CHECK(!ctx->beam.on(), "a beam search is active");
   OM_CHECK(!ctx->group.on(), "a sampled group shares its prompt: a verify step runs one sequence (omchat_group_begin with b = 0 first)");
   OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
@@ -1893,6 +1895,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   OM_CHECK(mx4_rows_ok(ctx, b), MX4_ROWS_MSG);
   OM_CHECK(ctx->dec_mode != 1, "omchat_decode_step_masked after omchat_decode_step on the same prefill: the two place the cache rows differently");
   OM_CHECK(ctx->tp_size == 1, "masked decode: one GPU (under tensor parallelism right-padded batches take the per-sequence step)");
+  OM_CHECK(!ctx->pick.guidance_on(), "masked decode: guidance is on, and its twin rows run at their own lengths (omchat_set_guidance with b = 0 first)");
   OM_CHECK(!ctx->group.on(), "masked decode: a sampled group shares its prompt, and the shared attention has no key mask (omchat_group_begin with b = 0 first)");
   OM_CHECK(ctx->pre_S + ctx->masked_steps + 1 <= c.max_seq, "KV cache full (max_seq)");
   if (!ctx->d_mask) {

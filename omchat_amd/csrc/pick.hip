@@ -1,4 +1,4 @@
-// The token pick of a step, with its state (PickState, ctx.h): the ban stage of the logits constraints (constrain.hip), the automaton
+// The token pick of a step, with its state (PickState, ctx.h): the guidance stage (guidance.hip), the ban stage of the logits constraints (constrain.hip), the automaton
 // stage of the token FSM (fsm.hip), the argmax (elementwise.hip) or the sampler (sample.hip), the record stage of the per-token log-probabilities (logprob.hip) -- their order, the
 // refusals and host counters in front of a step, their setters and their rewind.  model.hip sees the functions ctx.h declares.  Host C++.
 #include "ctx.h"
@@ -78,8 +78,22 @@ int fsm_stage(omchat_ctx* ctx, const float** lg, int b, const int32_t* fed, hipS
   return 0;
 }
 
-// The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits, proc = what the pick ran on (the
-// banned copy when constraints are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
+// The guidance stage in front of the ban stage (omchat_set_guidance; nothing when it is off): the pick was handed 2b rows; *lg then points
+// at the context's copy with the b rows of guided scores, which the stages behind it write in place, and *b is the b rows that pick.
+int guidance_stage(omchat_ctx* ctx, const float** lg, int* b, hipStream_t s) {
+  const PickState& P = ctx->pick;
+  if (!P.gd.on) return 0;
+  OM_CHECK(*b == 2 * P.gd.b, "guidance is on: a pick takes the 2b rows omchat_set_guidance was given (conditional rows, then their twins)");
+  const omchat_config& c = ctx->c;
+  TRY(launch_guidance(*lg, c.t_vocab, P.gd.b, c.t_vocab, P.gd.scale, P.gd_ws, P.con_logits, c.t_vocab, s));
+  *lg = P.con_logits;
+  *b = P.gd.b;
+  return 0;
+}
+
+// The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits (under guidance its first b rows:
+// the conditional rows' raw logits), proc = what the pick ran on (the guided scores when guidance is on, with the bans and the automaton's
+// mask when those are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
 int logprob_stage(omchat_ctx* ctx, const float* raw, const float* proc, int b, const int32_t* ids, hipStream_t s) {
   const PickState& P = ctx->pick;
   if (!P.lp.on) return 0;
@@ -165,11 +179,20 @@ int greedy_pick(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, h
 int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipStream_t s, bool advance, const int32_t* fed, bool force_greedy) {
   const PickState& P = ctx->pick;
   const float* raw = lg;
+  TRY(guidance_stage(ctx, &lg, &b, s));
+  // under guidance the pick's launches move nothing: the twin launch behind them copies the ids and moves the positions of all 2b rows
+  const bool guided = P.gd.on;
+  const bool adv = advance;
+  advance = advance && !guided;
+  auto finish = [&]() -> int {
+    if (guided) TRY(launch_guidance_twin(next_tokens, b, adv ? ctx->d_pos : nullptr, adv ? ctx->d_len : nullptr, s));
+    return logprob_stage(ctx, raw, lg, b, next_tokens, s);
+  };
   TRY(ban_stage(ctx, &lg, b, fed, s));
   TRY(fsm_stage(ctx, &lg, b, fed, s));
   if (force_greedy || !P.smp.on) {
     TRY(greedy_pick(ctx, lg, b, next_tokens, s, advance));
-    return logprob_stage(ctx, raw, lg, b, next_tokens, s);
+    return finish();
   }
   const omchat_config& c = ctx->c;
   SampleArgs a;
@@ -183,7 +206,13 @@ int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipS
   a.out = next_tokens; a.ws = P.smp_ws; a.table = P.tp_table;
   a.xchg = smp_xchg; a.xchg_user = ctx;
   TRY(launch_sample(a, s));
-  return logprob_stage(ctx, raw, lg, b, next_tokens, s);
+  return finish();
+}
+
+const char* pick_rows_refusal(omchat_ctx* ctx, int rows) {
+  const PickState& P = ctx->pick;
+  if (P.gd.on && rows != 2 * P.gd.b) return "guidance is on: this call takes exactly 2b rows -- the b conditional rows, then their twins (omchat_set_guidance with b = 0 first)";
+  return nullptr;
 }
 
 const char* pick_verify_refusal(omchat_ctx* ctx, int flags) {
@@ -224,6 +253,7 @@ void pick_verify_committed(omchat_ctx* ctx, int n_picks) { ctx->pick.smp_vcommit
 // (rows beyond those the constraints are on for are not the history's: no refusal here, unlike the ban stage of a step that picks)
 int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s) {
   const PickState& P = ctx->pick;
+  b = P.pick_rows(b);      // (under guidance the twins are fed their rows' ids: the first b of `fed`)
   if (P.con.on && b <= P.con.b) TRY(launch_constrain_append((int32_t*)P.con_hist.p, P.con_ld, P.con_len, fed, b, s));
   if (P.fsm.on && b <= P.fsm.b) TRY(launch_fsm_advance(P.fsm_tab, fsm_args(ctx, b, fed), s));
   return 0;
@@ -231,6 +261,8 @@ int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s) {
 
 const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n) {
   const PickState& P = ctx->pick;
+  if (const char* why = pick_rows_refusal(ctx, b)) return why;
+  b = P.pick_rows(b);      // 2b cache rows go back, b rows of pick state
   if (P.lp.on && b < P.lp.b) return "rewind of fewer rows than omchat_set_logprobs switched on: the rows' records would fall out of step";
   if (P.smp.on && b == 1 && P.smp_vcommit > 0 && n <= P.smp_vcommit) return nullptr;      // the picks of a sampled verify step
   if (P.smp.on && n != 1 && P.smp.penalty != 1.f) return "rewind of more than one step with the repetition penalty on: only the last pick's bit is recorded";
@@ -239,6 +271,7 @@ const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n) {
 
 int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s) {
   PickState& P = ctx->pick;
+  b = P.pick_rows(b);
   if (P.smp.on && b == 1 && P.smp_vcommit > 0 && n <= P.smp_vcommit) {
     // the last picks are a sampled verify step's: each recorded the bit it newly set
     TRY(launch_sample_rewind_verify(P.smp.penalty != 1.f ? P.smp_bm : nullptr, P.smp_vlast, P.smp_step, P.smp_vcommit, n, s));
@@ -268,6 +301,7 @@ int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s) {
 
 extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  if (const char* why = pick_rows_refusal(ctx, b)) OM_CHECK(false, why);
   TRY(lp_room(ctx));      // (in front of the refusal below as well: a full record is the first thing this call reports)
   // (the sampler's state is not this pick's: with sampling on, the first token comes from omchat_sample)
   OM_CHECK(!ctx->pick.lp.on || !ctx->pick.smp.on, "logprobs: omchat_greedy while sampling is on (omchat_sample picks the first token then)");
@@ -278,6 +312,7 @@ extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_
 // the first token after the prefill (omchat_greedy's sampled counterpart): advances the step counters, not the decode positions
 extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
+  if (const char* why = pick_rows_refusal(ctx, b)) OM_CHECK(false, why);
   TRY(pick_admit(ctx, true, false));
   return pick_run(ctx, logits, b, next_tokens, (hipStream_t)stream);
 }
@@ -648,5 +683,33 @@ extern "C" int omchat_fsm_states(omchat_ctx* ctx, int b, int32_t* out, void* str
   OM_HIP(hipMemcpy(cnt.data(), P.fsm_cnt, (size_t)b * 4, hipMemcpyDeviceToHost));
   OM_HIP(hipMemcpy(trail.data(), P.fsm_trail.p, trail.size() * 4, hipMemcpyDeviceToHost));
   for (int i = 0; i < b; ++i) out[i] = trail[(size_t)i * P.fsm_cap + std::min(std::max(cnt[i], 0), P.fsm_cap - 1)];
+  return 0;
+}
+
+// ---- classifier-free guidance (include/omchat_hip.h)
+// The scale, b and the buffers are kernel arguments of the captured decode graphs, as the sampler's parameters are: a change drops them, the
+// same b and scale on the next call keep them.
+extern "C" int omchat_set_guidance(omchat_ctx* ctx, int b, float scale, void* stream) {
+  (void)stream;
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  if (b <= 0) {
+    if (P.gd.on) drop_decode_graphs(ctx);
+    P.gd = PickState::Guidance{};
+    return 0;
+  }
+  // every refusal before anything is allocated or changed
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(ctx->tp_size == 1, "guidance: one GPU (the vocabulary-parallel exchange of the two log-sum-exps is not built)");
+  OM_CHECK(2 * b <= c.max_batch, "guidance: b rows and their b twins exceed max_batch");
+  OM_CHECK(isfinite(scale), "guidance: the scale must be a finite float");
+  OM_CHECK(!ctx->beam.on(), "guidance: a beam search is active");
+  OM_CHECK(!ctx->group.on(), "guidance: a sampled group shares its prompt (omchat_group_begin with b = 0 first)");
+  void* old_copy = P.con_logits;
+  if (!P.gd_ws) TRY(ctx->alloc(&P.gd_ws, guidance_ws_bytes(c.max_batch / 2, c.t_vocab)));
+  if (!P.con_logits) TRY(ctx->alloc((void**)&P.con_logits, (size_t)c.max_batch * c.t_vocab * 4));
+  if (!P.gd.on || P.gd.b != b || P.gd.scale != scale || old_copy != P.con_logits) drop_decode_graphs(ctx);
+  P.gd.on = true; P.gd.b = b; P.gd.scale = scale;
   return 0;
 }

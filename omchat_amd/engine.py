@@ -735,6 +735,31 @@ class Engine:
         check(self.lib.omchat_fsm_states(self.h, int(b), ptr(out), cur_stream()))
         return [int(x) for x in out]
 
+    # ------------------------------------------------------------------ classifier-free guidance (include/omchat_hip.h: omchat_set_guidance)
+    def set_guidance(self, b, scale):
+        """rows 0..b-1 are conditional rows and rows b..2b-1 their twins over the negative prompt: argmax, sample, decode_step and kv_rewind
+        then take exactly 2b rows and pick b ids from scale * (lc - lu) + lu; the returned ids have 2b entries, the
+        twins' equal to their rows'.  Sampling, constraints, the token FSM and the log-prob record keep taking b.  Sticky until
+        guidance_off() (or b = 0); the same b and scale keep the captured decode graphs."""
+        check(self.lib.omchat_set_guidance(self.h, int(b), float(scale), cur_stream()))
+        self._guidance_on = int(b) > 0
+
+    def guidance_off(self):
+        if vars(self).get("_guidance_on", False):
+            check(self.lib.omchat_set_guidance(self.h, 0, 1.0, cur_stream()))
+        self._guidance_on = False
+
+    def guidance(self, logits, b, scale, out=None):
+        """the stage alone (omchat_op_guidance): logits fp32 [2b, ld] (any row stride >= V = logits.shape[1]) -> guided scores fp32 [b, V]"""
+        torch = _torch()
+        V = logits.shape[1]
+        ws = torch.empty(max(int(self.lib.omchat_op_guidance_ws(int(b), int(V))), 16), dtype=torch.uint8, device=self.device)
+        out = out if out is not None else torch.empty(b, V, dtype=torch.float32, device=self.device)
+        check(self.lib.omchat_op_guidance(ptr(logits), int(logits.stride(0)), int(b), int(V), float(scale), ptr(ws), ptr(out), int(out.stride(0)),
+                                          cur_stream()))
+        torch.cuda.current_stream().synchronize()      # (ws is released when this returns)
+        return out
+
     # ------------------------------------------------------------------ sampled groups (include/omchat_hip.h: omchat_group_begin)
     def group_share_refusal(self, N):
         """why the shared-prompt form is not available for N rows per prompt on this engine, or None (host data only)"""

@@ -361,6 +361,131 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise ValueError(f"prompt_lookup_num_tokens={k} exceeds the limit of {MAX_LOOKUP_TOKENS} draft tokens per verify step")
         return int(k), int(m), bool(do_sample and smp)
 
+    def _guidance_params(self, input_ids, images, attention_mask, kwargs, nb, num_return_sequences, suffixes, reuse):
+        """dict(scale, neg_ids int64 [b, Tn] on the CPU, neg_images) of generate(guidance_scale=...), or None when guidance is off -- no
+        scale (argument or generation_config) or a scale of 1, where HF adds no processor either and the negative arguments are ignored.
+        The four keywords are popped from `kwargs`.  Every refusal is raised here, from host data alone, before any work is enqueued."""
+        import math
+        import numbers
+        gc = self.generation_config
+        def take(name):
+            v = kwargs.pop(name, None)
+            return v if v is not None else getattr(gc, name, None)
+        scale, neg, neg_mask, neg_images = (take(n) for n in ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask",
+                                                              "negative_images"))
+        if scale is None:
+            return None
+        if isinstance(scale, bool) or not isinstance(scale, numbers.Real):
+            raise ValueError(f"`guidance_scale` has to be a finite number, but is {scale!r}")
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"`guidance_scale` has to be a finite number, but is {scale}")
+        if scale == 1.0:
+            return None
+        e = self.engine
+        nret = num_return_sequences if num_return_sequences is not None else (getattr(gc, "num_return_sequences", None) or 1)
+        k = kwargs.get("prompt_lookup_num_tokens", None)
+        k = k if k is not None else getattr(gc, "prompt_lookup_num_tokens", None)
+        if nb > 1:
+            raise NotImplementedError("guidance_scale with num_beams > 1 is not implemented: every beam row would need its twin")
+        if isinstance(nret, int) and nret > 1:
+            raise NotImplementedError("guidance_scale with num_return_sequences > 1 is not implemented: every sibling row would need its twin")
+        if suffixes is not None:
+            raise NotImplementedError("guidance_scale with suffixes= is not implemented: the suffix rows share one prompt, the twins would not")
+        if k is not None:
+            raise NotImplementedError("guidance_scale with prompt_lookup_num_tokens is not implemented: a verify step runs one sequence")
+        if reuse:
+            raise NotImplementedError("guidance_scale with reuse_cache=True is not implemented: the kept cache holds one conversation, not its twin")
+        if e.tp_size > 1:
+            raise NotImplementedError("guidance_scale under tensor parallelism is not implemented: the vocabulary-parallel exchange of the two "
+                                      "log-sum-exps is not built (DESIGN.md section 7)")
+        if vars(e).get("_fp8_kv", False) or vars(e).get("_fp8_prefill", False):
+            raise NotImplementedError("guidance_scale with the e4m3 KV cache or fp8 x fp8 prefill GEMMs is not implemented (DESIGN.md section 7)")
+        ids = input_ids.detach().to("cpu", torch.int64)
+        b = ids.shape[0]
+        if attention_mask is not None and bool((attention_mask == 0).any()):
+            raise NotImplementedError("guidance_scale over a padded batch (attention_mask with zeros) is not implemented: pad the prompts to "
+                                      "equal length or use b = 1")
+        V = e.c.t_vocab_total
+        if neg is None:
+            neg = ids[:, -1:]                                         # HF: the unconditional context is the last prompt token alone
+        neg = torch.as_tensor(neg).detach().to("cpu", torch.int64)
+        neg = neg.view(1, -1) if neg.dim() == 1 else neg
+        if neg.dim() != 2 or neg.shape[0] != b or neg.shape[1] < 1:
+            raise ValueError(f"negative_prompt_ids {tuple(neg.shape)} must have one non-empty row per row of input_ids ({b})")
+        if neg_mask is not None:
+            neg_mask = torch.as_tensor(neg_mask).detach().to("cpu")
+            if tuple(neg_mask.shape) != tuple(neg.shape):
+                raise ValueError(f"negative_prompt_attention_mask {tuple(neg_mask.shape)} must have the shape {tuple(neg.shape)} of negative_prompt_ids")
+            if bool((neg_mask == 0).any()):
+                raise NotImplementedError("guidance_scale over padded negative prompts (negative_prompt_attention_mask with zeros) is not "
+                                          "implemented: pad them to equal length or use b = 1")
+        if bool(((neg != IMAGE_TOKEN_INDEX) & ((neg < 0) | (neg >= V))).any()):
+            raise ValueError(f"negative_prompt_ids holds an id outside the vocabulary [0, {V}) that is not the image sentinel {IMAGE_TOKEN_INDEX}")
+        n_sent = int((neg == IMAGE_TOKEN_INDEX).sum())
+        if n_sent and neg_images is None:
+            raise ValueError(f"negative_prompt_ids holds the image sentinel {IMAGE_TOKEN_INDEX} and negative_images is None: pass the tiles it "
+                             "stands for, or a text-only negative prompt")
+        if neg_images is not None and not n_sent:
+            raise ValueError(f"negative_images without the image sentinel {IMAGE_TOKEN_INDEX} in negative_prompt_ids: nothing would see them")
+        if 2 * b > e.c.max_batch:
+            raise ValueError(f"guidance_scale needs 2 * b = {2 * b} cache rows (the prompts and their twins): create the model with max_batch >= "
+                             f"{2 * b} (it has {e.c.max_batch})")
+        tiles = (_n_tiles(images) if bool((ids == IMAGE_TOKEN_INDEX).any()) else 0) + (_n_tiles(neg_images) if n_sent else 0)
+        if tiles > e.c.max_tiles:
+            raise ValueError(f"guidance_scale: images and negative_images hold {tiles} tiles together, the model was created with max_tiles = {e.c.max_tiles}")
+        len_c = self._spliced_lengths(ids, images)
+        len_n = self._spliced_lengths(neg, neg_images)
+        if len(set(len_c)) > 1:
+            raise NotImplementedError("guidance_scale over rows of different spliced length is not implemented: pad the prompts to equal "
+                                      "length or use b = 1")
+        if len(set(len_n)) > 1:
+            raise NotImplementedError("guidance_scale over negative prompts of different spliced length is not implemented: pad them to equal "
+                                      "length or use b = 1")
+        S = max(len_c[0], len_n[0])
+        if S + 1 > e.c.max_seq or 2 * b * S > e.c.max_prefill_rows:
+            raise ValueError(f"guidance_scale: 2 * b = {2 * b} rows of up to {S} slots do not fit max_seq = {e.c.max_seq} / max_prefill_rows = "
+                             f"{e.c.max_prefill_rows}")
+        return dict(scale=scale, neg_ids=neg, neg_images=neg_images)
+
+    def _forward_guided(self, input_ids, images, gd):
+        """The prefill of generate(guidance_scale=...) (the arguments went through _guidance_params): the b prompts and their b twins -- the
+        negative prompts, spliced with negative_images or text-only -- as ONE right-padded ragged batch of 2b rows, every row at its own
+        length; the tower runs once over the tiles of both.  -> forward()'s output with `local_logits` [2b, V], rows [b, 2b) the twins'."""
+        e = self.engine
+        ids = input_ids.detach().to("cpu", torch.int64)
+        neg = gd["neg_ids"]
+        b = ids.shape[0]
+
+        def tiles(im, rows):
+            if im is None or self.get_vision_tower() is None or not bool((rows == IMAGE_TOKEN_INDEX).any()):
+                return None
+            if type(im) is list:
+                if any(t.ndim != 3 for t in im):
+                    raise NotImplementedError("video inputs: the reference calls an undefined encode_videos (omchat_arch.py:87)")
+                im = torch.stack(im)
+            elif im.ndim == 5:
+                raise NotImplementedError("video inputs: the reference calls an undefined encode_videos (omchat_arch.py:87)")
+            return im
+        px_c, px_n = tiles(images, ids), tiles(gd["neg_images"], neg)
+        px = [p for p in (px_c, px_n) if p is not None]
+        feats = self.encode_images(torch.cat([p.to(px[0].device, px[0].dtype) for p in px])) if px else None
+        n_c = 0 if px_c is None else px_c.shape[0]
+        maxlen = getattr(self.config, "tokenizer_model_max_length", None)
+        emb_c, len_c, _ = e.splice(ids, None, None if px_c is None else feats[:n_c], "right", maxlen)
+        emb_n, len_n, _ = e.splice(neg, None, None if px_n is None else feats[n_c:], "right", maxlen)
+        S = max(emb_c.shape[1], emb_n.shape[1])
+        embeds = torch.zeros(2 * b, S, emb_c.shape[2], dtype=emb_c.dtype, device=emb_c.device)
+        embeds[:b, :emb_c.shape[1]] = emb_c
+        embeds[b:, :emb_n.shape[1]] = emb_n
+        logits, _ = e.prefill(embeds, list(len_c) + list(len_n))
+        self._padded_batch = False
+        self._last_lengths = None
+        self._prefill_slots = S
+        out = CausalLMOutputWithPast(e.full_logits(logits[:b]).unsqueeze(1), KVHandle(e, 2 * b))
+        out.local_logits = logits
+        return out
+
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, do_sample=None, temperature=None, max_new_tokens=None, streamer=None, use_cache=True,
                  eos_token_id=None, pad_token_id=None, attention_mask=None, stopping_criteria=None, top_k=None, top_p=None,
@@ -431,7 +556,25 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         return_dict_in_generate=True the output carries .fsm_states [rows]: omchat_amd.fsm.DEAD (-1) for a row that ended with an EOS, else
         the state the row stopped in (an answer cut by max_new_tokens).  Refused with num_beams > 1 and with prompt_lookup_num_tokens
         (NotImplementedError), and for a start state out of range or without an edge (ValueError).  HF's prefix_allowed_tokens_fn itself
-        stays refused: TokenFSM.as_prefix_allowed_tokens_fn gives the callback that computes the same constraint there."""
+        stays refused: TokenFSM.as_prefix_allowed_tokens_fn gives the callback that computes the same constraint there.
+        guidance_scale=s with negative_prompt_ids [b, Tn] (negative_prompt_attention_mask, negative_images; all also read from
+        generation_config): HF's UnbatchedClassifierFreeGuidanceLogitsProcessor on the device.  Prompt row r gets a
+        twin cache row that holds the negative prompt -- negative_prompt_ids=None: the last prompt token alone, as HF does --, all 2b rows
+        are prefilled as one ragged batch and decoded at their own lengths, and every pick of row r runs on
+        s * (lc - lu) + lu, lc / lu the log-softmax of the row's and of the twin's logits, in front of the token-banning arguments, the
+        automaton and the argmax or sampler; the id picked for row r is fed to its twin too.  negative_images (this project's extension):
+        None = the twin is text-only, which is what HF's processor computes (it calls the model without `images`); otherwise the -200
+        sentinels of negative_prompt_ids are spliced with those tiles -- the same question over a blank or another picture (visual
+        contrastive decoding).  s of None or 1: nothing happens -- no twin rows, the launches and ids of a call without the keyword (HF
+        adds the processor only when the scale is not 1).  Ban history, the penalty's seen set, automaton states, log-prob records,
+        stopping criteria, the streamer and the returned sequences belong to the b prompt rows; .logprobs is the prompt row's raw
+        log-softmax, .processed_logprobs that of the guided scores as the pick saw them.  Works greedy and with do_sample=True (all
+        parameters and filters), with the decode graph and MXFP4 decode (a guided b = 1 step is a 2-row step: batched=True).  Refused from
+        host data, before any work (_guidance_params): NotImplementedError for num_beams > 1, num_return_sequences > 1, suffixes=,
+        prompt_lookup_num_tokens, reuse_cache=True, padded or ragged prompt rows or negative rows, tensor parallelism, the e4m3 KV cache
+        and fp8 prefill GEMMs; ValueError for a scale that is no finite number, another row count than input_ids', ids outside the
+        vocabulary other than -200, -200 without negative_images (or negative_images without -200), 2b > max_batch, more tiles than
+        max_tiles, rows that do not fit max_seq / max_prefill_rows."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -444,6 +587,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             if getattr(self.engine, "_fp8_kv", False) or getattr(self.engine, "_fp8_prefill", False) or self.engine.tp_size > 1:
                 raise NotImplementedError("reuse_cache=True with the e4m3 KV cache, fp8 x fp8 prefill GEMMs or tensor parallelism is not "
                                           "implemented (DESIGN.md section 7)")
+        # classifier-free guidance: resolved and refused from host data, before any work
+        gd = self._guidance_params(input_ids, images, attention_mask, kwargs, nb, num_return_sequences, suffixes, reuse)
         sfx = None
         if suffixes is not None:      # every refusal that host data decides, before any work (and before the other modes' own refusals)
             sfx = self._suffix_params(input_ids, images, attention_mask, suffixes, nb, num_return_sequences, share_prompt, reuse, kwargs, streamer)
@@ -480,6 +625,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             self.engine.logprobs_off()
         if fsm_rows is None and vars(self.engine).get("_fsm_on", False):      # sticky too: a call without the keyword is unconstrained
             self.engine.token_fsm_off()
+        if gd is None and vars(self.engine).get("_guidance_on", False):      # sticky too: a call without the keyword (or with scale 1) is unguided
+            self.engine.guidance_off()
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -502,6 +649,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             b = len(sfx[0])
         elif reuse:
             out, prompt_slots = self._forward_reuse(input_ids, images)
+        elif gd is not None:
+            out = self._forward_guided(input_ids, images, gd)         # 2b rows: the prompts, then their twins over the negative prompts
         else:
             out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
         # ONE rule for the first token at every TP degree: omchat_greedy on this rank's vocabulary shard -- local first-index-wins argmax,
@@ -530,6 +679,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             self.engine.token_fsm_begin(b, fsm_rows, max_new_tokens)
         if olp:
             self.engine.set_logprobs(b, max_new_tokens, top_n, score_ids)      # the prefill's pick below is record 0
+        # every stage above keeps b rows; under guidance the picks and steps below run 2b rows -- `tok` holds the b picked ids, then the
+        # twins' copies of them -- and the host looks at the first b
+        rows = b
+        if gd is not None:
+            self.engine.set_guidance(b, gd["scale"])
+            rows = 2 * b
         if smp is not None:
             seen = [[int(i) for i in row if int(i) >= 0] for row in (input_ids.tolist() if hist is None else hist)]
             self.engine.set_sampling(b, seen=seen, **smp)
@@ -542,7 +697,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         # many tokens as fit and stop cleanly, returning what was produced, instead of failing mid-stream with 'KV cache full'.
         # A padded batch appends at the COMMON slot (omchat_arch.py:61-70: the cache length, pads included), so its room is counted from
         # there, not from the longest row's own length
-        used = self._prefill_slots if padded else max(self.engine.kv_lengths(b))
+        used = self._prefill_slots if padded else max(self.engine.kv_lengths(rows))      # (under guidance: the longest of the 2b rows)
         room = self.engine.c.max_seq - used + 1
         if max_new_tokens > room:
             import warnings
@@ -580,12 +735,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         evt = self._stage_event
         for step in range(max_new_tokens):
             last = step == max_new_tokens - 1
-            stage[step].copy_(tok.to(torch.int32), non_blocking=True)
+            stage[step].copy_((tok if gd is None else tok[:b]).to(torch.int32), non_blocking=True)
             evt.record()
             ahead = None
             if not last:
                 # rows that already ended are fed the pad id, as HF's loop does (their cache content then equals the reference's too)
-                feed = tok if (pad is None or not bool(done.any())) else torch.where(done.to(tok.device), torch.full_like(tok, pad), tok)
+                feed = tok if (pad is None or not bool(done.any())) else torch.where(done.repeat(rows // b).to(tok.device), torch.full_like(tok, pad), tok)      # (an ended row's twin is fed the pad too)
                 ahead, _ = step_fn(feed)                              # runs while the host handles token `step`
             evt.synchronize()
             t_cpu = stage[step].to(torch.int64)
@@ -605,7 +760,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 stop = any(bool(c(so_far, None)) for c in stopping_criteria)
             if stop:
                 if ahead is not None:
-                    self.engine.kv_rewind(b, 1)
+                    self.engine.kv_rewind(rows, 1)
                 break
             tok = ahead
         if streamer is not None:
