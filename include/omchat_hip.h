@@ -771,6 +771,15 @@ int omchat_op_attn_prefill_left(int dtype, const void* q, const void* k, const v
  * before anything is launched.  Synchronises. */
 int omchat_op_rope_kv_pos(int dtype, void* qkv, int b, int S, int Hq, int Hkv, const int32_t* pos, int pos0, int slot0, int max_pos, float theta,
                           void* kcache, void* vcache, int cap, void* stream);
+/* test hook (tests/test_gpu_decode_append.py): one decode step's attention over the 16-bit cache INCLUDING the new token's RoPE + append, as the
+ * decoder layer issues it.  qkv [b][(Hq + 2 Hkv) * 128] raw projections (not modified); sequence i holds kv_len[i] keys counting the new one
+ * (NULL: L); the rotated k and v go to slot kv_len[i] - 1 of k / v [b,Hkv,cap,128] (the bytes omchat_op_rope_kv writes), and that slot is the RoPE
+ * position.  key_mask (device bytes [b][mask_sb], mask_sb % 64 == 0, kv_len NULL): key j of row i is visible iff key_mask[i][j] != 0, the RoPE
+ * position is pos[i] (device int32 [b]) and the slot L - 1 for every row.  pack_nb != 0: out in the packed x layout.  NULL pointers, L < 1,
+ * L > cap, key_mask without pos or with kv_len are refused before anything is launched.  Synchronises. */
+int omchat_op_attn_decode_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int b, int Hq, int Hkv, int cap, int L,
+                                 const int32_t* kv_len, const int32_t* pos, const unsigned char* key_mask, int64_t mask_sb, int pack_nb,
+                                 float scale, void* ws, size_t ws_bytes, void* stream);
 /* test hook: omchat_op_argmax over rows of stride ld >= V; adv_pos / adv_len device int32 [b] or NULL: each advanced by one per row */
 int omchat_op_argmax_ld(const float* logits, int ld, int b, int V, int32_t* out, int32_t* adv_pos, int32_t* adv_len, void* stream);
 /* test hook: pixels [B,3,HW,HW] -> cols [B * (HW / patch)^2, Kpad], columns (channel, ky, kx), zero beyond 3 * patch^2 */

@@ -382,6 +382,30 @@ extern "C" int omchat_op_attn_decode_kv8_append(int dtype, void* qkv, float thet
   return rc;
 }
 
+// The same step over the 16-bit cache, as the decoder layer issues it (model.hip, ctx.h bind_attn): q rotated in registers, the split that owns
+// the new position rotates the fresh key and appends k / v (rope_kv_kernel's bytes, slot kv_len[i] - 1, which is also the RoPE position).  With
+// key_mask (device bytes [b][mask_sb], the padded batch; kv_len must be NULL) the RoPE position of row i is pos[i] and the slot L - 1 for every
+// row.  pack_nb != 0: out in the packed x layout (common.h).  qkv is read-only.  Synchronises.
+extern "C" int omchat_op_attn_decode_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int b, int Hq, int Hkv, int cap,
+                                            int L, const int32_t* kv_len, const int32_t* pos, const unsigned char* key_mask, int64_t mask_sb,
+                                            int pack_nb, float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(qkv && k && v && out && ws, "null argument");
+  OM_CHECK(b >= 1 && Hq >= 1 && Hkv >= 1, "empty attention");
+  OM_CHECK(L >= 1 && L <= cap, "L exceeds the cache capacity");
+  OM_CHECK(!key_mask || pos, "key_mask needs the RoPE positions (pos)");
+  OM_CHECK(!key_mask || !kv_len, "key_mask: every row holds L keys (kv_len must be null)");
+  float* tab = rope_table_device(L, theta);
+  OM_CHECK(tab, "rope table allocation failed");
+  AttnDecodeArgs a{};
+  bind_dense(a, qkv, true, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  bind_new_rows(a, tab, L);
+  a.batch = b; a.L = L; a.kv_len = kv_len; a.pos = pos; a.key_mask = key_mask; a.mask_sb = mask_sb; a.o_pack_nb = pack_nb;
+  const int rc = launch_attn_decode(dtype, a, S(stream));
+  hipStreamSynchronize(S(stream));
+  hipFree(tab);
+  return rc;
+}
+
 static int op_rope_kv_impl(int dtype, void* qkv, int b, int Sq, int Hq, int Hkv, int pos0, float theta, void* kcache, void* vcache, int cap,
                            void* k8, void* v8, float* ks, float* vs, void* stream);
 extern "C" int omchat_op_rope_kv(int dtype, void* qkv, int b, int Sq, int Hq, int Hkv, int pos0, float theta, void* kcache, void* vcache, int cap,

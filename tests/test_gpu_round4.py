@@ -262,8 +262,10 @@ def test_batched_decode_attention_dma_ring_vs_reference_and_register_form(gpu_li
 def test_batched_decode_attention_dma_ring_in_the_model(gpu_lib, dt):
     """inside the decode step the split that owns the new position rotates the fresh key row, patches it into its LDS image and appends k / v:
     ragged contexts whose new positions sit on the last row of a 32-key tile, the first row, mid-tile and in a one-tile split; 5 free-running
-    steps; logits against the one-tile kernel (key 10 = 1) and the register multi-tile form (key 25 = 0), and the cache rows the steps
-    appended must be the same bits in all three (the next step reads them)"""
+    steps; the logits of the register multi-tile form (key 25 = 0) and of the ring form at two slot counts against the one-tile kernel's
+    (key 10 = 1) within TOL_DEEP, every step finite.  The cache is not read here: across forms the later layers' inputs differ in rounding,
+    so the rows they append are not the same bits.  That the appended rows are rope_kv_kernel's bytes, form by form, is asserted at op level
+    (tests/test_gpu_decode_append.py)"""
     cfg = tiny(q_heads=4, kv_heads=2)
     sd = _decoder_sd(cfg, 5)
     b, S = 5, 200
