@@ -637,6 +637,22 @@ int omchat_op_gemv(int dtype, const void* X, int ldx, const void* W, int ldw, vo
 int omchat_op_gemv_packed(int dtype, const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int b, int N, int K,
                           const void* bias, int epi, int out_f32, int ksplit, int w_packed, int y_packed, void* stream);
 int omchat_op_pack_x(int dtype, const void* X, int ldx, int b, int K, void* out, void* stream);
+/* Test hook: the launch that the skinny-GEMM entry points above would make for these integers on the current tuning state, decided on the
+ * host without a launch (dense operands).  flags: bit 0 x_packed, 1 w_packed, 2 y_packed, 3 norm_w given, 4 out_f32, 5 force_mfma, 6 resid given;
+ * wf: weights 0 = 16-bit, 1 = e4m3 + row scales, 2 = MXFP4, 3 = bf16x12; n_cu: compute units to plan for (<= 0: the device's).
+ * out[OMCHAT_GEMV_PLAN_INTS] (fields that the kernel family does not have are 0):
+ *   [0] family: 0 gemv_kernel (MFMA), 1 gemv_pk, 2 gemv_xs, 3 gemv_xs_split, 4 gemv_rows, 5 gemv_rows_norm, 6 gemv_rows_norm_loop,
+ *       7 gemv_rows_longk, and in -DOMCHAT_EXPERIMENTS=1 builds 8 gemv_rows_norm_dyn, 9 gemv_rows_longk_direct
+ *   [1] weight form (as wf)  [2] packed W (gemv_pk)  [3] epilogue  [4] NTILE  [5] WAVES  [6] UNROLL  [7] NB  [8] RR  [9] NCH  [10] NORM (gemv_xs)
+ *   [11] grid x  [12] grid y  [13] block  [14] dynamic LDS bytes  [15] per_wg  [16] skew (loop form)  [17] rows_per_wg (long-K form)
+ *   [18] n5 (gemv_xs_split)  [19] xskew (experiments build)
+ * A call that the entry points refuse returns 1 with their text in omchat_last_error.
+ * The hook passes no work counters (GemvArgs::dyn_ctr), so tuning key 24 (family 8) does not show through it.
+ * omchat_op_gemv_split_k: the K slices (ksplit) that a decode step of batch b and hidden size H gives its o_proj (down = 0, K = q width) or
+ * down_proj (down = 1, K = mlp width) launch; packed: the step streams a packed weight replica. */
+#define OMCHAT_GEMV_PLAN_INTS 20
+int omchat_op_gemv_plan(int dtype, int b, int N, int K, int epi, int ksplit, int flags, int wf, int n_cu, int* out);
+int omchat_op_gemv_split_k(int b, int K, int H, int packed, int down);
 /* fp8 x fp8 MFMA GEMM (BASELINE configs[4] "fp8 MFMA weights"): A8 [M, K] and W8 [N, K] are OCP e4m3 bytes with one fp32 scale per row;
  * C (dtype) = epi(a_scale[m] * w_scale[n] * A8 W8^T), epilogues as omchat_op_gemm (ls unused).  K % 128 == 0.
  * omchat_op_quant_rows_fp8: per-row (per token) quantisation of activations, optionally behind an RMSNorm (norm_w != NULL). */

@@ -103,6 +103,8 @@ _SIGS = {
     "omchat_op_gemv": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "omchat_op_gemv_packed": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "omchat_op_pack_x": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
+    "omchat_op_gemv_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "omchat_op_gemv_split_k": (_i, [_i, _i, _i, _i, _i]),
     "omchat_op_gemm_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "omchat_op_quant_rows_fp8": (_i, [_i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
     "omchat_enable_fp8_decode": (_i, [_vp, _i]),

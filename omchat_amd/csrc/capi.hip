@@ -170,6 +170,30 @@ extern "C" int omchat_op_gemv_packed(int dtype, const void* X, int ldx, const vo
 }
 extern "C" int omchat_op_pack_x(int dtype, const void* X, int ldx, int b, int K, void* out, void* stream) { return launch_pack_x(dtype, X, ldx, b, K, out, S(stream)); }
 
+// What launch_gemv decides for a call of these integers on the current tuning state, without launching (gemv_plan; fields and flag bits:
+// include/omchat_hip.h).  The operands are dense (ldx = K, ldw = a row of the weight form); n_cu <= 0 = the device's compute units.
+extern "C" int omchat_op_gemv_plan(int dtype, int b, int N, int K, int epi, int ksplit, int flags, int wf, int n_cu, int* out) {
+  OM_CHECK(out && wf >= WF_16 && wf <= WF_X12, "null out or weight form outside 0..3");
+  static const unsigned set[1] = {0};      // what the plan reads of a pointer is whether it is null (dyn_ctr stays null: key 24 does not show here)
+  GemvArgs a{};
+  a.b = b; a.N = N; a.K = K; a.epi = epi; a.ksplit = ksplit;
+  a.ldx = K; a.ldy = a.ldr = N; a.ldw = wf == WF_MX4 ? K / 2 : wf == WF_X12 ? K / 2 * 3 : K;
+  a.x_packed = flags & 1; a.w_packed = flags >> 1 & 1; a.y_packed = flags >> 2 & 1; a.out_f32 = flags >> 4 & 1; a.force_mfma = flags >> 5 & 1;
+  if (flags & 8) a.norm_w = set;
+  if (flags & 64) a.resid = set;
+  if (wf == WF_E4M3) a.w_scale = (const float*)set;
+  if (wf == WF_MX4) a.mx_scale = (const unsigned char*)set;
+  if (wf == WF_X12) { a.x12_top = a.x12_cnt = (const unsigned char*)set; a.x12_patch = set; }
+  const GemvPlan g = gemv_plan(dtype, a, gemv_tuning(), n_cu > 0 ? n_cu : device_cus());
+  if (g.refusal) { omchat_set_error(g.refusal); return 1; }
+  const int f[OMCHAT_GEMV_PLAN_INTS] = {g.family, g.wf, g.wpack, g.epi, g.ntile, g.waves, g.unroll, g.nb, g.rr, g.nch, g.norm, g.gx, g.gy, g.block, g.lds,
+                                        g.per_wg, (int)g.skew, g.rows_per_wg, g.n5, g.xskew};
+  for (int i = 0; i < OMCHAT_GEMV_PLAN_INTS; ++i) out[i] = f[i];
+  return 0;
+}
+// ... and the K slices a decode step gives its o_proj (down = 0, K = q width) or down_proj (down = 1, K = mlp width) launch (gemv_split_k)
+extern "C" int omchat_op_gemv_split_k(int b, int K, int H, int packed, int down) { return gemv_split_k(b, K, H, packed != 0, down != 0, gemv_tuning()); }
+
 // fp8 x fp8 GEMM (BASELINE configs[4]): A8 [M, K], W8 [N, K] e4m3 bytes with per-row fp32 scales -> C (dtype) = epi(sa[m] sw[n] A8 W8^T)
 extern "C" int omchat_op_gemm_fp8(int dtype, const void* A8, const float* a_scale, const void* W8, const float* w_scale, void* C, int ldc, int M,
                                   int N, int K, const void* bias, const void* resid, int ldr, int epi, void* stream) {

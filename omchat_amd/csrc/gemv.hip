@@ -35,7 +35,7 @@ struct GemvP {
 // weight format of the whole-row batch-1 forms (template switch): 16-bit, OCP e4m3 bytes + one fp32 scale per row, MXFP4 (OCP Microscaling
 // v1.0: e2m1 codes, two per byte, + one e8m0 scale per 32 consecutive k)
 // ... and bf16x12, the lossless 12-bit coding of bf16 rows (below: "bf16x12"): the same weights bit for bit, three quarters of the bytes
-constexpr int WF_16 = 0, WF_E4M3 = 1, WF_MX4 = 2, WF_X12 = 3;
+// (WF_16 / WF_E4M3 / WF_MX4 / WF_X12: kernels.h)
 // stamps: [0] merge end, [1] o_proj first start (stored inverted: max of ~t), [2] o_proj flags seen, [3] o_proj end, [4] gate|up first start (inverted), [5] gate|up end,
 // [6] down_proj first start (inverted), [7] down_proj end, [8] qkv first start (inverted), [9] qkv end, [10] attention first start (inverted), [11] attention end, [12] merge first start (inverted), [16 + x] gate|up end on XCD x
 #if OMCHAT_EXPERIMENTS
@@ -700,13 +700,25 @@ __global__ void pack_w4_kernel(const unsigned char* W4, const unsigned char* S, 
 // takes R rows at a time (all R x NCH loads in flight), v_dot2 per 32 bits, butterfly over the wave, lane 0 applies the
 // epilogue.  Split-K slices are chunk ranges of 512 elements, <= RW_MAXC chunks each.
 // ---------------------------------------------------------------------------------------------------------
-int g_gemv_force_mfma = 0;     // tuning knob (omchat_op_set_tuning key 1): A/B the two forms
-int g_gemv_no_xs = 0;          // tuning knob (key 11): 1 = batched decode never takes the x-stationary persistent kernel (A/B)
-// omchat_op_set_tuning key 34: launch shapes for the SHARD widths of a tensor-parallel rank (round 5; N or K an eighth of the model's):
+// The tuning state (GemvTuning, kernels.h), by omchat_op_set_tuning key:
+// force_mfma (key 1): A/B the two forms
+// no_xs (key 11): 1 = batched decode never takes the x-stationary persistent kernel (A/B)
+// shard (key 34): launch shapes for the SHARD widths of a tensor-parallel rank (round 5; N or K an eighth of the model's):
 // bit 0 = x-stationary form for short EPI_NONE outputs (qkv shard: one tile per workgroup), bit 1 = one-tile / one-chunk-per-wave form for
 // short-K split-K slices (o_proj / down_proj shards), bit 2 = one (gate, up) pair per wave for the short batch-1 gate|up,
 // bit 3 = x-stationary form, one (gate, up) tile pair per workgroup, for a batched gate|up shard of at most one pair per CU
-int g_gemv_shard = 15;
+// longk_direct (key 39, experiments build): waves per workgroup (1, 2, 4) of the no-LDS long-K form; 0 = x through LDS (gemv_rows_longk_kernel)
+// rows_balance (key 17): 1 = one-row-per-wave launches whose rows deal evenly to 2 workgroups per CU take N / (2 CUs) waves per workgroup (o_proj 7, qkv 9)
+// skew (key 28, experiment): per-(blockIdx % 8) share deltas of the loop form, eight nibbles (d + 8)
+// dyn (key 24): 1 = the loop form takes its outputs from atomic work counters when the caller provides them (gemv_rows_norm_dyn_kernel)
+// gu_rr (key 38): (gate, up) pairs per wave of the NON-loop norm form of the batch-1 gate|up GEMV.  Round 5: ONE pair per wave (4736
+// workgroups of four waves for Qwen2-7B) beats the loop form's one resident round of 512 workgroups x 37 pairs: decode 2.650 -> 2.597 ms per token on
+// one box (3 pairs per wave: 2.671, 2: 2.624).  The XCDs do not deliver the same HBM bandwidth when all stream at once (DESIGN.md section 6, round 4), so a
+// static equal split ends on the slowest XCD; thousands of 14 KB-per-wave workgroups are re-balanced by the dispatcher as they retire, the way the
+// lm_head launch (9504 workgroups) always was -- it streams at 7.0 TB/s where the loop form reached 6.35.
+// gu_rr8: the same for the e4m3 replica (key 38, value x 16): 1.700 -> 1.678 -> 1.658 ms per token at 4 / 2 / 1 pairs per wave
+// norm_loop (key 16): loop form (gemv_rows_norm_loop_kernel) of a batch-1 step's bit 0 = gate|up, 1 = qkv, 2 = e4m3 gate|up, 3 = lm_head
+GemvTuning g_tune;
 constexpr int RW_MAXC = 8;
 // weight-only fp8 (OCP e4m3): 8 weights of a lane = 8 bytes.  gfx950's v_cvt_scalef32_pk_{bf16,f16}_fp8 widens two e4m3
 // values to a packed 16-bit pair in one instruction (exact: 3 mantissa bits), which then feeds the same v_dot2 as the
@@ -1742,405 +1754,383 @@ template <typename T>
 __global__ __launch_bounds__(256) void gemv_rows_longk_direct_mx4_kernel(GemvP p) { gemv_rows_longk_direct_body<T, WF_MX4>(p); }
 
 #endif
-int g_gemv_longk_direct = 0;   // omchat_op_set_tuning key 39 (experiments build): waves per workgroup (1, 2, 4) of the no-LDS long-K form; 0 = x through LDS (gemv_rows_longk_kernel)
 
-template <typename T>
-int launch_rows_longk(const GemvP& p, hipStream_t s) {
-#if OMCHAT_EXPERIMENTS
-  if (g_gemv_longk_direct > 0) {
-    const int wpw = g_gemv_longk_direct > 4 ? 4 : g_gemv_longk_direct;
-    if (p.mx_s) hipLaunchKernelGGL((gemv_rows_longk_direct_mx4_kernel<T>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
-    else if (p.w_scale) hipLaunchKernelGGL((gemv_rows_longk_direct_kernel<T, true>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
-    else hipLaunchKernelGGL((gemv_rows_longk_direct_kernel<T, false>), dim3(cdiv(p.N, wpw)), dim3(64 * wpw), 0, s, p);
-    return 0;
-  }
-#endif
-  const int n_cu = device_cus();
-  int rpw = cdiv(p.N, 2 * n_cu);                // two workgroups per CU
-  rpw = rpw < 1 ? 1 : (rpw > 8 ? 8 : rpw);
-  const int grid = cdiv(p.N, rpw);
-  const int npass = (cdiv(p.K, 512) + 7) / 8;
-  const size_t lds = (size_t)npass * 8 * 512 * 2;
-  if (p.x12_top) {
-    if constexpr (std::is_same<T, bf16>::value) {
-      static PerDeviceOnce set;
-      auto k = gemv_rows_longk_x12_kernel<T>;
-      if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      hipLaunchKernelGGL(k, dim3(grid), dim3(64 * rpw), lds, s, p, rpw);
-    }
-  } else if (p.mx_s) {
-    static PerDeviceOnce set;
-    auto k = gemv_rows_longk_mx4_kernel<T>;
-    if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * rpw), lds, s, p, rpw);
-  } else if (p.w_scale) {
-    auto k = gemv_rows_longk_kernel<T, true>;
-    static PerDeviceOnce set;
-    if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * rpw), lds, s, p, rpw);
-  } else {
-    auto k = gemv_rows_longk_kernel<T, false>;
-    static PerDeviceOnce set;
-    if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * rpw), lds, s, p, rpw);
-  }
-  return 0;
-}
-
-int g_gemv_rows_balance = 1;   // omchat_op_set_tuning key 17: 1 = one-row-per-wave launches whose rows deal evenly to 2 workgroups per CU take N / (2 CUs) waves per workgroup (o_proj 7, qkv 9)
-unsigned g_gemv_skew = 0;      // omchat_op_set_tuning key 28 (experiment): per-(blockIdx % 8) share deltas of the loop form, eight nibbles (d + 8)
-int g_gemv_dyn = 0;            // omchat_op_set_tuning key 24: 1 = the loop form takes its outputs from atomic work counters when the caller provides them (gemv_rows_norm_dyn_kernel)
-// omchat_op_set_tuning key 38: (gate, up) pairs per wave of the NON-loop norm form of the batch-1 gate|up GEMV.  Round 5: ONE pair per wave (4736
-// workgroups of four waves for Qwen2-7B) beats the loop form's one resident round of 512 workgroups x 37 pairs: decode 2.650 -> 2.597 ms per token on
-// one box (3 pairs per wave: 2.671, 2: 2.624).  The XCDs do not deliver the same HBM bandwidth when all stream at once (DESIGN.md section 6, round 4), so a
-// static equal split ends on the slowest XCD; thousands of 14 KB-per-wave workgroups are re-balanced by the dispatcher as they retire, the way the
-// lm_head launch (9504 workgroups) always was -- it streams at 7.0 TB/s where the loop form reached 6.35.
-int g_gemv_gu_rr = 1;
-int g_gemv_gu_rr8 = 1;          // the same for the e4m3 replica (key 38, value x 16): 1.700 -> 1.678 -> 1.658 ms per token at 4 / 2 / 1 pairs per wave
-int g_gemv_norm_loop = 0;      // omchat_op_set_tuning key 16: loop form (gemv_rows_norm_loop_kernel) of a batch-1 step's bit 0 = gate|up, 1 = qkv, 2 = e4m3 gate|up, 3 = lm_head
-
-template <typename T, int EPI, int RR, int F8, int NCH>
-void launch_rows_norm_n(const GemvP& p, hipStream_t s) {
-  const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
-  if constexpr (NCH >= 4) {        // the decoder's hidden sizes only (K > 1536): keeps the instantiation count down
-    // measured (profiles/r03_p): gate|up 44.3 -> 42.8 us (2.778 -> 2.738 ms per token); qkv 9.2 us either way; e4m3 gate|up 0.6 % slower
-    const bool want = EPI == EPI_SWIGLU ? (g_gemv_norm_loop & (F8 != WF_16 ? 4 : 1)) : (p.N < 32768 ? (g_gemv_norm_loop & 2) : (g_gemv_norm_loop & 8));
-    const int n_cu = device_cus();
-    // dynamic form: the outputs dealt by atomic counters instead of equal shares (the XCDs do not stream at the same rate); tuning key 24
-#if OMCHAT_EXPERIMENTS
-    if (want && p.dyn && g_gemv_dyn && n_out >= 8 * n_cu) {
-      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_dyn_mx4_kernel<T, EPI, NCH>), dim3(2 * n_cu), dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((gemv_rows_norm_dyn_kernel<T, EPI, NCH, F8 == WF_E4M3>), dim3(2 * n_cu), dim3(256), 0, s, p);
-      return;
-    }
-#endif
-    if (want && n_out >= 8 * n_cu) {
-      const int per = cdiv(n_out, 2 * n_cu);
-      const unsigned skew = (g_gemv_skew >= 256u && n_out == per * 2 * n_cu && (2 * n_cu) % 8 == 0) ? g_gemv_skew : 0u;
-      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_loop_mx4_kernel<T, EPI, NCH>), dim3(cdiv(n_out, per)), dim3(256), 0, s, p, per, skew);
-      else hipLaunchKernelGGL((gemv_rows_norm_loop_kernel<T, EPI, NCH, F8 == WF_E4M3>), dim3(cdiv(n_out, per)), dim3(256), 0, s, p, per, skew);
-      return;
-    }
-  }
-  if constexpr (NCH >= 4 && EPI == EPI_NONE && RR <= 2) {
-    // qkv of a batch-1 step: 4608 rows = 9 x 512: one row per wave, nine waves per workgroup, 2 workgroups per CU (every CU streams 18 rows)
-    // instead of 576 workgroups of 8 rows on 4 waves (2.25 per CU)
-    const int n_cu = device_cus();
-    if (g_gemv_rows_balance && n_out == 9 * 2 * n_cu) {
-      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_mx4_kernel<T, EPI, 1, NCH, 9>), dim3(2 * n_cu), dim3(576), 0, s, p);
-      else hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, 1, NCH, F8 == WF_E4M3, 9>), dim3(2 * n_cu), dim3(576), 0, s, p);
-      return;
-    }
-  }
-  // (four waves per workgroup: 8 / 16 waves -- fewer repeats of the norm -- measured 2.633 / 2.646 against 2.599 ms per token; down_proj's long-K form
-  // with fewer rows per workgroup 2.615-2.765: each workgroup stages the 37 KB x for itself; lm_head with 2 / 1 rows per wave 2.591 against 2.597: noise)
-#if OMCHAT_EXPERIMENTS
-  if constexpr (EPI == EPI_SWIGLU && RR == 1) {
-    const int nwg = cdiv(n_out, 4), xs = (int)(g_gemv_skew < 256u ? g_gemv_skew : 0u);
-    if (xs > 0 && nwg % 8 == 0 && n_out % 4 == 0 && xs < nwg / 8) {
-      GemvP q = p; q.xskew = xs;
-      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_mx4_kernel<T, EPI, RR, NCH>), dim3(8 * (nwg / 8 + xs)), dim3(256), 0, s, q);
-      else hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, RR, NCH, F8 == WF_E4M3>), dim3(8 * (nwg / 8 + xs)), dim3(256), 0, s, q);
-      return;
-    }
-  }
-#endif
-  if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_norm_mx4_kernel<T, EPI, RR, NCH>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((gemv_rows_norm_kernel<T, EPI, RR, NCH, F8 == WF_E4M3>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
-}
-template <typename T, int EPI, int RR, int F8>
-void launch_rows_norm(const GemvP& p, hipStream_t s) {
-  switch (cdiv(p.K, 512)) {
-    case 1: launch_rows_norm_n<T, EPI, RR, F8, 1>(p, s); break;
-    case 2: launch_rows_norm_n<T, EPI, RR, F8, 2>(p, s); break;
-    case 3: launch_rows_norm_n<T, EPI, RR, F8, 3>(p, s); break;
-    case 4: launch_rows_norm_n<T, EPI, RR, F8, 4>(p, s); break;
-    case 5: launch_rows_norm_n<T, EPI, RR, F8, 5>(p, s); break;
-    case 6: launch_rows_norm_n<T, EPI, RR, F8, 6>(p, s); break;
-    case 7: launch_rows_norm_n<T, EPI, RR, F8, 7>(p, s); break;
-    default: launch_rows_norm_n<T, EPI, RR, F8, 8>(p, s); break;
-  }
-}
-
-// bf16x12 rows in the default (non-loop) norm form, on the 16-bit launch's grid: gate|up one pair per wave, everything else four rows per wave
-template <int EPI, int NCH>
-void launch_rows_norm_x12_n(const GemvP& p, hipStream_t s) {
-  constexpr int RR = EPI == EPI_SWIGLU ? 1 : 4;
-  const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
-  hipLaunchKernelGGL((gemv_rows_norm_x12_kernel<bf16, EPI, RR, NCH>), dim3(cdiv(cdiv(n_out, RR), 4)), dim3(256), 0, s, p);
-}
-template <int EPI>
-void launch_rows_norm_x12(const GemvP& p, hipStream_t s) {
-  switch (p.K / 512) {
-    case 1: launch_rows_norm_x12_n<EPI, 1>(p, s); break;
-    case 2: launch_rows_norm_x12_n<EPI, 2>(p, s); break;
-    case 3: launch_rows_norm_x12_n<EPI, 3>(p, s); break;
-    case 4: launch_rows_norm_x12_n<EPI, 4>(p, s); break;
-    case 5: launch_rows_norm_x12_n<EPI, 5>(p, s); break;
-    case 6: launch_rows_norm_x12_n<EPI, 6>(p, s); break;
-    case 7: launch_rows_norm_x12_n<EPI, 7>(p, s); break;
-    default: launch_rows_norm_x12_n<EPI, 8>(p, s); break;
-  }
-}
-
-template <typename T, int EPI, int RR, int F8>
-void launch_rows_r(const GemvP& p, hipStream_t s) {
-  const int n_out = EPI == EPI_SWIGLU ? p.N / 2 : p.N;
-  if constexpr (RR == 1 && EPI == EPI_RESID) {
-    // o_proj of a batch-1 step: 3584 rows as 896 four-wave workgroups are 3.5 per CU (one CU in two streams a fourth workgroup); as
-    // 512 seven-wave workgroups every CU streams the same 14 rows (profiles/r03_r)
-    const int n_cu = device_cus();
-    if (g_gemv_rows_balance && p.ksplit == 1 && n_out == 7 * 2 * n_cu) {
-      if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_mx4_kernel<T, EPI, 1, 7>), dim3(2 * n_cu, 1), dim3(448), 0, s, p);
-      else hipLaunchKernelGGL((gemv_rows_kernel<T, EPI, 1, 7, F8 == WF_E4M3>), dim3(2 * n_cu, 1), dim3(448), 0, s, p);
-      return;
-    }
-  }
-  int grid = cdiv(cdiv(n_out, RR), 4);
-  grid = grid > 2048 ? 2048 : grid;
-  if constexpr (F8 == WF_MX4) hipLaunchKernelGGL((gemv_rows_mx4_kernel<T, EPI, RR, 4>), dim3(grid, p.ksplit), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((gemv_rows_kernel<T, EPI, RR, 4, F8 == WF_E4M3>), dim3(grid, p.ksplit), dim3(256), 0, s, p);
-}
+// ---------------------------------------------------------------------------------------------------------
+// Host side.  gemv_plan decides which kernel a call takes and with which grid (pure: every shape rule and every refusal, once);
+// gemv_launch is the table from such a plan to the kernel instantiation.
+// ---------------------------------------------------------------------------------------------------------
+// rows (SwiGLU: pairs) per wave of the whole-row batch-1 forms, by weight form.
 // rows per wave-group from tools/experiments/tune_rows.hip (MI355X, r01): short outputs (fused qkv) are latency-bound and want the most
 // waves (R = 1: 7.8 vs 8.8 us), everything else is flat in R; 4 waves per workgroup beat 8.  fp8 rows are half as many
 // bytes: the wide lm_head takes 8 rows per group, the split-K shapes measured flat (o_proj slightly worse) and keep 4.
 // quantised weights (e4m3 rows are half as many bytes as 16-bit ones, MXFP4 a quarter): the same launch shapes for both
-template <typename T, int EPI, int WF>
-void launch_rows_q(const GemvP& p, hipStream_t s) {
-  if constexpr (EPI == EPI_SWIGLU || EPI == EPI_NONE) {
-    if (p.norm_w) {
-      if (EPI == EPI_NONE && p.N < 32768) launch_rows_norm<T, EPI, 2, WF>(p, s);
-      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr8 == 2) launch_rows_norm<T, EPI, 2, WF>(p, s);
-      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr8 == 1) launch_rows_norm<T, EPI, 1, WF>(p, s);
-      else launch_rows_norm<T, EPI, 4, WF>(p, s);
-      return;
-    }
+int rows_per_wave(const GemvArgs& a, int wf, const GemvTuning& t, int n_cu) {
+  if (a.norm_w) {          // the norm shared through LDS; 3 (gate, up) pairs per wave: 6 x 7 chunks of weights + the row fit 256 VGPRs
+    // bf16x12 rows on the 16-bit launch's default grid: gate|up one pair per wave, everything else four rows per wave
+    if (wf == WF_X12) return a.epi == EPI_SWIGLU ? 1 : 4;
+    if (a.epi == EPI_NONE) return a.N < 32768 ? 2 : 4;      // qkv: 8 rows (56 KB) per workgroup against 14 KB of x + norm weights
+    if (wf == WF_16) return t.gu_rr == 2 || t.gu_rr == 3 ? t.gu_rr : 1;
+    return t.gu_rr8 == 2 || t.gu_rr8 == 1 ? t.gu_rr8 : 4;
   }
-  if ((EPI == EPI_NONE || EPI == EPI_RESID) && p.N < 32768) launch_rows_r<T, EPI, 1, WF>(p, s);
-  else if (EPI == EPI_NONE) launch_rows_r<T, EPI, 8, WF>(p, s);      // lm_head: 80.7 vs 82.3 us
-  else launch_rows_r<T, EPI, 4, WF>(p, s);
-}
-template <typename T, int EPI>
-void launch_rows(const GemvP& p, hipStream_t s) {
-  if (p.mx_s) { launch_rows_q<T, EPI, WF_MX4>(p, s); return; }
-  if (p.w_scale) { launch_rows_q<T, EPI, WF_E4M3>(p, s); return; }
-  if constexpr (EPI == EPI_SWIGLU || EPI == EPI_NONE) {
-    if (p.norm_w) {          // the norm shared through LDS; 3 (gate, up) pairs per wave: 6 x 7 chunks of weights + the row fit 256 VGPRs
-      if (EPI == EPI_NONE && p.N < 32768) launch_rows_norm<T, EPI, 2, WF_16>(p, s);      // qkv: 8 rows (56 KB) per workgroup against 14 KB of x + norm weights
-      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr == 2) launch_rows_norm<T, EPI, 2, WF_16>(p, s);
-      else if (EPI == EPI_SWIGLU && g_gemv_gu_rr == 3) launch_rows_norm<T, EPI, 3, WF_16>(p, s);
-      else if (EPI == EPI_SWIGLU) launch_rows_norm<T, EPI, 1, WF_16>(p, s);
-      else launch_rows_norm<T, EPI, 4, WF_16>(p, s);
-      return;
-    }
-  }
-  if ((EPI == EPI_NONE || EPI == EPI_RESID) && p.N < 32768) launch_rows_r<T, EPI, 1, WF_16>(p, s);      // short outputs: one row per wave (latency-bound)
+  if ((a.epi == EPI_NONE || a.epi == EPI_RESID) && a.N < 32768) return 1;      // short outputs: one row per wave (latency-bound)
+  if (wf != WF_16) return a.epi == EPI_NONE ? 8 : 4;      // lm_head: 80.7 vs 82.3 us
   // a tensor-parallel rank's gate|up shard (2368 pairs at TP = 8): 4 pairs per wave are 148 workgroups on 256 CUs; one pair per wave
   // gives every CU ~9 waves (round 5)
-  else if (EPI == EPI_SWIGLU && (g_gemv_shard & 4) && p.N / 2 < 16 * device_cus()) launch_rows_r<T, EPI, 1, WF_16>(p, s);
-  else launch_rows_r<T, EPI, 4, WF_16>(p, s);
+  return a.epi == EPI_SWIGLU && (t.shard & 4) && a.N / 2 < 16 * n_cu ? 1 : 4;
 }
-
-// Launch shapes measured with tools/experiments/tune_gemv.hip on MI355X (r01): plain loads beat non-temporal ones for this access
-// shape (gate|up 54.9 -> 49.4 us), split-K slices prefer 4 waves x 8 chunks in flight when a slice is short.
-template <typename T>
-int launch_t(const GemvArgs& a, hipStream_t s) {
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  GemvP p{a.X, a.W, a.Y, a.bias, a.resid, a.ldx, a.ldw, a.ldy, a.ldr, a.b, a.N, a.K, a.out_f32, ks, a.w_scale, a.y_packed, a.norm_w, a.norm_eps,
-          (unsigned*)a.dyn_ctr, a.y_pack, a.dbg, a.mx_scale, a.x12_top, a.x12_cnt, a.x12_patch};
-  if (a.norm_w && a.x_packed && !(a.w_packed && ks == 1 && (a.K >> 6) == 56 && a.epi == EPI_SWIGLU && a.N % 32 == 0 && !g_gemv_no_xs)) {
-    omchat_set_error("launch_gemv: the in-register RMSNorm on packed x exists for the x-stationary gate|up form only (packed W, K = 3584, no split-K)");
-    return 1;
-  }
-  if (a.epi == EPI_RESID && a.x_packed && !(a.w_packed && ks == 1 && (a.K >> 6) == 56 && a.N % 16 == 0 && a.N / 16 <= device_cus() && !g_gemv_no_xs)) {
-    omchat_set_error("launch_gemv: the batched residual epilogue exists for the x-stationary form only (packed W, K = 3584, N / 16 <= CUs, no split-K)");
-    return 1;
-  }
-  if (a.x_packed) {
-    // launch shapes from tools/experiments/tune_gemv32.hip (MI355X): <NTILE, WAVES, UNROLL> per shape class
-#define OM_PK(NT_, EPI_, WV_, UN_)                                                                                                  \
-  do {                                                                                                                              \
-    const dim3 grid(cdiv(cdiv(a.N, 16), NT_), ks);                                                                                  \
-    if (a.mx_scale) { if (a.b > 16) hipLaunchKernelGGL((gemv_pk_mx4_kernel<T, NT_, EPI_, WV_, UN_, 2>), grid, dim3(WV_ * 64), 0, s, p);     \
-                      else hipLaunchKernelGGL((gemv_pk_mx4_kernel<T, NT_, EPI_, WV_, UN_, 1>), grid, dim3(WV_ * 64), 0, s, p); }             \
-    else if (a.b > 16) { if (a.w_packed) hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 2, true>), grid, dim3(WV_ * 64), 0, s, p);   \
-                    else hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 2, false>), grid, dim3(WV_ * 64), 0, s, p); }            \
-    else { if (a.w_packed) hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 1, true>), grid, dim3(WV_ * 64), 0, s, p);            \
-           else hipLaunchKernelGGL((gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, 1, false>), grid, dim3(WV_ * 64), 0, s, p); }                     \
-  } while (0)
-    // long launches with K = 64 * 8 * 7 (= 3584: gate|up, lm_head): x-stationary persistent form, one workgroup per CU, >= 4 units each
-    const int n_cu = device_cus();
-    if (a.mx_scale && (a.norm_w || a.epi == EPI_RESID)) {
-      omchat_set_error("launch_gemv: the batched norm-in-GEMV / residual forms read 16-bit weights only (no MXFP4 instantiation)");
-      return 1;
+// one row per wave, `waves` per workgroup, when the rows then deal evenly to 2 workgroups per CU (tuning key 17)
+bool plan_balanced(GemvPlan& g, int n_out, int waves, const GemvTuning& t, int n_cu) {
+  if (!t.rows_balance || n_out != waves * 2 * n_cu) return false;
+  g.rr = 1; g.waves = waves; g.gx = 2 * n_cu; g.gy = 1; g.block = 64 * waves;
+  return true;
+}
+void plan_rows(GemvPlan& g, const GemvArgs& a, int ks, const GemvTuning& t, int n_cu) {
+  const int n_out = a.epi == EPI_SWIGLU ? a.N / 2 : a.N;
+  g.family = GF_ROWS; g.waves = 4; g.block = 256; g.gy = ks;
+  // o_proj of a batch-1 step: 3584 rows as 896 four-wave workgroups are 3.5 per CU (one CU in two streams a fourth workgroup); as
+  // 512 seven-wave workgroups every CU streams the same 14 rows (profiles/r03_r)
+  if (g.rr == 1 && a.epi == EPI_RESID && ks == 1 && plan_balanced(g, n_out, 7, t, n_cu)) return;
+  g.gx = std::min(2048, cdiv(cdiv(n_out, g.rr), 4));
+}
+void plan_rows_norm(GemvPlan& g, const GemvArgs& a, const GemvTuning& t, int n_cu) {
+  const int n_out = a.epi == EPI_SWIGLU ? a.N / 2 : a.N;
+  const int chunks = cdiv(a.K, 512);
+  g.family = GF_ROWS_NORM; g.waves = 4; g.block = 256; g.nch = chunks >= 1 && chunks <= 7 ? chunks : 8;      // (K = 0 passes the checks: 0 chunks take 8)
+  if (g.wf != WF_X12 && g.nch >= 4) {        // the decoder's hidden sizes only (K > 1536): keeps the instantiation count down
+    // measured (profiles/r03_p): gate|up 44.3 -> 42.8 us (2.778 -> 2.738 ms per token); qkv 9.2 us either way; e4m3 gate|up 0.6 % slower
+    const bool want = a.epi == EPI_SWIGLU ? (t.norm_loop & (g.wf != WF_16 ? 4 : 1)) : (a.N < 32768 ? (t.norm_loop & 2) : (t.norm_loop & 8));
+    if (want && n_out >= 8 * n_cu) {
+      g.rr = g.waves = 0;
+      // dynamic form: the outputs dealt by atomic counters instead of equal shares (the XCDs do not stream at the same rate); tuning key 24
+      if (OMCHAT_EXPERIMENTS && a.dyn_ctr && t.dyn) { g.family = GF_ROWS_NORM_DYN; g.gx = 2 * n_cu; return; }
+      g.family = GF_ROWS_NORM_LOOP;
+      g.per_wg = cdiv(n_out, 2 * n_cu);
+      g.skew = (t.skew >= 256u && n_out == g.per_wg * 2 * n_cu && (2 * n_cu) % 8 == 0) ? t.skew : 0u;
+      g.gx = cdiv(n_out, g.per_wg);
+      return;
     }
-    // (units = what one workgroup walks: (gate, up) tile pairs or single tiles; fewer than 4 per workgroup leaves the last round too empty)
-#if !OMCHAT_EXPERIMENTS
+    // qkv of a batch-1 step: 4608 rows = 9 x 512: one row per wave, nine waves per workgroup, 2 workgroups per CU (every CU streams 18 rows)
+    // instead of 576 workgroups of 8 rows on 4 waves (2.25 per CU)
+    if (a.epi == EPI_NONE && g.rr <= 2 && plan_balanced(g, n_out, 9, t, n_cu)) return;
+  }
+  // (four waves per workgroup: 8 / 16 waves -- fewer repeats of the norm -- measured 2.633 / 2.646 against 2.599 ms per token; down_proj's long-K form
+  // with fewer rows per workgroup 2.615-2.765: each workgroup stages the 37 KB x for itself; lm_head with 2 / 1 rows per wave 2.591 against 2.597: noise)
+  g.gx = cdiv(cdiv(n_out, g.rr), 4);
+  if (OMCHAT_EXPERIMENTS && g.wf != WF_X12 && a.epi == EPI_SWIGLU && g.rr == 1) {
+    const int nwg = cdiv(n_out, 4), xs = (int)(t.skew < 256u ? t.skew : 0u);
+    if (xs > 0 && nwg % 8 == 0 && n_out % 4 == 0 && xs < nwg / 8) { g.xskew = xs; g.gx = 8 * (nwg / 8 + xs); }
+  }
+}
+// long K in one piece: x through LDS, the result complete when the launch ends
+void plan_longk(GemvPlan& g, const GemvArgs& a, const GemvTuning& t, int n_cu) {
+  if (OMCHAT_EXPERIMENTS && t.longk_direct > 0) {      // (no bf16x12 instantiation: such rows would go to the 16-bit kernel; gemv_x12_default_forms keeps model.hip from it)
+    g.family = GF_ROWS_LONGK_DIRECT; g.waves = std::min(4, t.longk_direct);
+    if (g.wf == WF_X12) g.wf = WF_16;
+    g.gx = cdiv(a.N, g.waves); g.block = 64 * g.waves;
+    return;
+  }
+  g.family = GF_ROWS_LONGK;
+  g.rows_per_wg = std::max(1, std::min(8, cdiv(a.N, 2 * n_cu)));                // two workgroups per CU
+  g.gx = cdiv(a.N, g.rows_per_wg); g.block = 64 * g.rows_per_wg;
+  g.lds = (cdiv(a.K, 512) + 7) / 8 * 8 * 512 * 2;
+}
+// packed x, one of the x-stationary persistent forms; false = none fits
+bool plan_xs(GemvPlan& g, const GemvArgs& a, int ks, const GemvTuning& t, int n_cu) {
+  if (!a.w_packed || t.no_xs) return false;
+  g.block = 512; g.nch = 7;
+  // long launches with K = 64 * 8 * 7 (= 3584: gate|up, lm_head): x-stationary persistent form, one workgroup per CU, >= 4 units each
+  // (units = what one workgroup walks: (gate, up) tile pairs or single tiles; fewer than 4 per workgroup leaves the last round too empty)
+  const int tiles = a.N / 16, units = a.epi == EPI_SWIGLU ? a.N / 32 : tiles;
+  if (OMCHAT_EXPERIMENTS && ks == 1 && (a.K >> 6) == 56 && a.epi == EPI_RESID) {      // un-split o_proj (+ residual): one tile per workgroup
+    g.family = GF_XS; g.gx = tiles;
+    return true;
+  }
+  if (ks == 1 && (a.K >> 6) == 56 && a.N % 32 == 0 && (a.epi == EPI_SWIGLU || a.epi == EPI_NONE) &&
+      (units >= 4 * n_cu || (a.epi == EPI_NONE && tiles >= n_cu && tiles <= 2 * n_cu) ||
+       ((t.shard & 1) && a.epi == EPI_NONE && tiles < n_cu) || ((t.shard & 8) && a.epi == EPI_SWIGLU && units <= n_cu))) {
+    // the fused qkv projection (288 tiles on 256 CUs) cannot give every CU 4 units: it takes HALF as many workgroups as tiles, two tiles
+    // each -- x is read 144 times instead of 288 and the second tile's loads run under the first's reduction (13.3 -> 11.7 us at b = 32)
+    // a tensor-parallel rank's qkv shard (768 rows = 48 tiles at TP = 8) is shorter than one tile per CU: one tile per workgroup, 48
+    // workgroups that each read x once, instead of gemv_pk_kernel's 24 workgroups of two tiles (round 5: 11.4 us -> see DESIGN.md section 6)
+    g.family = GF_XS; g.norm = OMCHAT_EXPERIMENTS && a.epi == EPI_SWIGLU && a.norm_w;
+    g.gx = units >= 4 * n_cu ? n_cu : (a.epi == EPI_SWIGLU || tiles < n_cu ? units : a.N / 32);
+    return true;
+  }
+  // split-K launch whose chunks cut into ks slices of 40 and 16 (down_proj at TP = 1: 296 = 7 x 40 + 16, ks = 8): same form, one slice per blockIdx.y
+  if (a.epi == EPI_PARTIAL && ks > 1 && (a.K >> 6) % 8 == 0 && a.N % 16 == 0) {
+    const int q = (a.K >> 6) / 8;                 // chunks per wave over the whole K
+    // q = 5 * a5 + 2 * a2 with a5 + a2 == ks
+    int a5 = -1;
+    for (int i = 0; i <= ks; ++i) if (5 * i + 2 * (ks - i) == q) a5 = i;
+    int gx = std::max(1, n_cu / ks);
+    // short launches (o_proj: 224 tiles x 2 slices): two tiles per workgroup instead of >= 4 units on every CU (as for qkv)
+    if (tiles < 4 * gx && tiles % 2 == 0 && (long)tiles * ks >= n_cu && (long)tiles * ks <= 2L * n_cu) gx = tiles / 2;
+    if (a5 >= 0 && (tiles >= 4 * gx || gx == tiles / 2)) {
+      g.family = GF_XS_SPLIT; g.nch = 0; g.gx = gx; g.gy = ks; g.n5 = a5;
+      return true;
+    }
+  }
+  g.block = g.nch = 0;
+  return false;
+}
+}  // namespace
+
+// Every tuple of template integers that a rule here or in the plan_* helpers can answer must also be listed in gemv_launch below: a tuple
+// that is missing there is found at run time only ("the plan names no kernel instantiation"), not by the compiler.
+#define OM_NEED(cond, text) do { if (!(cond)) { g.refusal = text; return g; } } while (0)
+GemvPlan gemv_plan(int dtype, const GemvArgs& a, const GemvTuning& t, int n_cu) {
+  GemvPlan g{};
+  OM_NEED(a.b >= 1 && a.b <= 32, "launch_gemv: batch must be 1..32 per call");
+  OM_NEED(!a.x_packed || !a.w_scale, "launch_gemv: packed x: 16-bit or MXFP4 weights");
+  OM_NEED(!(a.x_packed && a.mx_scale) || (a.w_packed && a.K % 64 == 0), "launch_gemv: packed x with MXFP4 weights: the packed MXFP4 replica (w_packed), K % 64 == 0");
+  OM_NEED(!(a.w_scale && a.mx_scale), "launch_gemv: one weight format per launch: e4m3 (w_scale) or MXFP4 (mx_scale)");      // (EPI_RESID: x-stationary form only, checked below)
+  OM_NEED(!a.w_packed || (a.x_packed && a.N % 16 == 0), "launch_gemv: packed W needs packed x and N % 16 == 0");
+  OM_NEED(!a.y_packed || (a.x_packed && a.epi == EPI_SWIGLU), "launch_gemv: packed y: SwiGLU epilogue of the packed kernel only");
+  if (a.mx_scale) OM_NEED(a.K % 32 == 0 && a.ldw % 4 == 0 && a.ldx % 8 == 0, "launch_gemv: MXFP4 weights: K % 32 == 0 (one e8m0 scale per 32 k), ldw (bytes) % 4, ldx % 8");
+  else OM_NEED(a.K % 64 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0, "launch_gemv: K % 64, ldw % 8, ldx % 8");
+  OM_NEED((!a.w_scale && !(a.mx_scale && !a.x_packed)) || a.b == 1, "launch_gemv: fp8 / MXFP4 weights: batch 1 only (MXFP4 at b > 1: packed x and the packed MXFP4 replica)");
+  OM_NEED(a.epi == EPI_NONE || a.epi == EPI_RESID || a.epi == EPI_SWIGLU || a.epi == EPI_PARTIAL, "launch_gemv: bad epilogue");
+  OM_NEED(a.ksplit <= 1 || a.epi == EPI_PARTIAL, "launch_gemv: ksplit > 1 only with EPI_PARTIAL (fp32 slices)");
+  OM_NEED(a.ksplit <= (a.K + 63) / 64, "launch_gemv: ksplit exceeds the number of 64-wide K chunks");
+  OM_NEED(a.epi != EPI_RESID || a.resid, "launch_gemv: resid missing");
+  OM_NEED(a.epi != EPI_SWIGLU || a.N % 32 == 0, "launch_gemv: SwiGLU needs N % 32 == 0");
+  OM_NEED(!(a.out_f32 && a.epi != EPI_NONE), "launch_gemv: fp32 output only with EPI_NONE");
+  OM_NEED(dtype == OMCHAT_F16 || dtype == OMCHAT_BF16, "launch_gemv: bad dtype");
+  const int ks = a.ksplit > 1 ? a.ksplit : 1;
+  const bool mfma = a.force_mfma || t.force_mfma;
+  g.epi = a.epi; g.gy = 1;
+  g.wf = a.x12_top ? WF_X12 : a.mx_scale ? WF_MX4 : a.w_scale ? WF_E4M3 : WF_16;
+  OM_NEED(!(a.norm_w && a.x_packed) || (a.w_packed && ks == 1 && (a.K >> 6) == 56 && a.epi == EPI_SWIGLU && a.N % 32 == 0 && !t.no_xs),
+          "launch_gemv: the in-register RMSNorm on packed x exists for the x-stationary gate|up form only (packed W, K = 3584, no split-K)");
+  OM_NEED(!(a.epi == EPI_RESID && a.x_packed) || (a.w_packed && ks == 1 && (a.K >> 6) == 56 && a.N % 16 == 0 && a.N / 16 <= n_cu && !t.no_xs),
+          "launch_gemv: the batched residual epilogue exists for the x-stationary form only (packed W, K = 3584, N / 16 <= CUs, no split-K)");
+  if (a.x_packed) {
+    g.nb = a.b > 16 ? 2 : 1;
+    if (g.wf == WF_X12) g.wf = WF_16;      // (packed operands carry no bf16x12 form: x12_top is not read)
+    OM_NEED(!(a.mx_scale && (a.norm_w || a.epi == EPI_RESID)), "launch_gemv: the batched norm-in-GEMV / residual forms read 16-bit weights only (no MXFP4 instantiation)");
     // the seven-launch batched layer (un-split o_proj + residual, RMSNorm in the gate|up GEMV's registers; round 5) measured SLOWER than the eight
     // launches (configs[2] decode 4.57-4.87 vs 4.28 ms per step: the norm delays the weight stream by ~3 us in every workgroup and the NB = 2
     // form spills 35-120 VGPRs next to the 168 registers that hold x and two weight tiles): compiled with -DOMCHAT_EXPERIMENTS=1 only
-    if (a.norm_w || a.epi == EPI_RESID) { omchat_set_error("launch_gemv: the batched norm-in-GEMV / residual forms need a -DOMCHAT_EXPERIMENTS=1 build"); return 1; }
-#else
-    if (a.w_packed && ks == 1 && !g_gemv_no_xs && (a.K >> 6) == 56 && a.epi == EPI_RESID) {      // un-split o_proj (+ residual): one tile per workgroup
-      const dim3 grid(a.N / 16);
-      if (a.b > 16) hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_RESID, 2, 7>), grid, dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_RESID, 1, 7>), grid, dim3(512), 0, s, p);
-      OM_LAUNCH_CHECK();
-      return 0;
-    }
-#endif
-    if (a.w_packed && ks == 1 && !g_gemv_no_xs && (a.K >> 6) == 56 && a.N % 32 == 0 && (a.epi == EPI_SWIGLU || a.epi == EPI_NONE) &&
-        ((a.epi == EPI_SWIGLU ? a.N / 32 : a.N / 16) >= 4 * n_cu || (a.epi == EPI_NONE && a.N / 16 >= n_cu && a.N / 16 <= 2 * n_cu) ||
-         ((g_gemv_shard & 1) && a.epi == EPI_NONE && a.N / 16 < n_cu) || ((g_gemv_shard & 8) && a.epi == EPI_SWIGLU && a.N / 32 <= n_cu))) {
-      // the fused qkv projection (288 tiles on 256 CUs) cannot give every CU 4 units: it takes HALF as many workgroups as tiles, two tiles
-      // each -- x is read 144 times instead of 288 and the second tile's loads run under the first's reduction (13.3 -> 11.7 us at b = 32)
-      // a tensor-parallel rank's qkv shard (768 rows = 48 tiles at TP = 8) is shorter than one tile per CU: one tile per workgroup, 48
-      // workgroups that each read x once, instead of gemv_pk_kernel's 24 workgroups of two tiles (round 5: 11.4 us -> see DESIGN.md section 6)
-      const dim3 grid((a.epi == EPI_SWIGLU ? a.N / 32 : a.N / 16) >= 4 * n_cu ? n_cu : (a.epi == EPI_SWIGLU ? a.N / 32 : a.N / 16 < n_cu ? a.N / 16 : a.N / 32));
-#if OMCHAT_EXPERIMENTS
-      if (a.epi == EPI_SWIGLU && a.norm_w) {
-        if (a.b > 16) hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 2, 7, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 1, 7, true>), grid, dim3(512), 0, s, p);
-      } else
-#endif
-      if (a.mx_scale) {
-        if (a.epi == EPI_SWIGLU) {
-          if (a.b > 16) hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_SWIGLU, 2, 7>), grid, dim3(512), 0, s, p);
-          else hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_SWIGLU, 1, 7>), grid, dim3(512), 0, s, p);
-        } else {
-          if (a.b > 16) hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_NONE, 2, 7>), grid, dim3(512), 0, s, p);
-          else hipLaunchKernelGGL((gemv_xs_mx4_kernel<T, EPI_NONE, 1, 7>), grid, dim3(512), 0, s, p);
-        }
-      } else if (a.epi == EPI_SWIGLU) {
-        if (a.b > 16) hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 2, 7>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_SWIGLU, 1, 7>), grid, dim3(512), 0, s, p);
-      } else {
-        if (a.b > 16) hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_NONE, 2, 7>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((gemv_xs_kernel<T, EPI_NONE, 1, 7>), grid, dim3(512), 0, s, p);
-      }
-      OM_LAUNCH_CHECK();
-      return 0;
-    }
-    // split-K launch whose chunks cut into ks slices of 40 and 16 (down_proj at TP = 1: 296 = 7 x 40 + 16, ks = 8): same form, one slice per blockIdx.y
-    if (a.w_packed && !g_gemv_no_xs && a.epi == EPI_PARTIAL && ks > 1 && (a.K >> 6) % 8 == 0 && a.N % 16 == 0) {
-      const int q = (a.K >> 6) / 8;                 // chunks per wave over the whole K
-      // q = 5 * a5 + 2 * a2 with a5 + a2 == ks
-      int a5 = -1;
-      for (int t = 0; t <= ks; ++t) if (5 * t + 2 * (ks - t) == q) a5 = t;
-      const int n_cu2 = device_cus();
-      int gx = std::max(1, n_cu2 / ks);
-      const int tiles = a.N / 16;
-      // short launches (o_proj: 224 tiles x 2 slices): two tiles per workgroup instead of >= 4 units on every CU (as for qkv)
-      if (tiles < 4 * gx && tiles % 2 == 0 && (long)tiles * ks >= n_cu2 && (long)tiles * ks <= 2L * n_cu2) gx = tiles / 2;
-      if (a5 >= 0 && (tiles >= 4 * gx || gx == tiles / 2)) {
-        const dim3 grid(gx, ks);
-        if (a.mx_scale) {
-          if (a.b > 16) hipLaunchKernelGGL((gemv_xs_split_mx4_kernel<T, 2>), grid, dim3(512), 0, s, p, a5);
-          else hipLaunchKernelGGL((gemv_xs_split_mx4_kernel<T, 1>), grid, dim3(512), 0, s, p, a5);
-        } else if (a.b > 16) hipLaunchKernelGGL((gemv_xs_split_kernel<T, 2>), grid, dim3(512), 0, s, p, a5);
-        else hipLaunchKernelGGL((gemv_xs_split_kernel<T, 1>), grid, dim3(512), 0, s, p, a5);
-        OM_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    if (a.norm_w) { omchat_set_error("launch_gemv: packed-x RMSNorm form: gate|up shape outside the x-stationary launch (N / 32 >= 4 CUs)"); return 1; }
-    if (a.epi == EPI_SWIGLU) OM_PK(2, EPI_SWIGLU, 8, 4);
-    else if (a.epi == EPI_PARTIAL) {
+    OM_NEED(OMCHAT_EXPERIMENTS || !(a.norm_w || a.epi == EPI_RESID), "launch_gemv: the batched norm-in-GEMV / residual forms need a -DOMCHAT_EXPERIMENTS=1 build");
+    if (plan_xs(g, a, ks, t, n_cu)) return g;
+    OM_NEED(!a.norm_w, "launch_gemv: packed-x RMSNorm form: gate|up shape outside the x-stationary launch (N / 32 >= 4 CUs)");
+    // launch shapes from tools/experiments/tune_gemv32.hip (MI355X): <NTILE, WAVES, UNROLL> per shape class
+    g.family = GF_PK; g.wpack = a.w_packed != 0; g.ntile = 2; g.waves = 8; g.unroll = 4;
+    if (a.epi == EPI_PARTIAL) {
       // short K slices (a tensor-parallel rank's o_proj: K = 512 = 8 chunks; down_proj: 37 chunks in two slices): one chunk per wave per
       // step so that all eight waves of a workgroup load, and one tile per workgroup so that the grid covers the CUs (round 5)
       const int cps = cdiv(a.K >> 6, ks);
-      if ((g_gemv_shard & 2) && cps <= 8) OM_PK(1, EPI_PARTIAL, 8, 1);
-      else if ((g_gemv_shard & 2) && cps <= 32) OM_PK(1, EPI_PARTIAL, 8, 2);
-      else if (a.K / ks >= 1536) OM_PK(4, EPI_PARTIAL, 4, 2);
-      else OM_PK(2, EPI_PARTIAL, 8, 4);
-    }
-    else if (a.N >= 32768) OM_PK(4, EPI_NONE, 4, 4);
-    else OM_PK(2, EPI_NONE, 8, 4);
-#undef OM_PK
-    OM_LAUNCH_CHECK();
-    return 0;
+      if ((t.shard & 2) && cps <= 32) { g.ntile = 1; g.unroll = cps <= 8 ? 1 : 2; }
+      else if (a.K / ks >= 1536) { g.ntile = 4; g.waves = 4; g.unroll = 2; }
+    } else if (a.epi == EPI_NONE && a.N >= 32768) { g.ntile = 4; g.waves = 4; }
+    g.gx = cdiv(cdiv(a.N, 16), g.ntile); g.gy = ks; g.block = 64 * g.waves;
+    return g;
   }
   if (a.x12_top) {      // bf16x12 rows: the three long launches of the batch-1 step, nothing else
-    const bool ok = std::is_same<T, bf16>::value && a.b == 1 && !a.x_packed && !a.w_packed && ks == 1 && a.K >= 512 && a.K % 512 == 0 &&
-                    a.ldw == a.K / 2 * 3 && a.x12_cnt && a.x12_patch && !a.w_scale && !a.mx_scale && !a.force_mfma && !g_gemv_force_mfma;
+    const bool ok = dtype == OMCHAT_BF16 && a.b == 1 && !a.w_packed && ks == 1 && a.K >= 512 && a.K % 512 == 0 &&
+                    a.ldw == a.K / 2 * 3 && a.x12_cnt && a.x12_patch && !a.w_scale && !a.mx_scale && !mfma;
     const bool norm = ok && a.norm_w && (a.epi == EPI_SWIGLU || a.epi == EPI_NONE) && a.K <= RW_MAXC * 512;
     const bool longk = ok && !a.norm_w && a.epi == EPI_RESID && !a.out_f32 && a.K > RW_MAXC * 512 && a.K <= 32768;
-    if (!norm && !longk) {
-      omchat_set_error("launch_gemv: bf16x12 weights: bf16, b == 1, K % 512 == 0, and norm_w with EPI_SWIGLU / EPI_NONE (K <= 4096) or EPI_RESID on 4096 < K <= 32768");
-      return 1;
-    }
-    if (longk) { const int rc = launch_rows_longk<T>(p, s); if (rc) return rc; }
-    else if (a.epi == EPI_SWIGLU) launch_rows_norm_x12<EPI_SWIGLU>(p, s);
-    else launch_rows_norm_x12<EPI_NONE>(p, s);
-    OM_LAUNCH_CHECK();
-    return 0;
+    OM_NEED(norm || longk, "launch_gemv: bf16x12 weights: bf16, b == 1, K % 512 == 0, and norm_w with EPI_SWIGLU / EPI_NONE (K <= 4096) or EPI_RESID on 4096 < K <= 32768");
+    if (longk) plan_longk(g, a, t, n_cu);
+    else { g.rr = rows_per_wave(a, WF_X12, t, n_cu); plan_rows_norm(g, a, t, n_cu); }
+    return g;
   }
-  if (a.b == 1 && !a.x_packed && a.epi == EPI_RESID && ks == 1 && !a.out_f32 && a.K > RW_MAXC * 512 && a.K % 8 == 0 && a.K <= 32768 &&
-      ((!a.force_mfma && !g_gemv_force_mfma) || a.mx_scale)) {
-    const int rc = launch_rows_longk<T>(p, s);      // long K in one piece: x through LDS, the result complete when the launch ends
-    if (rc) return rc;
-    OM_LAUNCH_CHECK();
-    return 0;
+  if (a.b == 1 && a.epi == EPI_RESID && ks == 1 && !a.out_f32 && a.K > RW_MAXC * 512 && a.K % 8 == 0 && a.K <= 32768 && (!mfma || a.mx_scale)) {
+    plan_longk(g, a, t, n_cu);
+    return g;
   }
   const bool rows_ok = a.b == 1 && cdiv(cdiv(a.K, 512), ks) <= RW_MAXC;
-  if (a.norm_w && !(rows_ok && ks == 1 && !a.force_mfma && !g_gemv_force_mfma && (a.epi == EPI_NONE || a.epi == EPI_SWIGLU))) {
-    omchat_set_error("launch_gemv: the in-register RMSNorm needs the whole-row batch-1 form without split-K (K <= 4096), epilogue NONE / SWIGLU");
-    return 1;
+  OM_NEED(!a.norm_w || (rows_ok && ks == 1 && !mfma && (a.epi == EPI_NONE || a.epi == EPI_SWIGLU)),
+          "launch_gemv: the in-register RMSNorm needs the whole-row batch-1 form without split-K (K <= 4096), epilogue NONE / SWIGLU");
+  OM_NEED(!(a.w_scale || a.mx_scale) || rows_ok, "launch_gemv: fp8 / MXFP4 weights need b == 1 and <= 8 chunks of 512 per K slice");
+  if (rows_ok && (a.w_scale || a.mx_scale || !mfma)) {       // whole-row streaming form
+    g.rr = rows_per_wave(a, g.wf, t, n_cu);
+    if (a.norm_w) plan_rows_norm(g, a, t, n_cu);
+    else plan_rows(g, a, ks, t, n_cu);
+    return g;
   }
-  if ((a.w_scale || a.mx_scale) && !rows_ok) { omchat_set_error("launch_gemv: fp8 / MXFP4 weights need b == 1 and <= 8 chunks of 512 per K slice"); return 1; }
-  if (rows_ok && (a.w_scale || a.mx_scale || (!a.force_mfma && !g_gemv_force_mfma))) {       // whole-row streaming form
-    switch (a.epi) {
-      case EPI_PARTIAL: launch_rows<T, EPI_PARTIAL>(p, s); break;
-      case EPI_SWIGLU: launch_rows<T, EPI_SWIGLU>(p, s); break;
-      case EPI_RESID: launch_rows<T, EPI_RESID>(p, s); break;
-      default: launch_rows<T, EPI_NONE>(p, s); break;
-    }
-    OM_LAUNCH_CHECK();
-    return 0;
-  }
-  if (a.b > 16) {       // two batch tiles per weight fragment: weights still stream once for b <= 32
-    if (a.epi == EPI_PARTIAL) hipLaunchKernelGGL((gemv_kernel<T, 1, EPI_PARTIAL, 8, 4, false, 2>), dim3(cdiv(a.N, 16), ks), dim3(512), 0, s, p);
-    else if (a.epi == EPI_SWIGLU) hipLaunchKernelGGL((gemv_kernel<T, 2, EPI_SWIGLU, 8, 4, false, 2>), dim3(cdiv(a.N, 32)), dim3(512), 0, s, p);
-    else if (a.epi == EPI_RESID) hipLaunchKernelGGL((gemv_kernel<T, 1, EPI_RESID, 8, 4, false, 2>), dim3(cdiv(a.N, 16)), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((gemv_kernel<T, 2, EPI_NONE, 8, 4, false, 2>), dim3(cdiv(a.N, 32)), dim3(512), 0, s, p);
-    OM_LAUNCH_CHECK();
-    return 0;
-  }
-  if (a.epi == EPI_PARTIAL) {
-    if (a.K / 64 / ks <= 32)
-      hipLaunchKernelGGL((gemv_kernel<T, 1, EPI_PARTIAL, 4, 8>), dim3(cdiv(a.N, 16), ks), dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemv_kernel<T, 1, EPI_PARTIAL, 8, 4>), dim3(cdiv(a.N, 16), ks), dim3(512), 0, s, p);
-  } else if (a.epi == EPI_SWIGLU) {
-    hipLaunchKernelGGL((gemv_kernel<T, 2, EPI_SWIGLU, 8, 4>), dim3(cdiv(a.N, 32)), dim3(512), 0, s, p);
-  } else if (a.epi == EPI_RESID) {
-    hipLaunchKernelGGL((gemv_kernel<T, 1, EPI_RESID, 8, 4>), dim3(cdiv(a.N, 16)), dim3(512), 0, s, p);
-  } else {
-    // wide outputs (lm_head): 2 tiles per workgroup halves the x re-reads
-    if (a.N >= 16384)
-      hipLaunchKernelGGL((gemv_kernel<T, 2, EPI_NONE, 8, 8>), dim3(cdiv(a.N, 32)), dim3(512), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemv_kernel<T, 1, EPI_NONE, 8, 8>), dim3(cdiv(a.N, 16)), dim3(512), 0, s, p);
-  }
-  OM_LAUNCH_CHECK();
-  return 0;
+  // the MFMA form.  Launch shapes measured with tools/experiments/tune_gemv.hip on MI355X (r01): plain loads beat non-temporal ones for this access
+  // shape (gate|up 54.9 -> 49.4 us), split-K slices prefer 4 waves x 8 chunks in flight when a slice is short.
+  // b > 16: two batch tiles per weight fragment: weights still stream once for b <= 32
+  g.family = GF_MFMA; g.nb = a.b > 16 ? 2 : 1; g.waves = 8; g.unroll = 4;
+  // wide outputs (lm_head): 2 tiles per workgroup halves the x re-reads
+  g.ntile = a.epi == EPI_SWIGLU || (a.epi == EPI_NONE && (g.nb == 2 || a.N >= 16384)) ? 2 : 1;
+  if (g.nb == 1 && a.epi == EPI_PARTIAL && a.K / 64 / ks <= 32) { g.waves = 4; g.unroll = 8; }
+  if (g.nb == 1 && a.epi == EPI_NONE) g.unroll = 8;
+  g.gx = cdiv(a.N, 16 * g.ntile); g.gy = ks; g.block = 64 * g.waves;
+  return g;
+}
+#undef OM_NEED
+
+int gemv_split_k(int b, int K, int H, bool packed, bool down, const GemvTuning& t) {
+  // K slices: batch 1 (whole-row streaming form) wants <= 8 chunks of 512 per slice and >= ~2500 waves in the grid;
+  // the MFMA form (b > 1) wants ~2-3 workgroups per CU
+  // (tools/experiments/tune_rows.hip: down_proj 18944 -> 8 slices 23.3 us vs 5 slices 27.6 us; o_proj is latency-bound, 1-3 slices alike)
+  if (b == 1) { const int nch = cdiv(K, 512); return nch >= 16 ? std::min(DEC_KS_MAX, nch) : std::max(1, std::min(3, nch)); }
+  // batched o_proj: K = 3584 cuts into two exact slices for the x-stationary form (40 + 16 chunks, gemv_xs_split_kernel) when the packed
+  // replica is in use; otherwise ~2 workgroups per CU for the MFMA form
+  if (!down && packed && K == 3584) return 2;
+  // shard widths of a tensor-parallel rank (round 5): a K of <= 64 chunks is cut into slices of >= 16 chunks only (o_proj K = 512: one
+  // slice, down_proj K = 2368: two) -- eight slices of 4-5 chunks left seven of a workgroup's eight waves without a chunk, and every slice
+  // is 4 b H bytes that the residual + RMSNorm launch (under TP: the peer exchange) has to read
+  if ((t.shard & 2) && K / 64 <= 64) return std::max(1, std::min(DEC_KS_MAX, (K / 64) / 16));
+  return std::max(1, std::min(DEC_KS_MAX, std::min(K / 64, (down ? 3 : 1) * cdiv(512, cdiv(H, 16)))));
 }
 
+namespace {
+template <auto KERNEL, typename... A>
+int launch_k(const GemvPlan& g, hipStream_t s, const A&... args) {
+  hipLaunchKernelGGL(KERNEL, dim3(g.gx, g.gy), dim3(g.block), (size_t)g.lds, s, args...);
+  return 0;
+}
+// ... after raising the kernel's dynamic-LDS limit to 64 KB, once per device
+template <auto KERNEL, typename... A>
+int launch_k_lds64(const GemvPlan& g, hipStream_t s, const A&... args) {
+  static PerDeviceOnce set;
+  if (set.first()) OM_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+  return launch_k<KERNEL>(g, s, args...);
+}
+// runtime integer -> template argument: f(std::integral_constant<int, V>) for the listed V that equals v; -1 when none does
+template <int... V, typename F>
+int with_int(int v, F&& f) {
+  int rc = -1;
+  (void)((v == V ? (rc = f(std::integral_constant<int, V>{}), true) : false) || ...);
+  return rc;
+}
+#define IV(c) decltype(c)::value
+// the (epilogue, rows per wave) pairs that rows_per_wave answers without / with norm_w, for 16-bit (q = false) and quantised rows (the norm
+// form's one row per wave on EPI_NONE exists as the nine-wave workgroup only).  gemv_launch asks them in a plain `if`, not `if constexpr`, on
+// purpose: the library's device code has always held the kernels of the other pairs too (no launch reaches them, and the host compiler drops
+// their stubs as dead code), and a discarded branch would take them out of it.
+constexpr bool rows_rr(int epi, int rr, bool q) {
+  return epi == EPI_NONE ? rr == 1 || rr == (q ? 8 : 4) : epi == EPI_RESID ? rr == 1 || rr == 4 : epi == EPI_SWIGLU ? rr == 4 || (rr == 1 && !q) : rr == 4;
+}
+constexpr bool norm_rr(int epi, int rr, bool q) { return epi == EPI_NONE ? rr == 2 || rr == 4 : q ? rr == 1 || rr == 2 || rr == 4 : rr <= 3; }
+
+// The only place that names kernel instantiations: the library holds exactly the ones listed here.  -1 = the plan names none.
+template <typename T>
+int gemv_launch(const GemvPlan& g, const GemvP& p, hipStream_t s) {
+  switch (g.family) {
+    case GF_MFMA:
+#define OM_MFMA(NT_, EPI_, WV_, UN_, NB_)                                                                  \
+  if (g.ntile == NT_ && g.epi == EPI_ && g.waves == WV_ && g.unroll == UN_ && g.nb == NB_)                 \
+    return launch_k<gemv_kernel<T, NT_, EPI_, WV_, UN_, false, NB_>>(g, s, p)
+      OM_MFMA(1, EPI_PARTIAL, 8, 4, 2); OM_MFMA(2, EPI_SWIGLU, 8, 4, 2); OM_MFMA(1, EPI_RESID, 8, 4, 2); OM_MFMA(2, EPI_NONE, 8, 4, 2);
+      OM_MFMA(1, EPI_PARTIAL, 4, 8, 1); OM_MFMA(1, EPI_PARTIAL, 8, 4, 1); OM_MFMA(2, EPI_SWIGLU, 8, 4, 1); OM_MFMA(1, EPI_RESID, 8, 4, 1);
+      OM_MFMA(2, EPI_NONE, 8, 8, 1); OM_MFMA(1, EPI_NONE, 8, 8, 1);
+#undef OM_MFMA
+      return -1;
+    case GF_PK:
+#define OM_PK(NT_, EPI_, WV_, UN_)                                                                         \
+  if (g.ntile == NT_ && g.epi == EPI_ && g.waves == WV_ && g.unroll == UN_)                                \
+    return with_int<1, 2>(g.nb, [&](auto NB) {                                                             \
+      if (g.wf == WF_MX4) return launch_k<gemv_pk_mx4_kernel<T, NT_, EPI_, WV_, UN_, IV(NB)>>(g, s, p);      \
+      if (g.wpack) return launch_k<gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, IV(NB), true>>(g, s, p);           \
+      return launch_k<gemv_pk_kernel<T, NT_, EPI_, WV_, UN_, IV(NB), false>>(g, s, p);                       \
+    })
+      OM_PK(2, EPI_SWIGLU, 8, 4); OM_PK(1, EPI_PARTIAL, 8, 1); OM_PK(1, EPI_PARTIAL, 8, 2); OM_PK(4, EPI_PARTIAL, 4, 2); OM_PK(2, EPI_PARTIAL, 8, 4);
+      OM_PK(4, EPI_NONE, 4, 4); OM_PK(2, EPI_NONE, 8, 4);
+#undef OM_PK
+      return -1;
+    case GF_XS:
+      return with_int<1, 2>(g.nb, [&](auto NB) {
+#if OMCHAT_EXPERIMENTS
+        if (g.epi == EPI_RESID) return launch_k<gemv_xs_kernel<T, EPI_RESID, IV(NB), 7>>(g, s, p);
+        if (g.norm) return launch_k<gemv_xs_kernel<T, EPI_SWIGLU, IV(NB), 7, true>>(g, s, p);
+#endif
+        return with_int<EPI_SWIGLU, EPI_NONE>(g.epi, [&](auto EPI) {
+          if (g.wf == WF_MX4) return launch_k<gemv_xs_mx4_kernel<T, IV(EPI), IV(NB), 7>>(g, s, p);
+          return launch_k<gemv_xs_kernel<T, IV(EPI), IV(NB), 7>>(g, s, p);
+        });
+      });
+    case GF_XS_SPLIT:
+      return with_int<1, 2>(g.nb, [&](auto NB) {
+        if (g.wf == WF_MX4) return launch_k<gemv_xs_split_mx4_kernel<T, IV(NB)>>(g, s, p, g.n5);
+        return launch_k<gemv_xs_split_kernel<T, IV(NB)>>(g, s, p, g.n5);
+      });
+    case GF_ROWS:      // four waves, the rows per wave that rows_per_wave can answer; seven waves for the balanced o_proj
+      return with_int<EPI_NONE, EPI_RESID, EPI_SWIGLU, EPI_PARTIAL>(g.epi, [&](auto EPI) {
+        return with_int<1, 4, 8>(g.rr, [&](auto RR) {
+          auto wf = [&](auto WAVES) {
+            if (rows_rr(IV(EPI), IV(RR), true)) {
+              if (g.wf == WF_MX4) return launch_k<gemv_rows_mx4_kernel<T, IV(EPI), IV(RR), IV(WAVES)>>(g, s, p);
+              if (g.wf == WF_E4M3) return launch_k<gemv_rows_kernel<T, IV(EPI), IV(RR), IV(WAVES), true>>(g, s, p);
+            }
+            if constexpr (IV(RR) != 8) if (rows_rr(IV(EPI), IV(RR), false) && g.wf == WF_16) return launch_k<gemv_rows_kernel<T, IV(EPI), IV(RR), IV(WAVES), false>>(g, s, p);
+            return -1;
+          };
+          if constexpr (IV(EPI) == EPI_RESID && IV(RR) == 1) if (g.waves == 7) return wf(std::integral_constant<int, 7>{});
+          return wf(std::integral_constant<int, 4>{});
+        });
+      });
+    case GF_ROWS_NORM:      // four waves; RR = 3 for 16-bit rows only; nine waves for the balanced qkv; bf16x12: one pair or four rows per wave
+      return with_int<EPI_SWIGLU, EPI_NONE>(g.epi, [&](auto EPI) {
+        return with_int<1, 2, 3, 4, 5, 6, 7, 8>(g.nch, [&](auto NCH) {
+          if (g.wf == WF_X12) {
+            constexpr int RR = IV(EPI) == EPI_SWIGLU ? 1 : 4;
+            if constexpr (std::is_same<T, bf16>::value) if (g.rr == RR) return launch_k<gemv_rows_norm_x12_kernel<bf16, IV(EPI), RR, IV(NCH)>>(g, s, p);
+            return -1;
+          }
+          if constexpr (IV(EPI) == EPI_NONE && IV(NCH) >= 4) if (g.waves == 9 && g.rr == 1) {
+            if (g.wf == WF_MX4) return launch_k<gemv_rows_norm_mx4_kernel<T, IV(EPI), 1, IV(NCH), 9>>(g, s, p);
+            return g.wf == WF_E4M3 ? launch_k<gemv_rows_norm_kernel<T, IV(EPI), 1, IV(NCH), true, 9>>(g, s, p) : launch_k<gemv_rows_norm_kernel<T, IV(EPI), 1, IV(NCH), false, 9>>(g, s, p);
+          }
+          return with_int<1, 2, 3, 4>(g.rr, [&](auto RR) {
+            if constexpr (IV(RR) != 3) if (norm_rr(IV(EPI), IV(RR), true)) {
+              if (g.wf == WF_MX4) return launch_k<gemv_rows_norm_mx4_kernel<T, IV(EPI), IV(RR), IV(NCH)>>(g, s, p);
+              if (g.wf == WF_E4M3) return launch_k<gemv_rows_norm_kernel<T, IV(EPI), IV(RR), IV(NCH), true>>(g, s, p);
+            }
+            if (norm_rr(IV(EPI), IV(RR), false) && g.wf == WF_16) return launch_k<gemv_rows_norm_kernel<T, IV(EPI), IV(RR), IV(NCH), false>>(g, s, p);
+            return -1;
+          });
+        });
+      });
+    case GF_ROWS_NORM_LOOP:
+      return with_int<EPI_SWIGLU, EPI_NONE>(g.epi, [&](auto EPI) {
+        return with_int<4, 5, 6, 7, 8>(g.nch, [&](auto NCH) {
+          if (g.wf == WF_MX4) return launch_k<gemv_rows_norm_loop_mx4_kernel<T, IV(EPI), IV(NCH)>>(g, s, p, g.per_wg, g.skew);
+          return g.wf == WF_E4M3 ? launch_k<gemv_rows_norm_loop_kernel<T, IV(EPI), IV(NCH), true>>(g, s, p, g.per_wg, g.skew) : launch_k<gemv_rows_norm_loop_kernel<T, IV(EPI), IV(NCH), false>>(g, s, p, g.per_wg, g.skew);
+        });
+      });
+    case GF_ROWS_LONGK:
+      if (g.wf == WF_X12) {
+        if constexpr (std::is_same<T, bf16>::value) return launch_k_lds64<gemv_rows_longk_x12_kernel<T>>(g, s, p, g.rows_per_wg);
+        return -1;
+      }
+      if (g.wf == WF_MX4) return launch_k_lds64<gemv_rows_longk_mx4_kernel<T>>(g, s, p, g.rows_per_wg);
+      return g.wf == WF_E4M3 ? launch_k_lds64<gemv_rows_longk_kernel<T, true>>(g, s, p, g.rows_per_wg) : launch_k_lds64<gemv_rows_longk_kernel<T, false>>(g, s, p, g.rows_per_wg);
+#if OMCHAT_EXPERIMENTS
+    case GF_ROWS_NORM_DYN:
+      return with_int<EPI_SWIGLU, EPI_NONE>(g.epi, [&](auto EPI) {
+        return with_int<4, 5, 6, 7, 8>(g.nch, [&](auto NCH) {
+          if (g.wf == WF_MX4) return launch_k<gemv_rows_norm_dyn_mx4_kernel<T, IV(EPI), IV(NCH)>>(g, s, p);
+          return g.wf == WF_E4M3 ? launch_k<gemv_rows_norm_dyn_kernel<T, IV(EPI), IV(NCH), true>>(g, s, p) : launch_k<gemv_rows_norm_dyn_kernel<T, IV(EPI), IV(NCH), false>>(g, s, p);
+        });
+      });
+    case GF_ROWS_LONGK_DIRECT:
+      if (g.wf == WF_MX4) return launch_k<gemv_rows_longk_direct_mx4_kernel<T>>(g, s, p);
+      return g.wf == WF_E4M3 ? launch_k<gemv_rows_longk_direct_kernel<T, true>>(g, s, p) : launch_k<gemv_rows_longk_direct_kernel<T, false>>(g, s, p);
+#endif
+  }
+  return -1;
+}
 }  // namespace
 
-void gemv_set_force_mfma(int v) { g_gemv_force_mfma = v; }
-int gemv_get_force_mfma() { return g_gemv_force_mfma; }
-void gemv_set_no_xs(int v) { g_gemv_no_xs = v; }
-void gemv_set_shard_shapes(int v) { g_gemv_shard = v; }
-int gemv_get_shard_shapes() { return g_gemv_shard; }
-void gemv_set_norm_loop(int v) { g_gemv_norm_loop = v; }
-void gemv_set_gu_rr(int v) { if (v >= 16) g_gemv_gu_rr8 = v / 16; else g_gemv_gu_rr = v; }
-void gemv_set_dyn(int v) { g_gemv_dyn = v; }
-void gemv_set_longk_direct(int v) { g_gemv_longk_direct = v; }
-void gemv_set_skew(int v) { g_gemv_skew = (unsigned)v; }
-void gemv_set_rows_balance(int v) { g_gemv_rows_balance = v; }
+const GemvTuning& gemv_tuning() { return g_tune; }
+void gemv_set_force_mfma(int v) { g_tune.force_mfma = v; }
+int gemv_get_force_mfma() { return g_tune.force_mfma; }
+void gemv_set_no_xs(int v) { g_tune.no_xs = v; }
+void gemv_set_shard_shapes(int v) { g_tune.shard = v; }
+int gemv_get_shard_shapes() { return g_tune.shard; }
+void gemv_set_norm_loop(int v) { g_tune.norm_loop = v; }
+void gemv_set_gu_rr(int v) { if (v >= 16) g_tune.gu_rr8 = v / 16; else g_tune.gu_rr = v; }
+void gemv_set_dyn(int v) { g_tune.dyn = v; }
+void gemv_set_longk_direct(int v) { g_tune.longk_direct = v; }
+void gemv_set_skew(int v) { g_tune.skew = (unsigned)v; }
+void gemv_set_rows_balance(int v) { g_tune.rows_balance = v; }
 int gemv_x12_default_forms() {
-  return ((g_gemv_norm_loop & 1) == 0 && g_gemv_gu_rr == 1 && g_gemv_skew == 0u ? 1 : 0) | (g_gemv_longk_direct == 0 ? 2 : 0) | ((g_gemv_norm_loop & 8) == 0 ? 4 : 0);
+  return ((g_tune.norm_loop & 1) == 0 && g_tune.gu_rr == 1 && g_tune.skew == 0u ? 1 : 0) | (g_tune.longk_direct == 0 ? 2 : 0) | ((g_tune.norm_loop & 8) == 0 ? 4 : 0);
 }
 
 namespace {
@@ -2423,23 +2413,17 @@ int launch_gemv_wait(int dtype, const GemvArgs& a, const unsigned* flags, unsign
 }
 
 int launch_gemv(int dtype, const GemvArgs& a, hipStream_t s) {
-  OM_CHECK(a.b >= 1 && a.b <= 32, "batch must be 1..32 per call");
-  OM_CHECK(!a.x_packed || !a.w_scale, "packed x: 16-bit or MXFP4 weights");
-  OM_CHECK(!(a.x_packed && a.mx_scale) || (a.w_packed && a.K % 64 == 0), "packed x with MXFP4 weights: the packed MXFP4 replica (w_packed), K % 64 == 0");
-  OM_CHECK(!(a.w_scale && a.mx_scale), "one weight format per launch: e4m3 (w_scale) or MXFP4 (mx_scale)");      // (EPI_RESID: x-stationary form only, checked in launch_t)
-  OM_CHECK(!a.w_packed || (a.x_packed && a.N % 16 == 0), "packed W needs packed x and N % 16 == 0");
-  OM_CHECK(!a.y_packed || (a.x_packed && a.epi == EPI_SWIGLU), "packed y: SwiGLU epilogue of the packed kernel only");
-  if (a.mx_scale) OM_CHECK(a.K % 32 == 0 && a.ldw % 4 == 0 && a.ldx % 8 == 0, "MXFP4 weights: K % 32 == 0 (one e8m0 scale per 32 k), ldw (bytes) % 4, ldx % 8");
-  else OM_CHECK(a.K % 64 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0, "K % 64, ldw % 8, ldx % 8");
-  OM_CHECK((!a.w_scale && !(a.mx_scale && !a.x_packed)) || a.b == 1, "fp8 / MXFP4 weights: batch 1 only (MXFP4 at b > 1: packed x and the packed MXFP4 replica)");
-  OM_CHECK(a.epi == EPI_NONE || a.epi == EPI_RESID || a.epi == EPI_SWIGLU || a.epi == EPI_PARTIAL, "bad epilogue");
-  OM_CHECK(a.ksplit <= 1 || a.epi == EPI_PARTIAL, "ksplit > 1 only with EPI_PARTIAL (fp32 slices)");
-  OM_CHECK(a.ksplit <= (a.K + 63) / 64, "ksplit exceeds the number of 64-wide K chunks");
-  OM_CHECK(a.epi != EPI_RESID || a.resid, "resid missing");
-  OM_CHECK(a.epi != EPI_SWIGLU || a.N % 32 == 0, "SwiGLU needs N % 32 == 0");
-  OM_CHECK(!(a.out_f32 && a.epi != EPI_NONE), "fp32 output only with EPI_NONE");
-  if (dtype == OMCHAT_F16) return launch_t<f16>(a, s);
-  if (dtype == OMCHAT_BF16) return launch_t<bf16>(a, s);
-  omchat_set_error("launch_gemv: bad dtype");
-  return 1;
+  const GemvPlan g = gemv_plan(dtype, a, g_tune, device_cus());
+  if (g.refusal) { omchat_set_error(g.refusal); return 1; }
+  GemvP p{a.X, a.W, a.Y, a.bias, a.resid, a.ldx, a.ldw, a.ldy, a.ldr, a.b, a.N, a.K, a.out_f32, a.ksplit > 1 ? a.ksplit : 1, a.w_scale, a.y_packed, a.norm_w, a.norm_eps,
+          (unsigned*)a.dyn_ctr, a.y_pack, a.dbg, a.mx_scale, a.x12_top, a.x12_cnt, a.x12_patch};
+#if OMCHAT_EXPERIMENTS
+  p.xskew = g.xskew;
+#endif
+  const int rc = dtype == OMCHAT_F16 ? gemv_launch<f16>(g, p, s) : gemv_launch<bf16>(g, p, s);
+  if (rc < 0) { omchat_set_error("launch_gemv: the plan names no kernel instantiation"); return 1; }
+  if (rc) return rc;
+  OM_LAUNCH_CHECK();
+  return 0;
 }
+

@@ -145,6 +145,32 @@ int launch_pack_w(int dtype, const void* W, int ldw, int N, int K, void* out, hi
 // SP (N K / 32 bytes); a byte shuffle.  N % 16 == 0, K % 64 == 0
 int launch_pack_w4(const void* W4, const unsigned char* S, int N, int K, void* W4P, unsigned char* SP, hipStream_t s);
 int launch_gemv(int dtype, const GemvArgs& a, hipStream_t stream);
+// What the tuning keys set for the GEMVs (process-global: one instance in gemv.hip behind gemv_set_* / gemv_get_*; gemv.hip has each key's meaning)
+struct GemvTuning {
+  int force_mfma = 0, no_xs = 0, shard = 15, norm_loop = 0, gu_rr = 1, gu_rr8 = 1, dyn = 0, longk_direct = 0, rows_balance = 1;
+  unsigned skew = 0;
+};
+const GemvTuning& gemv_tuning();
+// kernel families of launch_gemv (omchat_op_gemv_plan reports them by these numbers); the last two exist in -DOMCHAT_EXPERIMENTS=1 builds only
+enum GemvFamily { GF_MFMA = 0, GF_PK, GF_XS, GF_XS_SPLIT, GF_ROWS, GF_ROWS_NORM, GF_ROWS_NORM_LOOP, GF_ROWS_LONGK, GF_ROWS_NORM_DYN, GF_ROWS_LONGK_DIRECT };
+constexpr int WF_16 = 0, WF_E4M3 = 1, WF_MX4 = 2, WF_X12 = 3;      // weight forms (gemv.hip)
+// The whole launch decision of one launch_gemv call: either `refusal` (launch_gemv's error text) or the kernel -- family, weight form, epilogue
+// and the integer template arguments that the family has (the others stay 0) -- with its grid, block, dynamic LDS and scalar arguments.
+struct GemvPlan {
+  const char* refusal;
+  int family, wf, wpack, epi, ntile, waves, unroll, nb, rr, nch, norm;      // norm: gemv_xs_kernel's NORM (experiments build)
+  int gx, gy, block, lds;
+  int per_wg; unsigned skew;      // gemv_rows_norm_loop_kernel
+  int rows_per_wg;                // gemv_rows_longk_kernel
+  int n5;                         // gemv_xs_split_kernel
+  int xskew;                      // GemvP::xskew of the non-loop gate|up form (experiments build, tuning key 28 < 256)
+};
+// pure: reads its arguments only (of a's pointers only whether they are null); n_cu = the device's compute units
+GemvPlan gemv_plan(int dtype, const GemvArgs& a, const GemvTuning& t, int n_cu);
+constexpr int DEC_KS_MAX = 8;
+// K slices (ksplit of the EPI_PARTIAL launch) of a decode step's o_proj (down = false, K = q width) or down_proj (down = true, K = mlp width)
+// at batch b and hidden size H; packed: the step streams a packed replica (16-bit or MXFP4)
+int gemv_split_k(int b, int K, int H, bool packed, bool down, const GemvTuning& t);
 // experiments build (tuning key 42): the batch-1 o_proj GEMV launched out of order behind the split-KV merge, waiting on its per-head completion flags
 int launch_gemv_wait(int dtype, const GemvArgs& a, const unsigned* flags, unsigned epoch, int nflags, unsigned* err, int mode, hipStream_t s);
 // per-row (output channel) symmetric quantisation of W [N][ldw] (T) to OCP e4m3: scale[n] = absmax_n / 448 (1 if the row is 0),

@@ -751,3 +751,84 @@ def test_split_kv_workspace_sizing_is_pinned(name, args, want):
     if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
         pytest.skip("the table is recorded for 256 compute units")
     assert getattr(_lib.lib(), "omchat_op_attn_" + name)(*args) == want
+
+
+# tests/golden/gemv_plan_table.json.  "traced": (omchat_op_gemv_plan arguments dtype, b, N, K, epi, ksplit, flags, wf; tuning keys set
+# for the call; the plan's fields at 256 compute units, or the refusal text), one row per distinct call of a launch matrix that drove
+# the ten omchat_op_gemv* hooks on an MI355X under a kernel trace with a PRODUCT library built BEFORE gemv_plan existed: both dtypes;
+# the four decoder projections and the lm_head of the default config at b = 1, 2, 16, 17, 32, 33, at the TP = 1, 2, 4, 8 shard widths
+# with the decode step's split-K counts; ragged shapes that reach the MFMA fallbacks; both sides of K = 4096 and 32768; tuning keys 1,
+# 11, 16, 17, 28, 34, 38; every refusal the hooks can reach.  "unreached": the refusals no hook reaches (packed operands with a norm, a
+# residual or N % 16 != 0), texts from the ladder's source.  "experiments": what only a -DOMCHAT_EXPERIMENTS=1 library answers (key 28
+# below 256, key 39, the packed residual / norm forms), worked out by hand from the ladder's source; such a library answers the
+# product rows too, except the ones that record the product build's own behaviour (its "need a -DOMCHAT_EXPERIMENTS=1 build" refusal
+# and its ignoring key 28 below 256).  "split_k": (b, K, H, packed, down, key 34) -> the decode step's ksplit.
+_GEMV_TUNING_DEFAULTS = {1: (0,), 11: (0,), 16: (0,), 17: (1,), 28: (0,), 34: (15,), 38: (1, 16), 39: (0,)}
+
+
+@pytest.fixture(scope="module")
+def gemv_table():
+    with open(os.path.join(ROOT, "tests", "golden", "gemv_plan_table.json")) as f:
+        return json.load(f)
+
+
+def _with_tuning(l, pairs, fn):
+    try:
+        for k, v in pairs:
+            assert l.omchat_op_set_tuning(k, v) == 0
+        return fn()
+    finally:
+        for k, _ in pairs:
+            for v in _GEMV_TUNING_DEFAULTS[k]:
+                assert l.omchat_op_set_tuning(k, v) == 0
+
+
+def _product_only(tune, want):
+    return (isinstance(want, str) and "need a -DOMCHAT_EXPERIMENTS=1 build" in want) or any(k == 28 and 0 < v < 256 for k, v in tune)
+
+
+@pytest.mark.parametrize("part", ["traced", "unreached", "experiments"])
+def test_gemv_plan_is_pinned(part, gemv_table):
+    """gemv_plan (what launch_gemv launches from) answers every row of the launch matrix as the launch ladder it replaced did.
+    Family, weight form, packed flag, epilogue, NTILE, WAVES, UNROLL, NB, RR, NCH, NORM, grid x / y and block of every traced row are
+    the traced kernel's name and dispatch.  The trace does not show the rest; those fields were CHECKED BY HAND against the ladder's
+    formulas: dynamic LDS bytes and rows_per_wg of the long-K form ((cdiv(K, 512) + 7) / 8 * 8192; clamp(cdiv(N, 2 CUs), 1, 8)), per_wg
+    and skew of the loop form (cdiv(n_out, 2 CUs); key 28 when >= 256 and n_out == per_wg * 2 CUs), n5 of the split form
+    (K / 512 = 5 n5 + 2 (ksplit - n5)), xskew (0 outside the experiments build).  The "experiments" rows are by hand throughout."""
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the table is recorded for 256 compute units")
+    l = _lib.lib()
+    twin = bool(l.omchat_has_experiments())
+    if part == "experiments" and not twin:
+        pytest.skip("rows of the -DOMCHAT_EXPERIMENTS=1 build")
+    out = (C.c_int * 20)()
+    assert gemv_table["fields"][:4] == ["family", "wf", "wpack", "epi"] and len(gemv_table["fields"]) == 20
+    assert len(gemv_table[part]) >= {"traced": 1000, "unreached": 9, "experiments": 10}[part]
+    wrong = []
+    for args, tune, want in gemv_table[part]:
+        if twin and part != "experiments" and _product_only(tune, want):
+            continue
+
+        def plan():
+            if l.omchat_op_gemv_plan(*args, 256, out):
+                return l.omchat_last_error().decode()
+            return list(out)
+        got = _with_tuning(l, tune, plan)
+        if got != want:
+            wrong.append((args, tune, want, got))
+    assert not wrong, f"{len(wrong)} rows differ, the first: {wrong[:3]}"
+
+
+def test_gemv_split_k_is_pinned(gemv_table):
+    """the K slices decode_body passes for o_proj and down_proj (gemv_split_k): b in {1, 2, 16, 32}, packed replica or not, at the TP = 1
+    and TP = 8 widths, with key 34 at its default and at 0 -- the values the step computed inline before the function existed"""
+    l = _lib.lib()
+    wrong = []
+    for b, K, H, packed, down, shard, want in gemv_table["split_k"]:
+        got = _with_tuning(l, [(34, shard)], lambda: l.omchat_op_gemv_split_k(b, K, H, packed, down))
+        if got != want:
+            wrong.append((b, K, H, packed, down, shard, want, got))
+    assert len(gemv_table["split_k"]) == 64
+    assert not wrong, wrong
+
+
