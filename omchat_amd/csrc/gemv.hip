@@ -1583,9 +1583,15 @@ __global__ __launch_bounds__(256) void gemv_rows_norm_dyn_mx4_kernel(GemvP p) { 
 // so how the chunks are grouped into passes changes no bit.  CP divides 8, so the passes cover exactly the 16-bit form's ceil8(nch)
 // chunks: those in [nch, ceil8(nch)) read weights 0..7 against zeros of x (the clamped address) and there is none beyond -- with
 // K % 4096 == 0 no w * 0 term exists, and a row with an infinite weight among its first eight stays infinite at every CP.
-// 16-bit, e4m3 and MXFP4 rows: 8 chunks (24 KB per wave in the three buffers).  bf16x12: 4 chunks -- 68 VGPRs, where 8 take 136 and
-// leave one workgroup per CU.
-template <typename T, int F8, int CP = 8, int G = 2>
+// 16-bit, e4m3 and MXFP4 rows: 8 chunks.  bf16x12: 4 chunks, where 8 leave one workgroup per CU.
+// NB = 0 is the three-buffer loop of rounds 3-4, whose rotation is in the source only: its loads stand under conditions, the compiler's wait in
+// front of a pass's dot products is the smallest count over the paths that meet there, and the tail path has none behind the buffer in use --
+// the 16-bit instance waits vmcnt(7) .. vmcnt(0) behind the loads it has just issued and computes with nothing in flight; x is staged as a
+// chain of load, vmcnt(0), LDS write per vector, whose first wait drains the three buffers.  NB > 0 is the counted pipeline over NB buffers
+// (below): the coded instance runs NB = 3 and waits vmcnt(22) / (20) / (18) / (16) in front of its four chunks -- two whole passes stay in
+// flight -- at 93 VGPRs, no scratch, 5 waves per SIMD by registers, both workgroups of a CU resident.  The 16-bit instance did not gain from
+// it in the role bench (8 x 2, 4 x 3, 4 x 4: LOG.md 2026-10-20) and keeps NB = 0 with the e4m3 and MXFP4 ones, which were not timed.
+template <typename T, int F8, int CP = 8, int G = 2, int NB = 0, int XB = 6>
 __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_per_wg) {
   static_assert(8 % CP == 0 && CP % G == 0, "whole passes cover ceil8(nch) chunks, whole decode groups a pass");
   extern __shared__ __attribute__((aligned(16))) char xs_raw[];
@@ -1629,7 +1635,91 @@ __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_pe
         acc = rw_dotw<T, F8>(w[c], xr, acc);
       }
     }
+    // the counted form: the pass's sum is complete HERE (the compiler otherwise sinks the dot products of all passes of an iteration to its
+    // end and keeps their decoded weights and x rows live: 199 VGPRs)
+    if constexpr (NB > 0) asm volatile("" : "+v"(acc));
   };
+  if constexpr (NB > 0) {
+    // ---- the counted pipeline.  The vector-memory counter is in order and the compiler's wait in front of a use is the SMALLEST number of
+    // younger loads over all paths that reach it: one path without loads behind the use's operand and the wait is vmcnt(0) for every path.
+    // So (a) x goes out FIRST, all of a thread's vectors (XB per batch, the condition in the address), and is written to LDS behind one wait that
+    // leaves the weight passes in flight; (b) every load_w of the repeated part is unconditional; (c) the passes that finish a row are
+    // straight-line cases per number of remaining passes that meet only at the reduction, with nothing in flight.
+    const int nx = npass8 * 8 * 64, bd = (int)blockDim.x;
+    const rw_u32x4 z = {0u, 0u, 0u, 0u};
+    // vector j of a batch; one beyond the staged x repeats the thread's own first vector (nx >= 1024 > threadIdx.x: the same value to the same
+    // address again), so that neither a load nor a write stands under a branch
+    auto xi = [&](int base, int j) { const int i = base + (int)threadIdx.x + j * bd; return i < nx ? i : (int)threadIdx.x; };
+    rw_u32x4 xv[XB];
+#pragma unroll
+    for (int j = 0; j < XB; ++j) {
+      xv[j] = *reinterpret_cast<const rw_u32x4*>((const T*)p.X + (xi(0, j) * 8 < p.K ? xi(0, j) * 8 : 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    wreg_t w[NB][CP];
+    load_w(w[0], 0);
+    if constexpr (F8 == WF_X12) x12_row_load(xst, p, (size_t)row, lane);
+    __builtin_amdgcn_sched_barrier(0);          // (the row's top and patch count stay right behind the first pass: scheduled last, their wait drains every buffer)
+#pragma unroll
+    for (int b = 1; b < NB; ++b) {            // K > 4096: at least 16 / CP passes, loaded without a condition
+      if (b < 16 / CP || b < npass) load_w(w[b], b);
+    }
+    const float e_bias_raw = tof(((const T*)(p.bias ? p.bias : p.X))[p.bias ? row : 0]);
+    const float e_res_raw = tof(((const T*)(p.resid ? p.resid : p.X))[p.resid ? row : 0]);
+    const float e_bias = p.bias ? e_bias_raw : 0.f, e_res = p.resid ? e_res_raw : 0.f;
+    float e_scale = 1.f;
+    if constexpr (F8 == WF_E4M3) e_scale = p.w_scale[row];
+#pragma unroll
+    for (int j = 0; j < XB; ++j) {
+      *reinterpret_cast<rw_u32x4*>(xs + xi(0, j) * 8) = xi(0, j) * 8 < p.K ? xv[j] : z;
+    }
+    // (a workgroup of fewer than nx / XB threads -- few rows per workgroup, or K beyond XB * 512 * rows_per_wg: the rest in further batches)
+    for (int base = XB * bd; base < nx; base += XB * bd) {
+#pragma unroll
+      for (int j = 0; j < XB; ++j) {
+        xv[j] = *reinterpret_cast<const rw_u32x4*>((const T*)p.X + (xi(base, j) * 8 < p.K ? xi(base, j) * 8 : 0));
+      }
+#pragma unroll
+      for (int j = 0; j < XB; ++j) {
+        *reinterpret_cast<rw_u32x4*>(xs + xi(base, j) * 8) = xi(base, j) * 8 < p.K ? xv[j] : z;
+      }
+    }
+    __syncthreads();
+    if constexpr (F8 == WF_X12) x12_row_finish(xst);
+    // w[b] holds pass ps + b; NB - 1 whole passes stay in flight under every dots() of the repeated part
+    auto last = [&](int ps, auto rem) {         // the last rem passes of the row (1 .. 2 NB - 1), the first min(rem, NB) of them loaded or on their way
+#pragma unroll
+      for (int b = 0; b < decltype(rem)::value; ++b) {
+        dots(w[b % NB], ps + b);
+        if (b + NB < decltype(rem)::value) load_w(w[b % NB], ps + b + NB);
+      }
+    };
+    int ps = 0;
+#pragma unroll 1
+    for (; ps + 2 * NB <= npass; ps += NB) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) { dots(w[b], ps + b); load_w(w[b], ps + b + NB); }
+    }
+    switch (npass - ps) {
+      case 1: last(ps, std::integral_constant<int, 1>()); break;
+      case 2: last(ps, std::integral_constant<int, 2>()); break;
+      case 3: last(ps, std::integral_constant<int, 3 < 2 * NB ? 3 : 1>()); break;
+      case 4: last(ps, std::integral_constant<int, 4 < 2 * NB ? 4 : 1>()); break;
+      case 5: last(ps, std::integral_constant<int, 5 < 2 * NB ? 5 : 1>()); break;
+      case 6: last(ps, std::integral_constant<int, 6 < 2 * NB ? 6 : 1>()); break;
+      default: last(ps, std::integral_constant<int, 7 < 2 * NB ? 7 : 1>()); break;
+    }
+    float a = acc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if constexpr (F8 == WF_E4M3) a *= e_scale;
+    if (lane == 0 && valid) {
+      const float y = rnd<T>(a + e_bias);
+      ((T*)p.Y)[n] = fromf<T>(e_res + y);
+    }
+    OM_DBG_MAX(7, (blockIdx.x & 7) == 0);
+    return;
+  }
   wreg_t wa[CP], wb[CP], wc[CP];
   load_w(wa, 0);
   if constexpr (F8 == WF_X12) x12_row_load(xst, p, (size_t)row, lane);      // bf16x12: the row's top and patches right behind the first pass, which needs them
@@ -1650,7 +1740,8 @@ __device__ __forceinline__ void gemv_rows_longk_body(const GemvP& p, int rows_pe
   }
   __syncthreads();
   if constexpr (F8 == WF_X12) x12_row_finish(xst);
-  // three register buffers: the weights of passes ps + 1 and ps + 2 are in flight under the dot products of pass ps
+  // three register buffers.  In this source the weights of passes ps + 1 and ps + 2 are in flight under the dot products of pass ps; in the
+  // machine code the conditions around the loads make every wait a vmcnt(0) behind the newest load (see the head of this body)
   for (int ps = 0; ps < npass; ps += 3) {
     if (ps > 0 && ps + 2 < npass) load_w(wc, ps + 2);
     dots(wa, ps);
@@ -1679,7 +1770,7 @@ __global__ __launch_bounds__(512) void gemv_rows_longk_kernel(GemvP p, int rows_
 template <typename T>
 __global__ __launch_bounds__(512) void gemv_rows_longk_mx4_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_MX4>(p, rows_per_wg); }
 template <typename T>
-__global__ __launch_bounds__(512) void gemv_rows_longk_x12_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_X12, 4>(p, rows_per_wg); }
+__global__ __launch_bounds__(512) void gemv_rows_longk_x12_kernel(GemvP p, int rows_per_wg) { gemv_rows_longk_body<T, WF_X12, 4, 2, 3>(p, rows_per_wg); }
 
 #if OMCHAT_EXPERIMENTS
 // The same rows WITHOUT the LDS stage (round 5, tuning key 39): a wave streams one row and uses every x element once, so the LDS copy only saves L2
