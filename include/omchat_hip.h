@@ -249,6 +249,35 @@ int omchat_fsm_states(omchat_ctx* ctx, int b, int32_t* out, void* stream);
  * (max_batch rows of tile partials) and the copy are context-owned and counted in omchat_device_bytes.  Deterministic: the same logits
  * give the same scores, bit for bit, eager or in a graph. */
 int omchat_set_guidance(omchat_ctx* ctx, int b, float scale, void* stream);
+/* ---- layer-contrastive decoding (generate(dola_layers=)) --------------------------------------------------------------- */
+/* omchat_set_dola: from now on every pick of rows 0..b-1 of this context contrasts the final layer's next-token distribution with an early
+ * layer's from the same forward pass (Chuang et al., "DoLa: Decoding by Contrasting Layers"; HF 4.4x's _dola_decoding).  layers: k host
+ * indices into HF's hidden_states tuple -- 0 the embedding row of the fed token, i the residual stream behind decoder layer i, all below
+ * num_hidden_layers --, 1 <= k <= OMCHAT_DOLA_MAX_LAYERS.  omchat_prefill (with logits_last) and omchat_decode_step then also keep each
+ * sequence's last-position hidden row at those layers, push all (k + 1) b rows -- the final row through the final RMSNorm, the candidate rows
+ * as they are, or normalised too with norm != 0 ("logit lens", this project's extension) -- through the 16-bit lm_head in one pass, and
+ * leave the raw fp32 logits [(k + 1) b][V] in a context-owned buffer: rows [0, b) the final rows, row (1 + j) b + r candidate j of sequence
+ * r.  The logits handed back to the caller stay the b final rows.  Every pick (omchat_greedy, omchat_sample, the step's own) runs on
+ *   out[v] = lm[v] - lp[v] where lm[v] >= max lm + log(relative_top), -inf elsewhere;  lm = log_softmax(final), lp = log_softmax(candidate)
+ * of the candidate with the largest Jensen-Shannon divergence from the final row (the first on ties; k == 1: that one), written to the
+ * context's copy in front of the bans of omchat_set_constraints and the automaton of omchat_fsm_begin.  Every row picks its own layer (HF
+ * averages the divergence over the batch; at b = 1 the two agree).  While it is on, omchat_greedy and omchat_sample read the context's rows of
+ * the last prefill or step -- their `logits` argument must be what that call returned -- and a pick, a step or a rewind takes exactly b rows.
+ * The log-prob record's raw number is the final row's raw log-softmax, the processed one what the pick saw.  One int32 per row and pick --
+ * the HF index of the picked layer -- is recorded on the device (omchat_dola_read); omchat_kv_rewind takes its lines back with the slots.
+ * Refused here, before anything changes: a tensor-parallel context, an active beam search, guidance, a sampled group, the fp8 or MXFP4
+ * decode replicas (the head pass is 16-bit), (k + 1) b > min(max_batch, 32), an index outside [0, num_hidden_layers), a relative_top outside
+ * (0, 1].  Refused while it is on, before anything is enqueued: omchat_beam_begin, omchat_set_guidance, omchat_group_begin,
+ * omchat_prefill_suffixes, omchat_decode_verify, the masked steps, omchat_prefill_left, omchat_prefill_extend, the two replica switches.
+ * b = 0 switches it off: no launch, no graph node remains.  Sticky; every parameter is a kernel argument of the captured decode graphs, which
+ * a change drops.  Deterministic: the same logits give the same scores and the same layer, bit for bit, eager or in a graph. */
+#define OMCHAT_DOLA_MAX_LAYERS 16
+int omchat_set_dola(omchat_ctx* ctx, int b, const int32_t* layers, int k, float relative_top, int norm, void* stream);
+/* the record: out host int32 [rows][steps], line t of row r = the HF index of the layer pick t of row r contrasted with, -1 where no such
+ * pick was made (yet).  Synchronises the device. */
+int omchat_dola_read(omchat_ctx* ctx, int32_t* out, int rows, int steps);
+/* test hook: the raw rows of the last prefill or step, host fp32 [(k + 1) b][V].  Synchronises the device. */
+int omchat_dola_rows(omchat_ctx* ctx, float* out);
 /* ---- per-token log-probabilities of the picked ids (generate(output_logprobs=True)) ---------------------------------- */
 /* omchat_set_logprobs: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both
  * masked steps, the captured decode graph -- also records two fp32 numbers on the device, without a host sync: raw = log_softmax(logits)[id]
@@ -837,6 +866,14 @@ int omchat_op_fsm(int n_states, const int32_t* off, const int32_t* tok, const in
  * synchronise. */
 size_t omchat_op_guidance_ws(int b, int V);
 int omchat_op_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, void* stream);
+
+/* context-free stage of omchat_set_dola (test hook): logits device fp32 [(k + 1) b][ld] in the row order given there, V <= ld ids per row (any
+ * V; 16-byte accesses when ld % 4 == 0 and the base is aligned, scalar ones otherwise); out device fp32 [b][ld_out], ld_out >= V; picked
+ * device int32 [b] (or NULL): the chosen candidate's POSITION 0..k-1; ws device memory of ws_bytes >= omchat_op_dola_ws(b, k, V) bytes,
+ * 8-byte aligned.  Enqueues three launches (two at k == 1), does not synchronise. */
+size_t omchat_op_dola_ws(int b, int k, int V);
+int omchat_op_dola(const float* logits, int ld, int V, int b, int k, float relative_top, float* out, int ld_out, int32_t* picked, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* context-free sampler over logits fp32 [b, V] with the parameters of omchat_set_sampling; every row at step `step`.  thr_out (device uint32 [b]
  * or NULL, test hook): the kept set's threshold -- the order-preserving key of the smallest kept processed logit (0 = everything kept). */

@@ -62,6 +62,11 @@ _SIGS = {
     "omchat_set_guidance": (_i, [_vp, _i, _f, _vp]),
     "omchat_op_guidance_ws": (_sz, [_i, _i]),
     "omchat_op_guidance": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "omchat_set_dola": (_i, [_vp, _i, _vp, _i, _f, _i, _vp]),
+    "omchat_dola_read": (_i, [_vp, _vp, _i, _i]),
+    "omchat_dola_rows": (_i, [_vp, _vp]),
+    "omchat_op_dola_ws": (_sz, [_i, _i, _i]),
+    "omchat_op_dola": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _sz, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),
     "omchat_set_logprobs": (_i, [_vp, _i, _i, _vp]),

@@ -430,6 +430,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_CHECK(!ctx->pick.logprobs_on(), "beam search: logprobs are on (omchat_set_logprobs with b = 0 first); a beam search reports sequences_scores");
   OM_CHECK(!ctx->pick.fsm_on(), "beam search: a token FSM is on (omchat_fsm_begin with b = 0 first); each beam row would need its parent's state");
   OM_CHECK(!ctx->pick.guidance_on(), "beam search: guidance is on (omchat_set_guidance with b = 0 first); each beam row would need its twin");
+  OM_CHECK(!ctx->pick.dola_on(), "beam search: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); each beam row would need its candidate rows");
   OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
   OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
   const int KB = std::max(2, 1 + n_eos) * N;
@@ -488,6 +489,7 @@ extern "C" int omchat_group_begin(omchat_ctx* ctx, int b, int N, int prompt_len,
   OM_CHECK(b >= 1 && N >= 1, "sampled group: b >= 1 prompts, N >= 1 rows each");
   OM_CHECK(!ctx->beam.on(), "sampled group: a beam search is active");
   OM_CHECK(!ctx->pick.guidance_on(), "sampled group: guidance is on (omchat_set_guidance with b = 0 first); each sibling row would need its twin");
+  OM_CHECK(!ctx->pick.dola_on(), "sampled group: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); each sibling row would need its candidate rows");
   OM_CHECK(b * N <= c.max_batch, "sampled group: b * N exceeds max_batch");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "sampled group: a left-padded or masked-decode batch (pad equal or use b = 1)");
   OM_CHECK(prompt_len >= 1 && prompt_len < c.max_seq, "sampled group: prompt_len outside [1, max_seq)");

@@ -675,6 +675,7 @@ extern "C" int omchat_op_top_logprobs(const float* logits, int b, int V, int ld,
   return rc;
 }
 
+static_assert(DOLA_MAX_LAYERS == OMCHAT_DOLA_MAX_LAYERS, "layer-contrastive decoding cap: kernels.h and omchat_hip.h");
 static_assert(LP_MAX_TOP == OMCHAT_LP_MAX_TOP && LP_MAX_SCORED == OMCHAT_LP_MAX_SCORED, "log-prob extras caps: kernels.h and omchat_hip.h");
 static_assert(CON_NGRAM_MAX == OMCHAT_CON_MAX_NGRAM && CON_EOS_MAX == OMCHAT_CON_MAX_EOS && CON_SUPPRESS_MAX == OMCHAT_CON_MAX_SUPPRESS &&
               CON_BAD_WORDS_MAX == OMCHAT_CON_MAX_BAD_WORDS && CON_BAD_WORD_IDS_MAX == OMCHAT_CON_MAX_BAD_WORD_IDS, "constraint caps: kernels.h and omchat_hip.h");
@@ -791,6 +792,16 @@ extern "C" size_t omchat_op_guidance_ws(int b, int V) { return b >= 1 && V >= 1 
 
 extern "C" int omchat_op_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, void* stream) {
   return launch_guidance(logits, ld, b, V, scale, ws, out, ld_out, S(stream));
+}
+
+extern "C" size_t omchat_op_dola_ws(int b, int k, int V) { return b >= 1 && k >= 1 && V >= 1 ? dola_ws_bytes(b, k, V) : 0; }
+
+extern "C" int omchat_op_dola(const float* logits, int ld, int V, int b, int k, float relative_top, float* out, int ld_out, int32_t* picked, void* ws,
+                              size_t ws_bytes, void* stream) {
+  DolaArgs a;
+  a.logits = logits; a.ld = ld; a.V = V; a.b = b; a.k = k; a.relative_top = relative_top;
+  a.out = out; a.ld_out = ld_out; a.picked = picked; a.ws = ws; a.ws_bytes = ws_bytes;
+  return launch_dola(a, S(stream));
 }
 
 extern "C" size_t omchat_beam_state_words(int b, int N, int max_new) { return beam_state_words(b, N, max_new); }

@@ -4,6 +4,7 @@
 #include "kernels.h"
 #include "../../include/omchat_hip.h"
 #include <rccl/rccl.h>
+#include <algorithm>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -28,7 +29,7 @@ struct Grown {
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-// The token pick of a step (pick.hip): guidance stage, ban stage, automaton stage, argmax or sampler, record stage -- with everything the
+// The token pick of a step (pick.hip): guidance or layer-contrast stage, ban stage, automaton stage, argmax or sampler, record stage -- with everything the
 // stages keep between picks.
 struct PickState {
   void* arg_scratch = nullptr;      // partials of the two-stage argmax
@@ -114,13 +115,35 @@ struct PickState {
   struct Guidance { bool on = false; int b = 0; float scale = 1.f; };
   Guidance gd;
   void* gd_ws = nullptr;
+  // layer-contrastive decoding (omchat_set_dola; dola.hip): while it is on for b rows a prefill or step leaves (k + 1) b raw rows in
+  // dola_logits -- the final rows, then candidate j's at (1 + j) b + r -- from the hidden rows dola_hid [(k + 1) b][H] it kept at the layers
+  // of the list (device copy dola_layers, for the record); the stage writes the b rows of contrasted scores to con_logits.  dola_rec int32
+  // [dola_cap][max_batch] with a device counter per row: the HF index of every pick's layer.  dola_fresh: dola_logits holds the rows of the
+  // last prefill or step (a pick without them is refused)
+  struct Dola {
+    bool on = false, norm = false; int b = 0, k = 0; float relative_top = 0.1f; int layers[DOLA_MAX_LAYERS] = {};
+    bool operator==(const Dola& o) const {
+      return on == o.on && norm == o.norm && b == o.b && k == o.k && relative_top == o.relative_top && std::equal(layers, layers + DOLA_MAX_LAYERS, o.layers);
+    }
+    int rows() const { return (k + 1) * b; }
+    int slot(int hf_index) const { for (int j = 0; j < k; ++j) if (layers[j] == hf_index) return j; return -1; }      // position in the list, or -1
+  };
+  Dola dola;
+  float* dola_logits = nullptr;
+  void* dola_hid = nullptr;
+  void* dola_ws = nullptr; size_t dola_ws_cap = 0;
+  int32_t* dola_layers = nullptr;
+  int* dola_cnt = nullptr;
+  Grown dola_rec; int dola_cap = 0;
+  bool dola_fresh = false;
+  bool dola_on() const { return dola.on; }
   bool guidance_on() const { return gd.on; }
   int pick_rows(int rows) const { return gd.on ? rows / 2 : rows; }      // the rows that pick, of the rows a step runs
   bool sampling_on() const { return smp.on; }
   bool constraints_on() const { return con.on; }
   bool logprobs_on() const { return lp.on; }
   bool fsm_on() const { return fsm.on; }
-  void release() { con_hist.release(); lp_rec.release(); lp_xrec.release(); fsm_mem.release(); fsm_trail.release(); }
+  void release() { con_hist.release(); lp_rec.release(); lp_xrec.release(); fsm_mem.release(); fsm_trail.release(); dola_rec.release(); }
 };
 
 // beam search (omchat_beam_begin; beam.hip): parameters of the current search, its step counter, and device buffers grown on demand
@@ -212,7 +235,7 @@ struct omchat_ctx {
   // (shared-prompt mode of a sampled group: N, P and the workspace are kernel arguments too, so the graph remembers them and is captured again
   // when they change; its cap_len is the suffix bucket the eager step would take, so both issue the same launches)
   struct DecodeGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int cap_len = 0, grp_N = 0, grp_P = 0; const void* grp_ws = nullptr; };
-  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0), the weights by the step's format; + (1 << 20) in the shared-prompt mode
+  std::unordered_map<int, DecodeGraph> graphs;      // key = b * 8 + (MXFP4 weights ? 4 : 0) + (fp8 weights ? 2 : 0) + (fp8 KV cache ? 1 : 0), the weights by the step's format; + (1 << 19) with layer-contrastive decoding on, + (1 << 20) in the shared-prompt mode, + the bf16x12 roles << 21 (b <= 32: the fields do not overlap)
   bool graph_on = false;
   hipStream_t graph_stream = nullptr;
   hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;
@@ -463,5 +486,9 @@ void pick_verify_committed(omchat_ctx* ctx, int n_picks);      // the acceptance
 int pick_feed(omchat_ctx* ctx, const int32_t* fed, int b, hipStream_t s);      // a step that picks nothing still feeds the history
 const char* pick_rewind_refusal(omchat_ctx* ctx, int b, int n);      // why the pick state cannot go back n steps, or NULL
 int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s);
-// while guidance is on for b rows a step, a pick or a rewind takes exactly 2b rows: why `rows` will not do, or NULL (NULL when it is off)
+// while guidance is on for b rows a step, a pick or a rewind takes exactly 2b rows, while layer-contrastive decoding is on exactly its b: why
+// `rows` will not do, or NULL (NULL when both are off)
 const char* pick_rows_refusal(omchat_ctx* ctx, int rows);
+// layer-contrastive decoding (omchat_set_dola): why this context's state does not go with it, or NULL -- asked by the setter and again by
+// every prefill and step while it is on (the replica switches may have come later)
+const char* dola_state_refusal(const omchat_ctx* ctx);

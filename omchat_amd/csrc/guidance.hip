@@ -8,41 +8,9 @@
 // The -inf rule (HF's formula gives NaN there): where the conditional or the twin logit is -inf the output is -inf -- an id that one of the two
 // contexts excludes stays excluded.  -inf entries add nothing to a row's sum, and a row of nothing but -inf gives nothing but -inf.
 // tests/guidance_ref.py is the float64 restatement, pinned to HF's processor.
-#include "kernels.h"
-#include <math.h>
+#include "logits_tile.h"
 
 namespace {
-
-constexpr int GD_TILE = 2048;      // logits per workgroup: 256 threads x two 16-byte pieces
-
-// all 256 threads get the same value; a fixed tree (xor shuffles inside a wave, then the four waves in order)
-template <bool MAX>
-__device__ float gd_block_reduce(float v, float* sh) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float o = __shfl_xor(v, m);
-    v = MAX ? fmaxf(v, o) : v + o;
-  }
-  __syncthreads();      // (sh may still be read from the reduction before)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return MAX ? fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) : ((sh[0] + sh[1]) + (sh[2] + sh[3]));
-}
-
-// the thread's eight logits of its tile: pieces e = 0, 1 at i = t0 + (e * 256 + t) * 4; ids at or beyond V read as -inf
-__device__ void gd_load(const float* row, int t0, int V, bool vec, float x[8]) {
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int i = t0 + (e * 256 + (int)threadIdx.x) * 4;
-    if (vec && i + 4 <= V) {
-      const float4 q = *(const float4*)(row + i);
-      x[e * 4] = q.x; x[e * 4 + 1] = q.y; x[e * 4 + 2] = q.z; x[e * 4 + 3] = q.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) x[e * 4 + k] = i + k < V ? row[i + k] : -INFINITY;
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void guidance_partial_kernel(const float* logits, int ld, int V, int nt, bool vec, float2* ws) {
   __shared__ float sh[4];
@@ -60,19 +28,6 @@ __global__ __launch_bounds__(256) void guidance_partial_kernel(const float* logi
   }
   s = gd_block_reduce<false>(s, sh);
   if (threadIdx.x == 0) ws[(size_t)row * nt + tile] = make_float2(m, s);
-}
-
-// log-sum-exp of a row from its nt tile partials (-inf for a row of nothing but -inf)
-__device__ float gd_fold(const float2* p, int nt, float* sh) {
-  const int t = threadIdx.x;
-  float m = -INFINITY;
-  for (int i = t; i < nt; i += 256) m = fmaxf(m, p[i].x);
-  m = gd_block_reduce<true>(m, sh);
-  float s = 0.f;
-  if (m > -INFINITY)
-    for (int i = t; i < nt; i += 256) s += p[i].y * expf(p[i].x - m);
-  s = gd_block_reduce<false>(s, sh);
-  return m > -INFINITY ? m + logf(s) : -INFINITY;
 }
 
 __device__ __forceinline__ float gd_mix(float xc, float xu, float lse_c, float lse_u, float scale) {

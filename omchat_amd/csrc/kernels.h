@@ -592,6 +592,22 @@ size_t guidance_ws_bytes(int b, int V);
 int launch_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, hipStream_t s);
 // behind the pick: next_tokens[b + r] = next_tokens[r]; with pos / len (both or neither) pos += 1, len += 1 for all 2b rows
 int launch_guidance_twin(int32_t* next_tokens, int b, int* pos, int* len, hipStream_t s);
+// layer-contrastive decoding (dola.hip; tests/dola_ref.py restates it): logits fp32 [(k + 1) * b][ld], rows [0, b) the
+// final layer's, row (1 + j) * b + r candidate j of sequence r; out [b][ld_out] = the relative-top-filtered contrast of each sequence's final
+// row with the candidate of the largest Jensen-Shannon divergence from it (the lowest j on ties; k == 1: no divergence is computed).
+// picked (or NULL): that candidate's position per sequence.  rec (or NULL): layers[position] is appended to line cnt[r] of the int32 record
+// [cap][rec_ld] and cnt[r] += 1.  ws: dola_ws_bytes(b, k, V) bytes, written and read by the launches of one call.  Deterministic.
+constexpr int DOLA_MAX_LAYERS = 16;
+struct DolaArgs {
+  const float* logits = nullptr; int ld = 0, V = 0, b = 0, k = 0;
+  float relative_top = 0.1f;
+  float* out = nullptr; int ld_out = 0;
+  int32_t* picked = nullptr;
+  void* ws = nullptr; size_t ws_bytes = 0;
+  const int32_t* layers = nullptr; int32_t* rec = nullptr; int* cnt = nullptr; int cap = 0, rec_ld = 0;
+};
+size_t dola_ws_bytes(int b, int k, int V);
+int launch_dola(const DolaArgs& a, hipStream_t s);
 // beam search (beam.hip; tests/beam_ref.py restates it).  The vocabulary is cut into beam_slices(V, tp) equal slices
 // of at most BEAM_SLICE_CAP ids, the same at every TP degree; a rank owns ns / tp whole slices.  Exchange table: [rows][ns][4 + 2K] fp32.
 constexpr int BEAM_KMAX = 32;            // candidates kept per step and prompt: max(2, 1 + n_eos) * N

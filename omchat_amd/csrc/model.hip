@@ -951,6 +951,24 @@ static int lm_head_rows(omchat_ctx* ctx, const void* hidden, int n, float* logit
   return 0;
 }
 
+// Layer-contrastive decoding (omchat_set_dola): the head pass of a prefill or step.  dola_hid holds the candidate rows at
+// (1 + j) * b + r; xf = the b last-position rows of the residual stream behind the last layer.  They go to rows [0, b) and through the final
+// RMSNorm (with `norm` the candidate rows too: the same launch over more rows), then all (k + 1) b rows through the 16-bit head in one pass
+// into the context's rows; the caller's logits (or NULL) get the b final rows.
+static int dola_head(omchat_ctx* ctx, const void* xf, float* logits, hipStream_t s) {
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  const int H = c.t_hidden, b = P.dola.b, n = P.dola.rows();
+  OM_HIP(hipMemcpyAsync(P.dola_hid, xf, (size_t)b * H * 2, hipMemcpyDeviceToDevice, s));
+  TRY(launch_rmsnorm(ctx->dt, P.dola_hid, H, ctx->t_norm, P.dola_hid, H, P.dola.norm ? n : b, H, c.t_eps, s));
+  TRY(lm_head_rows(ctx, P.dola_hid, n, P.dola_logits, s, ctx->lm_w(OMCHAT_WFMT_16)));
+  if (logits) OM_HIP(hipMemcpyAsync(logits, P.dola_logits, (size_t)b * c.t_vocab * 4, hipMemcpyDeviceToDevice, s));
+  P.dola_fresh = true;
+  return 0;
+}
+// ... and the rows a candidate layer keeps: dst = row block (1 + j) of dola_hid
+static void* dola_slot(omchat_ctx* ctx, int j) { return (char*)ctx->pick.dola_hid + (size_t)(1 + j) * ctx->pick.dola.b * ctx->c.t_hidden * 2; }
+
 // (Re)build one replica of the decode-streamed weights: the layers * 4 + 1 entries of its table, by proj_shape.  The first build takes every
 // buffer or none and commits the table only then (a half-built table must never reach a launch); a rebuild after omchat_load_tensor fills
 // the same buffers in place (same device pointers: a captured graph stays valid).  Synchronous, never inside a graph capture.
@@ -1061,6 +1079,7 @@ extern "C" int omchat_enable_fp8_decode(omchat_ctx* ctx, int on) {
   OM_CHECK(ctx->c.t_layers > 0, "context has no decoder");
   if (!on) { ctx->fp8_decode = false; return 0; }
   OM_CHECK(!ctx->mxfp4_mode, "MXFP4 decode is on: one weight format per step (omchat_enable_mxfp4_decode(ctx, 0) first)");
+  OM_CHECK(!on || !ctx->pick.dola_on(), "fp8 decode: layer-contrastive decoding is on, and its head pass is 16-bit only (omchat_set_dola with b = 0 first)");
   TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));
   ctx->fp8_decode = true;
   return 0;
@@ -1073,6 +1092,7 @@ extern "C" int omchat_enable_mxfp4_decode(omchat_ctx* ctx, int mode) {
   OM_CHECK(mode >= 0 && mode <= 2, "mode: 0 = off, 1 = batch-1 steps, 2 = steps of up to 32 rows as well");
   if (!mode) { ctx->mxfp4_mode = 0; return 0; }
   OM_CHECK(!ctx->fp8_decode, "fp8 decode is on: one weight format per step (omchat_enable_fp8_decode(ctx, 0) first)");
+  OM_CHECK(!mode || !ctx->pick.dola_on(), "MXFP4 decode: layer-contrastive decoding is on, and its head pass is 16-bit only (omchat_set_dola with b = 0 first)");
   OM_CHECK(ctx->tp_size == 1, "MXFP4 decode under tensor parallelism is not implemented");
   if (mode == 2) {
     const omchat_config& c = ctx->c;
@@ -1185,6 +1205,15 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   OM_CHECK((int64_t)b * S <= c.max_prefill_rows, "b * S exceeds max_prefill_rows");
   OM_CHECK(omchat_weights_missing(ctx) == 0, std::string(omchat_last_error()));
   for (int i = 0; i < b; ++i) OM_CHECK(lengths[i] >= 1 && lengths[i] <= S, "lengths must be in [1, S]");
+  // layer-contrastive decoding: the first generated id comes from this prefill, so it keeps the candidate layers' last rows too
+  const PickState::Dola& D = ctx->pick.dola;
+  const bool dola = D.on && logits_last;
+  if (dola) {
+    OM_CHECK(!left, "layer-contrastive decoding is on: a left-padded batch decodes with the masked step, which has no candidate rows (omchat_set_dola with b = 0 first)");
+    OM_CHECK(keep == 0 && !sfx, "layer-contrastive decoding is on: prefill_extend and the suffix pass are not implemented with it (omchat_set_dola with b = 0 first)");
+    OM_CHECK(b == D.b, "layer-contrastive decoding is on: a prefill takes exactly the b rows omchat_set_dola was given");
+    if (const char* why = dola_state_refusal(ctx)) OM_CHECK(false, why);
+  }
   hipStream_t s = (hipStream_t)stream;
   if (ctx->fp8_prefill) TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));      // weights were reloaded: re-quantise in place
   const int H = c.t_hidden, It = c.t_mlp, rows = b * S, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
@@ -1212,6 +1241,15 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   void* x = ctx->tw_x;
   void* y = ctx->tw_x2;
   OM_HIP(hipMemcpyAsync(x, embeds, (size_t)rows * H * 2, hipMemcpyDeviceToDevice, s));
+  // HF's hidden_states index h (0 = the embeddings, h = behind decoder layer h) is a candidate: keep the rows' last positions
+  auto dola_keep = [&](int h) -> int {
+    const int j = dola ? D.slot(h) : -1;
+    return j < 0 ? 0 : launch_gather_rows(ctx->dt, ctx->d_idx, x, nullptr, dola_slot(ctx, j), b, H, s);
+  };
+  if (dola) {
+    hipLaunchKernelGGL(last_row_index_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_len, S, b, ctx->d_idx, keep);
+    TRY(dola_keep(0));
+  }
   // sequence-parallel norms (gemm_sp): not with the fp8 prefill (its norm writes e4m3 + scales) nor with fp32 partial sums (tuning key 29)
   const bool sp = g_tp_sp && ctx->tp_size > 1 && !g_tp_f32 && !(ctx->fp8_prefill && ctx->built(OMCHAT_WFMT_E4M3));
   for (int i = 0; i < c.t_layers; ++i) {
@@ -1285,10 +1323,14 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
       TRY(gemm_allreduce(ctx, ctx->tw_act, It, L.wd, It, y, H, rows, It, nullptr, nullptr, x, EPI_RESID, s));
       std::swap(x, y);
     }
+    TRY(dola_keep(i + 1));
   }
   TRY(sp_drain(ctx, s));
   if (hidden_out) TRY(launch_rmsnorm(ctx->dt, x, H, ctx->t_norm, hidden_out, H, rows, H, c.t_eps, s));
-  if (logits_last) {
+  if (dola) {
+    TRY(launch_gather_rows(ctx->dt, ctx->d_idx, x, nullptr, ctx->tw_last, b, H, s));
+    TRY(dola_head(ctx, ctx->tw_last, logits_last, s));
+  } else if (logits_last) {
     // only the last valid position feeds generation (Qwen2ForCausalLM.forward :462-465 projects all; same values)
     hipLaunchKernelGGL(last_row_index_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_len, S, b, ctx->d_idx, keep);
     TRY(launch_gather_rows(ctx->dt, ctx->d_idx, x, nullptr, ctx->tw_last, b, H, s));
@@ -1331,6 +1373,7 @@ extern "C" int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(ctx->tp_size == 1, "prefill_extend: tensor-parallel contexts are not implemented (DESIGN.md section 7)");
+  OM_CHECK(!ctx->pick.dola_on(), "prefill_extend: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); the kept slots' candidate rows are gone");
   OM_CHECK(!ctx->fp8_kv, "prefill_extend: the e4m3 KV cache is not implemented (DESIGN.md section 7): omchat_enable_fp8_kv(ctx, 0)");
   OM_CHECK(!ctx->fp8_prefill, "prefill_extend: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
   OM_CHECK(!ctx->left_padded, "prefill_extend: the cache holds a left-padded batch");
@@ -1354,6 +1397,7 @@ extern "C" int omchat_prefill_suffixes(omchat_ctx* ctx, const void* embeds, int 
   const omchat_config& c = ctx->c;
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(ctx->tp_size == 1, "prefill_suffixes: tensor-parallel contexts are not implemented (DESIGN.md section 7)");
+  OM_CHECK(!ctx->pick.dola_on(), "prefill_suffixes: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); the suffix pass keeps no candidate rows");
   OM_CHECK(!ctx->fp8_kv, "prefill_suffixes: the e4m3 KV cache is not implemented (DESIGN.md section 7): omchat_enable_fp8_kv(ctx, 0)");
   OM_CHECK(!ctx->fp8_prefill, "prefill_suffixes: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "prefill_suffixes: the cache holds a left-padded or masked-decode (padded batch) state");
@@ -1450,6 +1494,16 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   void* x = ctx->tw_x;
   void* y = ctx->tw_x2;
   TRY(launch_gather_rows(ctx->dt, tokens, ctx->t_embed, nullptr, x, b, H, s));      // embed_tokens
+  // layer-contrastive decoding (the step entries refused every other mode): the step's rows of the residual stream are kept at the candidate
+  // layers -- HF's hidden_states index h: 0 = the embeddings, h = behind decoder layer h -- with a device-to-device copy, which a graph captures
+  const PickState::Dola& D = ctx->pick.dola;
+  const bool dola = D.on && vL < 0 && !masked;
+  auto dola_keep = [&](int h) -> int {
+    const int j = dola ? D.slot(h) : -1;
+    if (j >= 0) OM_HIP(hipMemcpyAsync(dola_slot(ctx, j), x, (size_t)b * H * 2, hipMemcpyDeviceToDevice, s));
+    return 0;
+  };
+  TRY(dola_keep(0));
   // One weight format per step (omchat_decode_weight_format): e4m3 or MXFP4 at b == 1 (under tensor parallelism every rank streams the e4m3
   // replica of its own shard), and on batched steps (2 <= b <= 32) the packed MXFP4 replica in mode 2, else the 16-bit packed one once it
   // exists.  pk: the activations that feed a GEMV of a batched step (tw_xn, tw_ao, tw_act) are produced in the packed x layout (common.h)
@@ -1525,7 +1579,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     if (!fused) TRY(launch_rmsnorm(ctx->dt, x, H, L.ln1, ctx->tw_xn, H, b, H, c.t_eps, s));
     // batch 1, one GPU (round 4): the whole layer as ONE launch with in-launch hand-offs (decode_layer.hip; the same bits as the six
     // launches below).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
-    if (g_decode_layer && n1 && exact_len && !masked && !wq && !(ctx->fp8_kv && ctx->kv8_valid) && ctx->dl_ws) {      // (the layer kernel has no key mask)
+    if (g_decode_layer && !dola && n1 && exact_len && !masked && !wq && !(ctx->fp8_kv && ctx->kv8_valid) && ctx->dl_ws) {      // (the layer kernel has no key mask)
       DecodeLayerArgs d{L.ln1, L.ln2, W16[QKV].W, L.bqkv, W16[O].W, W16[GU].W, W16[DOWN].W, kc, vc, ctx->cache_sh(), x, H, qd, ctx->t_kvdim, It, c.t_heads, c.t_kv_heads, Lmax,
                         ctx->rope, c.max_seq, c.t_eps, omchat_ctx::T_ATTN_SCALE, ctx->dl_ws, ++ctx->fd_epoch, ctx->fd_err, 2000};
       if (decode_layer_ok(d)) {
@@ -1576,7 +1630,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
     // batch 1, one GPU (round 4): attention + merge + o_proj (+ residual) as ONE launch with in-launch hand-offs (fused_decode.hip; the same
     // bits as the three launches).  Eager steps only: the launch is tagged with a per-launch counter, which a captured graph would freeze.
     bool ao_oproj = false;
-    const bool fuse_ao = g_fuse_attn_oproj && n2 && exact_len && !wq && a.rope && ctx->fd_ws && attn_oproj_fused_ok(a, H, qd);
+    const bool fuse_ao = g_fuse_attn_oproj && !dola && n2 && exact_len && !wq && a.rope && ctx->fd_ws && attn_oproj_fused_ok(a, H, qd);
     if (vL < 0 && ctx->group.on()) {
       // sampled group sharing its prompt (omchat_group_begin): the prompt keys once per group, each row's own keys per row; the lengths come
       // from the device, Lmax (the suffix bucket, omchat_decode_step) sizes the grid -- the same launch eager and captured
@@ -1675,10 +1729,16 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
       TRY(ctx->allreduce(y, (size_t)b * H, s));
       std::swap(x, y);
     }
+    TRY(dola_keep(i + 1));
   }
   if (!fused)   TRY(launch_rmsnorm(ctx->dt, x, H, ctx->t_norm, ctx->tw_xn, H, b, H, c.t_eps, s));
   float* lg = logits ? logits : ctx->tw_logits;
-  if (n1) {
+  int pick_b = b;
+  if (dola) {
+    // in place of the batch-1 head with its fused norm and coded stream: the final norm as a launch, one 16-bit pass over (k + 1) b rows
+    TRY(dola_head(ctx, x, logits, s));
+    lg = ctx->pick.dola_logits; pick_b = D.rows();
+  } else if (n1) {
     GemvArgs g{x, H, nullptr, 0, lg, c.t_vocab, 1, c.t_vocab, H, nullptr, nullptr, 0, EPI_NONE, 1};
     use_weight(g, ctx->lm_w(fmt));
     if (const auto* r = x12_of(omchat_ctx::X12_LM, 0)) { use_weight_x12(g, *r, H); ++ctx->x12_launches[omchat_ctx::X12_LM]; }
@@ -1689,7 +1749,7 @@ static int decode_body(omchat_ctx* ctx, const int32_t* tokens, int b, int Lmax, 
   }
   // the position bookkeeping (pos += 1, len += 1) rides in the argmax's second stage when the step picks a token (one launch less per token)
   if (vL >= 0) TRY(pick_verify(ctx, lg, b, tokens, next_tokens, s, vsample));
-  else if (next_tokens) TRY(pick_run(ctx, lg, b, next_tokens, s, true, tokens));
+  else if (next_tokens) TRY(pick_run(ctx, lg, pick_b, next_tokens, s, true, tokens));
   else {
     hipLaunchKernelGGL(advance_lens_kernel, dim3(1), dim3(64 > b ? 64 : b), 0, s, ctx->d_pos, ctx->d_len, b);
     TRY(pick_feed(ctx, tokens, b, s));
@@ -1753,6 +1813,8 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   OM_CHECK(b >= 1 && b <= c.max_batch, "batch exceeds max_batch");
   OM_CHECK(mx4_rows_ok(ctx, b), MX4_ROWS_MSG);
   if (const char* why = pick_rows_refusal(ctx, b)) OM_CHECK(false, why);
+  if (ctx->pick.dola_on())
+    if (const char* why = dola_state_refusal(ctx)) OM_CHECK(false, why);
   int Lmax = 0;
   OM_CHECK(!ctx->left_padded, "per-sequence decode after a left-padded prefill: use omchat_decode_step_masked (the reference positions such a "
                               "batch with sum(mask) - 1 and a per-row key mask, omchat_arch.py:61-70; DESIGN.md section 7)");
@@ -1789,7 +1851,8 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   } else {
     const int fmt = step_format(ctx, b);
     omchat_ctx::DecodeGraph& g = ctx->graphs[b * 8 + (is_mxfp4(fmt) ? 4 : 0) + (fmt == OMCHAT_WFMT_E4M3 ? 2 : 0) + ((ctx->fp8_kv && ctx->kv8_valid) ? 1 : 0) +
-                                             (grp ? (1 << 20) : 0) + (x12_step_mask(ctx, b, fmt) << 21)];      // (+ the bf16x12 roles of tuning key 50: switching captures again)
+                                             (ctx->pick.dola_on() ? (1 << 19) : 0) + (grp ? (1 << 20) : 0) +
+                                             (x12_step_mask(ctx, b, fmt) << 21)];      // (+ the bf16x12 roles of tuning key 50: switching captures again)
     hipStream_t gs = ctx->graph_stream;
     OM_HIP(hipEventRecord(ctx->graph_ev_in, s));
     OM_HIP(hipStreamWaitEvent(gs, ctx->graph_ev_in, 0));
@@ -1837,6 +1900,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(!ctx->pick.constraints_on(), "constraints are on: each verify row would need its own ban set (omchat_set_constraints with b = 0 first)");
   OM_CHECK(!ctx->pick.fsm_on(), "a token FSM is on: each verify row would need its own state (omchat_fsm_begin with b = 0 first)");
   OM_CHECK(!ctx->pick.guidance_on(), "guidance is on: each verify row would need its twin (omchat_set_guidance with b = 0 first)");
+  OM_CHECK(!ctx->pick.dola_on(), "layer-contrastive decoding is on: each verify row would need its candidate rows (omchat_set_dola with b = 0 first)");
   OM_CHECK(!ctx->beam.on(), "a beam search is active");
   OM_CHECK(!ctx->group.on(), "a sampled group shares its prompt: a verify step runs one sequence (omchat_group_begin with b = 0 first)");
   OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
@@ -1881,6 +1945,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   OM_CHECK(ctx->dec_mode != 1, "omchat_decode_step_masked after omchat_decode_step on the same prefill: the two place the cache rows differently");
   OM_CHECK(ctx->tp_size == 1, "masked decode: one GPU (under tensor parallelism right-padded batches take the per-sequence step)");
   OM_CHECK(!ctx->pick.guidance_on(), "masked decode: guidance is on, and its twin rows run at their own lengths (omchat_set_guidance with b = 0 first)");
+  OM_CHECK(!ctx->pick.dola_on(), "masked decode: layer-contrastive decoding is on, and the padded-batch step keeps no candidate rows (omchat_set_dola with b = 0 first)");
   OM_CHECK(!ctx->group.on(), "masked decode: a sampled group shares its prompt, and the shared attention has no key mask (omchat_group_begin with b = 0 first)");
   OM_CHECK(ctx->pre_S + ctx->masked_steps + 1 <= c.max_seq, "KV cache full (max_seq)");
   if (!ctx->d_mask) {

@@ -1,4 +1,4 @@
-// The token pick of a step, with its state (PickState, ctx.h): the guidance stage (guidance.hip), the ban stage of the logits constraints (constrain.hip), the automaton
+// The token pick of a step, with its state (PickState, ctx.h): the guidance stage (guidance.hip) or the layer-contrast stage (dola.hip), the ban stage of the logits constraints (constrain.hip), the automaton
 // stage of the token FSM (fsm.hip), the argmax (elementwise.hip) or the sampler (sample.hip), the record stage of the per-token log-probabilities (logprob.hip) -- their order, the
 // refusals and host counters in front of a step, their setters and their rewind.  model.hip sees the functions ctx.h declares.  Host C++.
 #include "ctx.h"
@@ -91,6 +91,34 @@ int guidance_stage(omchat_ctx* ctx, const float** lg, int* b, hipStream_t s) {
   return 0;
 }
 
+// The layer-contrast stage in the same place (omchat_set_dola; nothing when it is off; the two exclude each other): the pick was handed the
+// (k + 1) b rows a prefill or step left in the context -- the final rows, then the candidates' --; *lg then points at the context's copy with
+// the b rows of contrasted scores, *b is the b rows that pick, and the record takes the layer every row chose.
+int dola_stage(omchat_ctx* ctx, const float** lg, int* b, hipStream_t s) {
+  const PickState& P = ctx->pick;
+  if (!P.dola.on) return 0;
+  OM_CHECK(*b == P.dola.rows() && *lg == P.dola_logits, "layer-contrastive decoding is on: a pick takes the (k + 1) b rows of the last prefill or step");
+  const omchat_config& c = ctx->c;
+  DolaArgs a;
+  a.logits = *lg; a.ld = c.t_vocab; a.V = c.t_vocab; a.b = P.dola.b; a.k = P.dola.k; a.relative_top = P.dola.relative_top;
+  a.out = P.con_logits; a.ld_out = c.t_vocab; a.ws = P.dola_ws; a.ws_bytes = P.dola_ws_cap;
+  a.layers = P.dola_layers; a.rec = (int32_t*)P.dola_rec.p; a.cnt = P.dola_cnt; a.cap = P.dola_cap; a.rec_ld = c.max_batch;
+  TRY(launch_dola(a, s));
+  *lg = P.con_logits;
+  *b = P.dola.b;
+  return 0;
+}
+
+// a pick entry's rows while layer-contrastive decoding is on: the context's own (the caller's b rows are the final rows of the same call)
+int dola_entry_rows(omchat_ctx* ctx, const float** lg, int* b) {
+  const PickState& P = ctx->pick;
+  if (!P.dola.on) return 0;
+  OM_CHECK(P.dola_fresh, "layer-contrastive decoding is on: no prefill or step since omchat_set_dola has left the rows of this pick");
+  *lg = P.dola_logits;
+  *b = P.dola.rows();
+  return 0;
+}
+
 // The record stage behind a pick (omchat_set_logprobs; nothing when it is off): raw = the caller's logits (under guidance its first b rows:
 // the conditional rows' raw logits), proc = what the pick ran on (the guided scores when guidance is on, with the bans and the automaton's
 // mask when those are on).  The sampler's parameters, seen bitmap, newly-set bits and thresholds are read where the pick left them.
@@ -180,6 +208,7 @@ int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipS
   const PickState& P = ctx->pick;
   const float* raw = lg;
   TRY(guidance_stage(ctx, &lg, &b, s));
+  TRY(dola_stage(ctx, &lg, &b, s));      // (raw stays the first b of its rows: the final rows)
   // under guidance the pick's launches move nothing: the twin launch behind them copies the ids and moves the positions of all 2b rows
   const bool guided = P.gd.on;
   const bool adv = advance;
@@ -212,6 +241,17 @@ int pick_run(omchat_ctx* ctx, const float* lg, int b, int32_t* next_tokens, hipS
 const char* pick_rows_refusal(omchat_ctx* ctx, int rows) {
   const PickState& P = ctx->pick;
   if (P.gd.on && rows != 2 * P.gd.b) return "guidance is on: this call takes exactly 2b rows -- the b conditional rows, then their twins (omchat_set_guidance with b = 0 first)";
+  if (P.dola.on && rows != P.dola.b) return "layer-contrastive decoding is on: this call takes exactly the b rows omchat_set_dola was given (omchat_set_dola with b = 0 first)";
+  return nullptr;
+}
+
+const char* dola_state_refusal(const omchat_ctx* ctx) {
+  if (ctx->tp_size > 1) return "layer-contrastive decoding: one GPU (the vocabulary-parallel exchange of the log-sum-exps and divergences is not built)";
+  if (ctx->beam.on()) return "layer-contrastive decoding: a beam search is active";
+  if (ctx->pick.gd.on) return "layer-contrastive decoding: guidance is on (omchat_set_guidance with b = 0 first); the two stages write the same copy";
+  if (ctx->group.on()) return "layer-contrastive decoding: a sampled group shares its prompt (omchat_group_begin with b = 0 first)";
+  if (ctx->fp8_decode) return "layer-contrastive decoding: the e4m3 decode replica is on, and the head pass over the candidate rows is 16-bit only (omchat_enable_fp8_decode(ctx, 0) first)";
+  if (ctx->mxfp4_mode) return "layer-contrastive decoding: the MXFP4 decode replica is on, and the head pass over the candidate rows is 16-bit only (omchat_enable_mxfp4_decode(ctx, 0) first)";
   return nullptr;
 }
 
@@ -291,6 +331,7 @@ int pick_rewind(omchat_ctx* ctx, int b, int n, hipStream_t s) {
     TRY(launch_constrain_rewind(P.con_len, P.con_plen, std::min(b, P.con.b), n, s));
     P.con_fed = std::max(0, P.con_fed - n);
   }
+  if (P.dola.on) TRY(launch_logprob_rewind(P.dola_cnt, std::min(b, P.dola.b), n, s));      // the layer record forgets those picks too
   if (P.fsm.on) {
     // the trail keeps every state: going back is the counts alone
     TRY(launch_fsm_rewind(P.fsm_cnt, std::min(b, P.fsm.b), n, s));
@@ -305,6 +346,7 @@ extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_
   TRY(lp_room(ctx));      // (in front of the refusal below as well: a full record is the first thing this call reports)
   // (the sampler's state is not this pick's: with sampling on, the first token comes from omchat_sample)
   OM_CHECK(!ctx->pick.lp.on || !ctx->pick.smp.on, "logprobs: omchat_greedy while sampling is on (omchat_sample picks the first token then)");
+  TRY(dola_entry_rows(ctx, &logits, &b));
   TRY(pick_admit(ctx, true, false));
   return pick_run(ctx, logits, b, next_tokens, (hipStream_t)stream, false, nullptr, true);
 }
@@ -313,6 +355,7 @@ extern "C" int omchat_greedy(omchat_ctx* ctx, const float* logits, int b, int32_
 extern "C" int omchat_sample(omchat_ctx* ctx, const float* logits, int b, int32_t* next_tokens, void* stream) {
   OM_CHECK(ctx && logits && next_tokens && b >= 1 && b <= ctx->c.max_batch, "bad argument");
   if (const char* why = pick_rows_refusal(ctx, b)) OM_CHECK(false, why);
+  TRY(dola_entry_rows(ctx, &logits, &b));
   TRY(pick_admit(ctx, true, false));
   return pick_run(ctx, logits, b, next_tokens, (hipStream_t)stream);
 }
@@ -706,10 +749,87 @@ extern "C" int omchat_set_guidance(omchat_ctx* ctx, int b, float scale, void* st
   OM_CHECK(isfinite(scale), "guidance: the scale must be a finite float");
   OM_CHECK(!ctx->beam.on(), "guidance: a beam search is active");
   OM_CHECK(!ctx->group.on(), "guidance: a sampled group shares its prompt (omchat_group_begin with b = 0 first)");
+  OM_CHECK(!P.dola.on, "guidance: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); the two stages write the same copy");
   void* old_copy = P.con_logits;
   if (!P.gd_ws) TRY(ctx->alloc(&P.gd_ws, guidance_ws_bytes(c.max_batch / 2, c.t_vocab)));
   if (!P.con_logits) TRY(ctx->alloc((void**)&P.con_logits, (size_t)c.max_batch * c.t_vocab * 4));
   if (!P.gd.on || P.gd.b != b || P.gd.scale != scale || old_copy != P.con_logits) drop_decode_graphs(ctx);
   P.gd.on = true; P.gd.b = b; P.gd.scale = scale;
+  return 0;
+}
+
+// ---- layer-contrastive decoding (include/omchat_hip.h)
+// b, k, the layers, relative_top, norm and the buffers are kernel arguments (or launches) of the captured decode graphs: a change drops them,
+// the same values on the next call keep them.  Every call begins a new record.
+extern "C" int omchat_set_dola(omchat_ctx* ctx, int b, const int32_t* layers, int k, float relative_top, int norm, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  PickState& P = ctx->pick;
+  const omchat_config& c = ctx->c;
+  if (b <= 0) {
+    if (P.dola.on) drop_decode_graphs(ctx);
+    P.dola = PickState::Dola{};
+    P.dola_fresh = false;
+    return 0;
+  }
+  // every refusal before anything is allocated or changed
+  OM_CHECK(c.t_layers > 0, "context has no decoder");
+  if (const char* why = dola_state_refusal(ctx)) OM_CHECK(false, why);
+  OM_CHECK(layers && k >= 1 && k <= OMCHAT_DOLA_MAX_LAYERS, "layer-contrastive decoding: 1 <= k <= 16 candidate layers");
+  const int R = std::min(c.max_batch, 32);
+  OM_CHECK((int64_t)(k + 1) * b <= R, "layer-contrastive decoding: (k + 1) * b rows go through the head in one pass: at most min(max_batch, 32)");
+  OM_CHECK(relative_top > 0.f && relative_top <= 1.f, "layer-contrastive decoding: relative_top must lie in (0, 1]");
+  PickState::Dola p;
+  p.on = true; p.norm = norm != 0; p.b = b; p.k = k; p.relative_top = relative_top;
+  for (int j = 0; j < k; ++j) {
+    OM_CHECK(layers[j] >= 0 && layers[j] < c.t_layers, "layer-contrastive decoding: a candidate index outside [0, num_hidden_layers) of HF's hidden_states");
+    for (int i = 0; i < j; ++i) OM_CHECK(layers[i] != layers[j], "layer-contrastive decoding: the candidate layers must be distinct");
+    p.layers[j] = layers[j];
+  }
+  void* old_copy = P.con_logits;
+  if (!P.dola_logits) {
+    const size_t nt = (size_t)cdiv(c.t_vocab, 2048);
+    TRY(ctx->alloc((void**)&P.dola_logits, (size_t)R * c.t_vocab * 4));
+    TRY(ctx->alloc(&P.dola_hid, (size_t)R * c.t_hidden * 2));
+    P.dola_ws_cap = (size_t)R * nt * 12;      // >= dola_ws_bytes(b, k, V) for every (k + 1) * b <= R
+    TRY(ctx->alloc(&P.dola_ws, P.dola_ws_cap));
+    TRY(ctx->alloc((void**)&P.dola_layers, (size_t)OMCHAT_DOLA_MAX_LAYERS * 4));
+    TRY(ctx->alloc((void**)&P.dola_cnt, (size_t)c.max_batch * 4));
+    P.dola_cap = c.max_seq + 1;      // a sequence cannot be picked for more often than it has slots
+    TRY(ctx->grow(P.dola_rec, (size_t)P.dola_cap * c.max_batch * 4));
+  }
+  OM_CHECK(dola_ws_bytes(b, k, c.t_vocab) <= P.dola_ws_cap, "layer-contrastive decoding: workspace");
+  if (!P.con_logits) TRY(ctx->alloc((void**)&P.con_logits, (size_t)c.max_batch * c.t_vocab * 4));
+  if (!(p == P.dola) || old_copy != P.con_logits) drop_decode_graphs(ctx);
+  P.dola = p;
+  P.dola_fresh = false;
+  hipStream_t s = (hipStream_t)stream;
+  OM_HIP(hipMemcpyAsync(P.dola_layers, P.dola.layers, (size_t)OMCHAT_DOLA_MAX_LAYERS * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(P.dola_cnt, 0, (size_t)c.max_batch * 4, s));
+  OM_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int omchat_dola_read(omchat_ctx* ctx, int32_t* out, int rows, int steps) {
+  OM_CHECK(ctx && out, "null argument");
+  const PickState& P = ctx->pick;
+  const int mb = ctx->c.max_batch;
+  OM_CHECK(P.dola_cnt && rows >= 1 && rows <= mb && steps >= 0, "omchat_dola_read: rows that omchat_set_dola switched on");
+  OM_HIP(hipDeviceSynchronize());
+  std::vector<int> cnt(mb);
+  OM_HIP(hipMemcpy(cnt.data(), P.dola_cnt, cnt.size() * 4, hipMemcpyDeviceToHost));
+  const int lines = std::min(steps, P.dola_cap);
+  std::vector<int32_t> rec((size_t)lines * mb);
+  if (lines) OM_HIP(hipMemcpy(rec.data(), P.dola_rec.p, rec.size() * 4, hipMemcpyDeviceToHost));
+  for (int r = 0; r < rows; ++r)
+    for (int t = 0; t < steps; ++t) out[(size_t)r * steps + t] = t < lines && t < cnt[r] ? rec[(size_t)t * mb + r] : -1;
+  return 0;
+}
+
+extern "C" int omchat_dola_rows(omchat_ctx* ctx, float* out) {
+  OM_CHECK(ctx && out, "null argument");
+  const PickState& P = ctx->pick;
+  OM_CHECK(P.dola.on && P.dola_fresh, "omchat_dola_rows: no prefill or step has run since omchat_set_dola");
+  OM_HIP(hipDeviceSynchronize());
+  OM_HIP(hipMemcpy(out, P.dola_logits, (size_t)P.dola.rows() * ctx->c.t_vocab * 4, hipMemcpyDeviceToHost));
   return 0;
 }

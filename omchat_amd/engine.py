@@ -180,6 +180,7 @@ class Engine:
     def enable_fp8_decode(self, on=True):
         """Weight-only OCP e4m3 replica of the decode-streamed decoder weights (quantised on first call); batch-1 decode only."""
         check(self.lib.omchat_enable_fp8_decode(self.h, int(on)))
+        self._fp8_decode = bool(on)
 
     def enable_mxfp4_decode(self, on=True, batched=False):
         """Weight-only MXFP4 replica (OCP Microscaling: e2m1 codes + one e8m0 scale per 32 k, 4.25 bits per weight) of the decode-streamed
@@ -759,6 +760,54 @@ class Engine:
                                           cur_stream()))
         torch.cuda.current_stream().synchronize()      # (ws is released when this returns)
         return out
+
+    # ------------------------------------------------------------------ layer-contrastive decoding (include/omchat_hip.h: omchat_set_dola)
+    def set_dola(self, b, layers, relative_top=0.1, norm=False):
+        """every following prefill and decode step of rows 0..b-1 also keeps the rows' last-position hidden state at `layers` (indices into
+        HF's hidden_states: 0 = the embeddings, i = behind decoder layer i) and pushes them through the head with the final row; every pick
+        then runs on the relative-top-filtered contrast of the final row with the candidate of the largest Jensen-Shannon divergence from
+        it.  Call it BEFORE the prefill whose logits pick the first token.  Begins a new record (dola_record).
+        Sticky until dola_off() (or b = 0); the same arguments keep the captured decode graphs."""
+        torch = _torch()
+        ls = torch.tensor([int(i) for i in layers] or [0], dtype=torch.int32)
+        check(self.lib.omchat_set_dola(self.h, int(b), ptr(ls), len(layers), float(relative_top), int(bool(norm)), cur_stream()))
+        self._dola = (int(b), len(layers)) if int(b) > 0 else None
+
+    def dola_off(self):
+        if vars(self).get("_dola", None) is not None:
+            check(self.lib.omchat_set_dola(self.h, 0, None, 0, 0.1, 0, cur_stream()))
+        self._dola = None
+
+    def dola_rows(self):
+        """test hook: the raw logits [(k + 1) * b, V] of the last prefill or step on the host -- rows [0, b) the final rows, row
+        (1 + j) * b + r candidate j of sequence r (synchronises)"""
+        torch = _torch()
+        b, k = self._dola
+        out = torch.empty((k + 1) * b, self.c.t_vocab, dtype=torch.float32)
+        check(self.lib.omchat_dola_rows(self.h, ptr(out)))
+        return out
+
+    def dola_record(self, rows, steps):
+        """int64 [rows, steps] on the host: the HF index of the layer every pick since set_dola contrasted with, -1 where a row has no such
+        pick (synchronises)"""
+        torch = _torch()
+        out = torch.full((int(rows), max(int(steps), 1)), -1, dtype=torch.int32)
+        check(self.lib.omchat_dola_read(self.h, ptr(out), int(rows), max(int(steps), 1)))
+        return out[:, :int(steps)].to(torch.int64)
+
+    def dola(self, logits, b, k, relative_top=0.1, out=None):
+        """the stage alone (omchat_op_dola): logits fp32 [(k + 1) * b, ld] (any row stride >= V = logits.shape[1]) -> (scores fp32 [b, V],
+        the picked candidate positions int32 [b])"""
+        torch = _torch()
+        V = logits.shape[1]
+        n = max(int(self.lib.omchat_op_dola_ws(int(b), int(k), int(V))), 16)
+        ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out = out if out is not None else torch.empty(b, V, dtype=torch.float32, device=self.device)
+        picked = torch.empty(b, dtype=torch.int32, device=self.device)
+        check(self.lib.omchat_op_dola(ptr(logits), int(logits.stride(0)), int(V), int(b), int(k), float(relative_top), ptr(out), int(out.stride(0)),
+                                      ptr(picked), ptr(ws), n, cur_stream()))
+        torch.cuda.current_stream().synchronize()      # (ws is released when this returns)
+        return out, picked
 
     # ------------------------------------------------------------------ sampled groups (include/omchat_hip.h: omchat_group_begin)
     def group_share_refusal(self, N):

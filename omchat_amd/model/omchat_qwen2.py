@@ -574,7 +574,25 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         prompt_lookup_num_tokens, reuse_cache=True, padded or ragged prompt rows or negative rows, tensor parallelism, the e4m3 KV cache
         and fp8 prefill GEMMs; ValueError for a scale that is no finite number, another row count than input_ids', ids outside the
         vocabulary other than -200, -200 without negative_images (or negative_images without -200), 2b > max_batch, more tiles than
-        max_tiles, rows that do not fit max_seq / max_prefill_rows."""
+        max_tiles, rows that do not fit max_seq / max_prefill_rows.
+        dola_layers='low' | 'high' | [indices] with dola_relative_top (default 0.1) and dola_norm (all also read from generation_config;
+        DESIGN.md section 22): HF's DoLa decoding (Chuang et al., "Decoding by Contrasting Layers") on the device.  The indices count HF's
+        hidden_states -- 0 the embedding row, i the residual stream behind decoder layer i --; 'low' and 'high' resolve as HF's do
+        (omchat_amd/dola.py).  At every pick each row's last-position hidden state at the k candidate layers goes through the head with the
+        final row, in one pass over the head and without a second pass over the decoder; the candidate with the largest Jensen-Shannon
+        divergence from the final row's distribution is contrasted with it: lm - lp on the ids with lm >= max lm + log(dola_relative_top),
+        -inf elsewhere, in front of the token-banning arguments, the automaton and the argmax or sampler.  The candidate rows skip the
+        final norm, as in HF; dola_norm=True (this project's extension) normalises them too.  Every row picks its own layer (HF averages
+        the divergence over the batch: the same at b = 1; at b > 1 a row gets what it would get alone).  dola_layers=None: nothing happens
+        -- the launches and ids of a call without the keyword.  .logprobs stays the final row's raw log-softmax, .processed_logprobs is what
+        the pick saw; with return_dict_in_generate=True the output carries .dola_premature_layers [b, new]: the index of the layer every
+        pick contrasted with, -1 behind a row's EOS.  Works greedy and with do_sample=True (all parameters and filters), with the ban
+        arguments, token_fsm, output_logprobs and its extras, a streamer, stopping criteria and the decode graph.  Refused from host data,
+        before any work (omchat_amd/dola.py): NotImplementedError for num_beams > 1, guidance_scale, num_return_sequences > 1, suffixes=,
+        prompt_lookup_num_tokens, reuse_cache=True, padded or left-padded batches, tensor parallelism and the fp8 / MXFP4 decode modes;
+        ValueError for a value that is none of the three forms, a negative or repeated index, no index below num_hidden_layers, more than
+        16 layers, a dola_relative_top outside (0, 1], (k + 1) * b > min(max_batch, 32).  Not pinned against HF: transformers 5 moved DoLa
+        out of the library; tests/dola_ref.py restates HF 4.4x's functions."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -589,6 +607,18 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                                           "implemented (DESIGN.md section 7)")
         # classifier-free guidance: resolved and refused from host data, before any work
         gd = self._guidance_params(input_ids, images, attention_mask, kwargs, nb, num_return_sequences, suffixes, reuse)
+        # layer-contrastive decoding: resolved and refused from host data, before any work
+        from .. import dola as _dola
+        dl = _dola.resolve_dola(gc, kwargs, lambda: self.engine.c.t_layers, bool(getattr(self.config, "tie_word_embeddings", False)))
+        if dl is not None:
+            e = self.engine
+            nret = num_return_sequences if num_return_sequences is not None else (getattr(gc, "num_return_sequences", None) or 1)
+            plk = kwargs.get("prompt_lookup_num_tokens", None)
+            plk = plk if plk is not None else getattr(gc, "prompt_lookup_num_tokens", None)
+            ragged = input_ids.shape[0] > 1 and len(set(self._spliced_lengths(input_ids.detach().to("cpu", torch.int64), images))) > 1
+            _dola.refuse(input_ids.shape[0], len(dl["layers"]), e.c.max_batch, nb, gd is not None, nret, suffixes is not None, plk is not None, reuse,
+                         ragged or (attention_mask is not None and bool((attention_mask == 0).any())), e.tp_size,
+                         vars(e).get("_fp8_decode", False), vars(e).get("_mxfp4_decode", False))
         sfx = None
         if suffixes is not None:      # every refusal that host data decides, before any work (and before the other modes' own refusals)
             sfx = self._suffix_params(input_ids, images, attention_mask, suffixes, nb, num_return_sequences, share_prompt, reuse, kwargs, streamer)
@@ -627,6 +657,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             self.engine.token_fsm_off()
         if gd is None and vars(self.engine).get("_guidance_on", False):      # sticky too: a call without the keyword (or with scale 1) is unguided
             self.engine.guidance_off()
+        if dl is None and vars(self.engine).get("_dola", None) is not None:      # sticky too: a call without the keyword contrasts nothing
+            self.engine.dola_off()
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -652,6 +684,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         elif gd is not None:
             out = self._forward_guided(input_ids, images, gd)         # 2b rows: the prompts, then their twins over the negative prompts
         else:
+            if dl is not None:                                        # before the prefill: the first id comes from its candidate rows
+                self.engine.set_dola(b, dl["layers"], dl["relative_top"], dl["norm"])
             out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
         # ONE rule for the first token at every TP degree: omchat_greedy on this rank's vocabulary shard -- local first-index-wins argmax,
         # then the (max, index) exchange the decode step uses (pick.hip: greedy_pick); no torch re-statement on the gathered logits.
@@ -712,7 +746,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 streamer.end()
             self._record_prefix(prompt_slots, gen)
             return torch.cat([input_ids.cpu(), torch.tensor([gen], dtype=torch.int64)], dim=1)
-        new, padded_out = [], []
+        new, padded_out, padded_out_eos = [], [], []                  # (padded_out_eos: the rows already ended, whatever the pad id)
         done = torch.zeros(b, dtype=torch.bool)
         # padded batch (rows of different spliced length, or left padding): decoded as the reference does it (omchat_arch.py:61-70).  HF generate
         # passes the token-level mask grown by one 1 per generated token and `images` on every step; the decode branch pads it with ones to the
@@ -748,6 +782,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 t_cpu = torch.where(done, torch.full_like(t_cpu, pad), t_cpu)
             new.append(t_cpu)
             padded_out.append(done if pad is not None else torch.zeros_like(done))
+            padded_out_eos.append(done)
             if streamer is not None:
                 streamer.put(t_cpu)
             done = done | torch.tensor([int(x) in eos for x in t_cpu])
@@ -774,11 +809,18 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             from ..fsm import DEAD
             dev = self.engine.token_fsm_states(b)
             fsm_states = torch.tensor([DEAD if bool(done[r]) else token_fsm.next(dev[r], int(new[-1][r])) for r in range(b)], dtype=torch.int64)
+        dola_rec = None
+        if dl is not None and return_dict_in_generate:
+            # one line per pick that was not taken back; behind a row's EOS the row was fed the pad and its picks count for nothing
+            dola_rec = torch.where(torch.stack(padded_out_eos, dim=1), torch.full((), -1, dtype=torch.int64), self.engine.dola_record(b, len(new)))
         if not olp:
-            if fsm_states is None:
+            if fsm_states is None and dola_rec is None:
                 return seqs
             res = GenerateOutput(seqs, None, None)
-            res.add("fsm_states", fsm_states)
+            if fsm_states is not None:
+                res.add("fsm_states", fsm_states)
+            if dola_rec is not None:
+                res.add("dola_premature_layers", dola_rec)
             return res
         # the step enqueued ahead was taken back with its record: exactly one record per generated token
         raw, proc, counts = self.engine.read_logprobs(b)
@@ -799,6 +841,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
                 res.add("scored_logprobs", torch.where(k3, sc, zero))
         if fsm_states is not None:
             res.add("fsm_states", fsm_states)
+        if dola_rec is not None:
+            res.add("dola_premature_layers", dola_rec)
         return res
 
     def _group_params(self, input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer):
