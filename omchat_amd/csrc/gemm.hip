@@ -960,7 +960,8 @@ int launch_epi(const GemmArgs& a, hipStream_t stream) {
   const int tile = a.force_tile ? a.force_tile : pick_tile(a.M, a.N, EPI);
   switch (tile) {
     case 1: return launch_cfg<T, 128, 128, 2, 2, EPI>(a, stream);
-    case 3: return launch_cfg<T, 256, 192, 2, 4, EPI>(a, stream);
+    // (48-column wave tiles, NR = 3: the SwiGLU epilogue's (gate, up) block pairs do not fit them -- as for tiles 10 / 11)
+    case 3: if constexpr (EPI != EPI_SWIGLU) return launch_cfg<T, 256, 192, 2, 4, EPI>(a, stream); else break;
     case 4: return launch_cfg<T, 224, 256, 2, 4, EPI>(a, stream);
     case 5: return launch_cfg<T, 192, 256, 2, 4, EPI>(a, stream);
     case 6: return launch_cfg<T, 256, 256, 2, 4, EPI>(a, stream);     // one-barrier-per-K-step structure (kept for A/B)
