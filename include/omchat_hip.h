@@ -786,9 +786,25 @@ int omchat_op_attn_suffix(int dtype, const void* q, const void* k, const void* v
 int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,
                                  int L, float scale, void* ws, size_t ws_bytes, void* stream);
 /* the same over an e4m3 KV cache (omchat_enable_fp8_kv; BASELINE configs[4]): k8 / v8 [b,Hkv,cap,128] OCP e4m3 bytes, ks / vs [b,Hkv,cap] fp32, one
- * scale per cached row (as omchat_op_rope_kv_q8 writes them): score = (q . k8) * ks in fp32, the value scale folded into the probabilities */
+ * scale per cached row (as omchat_op_rope_kv_q8 writes them): score = (q . k8) * ks in fp32, the value scale folded into the probabilities (f16:
+ * divided by a power of two per 64-key tile first, so that the folded factor stays in f16's normal range for value rows of any finite size) */
 int omchat_op_attn_decode_kv8(int dtype, const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out, int b,
                               int Hq, int Hkv, int cap, int L, const int32_t* kv_len, float scale, void* ws, size_t ws_bytes, void* stream);
+/* test hooks (tests/test_gpu_kv8_attn.py).
+ * omchat_op_attn_decode_kv8_masked: omchat_op_attn_decode_kv8 over a padded batch: every row holds L keys, key j of row i is visible iff
+ * key_mask[i][j] != 0 (device bytes [b][mask_sb], mask_sb % 64 == 0, mask_sb >= L).
+ * omchat_op_attn_merge: the split-KV merge every attention launch ends in, alone, over given partials ws [rows][q_heads][nsplit][132] floats (O at
+ * 0..127, the split's score maximum at 128, its exponential sum at 129): row r merges its first min(nsplit, ceil(kv_len[r] / split_keys)) partials
+ * (kv_len NULL: L for every row) with weights 2^((m_s - max m) * scale * log2(e)); out [rows][q_heads][128].  Tuning keys 19 / 21 pick the kernel.
+ * omchat_op_kv_quant: rows [lo, min(lo + max_rows, len[i])) of k16 / v16 [b,Hkv,cap,128] quantised into k8 / v8 / ks / vs (s = absmax / 448, 1 for a
+ * zero row; bytes = e4m3_rne(x / s)); lo = pos_lo[i] (device int32 [b]) or pos0 (pos_lo NULL); len device int32 [b] or NULL (no upper bound). */
+int omchat_op_attn_decode_kv8_masked(int dtype, const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out, int b,
+                                     int Hq, int Hkv, int cap, int L, const unsigned char* key_mask, int64_t mask_sb, float scale, void* ws,
+                                     size_t ws_bytes, void* stream);
+int omchat_op_attn_merge(int dtype, const float* ws, int nsplit, int q_heads, int rows, const int32_t* kv_len, int L, float scale, void* out,
+                         int split_keys, void* stream);
+int omchat_op_kv_quant(int dtype, const void* k16, const void* v16, void* k8, void* v8, float* ks, float* vs, int b, int Hkv, int cap,
+                       const int32_t* pos_lo, int pos0, const int32_t* len, int max_rows, void* stream);
 /* one decode step's attention over the e4m3 cache INCLUDING the new token's RoPE + append + quantisation, as the decoder layer issues it: qkv
  * [b][(Hq + 2 Hkv) * 128] raw projections; sequence i holds kv_len[i] keys counting the new one (NULL: L), whose rows go to position kv_len[i] - 1
  * of k8 / v8 / ks / vs and of the 16-bit caches k16 / v16 [b,Hkv,cap,128]; pos = kv_len - 1 (device, NULL with kv_len).  Launches long enough for

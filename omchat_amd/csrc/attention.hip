@@ -1041,6 +1041,7 @@ __global__ __launch_bounds__(64 * NW, FUSE ? 1 : 2) void attn_decode_kv8_walk_ke
 #pragma unroll
   for (int dn = 0; dn < 8; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float m_run = NEG_BIG, l_run = 0.f;
+  float u_run = 1.f;      // f16: the power-of-two unit o is held in (FoldRescale)
   const int tq = fc >> 2, tp = fc & 3;
   const int vrow_lo = 4 * fg + tq;
   const int vswz = ((vrow_lo & 7) << 1);
@@ -1147,6 +1148,15 @@ __global__ __launch_bounds__(64 * NW, FUSE ? 1 : 2) void attn_decode_kv8_walk_ke
       }
     }
 
+    // f16 (attn_common.h FoldRescale): the value scales are handed over divided by the tile's u, o counts in units of the current tile's u,
+    // and the change of unit rides on the rescaling by alpha below (exact)
+    float unit_step = 1.f;
+    if constexpr (FoldRescale<T>::value) {
+      const float u = fold_unit_of(wave_max(cur.vs));
+      unit_step = u_run / u;
+      u_run = u;
+      cur.vs *= 1.0f / u;
+    }
     // ---- scales into the score layout
     Ss[lane] = cur.ks; Ss[KV_TILE + lane] = cur.vs;
     asm volatile("" ::: "memory");
@@ -1183,8 +1193,9 @@ __global__ __launch_bounds__(64 * NW, FUSE ? 1 : 2) void attn_decode_kv8_walk_ke
       const float m_new = fmaxf(m_run, mx);
       const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.c);
       l_run *= alpha;
+      const float oa = FoldRescale<T>::value ? alpha * unit_step : alpha;
 #pragma unroll
-      for (int dn = 0; dn < 8; ++dn) o[dn] *= alpha;
+      for (int dn = 0; dn < 8; ++dn) o[dn] *= oa;
       mx = m_new;
     }
     m_run = mx;
@@ -1226,6 +1237,10 @@ __global__ __launch_bounds__(64 * NW, FUSE ? 1 : 2) void attn_decode_kv8_walk_ke
     asm volatile("" ::: "memory");
   }
   float l = sum_xor32(sum_xor16(l_run));
+  if constexpr (FoldRescale<T>::value) {
+#pragma unroll
+    for (int dn = 0; dn < 8; ++dn) o[dn] *= u_run;
+  }
   if constexpr (NW > 1) {
     // the waves' states meet in LDS (each wave's own image region is dead: its last transposed reads are behind it in its LDS order):
     // [32 O values + m + l][64 lanes] floats per wave; wave 0 folds them in wave order
@@ -1919,6 +1934,17 @@ static void launch_merge(const float* ws, int nsplit, int q_heads, int rows, con
     hipLaunchKernelGGL(attn_merge_kernel<T>, mgrid, dim3(128), 0, s, ws, nsplit, q_heads, kv_len, L, c, (T*)O, o_sb, o_sh, pack_nb, split_keys,
                        done.flags, done.epoch, done.mode, done.dbg);
   }
+}
+
+int launch_attn_merge(int dtype, const float* ws, int nsplit, int q_heads, int rows, const int* kv_len, int L, float scale, void* O, int split_keys,
+                      hipStream_t s) {
+  OM_CHECK(ws && O && nsplit > 0 && q_heads > 0 && rows > 0 && L > 0 && split_keys > 0, "launch_attn_merge: null or empty argument");
+  const float c = scale * 1.4426950408889634f;
+  if (dtype == OMCHAT_F16) launch_merge<f16>(ws, nsplit, q_heads, rows, kv_len, L, c, O, (int64_t)q_heads * 128, 128, 0, split_keys, s);
+  else if (dtype == OMCHAT_BF16) launch_merge<bf16>(ws, nsplit, q_heads, rows, kv_len, L, c, O, (int64_t)q_heads * 128, 128, 0, split_keys, s);
+  else { omchat_set_error("launch_attn_merge: bad dtype"); return 1; }
+  OM_LAUNCH_CHECK();
+  return 0;
 }
 
 // what launch_attn_decode's plan decided; launch_decode_form turns it into the attention kernel (first match wins) and the merge

@@ -110,6 +110,32 @@ __device__ __forceinline__ float sum_xor16(float v) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+// e4m3 cache, T = f16: the per-key value scale is folded into the probabilities before they become the PV MFMA's 16-bit operand, and with
+// small value rows (absmax ~0.01: scale ~3e-5) e * scale falls into f16's subnormal range -- the head lost 1e-2 and more.  The fold is kept
+// in the normal range by an EXACT rescaling: the tile's scales are divided by u = the power of two at or below the largest of them (so the
+// folded factor of the tile's largest row is e * [1, 2): no overflow whatever the scale) and the tile's PV product counts u times in fp32.
+// bf16 has fp32's exponent range: its fold stays as it is, bit for bit.
+template <typename T> struct FoldRescale { static constexpr bool value = false; };
+template <> struct FoldRescale<f16> { static constexpr bool value = true; };
+// u of a tile whose largest value scale is vm
+__device__ __forceinline__ float fold_unit_of(float vm) {
+  const unsigned eb = __float_as_uint(vm) & 0x7F800000u;
+  return eb ? __uint_as_float(eb) : 1.f;      // (a subnormal or zero maximum: no rescaling)
+}
+// the tile's scales (key0 + 16 kt + 4 fg + r: the same in the 16 fc lanes) divided by u in place; returns u
+__device__ __forceinline__ float fold_unit(f32x4 (&vsc)[4]) {
+  float vm = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) vm = fmaxf(vm, vsc[kt][r]);
+  const float u = fold_unit_of(max_xor32(max_xor16(vm)));
+  const float inv = 1.0f / u;                            // exact: a power of two
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) vsc[kt] *= inv;
+  return u;
+}
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -286,6 +312,8 @@ __device__ __forceinline__ void attn_decode_tile(const AttnP& p, int split, int 
       mx = fmaxf(mx, v);
     }
   mx = max_xor32(max_xor16(mx));
+  float vunit = 1.f;
+  if constexpr (KV8 && FoldRescale<T>::value) vunit = fold_unit(vsc);
   const float mc = mx * p.c;
   float psum = 0.f;
   frag_t pf[2];
@@ -332,6 +360,10 @@ __device__ __forceinline__ void attn_decode_tile(const AttnP& p, int split, int 
       const s16x8 cat = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       o[dn] = mfma16(__builtin_bit_cast(frag_t, cat), pf[ks], o[dn]);
     }
+  if constexpr (KV8 && FoldRescale<T>::value) {
+#pragma unroll
+    for (int dn = 0; dn < 8; ++dn) o[dn] *= vunit;
+  }
   mx_out = mx;
   l_out = l;
 }

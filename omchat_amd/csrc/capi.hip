@@ -268,6 +268,33 @@ extern "C" int omchat_op_attn_decode_kv8(int dtype, const void* q, const void* k
   return launch_attn_decode(dtype, a, S(stream));
 }
 
+// test hook: the same over a padded batch -- key j of row i is visible iff key_mask[i][j] != 0 (rows of mask_sb bytes), every row holds L keys
+extern "C" int omchat_op_attn_decode_kv8_masked(int dtype, const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out,
+                                                int b, int Hq, int Hkv, int cap, int L, const unsigned char* key_mask, int64_t mask_sb, float scale,
+                                                void* ws, size_t ws_bytes, void* stream) {
+  if (!k8 || !v8 || !ks || !vs || !key_mask) { omchat_set_error("omchat_op_attn_decode_kv8_masked: null cache, scale or mask pointer"); return 1; }
+  AttnDecodeArgs a{};
+  bind_dense(a, q, false, k8, v8, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  a.k_scale = ks; a.v_scale = vs; a.scale_sb = (int64_t)Hkv * cap; a.scale_sh = cap;
+  a.batch = b; a.L = L; a.key_mask = key_mask; a.mask_sb = mask_sb;
+  return launch_attn_decode(dtype, a, S(stream));
+}
+
+// test hook: the split-KV merge alone over hand-made partials (tests/test_gpu_kv8_attn.py)
+extern "C" int omchat_op_attn_merge(int dtype, const float* ws, int nsplit, int q_heads, int rows, const int32_t* kv_len, int L, float scale, void* out,
+                                    int split_keys, void* stream) {
+  return launch_attn_merge(dtype, ws, nsplit, q_heads, rows, kv_len, L, scale, out, split_keys, S(stream));
+}
+
+// test hook: the e4m3 cache quantiser over dense caches k16 / v16 / k8 / v8 [b, Hkv, cap, 128] and scales [b, Hkv, cap]
+extern "C" int omchat_op_kv_quant(int dtype, const void* k16, const void* v16, void* k8, void* v8, float* ks, float* vs, int b, int Hkv, int cap,
+                                  const int32_t* pos_lo, int pos0, const int32_t* len, int max_rows, void* stream) {
+  if (!k16 || !v16 || !k8 || !v8 || !ks || !vs) { omchat_set_error("omchat_op_kv_quant: null argument"); return 1; }
+  if (!pos_lo && (pos0 < 0 || (int64_t)pos0 + max_rows > cap)) { omchat_set_error("omchat_op_kv_quant: rows exceed the cache capacity"); return 1; }
+  return launch_kv_quant(dtype, k16, v16, k8, v8, ks, vs, b, Hkv, (int64_t)Hkv * cap * 128, (int64_t)cap * 128, (int64_t)Hkv * cap, cap, pos_lo, pos0, len,
+                         max_rows, S(stream));
+}
+
 static float* rope_table_device(int max_pos, float theta) {
   std::vector<float> tab((size_t)max_pos * 128);
   for (int i = 0; i < 64; ++i) {

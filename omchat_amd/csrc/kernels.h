@@ -321,6 +321,10 @@ int launch_kv_quant(int dtype, const void* kc, const void* vc, void* k8, void* v
                     int64_t s_sb, int64_t s_sh, const int* pos_lo, int pos0, const int* len, int max_rows, hipStream_t s);
 size_t attn_decode_ws_bytes(int batch, int q_heads, int max_len);
 int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s);
+// the split-KV merge alone over given partials ws [rows][q_heads][nsplit][132] (O 0..127, m at 128, l at 129), as launch_attn_decode ends: row r
+// holds kv_len[r] keys (null: L) in splits of split_keys; out [rows][q_heads][128], unpacked (test hook omchat_op_attn_merge)
+int launch_attn_merge(int dtype, const float* ws, int nsplit, int q_heads, int rows, const int* kv_len, int L, float scale, void* O, int split_keys,
+                      hipStream_t s);
 
 // Multi-query decode attention (prompt-lookup verify): T consecutive new tokens of ONE sequence on top of its L cached
 // keys.  Query row t sits at position L + t and sees keys 0 .. L + t.  Every K / V tile is read once for all T x n_rep query rows.
