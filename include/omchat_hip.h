@@ -785,6 +785,16 @@ int omchat_op_attn_suffix(int dtype, const void* q, const void* k, const void* v
  * (the bytes omchat_op_rope_kv writes).  Synchronises. */
 int omchat_op_attn_verify_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int T, int Hq, int Hkv, int cap,
                                  int L, float scale, void* ws, size_t ws_bytes, void* stream);
+/* test hook (tests/test_gpu_attn_block_rows.py): omchat_op_attn_shared[_lens] with the RoPE + append fused in, as omchat_decode_step runs it over
+ * a shared-prompt group: qkv [G*N][(Hq + 2 Hkv) * 128] raw projections (not modified); row r holds kv_len[r] keys counting the new one (device
+ * int32 [G*N], or NULL: L for every row); q is rotated at kv_len[r] - 1, the rotated k and the raw v go to that slot of row r's own cache (the
+ * bytes omchat_op_rope_kv_pos writes with slot = position).  No other cache byte is written.  Synchronises. */
+int omchat_op_attn_shared_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap,
+                                 int P, int L, const int32_t* kv_len, float scale, void* ws, size_t ws_bytes, void* stream);
+/* test hook: the plan of the split-KV block attention on the current device.  mode: 0 verify (S = T, L), 1 extend (S = Sq, L), 2 shared
+ * (G, N, P, L), 3 suffix (N, S, P); the integers a mode does not name are ignored.  out[4] (host) = {tpw: 64-key tiles per split (shared / suffix:
+ * per prefix split), nsp: such splits, nss: suffix splits per row, tps: tiles per suffix split}.  Pure: launches nothing. */
+int omchat_op_attn_block_plan(int mode, int G, int N, int S, int Hq, int Hkv, int P, int L, int* out);
 /* the same over an e4m3 KV cache (omchat_enable_fp8_kv; BASELINE configs[4]): k8 / v8 [b,Hkv,cap,128] OCP e4m3 bytes, ks / vs [b,Hkv,cap] fp32, one
  * scale per cached row (as omchat_op_rope_kv_q8 writes them): score = (q . k8) * ks in fp32, the value scale folded into the probabilities (f16:
  * divided by a power of two per 64-key tile first, so that the folded factor stays in f16's normal range for value rows of any finite size) */

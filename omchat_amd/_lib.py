@@ -156,6 +156,9 @@ _SIGS = {
     "omchat_op_attn_suffix_ws": (_sz, [_i, _i, _i, _i, _i]),
     "omchat_op_attn_suffix": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_verify_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    # test hooks of tests/test_gpu_attn_block_rows.py: the shared mode with its fused RoPE + append; the launcher's plan {tpw, nsp, nss, tps}
+    "omchat_op_attn_shared_append": (_i, [_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
+    "omchat_op_attn_block_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "omchat_op_attn_decode_kv8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
     "omchat_op_attn_decode_kv8_masked": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64, _f, _vp, _sz, _vp]),
     "omchat_op_attn_merge": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _i, _vp]),

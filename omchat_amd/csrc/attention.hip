@@ -2327,6 +2327,13 @@ static BlockPlan attn_block_plan(const AttnBlockArgs& a) {
   }
   return pl;
 }
+int attn_block_plan_query(int mode, int G, int N, int S, int q_heads, int kv_heads, int P, int L, int out[4]) {
+  AttnBlockArgs a{};
+  a.mode = mode; a.G = G; a.N = N; a.S = S; a.q_heads = q_heads; a.kv_heads = kv_heads; a.P = P; a.L = L;
+  const BlockPlan pl = attn_block_plan(a);
+  out[0] = pl.tpw; out[1] = pl.nsp; out[2] = pl.nss; out[3] = pl.tps;
+  return 0;
+}
 size_t attn_block_ws_bytes(const AttnBlockArgs& a) {
   size_t rows = a.S;
   switch (a.mode) {

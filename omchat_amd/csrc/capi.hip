@@ -400,6 +400,32 @@ extern "C" int omchat_op_attn_verify_append(int dtype, const void* qkv, float th
   return rc;
 }
 
+// test hook (tests/test_gpu_attn_block_rows.py): the shared-prompt decode attention WITH its fused RoPE + append, as omchat_decode_step issues it over
+// a sampled group: qkv [G N][(Hq + 2 Hkv) * 128] raw projections (read-only); row r holds kv_len[r] keys counting the new one (NULL: L), q is rotated
+// at kv_len[r] - 1 and the rotated k / raw v go to that slot of row r's own cache (omchat_op_rope_kv_pos's bytes).  Synchronises.
+extern "C" int omchat_op_attn_shared_append(int dtype, const void* qkv, float theta, void* k, void* v, void* out, int G, int N, int Hq, int Hkv, int cap,
+                                            int P, int L, const int32_t* kv_len, float scale, void* ws, size_t ws_bytes, void* stream) {
+  OM_CHECK(qkv && k && v && out && ws, "null argument");
+  OM_CHECK(Hkv > 0 && G >= 1 && N >= 1 && P >= 1 && L > P && L <= cap, "1 <= P < L <= cap");
+  float* tab = rope_table_device(L, theta);
+  OM_CHECK(tab, "rope table allocation failed");
+  AttnBlockArgs a{};
+  bind_dense(a, qkv, true, k, v, out, Hq, Hkv, cap, scale, ws, ws_bytes);
+  bind_new_rows(a, tab, L);
+  a.mode = ATTN_SHARED; a.G = G; a.N = N; a.P = P; a.L = L; a.kv_len = kv_len;
+  const int rc = launch_attn_block(dtype, a, S(stream));
+  hipStreamSynchronize(S(stream));
+  hipFree(tab);
+  return rc;
+}
+
+// test hook: the plan launch_attn_block takes on the current device for a mode (0 verify, 1 extend, 2 shared, 3 suffix) and its integers (those the
+// mode does not name are ignored): out = {tpw, nsp, nss, tps}.  Pure: launches nothing.
+extern "C" int omchat_op_attn_block_plan(int mode, int G, int N, int S, int Hq, int Hkv, int P, int L, int* out) {
+  OM_CHECK(out && mode >= ATTN_VERIFY && mode <= ATTN_SUFFIX && Hq >= 1 && Hkv >= 1, "bad mode, heads or null output");
+  return attn_block_plan_query(mode, G, N, S, Hq, Hkv, P, L, out);
+}
+
 // One decode step's attention over the e4m3 cache INCLUDING the new token's RoPE + append, as the decoder layer issues it (model.hip): qkv
 // [b][(Hq + 2 Hkv) * 128] raw projections of the new token; sequence i holds kv_len[i] keys counting the new one (NULL: L for every sequence), the
 // new row goes to position kv_len[i] - 1 of k8 / v8 / ks / vs and of the 16-bit caches k16 / v16.  Long launches take the walking form, which does

@@ -363,6 +363,8 @@ constexpr int VERIFY_MAX_T = 16;
 size_t attn_block_ws_bytes(const AttnBlockArgs& a);      // bytes of partials the launch needs: reads the mode, its integers and the heads only
 int launch_attn_block(int dtype, const AttnBlockArgs& a, hipStream_t s);
 int attn_verify_tpw(int keys, int kv_heads);      // 64-key tiles per split of an ATTN_VERIFY launch over `keys` keys
+// the plan launch_attn_block takes for a mode and its integers on this device: out = {tpw, nsp, nss, tps} (test hook omchat_op_attn_block_plan)
+int attn_block_plan_query(int mode, int G, int N, int S, int q_heads, int kv_heads, int P, int L, int out[4]);
 size_t attn_extend_ws_bytes(int Sq, int q_heads, int kv_heads, int L);
 size_t attn_shared_ws_bytes(int G, int N, int q_heads, int kv_heads, int P, int L);
 size_t attn_suffix_ws_bytes(int N, int S, int q_heads, int kv_heads, int P);
