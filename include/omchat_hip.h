@@ -627,6 +627,10 @@ int omchat_op_mha_qnorm(int dtype, const void* qkv, int B, int Sq, int H, const 
  * 14.9 us per attention + merge), 1 = always one wave per tile, 2 / 3 / 4 = tiles per wave forced, 11 = 3 tiles x 4 waves forced;
  * key 48: 1 (default) = that walking form also rotates q / k and appends + quantises the new token's k / v rows (no RoPE + append launch in front of
  * the attention of a long-context e4m3 decode step; the same bytes), 0 = separate launch;
+ * key 52: the unmasked one-tile split-KV decode attention over the 16-bit cache (one workgroup per 64-key split, kv head, sequence): 1 (default) = a
+ * single sequence's launch shares each tile among four waves (attn_decode_4w_kernel: K through an LDS image, S^T and the softmax in every wave, the PV
+ * product and the partial's columns by quarters), 0 = one wave per tile (attn_decode_kernel), 2 = four waves at every batch size; the same partials,
+ * output and appended cache bytes bit for bit;
  * key 45: 1 (default) = sequence-parallel norms under tensor parallelism (omchat_ctx_sp_stats), 0 = one all-reduce per sub-block and replicated norms;
  * key 37: 1 (default) = the GEMM epilogues store 16 bytes per lane (two column blocks exchanged between lane pairs), 0 = 8 bytes (same bits);
  * key 38: (gate, up) pairs per wave of the batch-1 gate|up GEMV's non-loop norm form: 1 (default: thousands of small workgroups that the dispatcher

@@ -696,6 +696,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn2_kernel(AttnP p) {
 // round trip -- then S^T from registers, softmax, V -> LDS, PV through ds_read_b64_tr_b16.  With `rope` set it also
 // rotates q in registers and, in the split that owns the new position, rotates k and appends k / v to the cache
 // (replaces the separate RoPE + KV-append launch for S = 1).
+// Since the four-wave form below (tuning key 52) this one runs the e4m3 cache, the masked step and the one-tile launches of more than one
+// sequence; a single sequence over the 16-bit cache takes it with key 52 = 0 only (the reference the four-wave form's bits are tested against).
 // ---------------------------------------------------------------------------------------------------------
 template <typename T, bool KV8 = false, bool MASKED = false>
 __global__ __launch_bounds__(64, 2) void attn_decode_kernel(AttnP p) {
@@ -719,6 +721,195 @@ __global__ __launch_bounds__(64, 2) void attn_decode_kernel(AttnP p) {
 #pragma unroll
     for (int dn = 0; dn < 8; ++dn) *reinterpret_cast<f32x4*>(wsb + dn * 16 + fg * 4) = o[dn];
     if (fg == 0) { wsb[128] = mx; wsb[129] = l; }
+  }
+#if OMCHAT_EXPERIMENTS
+  if (p.dbg && kvh == 0 && lane == 0) atomicMax(p.dbg + 11, wall_clock64());
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same tile on FOUR waves (tuning key 52; a single sequence: ~one workgroup per CU, three SIMDs of which the one-wave form leaves idle).
+// The partial (o, m, l) and the appended cache rows are the one-wave kernel's bit for bit: no sum changes its order.
+//   K:  wave w loads key rows 16 w .. 16 w + 15 as whole 256-byte rows (chunk fc of row 16 w + 4 i + fg) into a K image in LDS
+//       (chunk' = chunk ^ (row & 15), the image of attn_decode_multi_kernel<KLDS>); after ONE workgroup barrier every wave reads all 64
+//       keys' A fragments and runs S^T and the softmax itself -- the same instructions on the same values in every wave, so m, l and the
+//       P fragments are the one-wave kernel's in each of them.
+//   V:  wave w owns output blocks dn = 2 w, 2 w + 1 (d = 32 w .. 32 w + 31): it loads only that 64-byte slice of each of the 64 rows, writes
+//       it to the V transpose image and reads it back alone (the swizzle chunk ^ ((row & 7) << 1) permutes chunks within a row, so the
+//       four waves' slices stay disjoint): no workgroup barrier for V, and the softmax runs under these loads.  Each o[dn] sees the same
+//       two PV MFMAs in the same order as in the one-wave kernel.
+//   RoPE + append: wave w rotates fragment w of q (the B operand of S^T) and the four pass their fragments through LDS behind the same
+//       barrier; a wave whose sixteen rows reach the new position rotates the new key in row layout (partner chunk fc ^ 8 loaded next to
+//       the own one) and SELECTS it into its rows >= pp; the lanes that hold row pp itself (one wave's) append it, and each wave appends
+//       its own slice of the new v row.
+// Per wave: 8 KB of the tile instead of 32, 4 KB of LDS image written instead of 16, 8 transposed reads + 4 PV MFMAs instead of 32 + 16.
+// ---------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void attn_decode_4w_kernel(AttnP p) {
+  typedef typename V8<T>::type frag_t;
+  __shared__ __attribute__((aligned(256))) char Ks[KV_TILE * 256];
+  __shared__ __attribute__((aligned(256))) char Vs[KV_TILE * 256];
+  __shared__ __attribute__((aligned(16))) char Qs[4 * 64 * 16];      // q as the B fragments of S^T: [ds][lane]
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, fc = lane & 15, fg = lane >> 4;
+  const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+  const int n_rep = p.q_heads / p.kv_heads, hq0 = kvh * n_rep;
+  const int kv_len = p.kv_len ? p.kv_len[b] : p.Skv;
+#if OMCHAT_EXPERIMENTS
+  if (p.dbg && split < 8 && kvh == 0 && threadIdx.x == 0) atomicMax(p.dbg + 10, ~wall_clock64());      // measurement: first start (stored inverted)
+#endif
+  float* wsb = p.ws + ((size_t)(b * p.q_heads + hq0 + (fc < n_rep ? fc : 0)) * p.nsplit + split) * WS_STRIDE;
+  const int key0 = split * KV_TILE;
+  if (key0 >= kv_len) {                       // empty split (uniform): neutral partial
+    if (w == 0 && fc < n_rep && fg == 0) { wsb[128] = NEG_BIG; wsb[129] = 0.f; }
+    return;
+  }
+  const bool fuse = p.rope != nullptr;
+  const int pp = kv_len - 1;                  // position of the token being appended (fuse)
+  const int pt = pp < p.rope_max ? (pp > 0 ? pp : 0) : p.rope_max - 1;
+  const T* Kg = (const T*)p.K + b * p.k_sb + kvh * p.k_sh;
+  const T* Vg = (const T*)p.V + b * p.v_sb + kvh * p.v_sh;
+  const T* kn = fuse ? (const T*)p.k_new + b * p.new_sb + kvh * 128 : nullptr;
+  const T* vn = fuse ? (const T*)p.v_new + b * p.new_sb + kvh * 128 : nullptr;
+
+  // ---- q, the new key row and the RoPE table row in front of the tile, without a branch around them (attn_decode_tile: vector memory
+  // returns in order, and a conditional block would end in a wait for everything issued inside it); without RoPE they read q's own bytes.
+  // Wave w rotates fragment w of q only (d = 32 w + 8 fg + j; its rotate-half partner is fragment w ^ 2 of the same lane) and hands it to
+  // the others through LDS: a quarter of the rotation's VALU work per wave, which one wave alone does not finish under the tile's loads
+  const int hh = fc < n_rep ? fc : n_rep - 1;
+  const T* qp = (const T*)p.Q + b * p.q_sb + (hq0 + hh) * p.q_sh;
+  const frag_t q_own = ld8<T>(qp + w * 32 + fg * 8), q_par = ld8<T>(qp + (w ^ 2) * 32 + fg * 8);
+  float csq[16];                              // table entries d mod 64 = 32 (w & 1) + 8 fg + j
+  {
+    const f32x4* cs = reinterpret_cast<const f32x4*>(fuse ? p.rope + ((size_t)pt * 64 + (w & 1) * 32 + fg * 8) * 2 : (const float*)p.Q);
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) { const f32x4 v = cs[q4]; csq[4 * q4] = v[0]; csq[4 * q4 + 1] = v[1]; csq[4 * q4 + 2] = v[2]; csq[4 * q4 + 3] = v[3]; }
+  }
+  // the new key in ROW layout: chunk fc (d = 8 fc + j) and its rotate-half partner, chunk fc ^ 8; table entries d mod 64 = 8 (fc & 7) + j
+  const frag_t kn_own = ld8<T>((fuse ? kn : (const T*)p.Q) + fc * 8), kn_par = ld8<T>((fuse ? kn : (const T*)p.Q) + (fc ^ 8) * 8);
+  float csk[16];
+  {
+    const f32x4* cs = reinterpret_cast<const f32x4*>(fuse ? p.rope + ((size_t)pt * 64 + (fc & 7) * 8) * 2 : (const float*)p.Q);
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) { const f32x4 v = cs[q4]; csk[4 * q4] = v[0]; csk[4 * q4 + 1] = v[1]; csk[4 * q4 + 2] = v[2]; csk[4 * q4 + 3] = v[3]; }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- this wave's quarter of the tile: K rows 16 w + 4 i + fg (chunk fc), V chunks 4 w + (lane & 3) of rows 16 i + vrl
+  frag_t kr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int key = key0 + 16 * w + 4 * i + fg;
+    // (rows >= pp under fused RoPE are replaced by the rotated new key below: their lanes read the last cached row, or row 0 of an empty cache)
+    const int kc = fuse ? (key < pp ? key : (pp > 0 ? pp - 1 : 0)) : (key < kv_len ? key : kv_len - 1);
+    kr[i] = ld8s<T>(Kg + (int64_t)kc * p.k_sr + fc * 8);
+  }
+  // sixteen lanes of a ds_write_b128 pass hold four rows x this wave's four chunks: rows 0, 2, 4, 6 (+ 1, + 8, + 9) of the sixteen, whose swizzle
+  // terms differ in the bits above the wave's chunk pair, keep the pass on sixteen distinct chunk columns
+  const int vrr = lane >> 2, vrl = (vrr & 8) | ((vrr & 3) << 1) | ((vrr >> 2) & 1), vch = 4 * w + (lane & 3);
+  frag_t vr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int key = key0 + 16 * i + vrl;
+    const bool fresh = fuse && key >= pp;
+    const T* src = fresh ? vn : Vg + (int64_t)(key < kv_len ? key : kv_len - 1) * p.v_sr;
+    vr[i] = ld8s<T>(src + vch * 8);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+
+  *reinterpret_cast<frag_t*>(Qs + (w * 64 + lane) * 16) = fuse ? rope_chunk<T>(q_own, q_par, csq, w >= 2) : q_own;
+  if (fuse && key0 + 16 * w + 15 >= pp) {     // this wave's sixteen rows reach the new position (uniform; the owning split only)
+    const frag_t rot = rope_chunk<T>(kn_own, kn_par, csk, fc >= 8);
+    // rows >= pp (per lane) take the rotated new key; the lanes that hold the real row pp append it (N14)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int key = key0 + 16 * w + 4 * i + fg;
+      kr[i] = key >= pp ? rot : kr[i];
+      if (key == pp) st8<T>((T*)p.k_cache_w + b * p.k_sb + kvh * p.k_sh + (int64_t)pp * p.k_sr + fc * 8, kr[i]);
+    }
+  }
+  // ---- K image, published to the four waves with q
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 16 * w + 4 * i + fg;
+    *reinterpret_cast<frag_t*>(Ks + row * 256 + ((fc ^ (row & 15)) << 4)) = kr[i];
+  }
+  __syncthreads();
+  frag_t qf[4];
+#pragma unroll
+  for (int ds = 0; ds < 4; ++ds) qf[ds] = *reinterpret_cast<const frag_t*>(Qs + (ds * 64 + lane) * 16);
+
+  // ---- S^T = K Q^T, every wave all 64 keys: A operand key = key0 + 16*kt + fc, d = 32*ds + 8*fg + j
+  f32x4 s[4];
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+    frag_t kf[4];
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) kf[ds] = *reinterpret_cast<const frag_t*>(Ks + (kt * 16 + fc) * 256 + (((ds * 4 + fg) ^ fc) << 4));
+    s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) s[kt] = mfma16(kf[ds], qf[ds], s[kt]);
+  }
+  // ---- softmax over this split (keys >= kv_len masked)
+  float mx = NEG_BIG;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float v = key0 + kt * 16 + 4 * fg + r < kv_len ? s[kt][r] : NEG_BIG;
+      s[kt][r] = v;
+      mx = fmaxf(mx, v);
+    }
+  mx = max_xor32(max_xor16(mx));
+  const float mc = mx * p.c;
+  float psum = 0.f;
+  frag_t pf[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    typedef float f32x8 __attribute__((ext_vector_type(8)));
+    f32x8 e;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      e[j] = __builtin_amdgcn_exp2f(fmaf(s[2 * ks + (j >> 2)][j & 3], p.c, -mc));
+      psum += e[j];
+    }
+    pf[ks] = __builtin_convertvector(e, frag_t);
+  }
+  const float l = sum_xor32(sum_xor16(psum));
+
+  // ---- this wave's V slice -> transpose image, its slice of the fresh v row appended; written and read by this wave alone
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 16 * i + vrl;
+    *reinterpret_cast<frag_t*>(Vs + row * 256 + ((vch ^ ((row & 7) << 1)) << 4)) = vr[i];
+    if (fuse && key0 + row == pp)
+      st8<T>((T*)p.v_cache_w + b * p.v_sb + kvh * p.v_sh + (int64_t)pp * p.v_sr + vch * 8, vr[i]);
+  }
+  __builtin_amdgcn_wave_barrier(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier();
+
+  // ---- O^T = V^T P^T, output blocks dn = 2 w, 2 w + 1
+  const int tq = fc >> 2, tp = fc & 3;
+  const int vrow_lo = 4 * fg + tq;
+  const int vswz = ((vrow_lo & 7) << 1);
+  f32x4 o[2];
+#pragma unroll
+  for (int dd = 0; dd < 2; ++dd) o[dd] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int dd = 0; dd < 2; ++dd) {
+      const int ch = (2 * (2 * w + dd) + (tp >> 1)) ^ vswz;
+      const char* a0 = Vs + (ks * 32 + vrow_lo) * 256 + (ch << 4) + 8 * (tp & 1);
+      const s16x4 lo = tr_read(a0);
+      const s16x4 hi = tr_read(a0 + 16 * 256);
+      typedef short s16x8 __attribute__((ext_vector_type(8)));
+      const s16x8 cat = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      o[dd] = mfma16(__builtin_bit_cast(frag_t, cat), pf[ks], o[dd]);
+    }
+  if (fc < n_rep) {
+#pragma unroll
+    for (int dd = 0; dd < 2; ++dd) *reinterpret_cast<f32x4*>(wsb + (2 * w + dd) * 16 + fg * 4) = o[dd];
+    if (w == 0 && fg == 0) { wsb[128] = mx; wsb[129] = l; }
   }
 #if OMCHAT_EXPERIMENTS
   if (p.dbg && kvh == 0 && lane == 0) atomicMax(p.dbg + 11, wall_clock64());
@@ -1713,6 +1904,8 @@ int launch_kv_quant(int dtype, const void* kc, const void* vc, void* k8, void* v
 
 int g_attn_kv8_tpw = 0;     // omchat_op_set_tuning key 47: 64-key tiles per wave of the decode attention over the e4m3 cache (attn_decode_kv8_walk_kernel): 0 = by the launch's size, 1 = one wave per tile (attn_decode_kernel), 2 / 3 / 4 forced, 11 = 3 tiles per wave x 4 waves per workgroup folded in LDS
 void attn_set_kv8_tpw(int v) { g_attn_kv8_tpw = v < 0 || v > 15 ? 0 : v; }
+int g_attn_4w = 1;      // omchat_op_set_tuning key 52: the unmasked one-tile decode attention over the 16-bit cache: 1 = four waves per tile at batch 1 (attn_decode_4w_kernel), 0 = one wave per tile (attn_decode_kernel), 2 = four waves at every batch size
+void attn_set_4w(int v) { g_attn_4w = v < 0 || v > 2 ? 1 : v; }
 int g_attn_tpw = 0;     // omchat_op_set_tuning key 10: key tiles per wave of the decode attention (0 = by grid size; 1, 2, 4 force)
 void attn_set_tpw(int v) { g_attn_tpw = v < 0 ? 0 : v; }
 int g_merge_dg = 1;       // omchat_op_set_tuning key 21: split-KV merge, column groups per head: 0 = none, 1 = 4 groups beyond 256 partials (default), 2 = also 2 groups for 65..256
@@ -1948,7 +2141,7 @@ int launch_attn_merge(int dtype, const float* ws, int nsplit, int q_heads, int r
 }
 
 // what launch_attn_decode's plan decided; launch_decode_form turns it into the attention kernel (first match wins) and the merge
-struct DecodeForm { bool masked, kv8, kv8_fuse, dma; int tpw, kv8_nw, dma_lds, nsplit, split_keys; };
+struct DecodeForm { bool masked, kv8, kv8_fuse, dma, w4; int tpw, kv8_nw, dma_lds, nsplit, split_keys; };
 template <typename T>
 static void launch_decode_form(const AttnDecodeArgs& a, const DecodeForm& f, dim3 grid, const AttnP& p, hipStream_t s) {
   if (f.masked && f.kv8) hipLaunchKernelGGL((attn_decode_kernel<T, true, true>), grid, dim3(64), 0, s, p);
@@ -1965,6 +2158,7 @@ static void launch_decode_form(const AttnDecodeArgs& a, const DecodeForm& f, dim
   else if (f.dma) hipLaunchKernelGGL((attn_decode_dma_kernel<T, 4>), grid, dim3(64), f.dma_lds, s, p);
   else if (f.tpw > 1 && g_attn_klds) hipLaunchKernelGGL((attn_decode_multi_kernel<T, true>), grid, dim3(64), 0, s, p);
   else if (f.tpw > 1) hipLaunchKernelGGL((attn_decode_multi_kernel<T, false>), grid, dim3(64), 0, s, p);
+  else if (f.w4) hipLaunchKernelGGL(attn_decode_4w_kernel<T>, grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((attn_decode_kernel<T, false>), grid, dim3(64), 0, s, p);
   launch_merge<T>(a.ws, f.nsplit, a.q_heads, a.batch, a.kv_len, a.L, p.c, a.O, a.o_sb, a.o_sh, a.o_pack_nb, f.split_keys, s,
                   MergeDone{a.done_flags, a.done_epoch, a.done_mode, a.done_dbg});
@@ -2029,7 +2223,9 @@ int launch_attn_decode(int dtype, const AttnDecodeArgs& a, hipStream_t s) {
   const int dma_lds = std::min(65536, std::max(g_attn_dma_stages * 16384, (160 / dma_slots) * 1024));
   dim3 grid(nsplit, a.kv_heads, a.batch);
   if (a.done_flags && (a.batch != 1 || nsplit > 64 || nsplit > g_merge_mid_min)) { omchat_set_error("launch_attn_decode: completion flags exist for the one-round-trip merge only (batch 1, <= 64 splits)"); return 1; }
-  const DecodeForm f{a.key_mask != nullptr, kv8, kv8_fuse, dma, tpw, kv8_nw, dma_lds, nsplit, split_keys};
+  // the one-tile form of a single sequence is at most about one wave per CU: four waves share the tile (same bits)
+  const bool w4 = !kv8 && !a.key_mask && !dma && tpw == 1 && (g_attn_4w == 2 || (g_attn_4w == 1 && a.batch == 1));
+  const DecodeForm f{a.key_mask != nullptr, kv8, kv8_fuse, dma, w4, tpw, kv8_nw, dma_lds, nsplit, split_keys};
   if (dtype == OMCHAT_F16) launch_decode_form<f16>(a, f, grid, p, s);
   else if (dtype == OMCHAT_BF16) launch_decode_form<bf16>(a, f, grid, p, s);
   else { omchat_set_error("launch_attn_decode: bad dtype"); return 1; }

@@ -106,6 +106,7 @@ extern "C" int omchat_op_set_tuning(int key, int value) {
   if (key == 49) { model_set_extend_attn(value); return 0; }
   if (key == 50) { model_set_x12_roles(value); return 0; }
   if (key == 51) { model_set_suffix_attn(value); return 0; }
+  if (key == 52) { attn_set_4w(value); return 0; }
   if (key == 38) { gemv_set_gu_rr(value); return 0; }
   if (key == 39) { gemv_set_longk_direct(value); return 0; }
   if (key == 40) { norm_set_wave(value); return 0; }

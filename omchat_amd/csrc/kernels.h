@@ -256,6 +256,7 @@ void attn_set_kg(int v);      // tuning key 36
 void attn_set_peel(int v);    // tuning key 46
 void attn_set_kv8_tpw(int v); // tuning key 47
 void attn_set_kv8_fuse(int v); // tuning key 48
+void attn_set_4w(int v);       // tuning key 52
 void model_set_extend_attn(int v); // tuning key 49
 void model_set_x12_roles(int v);   // tuning key 50
 void model_set_suffix_attn(int v); // tuning key 51

@@ -1,6 +1,6 @@
 """Kernel-level A/B of the batched decode attention (attention + merge launches) at the configs[2] shape: b sequences x 4 kv heads x L keys.
    python tools/bench_attn_decode.py [b] [L]     prints us per call for the register multi-tile form and the LDS-DMA ring form at several
-   slot counts (tuning keys 25 / 26)."""
+   slot counts (tuning keys 25 / 26).  b = 1 also times the one-tile form with one wave per tile against four (tuning key 52), two alternating passes."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -46,3 +46,35 @@ for name, dma, slots, rot in (("register form", 0, 4, 0), ("dma ring, 4 slots x 
     if ref is None: ref = o
     print(f"b {b} L {L} cap {cap} ({mb:.0f} MB)  {name:34s} {us:7.2f} us per attention + merge   ({mb / us / 1e3 * 1e3:.0f} GB/s incl. merge)   max |diff| vs first {float((o - ref).abs().max()):.3e}")
 lib.omchat_op_set_tuning(25, 1); lib.omchat_op_set_tuning(26, 0); lib.omchat_op_set_tuning(27, 0); lib.omchat_op_set_tuning(10, 0)
+if b == 1:
+    # launches from Python arrive slower than these kernels run: the timed window is a captured chain of 200 attention + merge pairs, replayed
+    import ctypes
+    lib.omchat_op_set_tuning(25, 0)
+    st = torch.cuda.Stream()
+    sp = ctypes.c_void_p(st.cuda_stream)
+    graphs = {}
+    for w4 in (0, 1):
+        lib.omchat_op_set_tuning(52, w4)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=st):
+            for i in range(200):
+                kk, vv = (k, v) if i & 1 else (k2, v2)
+                _lib.check(lib.omchat_op_attn_decode(1, P(q), P(kk), P(vv), P(out), b, Hq, Hkv, cap, L, P(dl), 128 ** -0.5, P(ws), wsb, sp))
+        graphs[w4] = gr
+    ref = None
+    for name, w4 in (("one wave per tile (key 52 = 0)", 0), ("four waves per tile (key 52 = 1)", 1)) * 2:
+        gr = graphs[w4]
+        for _ in range(5): gr.replay()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(7):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10): gr.replay()
+            e1.record(); torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1000 / 2000)
+        o = out.view(torch.int16).clone()
+        if ref is None: ref = o
+        us.sort()
+        print(f"b {b} L {L} cap {cap}  {name:34s} {us[3]:7.2f} us per attention + merge, median of 7 windows of 2000 pairs [{us[0]:.2f}, {us[-1]:.2f}]   output bits equal to first: {bool(torch.equal(o, ref))}")
+    lib.omchat_op_set_tuning(25, 1); lib.omchat_op_set_tuning(52, 1)

@@ -60,7 +60,7 @@ def label(seq):
         if f == "attn2_kernel":
             ctx = "pre" if e == 1 else "vit"
             out[i] = "prefill attention (causal GQA)" if e == 1 else "ViT attention (MHA)"
-        elif f in ("attn_decode_kernel", "attn_decode_dma_kernel", "attn_decode_multi_kernel", "attn_decode_kv8_walk_kernel"):
+        elif f in ("attn_decode_kernel", "attn_decode_4w_kernel", "attn_decode_dma_kernel", "attn_decode_multi_kernel", "attn_decode_kv8_walk_kernel"):
             ctx = "dec"
             out[i] = "decode attention (split-KV)"
         elif f in ("attn_merge_kernel", "attn_merge_mid_kernel"):
