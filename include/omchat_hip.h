@@ -278,6 +278,39 @@ int omchat_set_dola(omchat_ctx* ctx, int b, const int32_t* layers, int k, float 
 int omchat_dola_read(omchat_ctx* ctx, int32_t* out, int rows, int steps);
 /* test hook: the raw rows of the last prefill or step, host fp32 [(k + 1) b][V].  Synchronises the device. */
 int omchat_dola_rows(omchat_ctx* ctx, float* out);
+/* ---- contrastive search (generate(penalty_alpha=, top_k=)) ----------------------------------------------------------- */
+/* omchat_set_contrastive: HF 4.4x's _contrastive_search (Su et al., "A Contrastive Framework for Neural Text Generation") for ONE sequence.
+ * 2 <= k <= min(OMCHAT_CS_MAX_K, max_batch) candidates per token, 0 < alpha <= 1, max_new emitted ids at most, share != 0: the k rows share
+ * the prompt's cache slots (omchat_group_begin's share), eos_ids: up to 8 host ids.  k = 0 switches the mode off.  Call it BEFORE the
+ * prefill: while it is on, omchat_prefill with b = 1 also keeps the post-final-norm hidden rows of all its P positions as the history
+ * (16-bit rows [P + max_new][hidden] and one fp32 inverse L2 norm per row) and refuses P + max_new > max_seq before any work.
+ * omchat_contrastive_step(logits, rows, next_tokens, done_word): the FIRST call after the prefill takes the prefill's logits with
+ * rows = 1: the k largest ids of the row (ties to the lower id) with their fp32 softmax probabilities are the candidates, the prompt row is
+ * forked or shared into rows 0..k-1 (omchat_group_begin), next_tokens[0..k) = the candidates, next_tokens[k] = -1.  The caller then runs
+ * omchat_decode_step with those k tokens and b = k (eager or through the decode graph) and hands its logits [k][V] to the next call with
+ * rows = k: pen_i = max_j cos(h_i, history_j) over the step's final-normed rows, pick = the first maximum of (1 - alpha) p_i - alpha pen_i,
+ * next_tokens[k] = the emitted id, *done_word (device, or NULL) = 1 when that id is an EOS id or max_new ids are out, else 0; the picked
+ * row's hidden state joins the history, the ONE new cache slot of the picked row is copied to the other rows, and next_tokens[0..k) are the
+ * next candidates from logits row `pick`.  Nothing synchronises with the host.  One record per emitted id stays on the device
+ * (omchat_contrastive_read).  Afterwards every row holds prompt + emitted ids; omchat_group_begin with b = 0 and omchat_set_contrastive
+ * with k = 0 leave row 0 as a plain sequence.
+ * Refused here, before anything changes: a tensor-parallel context, the e4m3 KV cache, fp8 prefill GEMMs, MXFP4 decode mode 1 (batch-1
+ * steps only), an active beam search, guidance, layer-contrastive decoding, a token FSM, constraints, logprobs, sampling, a sampled group,
+ * k or alpha out of range, a hidden size that is no multiple of 32.  Refused while it is on, before anything is enqueued: omchat_beam_begin,
+ * omchat_decode_verify, omchat_set_guidance, omchat_set_dola, omchat_fsm_begin, omchat_set_constraints, omchat_set_logprobs,
+ * omchat_set_sampling, both masked steps, omchat_prefill_left, omchat_prefill_extend, omchat_prefill_suffixes, a prefill of b > 1, a
+ * foreign omchat_group_begin and a decode step of other than k rows.  Deterministic: no float atomics, fixed reduction orders. */
+#define OMCHAT_CS_MAX_K 16
+#define OMCHAT_CS_REC_WORDS 52
+int omchat_set_contrastive(omchat_ctx* ctx, int k, double alpha, int max_new, int share, const int32_t* eos_ids, int n_eos, void* stream);
+int omchat_contrastive_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* next_tokens, int32_t* done_word, void* stream);
+/* the record: out host int32 [steps][OMCHAT_CS_REC_WORDS] -- words [0, 16) the candidates' ids, [16, 32) their probabilities and [32, 48)
+ * their penalties (fp32 bits), [48] the pick (the selected candidate's rank), [49] the emitted id, [50] the penalty launch's chunks, [51] the
+ * history's rows at that pick.  steps <= the picks since the prefill.  Synchronises the device. */
+int omchat_contrastive_read(omchat_ctx* ctx, int32_t* out, int steps);
+/* test hook: rows [row0, row0 + n) of the history (host, 16-bit [n][hidden]; or NULL), their inverse norms (host fp32 [n]; or NULL) and
+ * the final-normed rows of the last k-row step in row-major order (host, 16-bit [k][hidden]; or NULL).  Synchronises the device. */
+int omchat_contrastive_rows(omchat_ctx* ctx, int row0, int n, void* hist_out, float* inv_out, void* cand_out);
 /* ---- per-token log-probabilities of the picked ids (generate(output_logprobs=True)) ---------------------------------- */
 /* omchat_set_logprobs: from now on every token pick of rows 0..b-1 of this context -- omchat_greedy, omchat_sample, omchat_decode_step, both
  * masked steps, the captured decode graph -- also records two fp32 numbers on the device, without a host sync: raw = log_softmax(logits)[id]
@@ -896,6 +929,28 @@ int omchat_op_fsm(int n_states, const int32_t* off, const int32_t* tok, const in
  * synchronise. */
 size_t omchat_op_guidance_ws(int b, int V);
 int omchat_op_guidance(const float* logits, int ld, int b, int V, float scale, void* ws, float* out, int ld_out, void* stream);
+
+/* context-free launches of contrastive search (test hooks; the launchers omchat_contrastive_step calls).  dtype: OMCHAT_DTYPE of the 16-bit
+ * rows.  None synchronises.
+ * plan: the penalty launch's cut of L history rows on this device: chunk c covers rows [c * rows_per_chunk, min(L, (c + 1) * rows_per_chunk)).
+ * penalty: hist device [L][H], inv device fp32 [L] (with compute_norms != 0 it is written first, by the launch the prefill uses), cand
+ *   device k rows, row-major (cand_nb = 0) or in the packed x layout with cand_nb blocks of 16 rows; part device fp32 [chunks][16] receives
+ *   the partial maxima, cand_inv device fp32 [16] the candidates' inverse norms.  H % 32 == 0.
+ * topk: logits device fp32 rows of stride ld, row *row_sel (device int32; NULL = row 0), V <= ld ids (columns at or beyond V are never
+ *   read); ids device int32 [k], probs device fp32 [k]; ws device memory of omchat_op_contrastive_topk_ws(V) bytes, 8-byte aligned.
+ * select: folds part [chunks][16], scores, picks and commits: out device int32 [OMCHAT_CS_REC_WORDS] the record; hist / inv (or NULL, NULL):
+ *   the picked row of cand and cand_inv[pick] are appended at row n_hist; parents device int32 [k], sel / token / done_word device int32
+ *   (each may be NULL). */
+int omchat_op_contrastive_plan(int L, int* chunks, int* rows_per_chunk);
+int omchat_op_contrastive_penalty(int dtype, void* hist, float* inv, int compute_norms, int L, int H, const void* cand, int cand_nb, int k,
+                                  float* part, float* cand_inv, void* stream);
+size_t omchat_op_contrastive_topk_ws(int V);
+int omchat_op_contrastive_topk(const float* logits, int ld, const int32_t* row_sel, int V, int k, int32_t* ids, float* probs, void* ws,
+                               void* stream);
+int omchat_op_contrastive_select(int dtype, const float* part, int chunks, int k, double alpha, const int32_t* ids, const float* probs,
+                                 const float* cand_inv, const void* cand, int cand_nb, int H, void* hist, float* inv, int n_hist,
+                                 const int32_t* eos_ids, int n_eos, int last, int32_t* rec, int32_t* parents, int32_t* sel, int32_t* token,
+                                 int32_t* done_word, void* stream);
 
 /* context-free stage of omchat_set_dola (test hook): logits device fp32 [(k + 1) b][ld] in the row order given there, V <= ld ids per row (any
  * V; 16-byte accesses when ld % 4 == 0 and the base is aligned, scalar ones otherwise); out device fp32 [b][ld_out], ld_out >= V; picked

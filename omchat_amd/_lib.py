@@ -30,7 +30,7 @@ class OmchatError(RuntimeError):
     pass
 
 
-_vp, _i, _f, _i64, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64, C.c_size_t
+_vp, _i, _f, _d, _i64, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64, C.c_uint64, C.c_size_t
 _SIGS = {
     "omchat_last_error": (C.c_char_p, []),
     "omchat_version": (C.c_char_p, []),
@@ -66,6 +66,15 @@ _SIGS = {
     "omchat_dola_read": (_i, [_vp, _vp, _i, _i]),
     "omchat_dola_rows": (_i, [_vp, _vp]),
     "omchat_op_dola_ws": (_sz, [_i, _i, _i]),
+    "omchat_set_contrastive": (_i, [_vp, _i, _d, _i, _i, _vp, _i, _vp]),
+    "omchat_contrastive_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "omchat_contrastive_read": (_i, [_vp, _vp, _i]),
+    "omchat_contrastive_rows": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "omchat_op_contrastive_plan": (_i, [_i, _vp, _vp]),
+    "omchat_op_contrastive_penalty": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "omchat_op_contrastive_topk_ws": (_sz, [_i]),
+    "omchat_op_contrastive_topk": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "omchat_op_contrastive_select": (_i, [_i, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_dola": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _sz, _vp]),
     "omchat_kv_lengths": (_i, [_vp, _vp, _i]),
     "omchat_kv_rewind": (_i, [_vp, _i, _i, _vp]),

@@ -6,7 +6,7 @@ SRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libomchat_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["gemm.hip", "gemv.hip", "attention.hip", "elementwise.hip", "preproc.hip", "model.hip", "pick.hip", "capi.hip", "comm.hip", "sample.hip", "beam.hip", "constrain.hip", "logprob.hip", "score.hip", "fsm.hip", "guidance.hip", "dola.hip"]
+SOURCES = ["gemm.hip", "gemv.hip", "attention.hip", "elementwise.hip", "preproc.hip", "model.hip", "pick.hip", "capi.hip", "comm.hip", "sample.hip", "beam.hip", "constrain.hip", "logprob.hip", "score.hip", "fsm.hip", "guidance.hip", "dola.hip", "contrastive.hip"]
 # measured-negative experiment kernels (one-launch decode layer, fused attention + o_proj): NOT part of the product library -- compiled only
 # into the `--twin ... -DOMCHAT_EXPERIMENTS=1` build that the experiment tests and tools load through OMCHAT_LIB
 EXPERIMENT_SOURCES = ["experiments/fused_decode.hip", "experiments/decode_layer.hip"]

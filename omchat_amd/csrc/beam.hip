@@ -431,6 +431,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_CHECK(!ctx->pick.fsm_on(), "beam search: a token FSM is on (omchat_fsm_begin with b = 0 first); each beam row would need its parent's state");
   OM_CHECK(!ctx->pick.guidance_on(), "beam search: guidance is on (omchat_set_guidance with b = 0 first); each beam row would need its twin");
   OM_CHECK(!ctx->pick.dola_on(), "beam search: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); each beam row would need its candidate rows");
+  OM_CHECK(!ctx->contrastive_on(), "beam search: contrastive search is on (omchat_set_contrastive with k = 0 first); its k rows are one sequence's candidates");
   OM_CHECK(b * N <= c.max_batch, "beam search: b * num_beams exceeds max_batch");
   OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "beam search: at most 8 eos ids");
   const int KB = std::max(2, 1 + n_eos) * N;
@@ -490,6 +491,7 @@ extern "C" int omchat_group_begin(omchat_ctx* ctx, int b, int N, int prompt_len,
   OM_CHECK(!ctx->beam.on(), "sampled group: a beam search is active");
   OM_CHECK(!ctx->pick.guidance_on(), "sampled group: guidance is on (omchat_set_guidance with b = 0 first); each sibling row would need its twin");
   OM_CHECK(!ctx->pick.dola_on(), "sampled group: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); each sibling row would need its candidate rows");
+  OM_CHECK(!ctx->contrastive_on() || (!ctx->cs.forked && b == 1 && N == ctx->cs.k), "sampled group: contrastive search is on and forks its own k rows (omchat_set_contrastive with k = 0 first)");
   OM_CHECK(b * N <= c.max_batch, "sampled group: b * N exceeds max_batch");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "sampled group: a left-padded or masked-decode batch (pad equal or use b = 1)");
   OM_CHECK(prompt_len >= 1 && prompt_len < c.max_seq, "sampled group: prompt_len outside [1, max_seq)");

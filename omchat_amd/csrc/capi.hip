@@ -848,6 +848,37 @@ extern "C" int omchat_op_guidance(const float* logits, int ld, int b, int V, flo
   return launch_guidance(logits, ld, b, V, scale, ws, out, ld_out, S(stream));
 }
 
+static_assert(OMCHAT_CS_MAX_K == CS_KMAX && OMCHAT_CS_REC_WORDS == CS_REC_WORDS, "contrastive search: the public header's caps");
+extern "C" int omchat_op_contrastive_plan(int L, int* chunks, int* rows_per_chunk) {
+  OM_CHECK(L >= 1 && chunks && rows_per_chunk, "contrastive plan: L >= 1");
+  cs_plan(L, device_cus(), chunks, rows_per_chunk);
+  return 0;
+}
+extern "C" int omchat_op_contrastive_penalty(int dtype, void* hist, float* inv, int compute_norms, int L, int H, const void* cand, int cand_nb, int k,
+                                             float* part, float* cand_inv, void* stream) {
+  if (compute_norms) { const int rc = launch_cs_norms(dtype, hist, L, H, inv, S(stream)); if (rc) return rc; }
+  return launch_cs_penalty(dtype, hist, inv, L, H, cand, cand_nb, k, part, cand_inv, S(stream));
+}
+extern "C" size_t omchat_op_contrastive_topk_ws(int V) { return V >= 1 ? cs_topk_ws_bytes(V) : 0; }
+extern "C" int omchat_op_contrastive_topk(const float* logits, int ld, const int32_t* row_sel, int V, int k, int32_t* ids, float* probs, void* ws,
+                                          void* stream) {
+  return launch_cs_topk(logits, ld, row_sel, V, k, ids, probs, ws, S(stream));
+}
+extern "C" int omchat_op_contrastive_select(int dtype, const float* part, int chunks, int k, double alpha, const int32_t* ids, const float* probs,
+                                            const float* cand_inv, const void* cand, int cand_nb, int H, void* hist, float* inv, int n_hist,
+                                            const int32_t* eos_ids, int n_eos, int last, int32_t* rec, int32_t* parents, int32_t* sel, int32_t* token,
+                                            int32_t* done_word, void* stream) {
+  OM_CHECK(n_eos >= 0 && n_eos <= CS_EOS_MAX && (n_eos == 0 || eos_ids), "contrastive select: at most 8 eos ids");
+  CsSelectArgs a;
+  a.part = part; a.chunks = chunks; a.k = k; a.alpha = (float)alpha; a.one_minus_alpha = (float)(1.0 - alpha);
+  a.ids = ids; a.probs = probs; a.cand_inv = cand_inv; a.cand = cand; a.cand_nb = cand_nb; a.H = H;
+  a.hist = hist; a.inv = inv; a.n_hist = n_hist;
+  a.n_eos = n_eos;
+  for (int q = 0; q < n_eos; ++q) a.eos[q] = eos_ids[q];
+  a.last = last; a.rec = rec; a.parents = parents; a.sel = sel; a.token = token; a.done_word = done_word;
+  return launch_cs_select(dtype, a, S(stream));
+}
+
 extern "C" size_t omchat_op_dola_ws(int b, int k, int V) { return b >= 1 && k >= 1 && V >= 1 ? dola_ws_bytes(b, k, V) : 0; }
 
 extern "C" int omchat_op_dola(const float* logits, int ld, int V, int b, int k, float relative_top, float* out, int ld_out, int32_t* picked, void* ws,

@@ -170,6 +170,27 @@ struct GroupState {
   void release() { ws.release(); }
 };
 
+// contrastive search (omchat_set_contrastive; contrastive.hip): the history H_ctx of post-final-norm hidden rows
+// [cap][t_hidden] (16-bit) with one fp32 inverse L2 norm per row, the candidates of the next k-row step (ids, probabilities), the partial
+// maxima of the penalty launch (part), the top-k's tile partials (tk_ws), the parents / selected row of the last pick, the per-step record
+// and the one-slot stash of the KV gather.
+// n_hist: rows of the history (host; P after the prefill, + 1 per pick); t: picks made; forked: the prompt row was forked / shared into k rows
+struct ContrastiveState {
+  bool on = false, share = false; int k = 0, max_new = 0; float alpha = 0.f, one_minus = 1.f;      // (one_minus: fp32(1 - alpha), as torch rounds the scalar)
+  std::vector<int> eos;
+  int cap = 0, n_hist = 0, t = 0, P = 0;
+  bool have_hist = false, forked = false;
+  Grown hist, inv, part, tk_ws, small, rec, stash;
+  // `small` (int32 words): [0, 16) candidate ids, [16, 32) candidate probabilities, [32, 48) inverse norms of the step's rows, [48, 64) parents,
+  // [64] the selected row
+  int32_t* cand_ids() const { return (int32_t*)small.p; }
+  float* cand_probs() const { return (float*)small.p + 16; }
+  float* cand_inv() const { return (float*)small.p + 32; }
+  int* parents() const { return (int*)small.p + 48; }
+  int* sel() const { return (int*)small.p + 64; }
+  void release() { for (Grown* g : {&hist, &inv, &part, &tk_ws, &small, &rec, &stash}) g->release(); }
+};
+
 struct omchat_ctx {
   omchat_config c;
   int dt = OMCHAT_BF16;
@@ -282,6 +303,8 @@ struct omchat_ctx {
   PickState pick;
   BeamState beam;
   GroupState group;
+  ContrastiveState cs;
+  bool contrastive_on() const { return cs.on; }
   Grown ext_ws;      // partials of the split-KV block attention (omchat_prefill_extend)
   Grown score_ws;    // (max, sum) planes and target logits of teacher-forced scoring (omchat_score_hidden)
   int grow(Grown& g, size_t n) {
@@ -464,6 +487,7 @@ inline void use_weight_x12(GemvArgs& g, const omchat_ctx::X12Ref& r, int K) {
 }
 
 // ---- model.hip
+int decode_x_pack_nb(const omchat_ctx* ctx, int rows);      // blocks of 16 rows of the packed x layout a decode step of `rows` rows leaves its norm buffer in (0: row-major)
 void drop_decode_graphs(omchat_ctx* ctx);      // pick parameters live in the kernel arguments of the captured decode graphs: a change drops them
 
 // ---- pick.hip: what model.hip knows of the pick pipeline
@@ -492,3 +516,8 @@ const char* pick_rows_refusal(omchat_ctx* ctx, int rows);
 // layer-contrastive decoding (omchat_set_dola): why this context's state does not go with it, or NULL -- asked by the setter and again by
 // every prefill and step while it is on (the replica switches may have come later)
 const char* dola_state_refusal(const omchat_ctx* ctx);
+
+// ---- contrastive.hip
+const char* contrastive_state_refusal(const omchat_ctx* ctx);      // why this context's state does not go with contrastive search, or NULL
+int contrastive_prefill_admit(omchat_ctx* ctx, int P);      // a b = 1 prefill while the mode is on, before anything is enqueued: the history's room
+int contrastive_prefill_keep(omchat_ctx* ctx, const void* x, int P, hipStream_t s);      // ... behind its last layer: the history and its inverse norms

@@ -615,6 +615,35 @@ struct DolaArgs {
 };
 size_t dola_ws_bytes(int b, int k, int V);
 int launch_dola(const DolaArgs& a, hipStream_t s);
+// contrastive search (contrastive.hip; tests/contrastive_ref.py restates it).  Deterministic: fixed orders, no atomics.
+constexpr int CS_KMAX = 16;              // candidates per step
+constexpr int CS_EOS_MAX = 8;
+constexpr int CS_REC_WORDS = 52;         // a step's record: ids [16], probabilities [16], penalties [16], the pick, the emitted id, chunks, history rows
+// the penalty launch's cut of L history rows into chunks of rows_per_chunk rows (a multiple of 16; one wave per chunk, up to 4 per CU)
+void cs_plan(int L, int cus, int* chunks, int* rows_per_chunk);
+// inv[r] = 1 / ||rows[r]||_2 in fp32 for n 16-bit rows [n][H] (H % 8 == 0)
+int launch_cs_norms(int dtype, const void* rows, int n, int H, float* inv, hipStream_t s);
+// part[c * 16 + i] = max over the history rows j of chunk c of dot(cand_i, hist_j) * inv[j] * inv_c[i]; cand: k 16-bit rows, row-major [k][H]
+// (cand_nb = 0) or in the packed x layout of common.h with cand_nb blocks of 16 rows; cand_inv [k] receives inv_c.  H % 32 == 0, L >= 1.
+int launch_cs_penalty(int dtype, const void* hist, const float* inv, int L, int H, const void* cand, int cand_nb, int k, float* part,
+                      float* cand_inv, hipStream_t s);
+// ids / probs [k]: the k largest of row (row_sel ? *row_sel : 0) of fp32 logits [rows][ld] by (value descending, id ascending) and their
+// softmax probabilities under the fp32 (max, sum exp) of the row's V ids; columns at or beyond V are never read.  ws: cs_topk_ws_bytes(V)
+size_t cs_topk_ws_bytes(int V);
+int launch_cs_topk(const float* logits, int ld, const int* row_sel, int V, int k, int32_t* ids, float* probs, void* ws, hipStream_t s);
+// the fold of the partial maxima, the scores (1 - alpha) p_i - alpha pen_i, the pick (the first maximum), the emitted id and the done word
+// (an EOS id, or `last`), the append of the picked row and its inverse norm to the history at row n_hist, the step's record, parents[r] = pick
+struct CsSelectArgs {
+  const float* part = nullptr; int chunks = 0, k = 0;
+  float alpha = 0.f, one_minus_alpha = 1.f;
+  const int32_t* ids = nullptr; const float* probs = nullptr; const float* cand_inv = nullptr;
+  const void* cand = nullptr; int cand_nb = 0, H = 0;
+  void* hist = nullptr; float* inv = nullptr; int n_hist = 0;
+  int eos[CS_EOS_MAX] = {0}; int n_eos = 0; int last = 0;
+  int32_t* rec = nullptr;                  // the step's CS_REC_WORDS words (or NULL)
+  int* parents = nullptr; int* sel = nullptr; int32_t* token = nullptr; int32_t* done_word = nullptr;      // (each may be NULL)
+};
+int launch_cs_select(int dtype, const CsSelectArgs& a, hipStream_t s);
 // beam search (beam.hip; tests/beam_ref.py restates it).  The vocabulary is cut into beam_slices(V, tp) equal slices
 // of at most BEAM_SLICE_CAP ids, the same at every TP degree; a rank owns ns / tp whole slices.  Exchange table: [rows][ns][4 + 2K] fp32.
 constexpr int BEAM_KMAX = 32;            // candidates kept per step and prompt: max(2, 1 + n_eos) * N

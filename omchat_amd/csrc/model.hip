@@ -372,7 +372,7 @@ extern "C" void omchat_ctx_destroy(omchat_ctx* ctx) {
   if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
   if (ctx->stage_f32) hipFree(ctx->stage_f32);
   if (ctx->stage_t) hipFree(ctx->stage_t);
-  ctx->beam.release(); ctx->group.release(); ctx->ext_ws.release(); ctx->score_ws.release(); ctx->pick.release();
+  ctx->beam.release(); ctx->group.release(); ctx->cs.release(); ctx->ext_ws.release(); ctx->score_ws.release(); ctx->pick.release();
   delete ctx;
 }
 
@@ -1214,6 +1214,13 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
     OM_CHECK(b == D.b, "layer-contrastive decoding is on: a prefill takes exactly the b rows omchat_set_dola was given");
     if (const char* why = dola_state_refusal(ctx)) OM_CHECK(false, why);
   }
+  // contrastive search: the b = 1 prefill keeps the post-final-norm rows of all its positions as the history
+  const bool cs = ctx->contrastive_on();
+  if (cs) {
+    OM_CHECK(!left && keep == 0 && !sfx, "contrastive search is on: a left-padded prefill, prefill_extend and the suffix pass are not implemented with it (omchat_set_contrastive with k = 0 first)");
+    OM_CHECK(b == 1, "contrastive search is on: a prefill takes exactly one row (omchat_set_contrastive with k = 0 first)");
+    TRY(contrastive_prefill_admit(ctx, lengths[0]));
+  }
   hipStream_t s = (hipStream_t)stream;
   if (ctx->fp8_prefill) TRY(build_replica(ctx, OMCHAT_WFMT_E4M3));      // weights were reloaded: re-quantise in place
   const int H = c.t_hidden, It = c.t_mlp, rows = b * S, qkvd = ctx->t_qkvdim, qd = ctx->t_qdim;
@@ -1327,6 +1334,7 @@ static int prefill_impl(omchat_ctx* ctx, const void* embeds, int b, int S, const
   }
   TRY(sp_drain(ctx, s));
   if (hidden_out) TRY(launch_rmsnorm(ctx->dt, x, H, ctx->t_norm, hidden_out, H, rows, H, c.t_eps, s));
+  if (cs) TRY(contrastive_prefill_keep(ctx, x, lengths[0], s));
   if (dola) {
     TRY(launch_gather_rows(ctx->dt, ctx->d_idx, x, nullptr, ctx->tw_last, b, H, s));
     TRY(dola_head(ctx, ctx->tw_last, logits_last, s));
@@ -1374,6 +1382,7 @@ extern "C" int omchat_prefill_extend(omchat_ctx* ctx, const void* embeds, int S_
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(ctx->tp_size == 1, "prefill_extend: tensor-parallel contexts are not implemented (DESIGN.md section 7)");
   OM_CHECK(!ctx->pick.dola_on(), "prefill_extend: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); the kept slots' candidate rows are gone");
+  OM_CHECK(!ctx->contrastive_on(), "prefill_extend: contrastive search is on (omchat_set_contrastive with k = 0 first); the kept slots' hidden rows are gone");
   OM_CHECK(!ctx->fp8_kv, "prefill_extend: the e4m3 KV cache is not implemented (DESIGN.md section 7): omchat_enable_fp8_kv(ctx, 0)");
   OM_CHECK(!ctx->fp8_prefill, "prefill_extend: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
   OM_CHECK(!ctx->left_padded, "prefill_extend: the cache holds a left-padded batch");
@@ -1398,6 +1407,7 @@ extern "C" int omchat_prefill_suffixes(omchat_ctx* ctx, const void* embeds, int 
   OM_CHECK(c.t_layers > 0, "context has no decoder");
   OM_CHECK(ctx->tp_size == 1, "prefill_suffixes: tensor-parallel contexts are not implemented (DESIGN.md section 7)");
   OM_CHECK(!ctx->pick.dola_on(), "prefill_suffixes: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); the suffix pass keeps no candidate rows");
+  OM_CHECK(!ctx->contrastive_on(), "prefill_suffixes: contrastive search is on (omchat_set_contrastive with k = 0 first); the suffix pass keeps no history rows");
   OM_CHECK(!ctx->fp8_kv, "prefill_suffixes: the e4m3 KV cache is not implemented (DESIGN.md section 7): omchat_enable_fp8_kv(ctx, 0)");
   OM_CHECK(!ctx->fp8_prefill, "prefill_suffixes: fp8 x fp8 prefill GEMMs are not implemented (DESIGN.md section 7): omchat_enable_fp8_prefill(ctx, 0)");
   OM_CHECK(!ctx->left_padded && ctx->dec_mode != 2, "prefill_suffixes: the cache holds a left-padded or masked-decode (padded batch) state");
@@ -1456,6 +1466,7 @@ static int step_format(const omchat_ctx* ctx, int rows, int* x_pack_nb = nullptr
   return omchat_decode_weight_format(rows, ctx->fp8_decode, ctx->mxfp4_mode, assume_packed16 || ctx->built(OMCHAT_WFMT_16_PACKED),
                                      c.t_hidden % 64 == 0 && ctx->t_qdim % 64 == 0 && c.t_mlp % 64 == 0, x_pack_nb);
 }
+int decode_x_pack_nb(const omchat_ctx* ctx, int rows) { int nb = 0; (void)step_format(ctx, rows, &nb); return nb; }
 static bool is_mxfp4(int fmt) { return fmt == OMCHAT_WFMT_MXFP4 || fmt == OMCHAT_WFMT_MXFP4_PACKED; }
 
 // Every replica a step of `rows` rows may stream is built and current -- called by the step entries before pick_admit, before any
@@ -1815,6 +1826,10 @@ extern "C" int omchat_decode_step(omchat_ctx* ctx, const int32_t* tokens, int b,
   if (const char* why = pick_rows_refusal(ctx, b)) OM_CHECK(false, why);
   if (ctx->pick.dola_on())
     if (const char* why = dola_state_refusal(ctx)) OM_CHECK(false, why);
+  if (ctx->contrastive_on()) {
+    OM_CHECK(ctx->cs.forked && b == ctx->cs.k, "contrastive search is on: a step takes the top_k candidate rows the first omchat_contrastive_step handed back (omchat_set_contrastive with k = 0 first)");
+    if (const char* why = contrastive_state_refusal(ctx)) OM_CHECK(false, why);
+  }
   int Lmax = 0;
   OM_CHECK(!ctx->left_padded, "per-sequence decode after a left-padded prefill: use omchat_decode_step_masked (the reference positions such a "
                               "batch with sum(mask) - 1 and a per-row key mask, omchat_arch.py:61-70; DESIGN.md section 7)");
@@ -1902,6 +1917,7 @@ extern "C" int omchat_decode_verify(omchat_ctx* ctx, const int32_t* tokens, int 
   OM_CHECK(!ctx->pick.guidance_on(), "guidance is on: each verify row would need its twin (omchat_set_guidance with b = 0 first)");
   OM_CHECK(!ctx->pick.dola_on(), "layer-contrastive decoding is on: each verify row would need its candidate rows (omchat_set_dola with b = 0 first)");
   OM_CHECK(!ctx->beam.on(), "a beam search is active");
+  OM_CHECK(!ctx->contrastive_on(), "contrastive search is on: its k rows are one sequence's candidates (omchat_set_contrastive with k = 0 first)");
   OM_CHECK(!ctx->group.on(), "a sampled group shares its prompt: a verify step runs one sequence (omchat_group_begin with b = 0 first)");
   OM_CHECK(!ctx->pick.logprobs_on(), "logprobs are on: a verify step's picks are not recorded (omchat_set_logprobs with b = 0 first)");
   OM_CHECK(!(ctx->fp8_kv && ctx->kv8_valid), "the e4m3 KV cache is not implemented");
@@ -1946,6 +1962,7 @@ static int masked_common_checks(omchat_ctx* ctx, int b) {
   OM_CHECK(ctx->tp_size == 1, "masked decode: one GPU (under tensor parallelism right-padded batches take the per-sequence step)");
   OM_CHECK(!ctx->pick.guidance_on(), "masked decode: guidance is on, and its twin rows run at their own lengths (omchat_set_guidance with b = 0 first)");
   OM_CHECK(!ctx->pick.dola_on(), "masked decode: layer-contrastive decoding is on, and the padded-batch step keeps no candidate rows (omchat_set_dola with b = 0 first)");
+  OM_CHECK(!ctx->contrastive_on(), "masked decode: contrastive search is on, and its k rows run one unpadded sequence (omchat_set_contrastive with k = 0 first)");
   OM_CHECK(!ctx->group.on(), "masked decode: a sampled group shares its prompt, and the shared attention has no key mask (omchat_group_begin with b = 0 first)");
   OM_CHECK(ctx->pre_S + ctx->masked_steps + 1 <= c.max_seq, "KV cache full (max_seq)");
   if (!ctx->d_mask) {
@@ -2160,6 +2177,7 @@ extern "C" int omchat_kv_rewind(omchat_ctx* ctx, int b, int n, void* stream) {
   OM_CHECK(ctx && b >= 1 && b <= (int)ctx->h_len.size() && n >= 0, "bad argument");
   if (n == 0) return 0;
   // every refusal before anything is enqueued or changed: the sampler's counters, the constraint history and the KV lengths stay in step
+  OM_CHECK(!ctx->contrastive_on(), "contrastive search is on: its history and record have no rewind (omchat_set_contrastive with k = 0 first)");
   const char* why = pick_rewind_refusal(ctx, b, n);
   OM_CHECK(!why, why);
   if (ctx->dec_mode == 2) {

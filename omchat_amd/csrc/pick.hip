@@ -248,6 +248,7 @@ const char* pick_rows_refusal(omchat_ctx* ctx, int rows) {
 const char* dola_state_refusal(const omchat_ctx* ctx) {
   if (ctx->tp_size > 1) return "layer-contrastive decoding: one GPU (the vocabulary-parallel exchange of the log-sum-exps and divergences is not built)";
   if (ctx->beam.on()) return "layer-contrastive decoding: a beam search is active";
+  if (ctx->contrastive_on()) return "layer-contrastive decoding: contrastive search is on (omchat_set_contrastive with k = 0 first); each candidate row would need its layers' rows";
   if (ctx->pick.gd.on) return "layer-contrastive decoding: guidance is on (omchat_set_guidance with b = 0 first); the two stages write the same copy";
   if (ctx->group.on()) return "layer-contrastive decoding: a sampled group shares its prompt (omchat_group_begin with b = 0 first)";
   if (ctx->fp8_decode) return "layer-contrastive decoding: the e4m3 decode replica is on, and the head pass over the candidate rows is 16-bit only (omchat_enable_fp8_decode(ctx, 0) first)";
@@ -370,6 +371,7 @@ extern "C" int omchat_set_sampling(omchat_ctx* ctx, int b, uint64_t seed, float 
   p.on = b > 0;
   if (p.on) {
     OM_CHECK(b <= c.max_batch, "sampling: batch exceeds max_batch");
+    OM_CHECK(!ctx->contrastive_on(), "sampling: contrastive search is on (omchat_set_contrastive with k = 0 first); it is a deterministic strategy");
     OM_CHECK(temperature > 0.f && isfinite(temperature), "sampling: temperature must be a strictly positive float (greedy: do_sample=False)");
     OM_CHECK(top_k >= 0, "sampling: top_k >= 0 (0 = off)");
     OM_CHECK(top_p > 0.0 && top_p <= 1.0, "sampling: top_p in (0, 1] (1 = off)");
@@ -467,6 +469,7 @@ extern "C" int omchat_set_constraints(omchat_ctx* ctx, int b, int no_repeat_ngra
   OM_CHECK(min_new_tokens >= 0 && min_length >= 0, "constraints: min_new_tokens and min_length >= 0");
   OM_CHECK(prompt_ids && prompt_len && max_new >= 1, "constraints: prompt ids, per-row lengths and max_new >= 1");
   OM_CHECK(!ctx->beam.on(), "constraints: a beam search is active (the processors act on log-softmax scores there)");
+  OM_CHECK(!ctx->contrastive_on(), "constraints: contrastive search is on (omchat_set_contrastive with k = 0 first); its pick runs on no banned copy");
   int maxP = 0;
   for (int i = 0; i < b; ++i) {
     OM_CHECK(prompt_len[i] >= 0, "constraints: prompt_len >= 0");
@@ -534,6 +537,7 @@ extern "C" int omchat_set_logprobs_ex(omchat_ctx* ctx, int b, int max_new, int t
     return 0;
   }
   OM_CHECK(c.t_layers > 0, "context has no decoder");
+  OM_CHECK(!ctx->contrastive_on(), "logprobs: contrastive search is on (omchat_set_contrastive with k = 0 first); its record holds the candidates' probabilities");
   OM_CHECK(b <= c.max_batch, "logprobs: batch exceeds max_batch");
   OM_CHECK(max_new >= 1, "logprobs: max_new >= 1");
   OM_CHECK(!ctx->beam.on(), "logprobs: a beam search is active (it reports sequences_scores)");
@@ -679,6 +683,7 @@ extern "C" int omchat_fsm_begin(omchat_ctx* ctx, int b, const int32_t* start_sta
     return 0;
   }
   // every refusal before anything is enqueued or changed
+  OM_CHECK(!ctx->contrastive_on(), "token FSM: contrastive search is on (omchat_set_contrastive with k = 0 first); its pick runs on no masked copy");
   OM_CHECK(P.fsm_tab.n_states > 0, "token FSM: no table is loaded (omchat_fsm_load first)");
   OM_CHECK(b <= c.max_batch, "token FSM: batch exceeds max_batch");
   OM_CHECK(start_states && max_new >= 1, "token FSM: start states and max_new >= 1");
@@ -750,6 +755,7 @@ extern "C" int omchat_set_guidance(omchat_ctx* ctx, int b, float scale, void* st
   OM_CHECK(!ctx->beam.on(), "guidance: a beam search is active");
   OM_CHECK(!ctx->group.on(), "guidance: a sampled group shares its prompt (omchat_group_begin with b = 0 first)");
   OM_CHECK(!P.dola.on, "guidance: layer-contrastive decoding is on (omchat_set_dola with b = 0 first); the two stages write the same copy");
+  OM_CHECK(!ctx->contrastive_on(), "guidance: contrastive search is on (omchat_set_contrastive with k = 0 first); each candidate row would need its twin");
   void* old_copy = P.con_logits;
   if (!P.gd_ws) TRY(ctx->alloc(&P.gd_ws, guidance_ws_bytes(c.max_batch / 2, c.t_vocab)));
   if (!P.con_logits) TRY(ctx->alloc((void**)&P.con_logits, (size_t)c.max_batch * c.t_vocab * 4));

@@ -809,6 +809,106 @@ class Engine:
         torch.cuda.current_stream().synchronize()      # (ws is released when this returns)
         return out, picked
 
+    # ------------------------------------------------------------------ contrastive search (include/omchat_hip.h: omchat_set_contrastive)
+    def set_contrastive(self, k, alpha, max_new, share=False, eos=()):
+        """contrastive search for ONE sequence.  Call it BEFORE the b = 1 prefill, which then keeps its post-final-norm
+        hidden rows as the history; then contrastive_step(prefill logits), and per emitted id decode_step(candidates) +
+        contrastive_step(its logits).  Sticky until contrastive_off()."""
+        torch = _torch()
+        ev = torch.tensor([int(i) for i in eos] or [0], dtype=torch.int32)
+        check(self.lib.omchat_set_contrastive(self.h, int(k), float(alpha), int(max_new), int(bool(share)), ptr(ev), len(eos), cur_stream()))
+        self._cs = (int(k), int(max_new))
+        self.contrastive_done = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def contrastive_off(self):
+        if vars(self).get("_cs", None) is not None:
+            check(self.lib.omchat_set_contrastive(self.h, 0, 0.0, 0, 0, None, 0, cur_stream()))
+        self._cs = None
+
+    def contrastive_step(self, logits):
+        """logits fp32 [1, V] of the prefill (the first call: top-k and the fork of the prompt row) or [k, V] of the k-row decode step over
+        the candidates (pick, commit, next top-k) -> int32 [k + 1] on the device: the k candidates of the next step, then the emitted id
+        (-1 from the first call); self.contrastive_done turns 1 on an EOS id or the last of max_new ids.  Nothing synchronises."""
+        torch = _torch()
+        k, _ = self._cs
+        if not hasattr(self, "_cs_out") or self._cs_out.shape[0] != k + 1:
+            self._cs_out = torch.empty(k + 1, dtype=torch.int32, device=self.device)
+        lg = logits if logits.is_contiguous() else logits.contiguous()
+        check(self.lib.omchat_contrastive_step(self.h, ptr(lg), lg.shape[0], ptr(self._cs_out), ptr(self.contrastive_done), cur_stream()))
+        self._prefix = None      # the rows changed hands
+        return self._cs_out
+
+    def contrastive_record(self, steps):
+        """the record of the first `steps` picks since the prefill (synchronises): dict of numpy arrays -- ids / probs / penalties
+        [steps, k], pick, token, chunks, rows [steps] (omchat_amd/contrastive.py: unpack_record)"""
+        torch = _torch()
+        from .contrastive import REC_WORDS, unpack_record
+        out = torch.zeros(max(int(steps), 1), REC_WORDS, dtype=torch.int32)
+        check(self.lib.omchat_contrastive_read(self.h, ptr(out), int(steps)))
+        return unpack_record(out[:int(steps)].numpy(), self._cs[0])
+
+    def contrastive_rows(self, row0, n, want_cand=True):
+        """test hook: (history rows [n, H], their inverse norms fp32 [n], the last k-row step's final-normed rows [k, H]) on the host"""
+        torch = _torch()
+        H = self.c.t_hidden
+        hist = torch.zeros(max(n, 1), H, dtype=self.torch_dtype)
+        inv = torch.zeros(max(n, 1), dtype=torch.float32)
+        cand = torch.zeros(self._cs[0], H, dtype=self.torch_dtype) if want_cand else None
+        check(self.lib.omchat_contrastive_rows(self.h, int(row0), int(n), ptr(hist), ptr(inv), ptr(cand)))
+        return hist[:n], inv[:n], cand
+
+    def contrastive_plan(self, L):
+        """(chunks, rows_per_chunk) of the penalty launch over L history rows on this device"""
+        ch, rpc = C.c_int(0), C.c_int(0)
+        check(self.lib.omchat_op_contrastive_plan(int(L), C.byref(ch), C.byref(rpc)))
+        return ch.value, rpc.value
+
+    def contrastive_penalty(self, hist, cand, cand_nb=0, k=None, inv=None):
+        """the penalty launch alone (omchat_op_contrastive_penalty): hist 16-bit [L, H], cand 16-bit [k, H] row-major (or the packed buffer
+        with cand_nb blocks and k given), inv fp32 [L] or None (then computed by the norms launch) -> (partial maxima fp32 [chunks, 16],
+        the candidates' inverse norms fp32 [16], inv fp32 [L]), all on the device"""
+        torch = _torch()
+        L, H = hist.shape
+        k = int(k if k is not None else cand.shape[0])
+        chunks, _ = self.contrastive_plan(L)
+        part = torch.full((chunks, 16), float("nan"), dtype=torch.float32, device=self.device)
+        cinv = torch.zeros(16, dtype=torch.float32, device=self.device)
+        comp = inv is None
+        inv = inv if inv is not None else torch.empty(L, dtype=torch.float32, device=self.device)
+        check(self.lib.omchat_op_contrastive_penalty(_lib.dtype_code(hist.dtype), ptr(hist), ptr(inv), int(comp), L, H, ptr(cand), int(cand_nb), k,
+                                                     ptr(part), ptr(cinv), cur_stream()))
+        return part, cinv, inv
+
+    def contrastive_topk(self, logits, V, k, row_sel=None):
+        """the top-k launch alone (omchat_op_contrastive_topk): logits fp32 [rows, ld], the first V ids of row *row_sel (device int32 [1];
+        None = row 0) -> (ids int32 [k], probs fp32 [k]) on the device"""
+        torch = _torch()
+        n = max(int(self.lib.omchat_op_contrastive_topk_ws(int(V))), 16)
+        ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        ids = torch.empty(k, dtype=torch.int32, device=self.device)
+        probs = torch.empty(k, dtype=torch.float32, device=self.device)
+        check(self.lib.omchat_op_contrastive_topk(ptr(logits), int(logits.stride(0)), ptr(row_sel), int(V), int(k), ptr(ids), ptr(probs), ptr(ws),
+                                                  cur_stream()))
+        torch.cuda.current_stream().synchronize()      # (ws is released when this returns)
+        return ids, probs
+
+    def contrastive_select(self, part, k, alpha, ids, probs, cand_inv, cand=None, cand_nb=0, hist=None, inv=None, n_hist=0, eos=(), last=False):
+        """the select-and-commit launch alone (omchat_op_contrastive_select) -> dict(rec int32 [REC_WORDS], parents int32 [k], sel, token,
+        done int32 [1]) on the device; with hist / inv / cand the picked row is appended at row n_hist"""
+        torch = _torch()
+        from .contrastive import REC_WORDS
+        dev = self.device
+        out = dict(rec=torch.zeros(REC_WORDS, dtype=torch.int32, device=dev), parents=torch.full((k,), -1, dtype=torch.int32, device=dev),
+                   sel=torch.full((1,), -1, dtype=torch.int32, device=dev), token=torch.full((1,), -1, dtype=torch.int32, device=dev),
+                   done=torch.full((1,), -1, dtype=torch.int32, device=dev))
+        ev = torch.tensor([int(i) for i in eos] or [0], dtype=torch.int32)
+        H = int(cand.shape[-1]) if (cand is not None and cand_nb == 0) else (int(hist.shape[1]) if hist is not None else 0)
+        check(self.lib.omchat_op_contrastive_select(self.dtype_code, ptr(part), int(part.shape[0]), int(k), float(alpha), ptr(ids), ptr(probs),
+                                                    ptr(cand_inv), ptr(cand), int(cand_nb), H, ptr(hist), ptr(inv), int(n_hist), ptr(ev), len(eos),
+                                                    int(bool(last)), ptr(out["rec"]), ptr(out["parents"]), ptr(out["sel"]), ptr(out["token"]),
+                                                    ptr(out["done"]), cur_stream()))
+        return out
+
     # ------------------------------------------------------------------ sampled groups (include/omchat_hip.h: omchat_group_begin)
     def group_share_refusal(self, N):
         """why the shared-prompt form is not available for N rows per prompt on this engine, or None (host data only)"""

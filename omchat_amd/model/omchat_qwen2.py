@@ -592,7 +592,24 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         prompt_lookup_num_tokens, reuse_cache=True, padded or left-padded batches, tensor parallelism and the fp8 / MXFP4 decode modes;
         ValueError for a value that is none of the three forms, a negative or repeated index, no index below num_hidden_layers, more than
         16 layers, a dola_relative_top outside (0, 1], (k + 1) * b > min(max_batch, 32).  Not pinned against HF: transformers 5 moved DoLa
-        out of the library; tests/dola_ref.py restates HF 4.4x's functions."""
+        out of the library; tests/dola_ref.py restates HF 4.4x's functions.
+        penalty_alpha=a with top_k=k (both also read from generation_config): HF's contrastive search (Su et al., "A
+        Contrastive Framework for Neural Text Generation") on the device, selected by HF's rule -- num_beams == 1, do_sample false,
+        penalty_alpha > 0, top_k > 1; in every other case the call is the call without the keyword.  Per emitted id the k likeliest ids
+        (ties to the lower id) run as the k rows of ONE decode step over the same cache -- the prompt row is forked into k rows once, or
+        shared by them: share_prompt as for sampled groups -- and the id that maximises (1 - a) p_i - a max_j cos(h_i, H_j) is emitted
+        (the first maximum), H the post-final-norm hidden rows of all earlier positions, image rows included; only the one new cache slot
+        of the picked row is copied to the other rows.  Works with images, max_new_tokens, eos_token_id, stopping_criteria, a streamer, the
+        decode graph and enable_mxfp4_decode(True, batched=True).  With return_dict_in_generate=True the output carries
+        .contrastive_ranks [1, new] (the emitted id's rank among the candidates) and .degeneration_penalties [1, new] (its penalty).
+        Refused from host data, before any work (omchat_amd/contrastive.py): NotImplementedError for b > 1, an attention_mask with zeros,
+        num_return_sequences > 1, suffixes=, prompt_lookup_num_tokens, reuse_cache=True, guidance_scale, dola_layers, token_fsm, the
+        token-banning arguments, repetition_penalty != 1, output_logprobs, tensor parallelism, the e4m3 KV cache, fp8 prefill GEMMs and
+        batch-1-only MXFP4; ValueError for penalty_alpha > 1, top_k > min(16, max_batch) (generation_config.top_k defaults to 50: pass
+        top_k), more than 8 distinct EOS ids (the device's done word knows 8) and prompt + max_new_tokens > max_seq.  The host reads every
+        emitted id behind an event before it enqueues the next step (the search has no rewind), so the device idles for one host round
+        trip per token.  Not pinned against HF: transformers 5 moved the strategy out of the library;
+        tests/contrastive_ref.py restates HF 4.4x's loop."""
         if do_sample is None:
             do_sample = bool(getattr(self.generation_config, "do_sample", False))
         gc = self.generation_config
@@ -619,6 +636,26 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             _dola.refuse(input_ids.shape[0], len(dl["layers"]), e.c.max_batch, nb, gd is not None, nret, suffixes is not None, plk is not None, reuse,
                          ragged or (attention_mask is not None and bool((attention_mask == 0).any())), e.tp_size,
                          vars(e).get("_fp8_decode", False), vars(e).get("_mxfp4_decode", False))
+        # contrastive search: HF's mode rule; resolved and refused from host data, before any work
+        from .. import contrastive as _cs
+        cs = _cs.resolve_contrastive(gc, kwargs, top_k, do_sample, nb, lambda: self.engine.c.max_batch)
+        if cs is not None:
+            e = self.engine
+            nret = num_return_sequences if num_return_sequences is not None else (getattr(gc, "num_return_sequences", None) or 1)
+            plk = kwargs.get("prompt_lookup_num_tokens", None)
+            plk = plk if plk is not None else getattr(gc, "prompt_lookup_num_tokens", None)
+            rp = repetition_penalty if repetition_penalty is not None else getattr(gc, "repetition_penalty", None)
+            olp_ = bool(output_logprobs if output_logprobs is not None else getattr(gc, "output_logprobs", False))
+            _cs.refuse(input_ids.shape[0], attention_mask is not None and bool((attention_mask == 0).any()), nret, suffixes is not None,
+                       plk is not None, reuse, gd is not None, dl is not None, token_fsm is not None, False, rp, olp_, e.tp_size,
+                       vars(e).get("_fp8_kv", False), vars(e).get("_fp8_prefill", False), vars(e).get("_mxfp4_decode", False),
+                       vars(e).get("_mxfp4_batched", False), share_prompt, e.group_share_refusal(cs["k"]))
+            cs["max_new"] = int(max_new_tokens if max_new_tokens is not None else (gc.max_new_tokens or 20))
+            if cs["max_new"] < 1:
+                raise ValueError(f"`max_new_tokens` has to be a strictly positive integer, but is {cs['max_new']}")
+            eos_cs = eos_token_id if eos_token_id is not None else gc.eos_token_id
+            _cs.check_eos(list(eos_cs) if isinstance(eos_cs, (list, tuple)) else ([eos_cs] if eos_cs is not None else []))
+            _cs.check_room(self._spliced_lengths(input_ids.detach().to("cpu", torch.int64), images)[0], cs["max_new"], e.c.max_seq)
         sfx = None
         if suffixes is not None:      # every refusal that host data decides, before any work (and before the other modes' own refusals)
             sfx = self._suffix_params(input_ids, images, attention_mask, suffixes, nb, num_return_sequences, share_prompt, reuse, kwargs, streamer)
@@ -640,6 +677,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         eos_ids = eos_token_id if eos_token_id is not None else gc.eos_token_id
         eos_ids = list(eos_ids) if isinstance(eos_ids, (list, tuple)) else ([eos_ids] if eos_ids is not None else [])
         con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None)
+        if cs is not None and con is not None:
+            _cs.refuse(banning=True)
         # the token automaton (omchat_amd/fsm.py): one start state per row of the expanded batch, refused here too
         from ..fsm import resolve_token_fsm
         n_prompts = input_ids.shape[0]
@@ -659,6 +698,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             self.engine.guidance_off()
         if dl is None and vars(self.engine).get("_dola", None) is not None:      # sticky too: a call without the keyword contrasts nothing
             self.engine.dola_off()
+        if vars(self.engine).get("_cs", None) is not None:      # sticky too (a call that raised midway): a call starts with the mode off
+            self.engine.group_end()
+            self.engine.contrastive_off()
+        if cs is not None:
+            return self._contrastive_generate(input_ids, images, attention_mask, cs, streamer, eos_ids, stopping_criteria, share_prompt,
+                                              return_dict_in_generate)
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
@@ -843,6 +888,58 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             res.add("fsm_states", fsm_states)
         if dola_rec is not None:
             res.add("dola_premature_layers", dola_rec)
+        return res
+
+    def _contrastive_generate(self, input_ids, images, attention_mask, cs, streamer, eos_ids, stopping_criteria, share_prompt,
+                              return_dict_in_generate):
+        """HF's _contrastive_search on the device (include/omchat_hip.h: omchat_set_contrastive).  The arguments went
+        through omchat_amd/contrastive.py: every refusal was raised before any work.  Per emitted id: one k-row decode step over the
+        candidates and one contrastive step (penalty, select and commit, one-slot KV gather, next top-k); the host reads the emitted id
+        behind an event, as the greedy loop does, for EOS, the streamer and the stopping criteria."""
+        e = self.engine
+        k, alpha, max_new = cs["k"], cs["alpha"], cs["max_new"]
+        eos = set(int(i) for i in eos_ids)
+        P = self._spliced_lengths(input_ids.detach().to("cpu", torch.int64), images)[0]
+        share = e.group_share_default(k, P) if share_prompt is None else bool(share_prompt)
+        e.sampling_off()
+        if streamer is not None:
+            streamer.put(input_ids.cpu())
+        e.set_contrastive(k, alpha, max_new, share, sorted(eos))
+        new = []
+        try:
+            out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
+            cand = e.contrastive_step(out.local_logits)               # top-k of the prefill's row, the fork / share of the prompt row
+            stage = self._stage_buffer(max_new, 1)
+            evt = self._stage_event
+            for step in range(max_new):
+                _, lg = e.decode_step(cand[:k], want_logits=True)
+                cand = e.contrastive_step(lg)
+                stage[step].copy_(cand[k:k + 1], non_blocking=True)
+                evt.record()
+                evt.synchronize()
+                tok = int(stage[step][0])
+                new.append(tok)
+                if streamer is not None:
+                    streamer.put(torch.tensor([tok], dtype=torch.int64))
+                if tok in eos:
+                    break
+                if stopping_criteria and step + 1 < max_new:
+                    so_far = torch.cat([input_ids.cpu(), torch.tensor([new], dtype=torch.int64)], dim=1)
+                    if any(bool(c(so_far, None)) for c in stopping_criteria):
+                        break
+            rec = e.contrastive_record(len(new)) if return_dict_in_generate else None
+        finally:
+            e.group_end()
+            e.contrastive_off()
+        if streamer is not None:
+            streamer.end()
+        seqs = torch.cat([input_ids.cpu(), torch.tensor([new], dtype=torch.int64)], dim=1)
+        if not return_dict_in_generate:
+            return seqs
+        res = GenerateOutput(seqs, None, None)
+        n = len(new)
+        res.add("contrastive_ranks", torch.from_numpy(rec["pick"].copy()).view(1, n))
+        res.add("degeneration_penalties", torch.from_numpy(rec["penalties"][range(n), rec["pick"]].copy()).view(1, n))
         return res
 
     def _group_params(self, input_ids, images, attention_mask, nb, do_sample, num_return_sequences, share_prompt, reuse, lookup, streamer):
