@@ -730,6 +730,9 @@ int omchat_op_quant_rows_fp8(int dtype, const void* x, const void* norm_w, float
 int omchat_op_quant_fp8(int dtype, const void* W, int N, int K, void* W8, float* scale, void* stream);
 int omchat_op_gemv_fp8(int dtype, const void* X, const void* W8, const float* scale, void* Y, int N, int K, const void* bias,
                        const void* resid, int epi, int out_f32, int ksplit, void* stream);
+/* ... with the preceding RMSNorm in registers: x is the RAW row, as in omchat_op_gemv_norm (K <= 4096, epi NONE / SWIGLU) */
+int omchat_op_gemv_fp8_norm(int dtype, const void* X, const void* W8, const float* scale, void* Y, int N, int K, const void* norm_w, float eps,
+                            const void* bias, int epi, int out_f32, void* stream);
 /* MXFP4 pieces (format: omchat_enable_mxfp4_decode above): W [N][K] (dtype), K % 32 == 0 -> W4 [N][K / 2] bytes + S [N][K / 32] e8m0 bytes;
  * y[N] = epi(sum over blocks of 2^e (codes . x)), batch 1, the epilogues and ksplit of omchat_op_gemv_fp8; _norm: x is the RAW row and the
  * RMSNorm runs in registers as in omchat_op_gemv_norm (K <= 4096, epi NONE / SWIGLU) */

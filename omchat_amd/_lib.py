@@ -141,6 +141,7 @@ _SIGS = {
     "omchat_op_encode_bf16x12": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "omchat_op_gemv_bf16x12": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "omchat_op_gemv_mxfp4_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
+    "omchat_op_gemv_fp8_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "omchat_op_rmsnorm": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "omchat_op_resid_rmsnorm": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "omchat_op_vit_qknorm": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _vp]),

@@ -1084,6 +1084,15 @@ extern "C" int omchat_op_gemv_mxfp4_norm(int dtype, const void* X, const void* W
   return launch_gemv(dtype, g, S(stream));
 }
 
+// ... and the same on e4m3 rows with one fp32 scale per row (omchat_op_gemv_fp8 with the RMSNorm in registers)
+extern "C" int omchat_op_gemv_fp8_norm(int dtype, const void* X, const void* W8, const float* scale, void* Y, int N, int K, const void* norm_w,
+                                       float eps, const void* bias, int epi, int out_f32, void* stream) {
+  OM_CHECK(X && W8 && scale && Y && norm_w, "null argument");
+  GemvArgs g{X, K, W8, K, Y, N, 1, N, K, bias, nullptr, 0, epi, out_f32, 0, 0, scale};
+  g.norm_w = norm_w; g.norm_eps = eps;
+  return launch_gemv(dtype, g, S(stream));
+}
+
 // bf16x12 pieces (include/omchat_hip.h): the encoder into caller-provided buffers, and the three batch-1 roles on coded operands --
 // norm_w with EPI_SWIGLU (gate|up) or EPI_NONE (lm_head form), or EPI_RESID with resid (down_proj, long K)
 extern "C" int omchat_op_encode_bf16x12(const void* W, int N, int K, void* coded, void* top, void* cnt, void* patch, void* over, void* stream) {

@@ -7,8 +7,8 @@ fp32 operation or one round-to-nearest-even to T, restated below in float64 with
 expected BITS of EPI_NONE / EPI_RESID / EPI_LS_RESID / EPI_F32OUT / EPI_PARTIAL / out_f32 and of the row-scale form are then determined;
 GELU and SwiGLU go through erf / exp and are compared in ulps of T (ulp_distance).
 
-tests/test_gemm_exact_cpu.py proves the preconditions for every case list below; tests/test_gpu_gemm_exact.py and
-tests/test_gpu_gemv_exact.py run the kernels."""
+tests/test_gemm_exact_cpu.py proves the preconditions for every case list below; tests/test_gpu_gemm_exact.py,
+tests/test_gpu_gemv_exact.py and tests/test_gpu_gemv_quant_exact.py (quantised weights, norm-in-GEMV: the last section) run the kernels."""
 import functools
 import math
 import torch
@@ -389,3 +389,328 @@ def gemv_reference(ops, form, dt):
     if form == "resid":
         return reference(ops, EPI_RESID, dt, bias=False)
     return reference(ops, EPI_SWIGLU, dt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Quantised weights (e4m3 rows + fp32 row scales, MXFP4) and the norm-in-GEMV launches: operands for which these are exact too.
+#
+# e4m3: integer weights in [-4, 4] and w_scale[n] = k / 8, never the same on adjacent rows; the kernels compute fp32(sum * scale) per K slice,
+# then + bias, T(), resid +  (gemv_rows_body / rw_rows_q in csrc/gemv.hip) -- reference(ops, epi, dt, scale = w_scale[None, :]).
+# MXFP4: codes over all 16 e2m1 values and e8m0 bytes built directly; the kernels widen the codes at scale 1 and multiply the fp32 partial of a
+# block by 2^e, so every intermediate is a multiple of one granule per row and the accumulation is exact while sum |x w| / granule < 2^24
+# (asserted per case, whatever the order).  The wide variant gives all blocks of row n the exponent -24 + n % 33: exact within a row, 2^-24 ..
+# 2^8 across rows -- a scale folded into an f16 convert underflows and changes bits.  Its outputs are fp32; the long-K family has no fp32 output,
+# so its wide case writes T(acc) (EPI_RESID on a zero residual) with exponents -24 .. +2 and |x| <= 31: every T(acc) is finite in f16 and
+# at least a quarter of them are real roundings in both types (test_gemm_exact_cpu.py asserts both).  The SwiGLU cases take block exponents
+# lower by 4, so that silu(gate) * up stays inside f16's range and the 2 ulp bound is a bound on nearly every output.
+# RMSNorm: x is made of groups of eight magnitudes {4, 3, 2, 1, 1, 1, 0, 0}, permuted, with random signs: the sum of squares is the integer
+# 4 K, tot / K == 4.0 exactly, rsqrtf(4 + 1e-6) is 0.5 to a few ulps, every x * inv lies within ~2^-21 of x / 2 in {0, .5, 1, 1.5, 2} -- far
+# from a rounding boundary of T -- so T(x * inv) == x / 2 whatever the last bits of the device's rsqrtf are, and with norm weights from
+# {.5, 1, 1.5, 2} xn = T(nw * T(x * inv)) == nw * x / 2 exactly: multiples of 1 / 4 up to 4.  The dot products are then exact as above.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+WF_16, WF_E4M3, WF_MX4 = 0, 1, 2
+GF_ROWS_NORM, GF_ROWS_NORM_LOOP = 5, 6
+PLAN_NORM = 8
+NORM_EPS = 1e-6
+NORM_GROUP = (4.0, 3.0, 2.0, 1.0, 1.0, 1.0, 0.0, 0.0)
+NORM_W = (0.5, 1.0, 1.5, 2.0)
+E2M1 = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=torch.float64)
+
+
+def norm_x(g, K):
+    """the exact-RMSNorm row [1, K]: K / 8 permuted, signed copies of NORM_GROUP"""
+    assert K % 8 == 0
+    grp = torch.tensor(NORM_GROUP, dtype=torch.float64).repeat(K // 8, 1)
+    perm = torch.rand((K // 8, 8), generator=g).argsort(dim=1)
+    sign = 1 - 2 * _randint(g, 0, 1, (K // 8, 8))
+    return (grp.gather(1, perm) * sign).reshape(1, K)
+
+
+def norm_weights(g, K):
+    return torch.tensor(NORM_W, dtype=torch.float64)[torch.randint(0, 4, (K,), generator=g)]
+
+
+def norm_inv(x, eps=NORM_EPS):
+    """fp32 rsqrt(tot / K + eps) as torch evaluates it: the centre of the +-8 ulp band the CPU test walks"""
+    tot = (x.float() * x.float()).sum()
+    return torch.rsqrt(tot / float(x.numel()) + torch.tensor(eps, dtype=torch.float32))
+
+
+def norm_xn(x, nw, inv, dt):
+    """T(nw * T(x * inv)) with fp32 products, the kernel's rounding points (gemv_rows_norm_body); inv an fp32 scalar tensor"""
+    T = DT[dt]
+    return (nw.float() * (x.float() * inv).to(T).float()).to(T).double()
+
+
+WIDE = 33                                # exponents of the wide variant: -24 .. +8
+WIDE_F16_OUT = 27                        # ... where T(acc) is the output: -24 .. +2, so that |acc| stays inside f16 (QUANT_CASES, the long-K entry)
+SWIGLU_E_SHIFT = -4                      # block exponents of the MXFP4 SwiGLU cases: -6 .. -2, so that silu(gate) * up stays inside f16
+
+
+def mx_exponents(N, K, seed, wide=0, shift=0):
+    """block exponents [N, K / 32]: ((3 n + 2 blk + seed) % 5) - 2 + shift.  The block step 2 and the row step 3 are both coprime to 5, so
+    adjacent blocks of a row and adjacent rows of a block never share an exponent.  wide > 0: -24 + n % wide in every block of row n"""
+    n, blk = torch.arange(N)[:, None], torch.arange(K // 32)[None, :]
+    if wide:
+        return (-24 + n % wide).expand(N, K // 32).contiguous()
+    return (3 * n + 2 * blk + seed) % 5 - 2 + shift
+
+
+def mx_dequant(codes, e):
+    """float64 [N, K] of e2m1 codes [N, K] (sign in bit 3) and block exponents [N, K / 32]"""
+    c = codes.to(torch.int64)
+    v = torch.where(c >= 8, -E2M1[c & 7], E2M1[c & 7])
+    return v * torch.ldexp(torch.ones(e.shape, dtype=torch.float64), e).repeat_interleave(32, dim=1)
+
+
+def e4m3_row_scales(N, seed):
+    """k / 8, k in 1 .. 8, as fp8_scales: the step of 5 keeps adjacent rows apart"""
+    return (1 + (torch.arange(N) * 5 + seed) % 8).to(torch.float64) / 8
+
+
+def quant_finish(ops, dt, need_bias=True):
+    """acc, the per-output scale and granule of a quantised / norm operand set, from its x (xn), weights and scales; asserts the exactness bounds"""
+    wf, xn = ops["wf"], ops["xn"]
+    gx = 0.25 if ops["norm"] else 1.0
+    if wf == WF_MX4:
+        ops["W"] = mx_dequant(ops["codes"], ops["e"])
+        gw = 0.5 * torch.ldexp(torch.ones(len(ops["e"]), dtype=torch.float64), ops["e"].min(dim=1).values)
+    else:
+        gw = torch.ones(len(ops["W"]), dtype=torch.float64)
+    acc = xn @ ops["W"].t()
+    bound = (xn.abs() @ ops["W"].abs().t()) / (gx * gw)[None, :]      # every partial sum in any order, in granules
+    assert float(bound.max()) < 2 ** 24, ("partial sums must stay below 2^24 granules", float(bound.max()))
+    assert bool((acc / (gx * gw) == (acc / (gx * gw)).round()).all())
+    scale = ops.get("w_scale")
+    s2 = None if scale is None else scale[None, :]
+    v = acc if s2 is None else acc * s2
+    assert bool((f32(v) == v).all()), "acc * scale must be exact in fp32"
+    if need_bias:
+        assert bool((f32(v + ops["bias"]) == v + ops["bias"]).all()), "acc * scale + bias must be exact in fp32"
+    ops["acc"], ops["scale"] = acc, s2
+    ops["granule"] = gx * gw * (0.125 if wf == WF_E4M3 else 1.0)      # of an output and of every EPI_PARTIAL slice (e4m3: each slice is scaled)
+    return ops
+
+
+def make_quant_operands(seed, wf, b, N, K, dt, norm=False, x_max=A_MAX, wide=0, e_shift=0):
+    """x [b, K] (norm: the exact-RMSNorm row and its norm weights), the weights of form wf with their scales, bias / resid as make_operands
+    defines them (wide: a zero residual), and acc = xn W^T (e4m3: before the row scale).  wide / e_shift: mx_exponents.  Every operand
+    survives its storage type; the bounds are asserted."""
+    g = torch.Generator().manual_seed(seed)
+    ops = dict(wf=wf, norm=norm, wide=wide)
+    if norm:
+        assert b == 1
+        x, nw = norm_x(g, K), norm_weights(g, K)
+        xn = nw[None, :] * x / 2
+        assert torch.equal(norm_xn(x, nw, norm_inv(x), dt), xn) and float(xn.abs().max()) <= 4 and torch.equal(xn * 4, (xn * 4).round())
+        ops.update(A=x, nw=nw, xn=xn)
+    else:
+        x = _randint(g, -x_max, x_max, (b, K))
+        ops.update(A=x, xn=x)
+    if wf == WF_MX4:
+        assert K % 32 == 0
+        ops["codes"] = torch.randint(0, 16, (N, K), generator=g).to(torch.uint8)
+        ops["e"] = mx_exponents(N, K, seed, wide, e_shift)      # (W, the de-quantised weights: quant_finish)
+    elif wf == WF_E4M3:
+        ops["W"] = _randint(g, -4, 4, (N, K))
+        ops["w_scale"] = e4m3_row_scales(N, seed)
+        assert bool((ops["w_scale"][1:] != ops["w_scale"][:-1]).all())
+    else:
+        ops["W"] = _randint(g, -W_MAX, W_MAX, (N, K))
+        assert bool(representable(ops["W"], dt).all())
+    den = BIAS_DEN[dt]
+    ops["bias"] = _randint(g, -den, den, (N,)) / den
+    ops["resid"] = (torch.zeros((b, N), dtype=torch.float64) if wide else _randint(g, -64, 64, (b, N)) / 4)
+    for name in ("A", "xn", "bias", "resid") + (("nw",) if norm else ()):
+        assert bool(representable(ops[name], dt).all()), (name, "does not survive a round trip through", dt)
+    return quant_finish(ops, dt, need_bias=not wide)
+
+
+@functools.lru_cache(maxsize=2)
+def cached_quant_operands(seed, wf, b, N, K, dt, norm=False, x_max=A_MAX, wide=0, e_shift=0):
+    return make_quant_operands(seed, wf, b, N, K, dt, norm, x_max, wide, e_shift)
+
+
+def quant_reference(ops, form, dt):
+    """as gemv_reference, with the e4m3 row scale on the accumulators; "f32" / "partial": fp32(acc * scale) (the sum of the scaled slices)"""
+    s = ops["scale"]
+    if form == "bias":
+        return reference(ops, EPI_NONE, dt, bias=True, scale=s)
+    if form in ("f32", "partial"):
+        return reference(ops, EPI_F32OUT, dt, scale=s)
+    if form == "resid":
+        return reference(ops, EPI_RESID, dt, bias=False, scale=s)
+    return reference(ops, EPI_SWIGLU, dt, scale=s)
+
+
+def quant_tail_floor(ops, dt):
+    return tail_floor(ops, EPI_SWIGLU, dt, scale=ops["scale"])
+
+
+# the corruptions that the reference must tell apart (test_gemm_exact_cpu.py): each returns operands a subtly wrong kernel would have computed on
+def corrupt(ops, kind, dt):
+    """None where the corruption does not apply to this operand set.  nibbles: the two codes of every byte swapped; last_scale: the last
+    block's e8m0 byte replaced by its neighbour's; next_row_scale: row n under row n + 1's scale(s); drop32: the last 32 k dropped;
+    swap_gate_up: gate and up exchanged in the last 32-row block"""
+    o = dict(ops)
+    wf = ops["wf"]
+    if kind == "nibbles":
+        if wf != WF_MX4:
+            return None
+        c = ops["codes"]
+        o["codes"] = torch.stack((c[:, 1::2], c[:, 0::2]), dim=2).reshape(c.shape)
+    elif kind == "last_scale":
+        if wf != WF_MX4 or ops["wide"]:
+            return None
+        o["e"] = ops["e"].clone()
+        o["e"][:, -1] = ops["e"][:, -2]
+    elif kind == "next_row_scale":
+        if wf == WF_MX4:
+            o["e"] = torch.roll(ops["e"], -1, 0)
+        elif wf == WF_E4M3:
+            o["w_scale"] = torch.roll(ops["w_scale"], -1, 0)
+        else:
+            return None
+    elif kind == "drop32":
+        if wf == WF_MX4:
+            o["codes"] = ops["codes"].clone()
+            o["codes"][:, -32:] = 0
+        else:
+            o["W"] = ops["W"].clone()
+            o["W"][:, -32:] = 0
+    elif kind == "swap_gate_up":
+        N = ops["W"].shape[0]
+        idx = torch.arange(N)
+        idx[N - 32:] = torch.cat((torch.arange(N - 16, N), torch.arange(N - 32, N - 16)))
+        for name in ("W", "codes", "e", "w_scale"):
+            if name in ops:
+                o[name] = ops[name][idx]
+    else:
+        raise ValueError(kind)
+    return quant_finish(o, dt, need_bias=False)
+
+
+def bias_before_scale(ops, dt):
+    """EPI_NONE on e4m3 with the bias added BEFORE the row scale: T(fp32(fp32(acc + bias) * scale))"""
+    return rT(f32(f32(ops["acc"] + ops["bias"]) * ops["scale"]), dt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Case list.  QCase: weight form, b, N (an int, or a function of the compute-unit count where the family depends on it), K, norm, max |x|,
+# packed (through omchat_op_gemv_mxfp4_packed), wide (the number of row exponents from -24 up; 0: the narrow form), tuning ((key, value,
+# restore), ...), pins ({index into the plan's ints: value}: 5 = waves per
+# workgroup, 8 = rows per wave) and forms ((form, ksplit, family), ...) as in GEMV_CASES.  Ragged K: K % 64 == 0 and K % 512 != 0 for 16-bit and
+# e4m3 rows, K % 32 == 0 and K % 64 != 0 for MXFP4 rows (the last 512-chunk ends inside a 64-k pair of blocks).
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class QCase:
+    def __init__(self, wf, b, N, K, forms, norm=False, x_max=A_MAX, packed=False, wide=0, tuning=(), pins=None, name=None):
+        self.wf, self.b, self._N, self.K, self.forms, self.norm, self.x_max = wf, b, N, K, forms, norm, x_max
+        self.packed, self.wide, self.tuning, self.pins = packed, wide, tuning, pins or {}
+        self.cu_dependent = callable(N)
+        self.e_shift = SWIGLU_E_SHIFT if wf == WF_MX4 and any(f[0].startswith("swiglu") for f in forms) else 0
+        self.id = "wf{}-b{}-N{}-K{}{}{}{}{}".format(wf, b, name if callable(N) else N, K, "-norm" if norm else "", "-pk" if packed else "",
+                                                    "-wide" if wide else "", "".join("-k{}v{}".format(k, v) for k, v, _ in tuning))
+
+    def N(self, n_cu):
+        return self._N(n_cu) if self.cu_dependent else self._N
+
+    def operands(self, dt, n_cu, cached=True):
+        f = cached_quant_operands if cached else make_quant_operands
+        return f(5, self.wf, self.b, self.N(n_cu), self.K, dt, self.norm, self.x_max, self.wide, self.e_shift)
+
+    def plan_args(self, form, ks):
+        epi, ks_, flags = gemv_plan_args(self.b, 0, self.K, self.packed, self.packed, form, ks)
+        return epi, ks_, flags | (PLAN_NORM if self.norm else 0)
+
+
+def balanced7(n_cu):
+    return 7 * 2 * n_cu
+
+
+def balanced9(n_cu):
+    return 9 * 2 * n_cu
+
+
+def loop_rows(n_cu):
+    """the smallest output count of at least 8 CUs that does not divide by 2 CUs"""
+    return 8 * n_cu + 1
+
+
+def loop_pairs2(n_cu):
+    """N of the SwiGLU loop case: (gate, up) pairs come in blocks of 16, so the smallest such pair count is 8 CUs + 16 (for 2 CUs > 16)"""
+    n = 8 * n_cu
+    while n % (2 * n_cu) == 0:
+        n += 16
+    return 2 * n
+
+
+def _ragged_k(wf, k16, k4):
+    return k4 if wf == WF_MX4 else k16
+
+
+def _quant_cases():
+    R, L, NM, LP = GF_ROWS, GF_ROWS_LONGK, GF_ROWS_NORM, GF_ROWS_NORM_LOOP
+    out = [QCase(WF_16, 1, balanced7, 64, (("resid", 0, R),), pins={5: 7}, name="14cu")]      # the seven-wave residual form (tuning key 17)
+    for wf in (WF_E4M3, WF_MX4):
+        out += [
+            QCase(wf, 1, 102, _ragged_k(wf, 64, 96), (("bias", 0, R), ("f32", 0, R), ("resid", 0, R)), pins={8: 1}),
+            QCase(wf, 1, 160, _ragged_k(wf, 192, 544), (("swiglu", 0, R),), pins={8: 4}),      # four pairs per wave
+            QCase(wf, 1, 102, 1024, (("partial", 0, R),), pins={8: 4}),
+            QCase(wf, 1, 70, 4096, (("partial", 3, R),), pins={8: 4}),                         # eight chunks cut 2 | 3 | 3
+            QCase(wf, 1, 32790, _ragged_k(wf, 64, 96), (("bias", 0, R), ("f32", 0, R)), pins={8: 8}),      # eight rows per wave, ragged last group
+            QCase(wf, 1, 1030, _ragged_k(wf, 4160, 4128), (("resid", 0, L),)),
+            QCase(wf, 1, 9, 32768, (("resid", 0, L),), x_max=1),                               # the upper K bound, the largest LDS staging
+        ]
+    for wf in (WF_16, WF_E4M3, WF_MX4):
+        kr = _ragged_k(wf, 576, 544)
+        out += [
+            QCase(wf, 1, 70, kr, (("bias", 0, NM), ("f32", 0, NM)), norm=True, pins={8: 2}),
+            QCase(wf, 1, 96, kr, (("swiglu", 0, NM),), norm=True, pins={8: 1}),
+            QCase(wf, 1, 70, 4096, (("bias", 0, NM),), norm=True, pins={8: 2}),
+            QCase(wf, 1, balanced9, 2048, (("bias", 0, NM),), norm=True, pins={5: 9, 8: 1}, name="18cu"),
+            QCase(wf, 1, 32790, _ragged_k(wf, 64, 96), (("bias", 0, NM),), norm=True, pins={8: 4}),      # lm_head's four rows per wave
+        ]
+        # every other rows-per-wave answer of the SwiGLU norm launch: tuning key 38 (16-bit: 2, 3; quantised, value x 16: 2, 4); 80 pairs
+        for v, rr, back in (((2, 2, 1), (3, 3, 1)) if wf == WF_16 else ((32, 2, 16), (64, 4, 16))):
+            out.append(QCase(wf, 1, 160, kr, (("swiglu", 0, NM),), norm=True, tuning=((38, v, back),), pins={8: rr}))
+        # the loop form (tuning key 16, every bit)
+        for k in (2048, _ragged_k(wf, 2112, 2080)):
+            out += [
+                QCase(wf, 1, loop_rows, k, (("bias", 0, LP),), norm=True, tuning=((16, 15, 0),), name="8cu+1"),
+                QCase(wf, 1, loop_pairs2, k, (("swiglu", 0, LP),), norm=True, tuning=((16, 15, 0),), name="16cu+32"),
+            ]
+    # packed MXFP4 (batched steps): the packed rows of GEMV_CASES with wf = 2
+    P, XS, SP = GF_PK, GF_XS, GF_XS_SPLIT
+    M = WF_MX4
+    out += [
+        QCase(M, 16, 48, 192, (("bias", 0, P), ("f32", 0, P), ("partial", 2, P)), packed=True),
+        QCase(M, 17, 48, 192, (("bias", 0, P), ("f32", 0, P), ("partial", 3, P)), packed=True),
+        QCase(M, 1, 48, 1024, (("bias", 0, P), ("partial", 2, P)), packed=True),
+        QCase(M, 32, 384, 64, (("swiglu", 0, P), ("swiglu_yp", 0, P)), packed=True),
+        QCase(M, 1, 384, 64, (("swiglu", 0, P), ("swiglu_yp", 0, P)), packed=True),
+        QCase(M, 1, 64, 3584, (("bias", 0, XS), ("f32", 0, XS)), packed=True),
+        QCase(M, 17, 64, 3584, (("bias", 0, XS), ("f32", 0, XS)), packed=True),
+        QCase(M, 16, 128, 3584, (("swiglu", 0, XS), ("swiglu_yp", 0, XS)), packed=True),
+        QCase(M, 32, 128, 3584, (("swiglu", 0, XS), ("swiglu_yp", 0, XS)), packed=True),
+        QCase(M, 17, 2080, 3584, (("partial", 2, SP),), packed=True),
+        QCase(M, 32, 2080, 3584, (("partial", 2, SP),), packed=True),
+    ]
+    # the wide-exponent variant, one per MXFP4 family: fp32 output (the long-K form has none: EPI_RESID on a zero residual, T(acc))
+    out += [
+        QCase(M, 1, 102, 96, (("f32", 0, R),), wide=WIDE),
+        QCase(M, 1, 1030, 4128, (("resid", 0, L),), x_max=31, wide=WIDE_F16_OUT),
+        QCase(M, 1, 70, 544, (("f32", 0, NM),), norm=True, wide=WIDE),
+        QCase(M, 1, loop_rows, 2048, (("f32", 0, LP),), norm=True, wide=WIDE, tuning=((16, 15, 0),), name="8cu+1"),
+        QCase(M, 16, 48, 192, (("f32", 0, P),), packed=True, wide=WIDE),
+        QCase(M, 17, 64, 3584, (("f32", 0, XS),), packed=True, wide=WIDE),
+        QCase(M, 17, 2080, 3584, (("partial", 2, SP),), packed=True, wide=WIDE),
+    ]
+    return out
+
+
+QUANT_CASES = _quant_cases()
+PREPACKED_CASE = next(i for i, c in enumerate(QUANT_CASES) if c.packed and c.b == 16 and not c.wide)      # also run through the pack-once entries
+# every (family, weight form) pair that the list must reach
+QUANT_PAIRS = ({(GF_ROWS, WF_16)} | {(f, w) for f in (GF_ROWS, GF_ROWS_LONGK) for w in (WF_E4M3, WF_MX4)} |
+               {(f, w) for f in (GF_ROWS_NORM, GF_ROWS_NORM_LOOP) for w in (WF_16, WF_E4M3, WF_MX4)} |
+               {(f, WF_MX4) for f in (GF_PK, GF_XS, GF_XS_SPLIT)})

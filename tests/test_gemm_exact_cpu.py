@@ -172,3 +172,132 @@ def test_gemv_cases_take_the_family_they_name():
     assert seen == set(X.GEMV_FAMILIES)
     assert batches[X.GF_MFMA] >= {1, 16, 17, 32} and batches[X.GF_PK] >= {1, 16, 17, 32} and batches[X.GF_XS] >= {1, 16, 17, 32}
     assert batches[X.GF_ROWS] == {1} and batches[X.GF_ROWS_LONGK] == {1}      # batch-1 forms
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# quantised weights and the norm-in-GEMV launches (X.QUANT_CASES; tests/test_gpu_gemv_quant_exact.py runs them)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+QIDS = [c.id for c in X.QUANT_CASES]
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", X.QUANT_CASES, ids=QIDS)
+def test_quant_case_preconditions(dt, case):
+    """make_quant_operands asserts the round trips through T, the 2^24-granule bound on every partial sum and the exactness of acc * scale (+ bias)
+    in fp32; here: the weights survive THEIR storage type, the scales differ between neighbours, and the final rounding is a real one"""
+    ops = case.operands(dt, N_CU)
+    N, K = case.N(N_CU), case.K
+    assert ops["W"].shape == (N, K) and ops["A"].shape == (case.b, K)
+    if case.wf == X.WF_E4M3:
+        assert torch.equal(X.e4m3_bytes(ops["W"]).view(torch.float8_e4m3fn).double(), ops["W"])
+        s = ops["w_scale"]
+        assert torch.equal(X.f32(s), s) and bool((s[1:] != s[:-1]).all()) and float(s.min()) >= 0.125 and float(s.max()) <= 1
+    if case.wf == X.WF_MX4:
+        e = ops["e"]
+        assert int(ops["codes"].max()) == 15 and len(ops["codes"].unique()) == 16 and 0 < int(e.min()) + 127 and int(e.max()) + 127 < 255
+        assert N == 1 or bool((e[1:] != e[:-1]).all()), "adjacent rows of a block share a scale"
+        if case.wide:
+            assert bool((e == e[:, :1]).all()) and N >= case.wide and (int(e.min()), int(e.max())) == (-24, case.wide - 25)
+            assert case.wide == X.WIDE or not all(form in ("f32", "partial") for form, _, _ in case.forms), "the full window wherever the output is fp32"
+        else:
+            assert (int(e.min()), int(e.max())) == (case.e_shift - 2, case.e_shift + 2)
+            assert bool((e[:, 1:] != e[:, :-1]).all()), "adjacent blocks of a row share a scale (the last block of a ragged chunk included)"
+        if not case.packed:
+            assert K % 32 == 0 and (K % 64 != 0 or K % 512 == 0), "MXFP4 rows: a ragged K ends inside a 64-k pair of blocks"
+    elif not case.packed and K % 512 != 0:
+        assert K % 64 == 0
+    if not case.wide:      # as for GEMV_CASES: on acc (* scale) + bias, whichever forms the case runs
+        v = ops["acc"] if ops["scale"] is None else ops["acc"] * ops["scale"]
+        assert X.unrepresentable_share(v + ops["bias"], dt) >= 0.25, X.unrepresentable_share(v + ops["bias"], dt)
+    else:                  # the wide cases write fp32 (no rounding to T), but for the one whose output is T(acc): that rounding
+        assert all(form in ("f32", "partial") for form, _, _ in case.forms) or X.unrepresentable_share(ops["acc"], dt) >= 0.25, X.unrepresentable_share(ops["acc"], dt)
+    for form, ks, _ in case.forms:
+        want = X.quant_reference(ops, form, dt)
+        assert torch.equal(want.float().double(), want)
+        if form.startswith("swiglu"):      # silu(g) * u may leave f16's range on a few outputs (the 16-bit GEMV_CASES: 2-3 %), where 2 ulp bounds nothing
+            assert float(torch.isfinite(want).double().mean()) >= 0.97, (form, float(torch.isfinite(want).double().mean()))
+        else:
+            assert bool(torch.isfinite(want).all()), (form, "an expected value is not finite")
+        if form == "partial":
+            assert bool((want / ops["granule"] == (want / ops["granule"]).round()).all())
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_exact_rmsnorm_survives_any_rsqrt(dt):
+    """xn = T(nw * T(x * inv)) equals nw * x / 2 for every inv within +-8 fp32 ulps of rsqrt(tot / K + eps), for every norm case: the bits of the
+    normalised row do not depend on the device's rsqrtf"""
+    seen = set()
+    for case in X.QUANT_CASES:
+        if not case.norm or (case.K, case.wf) in seen:
+            continue
+        seen.add((case.K, case.wf))
+        ops = case.operands(dt, N_CU, cached=False)
+        x, nw = ops["A"], ops["nw"]
+        assert case.K % 8 == 0 and float((x * x).sum()) == 4.0 * case.K
+        assert set(x.abs().reshape(-1, 8).sort(dim=1).values.unique(dim=0).flatten().tolist()) == {0.0, 1.0, 2.0, 3.0, 4.0}
+        tot = (x.float() * x.float()).sum()
+        assert float(tot / float(case.K)) == 4.0
+        inv0 = X.norm_inv(x)
+        assert abs(float(inv0) - 0.5) < 1e-6
+        for d in range(-8, 9):
+            inv = (inv0.view(torch.int32) + d).view(torch.float32)
+            assert torch.equal(X.norm_xn(x, nw, inv, dt), nw[None, :] * x / 2), (case.id, d)
+        assert torch.equal(ops["xn"], nw[None, :] * x / 2)
+    assert len(seen) >= 9
+
+
+def test_quant_cases_take_the_family_they_name():
+    """the plan at 256 compute units answers the listed family (and waves / rows per wave where the case pins them) for every form of every case,
+    under the case's tuning keys; and every family x weight-form pair of the issue is in the list"""
+    from omchat_amd import _lib
+    l = _lib.lib()
+    out = (C.c_int * 20)()
+    seen = set()
+    for case in X.QUANT_CASES:
+        for dt in (_lib.F16, _lib.BF16):
+            for form, ks, family in case.forms:
+                epi, ks_, flags = case.plan_args(form, ks)
+                try:
+                    for key, value, _ in case.tuning:
+                        assert l.omchat_op_set_tuning(key, value) == 0
+                    rc = l.omchat_op_gemv_plan(dt, case.b, case.N(N_CU), case.K, epi, ks_, flags, case.wf, N_CU, out)
+                finally:
+                    for key, _, back in case.tuning:
+                        assert l.omchat_op_set_tuning(key, back) == 0
+                assert rc == 0, (case.id, form, l.omchat_last_error().decode())
+                assert out[0] == family and out[1] == case.wf, (case.id, form, out[0], family)
+                for i, v in case.pins.items():
+                    assert out[i] == v, (case.id, form, "plan field", i, out[i], v)
+                seen.add((family, case.wf))
+    assert seen == X.QUANT_PAIRS, (seen ^ X.QUANT_PAIRS)
+    wide = {c.forms[0][2] for c in X.QUANT_CASES if c.wide}
+    assert wide == {f for f, w in X.QUANT_PAIRS if w == X.WF_MX4}, "one wide-exponent variant per MXFP4 family"
+    norm_rr = {(c.wf, c.forms[0][0] == "swiglu", c.pins.get(8)) for c in X.QUANT_CASES if c.norm and 8 in c.pins}
+    for wf in (X.WF_16, X.WF_E4M3, X.WF_MX4):      # every rows-per-wave answer of rows_per_wave for a norm launch (csrc/gemv.hip)
+        assert {r for w, s, r in norm_rr if w == wf and not s} == {1, 2, 4}
+        assert {r for w, s, r in norm_rr if w == wf and s} == ({1, 2, 3} if wf == X.WF_16 else {1, 2, 4})
+    assert {c.b for c in X.QUANT_CASES if c.packed} == {1, 16, 17, 32}
+
+
+CORRUPTIONS = ("nibbles", "last_scale", "next_row_scale", "drop32", "swap_gate_up")
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", X.QUANT_CASES, ids=QIDS)
+def test_quant_reference_discriminates(dt, case):
+    """a kernel that swaps the nibbles of a byte, takes the neighbouring block's or the next row's scale, drops the last 32 k, crosses gate and up in
+    the last block or adds the bias before the e4m3 scale would have computed on other operands: each must change at least one expected
+    element of every form it applies to"""
+    ops = case.operands(dt, N_CU)
+    for form, ks, _ in case.forms:
+        want = X.quant_reference(ops, form, dt)
+        for kind in CORRUPTIONS:
+            if kind == "swap_gate_up" and not form.startswith("swiglu"):
+                continue
+            bad = X.corrupt(ops, kind, dt)
+            if bad is None:
+                continue
+            other = X.quant_reference(bad, form, dt)
+            assert not torch.equal(other, want), (case.id, form, kind, "changes no expected element")
+        if form == "bias" and case.wf == X.WF_E4M3:
+            assert not torch.equal(X.bias_before_scale(ops, dt), want), (case.id, "bias before the scale changes no expected element")

@@ -7,8 +7,9 @@ results below fp32's smallest normal number, within gemm_exact_ref.tail_floor: t
 Each form first asks omchat_op_gemv_plan which family the launch takes on this device and asserts the one the case is listed under, so a
 later change to the plan cannot silently move a case to another kernel.  Y carries a sentinel in its ldy padding and in guard rows behind
 row b, which must survive.  The K ranges of the EPI_PARTIAL slices are the kernels' own business: asserted are that every slice holds
-integers (a partial sum of integer products) and that the slices add up to the exact product.  Norm-in-GEMV forms (the rsqrt makes them
-inexact) and quantised weights are out of scope here."""
+integers (a partial sum of integer products) and that the slices add up to the exact product.  The norm-in-GEMV forms (on an x whose
+normalised row does not depend on the last bits of the rsqrt), the quantised weights and the seven-wave residual form are held to the same
+standard in tests/test_gpu_gemv_quant_exact.py."""
 import ctypes as C
 import pytest
 import torch
