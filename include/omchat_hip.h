@@ -772,6 +772,12 @@ int omchat_op_resid_rmsnorm(int dtype, void* x, int ldx, const float* part, int 
                             float eps, int pack_nb, void* stream);
 int omchat_op_vit_qknorm(int dtype, void* qkv, int ld, const void* wq, const void* wk, int rows, int C, int C_total,
                          float eps, float q_scale, void* stream);
+/* test hooks: omchat_op_vit_qknorm with the statistics given (sumsq_in [rows, 2] fp32: the q and the k sum of squares of a row over ALL C_total
+ * channels, the tensor-parallel form; NULL = the row's own) and / or the K half alone (only_k != 0, needs sumsq_in); omchat_op_vit_qk_sumsq
+ * writes those [rows, 2] sums for the q | k columns [0, C) | [C, 2C) of rows of stride ld */
+int omchat_op_vit_qknorm_ex(int dtype, void* qkv, int ld, const void* wq, const void* wk, int rows, int C, int C_total,
+                            float eps, float q_scale, const float* sumsq_in, int only_k, void* stream);
+int omchat_op_vit_qk_sumsq(int dtype, const void* qkv, int ld, int rows, int C, float* sumsq_out, void* stream);
 /* q [b,Sq,Hq,128], k/v [b,Hkv,Skv,128] (cache layout), out [b,Sq,Hq,128]; kv_len device int32 [b] or NULL */
 int omchat_op_attn_prefill(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Sq, int Skv,
                            int Hq, int Hkv, const int32_t* kv_len, int causal, int q_pos0, float scale, void* stream);

@@ -145,6 +145,8 @@ _SIGS = {
     "omchat_op_rmsnorm": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "omchat_op_resid_rmsnorm": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "omchat_op_vit_qknorm": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
+    "omchat_op_vit_qknorm_ex": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _vp, _i, _vp]),
+    "omchat_op_vit_qk_sumsq": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "omchat_op_attn_prefill": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp]),
     "omchat_op_attn_prefill_d": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp]),
     "omchat_op_layernorm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

@@ -221,6 +221,16 @@ extern "C" int omchat_op_vit_qknorm(int dtype, void* qkv, int ld, const void* wq
                                     float q_scale, void* stream) {
   return launch_vit_qknorm(dtype, qkv, ld, wq, wk, rows, C, C_total, eps, q_scale, nullptr, S(stream));
 }
+// test hooks: the same launch with externally reduced statistics (sumsq_in [rows, 2], the tensor-parallel form) and / or the K half alone,
+// and the [rows, 2] sums of squares that form all-reduces
+extern "C" int omchat_op_vit_qknorm_ex(int dtype, void* qkv, int ld, const void* wq, const void* wk, int rows, int C, int C_total, float eps,
+                                       float q_scale, const float* sumsq_in, int only_k, void* stream) {
+  return launch_vit_qknorm(dtype, qkv, ld, wq, wk, rows, C, C_total, eps, q_scale, sumsq_in, S(stream), only_k);
+}
+extern "C" int omchat_op_vit_qk_sumsq(int dtype, const void* qkv, int ld, int rows, int C, float* sumsq_out, void* stream) {
+  OM_CHECK(qkv && sumsq_out, "null argument");
+  return launch_vit_qk_sumsq(dtype, qkv, ld, rows, C, sumsq_out, S(stream));
+}
 
 extern "C" int omchat_op_attn_prefill(int dtype, const void* q, const void* k, const void* v, void* out, int b, int Sq, int Skv, int Hq,
                                       int Hkv, const int32_t* kv_len, int causal, int q_pos0, float scale, void* stream) {

@@ -732,7 +732,8 @@ static int vit_run(omchat_ctx* ctx, const void* pixels, int B, int n_layers, hip
   const omchat_config& c = ctx->c;
   const int C = c.v_hidden, I = c.v_mlp, Cq = ctx->v_Cq, np = ctx->v_np, ntok = ctx->v_ntok, M = B * ntok;
   const bool lead = ctx->tp_rank == 0;
-  const bool fused = g_vit_fused && ctx->tp_size == 1 && c.v_norm_type == 0 && !c.v_no_qk_norm && ctx->v_hd == 128 && Cq % 64 == 0 && Cq / 64 <= 256;
+  // (Cq / 64 <= 64: vit_knorm_slots sums the q / k slots one per lane of a wave -- up to 32 heads of 128; a wider tower takes the round-5 layer)
+  const bool fused = g_vit_fused && ctx->tp_size == 1 && c.v_norm_type == 0 && !c.v_no_qk_norm && ctx->v_hd == 128 && Cq % 64 == 0 && Cq / 64 <= 64;
   if (fused) TRY(ensure_vit_folded(ctx, s));
   // InternVisionEmbeddings.forward (modeling_intern_vit.py:90-102)
   TRY(launch_im2col(ctx->dt, pixels, ctx->vw_cols, B, c.v_image, c.v_patch, ctx->v_kpad, s));

@@ -163,6 +163,14 @@ def _randint(g, lo, hi, shape):
     return torch.randint(lo, hi + 1, shape, generator=g).to(torch.float64)
 
 
+randint = _randint
+
+
+def pow2_scale(M):
+    """per-row factors 4, 2, 1, 1/2 -- rsqrt of the powers of four 1/16 .. 4; adjacent rows differ by a factor of at least 2"""
+    return 2.0 ** (1 - ((torch.arange(M) * 3 + 1) % 4).to(torch.float64))
+
+
 def make_operands(seed, M, N, K, dt, a_max=A_MAX, w_max=W_MAX):
     """A [M, K], W [N, K], bias [N], ls [N], resid [M, N], row_scale [M] as float64 tensors of integers and dyadics, with the exactness
     preconditions asserted (see the module docstring).  row_scale differs from row to row; ls is never 0."""
