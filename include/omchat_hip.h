@@ -375,6 +375,23 @@ int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float length_penalt
  * prompt that is over is frozen, so a step enqueued ahead of reading the word changes nothing.  Under tensor parallelism the candidates
  * cross ranks through one fp32 all-reduce; every rank takes the same decisions.  No host sync. */
 int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, int32_t* next_tokens, int32_t* done_word, void* stream);
+/* omchat_beam_processors: the search begun by omchat_beam_begin ranks processed scores, as HF's _beam_search does with a repetition penalty
+ * and the token bans of omchat_set_constraints: per running row lp = log_softmax(logits) in fp32; for every id of the row's history in
+ * [0, t_vocab_total) lp = lp < 0 ? lp * rep_penalty : lp / rep_penalty; the ids HF's NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength,
+ * SuppressTokens and SuppressTokensAtBegin processors exclude become -inf; then + the running score and the finish of the plain search, with
+ * the processed lp where the tie order names the raw logit.  The history of a row is its prompt row as passed (prompt_ids host int32
+ * [b][prompt_len]; the -200 image sentinel is an ordinary value for matching and is ignored by the penalty) plus the ids along the beam's
+ * own path: it follows the backpointers on the device.  The lists are those of omchat_set_constraints; the EOS ids of the two length
+ * bounds and of dropped one-EOS bad words are the search's own.  Valid only between omchat_beam_begin and the first omchat_beam_step.
+ * rep_penalty == 1 with nothing to ban leaves the search plain (the same launches).  Refused before anything is enqueued or changed:
+ * rep_penalty <= 0, values above the caps, tensor-parallel contexts, and t_vocab_total - (n_suppress + n_begin_suppress + n_bad_words +
+ * n_eos + prompt_len + max_new) < max(2, 1 + n_eos) * num_beams (the bans could leave a row fewer finite scores than a step keeps).  Every
+ * fed id is in [0, t_vocab_total).  The histories and two bitmaps per row are grown on demand and counted in omchat_device_bytes.  The
+ * pick's own constraint state stays off.  Synchronises. */
+int omchat_beam_processors(omchat_ctx* ctx, float rep_penalty, int no_repeat_ngram_size, int min_new_tokens, int min_length,
+                           const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
+                           const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
+                           int prompt_len, void* stream);
 /* The best num_return (<= N) finished hypotheses of every prompt, best first: tokens host int32 [b*num_return][max_len] (generated ids
  * only), lengths host int32 [b*num_return], scores host fp32 [b*num_return] (HF's sequences_scores).  Synchronises the device.  After a
  * beam search the cache rows hold running beams, not the returned hypotheses; omchat_kv_rewind leaves the beam state alone. */
@@ -1020,6 +1037,20 @@ int omchat_op_top_logprobs(const float* logits, int b, int V, int ld, int top_n,
 size_t omchat_beam_state_words(int b, int N, int max_new);
 int omchat_op_beam_select(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty, int early_stopping,
                           const int32_t* eos_ids, int n_eos, int32_t* state, int32_t* tokens, int32_t* parents, int32_t* done_word, void* stream);
+/* the same step on processed scores (test hook of the selection behind omchat_beam_processors): omchat_op_beam_select's arguments, then the
+ * rows' histories as omchat_op_constrain takes them (hist_ids host int32, the rows one after another, hist_len / prompt_len host int32
+ * [rows]), the repetition penalty and the lists.  A penalty of 1 with nothing to ban runs omchat_op_beam_select itself.  Synchronises. */
+int omchat_op_beam_select_processed(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty,
+                                    int early_stopping, const int32_t* eos_ids, int n_eos, int32_t* state, int32_t* tokens, int32_t* parents,
+                                    int32_t* done_word, const int32_t* hist_ids, const int32_t* hist_len, const int32_t* prompt_len,
+                                    float rep_penalty, int no_repeat_ngram_size, int min_new_tokens, int min_length, const int32_t* suppress_ids,
+                                    int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress, const int32_t* bad_word_ids,
+                                    const int32_t* bad_word_offsets, int n_bad_words, void* stream);
+/* per-path histories (test hook of the beam step's history move; all pointers device): dst[r][P, P + g) = src[parents[r]][P, P + g),
+ * dst[r][P + g] = tokens[r], len[r] = P + g + 1 for the rows [rows][ld] (N rows per prompt; a parent outside the row's prompt counts as the
+ * row itself; P + g + 1 <= ld); bitmap_words words at bitmaps are zeroed.  No host sync. */
+int omchat_op_beam_hist_move(const int32_t* src, int32_t* dst, int rows, int N, int ld, int P, int g, const int32_t* parents,
+                             const int32_t* tokens, int32_t* len, uint32_t* bitmaps, size_t bitmap_words, void* stream);
 /* KV-cache rows between sequences (test hook of the beam step's gather): k / v 16-bit [layers][rows_cap][kvh][max_seq][128]; k8 / v8 (e4m3
  * bytes, same layout) and ks / vs (fp32 [layers][rows_cap][kvh][max_seq]) or NULL.  Row r in [row0, row0 + nrows) becomes a copy of
  * parents[r] (device int32, values in [row0, row0 + nrows)) over slots [lo, hi), for any parent map (cycles, repeats); parents == NULL:

@@ -87,6 +87,7 @@ _SIGS = {
     "omchat_beam_begin": (_i, [_vp, _i, _i, _f, _i, _vp, _i, _i, _i, _vp]),
     "omchat_beam_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_beam_result": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "omchat_beam_processors": (_i, [_vp, _f, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "omchat_decode_verify": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "omchat_decode_step_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "omchat_masked_decode_begin": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
@@ -206,6 +207,9 @@ _SIGS = {
     "omchat_op_constrain": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "omchat_beam_state_words": (_sz, [_i, _i, _i]),
     "omchat_op_beam_select": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "omchat_op_beam_select_processed": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i,
+                                             _vp, _i, _vp, _vp, _i, _vp]),
+    "omchat_op_beam_hist_move": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "omchat_op_kv_gather": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "omchat_op_fill_uniform": (_i, [_i, _vp, _i64, _u64, _f, _f, _vp]),
     "omchat_preproc_plan": (_i, [_i, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

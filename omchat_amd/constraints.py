@@ -23,9 +23,10 @@ def _id_list(x):
     return [int(i) for i in (x if isinstance(x, (list, tuple)) else [x])]
 
 
-def resolve_constraints(generation_config, kwargs, eos, vocab_total, num_beams=1, lookup=False):
+def resolve_constraints(generation_config, kwargs, eos, vocab_total, num_beams=1, lookup=False, *, beam_processors=False):
     """Pops the constraint arguments from `kwargs` (None -> generation_config).  -> None when no constraint is set, else the keyword
-    arguments of Engine.set_constraints.  eos: the resolved EOS ids of the call."""
+    arguments of Engine.set_constraints.  eos: the resolved EOS ids of the call.  beam_processors: generate(beam_processors=True) -- with
+    num_beams > 1 the arguments are resolved for Engine.beam_processors (resolve_beam_processors) and not refused."""
     gc = generation_config
     for name in UNSUPPORTED:
         v = kwargs.pop(name, None)
@@ -69,7 +70,7 @@ def resolve_constraints(generation_config, kwargs, eos, vocab_total, num_beams=1
     sup, bsup = _id_list(got["suppress_tokens"]), _id_list(got["begin_suppress_tokens"])
     if not (n or words or min_new or min_len or sup or bsup):
         return None
-    if num_beams > 1:
+    if num_beams > 1 and not beam_processors:
         raise NotImplementedError("no_repeat_ngram_size / bad_words_ids / min_new_tokens / min_length / suppress_tokens / begin_suppress_tokens "
                                   "with num_beams > 1 are not implemented: HF applies them to log-softmax scores inside the beam scorer")
     if lookup:
@@ -87,3 +88,33 @@ def resolve_constraints(generation_config, kwargs, eos, vocab_total, num_beams=1
         raise ValueError(f"bad_words_ids: at most {MAX_BAD_WORDS} words and {MAX_BAD_WORD_IDS} ids in total")
     return dict(no_repeat_ngram_size=n, bad_words_ids=words or [], min_new_tokens=min_new, min_length=min_len, eos=eos, suppress_tokens=sup,
                 begin_suppress_tokens=bsup)
+
+
+def resolve_beam_processors(con, repetition_penalty, num_beams, eos, vocab_total, prompt_len, max_new, tp_size=1):
+    """generate(num_beams > 1, beam_processors=True): `con` (resolve_constraints' result or None) and the repetition penalty -> the keyword
+    arguments of Engine.beam_processors, or None when nothing changes the scores (the plain search).  eos: the search's EOS ids;
+    prompt_len: the prompt row's length in tokens.  Every refusal is raised here, from host data, before any work is enqueued."""
+    rp = 1.0 if repetition_penalty is None else repetition_penalty
+    if isinstance(rp, bool) or not isinstance(rp, (int, float, np.integer, np.floating)) or not rp > 0:
+        raise ValueError(f"`penalty` has to be a strictly positive float, but is {rp}")
+    rp = float(np.float32(rp))
+    if not np.isfinite(rp):
+        raise ValueError(f"`penalty` has to be a finite float, but is {repetition_penalty}")
+    if con is None and rp == 1.0:
+        return None
+    if tp_size != 1:
+        raise NotImplementedError("beam_processors=True under tensor parallelism is not implemented (DESIGN.md section 7): the row's "
+                                  "log-sum-exp would need an exchange of its own in front of the selection")
+    con = con or dict(no_repeat_ngram_size=0, bad_words_ids=[], min_new_tokens=0, min_length=0, suppress_tokens=[], begin_suppress_tokens=[])
+    eos = [int(e) for e in eos]      # as the search takes them: its candidates per step count the ids as passed
+    words = [w for w in con["bad_words_ids"] if not (len(w) == 1 and w[0] in eos)]      # HF drops a bad word that is one EOS id
+    KB = max(2, 1 + len(eos)) * int(num_beams)
+    n_sup, n_bsup = len(con["suppress_tokens"]), len(con["begin_suppress_tokens"])
+    left = int(vocab_total) - (n_sup + n_bsup + len(words) + len(eos) + int(prompt_len) + int(max_new))
+    if left < KB:
+        raise ValueError(f"beam_processors=True: the bans could leave a beam row fewer than {KB} finite scores (max(2, 1 + n_eos) * num_beams): "
+                         f"vocabulary {vocab_total} - ({n_sup} suppress_tokens + {n_bsup} begin_suppress_tokens + {len(words)} bad words + "
+                         f"{len(eos)} eos ids + {prompt_len} prompt tokens + {max_new} new tokens) = {left}")
+    return dict(repetition_penalty=rp, no_repeat_ngram_size=con["no_repeat_ngram_size"], bad_words_ids=con["bad_words_ids"],
+                min_new_tokens=con["min_new_tokens"], min_length=con["min_length"], suppress_tokens=con["suppress_tokens"],
+                begin_suppress_tokens=con["begin_suppress_tokens"])

@@ -6,7 +6,14 @@
 // exp(x - max) (integers, so the sum does not depend on order) and the slice's top K raw (value, global index) pairs.  The vocabulary is cut
 // into the same slices at every TP degree (beam_slices), so a rank owns whole slices and the exchange table -- zero-filled, every rank
 // writes its own slices, one fp32 all-reduce -- holds the same numbers as a TP = 1 run.  x -> fl(fl(x - max) - lse) + r is monotone in
-// x within a row, so the prompt's top K accumulated candidates are inside the union of the rows' top K raw logits.
+// x within a row, so the prompt's top K accumulated candidates are inside the union of the rows' top K raw logits.  That argument holds for
+// the plain search only.  With omchat_beam_processors a ban removes candidates and the repetition penalty moves the seen ids, so the
+// selection runs on the processed log-probabilities themselves: a statistics launch (SEL_STATS) leaves the slices' maxima and sums in the
+// table, the selection launch (SEL_PROC) recomputes the row's max and lse from them -- every workgroup of a row the same numbers, in slice
+// order -- applies penalty and ban in registers from two bitmaps (constrain.hip's ban pass builds both from the row's own path history) and
+// keeps the top K (lp, index) pairs; beam_finish_kernel then takes the table's values as log-probabilities (BeamFinishArgs::proc).
+// fl(lp + r) is monotone in lp, so the same union argument holds for the processed values.  The histories follow the backpointers in
+// beam_hist_move_kernel, which also clears the two bitmaps (a vocabulary slice does not own whole bitmap words, so no reader can).
 //
 // beam_finish_kernel (one workgroup per prompt) merges the slices, scores the candidates in HF's order of fp32 operations and updates the
 // running beams, the finished set and the per-prompt done flag.  A done prompt is frozen: later steps leave its state alone.
@@ -30,9 +37,29 @@ constexpr int FIN_THREADS = 256;
 __device__ __forceinline__ bool beats(float v, int g, float v2, int g2) { return v > v2 || (v == v2 && g < g2); }
 
 // ---------------------------------------------------------------------------------------------------------------- select
+// a row's max and log-sum-exp from its ns table entries: the slices' sums rebased to the row max in fp64, in slice order
+__device__ __forceinline__ void row_lse(const float* tr, int ns, int K, float& M_out, float& L_out) {
+  float M = -INFINITY;
+  for (int s = 0; s < ns; ++s) M = fmaxf(M, tr[s * (4 + 2 * K)]);
+  double S = 0.0;
+  for (int s = 0; s < ns; ++s) {
+    const float* e = tr + s * (4 + 2 * K);
+    const unsigned long long q = (unsigned long long)e[1] + ((unsigned long long)e[2] << 21) + ((unsigned long long)e[3] << 42);
+    S += ldexp((double)q, -32) * exp((double)e[0] - (double)M);
+  }
+  M_out = M;
+  L_out = (float)log(S);
+}
+
+// SEL_PLAIN: statistics and the top K raw logits (the plain search, every TP degree); SEL_STATS: the statistics alone; SEL_PROC: the top K
+// processed log-probabilities, from a table that holds the statistics of every slice of the row (TP = 1)
+enum { SEL_PLAIN = 0, SEL_STATS = 1, SEL_PROC = 2 };
+struct SelProc { const uint32_t* ban = nullptr; const uint32_t* seen = nullptr; int bmw = 0; float penalty = 1.f; };
+
 // grid (slices of this rank, rows); table row: [ns][4 + 2K] fp32 = max, three 21-bit limbs of the fixed-point sum, K x (value, global index)
+template <int MODE>
 __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(const float* logits, int ld, int sl, int s0, int gbase, int ns, int K,
-                                                                  float* table) {
+                                                                  float* table, SelProc pr) {
   const int row = blockIdx.y, sloc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const float* x = logits + (size_t)row * ld + (size_t)sloc * sl;
   __shared__ float red_v[SEL_THREADS / 64];
@@ -47,31 +74,53 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(const float* l
     v[k] = i < sl ? x[i] : -INFINITY;
     m = fmaxf(m, v[k]);
   }
-  m = wave_max(m);
-  if (lane == 0) red_v[wid] = m;
-  __syncthreads();
-  m = red_v[0];
-#pragma unroll
-  for (int w = 1; w < SEL_THREADS / 64; ++w) m = fmaxf(m, red_v[w]);
-  // fixed-point sum: terms below 2^-33 of the max round to 0 and are skipped
-  unsigned long long acc = 0;
-#pragma unroll
-  for (int k = 0; k < SEL_PER; ++k) {
-    const double d = (double)v[k] - (double)m;
-    if (d >= -23.0) acc += (unsigned long long)llrint(exp(d) * BEAM_FIX);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) red_s[wid] = acc;
   float* out = table + (size_t)row * ns * (4 + 2 * K) + (size_t)(s0 + sloc) * (4 + 2 * K);
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long s = 0;
-    for (int w = 0; w < SEL_THREADS / 64; ++w) s += red_s[w];
-    out[0] = m;
-    out[1] = (float)(s & 0x1FFFFFull);
-    out[2] = (float)((s >> 21) & 0x1FFFFFull);
-    out[3] = (float)(s >> 42);
+  if (MODE != SEL_PROC) {
+    m = wave_max(m);
+    if (lane == 0) red_v[wid] = m;
+    __syncthreads();
+    m = red_v[0];
+#pragma unroll
+    for (int w = 1; w < SEL_THREADS / 64; ++w) m = fmaxf(m, red_v[w]);
+    // fixed-point sum: terms below 2^-33 of the max round to 0 and are skipped
+    unsigned long long acc = 0;
+#pragma unroll
+    for (int k = 0; k < SEL_PER; ++k) {
+      const double d = (double)v[k] - (double)m;
+      if (d >= -23.0) acc += (unsigned long long)llrint(exp(d) * BEAM_FIX);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) red_s[wid] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long s = 0;
+      for (int w = 0; w < SEL_THREADS / 64; ++w) s += red_s[w];
+      out[0] = m;
+      out[1] = (float)(s & 0x1FFFFFull);
+      out[2] = (float)((s >> 21) & 0x1FFFFFull);
+      out[3] = (float)(s >> 42);
+    }
+    if (MODE == SEL_STATS) return;
+  } else {
+    // HF's order: log_softmax, RepetitionPenaltyLogitsProcessor on the log-probabilities, then the bans
+    __shared__ float s_ml[2];
+    if (tid == 0) row_lse(table + (size_t)row * ns * (4 + 2 * K), ns, K, s_ml[0], s_ml[1]);
+    __syncthreads();
+    const float M = s_ml[0], L = s_ml[1];
+    const uint32_t* bb = pr.ban + (size_t)row * pr.bmw;
+    const uint32_t* sb = pr.seen ? pr.seen + (size_t)row * pr.bmw : nullptr;
+#pragma unroll
+    for (int k = 0; k < SEL_PER; ++k) {
+      const int i = k * SEL_THREADS + tid;
+      if (i >= sl) continue;
+      const int g = gbase + sloc * sl + i;      // < bmw * 32 (launch_beam_select_processed)
+      const uint32_t bit = 1u << (g & 31);
+      float lp = __fsub_rn(__fsub_rn(v[k], M), L);
+      if (sb && (sb[g >> 5] & bit)) lp = lp < 0.f ? __fmul_rn(lp, pr.penalty) : __fdiv_rn(lp, pr.penalty);
+      if (bb[g >> 5] & bit) lp = -INFINITY;
+      v[k] = lp;
+    }
   }
   // top K by (value desc, index asc): K rounds of a block argmax over every thread's best remaining element
   float bv = -INFINITY; int bk = -1;
@@ -161,22 +210,12 @@ __global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(BeamFinishArgs
   const bool frozen = s_done_old != 0;
   if (!frozen) {
     // lse of every row: the slices' sums rebased to the row max in fp64, in slice order
-    if (tid < rows_pp) {
-      const float* tr = a.table + (size_t)(rbase + tid) * TS;
-      float M = -INFINITY;
-      for (int s = 0; s < ns; ++s) M = fmaxf(M, tr[s * (4 + 2 * K)]);
-      double S = 0.0;
-      for (int s = 0; s < ns; ++s) {
-        const float* e = tr + s * (4 + 2 * K);
-        const unsigned long long q = (unsigned long long)e[1] + ((unsigned long long)e[2] << 21) + ((unsigned long long)e[3] << 42);
-        S += ldexp((double)q, -32) * exp((double)e[0] - (double)M);
-      }
-      sM[tid] = M;
-      sL[tid] = (float)log(S);
-    }
+    // (a.proc: the selection pass has applied it already, the table's values are log-probabilities)
+    if (tid < rows_pp && !a.proc) row_lse(a.table + (size_t)(rbase + tid) * TS, ns, K, sM[tid], sL[tid]);
     __syncthreads();
-    // a row with fewer than K finite logits leaves survivor slots unwritten: they start as -inf with distinct out-of-vocabulary ids, so
-    // the ranking below stays a permutation (such a row is outside the contract: model logits are finite)
+    // a row with fewer than K finite values leaves survivor slots unwritten: they start as -inf with distinct out-of-vocabulary ids, so
+    // the ranking below stays a permutation.  Such a row is outside the contract: model logits are finite, and omchat_beam_processors
+    // refuses lists and lengths whose bans could leave a row fewer than K of them.  Under a.proc an id of such a slot is fed as 0.
     for (int e = tid; e < rows_pp * K; e += FIN_THREADS) { sv_acc[e] = -INFINITY; sv_raw[e] = -INFINITY; sv_g[e] = a.V_total + e; }
     __syncthreads();
     // each row's top K over its slices' sorted lists: rank = position in its own list + entries of the other lists that beat it
@@ -200,7 +239,7 @@ __global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(BeamFinishArgs
       if (rank < K) {
         const float r0 = t == 0 ? 0.f : ld_f(run + i * N + j);
         // HF: log_softmax = (x - max) - log(sum), then + running score, all fp32
-        const float lp = __fsub_rn(__fsub_rn(v, sM[j]), sL[j]);
+        const float lp = a.proc ? v : __fsub_rn(__fsub_rn(v, sM[j]), sL[j]);
         sv_acc[j * K + rank] = __fadd_rn(lp, r0);
         sv_raw[j * K + rank] = v;
         sv_g[j * K + rank] = g;
@@ -252,7 +291,7 @@ __global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(BeamFinishArgs
     if (tid < N) {
       const int r = i * N + tid, k = new_run[tid];
       st_f(run + r, c_trl[k]);
-      a.tokens[r] = c_tok[k];
+      a.tokens[r] = a.proc && c_tok[k] >= a.V_total ? 0 : c_tok[k];
       a.parents[r] = t == 0 ? r : i * N + c_row[k];
       bp[2 * r] = c_row[k]; bp[2 * r + 1] = c_tok[k];
       const int e = new_fin[tid];
@@ -347,7 +386,54 @@ __global__ __launch_bounds__(256) void kv_gather_kernel(KvGatherArgs a, const in
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- path histories
+constexpr int HM_CLEAR = 64;      // workgroups behind the row ones that zero the bitmaps
+
+// workgroups [0, rows): row r of dst takes its parent's generated ids and the token it was just given; the others zero bm[0, bm_words)
+__global__ __launch_bounds__(256) void beam_hist_move_kernel(const int32_t* src, int32_t* dst, int rows, int N, int ld, int P, int g,
+                                                             const int* parents, const int* tokens, int* len, uint32_t* bm, size_t bm_words) {
+  const int r = blockIdx.x, tid = threadIdx.x;
+  if (r >= rows) {
+    for (size_t i = (size_t)(r - rows) * 256 + tid; i < bm_words; i += (size_t)HM_CLEAR * 256) bm[i] = 0u;
+    return;
+  }
+  int p = parents[r];
+  if (p < r / N * N || p >= r / N * N + N) p = r;      // (never, behind beam_finish_kernel: no read outside the prompt's rows)
+  const int32_t* s = src + (size_t)p * ld + P;
+  int32_t* d = dst + (size_t)r * ld + P;
+  for (int i = tid; i < g; i += 256) d[i] = s[i];
+  if (tid == 0) { d[g] = tokens[r]; len[r] = P + g + 1; }
+}
+
 }  // namespace
+
+int launch_beam_stats(const float* logits, int ld, int rows, int V, int ns, int K, float* table, hipStream_t s) {
+  OM_CHECK(ns >= 1 && K >= 1 && K <= BEAM_KMAX && rows >= 1 && V % ns == 0 && V / ns <= BEAM_SLICE_CAP, "beam statistics: bad geometry");
+  hipLaunchKernelGGL(beam_select_kernel<SEL_STATS>, dim3(ns, rows), dim3(SEL_THREADS), 0, s, logits, ld, V / ns, 0, 0, ns, K, table, SelProc{});
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_beam_select_processed(const float* logits, int ld, int rows, int V, int ns, int K, float* table, const uint32_t* ban,
+                                 const uint32_t* seen, int bmw, float penalty, hipStream_t s) {
+  OM_CHECK(ns >= 1 && K >= 1 && K <= BEAM_KMAX && rows >= 1 && V % ns == 0 && V / ns <= BEAM_SLICE_CAP, "beam select: bad geometry");
+  OM_CHECK(ban && (int64_t)bmw * 32 >= V && penalty > 0.f && isfinite(penalty), "beam select: bitmaps narrower than the vocabulary, or penalty <= 0");
+  SelProc pr;
+  pr.ban = ban; pr.seen = seen; pr.bmw = bmw; pr.penalty = penalty;
+  hipLaunchKernelGGL(beam_select_kernel<SEL_PROC>, dim3(ns, rows), dim3(SEL_THREADS), 0, s, logits, ld, V / ns, 0, 0, ns, K, table, pr);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_beam_hist_move(const int32_t* src, int32_t* dst, int rows, int N, int ld, int P, int g, const int* parents, const int* tokens, int* len,
+                          uint32_t* bm, size_t bm_words, hipStream_t s) {
+  OM_CHECK(rows >= 0 && N >= 1 && (rows == 0 || (src && dst && src != dst && parents && tokens && len && P >= 0 && g >= 0 && P + g + 1 <= ld)),
+           "beam history: no room for one more id, or a null buffer");
+  OM_CHECK(bm || bm_words == 0, "beam history: null bitmaps");
+  hipLaunchKernelGGL(beam_hist_move_kernel, dim3(rows + HM_CLEAR), dim3(256), 0, s, src, dst, rows, N, ld, P, g, parents, tokens, len, bm, bm_words);
+  OM_LAUNCH_CHECK();
+  return 0;
+}
 
 int beam_slices(int V_total, int tp) {
   if (V_total < 1 || tp < 1) return -1;
@@ -364,7 +450,8 @@ int launch_beam_select(const float* logits, int ld, int rows, int V_local, int r
   OM_CHECK(ns >= 1 && ns % tp == 0 && K >= 1 && K <= BEAM_KMAX && rows >= 1, "beam select: bad geometry");
   const int nl = ns / tp, sl = V_local / nl;
   OM_CHECK(sl * nl == V_local && sl <= BEAM_SLICE_CAP, "beam select: the rank's vocabulary is not whole slices");
-  hipLaunchKernelGGL(beam_select_kernel, dim3(nl, rows), dim3(SEL_THREADS), 0, s, logits, ld, sl, rank * nl, rank * V_local, ns, K, table);
+  hipLaunchKernelGGL(beam_select_kernel<SEL_PLAIN>, dim3(nl, rows), dim3(SEL_THREADS), 0, s, logits, ld, sl, rank * nl, rank * V_local, ns, K, table,
+                     SelProc{});
   OM_LAUNCH_CHECK();
   return 0;
 }
@@ -446,6 +533,7 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_CHECK(!ctx->group.on(), "beam search: a sampled group shares its prompt (omchat_group_begin with b = 0 first)");
   BeamState::Search& B = ctx->beam.cur;
   B = BeamState::Search{};
+  ctx->beam.proc = BeamState::Proc{};
   B.b = b; B.N = N; B.KB = KB; B.max_new = max_new; B.P = prompt_tok_len; B.es = early_stopping; B.ns = ns; B.lp = length_penalty;
   B.eos.assign(eos_ids, eos_ids + n_eos);
   const int rows = b * N;
@@ -464,6 +552,74 @@ extern "C" int omchat_beam_begin(omchat_ctx* ctx, int b, int num_beams, float le
   OM_HIP(hipMemcpyAsync(ctx->beam.dn.p, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s));
   OM_HIP(hipStreamSynchronize(s));      // host vector
   B.on = true;
+  return 0;
+}
+
+// aux layout: [CON_LIST_WORDS id lists | len [b * N] | plen [b * N]]
+static ConstrainArgs beam_proc_ban_args(omchat_ctx* ctx, int rows) {
+  const BeamState::Search& B = ctx->beam.cur;
+  const BeamState::Proc& Q = ctx->beam.proc;
+  const int bN = B.b * B.N;
+  ConstrainArgs a;
+  // step 0 runs on the prompts' own rows: prompt i's history is row i * N of the first buffer
+  a.hist = (int32_t*)ctx->beam.hist.p + (size_t)(B.t & 1) * bN * Q.ld;
+  a.hist_ld = B.t == 0 ? B.N * Q.ld : Q.ld;
+  int32_t* aux = (int32_t*)ctx->beam.aux.p;
+  constrain_bind_lists(aux, a);
+  a.len = aux + CON_LIST_WORDS; a.plen = aux + CON_LIST_WORDS + bN;
+  a.b = rows; a.V = a.V_total = ctx->c.t_vocab_total; a.gbase = 0;
+  a.ngram = Q.ngram; a.min_new = Q.min_new; a.min_len = Q.min_len;
+  a.n_eos = Q.n_eos; a.n_sup = Q.n_sup; a.n_bsup = Q.n_bsup; a.n_bw = Q.n_bw;
+  a.ban = (uint32_t*)ctx->beam.bm.p; a.bmw = Q.bmw;
+  a.seen = Q.penalty != 1.f ? a.ban + (size_t)bN * Q.bmw : nullptr;
+  return a;
+}
+
+extern "C" int omchat_beam_processors(omchat_ctx* ctx, float rep_penalty, int no_repeat_ngram_size, int min_new_tokens, int min_length,
+                                      const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids, int n_begin_suppress,
+                                      const int32_t* bad_word_ids, const int32_t* bad_word_offsets, int n_bad_words, const int32_t* prompt_ids,
+                                      int prompt_len, void* stream) {
+  OM_CHECK(ctx, "null ctx");
+  BeamState::Search& B = ctx->beam.cur;
+  const omchat_config& c = ctx->c;
+  // every refusal before anything is enqueued or changed
+  OM_CHECK(B.on && B.t == 0, "beam processors: valid between omchat_beam_begin and the first omchat_beam_step");
+  OM_CHECK(ctx->tp_size == 1, "beam processors: tensor-parallel contexts are not implemented (DESIGN.md section 7): the row's log-sum-exp would need an exchange of its own in front of the selection");
+  OM_CHECK(isfinite(rep_penalty) && rep_penalty > 0.f, "beam processors: repetition_penalty must be a finite float > 0");
+  OM_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= CON_NGRAM_MAX, "beam processors: 0 <= no_repeat_ngram_size <= 64 (0 = off)");
+  OM_CHECK(min_new_tokens >= 0 && min_length >= 0, "beam processors: min_new_tokens and min_length >= 0");
+  OM_CHECK(prompt_ids && prompt_len >= 1, "beam processors: the b prompt rows [b][prompt_len], prompt_len >= 1");
+  std::vector<int32_t> lists(CON_LIST_WORDS);
+  ConstrainArgs la;
+  TRY(constrain_pack_lists(B.eos.data(), (int)B.eos.size(), suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_word_ids,
+                           bad_word_offsets, n_bad_words, lists.data(), la));
+  BeamState::Proc Q;
+  Q.penalty = rep_penalty; Q.ngram = no_repeat_ngram_size;
+  Q.min_new = la.n_eos ? min_new_tokens : 0; Q.min_len = la.n_eos ? min_length : 0;      // HF: no length processor without an EOS id
+  Q.n_eos = la.n_eos; Q.n_sup = la.n_sup; Q.n_bsup = la.n_bsup; Q.n_bw = la.n_bw;
+  if (Q.penalty == 1.f && !Q.ngram && !Q.min_new && !Q.min_len && !Q.n_sup && !Q.n_bsup && !Q.n_bw) return 0;      // the plain search
+  // the n-gram stage bans at most one id per history position, a bad word at most its last id: every row keeps KB finite scores
+  const int64_t can_ban = (int64_t)Q.n_sup + Q.n_bsup + Q.n_bw + Q.n_eos + prompt_len + B.max_new;
+  OM_CHECK(c.t_vocab_total - can_ban >= B.KB, "beam processors: the bans could leave a row fewer finite scores than the candidates kept per step");
+  const int bN = B.b * B.N;
+  Q.P = prompt_len; Q.ld = (prompt_len + B.max_new + 3) / 4 * 4; Q.bmw = (c.t_vocab_total + 31) / 32;
+  TRY(ctx->grow(ctx->beam.hist, (size_t)2 * bN * Q.ld * 4));
+  TRY(ctx->grow(ctx->beam.aux, ((size_t)CON_LIST_WORDS + 2 * (size_t)bN) * 4));
+  TRY(ctx->grow(ctx->beam.bm, (size_t)2 * bN * Q.bmw * 4));
+  // the prompt part of every row, in both buffers, written once
+  std::vector<int32_t> h((size_t)2 * bN * Q.ld, 0), len((size_t)2 * bN, prompt_len);
+  for (int u = 0; u < 2; ++u)
+    for (int r = 0; r < bN; ++r)
+      std::copy(prompt_ids + (size_t)(r / B.N) * prompt_len, prompt_ids + (size_t)(r / B.N + 1) * prompt_len, h.begin() + ((size_t)u * bN + r) * Q.ld);
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* aux = (int32_t*)ctx->beam.aux.p;
+  OM_HIP(hipMemcpyAsync(ctx->beam.hist.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(aux, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemcpyAsync(aux + CON_LIST_WORDS, len.data(), len.size() * 4, hipMemcpyHostToDevice, s));
+  OM_HIP(hipMemsetAsync(ctx->beam.bm.p, 0, (size_t)2 * bN * Q.bmw * 4, s));
+  OM_HIP(hipStreamSynchronize(s));      // host vectors and the caller's ids
+  Q.on = true;
+  ctx->beam.proc = Q;
   return 0;
 }
 
@@ -522,10 +678,20 @@ extern "C" int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, 
   hipStream_t s = (hipStream_t)stream;
   const size_t TS = (size_t)B.ns * (4 + 2 * B.KB);
   float* table = (float*)ctx->beam.table.p;
-  if (ctx->tp_size > 1) OM_HIP(hipMemsetAsync(table, 0, rows * TS * 4, s));
-  TRY(launch_beam_select(logits, c.t_vocab, rows, c.t_vocab, ctx->tp_rank, ctx->tp_size, B.ns, B.KB, table, s));
-  if (ctx->tp_size > 1) TRY(ctx->allreduce_f32(table, rows * TS, s));
+  const BeamState::Proc& Q = ctx->beam.proc;
+  if (Q.on) {
+    // (B.t < max_new, checked above, is the history's room: row length P + t <= ld - 1 here)
+    const ConstrainArgs ca = beam_proc_ban_args(ctx, rows);
+    TRY(launch_constrain_ban(ca, s));
+    TRY(launch_beam_stats(logits, c.t_vocab, rows, c.t_vocab, B.ns, B.KB, table, s));
+    TRY(launch_beam_select_processed(logits, c.t_vocab, rows, c.t_vocab, B.ns, B.KB, table, ca.ban, ca.seen, Q.bmw, Q.penalty, s));
+  } else {
+    if (ctx->tp_size > 1) OM_HIP(hipMemsetAsync(table, 0, rows * TS * 4, s));
+    TRY(launch_beam_select(logits, c.t_vocab, rows, c.t_vocab, ctx->tp_rank, ctx->tp_size, B.ns, B.KB, table, s));
+    if (ctx->tp_size > 1) TRY(ctx->allreduce_f32(table, rows * TS, s));
+  }
   BeamFinishArgs a;
+  a.proc = Q.on;
   a.table = table; a.ns = B.ns; a.K = a.KB = B.KB; a.V_total = c.t_vocab_total;
   a.b = B.b; a.N = B.N; a.t = B.t; a.max_new = B.max_new; a.es = B.es; a.lp_pos = B.lp > 0.f;
   a.dn = (const float*)ctx->beam.dn.p;
@@ -534,6 +700,15 @@ extern "C" int omchat_beam_step(omchat_ctx* ctx, const float* logits, int rows, 
   a.state = (int*)ctx->beam.state.p; a.tokens = next_tokens; a.parents = (int*)ctx->beam.parents.p; a.done_word = done_word;
   TRY(launch_beam_finish(a, s));
   const int bN = B.b * B.N;
+  if (Q.on) {
+    // the next step's histories: row r continues its parent's path with the token it was just given (nothing moves behind the last step);
+    // the launch also clears the two bitmaps this step's selection read
+    int32_t* h = (int32_t*)ctx->beam.hist.p;
+    int32_t* aux = (int32_t*)ctx->beam.aux.p;
+    const size_t half = (size_t)bN * Q.ld;
+    TRY(launch_beam_hist_move(h + (B.t & 1) * half, h + ((B.t + 1) & 1) * half, B.t + 1 < B.max_new ? bN : 0, B.N, Q.ld, Q.P, B.t, a.parents,
+                              next_tokens, aux + CON_LIST_WORDS, (uint32_t*)ctx->beam.bm.p, (size_t)2 * bN * Q.bmw, s));
+  }
   if (B.t == 0) {
     // fork: prompt i's row -> rows i*N .. i*N+N-1, last prompt first (its target rows lie above every source row not yet read)
     const KvGatherArgs g = beam_kv_args(ctx, false);

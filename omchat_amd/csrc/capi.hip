@@ -936,6 +936,92 @@ extern "C" int omchat_op_beam_select(const float* logits, int rows, int V, int b
   return rc;
 }
 
+extern "C" int omchat_op_beam_select_processed(const float* logits, int rows, int V, int b, int N, int t, int max_new, float length_penalty,
+                                               int early_stopping, const int32_t* eos_ids, int n_eos, int32_t* state, int32_t* tokens,
+                                               int32_t* parents, int32_t* done_word, const int32_t* hist_ids, const int32_t* hist_len,
+                                               const int32_t* prompt_len, float rep_penalty, int no_repeat_ngram_size, int min_new_tokens,
+                                               int min_length, const int32_t* suppress_ids, int n_suppress, const int32_t* begin_suppress_ids,
+                                               int n_begin_suppress, const int32_t* bad_word_ids, const int32_t* bad_word_offsets,
+                                               int n_bad_words, void* stream) {
+  OM_CHECK(logits && state && tokens && parents && b >= 1 && N >= 2 && N <= BEAM_NMAX, "bad argument");
+  OM_CHECK(n_eos >= 0 && n_eos <= BEAM_EOS_MAX && (n_eos == 0 || eos_ids), "at most 8 eos ids");
+  const int KB = std::max(2, 1 + n_eos) * N;
+  OM_CHECK(KB <= BEAM_KMAX && V >= KB, "max(2, 1 + n_eos) * N must not exceed 32 (nor V)");
+  OM_CHECK(t >= 0 && t < max_new && rows == (t == 0 ? b : b * N), "rows = b at t = 0, b * N afterwards");
+  OM_CHECK(early_stopping >= 0 && early_stopping <= 2, "early_stopping 0, 1 or 2");
+  OM_CHECK(hist_ids && hist_len && prompt_len, "the rows' histories, their lengths and the prompts' lengths");
+  OM_CHECK(isfinite(rep_penalty) && rep_penalty > 0.f, "repetition_penalty must be a finite float > 0");
+  OM_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= CON_NGRAM_MAX && min_new_tokens >= 0 && min_length >= 0, "constraint parameters out of range");
+  ConstrainArgs ca;
+  std::vector<int32_t> lists(CON_LIST_WORDS);
+  if (int rc = constrain_pack_lists(eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_word_ids, bad_word_offsets,
+                                    n_bad_words, lists.data(), ca)) return rc;
+  ca.ngram = no_repeat_ngram_size; ca.min_new = n_eos ? min_new_tokens : 0; ca.min_len = n_eos ? min_length : 0;
+  if (rep_penalty == 1.f && !ca.ngram && !ca.min_new && !ca.min_len && !ca.n_sup && !ca.n_bsup && !ca.n_bw)      // the plain search
+    return omchat_op_beam_select(logits, rows, V, b, N, t, max_new, length_penalty, early_stopping, eos_ids, n_eos, state, tokens, parents,
+                                 done_word, stream);
+  int maxL = 0; int64_t can_ban = (int64_t)ca.n_sup + ca.n_bsup + ca.n_bw + ca.n_eos;
+  for (int i = 0; i < rows; ++i) {
+    OM_CHECK(hist_len[i] >= 0 && prompt_len[i] >= 0, "history lengths out of range");
+    maxL = std::max(maxL, hist_len[i]);
+  }
+  OM_CHECK(V - (can_ban + maxL) >= KB, "the bans could leave a row fewer finite scores than the candidates kept per step");
+  const int ns = beam_slices(V, 1);
+  OM_CHECK(ns >= 1, "vocabulary cannot be sliced");
+  const size_t TS = (size_t)ns * (4 + 2 * KB);
+  std::vector<float> dn(max_new + 1, 1.f);
+  for (int g = 1; g <= max_new; ++g) dn[g] = (float)pow((double)g, (double)length_penalty);
+  const int ld = (maxL + 4) / 4 * 4, bmw = (V + 31) / 32;
+  std::vector<int32_t> h((size_t)rows * ld, 0);
+  size_t off = 0;
+  for (int i = 0; i < rows; ++i) {
+    std::copy(hist_ids + off, hist_ids + off + hist_len[i], h.begin() + (size_t)i * ld);
+    off += (size_t)hist_len[i];
+  }
+  const size_t tb = (rows * TS * 4 + 15) / 16 * 16, db = (dn.size() * 4 + 15) / 16 * 16, hb = h.size() * 4, lb = lists.size() * 4;
+  const size_t rb = ((size_t)rows * 4 + 15) / 16 * 16, bb = (size_t)2 * rows * bmw * 4;
+  char* mem = nullptr;
+  OM_HIP(hipMalloc(&mem, tb + db + hb + lb + 2 * rb + bb));
+  float* table = (float*)mem;
+  float* d_dn = (float*)(mem + tb);
+  int32_t* d_h = (int32_t*)(mem + tb + db);
+  int32_t* d_lists = (int32_t*)(mem + tb + db + hb);
+  int* d_len = (int*)(mem + tb + db + hb + lb);
+  int* d_plen = (int*)(mem + tb + db + hb + lb + rb);
+  uint32_t* d_bm = (uint32_t*)(mem + tb + db + hb + lb + 2 * rb);
+  hipStream_t s = S(stream);
+  hipMemcpyAsync(d_dn, dn.data(), dn.size() * 4, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_h, h.data(), hb, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_lists, lists.data(), lb, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_len, hist_len, (size_t)rows * 4, hipMemcpyHostToDevice, s);
+  hipMemcpyAsync(d_plen, prompt_len, (size_t)rows * 4, hipMemcpyHostToDevice, s);
+  hipMemsetAsync(d_bm, 0, bb, s);
+  ca.hist = d_h; ca.hist_ld = ld; ca.len = d_len; ca.plen = d_plen; ca.tok = nullptr;
+  ca.b = rows; ca.V = ca.V_total = V; ca.gbase = 0;
+  constrain_bind_lists(d_lists, ca);
+  ca.ban = d_bm; ca.bmw = bmw; ca.seen = rep_penalty != 1.f ? d_bm + (size_t)rows * bmw : nullptr;
+  int rc = launch_constrain_ban(ca, s);
+  if (!rc) rc = launch_beam_stats(logits, V, rows, V, ns, KB, table, s);
+  if (!rc) rc = launch_beam_select_processed(logits, V, rows, V, ns, KB, table, ca.ban, ca.seen, bmw, rep_penalty, s);
+  if (!rc) {
+    BeamFinishArgs a;
+    a.table = table; a.ns = ns; a.K = a.KB = KB; a.V_total = V; a.proc = true;
+    a.b = b; a.N = N; a.t = t; a.max_new = max_new; a.es = early_stopping; a.lp_pos = length_penalty > 0.f;
+    a.dn = d_dn; a.n_eos = n_eos;
+    for (int q = 0; q < n_eos; ++q) a.eos[q] = eos_ids[q];
+    a.state = state; a.tokens = tokens; a.parents = parents; a.done_word = done_word;
+    rc = launch_beam_finish(a, s);
+  }
+  hipStreamSynchronize(s);
+  hipFree(mem);
+  return rc;
+}
+
+extern "C" int omchat_op_beam_hist_move(const int32_t* src, int32_t* dst, int rows, int N, int ld, int P, int g, const int32_t* parents,
+                                        const int32_t* tokens, int32_t* len, uint32_t* bitmaps, size_t bitmap_words, void* stream) {
+  return launch_beam_hist_move(src, dst, rows, N, ld, P, g, parents, tokens, len, bitmaps, bitmap_words, S(stream));
+}
+
 extern "C" int omchat_op_kv_gather(int dtype, void* k, void* v, void* k8, void* v8, float* ks, float* vs, int layers, int rows_cap, int kvh,
                                    int max_seq, const int32_t* parents, int row0, int nrows, int fork_src, int lo, int hi, void* stream) {
   OM_CHECK(k && v && (dtype == OMCHAT_F16 || dtype == OMCHAT_BF16) && layers >= 1 && kvh >= 1 && max_seq >= 1, "bad argument");

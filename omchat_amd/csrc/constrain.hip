@@ -61,6 +61,11 @@ __global__ __launch_bounds__(256) void con_ban_kernel(ConstrainArgs a) {
       }
     }
   }
+  // the row's seen set (the repetition penalty of a beam search on processed scores, beam.hip): every id of the history, in a bitmap of its own
+  if (a.seen) {
+    uint32_t* sb = a.seen + (size_t)row * a.bmw;
+    for (int i = blockIdx.x * 256 + t; i < L; i += CON_CH * 256) con_ban(sb, H(i), a.gbase, a.V, a.V_total);
+  }
   if (blockIdx.x != 0) return;
   // NoBadWordsLogitsProcessor: a word of m ids bans its last id when the m - 1 ids in front equal the history's tail; m = 1 always bans,
   // words longer than the history are skipped

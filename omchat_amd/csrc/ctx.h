@@ -151,12 +151,17 @@ struct PickState {
 struct BeamState {
   struct Search { bool on = false; int b = 0, N = 0, KB = 0, max_new = 0, P = 0, es = 0, ns = 1, t = 0; float lp = 1.f; std::vector<int> eos; };
   Search cur;
-  Grown state, table, dn, parents, stash;
+  // the search runs on processed scores (omchat_beam_processors; off after every omchat_beam_begin): penalty and ban parameters, the two
+  // per-path history buffers [2][b * N][ld] used in turn (hist), the id lists with the rows' lengths behind them (aux) and the ban and seen
+  // bitmaps [2][b * N][bmw], all-zero between steps (bm)
+  struct Proc { bool on = false; float penalty = 1.f; int ngram = 0, min_new = 0, min_len = 0, n_eos = 0, n_sup = 0, n_bsup = 0, n_bw = 0, P = 0, ld = 0, bmw = 0; };
+  Proc proc;
+  Grown state, table, dn, parents, stash, hist, aux, bm;
   bool stash8 = false;
   std::vector<int> hpos, hlen;      // host sources of the fork's device lengths (alive until the next begin)
   bool on() const { return cur.on; }
   void end() { cur.on = false; }
-  void release() { for (Grown* g : {&state, &table, &dn, &parents, &stash}) g->release(); }
+  void release() { for (Grown* g : {&state, &table, &dn, &parents, &stash, &hist, &aux, &bm}) g->release(); }
 };
 
 // sampled groups (omchat_group_begin; beam.hip): the shared-prompt mode of the decode step -- b prompts x N sibling rows whose prompt keys

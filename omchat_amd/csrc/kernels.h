@@ -562,6 +562,7 @@ struct ConstrainArgs {
   const int32_t *eos = nullptr, *sup = nullptr, *bsup = nullptr, *bw_ids = nullptr, *bw_off = nullptr;
   int n_eos = 0, n_sup = 0, n_bsup = 0, n_bw = 0;
   uint32_t* ban = nullptr; int bmw = 0;             // [b][bmw] ban bitmap, all-zero on entry; bits of this pick's ban set are set
+  uint32_t* seen = nullptr;                         // [b][bmw] or NULL: the ids of the row's history (beam search's repetition penalty, beam.hip)
 };
 int launch_constrain_ban(const ConstrainArgs& a, hipStream_t s);
 // out [b][V] = logits with the banned ids at -inf; clears the bitmap; len (optional) += 1: the fed token the ban pass stored is now counted
@@ -666,9 +667,23 @@ struct BeamFinishArgs {
   int eos[BEAM_EOS_MAX] = {0}; int n_eos = 0;
   int* state = nullptr;                    // beam_state_words(b, N, max_new)
   int* tokens = nullptr; int* parents = nullptr; int* done_word = nullptr;      // [b * N], [b * N] (cache rows), 1 word
+  bool proc = false;                       // the table's values are processed log-probabilities (launch_beam_select_processed), not raw logits
 };
 int launch_beam_select(const float* logits, int ld, int rows, int V_local, int rank, int tp, int ns, int K, float* table, hipStream_t s);
 int launch_beam_finish(const BeamFinishArgs& a, hipStream_t s);
+// beam search on processed scores (omchat_beam_processors; tests/beam_proc_ref.py restates it; TP = 1 only).  Two launches in place of
+// launch_beam_select: the statistics pass leaves every (row, slice) max and fixed-point sum in the table; the selection pass recomputes the
+// row's (max, lse) from them, forms lp = fl(fl(x - max) - lse) in registers, scales the ids of `seen` (NULL: no penalty) by the repetition
+// penalty (lp < 0 ? lp * penalty : lp / penalty), sets the ids of `ban` to -inf and keeps each slice's top K (lp, id) pairs.  The bitmaps
+// [rows][bmw] are only read: launch_beam_hist_move clears them behind the finish.
+int launch_beam_stats(const float* logits, int ld, int rows, int V, int ns, int K, float* table, hipStream_t s);
+int launch_beam_select_processed(const float* logits, int ld, int rows, int V, int ns, int K, float* table, const uint32_t* ban,
+                                 const uint32_t* seen, int bmw, float penalty, hipStream_t s);
+// per-path token histories [rows][ld]: dst[r][P, P + g) = src[parents[r]][P, P + g), dst[r][P + g] = tokens[r], len[r] = P + g + 1 for
+// rows r < rows (rows = 0: nothing moves); a parent outside row r's own prompt (N rows each) counts as r itself.  The prompt parts [0, P)
+// are not touched.  Also zeroes bm_words words at bm (the ban and seen bitmaps of the step just finished).
+int launch_beam_hist_move(const int32_t* src, int32_t* dst, int rows, int N, int ld, int P, int g, const int* parents, const int* tokens, int* len,
+                          uint32_t* bm, size_t bm_words, hipStream_t s);
 // KV rows between sequences: cache layout [layers][rows_cap][kvh][max_seq][128] (16-bit; e4m3 bytes in the same layout, scales
 // [layers][rows_cap][kvh][max_seq]); the stash holds [layers][st_rows][kvh][st_slots] slots of the same kinds
 struct KvGatherArgs {

@@ -942,6 +942,29 @@ class Engine:
         self._prefix = None      # the fork overwrites sequence 0's row
         self.beam_done = torch.zeros(1, dtype=torch.int32, device=self.device)
 
+    def beam_processors(self, prompt, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, min_length=0,
+                        suppress_tokens=(), begin_suppress_tokens=()):
+        """between beam_begin and the first beam_step: the search ranks processed scores, as HF's _beam_search does -- the repetition
+        penalty on the log-probabilities of the ids of each beam's own history, then HF's token bans (the lists of set_constraints; the
+        EOS ids are the search's own).  prompt: the b equal-length prompt rows as HF's processors see them (-200 sentinels included).
+        A penalty of 1 with nothing to ban leaves the search plain."""
+        torch = _torch()
+        i32 = lambda xs: torch.tensor([int(x) for x in xs] or [0], dtype=torch.int32)
+        words = [list(w) for w in (bad_words_ids or [])]
+        off = [0]
+        for w in words:
+            off.append(off[-1] + len(w))
+        sup, bsup = list(suppress_tokens or ()), list(begin_suppress_tokens or ())
+        rows = [list(r) for r in prompt]
+        bm = vars(self).get("_beam")      # (None: no beam_begin yet -- the context refuses the call)
+        if not rows or len({len(r) for r in rows}) != 1 or not rows[0] or (bm is not None and len(rows) != bm[0]):
+            raise ValueError("beam_processors: one prompt row per prompt of the search, all of one length >= 1")
+        t_sup, t_bsup, t_bw, t_off = i32(sup), i32(bsup), i32([i for w in words for i in w]), i32(off)
+        t_ids = i32([i for r in rows for i in r])
+        check(self.lib.omchat_beam_processors(self.h, float(repetition_penalty), int(no_repeat_ngram_size or 0), int(min_new_tokens or 0),
+                                              int(min_length or 0), ptr(t_sup), len(sup), ptr(t_bsup), len(bsup), ptr(t_bw), ptr(t_off), len(words),
+                                              ptr(t_ids), len(rows[0]), cur_stream()))
+
     def beam_step(self, logits):
         """one beam step on rank-local logits [rows, V / tp] (the prefill's b rows first, then the b * num_beams beam rows) -> the next
         tokens of the b * num_beams rows (int32, device); self.beam_done turns 1 once every prompt is done"""

@@ -511,7 +511,16 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         last bits from a fresh prefill's, and ids at near-ties only.  Default False: nothing is kept.
         no_repeat_ngram_size, bad_words_ids, min_new_tokens, min_length, suppress_tokens, begin_suppress_tokens (also read from
         generation_config): HF's processors of the same names as a ban stage on the device in front of the pick,
-        greedy or sampled; refused with num_beams > 1 and with prompt_lookup_num_tokens.
+        greedy or sampled; refused with num_beams > 1 (unless beam_processors=True) and with prompt_lookup_num_tokens.
+        beam_processors=True with num_beams > 1 (also read from generation_config; ignored with num_beams == 1): the
+        beam search ranks processed scores as HF's _beam_search does -- per beam row log_softmax, then repetition_penalty (any value > 0)
+        on the log-probabilities of the ids of the row's own history (prompt row + the ids along that beam's path), then the six token
+        bans above, then + the running score.  The histories follow the beams on the device.  Without the keyword these arguments are
+        refused under num_beams > 1, as before; with it and nothing set the call is the plain beam search, bit for bit.  Refused from host
+        data, before any work: tensor parallelism (NotImplementedError); a penalty <= 0; lists and lengths that could leave a beam row
+        fewer than max(2, 1 + n_eos) * num_beams finite scores -- vocabulary - (suppress_tokens + begin_suppress_tokens + bad words + EOS
+        ids + prompt tokens + max_new_tokens) below that number (ValueError); and what the plain beam search refuses (do_sample, streamer,
+        stopping_criteria, token_fsm, guidance_scale, dola_layers, padded or ragged rows).
         output_logprobs=True with return_dict_in_generate=True (also read from generation_config): returns a
         GenerateOutput whose .sequences is what the call returns otherwise, .logprobs [b, new] the log-probability of every generated id
         under the model's raw distribution and .processed_logprobs [b, new] under the distribution the pick was made from (bans, repetition
@@ -676,7 +685,9 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         from ..constraints import resolve_constraints
         eos_ids = eos_token_id if eos_token_id is not None else gc.eos_token_id
         eos_ids = list(eos_ids) if isinstance(eos_ids, (list, tuple)) else ([eos_ids] if eos_ids is not None else [])
-        con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None)
+        bp = kwargs.pop("beam_processors", None)      # (ignored with num_beams == 1: the greedy and sampled paths have both stages already)
+        bp = bool(bp if bp is not None else getattr(gc, "beam_processors", False)) and nb > 1
+        con = resolve_constraints(gc, kwargs, eos_ids, self.engine.c.t_vocab_total, nb, lookup is not None, beam_processors=bp)
         if cs is not None and con is not None:
             _cs.refuse(banning=True)
         # the token automaton (omchat_amd/fsm.py): one start state per row of the expanded batch, refused here too
@@ -688,7 +699,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         smp = self._sampling_params(temperature, top_k, top_p, repetition_penalty, seed, generator, kwargs) if do_sample and nb == 1 else None
         for name in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"):      # do_sample=False (or beam search): ignored, as HF ignores them
             kwargs.pop(name, None)
-        if con is None:                                               # sticky context state, like the sampler: off unless this call sets it
+        if con is None or bp:                                         # sticky context state, like the sampler: off unless this call sets it
             self.engine.constraints_off()                             # (set below, after the prefill; equal parameters keep the decode graphs)
         if not olp and getattr(self.engine, "_logprobs_on", False):   # sticky too: a call without the keyword records nothing
             self.engine.logprobs_off()
@@ -707,7 +718,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         if nb > 1:
             return self._beam_generate(input_ids, images, attention_mask, nb, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
                                        stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences,
-                                       return_dict_in_generate)
+                                       return_dict_in_generate, bp, con)
         if max_new_tokens is None:
             max_new_tokens = self.generation_config.max_new_tokens or 20
         eos = eos_token_id if eos_token_id is not None else self.generation_config.eos_token_id
@@ -1111,10 +1122,12 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         return [int(x) for x in lens]
 
     def _beam_generate(self, input_ids, images, attention_mask, N, do_sample, max_new_tokens, streamer, eos_token_id, pad_token_id,
-                       stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences, return_dict_in_generate):
+                       stopping_criteria, repetition_penalty, length_penalty, early_stopping, num_return_sequences, return_dict_in_generate,
+                       beam_processors=False, con=None):
         """HF's _beam_search on the device (include/omchat_hip.h: omchat_beam_begin) with the one-step-ahead loop of
-        the greedy path: each prompt is prefilled once and its cache row forked into its N beam rows.  Every refusal is raised before any
-        work is enqueued."""
+        the greedy path: each prompt is prefilled once and its cache row forked into its N beam rows.  beam_processors: the repetition
+        penalty and the token bans `con` (resolve_constraints) act on the beam rows' log-probabilities (omchat_beam_processors).  Every
+        refusal is raised before any work is enqueued."""
         gc = self.generation_config
         pick = lambda v, name, d: v if v is not None else (getattr(gc, name, None) if getattr(gc, name, None) is not None else d)
         lp = float(pick(length_penalty, "length_penalty", 1.0))
@@ -1127,7 +1140,7 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
             raise ValueError("`streamer` cannot be used with beam search (yet!). Make sure that `num_beams` is set to 1.")
         if stopping_criteria:
             raise NotImplementedError("custom stopping_criteria are not implemented under beam search")
-        if float(rp) != 1.0:
+        if not beam_processors and float(rp) != 1.0:
             raise NotImplementedError("repetition_penalty is not implemented under beam search")
         if es not in (True, False, "never"):
             raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es}.")
@@ -1150,6 +1163,10 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         eos = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else ([eos] if eos is not None else []))]
         pad = pad_token_id if pad_token_id is not None else gc.pad_token_id
         fill = (pad or eos[0]) if eos else -1                   # HF: `pad_token_id or eos_token_id[0] if eos_token_id is not None else -1`
+        bpk = None
+        if beam_processors:
+            from ..constraints import resolve_beam_processors
+            bpk = resolve_beam_processors(con, rp, N, eos, self.engine.c.t_vocab_total, input_ids.shape[1], max_new_tokens, self.engine.tp_size)
         out = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, use_cache=True)
         lens = self.engine.kv_lengths(b)
         if getattr(self, "_padded_batch", False) or len(set(lens)) > 1:
@@ -1164,6 +1181,8 @@ class OmChatQwen2ForCausalLM(OmChatMetaForCausalLM):
         e = self.engine
         e.sampling_off()
         e.beam_begin(b, N, lp, es, eos, max_new_tokens, P)
+        if bpk is not None:
+            e.beam_processors(ids_cpu.tolist(), **bpk)
         tok = e.beam_step(out.local_logits)
         stage = self._stage_buffer(1, 1)
         evt = self._stage_event
